@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the VETO pairwise relation-prediction hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment launches the N ranks itself
@@ -14,6 +14,10 @@ BASELINE.json configs[1] -- 12 images x 36 objects = 15120 ordered pairs, d=576 
 4 layers, 51 predicates.  Weak scaling: every rank processes its own 12-image batch; for N > 1 each
 step ends with the RCCL all-gather of the [P, 51] logits (eval aggregation).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR: obj_dists.npy and
+rel_dists.npy, float32) and prints the headline line.  --full adds what takes runs of its own: the per-kernel hipEvent profile
+with the roofline / gather / GEMM objects, the CPU baseline (N = 1) and the `extra` lines (N = 1).
 """
 import argparse
 import json
@@ -123,8 +127,11 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=sorted(DTYPE_OF))
     ap.add_argument("--chunk", type=int, default=0, help="VETO_AMD.MAX_CHUNK_PAIRS (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra L6/H6 and other-precision lines (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel profile and roofline objects, the CPU baseline and the extra lines (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra L6/H6 and other-precision lines (N = 1 only)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     args = ap.parse_args()
 
@@ -159,7 +166,7 @@ def main():
         fake = torch.full((n_pairs, 51), float(rank))
 
         def step():
-            return vdist.all_gather_logits(fake, equal_counts=True, force=force_dist) if dist is not None else fake
+            return None, (vdist.all_gather_logits(fake, equal_counts=True, force=force_dist) if dist is not None else fake)
 
         def fence():
             if dist is not None:
@@ -183,7 +190,7 @@ def main():
             logits = torch.cat(list(out[1]), 0) if dist is not None else out[1]
             if dist is not None:
                 logits = vdist.all_gather_logits(logits, equal_counts=True, force=force_dist)
-            return logits
+            return out[0], logits
 
         def fence():
             if dist is not None:
@@ -195,7 +202,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        last = step()
+        last_obj, last = step()
     fence()
     elapsed = time.perf_counter() - t0
     ranks_seen, devices = 1, [0 if dry else torch.cuda.current_device()]
@@ -215,6 +222,9 @@ def main():
         gathered_rows = int(last.shape[0])
         assert gathered_rows == n_pairs * ranks_seen, (gathered_rows, n_pairs, ranks_seen)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"obj_dists": last_obj, "rel_dists": last})
+
     if dry:
         if rank == 0:
             print(json.dumps({"metric": "DRY RUN of the launch path (gloo, CPU, no model): not a measurement", "value": 0.0,
@@ -227,50 +237,24 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- per-kernel device time (hipEvents on the launch stream, inside the library) -------------
-    eng = model._engine
-    eng.profile_reset()
-    eng.profile_enable(True)
-    prof_steps = min(5, args.steps)
-    for _ in range(prof_steps):
-        with torch.no_grad():
-            model(props, pairs, None, None, roi_features=rgb, roi_depth_features=dep)
-    torch.cuda.synchronize(dev)
-    prof = eng.profile()
-    eng.profile_enable(False)
+    prof = prof_steps = None
+    if args.full:
+        # ---- per-kernel device time (hipEvents on the launch stream, inside the library) -------------
+        eng = model._engine
+        eng.profile_reset()
+        eng.profile_enable(True)
+        prof_steps = min(5, args.steps)
+        for _ in range(prof_steps):
+            with torch.no_grad():
+                model(props, pairs, None, None, roi_features=rgb, roi_depth_features=dep)
+        torch.cuda.synchronize(dev)
+        prof = eng.profile()
+        eng.profile_enable(False)
 
     if rank == 0:
         total_pairs = n_pairs * world
         ms_per_step = elapsed / args.steps * 1e3
         value = total_pairs * args.steps / elapsed
-        kern = {k: dict(ms_per_step=v["total_ms"] / prof_steps, launches_per_step=v["launches"] // prof_steps,
-                        avg_ms=v["total_ms"] / v["launches"],
-                        tflops=(v["flops_per_launch"] / (v["total_ms"] / v["launches"] * 1e-3) / 1e12)
-                        if v["flops_per_launch"] else None)
-                for k, v in prof.items()}
-        gemms = {k: v for k, v in kern.items() if k.startswith("gemm_") or k in ("ffn_fused", "out_ln_fused", "layer_tail_fused")}
-        # the dominant kernel = the matrix launch with the longest duration (round 3: the layer-tail launch -- out projection +
-        # residual + LayerNorm2 + FeedForward + residual + next LayerNorm1 of a full layer, 953 GF; before that the QKV projection);
-        # `gemm_all` below is the rate over all matrix launches
-        dom = max(gemms, key=lambda k: gemms[k]["avg_ms"])
-        achieved = gemms[dom]["tflops"]
-        gemm_ms = sum(v["ms_per_step"] for v in gemms.values())
-        gemm_flops = sum(prof[k]["flops_per_launch"] * kern[k]["launches_per_step"] for k in gemms)
-        # FLOPs the step actually executes (algorithmic 2*M*N*K of every launch, attention contractions included)
-        exec_flops = sum(prof[k]["flops_per_launch"] * kern[k]["launches_per_step"] for k in kern if prof[k]["flops_per_launch"])
-        f_ref = flops_per_pair(args.layers, args.heads)
-        passes = MFMA_PASSES[args.precision]
-        hbm_gbps = {k: round(prof[k]["bytes_per_launch"] / (kern[k]["avg_ms"] * 1e-3) / 1e9, 1)
-                    for k in ("attention", "attention_cls", "layernorm") if k in prof and prof[k]["bytes_per_launch"]}
-        gather_bytes = prof["assemble_tokens"]["bytes_per_launch"]      # bytes the kernel writes, as the library accounts them
-        gather_gbps = gather_bytes / (kern["assemble_tokens"]["avg_ms"] * 1e-3) / 1e9
-        # PMC-derived numbers for THIS workload (HBM bytes per launch, MFMA-busy fractions): counters cannot be collected inside a timed
-        # run, so they come from the committed rocprofv3 --pmc passes of the profile tag named in `traffic_source` (tools/pmc_traffic.py)
-        tj = load_traffic("traffic.json", [args.images, args.objs, args.layers, args.heads, args.precision])
-        traffic = tj["kernels"].get(dom, {}).get("hbm_bytes_per_launch") if tj else None
-        attention_pmc = tj.get("attention") if tj else None
-        tj_kernels = tj["kernels"] if tj else None
-        traffic_source = "profiles/%s_pmc_*.txt (rocprofv3 --pmc passes of profile tag %s)" % (tj["tag"], tj["tag"]) if tj else None
         res = {
             "metric": "relation-pairs/sec (PredCls, 36 obj/img)", "value": value, "unit": "pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -283,53 +267,14 @@ def main():
                        "parallelism": "image-sharded x%d, RCCL all-gather of logits" % world if world > 1 else "single GPU"},
             "ranks_seen": ranks_seen, "devices": devices,
             "per_rank_pairs_per_s": [round(n_pairs * args.steps / e, 1) for e in rank_elapsed],
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
-                         "note": "achieved = algorithmic 2*M*N*K of one launch / its mean hipEvent duration; this precision mode "
-                                 "issues %.4g bf16-equivalent MFMA passes per algorithmic FLOP" % passes},
-            # the four floors of the dominant launch (rates measured on MI355X in round 4): it runs above all of
-            # them because an in-order wave overlaps its matrix, LDS-DMA, L2-miss and HBM streams only partly
-            "floors": layer_tail_floors(n_pairs * 19, prof[dom], traffic, gemms[dom]["avg_ms"]) if dom == "layer_tail_fused" else None,
-            # north_star: "HBM GB/s on the gather and MFMA utilisation on the attention GEMMs"
-            "gather": {"bound": "hbm", "kernel": "assemble_tokens", "achieved": gather_gbps, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                       "frac": gather_gbps / PEAK_HBM_GBS,
-                       "bytes": gather_bytes,
-                       "gathered_bytes": float(n_pairs) * 18 * 2 * 576 * 4,
-                       "moved_gbps": (gather_bytes + float(n_pairs) * 18 * 2 * 576 * 4) / (kern["assemble_tokens"]["avg_ms"] * 1e-3) / 1e9,
-                       "note": "pair gather + token assembly: bytes = what the kernel writes (the [pairs, 19, 576] fp32 token rows plus, "
-                               "with layer 0 in the per-object form, the row statistics and the split rows of two of the 19 tokens); "
-                               "the per-object rows it gathers (gathered_bytes; moved_gbps counts them too) come from L2 / Infinity Cache"},
-            "attention": attention_pmc,
-            # the fused QKV projection + attention launch of the middle layers (round 5): algorithmic FLOPs of the projection and of the
-            # attention contractions / its mean hipEvent duration, counted HBM bytes per launch from the same PMC passes
-            "qkv_attn": ({"kernel": "qkv_attn_fused", "ms_per_launch": round(kern["qkv_attn_fused"]["avg_ms"], 4),
-                          "achieved": kern["qkv_attn_fused"]["tflops"], "unit": "TFLOP/s", "peak": PEAK_BF16_TFLOPS,
-                          "frac": kern["qkv_attn_fused"]["tflops"] / PEAK_BF16_TFLOPS,
-                          "traffic": (tj_kernels or {}).get("qkv_attn_fused", {}).get("hbm_bytes_per_launch"),
-                          "algorithmic_bytes": prof["qkv_attn_fused"]["bytes_per_launch"],
-                          "mfma_busy": (tj_kernels or {}).get("qkv_attn_fused", {}).get("mfma_busy")}
-                         if "qkv_attn_fused" in kern else None),
-            "gemm_all": {"kernel": "all GEMM launches of a step", "ms_per_step": round(gemm_ms, 4),
-                         "achieved": gemm_flops / (gemm_ms * 1e-3) / 1e12, "unit": "TFLOP/s",
-                         "frac": gemm_flops / (gemm_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS},
-            "hbm_kernels_gbps": hbm_gbps,
-            "mfma_issued": {"kernel": dom, "passes_per_flop": passes, "issued_tflops": achieved * passes,
-                            "frac_of_bf16_peak": achieved * passes / PEAK_BF16_TFLOPS,
-                            "note": "matrix-pipe work actually issued by the dominant GEMM, in bf16-rate units (an e4m3 K=128 MFMA "
-                                    "counts half of its FLOPs: it runs at twice the bf16 rate)"},
-            "whole_path": {"executed_flops_per_pair": exec_flops / n_pairs, "tflops_executed": value * exec_flops / n_pairs / 1e12,
-                           "frac_of_bf16_peak": value * exec_flops / n_pairs / 1e12 / PEAK_BF16_TFLOPS / world,
-                           "ref_flops_per_pair": f_ref, "tflops_ref_equivalent": value * f_ref / 1e12,
-                           "note": "frac uses the FLOPs the restructured path executes (SURVEY.md 8d); the reference-equivalent "
-                                   "figure (what the unrestructured formulation would need for the same pairs) is the labelled extra"},
-            "kernels_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])},
-            "gemm_tflops": {k: round(v["tflops"], 1) for k, v in gemms.items()},
         }
-        if world == 1 and not args.no_cpu_baseline:
-            gl = list(last.split([int(p.shape[0]) for p in pairs])) if torch.is_tensor(last) else last
-            res["cpu_baseline"], res["logit_max_abs_err"] = cpu_baseline(sd, args, batch, gl, pairs)
-        if world == 1 and not args.no_extra:
-            res["extra"] = extra_lines(args, dev, batch, sd)
+        if args.full:
+            res.update(kernel_lines(args, prof, prof_steps, n_pairs, value, world))
+            if world == 1 and not args.no_cpu_baseline:
+                gl = list(last.split([int(p.shape[0]) for p in pairs])) if torch.is_tensor(last) else last
+                res["cpu_baseline"], res["logit_max_abs_err"] = cpu_baseline(sd, args, batch, gl, pairs)
+            if world == 1 and not args.no_extra:
+                res["extra"] = extra_lines(args, dev, batch, sd)
         # RCCL writes its version banner through C stdio, which (when stdout is a file or pipe) only
         # drains at exit, i.e. AFTER a Python print: drain it first so that the JSON is the last line.
         import ctypes
@@ -339,6 +284,96 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, arrays, limit=64 * 2 ** 20):
+    """Writes each array (a tensor or a list of per-image tensors; None is skipped) as d/<name>.npy in float32.  Above `limit` bytes in
+    all, each keeps a fixed seeded sample of its rows (the same rows for the same shapes, so two builds compare output for output)."""
+    import numpy as np
+    arrays = {k: (v if torch.is_tensor(v) else torch.cat(list(v), 0)).float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, a.shape[0] * limit // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def kernel_lines(args, prof, prof_steps, n_pairs, value, world):
+    """The objects of the --full line that come from the per-kernel hipEvent profile (`prof`, over `prof_steps` forward steps) and the
+    committed PMC passes: roofline of the dominant launch, its floors, gather, attention, GEMM and whole-path rates."""
+    kern = {k: dict(ms_per_step=v["total_ms"] / prof_steps, launches_per_step=v["launches"] // prof_steps,
+                    avg_ms=v["total_ms"] / v["launches"],
+                    tflops=(v["flops_per_launch"] / (v["total_ms"] / v["launches"] * 1e-3) / 1e12)
+                    if v["flops_per_launch"] else None)
+            for k, v in prof.items()}
+    gemms = {k: v for k, v in kern.items() if k.startswith("gemm_") or k in ("ffn_fused", "out_ln_fused", "layer_tail_fused")}
+    # the dominant kernel = the matrix launch with the longest duration (round 3: the layer-tail launch -- out projection +
+    # residual + LayerNorm2 + FeedForward + residual + next LayerNorm1 of a full layer, 953 GF; before that the QKV projection);
+    # `gemm_all` below is the rate over all matrix launches
+    dom = max(gemms, key=lambda k: gemms[k]["avg_ms"])
+    achieved = gemms[dom]["tflops"]
+    gemm_ms = sum(v["ms_per_step"] for v in gemms.values())
+    gemm_flops = sum(prof[k]["flops_per_launch"] * kern[k]["launches_per_step"] for k in gemms)
+    # FLOPs the step actually executes (algorithmic 2*M*N*K of every launch, attention contractions included)
+    exec_flops = sum(prof[k]["flops_per_launch"] * kern[k]["launches_per_step"] for k in kern if prof[k]["flops_per_launch"])
+    f_ref = flops_per_pair(args.layers, args.heads)
+    passes = MFMA_PASSES[args.precision]
+    hbm_gbps = {k: round(prof[k]["bytes_per_launch"] / (kern[k]["avg_ms"] * 1e-3) / 1e9, 1)
+                for k in ("attention", "attention_cls", "layernorm") if k in prof and prof[k]["bytes_per_launch"]}
+    gather_bytes = prof["assemble_tokens"]["bytes_per_launch"]      # bytes the kernel writes, as the library accounts them
+    gather_gbps = gather_bytes / (kern["assemble_tokens"]["avg_ms"] * 1e-3) / 1e9
+    # PMC-derived numbers for THIS workload (HBM bytes per launch, MFMA-busy fractions): counters cannot be collected inside a timed
+    # run, so they come from the committed rocprofv3 --pmc passes of the profile tag named in `traffic_source` (tools/pmc_traffic.py)
+    tj = load_traffic("traffic.json", [args.images, args.objs, args.layers, args.heads, args.precision])
+    traffic = tj["kernels"].get(dom, {}).get("hbm_bytes_per_launch") if tj else None
+    attention_pmc = tj.get("attention") if tj else None
+    tj_kernels = tj["kernels"] if tj else None
+    traffic_source = "profiles/%s_pmc_*.txt (rocprofv3 --pmc passes of profile tag %s)" % (tj["tag"], tj["tag"]) if tj else None
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
+                     "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
+                     "note": "achieved = algorithmic 2*M*N*K of one launch / its mean hipEvent duration; this precision mode "
+                             "issues %.4g bf16-equivalent MFMA passes per algorithmic FLOP" % passes},
+        # the four floors of the dominant launch (DESIGN.md section 7.1; rates measured on MI355X in round 4): it runs above all of
+        # them because an in-order wave overlaps its matrix, LDS-DMA, L2-miss and HBM streams only partly
+        "floors": layer_tail_floors(n_pairs * 19, prof[dom], traffic, gemms[dom]["avg_ms"]) if dom == "layer_tail_fused" else None,
+        # north_star: "HBM GB/s on the gather and MFMA utilisation on the attention GEMMs"
+        "gather": {"bound": "hbm", "kernel": "assemble_tokens", "achieved": gather_gbps, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                   "frac": gather_gbps / PEAK_HBM_GBS,
+                   "bytes": gather_bytes,
+                   "gathered_bytes": float(n_pairs) * 18 * 2 * 576 * 4,
+                   "moved_gbps": (gather_bytes + float(n_pairs) * 18 * 2 * 576 * 4) / (kern["assemble_tokens"]["avg_ms"] * 1e-3) / 1e9,
+                   "note": "pair gather + token assembly: bytes = what the kernel writes (the [pairs, 19, 576] fp32 token rows plus, "
+                           "with layer 0 in the per-object form, the row statistics and the split rows of two of the 19 tokens); "
+                           "the per-object rows it gathers (gathered_bytes; moved_gbps counts them too) come from L2 / Infinity Cache"},
+        "attention": attention_pmc,
+        # the fused QKV projection + attention launch of the middle layers (round 5): algorithmic FLOPs of the projection and of the
+        # attention contractions / its mean hipEvent duration, counted HBM bytes per launch from the same PMC passes
+        "qkv_attn": ({"kernel": "qkv_attn_fused", "ms_per_launch": round(kern["qkv_attn_fused"]["avg_ms"], 4),
+                      "achieved": kern["qkv_attn_fused"]["tflops"], "unit": "TFLOP/s", "peak": PEAK_BF16_TFLOPS,
+                      "frac": kern["qkv_attn_fused"]["tflops"] / PEAK_BF16_TFLOPS,
+                      "traffic": (tj_kernels or {}).get("qkv_attn_fused", {}).get("hbm_bytes_per_launch"),
+                      "algorithmic_bytes": prof["qkv_attn_fused"]["bytes_per_launch"],
+                      "mfma_busy": (tj_kernels or {}).get("qkv_attn_fused", {}).get("mfma_busy")}
+                     if "qkv_attn_fused" in kern else None),
+        "gemm_all": {"kernel": "all GEMM launches of a step", "ms_per_step": round(gemm_ms, 4),
+                     "achieved": gemm_flops / (gemm_ms * 1e-3) / 1e12, "unit": "TFLOP/s",
+                     "frac": gemm_flops / (gemm_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS},
+        "hbm_kernels_gbps": hbm_gbps,
+        "mfma_issued": {"kernel": dom, "passes_per_flop": passes, "issued_tflops": achieved * passes,
+                        "frac_of_bf16_peak": achieved * passes / PEAK_BF16_TFLOPS,
+                        "note": "matrix-pipe work actually issued by the dominant GEMM, in bf16-rate units (an e4m3 K=128 MFMA "
+                                "counts half of its FLOPs: it runs at twice the bf16 rate)"},
+        "whole_path": {"executed_flops_per_pair": exec_flops / n_pairs, "tflops_executed": value * exec_flops / n_pairs / 1e12,
+                       "frac_of_bf16_peak": value * exec_flops / n_pairs / 1e12 / PEAK_BF16_TFLOPS / world,
+                       "ref_flops_per_pair": f_ref, "tflops_ref_equivalent": value * f_ref / 1e12,
+                       "note": "frac uses the FLOPs the restructured path executes (SURVEY.md 8d); the reference-equivalent "
+                               "figure (what the unrestructured formulation would need for the same pairs) is the labelled extra"},
+        "kernels_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])},
+        "gemm_tflops": {k: round(v["tflops"], 1) for k, v in gemms.items()},
+    }
 
 
 def extra_lines(args, dev, batch, sd):

@@ -234,3 +234,27 @@ def test_bench_reports_the_floors_of_the_layer_tail():
     assert abs(f["matrix_ms"] - 0.662) < 0.01 and abs(f["l2_to_lds_ms"] - 0.838) < 0.01 and abs(f["l2_miss_ms"] - 0.945) < 0.01
     assert 0.5 < f["hbm_ms"] < 0.6 and abs(f["frac_of_tightest_floor"] - 0.945 / 2.25) < 0.01
     assert bench.layer_tail_floors(rows, {"flops_per_launch": flops, "bytes_per_launch": 1.0}, None, 2.25)["l2_miss_ms"] is None
+
+
+def test_bench_dump_outputs_writes_float32_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output (a list of per-image tensors is concatenated); above the size limit every
+    array keeps the same seeded sample of its rows on every run, so two builds can be compared output for output."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rel = torch.arange(600 * 51, dtype=torch.float64).reshape(600, 51)
+    obj = [torch.eye(151)[:5], torch.eye(151)[5:12]]
+    bench.dump_outputs(str(tmp_path / "all"), {"obj_dists": obj, "rel_dists": rel, "absent": None})
+    assert sorted(os.listdir(tmp_path / "all")) == ["obj_dists.npy", "rel_dists.npy"]
+    r = np.load(tmp_path / "all" / "rel_dists.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, rel.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "obj_dists.npy"), torch.cat(obj).numpy())
+    limit = 40000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"obj_dists": obj, "rel_dists": rel}, limit=limit)
+    a, b = (np.load(tmp_path / d / "rel_dists.npy") for d in ("a", "b"))
+    assert np.array_equal(a, b) and 0 < a.shape[0] < 600
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= limit + 2 * 128   # + two .npy headers
+    assert np.all(np.diff(a[:, 0]) > 0) and np.all(a[:, 0] % 51 == 0)     # whole rows, in their original order
