@@ -11,6 +11,9 @@
  *   veto_forward           <- VETOPredictor.forward (eval)      roi_relation_predictors.py:4074-4139
  *                             Ensemble.forward (MEET, eval)     roi_relation_predictors.py:3752-3853
  *   veto_enumerate_pairs   <- RelationSampling.prepare_test_pairs   sampling.py:31-52 (GT-box branch)
+ *   veto_prepare_test_pairs <- the same, sgdet branch (box-overlap filter, capped pair order)   sampling.py:31-52
+ *   veto_obj_decode        <- obj_prediction_nms (PostProcessor)    utils_relation.py:94-128, inference.py:410-429
+ *                             Ensemble.nms_per_cls (MEET decoder)   roi_relation_predictors.py:3855-3874
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -177,7 +180,8 @@ typedef struct veto_post_args {
   int32_t max_pairs_per_image;    /* host-side maximum of the per-image pair counts; must be <= 4096 */
   int32_t reserved0;
   const float* rel_logits;        /* device [n_pair, n_rel_cls] */
-  const float* obj_logits;        /* device [n_obj, n_obj_cls]  (refine logits / predict_logits) */
+  const float* obj_logits;        /* device [n_obj, n_obj_cls]  (refine logits / predict_logits); NULL (sgdet): obj_scores and
+                                     obj_pred are INPUTS, filled by veto_obj_decode */
   const int64_t* rel_pairs;       /* device [n_pair, 2] image-local */
   const int32_t* img_obj_offset;  /* device [n_img + 1] */
   const int32_t* img_pair_offset; /* device [n_img + 1] */
@@ -204,7 +208,7 @@ typedef struct veto_post_meet_args {
   const float* const* group_logits;   /* HOST array of n_groups device pointers [n_pair, group_widths[k]] */
   const int32_t* group_widths;        /* HOST array [n_groups]: g_k + 2 */
   const int32_t* incre_idx_list;      /* HOST array [n_rel_cls]: 1-based group of each class, 0 = background */
-  const float* obj_logits;            /* device [n_obj, n_obj_cls] */
+  const float* obj_logits;            /* device [n_obj, n_obj_cls]; NULL (sgdet): obj_scores / obj_pred are inputs */
   const int64_t* rel_pairs;           /* device [n_pair, 2] */
   float* obj_scores;                  /* out device [n_obj] */
   int64_t* obj_pred;                  /* out device [n_obj] */
@@ -231,7 +235,7 @@ typedef struct veto_post_vote_args {
   const float* const* expert_logits;  /* HOST array of 3*n_groups device pointers, [3*k + e] = 'group_<k><e+1>' */
   const int32_t* group_widths;        /* HOST array [n_groups]: g_k + 2 */
   const int32_t* incre_idx_list;      /* HOST array [n_rel_cls] */
-  const float* obj_logits;            /* device [n_obj, n_obj_cls] */
+  const float* obj_logits;            /* device [n_obj, n_obj_cls]; NULL (sgdet): obj_scores / obj_pred are inputs */
   const int64_t* rel_pairs;           /* device [n_pair, 2] */
   float* obj_scores;                  /* out device [n_obj] */
   int64_t* obj_pred;                  /* out device [n_obj] */
@@ -244,6 +248,56 @@ typedef struct veto_post_vote_args {
 
 /* workspace: veto_postprocess_workspace_bytes(n_groups * n_pair, n_rel_cls) */
 int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* ---- sgdet: the relation head on the detector's own boxes (USE_GT_BOX False) ------------------------
+ * veto_obj_decode: greedy class-aware NMS over softmax(logits), for a ragged batch (one workgroup per image).
+ *   mode 0 = obj_prediction_nms (utils_relation.py:94-128) as the PostProcessor uses it (inference.py:410-429, the
+ *            MEET branch :317-341 and the voting branch :123-147): prob[:, 0] = 0, a row keeps its first label;
+ *   mode 1 = Ensemble.nms_per_cls (roi_relation_predictors.py:3855-3874), the MEET decoder's labels (:3776-3784):
+ *            prob[:, 0] = -1, a re-picked row takes the new label.  Input: the labels of the one-hot; every row is
+ *            built from the same two probabilities, so ties between rows are exact and go to the lower row.
+ *   N times: (b, c) = first row-major arg-max; label; prob[j, c] = 0 where IoU(boxes_per_cls[b, c], boxes_per_cls[j, c])
+ *   >= nms_thres (nms_overlaps, :56-92, TO_REMOVE 1); prob[b, :] = -1.
+ *   obj_scores[i] = softmax(logits)[i, label_i] with the background column zeroed; boxes[i] = boxes_per_cls[i, label_i]. */
+typedef struct veto_obj_decode_args {
+  int32_t struct_size;
+  int32_t n_img, n_obj, n_cls;        /* n_cls 151 (VG) / 201 (GQA); 2..1024 */
+  int32_t max_obj_per_image;          /* host-side maximum of the per-image counts, 1..256 (DETECTIONS_PER_IMG) */
+  int32_t mode;                       /* 0 = PostProcessor, 1 = MEET decoder */
+  float nms_thres;                    /* TEST.RELATION.LATER_NMS_PREDICTION_THRES */
+  int32_t reserved0;
+  const float* logits;                /* device [n_obj, n_cls] ('predict_logits'); mode 0, and whenever obj_scores is wanted */
+  const int64_t* labels;              /* device [n_obj] ('pred_labels'); mode 1 */
+  const float* boxes_per_cls;         /* device [n_obj, n_cls, 4] xyxy ('boxes_per_cls') */
+  const int32_t* img_obj_offset;      /* device [n_img + 1] */
+  int64_t* obj_pred;                  /* out device [n_obj] */
+  float* obj_scores;                  /* optional out device [n_obj] */
+  float* boxes;                       /* optional out device [n_obj, 4]: the regressed boxes */
+} veto_obj_decode_args_t;
+
+size_t veto_obj_decode_workspace_bytes(int32_t n_obj, int32_t n_cls);
+int veto_obj_decode(void* stream, const veto_obj_decode_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_prepare_test_pairs: RelationSampling.prepare_test_pairs (sampling.py:31-52) with detected boxes, per image:
+ * every ordered pair i != j, AND boxlist_iou > 0 (boxlist_ops.py:54-89) when require_overlap (REQUIRE_BOX_OVERLAP), in
+ * row-major order; above max_pairs the max_pairs best by scores[i] * scores[j], emitted in the total order
+ * (quality desc, row-major index asc) = torch.sort(stable=True, descending=True); [[0, 0]] when no pair is left.
+ * Image i writes rows img_out_offset[i] .. + counts[i]; its capacity must be min(max(n(n-1), 1), max_pairs). */
+typedef struct veto_pair_args {
+  int32_t struct_size;
+  int32_t n_img, n_obj;
+  int32_t max_obj_per_image;          /* 0..256 */
+  int32_t max_pairs;                  /* MAX_PROPOSAL_PAIR, 1..4096 */
+  int32_t require_overlap;
+  const float* boxes;                 /* device [n_obj, 4] xyxy (the proposals' bbox) */
+  const float* scores;                /* device [n_obj] ('pred_scores') */
+  const int32_t* img_obj_offset;      /* device [n_img + 1] */
+  const int32_t* img_out_offset;      /* device [n_img + 1] */
+  int64_t* pairs;                     /* out device [img_out_offset[n_img], 2] */
+  int32_t* counts;                    /* out device [n_img]: pairs written per image */
+} veto_pair_args_t;
+
+int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* args);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False
@@ -284,7 +338,7 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const
 
 /* ---- relation evaluators -----------------------------------------------
  * evaluate_relation_of_one_image (pysgg/data/datasets/evaluation/vg/vg_eval.py:459-566) over the evaluator
- * classes of sgg_eval.py for the GT-box modes: SGRecall (:121-187), SGNoGraphConstraintRecall (:195-255),
+ * classes of sgg_eval.py for the GT-box modes and sgdet (see reserved0 / pred_obj_offset): SGRecall (:121-187), SGNoGraphConstraintRecall (:195-255),
  * SGZeroShotRecall (:263-313), SGPairAccuracy (:322-369), SGMeanRecall (:377-466), SGNGMeanRecall (:470-546),
  * and their accumulation over the data set, K = 20 / 50 / 100.  Images are concatenated; the *_off arrays
  * are exclusive prefix sums.  For predcls pass the GT classes / boxes as the predicted ones and obj_scores = 1
@@ -295,7 +349,8 @@ typedef struct veto_sgg_eval_args {
   int32_t n_rel_cls;               /* 51 */
   int32_t n_zeroshot;
   float iou_thres;                 /* TEST.RELATION.IOU_THRESHOLD (0.5) */
-  int32_t reserved0;
+  int32_t reserved0;               /* mode: 0 = GT boxes (predcls / sgcls), 1 = sgdet (SGPairAccuracy records nothing,
+                                      sgg_eval.py:356: acc_rank is all 0x3fffffff and A@K is to be read as NaN) */
   const int32_t* gt_offset;        /* device [n_img + 1] GT relations */
   const int32_t* obj_offset;       /* device [n_img + 1] objects */
   const int32_t* pair_offset;      /* device [n_img + 1] predicted pairs */
@@ -318,6 +373,10 @@ typedef struct veto_sgg_eval_args {
   double* metrics;                 /* out device [18 + 6 * (n_rel_cls - 1) + 2]: R@20/50/100, ngR, zR, A, mR, ng-mR,
                                       per-class recall lists [2 kinds][3 K][n_rel_cls - 1], images evaluated,
                                       images with a zero-shot relation */
+  const int32_t* pred_obj_offset;  /* device [n_img + 1] predicted objects (pred_classes / pred_boxes / obj_scores); NULL =
+                                      obj_offset.  sgdet: the detector's boxes, whose count differs from the GT count
+                                      (vg_eval.py:491-495).  A caller built against the struct without this field passes
+                                      its shorter struct_size and gets NULL. */
 } veto_sgg_eval_args_t;
 
 size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_t n_gt_total, int32_t n_rel_cls);

@@ -284,7 +284,35 @@ struct VoteGroup {               // one MEET group with its three expert heads, 
 // voting: 0 = consensus ('C', two of three experts agree), 1 = unanimous ('U')
 hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_groups, int voting, hipStream_t s);
 int postprocess_max_pairs_per_image();
-hipError_t launch_postprocess(const PostArgs& a, hipStream_t s);
+hipError_t launch_postprocess(const PostArgs& a, hipStream_t s);   // obj_logits == nullptr: obj_scores / obj_pred are inputs
+
+// ---- sgdet: object decoding and test pairs on detected boxes (sgdet.hip) ----------------------------
+struct ObjDecodeArgs {
+  const float* logits;           // [n_obj, n_cls] (mode 0; and for obj_scores)
+  const int64_t* labels;         // [n_obj] (mode 1: the one-hot's labels)
+  const float* boxes_per_cls;    // [n_obj, n_cls, 4] xyxy
+  const int32_t* img_off;        // [n_img + 1]
+  int n_img, n_cls;
+  int mode;                      // 0: obj_prediction_nms (PostProcessor), 1: Ensemble.nms_per_cls (MEET decoder)
+  float thr;
+  float* prob_ws;                // [n_obj, n_cls]: the probability matrix of images that exceed the LDS tile
+  int64_t* obj_pred;             // out [n_obj]
+  float* obj_scores;             // optional out [n_obj]
+  float* out_boxes;              // optional out [n_obj, 4]
+};
+int obj_decode_max_objects();
+hipError_t launch_obj_decode(const ObjDecodeArgs& a, hipStream_t s);
+struct PairArgs {
+  const float* boxes;            // [n_obj, 4] xyxy
+  const float* scores;           // [n_obj] pred_scores
+  const int32_t* img_off;        // [n_img + 1]
+  const int32_t* out_off;        // [n_img + 1]: image i writes from row out_off[i]
+  int n_img, max_pairs, require_overlap;
+  int64_t* pairs;                // out [out_off[n_img], 2]
+  int32_t* counts;               // out [n_img]
+};
+int prepare_pairs_max_pairs();
+hipError_t launch_prepare_pairs(const PairArgs& a, hipStream_t s);
 
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
@@ -317,6 +345,8 @@ struct SggEvalArgs {
   float iou_thres;
   const int32_t* gt_off;         // [n_img + 1] prefix sum of GT relations
   const int32_t* obj_off;        // [n_img + 1] prefix sum of objects
+  const int32_t* pred_obj_off;   // [n_img + 1] prefix sum of predicted objects, or nullptr = obj_off (GT-box modes)
+  int mode;                      // 0 = GT boxes, 1 = sgdet (no pair-accuracy hits)
   const int32_t* pair_off;       // [n_img + 1] prefix sum of predicted pairs
   const int64_t* gt_rels;        // [sum G, 3] (subject, object, predicate), image-local indices
   const int64_t* gt_classes;     // [sum N]

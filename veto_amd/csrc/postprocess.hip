@@ -257,9 +257,15 @@ __global__ __launch_bounds__(256) void vote_rel_score_kernel(PostArgs a, VoteGro
 
 }  // namespace
 
-hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_groups, int voting, hipStream_t s) {
+// obj_logits == nullptr (sgdet): obj_scores / obj_pred were filled by the object decoding (sgdet.hip) and are inputs here
+static hipError_t launch_obj_scores(const PostArgs& a, hipStream_t s) {
+  if (!a.obj_logits) return hipSuccess;
   VETO_LAUNCH(obj_score_kernel, dim3((a.n_obj + 3) / 4), dim3(256), 0, s, a.obj_logits, a.n_obj, a.n_obj_cls, a.obj_scores, a.obj_pred);
-  hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_groups, int voting, hipStream_t s) {
+  hipError_t e = launch_obj_scores(a, s);
   if (e != hipSuccess) return e;
   for (int k = 0; k < n_groups; ++k) {
     VETO_LAUNCH(vote_rel_score_kernel, dim3((a.n_pair + 3) / 4), dim3(256), 0, s, a, groups[k], voting);
@@ -276,8 +282,7 @@ hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_gr
 }
 
 hipError_t launch_postprocess_meet(PostArgs a, const MeetGroup* groups, int n_groups, hipStream_t s) {
-  VETO_LAUNCH(obj_score_kernel, dim3((a.n_obj + 3) / 4), dim3(256), 0, s, a.obj_logits, a.n_obj, a.n_obj_cls, a.obj_scores, a.obj_pred);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_obj_scores(a, s);
   if (e != hipSuccess) return e;
   for (int k = 0; k < n_groups; ++k) {
     VETO_LAUNCH(meet_rel_score_kernel, dim3((a.n_pair + 3) / 4), dim3(256), 0, s, a, groups[k]);
@@ -296,8 +301,7 @@ hipError_t launch_postprocess_meet(PostArgs a, const MeetGroup* groups, int n_gr
 int postprocess_max_pairs_per_image() { return kSortMax; }
 
 hipError_t launch_postprocess(const PostArgs& a, hipStream_t s) {
-  VETO_LAUNCH(obj_score_kernel, dim3((a.n_obj + 3) / 4), dim3(256), 0, s, a.obj_logits, a.n_obj, a.n_obj_cls, a.obj_scores, a.obj_pred);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_obj_scores(a, s);
   if (e != hipSuccess) return e;
   VETO_LAUNCH(rel_score_kernel, dim3((a.n_pair + 3) / 4), dim3(256), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;

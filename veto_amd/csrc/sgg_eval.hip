@@ -1,7 +1,8 @@
 // Relation evaluators on the device: what the reference computes per image on the
 // host in numpy after pulling every BoxList back (pysgg/data/datasets/evaluation/vg/vg_eval.py:459-566 driving
 // sgg_eval.py): R@K, no-graph-constraint R@K, zero-shot R@K, GT-pair accuracy A@K, mean recall and
-// no-graph-constraint mean recall, K = 20 / 50 / 100, for the GT-box modes.
+// no-graph-constraint mean recall, K = 20 / 50 / 100, for the GT-box modes and sgdet.  sgdet (mode 1): the predicted
+// objects have their own count and offsets (pred_obj_off), and SGPairAccuracy records nothing (sgg_eval.py:356).
 //
 // All of them are functions of, per GT relation g, the position of the FIRST prediction that matches it
 // (sgg_eval.py:78-118 builds the inverse map pred -> [gt]; `reduce(np.union1d, pred_to_gt[:k])` contains g iff
@@ -63,7 +64,8 @@ __global__ __launch_bounds__(kThreads) void sgg_eval_image_kernel(SggEvalArgs a)
   __shared__ int s_ncand;
   const int img = blockIdx.x, tid = threadIdx.x;
   const int g0 = a.gt_off[img], G = a.gt_off[img + 1] - g0;
-  const int o0 = a.obj_off[img];
+  const int o0 = a.obj_off[img];                                     // GT objects
+  const int q0 = a.pred_obj_off ? a.pred_obj_off[img] : o0;          // predicted objects (sgdet: their own count)
   const int p0 = a.pair_off[img], P = a.pair_off[img + 1] - p0;
   const int C = a.n_rel_cls, Cf = C - 1;
   int* cls_tab = a.cls_table + (size_t)img * 7 * C;   // [count | hits gc@20,50,100 | hits ng@20,50,100][C]
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void sgg_eval_image_kernel(SggEvalArgs a)
     for (int g = ln; g < G; g += 64) flag |= (gt[3 * g] == s && gt[3 * g + 1] == o);
     flag = __any(flag);
     if (ln == 0) {
-      const float ps = a.obj_scores[o0 + s] * a.obj_scores[o0 + o];
+      const float ps = a.obj_scores[q0 + s] * a.obj_scores[q0 + o];
       a.label_tmp[p0 + p] = lab;
       a.pair_score[p0 + p] = ps;
       a.row_key[p0 + p] = float_key(ps * best);   // the row's largest cell (ps >= 0: the product is monotone)
@@ -285,11 +287,11 @@ __global__ __launch_bounds__(kThreads) void sgg_eval_image_kernel(SggEvalArgs a)
     const int gs = (int)gt[3 * g], go = (int)gt[3 * g + 1], gr = (int)gt[3 * g + 2];
     if (a.label_tmp[p0 + p] != gr) continue;
     const int s = (int)pairs[2 * p], o = (int)pairs[2 * p + 1];
-    if (a.pred_classes[o0 + s] != a.gt_classes[o0 + gs] || a.pred_classes[o0 + o] != a.gt_classes[o0 + go]) continue;
-    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + gs), a.pred_boxes + 4 * (size_t)(o0 + s)) < thr_iou) continue;
-    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + go), a.pred_boxes + 4 * (size_t)(o0 + o)) < thr_iou) continue;
+    if (a.pred_classes[q0 + s] != a.gt_classes[o0 + gs] || a.pred_classes[q0 + o] != a.gt_classes[o0 + go]) continue;
+    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + gs), a.pred_boxes + 4 * (size_t)(q0 + s)) < thr_iou) continue;
+    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + go), a.pred_boxes + 4 * (size_t)(q0 + o)) < thr_iou) continue;
     atomicMin(&a.gc_rank[g0 + g], p);
-    if (a.flag_tmp[p0 + p]) atomicMin(&a.acc_first[g0 + g], p);
+    if (a.flag_tmp[p0 + p] && a.mode == 0) atomicMin(&a.acc_first[g0 + g], p);   // sgdet: no pair-accuracy hits
   }
   for (int w = tid; w < G * n_list; w += kThreads) {
     const int g = w / n_list, j = w % n_list;
@@ -297,9 +299,9 @@ __global__ __launch_bounds__(kThreads) void sgg_eval_image_kernel(SggEvalArgs a)
     if (a.ng_cols[(size_t)img * kTop + j] != gr) continue;
     const int p = a.ng_rows[(size_t)img * kTop + j];
     const int s = (int)pairs[2 * p], o = (int)pairs[2 * p + 1];
-    if (a.pred_classes[o0 + s] != a.gt_classes[o0 + gs] || a.pred_classes[o0 + o] != a.gt_classes[o0 + go]) continue;
-    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + gs), a.pred_boxes + 4 * (size_t)(o0 + s)) < thr_iou) continue;
-    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + go), a.pred_boxes + 4 * (size_t)(o0 + o)) < thr_iou) continue;
+    if (a.pred_classes[q0 + s] != a.gt_classes[o0 + gs] || a.pred_classes[q0 + o] != a.gt_classes[o0 + go]) continue;
+    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + gs), a.pred_boxes + 4 * (size_t)(q0 + s)) < thr_iou) continue;
+    if (iou_plus1(a.gt_boxes + 4 * (size_t)(o0 + go), a.pred_boxes + 4 * (size_t)(q0 + o)) < thr_iou) continue;
     atomicMin(&a.ng_rank[g0 + g], j);
   }
   // zero-shot flag (:279-291): the GT (subject class, object class, predicate) occurs in the table

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1502,7 +1503,7 @@ int veto_postprocess(void* stream, const veto_post_args_t* a, void* workspace, s
   if (a->struct_size != (int32_t)sizeof(veto_post_args_t)) return fail(VETO_ERR_INVALID, "veto_post_args_t size mismatch");
   if (a->n_img <= 0 || a->n_obj <= 0 || a->n_pair <= 0 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
-  if (!a->rel_logits || !a->obj_logits || !a->rel_pairs || !a->img_obj_offset || !a->img_pair_offset || !a->obj_scores ||
+  if (!a->rel_logits || !a->rel_pairs || !a->img_obj_offset || !a->img_pair_offset || !a->obj_scores ||
       !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted)
     return fail(VETO_ERR_INVALID, "missing pointer");
   if (a->max_pairs_per_image < 1 || a->max_pairs_per_image > postprocess_max_pairs_per_image())
@@ -1530,7 +1531,7 @@ int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* wo
   if (a->struct_size != (int32_t)sizeof(veto_post_meet_args_t)) return fail(VETO_ERR_INVALID, "veto_post_meet_args_t size mismatch");
   if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
-  if (!a->group_logits || !a->group_widths || !a->incre_idx_list || !a->obj_logits || !a->rel_pairs || !a->obj_scores ||
+  if (!a->group_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
       !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted)
     return fail(VETO_ERR_INVALID, "missing pointer");
   const long total = (long)a->n_groups * a->n_pair;
@@ -1574,7 +1575,7 @@ int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* wo
   if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
   if (a->voting != 0 && a->voting != 1) return fail(VETO_ERR_INVALID, "voting must be 0 ('C') or 1 ('U')");
-  if (!a->expert_logits || !a->group_widths || !a->incre_idx_list || !a->obj_logits || !a->rel_pairs || !a->obj_scores ||
+  if (!a->expert_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
       !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted || !a->kept_count)
     return fail(VETO_ERR_INVALID, "missing pointer");
   const long total = (long)a->n_groups * a->n_pair;
@@ -1613,6 +1614,52 @@ int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* wo
   p.label_tmp = (int32_t*)base; base += align_up((size_t)total * 4, 256);
   p.perm = (int32_t*)base;
   HIP_TRY(launch_postprocess_vote(p, groups.data(), a->n_groups, a->voting, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+size_t veto_obj_decode_workspace_bytes(int32_t n_obj, int32_t n_cls) {
+  if (n_obj <= 0 || n_cls <= 0) return 0;
+  return align_up((size_t)n_obj * n_cls * 4, 256);
+}
+
+int veto_obj_decode(void* stream, const veto_obj_decode_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_obj_decode_args_t)) return fail(VETO_ERR_INVALID, "veto_obj_decode_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_obj <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->max_obj_per_image < 1 || a->max_obj_per_image > obj_decode_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 1..%d (DETECTIONS_PER_IMG)", a->max_obj_per_image,
+                obj_decode_max_objects());
+  if (a->mode != 0 && a->mode != 1) return fail(VETO_ERR_INVALID, "mode must be 0 (PostProcessor) or 1 (MEET decoder)");
+  if (!a->boxes_per_cls || !a->img_obj_offset || !a->obj_pred || (a->mode == 0 && !a->logits) || (a->mode == 1 && !a->labels) ||
+      (a->obj_scores && !a->logits))
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (!workspace || workspace_bytes < veto_obj_decode_workspace_bytes(a->n_obj, a->n_cls))
+    return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ObjDecodeArgs p{};
+  p.logits = a->logits; p.labels = a->labels; p.boxes_per_cls = a->boxes_per_cls; p.img_off = a->img_obj_offset;
+  p.n_img = a->n_img; p.n_cls = a->n_cls; p.mode = a->mode; p.thr = a->nms_thres;
+  p.prob_ws = (float*)workspace;
+  p.obj_pred = a->obj_pred; p.obj_scores = a->obj_scores; p.out_boxes = a->boxes;
+  HIP_TRY(launch_obj_decode(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_pair_args_t)) return fail(VETO_ERR_INVALID, "veto_pair_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_obj < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
+  if (a->max_obj_per_image < 0 || a->max_obj_per_image > obj_decode_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d", a->max_obj_per_image, obj_decode_max_objects());
+  if (a->max_pairs < 1 || a->max_pairs > prepare_pairs_max_pairs())
+    return fail(VETO_ERR_INVALID, "max_pairs %d outside 1..%d (MAX_PROPOSAL_PAIR)", a->max_pairs, prepare_pairs_max_pairs());
+  if ((a->n_obj > 0 && (!a->boxes || !a->scores)) || !a->img_obj_offset || !a->img_out_offset || !a->pairs || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  PairArgs p{};
+  p.boxes = a->boxes; p.scores = a->scores; p.img_off = a->img_obj_offset; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.max_pairs = a->max_pairs; p.require_overlap = a->require_overlap != 0;
+  p.pairs = a->pairs; p.counts = a->counts;
+  HIP_TRY(launch_prepare_pairs(p, (hipStream_t)stream));
   return VETO_OK;
 }
 
@@ -1687,7 +1734,13 @@ size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_
 int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_total, int32_t n_gt_total, void* workspace,
                   size_t workspace_bytes) {
   if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_sgg_eval_args_t)) return fail(VETO_ERR_INVALID, "veto_sgg_eval_args_t size mismatch");
+  // the struct before pred_obj_offset was appended is still accepted (GT-box modes, pred_obj_offset = NULL)
+  const bool has_pred_off = a->struct_size == (int32_t)sizeof(veto_sgg_eval_args_t);
+  if (!has_pred_off && a->struct_size != (int32_t)offsetof(veto_sgg_eval_args_t, pred_obj_offset))
+    return fail(VETO_ERR_INVALID, "veto_sgg_eval_args_t size mismatch");
+  if (a->reserved0 != 0 && a->reserved0 != 1) return fail(VETO_ERR_INVALID, "mode (reserved0) must be 0 (GT boxes) or 1 (sgdet)");
+  const int32_t* pred_off = has_pred_off ? a->pred_obj_offset : nullptr;
+  if (a->reserved0 == 1 && !pred_off) return fail(VETO_ERR_INVALID, "sgdet needs pred_obj_offset");
   if (a->n_img <= 0 || a->n_rel_cls < 2 || a->n_rel_cls > 4096 || a->n_zeroshot < 0 || n_pair_total < 0 || n_gt_total < 0)
     return fail(VETO_ERR_INVALID, "bad sizes");
   if (!(a->iou_thres >= 0.f && a->iou_thres <= 1.f)) return fail(VETO_ERR_INVALID, "iou_thres must be in [0, 1]");
@@ -1700,6 +1753,7 @@ int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_to
   SggEvalArgs p{};
   p.n_img = a->n_img; p.n_rel_cls = a->n_rel_cls; p.n_zeroshot = a->n_zeroshot; p.iou_thres = a->iou_thres;
   p.gt_off = a->gt_offset; p.obj_off = a->obj_offset; p.pair_off = a->pair_offset;
+  p.pred_obj_off = pred_off; p.mode = a->reserved0;
   p.gt_rels = a->gt_rels; p.gt_classes = a->gt_classes; p.gt_boxes = a->gt_boxes;
   p.pred_pairs = a->pred_pairs; p.rel_scores = a->rel_scores; p.pred_classes = a->pred_classes;
   p.pred_boxes = a->pred_boxes; p.obj_scores = a->obj_scores; p.zeroshot = a->zeroshot;

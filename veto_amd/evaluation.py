@@ -3,7 +3,9 @@
 Host-side counterpart of the reference's per-image routine `evaluate_relation_of_one_image`
 (pysgg/data/datasets/evaluation/vg/vg_eval.py:459-566) and of the evaluator classes it drives
 (sgg_eval.py: SGRecall, SGNoGraphConstraintRecall, SGZeroShotRecall, SGPairAccuracy, SGMeanRecall,
-SGNGMeanRecall) for the GT-box modes predcls / sgcls.  The reference pulls every BoxList to the host and loops
+SGNGMeanRecall) for the GT-box modes predcls / sgcls and for sgdet, where the predicted objects are the detector's (their
+count differs from the GT count) and SGPairAccuracy records nothing, so A@K is NaN as in the reference
+(sgg_eval.py:356, vg_eval.py:500-525).  The reference pulls every BoxList to the host and loops
 in numpy; here the sorted predictions stay on the device, one launch (veto_sgg_eval) scores all images of the
 batch, and only the final numbers (and, for inspection, the per-relation match ranks) come back.
 
@@ -31,8 +33,8 @@ def _t(x, dtype, device):
 
 class SGGEvaluator:
     def __init__(self, mode, num_rel_category, zeroshot_triplet, iou_thres=0.5, device="cuda"):
-        if mode not in ("predcls", "sgcls"):
-            raise NotImplementedError("veto_amd.SGGEvaluator covers the GT-box modes predcls / sgcls, got %r" % (mode,))
+        if mode not in ("predcls", "sgcls", "sgdet"):
+            raise NotImplementedError("veto_amd.SGGEvaluator covers predcls / sgcls / sgdet, got %r" % (mode,))
         self.mode, self.num_rel, self.iou_thres = mode, int(num_rel_category), float(iou_thres)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -84,8 +86,9 @@ class SGGEvaluator:
                 lists["recall_nogc"][k].append(float(nghit.sum()) / float(G))
                 if zs.any():
                     lists["zeroshot_recall"][k].append(float((hit & zs).sum()) / float(zs.sum()))
-                lists["acc_hit"][k].append(float((ac < k).sum()))
-                lists["acc_cnt"][k].append(float(G))
+                if self.mode != "sgdet":   # sgg_eval.py:356: SGPairAccuracy records nothing in sgdet -> A@K = NaN
+                    lists["acc_hit"][k].append(float((ac < k).sum()))
+                    lists["acc_cnt"][k].append(float(G))
                 for name, h in (("mean_recall", hit), ("ng_mean_recall", nghit)):
                     cnt = np.bincount(gt_pred, minlength=C)
                     hc = np.bincount(gt_pred[h], minlength=C)
@@ -130,13 +133,19 @@ class SGGEvaluator:
         else:
             pred_classes, pred_boxes = cat("pred_classes", i64, (-1,)), cat("pred_boxes", f32, (-1, 4))
             obj_scores = cat("obj_scores", f32, (-1,))
-            if pred_boxes.shape[0] != gt_boxes.shape[0]:
+            if self.mode == "sgcls" and pred_boxes.shape[0] != gt_boxes.shape[0]:
                 raise ValueError("sgcls: the number of predicted boxes must equal the number of GT boxes")
         rows = lambda x, width: int(x.numel() // width) if isinstance(x, torch.Tensor) else int(np.asarray(x).size // width)
         n_g = [rows(im["gt_rels"], 3) for im in images]
         n_o = [int(len(im["gt_classes"])) for im in images]
         n_p = [rows(im["pred_rel_inds"], 2) for im in images]
         obj_off, pair_off = cached_offsets(n_o, n_p, dev)
+        pred_off = None
+        if self.mode == "sgdet":   # the detector's objects: their own count per image (vg_eval.py:491-495)
+            n_q = [rows(im["pred_classes"], 1) for im in images]
+            if [rows(im["pred_boxes"], 4) for im in images] != n_q or [rows(im["obj_scores"], 1) for im in images] != n_q:
+                raise ValueError("sgdet: pred_classes, pred_boxes and obj_scores must have one row per predicted object")
+            pred_off = cached_offsets(n_q, n_q, dev)[0]
         gt_off = cached_offsets(n_g, n_g, dev)[0]
         n_img, sum_g, sum_p, C = len(images), sum(n_g), sum(n_p), self.num_rel
         out = {k: torch.empty(max(sum_g, 1), dtype=i32, device=dev) for k in ("gc_rank", "ng_rank", "acc_rank", "zeroshot_flag")}
@@ -155,6 +164,8 @@ class SGGEvaluator:
         a.pred_pairs, a.rel_scores = pred_pairs.data_ptr(), rel_scores.data_ptr()
         a.pred_classes, a.pred_boxes, a.obj_scores = pred_classes.data_ptr(), pred_boxes.data_ptr(), obj_scores.data_ptr()
         a.zeroshot = self.zeroshot.data_ptr() if self.zeroshot.shape[0] else None
+        a.reserved0 = 1 if pred_off is not None else 0
+        a.pred_obj_offset = pred_off.data_ptr() if pred_off is not None else None
         a.gc_rank, a.ng_rank, a.acc_rank = out["gc_rank"].data_ptr(), out["ng_rank"].data_ptr(), out["acc_rank"].data_ptr()
         a.zeroshot_flag = out["zeroshot_flag"].data_ptr()
         a.ng_rows, a.ng_cols, a.ng_count, a.metrics = ng_rows.data_ptr(), ng_cols.data_ptr(), ng_count.data_ptr(), metrics.data_ptr()
@@ -166,6 +177,8 @@ class SGGEvaluator:
         res = {"images_evaluated": int(m[18 + 6 * Cf]), "images_with_zeroshot": int(m[18 + 6 * Cf + 1])}
         for j, name in enumerate(("recall", "recall_nogc", "zeroshot_recall", "accuracy", "mean_recall", "ng_mean_recall")):
             res[name] = {k: float(m[3 * j + i]) for i, k in enumerate(KS)}
+        if self.mode == "sgdet":
+            res["accuracy"] = {k: float("nan") for k in KS}
         for kind, name in enumerate(("mean_recall_list", "ng_mean_recall_list")):
             res[name] = {k: m[18 + (kind * 3 + i) * Cf: 18 + (kind * 3 + i + 1) * Cf].tolist() for i, k in enumerate(KS)}
         # per-image views (what the reference keeps as lists in its result_dict), from the match ranks
@@ -196,7 +209,8 @@ class SGGEvaluator:
         return res
 
     def generate_print_string(self, res):
-        """The lines the reference logs (sgg_eval.py generate_print_string of the six evaluators)."""
+        """The lines the reference logs (sgg_eval.py generate_print_string of the six evaluators).  sgdet: the A@K line reads
+        nan, as the reference's mean over an empty list does."""
         fmt = lambda tag, d: "".join(" %s @ %d: %.4f; " % (tag, k, d[k]) for k in KS)
         m = self.mode
         return ("SGG eval: " + fmt(" R", res["recall"]) + " for mode=%s, type=Recall(Main).\n" % m +

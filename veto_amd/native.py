@@ -20,6 +20,7 @@ EXPORTS = [
     "veto_enumerate_pairs", "veto_profile_enable", "veto_profile_collect", "veto_profile_entry",
     "veto_profile_reset", "veto_debug_gemm", "veto_debug_gemm_workspace_bytes", "veto_debug_gemm_forms", "veto_debug_ffn", "veto_debug_ffn_workspace_bytes", "veto_debug_outproj", "veto_debug_outproj_workspace_bytes", "veto_debug_layer_tail", "veto_debug_layer_tail_workspace_bytes", "veto_debug_qkv_attn", "veto_debug_qkv_attn_workspace_bytes",
     "veto_postprocess", "veto_postprocess_workspace_bytes", "veto_postprocess_meet", "veto_postprocess_vote",
+    "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
@@ -68,6 +69,18 @@ class VetoPostArgs(Structure):
                                         "rel_labels_sorted", "triple_sorted")]
 
 
+class VetoObjDecodeArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_obj", "n_cls", "max_obj_per_image", "mode")] + \
+               [("nms_thres", ctypes.c_float), ("reserved0", c_int32)] + \
+               [(n, c_void_p) for n in ("logits", "labels", "boxes_per_cls", "img_obj_offset", "obj_pred", "obj_scores", "boxes")]
+
+
+class VetoPairArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_obj", "max_obj_per_image", "max_pairs",
+                                       "require_overlap")] + \
+               [(n, c_void_p) for n in ("boxes", "scores", "img_obj_offset", "img_out_offset", "pairs", "counts")]
+
+
 class VetoPostMeetArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_obj", "n_pair", "n_groups", "n_rel_cls", "n_obj_cls")] + \
                [(n, c_void_p) for n in ("group_logits", "group_widths", "incre_idx_list", "obj_logits", "rel_pairs",
@@ -98,7 +111,7 @@ class VetoSggEvalArgs(Structure):
                [(n, c_void_p) for n in ("gt_offset", "obj_offset", "pair_offset", "gt_rels", "gt_classes", "gt_boxes",
                                         "pred_pairs", "rel_scores", "pred_classes", "pred_boxes", "obj_scores", "zeroshot",
                                         "gc_rank", "ng_rank", "acc_rank", "zeroshot_flag", "ng_rows", "ng_cols", "ng_count",
-                                        "metrics")]
+                                        "metrics", "pred_obj_offset")]
 
 
 class VetoTrainOpts(Structure):
@@ -172,6 +185,10 @@ def load_library():
     lib.veto_postprocess.argtypes = [c_void_p, POINTER(VetoPostArgs), c_void_p, c_size_t]
     lib.veto_postprocess_meet.argtypes = [c_void_p, POINTER(VetoPostMeetArgs), c_void_p, c_size_t]
     lib.veto_postprocess_vote.argtypes = [c_void_p, POINTER(VetoPostVoteArgs), c_void_p, c_size_t]
+    lib.veto_obj_decode_workspace_bytes.argtypes = [c_int32, c_int32]
+    lib.veto_obj_decode_workspace_bytes.restype = c_size_t
+    lib.veto_obj_decode.argtypes = [c_void_p, POINTER(VetoObjDecodeArgs), c_void_p, c_size_t]
+    lib.veto_prepare_test_pairs.argtypes = [c_void_p, POINTER(VetoPairArgs)]
     lib.veto_train_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
     lib.veto_train_workspace_bytes.restype = c_size_t
     lib.veto_grad_floats.argtypes = [c_void_p]

@@ -1,9 +1,16 @@
 """Test-time pair enumeration, the caller-side contract of the hot path.
 
-Mirrors `RelationSampling.prepare_test_pairs` (sampling.py:31-52) for the GT-box modes the
-predictor is benchmarked in (predcls / sgcls): every ordered pair (i, j), i != j, in the row-major
-order of `torch.nonzero(ones - eye)`, or the `[[0, 0]]` placeholder when an image has no candidate
-pair.  The enumeration runs on the device through the C ABI (veto_enumerate_pairs)."""
+Mirrors `RelationSampling.prepare_test_pairs` (sampling.py:31-52).  GT-box modes (predcls / sgcls, the
+benchmarked path): every ordered pair (i, j), i != j, in the row-major order of `torch.nonzero(ones - eye)`,
+or the `[[0, 0]]` placeholder when an image has no candidate pair; the enumeration runs on the device through
+the C ABI (veto_enumerate_pairs) and the MAX_PROPOSAL_PAIR cap is a host-issued torch.sort.
+
+Detected boxes (sgdet, `use_gt_box=False`): one veto_prepare_test_pairs launch for the batch does the optional
+box-overlap filter (REQUIRE_BOX_OVERLAP, `boxlist_iou(p, p) > 0`), the row-major enumeration and the cap, whose
+survivors come in the total order (quality desc, row-major index asc) -- what torch.sort(stable=True,
+descending=True) gives; the reference's unstable sort leaves the order of tied pairs, e.g. (i, j) and (j, i),
+unspecified.  Without the filter every image's pair count is known on the host.  With it, the counts are data
+dependent: the batch's int32 counts are read back once (one device->host copy per batch) to split the list."""
 import ctypes
 
 import torch
@@ -11,11 +18,13 @@ import torch
 from . import native
 
 
-def prepare_test_pairs(device, proposals, max_proposal_pairs=2048):
+def prepare_test_pairs(device, proposals, max_proposal_pairs=2048, require_overlap=False, use_gt_box=True):
     lib = native.load_library()
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("veto_amd.prepare_test_pairs runs on a HIP device only (got %s)" % device)
+    if not use_gt_box:
+        return _prepare_detected_pairs(lib, device, proposals, max_proposal_pairs, require_overlap)
     stream = torch.cuda.current_stream(device).cuda_stream
     out = []
     for p in proposals:
@@ -30,3 +39,36 @@ def prepare_test_pairs(device, proposals, max_proposal_pairs=2048):
             idxs = idxs[torch.sort(q, descending=True)[1][:max_proposal_pairs]]
         out.append(idxs)
     return out
+
+
+def pair_capacity(n, max_proposal_pairs):
+    """Rows reserved for an image of n detections: all ordered pairs (or the placeholder), at most the cap."""
+    return min(max(n * (n - 1), 1), max_proposal_pairs)
+
+
+def _prepare_detected_pairs(lib, device, proposals, max_proposal_pairs, require_overlap):
+    from .predictor import cached_offsets
+    n_objs = [len(p) for p in proposals]
+    caps = [pair_capacity(n, max_proposal_pairs) for n in n_objs]
+    f32 = dict(device=device, dtype=torch.float32)
+    boxes = torch.cat([p.convert("xyxy").bbox.reshape(-1, 4) for p in proposals], 0).to(**f32).contiguous()
+    scores = torch.cat([p.get_field("pred_scores").reshape(-1) for p in proposals], 0).to(**f32).contiguous()
+    obj_off, out_off = cached_offsets(n_objs, caps, device)
+    pairs = torch.empty((sum(caps), 2), dtype=torch.int64, device=device)
+    counts = torch.empty(len(proposals), dtype=torch.int32, device=device)
+    a = native.VetoPairArgs()
+    a.struct_size = ctypes.sizeof(native.VetoPairArgs)
+    a.n_img, a.n_obj, a.max_obj_per_image = len(proposals), sum(n_objs), max(n_objs)
+    a.max_pairs, a.require_overlap = int(max_proposal_pairs), int(bool(require_overlap))
+    a.boxes, a.scores = boxes.data_ptr(), scores.data_ptr()
+    a.img_obj_offset, a.img_out_offset = obj_off.data_ptr(), out_off.data_ptr()
+    a.pairs, a.counts = pairs.data_ptr(), counts.data_ptr()
+    stream = torch.cuda.current_stream(device)
+    native.check(lib.veto_prepare_test_pairs(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
+    for t in (boxes, scores, obj_off, out_off):
+        t.record_stream(stream)
+    rows = pairs.split(caps)
+    if not require_overlap:
+        return list(rows)
+    kept = counts.tolist()   # the one device->host copy of the batch: the filtered counts decide the split
+    return [r[:k] for r, k in zip(rows, kept)]

@@ -10,8 +10,11 @@ libveto_amd.so (veto_postprocess).  When the relation logits are the MEET dict o
 through veto_postprocess_meet with the reference's quirks kept: one image per call, group-local
 labels, float pair indices.  With EXPERT_GROUP True (three expert heads per group, keys 'group_<k><e>') the
 voting branch (inference.py:93-283, ENSEMBLE_LEARNING.VOTING 'C' or 'U') runs through veto_postprocess_vote;
-its row count is data dependent, so that branch reads one int32 back from the device.  sgdet decoding
-(per-class NMS, inference.py:413-418) and attributes are not built; they raise."""
+its row count is data dependent, so that branch reads one int32 back from the device.  With detected boxes
+(sgdet, use_gt_box False) every branch first decodes the objects with the class-aware NMS of inference.py:413-429
+(veto_obj_decode, LATER_NMS_PREDICTION_THRES) and returns NEW BoxLists holding the regressed boxes
+boxes_per_cls[i, label_i]; the relation kernels then read those labels / scores (obj_logits = NULL).  Attributes
+are not built; they raise."""
 import ctypes
 
 import torch
@@ -35,8 +38,6 @@ class PostProcessor(nn.Module):
         relation_logits, refine_logits = x
         if self.attribute_on:
             raise NotImplementedError("veto_amd.PostProcessor: attribute head is outside the VETO path")
-        if not self.use_gt_box:
-            raise NotImplementedError("veto_amd.PostProcessor: sgdet decoding (per-class NMS) is not built")
         if isinstance(relation_logits, dict):
             if "group_01" in relation_logits:   # inference.py:93: three experts per group
                 return self._forward_vote(relation_logits, refine_logits, rel_pair_idxs, boxes, incre_idx_list)
@@ -57,8 +58,9 @@ class PostProcessor(nn.Module):
             raise ValueError("logit rows (%d, %d) do not match pairs/objects (%d, %d)" % (rel.shape[0], obj.shape[0], n_pair, n_obj))
         pairs = torch.cat([p.reshape(-1, 2) for p in rel_pair_idxs], 0).to(device=device, dtype=torch.int64).contiguous()
         obj_off, pair_off = cached_offsets(n_objs, n_pairs, device)   # no host-blocking H2D copy in the steady state
+        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes)
         out = {
-            "obj_scores": torch.empty(n_obj, **f32), "obj_pred": torch.empty(n_obj, dtype=torch.int64, device=device),
+            "obj_scores": obj_scores, "obj_pred": obj_pred,
             "prob": torch.empty((n_pair, rel.shape[1]), **f32),
             "pairs": torch.empty((n_pair, 2), dtype=torch.int64, device=device),
             "labels": torch.empty(n_pair, dtype=torch.int64, device=device), "triple": torch.empty(n_pair, **f32),
@@ -70,7 +72,8 @@ class PostProcessor(nn.Module):
         a.struct_size = ctypes.sizeof(native.VetoPostArgs)
         a.n_img, a.n_obj, a.n_pair = len(boxes), n_obj, n_pair
         a.n_rel_cls, a.n_obj_cls, a.max_pairs_per_image = rel.shape[1], obj.shape[1], max(n_pairs)
-        a.rel_logits, a.obj_logits, a.rel_pairs = rel.data_ptr(), obj.data_ptr(), pairs.data_ptr()
+        a.rel_logits, a.rel_pairs = rel.data_ptr(), pairs.data_ptr()
+        a.obj_logits = obj.data_ptr() if reg_boxes is None else None   # sgdet: labels / scores are the decoder's
         a.img_obj_offset, a.img_pair_offset = obj_off.data_ptr(), pair_off.data_ptr()
         a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
         a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
@@ -82,9 +85,11 @@ class PostProcessor(nn.Module):
             t.record_stream(stream)
         self.last_triple_scores = out["triple"].split(n_pairs)
         results = []
-        for box, sc, pr, prob, pidx, lab in zip(boxes, out["obj_scores"].split(n_objs), out["obj_pred"].split(n_objs),
-                                                out["prob"].split(n_pairs), out["pairs"].split(n_pairs),
-                                                out["labels"].split(n_pairs)):
+        regs = reg_boxes.split(n_objs) if reg_boxes is not None else [None] * len(boxes)
+        for box, reg, sc, pr, prob, pidx, lab in zip(boxes, regs, out["obj_scores"].split(n_objs), out["obj_pred"].split(n_objs),
+                                                     out["prob"].split(n_pairs), out["pairs"].split(n_pairs),
+                                                     out["labels"].split(n_pairs)):
+            box = self._result_box(box, reg)
             box.add_field("pred_labels", pr)       # inference.py:431-432 (the GT-box branch re-uses `box`)
             box.add_field("pred_scores", sc)
             box.add_field("rel_pair_idxs", pidx)   # :450-452
@@ -111,7 +116,8 @@ class PostProcessor(nn.Module):
         pairs = rel_pair_idxs[0].reshape(-1, 2).to(device=device, dtype=torch.int64).contiguous()
         n_obj, n_pair, K, n_rel = obj.shape[0], pairs.shape[0], len(groups), len(incre_idx_list)
         total = K * n_pair
-        out = {"obj_scores": torch.empty(n_obj, **f32), "obj_pred": torch.empty(n_obj, dtype=torch.int64, device=device),
+        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes[:1])
+        out = {"obj_scores": obj_scores, "obj_pred": obj_pred,
                "prob": torch.empty((total, n_rel), **f32), "pairs": torch.empty((total, 2), dtype=torch.int64, device=device),
                "labels": torch.empty(total, dtype=torch.int64, device=device), "triple": torch.empty(total, **f32)}
         need = lib.veto_postprocess_workspace_bytes(total, n_rel)
@@ -126,7 +132,8 @@ class PostProcessor(nn.Module):
         a.group_logits = ctypes.cast(ptrs, ctypes.c_void_p)
         a.group_widths = ctypes.cast(widths, ctypes.c_void_p)
         a.incre_idx_list = ctypes.cast(incre, ctypes.c_void_p)
-        a.obj_logits, a.rel_pairs = obj.data_ptr(), pairs.data_ptr()
+        a.obj_logits = obj.data_ptr() if reg_boxes is None else None
+        a.rel_pairs = pairs.data_ptr()
         a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
         a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
         a.rel_labels_sorted, a.triple_sorted = out["labels"].data_ptr(), out["triple"].data_ptr()
@@ -136,7 +143,7 @@ class PostProcessor(nn.Module):
         for t in groups + [obj, pairs]:
             t.record_stream(stream)
         self.last_triple_scores = [out["triple"]]
-        box = boxes[0]
+        box = self._result_box(boxes[0], reg_boxes)
         box.add_field("pred_labels", out["obj_pred"])
         box.add_field("pred_scores", out["obj_scores"])
         box.add_field("rel_pair_idxs", out["pairs"].to(torch.float32))  # torch.zeros(total, 2) in the reference (:381)
@@ -168,7 +175,8 @@ class PostProcessor(nn.Module):
         pairs = rel_pair_idxs[0].reshape(-1, 2).to(device=device, dtype=torch.int64).contiguous()
         n_obj, n_pair, n_rel = obj.shape[0], pairs.shape[0], len(incre_idx_list)
         total = K * n_pair
-        out = {"obj_scores": torch.empty(n_obj, **f32), "obj_pred": torch.empty(n_obj, dtype=torch.int64, device=device),
+        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes[:1])
+        out = {"obj_scores": obj_scores, "obj_pred": obj_pred,
                "prob": torch.empty((total, n_rel), **f32), "pairs": torch.empty((total, 2), dtype=torch.int64, device=device),
                "labels": torch.empty(total, dtype=torch.int64, device=device), "triple": torch.empty(total, **f32),
                "kept": torch.zeros(1, dtype=torch.int32, device=device)}
@@ -185,7 +193,8 @@ class PostProcessor(nn.Module):
         a.expert_logits = ctypes.cast(ptrs, ctypes.c_void_p)
         a.group_widths = ctypes.cast(widths, ctypes.c_void_p)
         a.incre_idx_list = ctypes.cast(incre, ctypes.c_void_p)
-        a.obj_logits, a.rel_pairs = obj.data_ptr(), pairs.data_ptr()
+        a.obj_logits = obj.data_ptr() if reg_boxes is None else None
+        a.rel_pairs = pairs.data_ptr()
         a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
         a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
         a.rel_labels_sorted, a.triple_sorted = out["labels"].data_ptr(), out["triple"].data_ptr()
@@ -197,13 +206,36 @@ class PostProcessor(nn.Module):
             t.record_stream(stream)
         kept = int(out["kept"].item())   # the one device read-back: the result's row count is data dependent
         self.last_triple_scores = [out["triple"][:kept]]
-        box = boxes[0]
+        box = self._result_box(boxes[0], reg_boxes)
         box.add_field("pred_labels", out["obj_pred"])
         box.add_field("pred_scores", out["obj_scores"])
         box.add_field("rel_pair_idxs", out["pairs"][:kept].to(torch.float32))  # float, as the reference (:267)
         box.add_field("pred_rel_scores", out["prob"][:kept])
         box.add_field("pred_rel_labels", out["labels"][:kept])                 # group-local labels
         return [box]
+
+    def _decode_objects(self, obj_logits, boxes):
+        """(obj_pred, obj_scores, regressed boxes) of the concatenated images.  GT boxes: two empty outputs that the
+        relation kernel fills from obj_logits, no boxes.  Detected boxes: the class-aware NMS decoding of
+        inference.py:413-429 on the device (veto_obj_decode), whose labels / scores the relation kernel then reads."""
+        device, n_obj = obj_logits.device, obj_logits.shape[0]
+        if self.use_gt_box:
+            return (torch.empty(n_obj, dtype=torch.int64, device=device), torch.empty(n_obj, dtype=torch.float32, device=device),
+                    None)
+        from .sgdet import decode_objects
+        for b in boxes:
+            if not b.has_field("boxes_per_cls"):
+                raise ValueError("sgdet post-processing needs the detector's 'boxes_per_cls' field on every proposal")
+        boxes_per_cls = torch.cat([b.get_field("boxes_per_cls").reshape(len(b), -1, 4) for b in boxes], 0).to(device)
+        return decode_objects(obj_logits, boxes_per_cls, [len(b) for b in boxes], self.later_nms_pred_thres, mode="post")
+
+    @staticmethod
+    def _result_box(box, reg):
+        """GT boxes: the proposal itself (inference.py:421-422).  sgdet: a new BoxList of the regressed boxes, xyxy, with
+        the proposal's size (:424-428)."""
+        if reg is None:
+            return box
+        return type(box)(reg, box.size, "xyxy")
 
 
 def make_roi_relation_post_processor(cfg):

@@ -615,6 +615,7 @@ class VETOPredictor_MEET(nn.Module, _NativeForward):
         self._train_forward_only = bool(getattr(getattr(config, "VETO_AMD", None), "TRAIN_FORWARD_ONLY", False))
         self._dataset, self._sampler = dataset, None
         self._zero_label_padding_mode = str(config.GCL_SETTING.ZERO_LABEL_PADDING_MODE)
+        self.nms_thresh = float(config.TEST.RELATION.LATER_NMS_PREDICTION_THRES)   # Ensemble.__init__ :3670
 
     def forward(self, proposals, rel_pair_idxs, rel_labels, logger, roi_features=None,
                 roi_depth_features=None, rel_binarys=None):
@@ -622,12 +623,19 @@ class VETOPredictor_MEET(nn.Module, _NativeForward):
             labels = _cat_field(proposals, "labels").long()
             dist_labels = labels
         else:
-            if self.mode == "sgdet":
-                raise NotImplementedError("veto_amd: MEET sgdet decoding (per-class NMS, "
-                                          "roi_relation_predictors.py:3855-3874) is outside the hot path")
             dist_labels = _cat_field(proposals, "pred_labels").detach().long()
-            # obj_dists[:, 1:].max(1)[1] + 1 over a one-hot (:3776-3784): the label itself, or 1 for label 0
-            labels = torch.where(dist_labels > 0, dist_labels, torch.ones_like(dist_labels))
+            if self.mode == "sgdet":
+                if self.training:
+                    raise NotImplementedError("veto_amd: MEET training on detected boxes (detect_relsample, sampling.py:109-) "
+                                              "is not built")
+                # :3778-3781: the decoder's class-aware NMS over softmax(one_hot(pred_labels)), on the device
+                from .sgdet import decode_objects
+                boxes_per_cls = torch.cat([p.get_field("boxes_per_cls").reshape(len(p), -1, 4) for p in proposals], 0)
+                labels, _, _ = decode_objects(dist_labels, boxes_per_cls.to(dist_labels.device), [len(p) for p in proposals],
+                                              self.nms_thresh, mode="meet", want_scores=False, want_boxes=False)
+            else:
+                # obj_dists[:, 1:].max(1)[1] + 1 over a one-hot (:3776-3784): the label itself, or 1 for label 0
+                labels = torch.where(dist_labels > 0, dist_labels, torch.ones_like(dist_labels))
         if self.training:
             # :3930-3969 expert sampling, :3806-3846 group label remap + per-group CE
             from .losses import MeetTrainingSampler, ce_loss, relation_ce_loss

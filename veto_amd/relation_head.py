@@ -11,6 +11,10 @@ test mode with GT boxes:
   :196-203  predictor(proposals, rel_pair_idxs, rel_labels, logger, roi_features=, roi_depth_features=)
   :229-230  object refine logits = the proposals' `predict_logits`
   :241-243  post_processor((relation_logits, obj_refine_logits), rel_pair_idxs, proposals, incre_idx_list=...)
+and for sgdet (USE_GT_BOX False) at test time: the proposals are the detector's (fields predict_logits, pred_labels,
+pred_scores, boxes_per_cls), the pairs come from the detected-box branch of prepare_test_pairs (TEST.RELATION.REQUIRE_OVERLAP
+filter, capped by pred_scores products), and the post-processor decodes the objects with the class-aware NMS.
+Training on detected boxes (detect_relsample) is not built.
 Everything numeric runs in libveto_amd.so; this file only moves fields around."""
 import torch
 from torch import nn
@@ -48,9 +52,11 @@ class VETORelationHead(nn.Module):
         rh = cfg.MODEL.ROI_RELATION_HEAD
         if rh.PREDICTOR not in ("VETOPredictor", "VETOPredictor_MEET"):
             raise ValueError("VETORelationHead only drives the VETO predictors, got %r" % (rh.PREDICTOR,))
-        if not rh.USE_GT_BOX:
-            raise NotImplementedError("sgdet (detected boxes) is outside the built path")
-        self.mode = "predcls" if rh.USE_GT_OBJECT_LABEL else "sgcls"
+        self.use_gt_box = bool(rh.USE_GT_BOX)
+        self.mode = ("predcls" if rh.USE_GT_OBJECT_LABEL else "sgcls") if self.use_gt_box else "sgdet"
+        # the test-time overlap filter is TEST.RELATION.REQUIRE_OVERLAP (sampling.py:37-38 with :321); REQUIRE_BOX_OVERLAP is
+        # its training-time counterpart (detect_relsample, :145)
+        self.require_overlap = bool(getattr(cfg.TEST.RELATION, "REQUIRE_OVERLAP", False)) and not self.use_gt_box
         self.box_feature_extractor = make_roi_box_feature_extractor(cfg, in_channels, for_relation=True)  # :53
         self.predictor = registry.make_roi_relation_predictor(cfg, in_channels)
         self.post_processor = make_roi_relation_post_processor(cfg)
@@ -67,6 +73,9 @@ class VETORelationHead(nn.Module):
         if depth_features is None:
             raise ValueError("the VETO predictors need depth_features (relation_head.py:141)")
         if self.training:
+            if not self.use_gt_box:
+                raise NotImplementedError("veto_amd: training on detected boxes (sgdet relation sampling, "
+                                          "samp_processor.detect_relsample, sampling.py:109-) is not built")
             # :112-121 GT-box relation sampling, :140-141 ROI features, :196-203 predictor -> losses, :247 return
             if targets is None:
                 raise ValueError("training needs the targets (GT BoxLists with a 'relation' matrix)")
@@ -101,7 +110,8 @@ class VETORelationHead(nn.Module):
             raise NotImplementedError("forward_pooled is the test-time tail; call forward(features, proposals, targets, ...) to train")
         device = roi_features.device
         self._overload_predcls_fields(proposals, device)
-        rel_pair_idxs = prepare_test_pairs(device, proposals, self.max_proposal_pairs)
+        rel_pair_idxs = prepare_test_pairs(device, proposals, self.max_proposal_pairs, require_overlap=self.require_overlap,
+                                           use_gt_box=self.use_gt_box)
         obj_dists, relation_logits, add_losses, incre_idx_list, _, _ = self.predictor(
             proposals, rel_pair_idxs, None, logger, roi_features=roi_features, roi_depth_features=roi_depth_features)
         obj_refine_logits = [p.get_field("predict_logits") for p in proposals]

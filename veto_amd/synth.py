@@ -303,3 +303,100 @@ def synthetic_roi_pyramid(channels=256, num_objs=(9, 17, 5), W=1024, H=640, seed
     depth = rng.randn(len(num_objs), channels, H >> 4, W >> 4).astype(np.float32)
     boxes = [roi_test_boxes(rng, n, W, H) for n in num_objs]
     return feats, depth, boxes, (W, H)
+
+
+# ---------------------------------------------------------------------------
+# sgdet: detector outputs for the detected-box path (object decoding, test pairs)
+# ---------------------------------------------------------------------------
+
+def synthetic_detections(seed, n, num_obj_cls=151, W=800, H=600, spread=1.0):
+    """One image of n detections in clusters, as a detector hands them to the relation head: per-class regressed boxes
+    `boxes_per_cls` [n, C, 4] xyxy (the detection's box plus a small per-class jitter), `predict_logits` [n, C] that favour
+    the cluster's class (so the class-aware NMS really suppresses), `pred_labels`, `pred_scores` and the proposal `boxes`.
+    spread > 1 gives every detection a cluster of its own and pulls the clusters apart (no overlaps)."""
+    tag = "sgdet.%d.%d" % (n, num_obj_cls)
+    k = n if spread > 1 else max(1, n // 6)
+    cl = np.arange(n) if spread > 1 else integers(seed, tag + ".cluster", (n,), 0, k)
+    cx = uniform(seed, tag + ".cx", (k,), 0.1 * W, 0.9 * W).astype(np.float64) * spread
+    cy = uniform(seed, tag + ".cy", (k,), 0.1 * H, 0.9 * H).astype(np.float64) * spread
+    bw = uniform(seed, tag + ".w", (k,), 40.0, 260.0).astype(np.float64)
+    bh = uniform(seed, tag + ".h", (k,), 40.0, 220.0).astype(np.float64)
+    jit = normal(seed, tag + ".jit", (n, 4), 0.0, 12.0).astype(np.float64)
+    x1 = cx[cl] - bw[cl] / 2 + jit[:, 0]
+    y1 = cy[cl] - bh[cl] / 2 + jit[:, 1]
+    x2 = cx[cl] + bw[cl] / 2 + jit[:, 2]
+    y2 = cy[cl] + bh[cl] / 2 + jit[:, 3]
+    det = np.stack([x1, y1, x2, y2], 1)
+    per_cls = normal(seed, tag + ".cls_jit", (n, num_obj_cls, 4), 0.0, 5.0).astype(np.float64)
+    bpc = det[:, None, :] + per_cls
+    lo = np.minimum(bpc[..., 0:2], bpc[..., 2:4] - 8.0)
+    bpc = np.concatenate([np.maximum(lo, 0.0), np.maximum(bpc[..., 2:4], lo + 8.0)], -1)
+    logits = normal(seed, tag + ".logits", (n, num_obj_cls), 0.0, 1.5).astype(np.float64)
+    main = integers(seed, tag + ".main", (k,), 1, num_obj_cls)
+    alt = integers(seed, tag + ".alt", (k,), 1, num_obj_cls)
+    logits[np.arange(n), main[cl]] += uniform(seed, tag + ".boost", (n,), 2.0, 6.0)
+    logits[np.arange(n), alt[cl]] += uniform(seed, tag + ".boost2", (n,), 1.0, 5.0)
+    logits = logits.astype(np.float32)
+    pred_labels = logits[:, 1:].argmax(1).astype(np.int64) + 1
+    return {"boxes_per_cls": bpc.astype(np.float32), "predict_logits": logits, "pred_labels": pred_labels,
+            "pred_scores": uniform(seed, tag + ".score", (n,), 0.05, 1.0),
+            "boxes": bpc[np.arange(n), pred_labels].astype(np.float32), "image_size": (W, H)}
+
+
+def synthetic_detections_iou_tie(num_obj_cls=151):
+    """Three detections whose class-5 boxes overlap at IoU exactly 0.5 and 0.25 (nms_overlaps arithmetic, +1 convention):
+    box 0 = [0, 0, 9, 9] (area 100), box 1 = [0, 0, 9, 4] (inter 50, union 100), box 2 = [0, 5, 9, 9] (IoU 0.5 with box 0,
+    0 with box 1).  Class 5 wins every row, rows in decreasing order of confidence."""
+    n, C = 3, num_obj_cls
+    base = np.array([[0, 0, 9, 9], [0, 0, 9, 4], [0, 5, 9, 9]], np.float64)
+    bpc = np.repeat(base[:, None, :], C, 1) + np.arange(C)[None, :, None] * 100.0 * (np.arange(C) != 5)[None, :, None]
+    logits = np.zeros((n, C), np.float64)
+    logits[:, 5] = [6.0, 5.0, 4.0]
+    logits[:, 7] = 3.0
+    return {"boxes_per_cls": bpc.astype(np.float32), "predict_logits": logits.astype(np.float32),
+            "pred_labels": np.full(n, 5, np.int64), "pred_scores": np.array([0.9, 0.8, 0.7], np.float32),
+            "boxes": base.astype(np.float32), "image_size": (16, 16)}
+
+
+def synthetic_eval_images_sgdet(seed, num_objs, num_rel_cls=51):
+    """sgdet evaluator inputs: the GT side of synthetic_eval_images(seed, num_objs, 'sgcls') with predictions on the
+    detector's OWN objects -- a jittered copy of most GT boxes (shifts of up to a quarter of the box, so the IoUs with
+    their GT box spread around 0.5), in shuffled order, plus a few spurious boxes; their count differs from the GT count.
+    Pairs are all ordered pairs of predicted objects sorted by triple score."""
+    base, zeroshot = synthetic_eval_images(seed, num_objs, "sgcls", num_rel_cls=num_rel_cls)
+    images = []
+    for i, im in enumerate(base):
+        tag = "eval_sgdet.%d." % i
+        gtb, gtc = im["gt_boxes"].astype(np.float64), im["gt_classes"]
+        n = len(gtb)
+        keep = np.nonzero(uniform01(seed, tag + "keep", n) < 0.8)[0]
+        n_extra = int(integers(seed, tag + "extra", (1,), 1, 4)[0])
+        wh = np.concatenate([gtb[:, 2:] - gtb[:, :2]] * 2, 1)
+        shift = (uniform(seed, tag + "shift", (n, 4), -0.25, 0.25).astype(np.float64) * wh)[keep]
+        boxes = gtb[keep] + shift
+        xy = uniform(seed, tag + "xy", (n_extra, 2), 0.0, 300.0).astype(np.float64)
+        ewh = uniform(seed, tag + "wh", (n_extra, 2), 30.0, 160.0).astype(np.float64)
+        boxes = np.concatenate([boxes, np.concatenate([xy, xy + ewh], 1)], 0)
+        src = np.concatenate([keep, -np.ones(n_extra, np.int64)])
+        flip = uniform01(seed, tag + "flip", len(src)) < 0.15
+        alt = integers(seed, tag + "alt", (len(src),), 1, 21)
+        classes = np.where((src >= 0) & ~flip, gtc[np.maximum(src, 0)], alt)
+        perm = np.argsort(uniform01(seed, tag + "perm", len(src)), kind="stable")
+        boxes, classes, src = boxes[perm], classes[perm], src[perm]
+        m = len(src)
+        pairs = np.array([(a, b) for a in range(m) for b in range(m) if a != b], dtype=np.int64).reshape(-1, 2)
+        w = uniform01(seed, tag + "w", len(pairs) * num_rel_cls).reshape(len(pairs), num_rel_cls) ** 3
+        boost = uniform01(seed, tag + "boost", len(im["gt_rels"]))
+        where = {int(s): k for k, s in enumerate(src) if s >= 0}
+        row_of = {(int(a), int(b)): r for r, (a, b) in enumerate(pairs)}
+        for g, (s, o, r) in enumerate(im["gt_rels"]):
+            if boost[g] < 0.7 and int(s) in where and int(o) in where:
+                w[row_of[(where[int(s)], where[int(o)])], int(r)] += 1.0 + 2.0 * boost[g]
+        rel_scores = (w / w.sum(1, keepdims=True)).astype(np.float32)
+        obj_scores = uniform(seed, tag + "objs", (m,), 0.3, 1.0)
+        triple = rel_scores[:, 1:].max(1) * obj_scores[pairs[:, 0]] * obj_scores[pairs[:, 1]]
+        srt = np.argsort(-triple, kind="stable")
+        images.append({"gt_rels": im["gt_rels"], "gt_classes": gtc, "gt_boxes": im["gt_boxes"],
+                       "pred_rel_inds": pairs[srt], "rel_scores": rel_scores[srt], "pred_classes": classes.astype(np.int64),
+                       "pred_boxes": boxes.astype(np.float32), "obj_scores": obj_scores})
+    return images, zeroshot
