@@ -12,6 +12,7 @@
  *                             Ensemble.forward (MEET, eval)     roi_relation_predictors.py:3752-3853
  *   veto_enumerate_pairs   <- RelationSampling.prepare_test_pairs   sampling.py:31-52 (GT-box branch)
  *   veto_prepare_test_pairs <- the same, sgdet branch (box-overlap filter, capped pair order)   sampling.py:31-52
+ *   veto_detect_relsample  <- RelationSampling.detect_relsample (sgdet training)   sampling.py:109-309
  *   veto_obj_decode        <- obj_prediction_nms (PostProcessor)    utils_relation.py:94-128, inference.py:410-429
  *                             Ensemble.nms_per_cls (MEET decoder)   roi_relation_predictors.py:3855-3874
  *
@@ -298,6 +299,61 @@ typedef struct veto_pair_args {
 } veto_pair_args_t;
 
 int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* args);
+
+/* veto_detect_relsample: RelationSampling.detect_relsample (sampling.py:109-176) with motif_rel_fg_bg_sampling (:179-309),
+ * the training-time relation sampler on detected boxes, for a ragged batch (one workgroup per image).  Per image:
+ *   ious = boxlist_iou(target, proposal) (TO_REMOVE 1); is_match = same label & iou > fg_thres; locating_match[p] = 1 if
+ *   any target has iou > fg_thres.  Candidates: every ordered pair i != j, or 0 < boxlist_iou(p_i, p_j) < 1 with
+ *   require_overlap (REQUIRE_BOX_OVERLAP); rows and columns of proposals labelled 0 cleared.
+ *   Foreground, GT relations in nonzero(relation) order: (matches of h) x (matches of t), head-major, self-pairs removed,
+ *   all of them removed from the candidates; above num_sample_per_gt_rel that many drawn without replacement with
+ *   probability proportional to iou[h, p_h] * iou[t, p_t], in draw order (npr.choice).  binary_rel (symmetric, self
+ *   entries included) gets (head matches) x (tail matches).  Above max_fg_per_image triplets, a uniformly random
+ *   max_fg_per_image of them in random order.
+ *   Background: num_neg = min(batch_size_per_image - n_fg, n_bg) of the window of the first 2 * num_neg remaining
+ *   candidates by (pred_scores[s] * pred_scores[o] desc, row-major index asc), uniformly at random, in random order.
+ *   No foreground and no background: two (0, 0, 0) rows.
+ *   labels_all (with relation_non_masked, :160-167): for each triplet relation i before the cap, the label of
+ *   nonzero(relation_non_masked)[i]; then zeros for the background rows.  counts[4 * img + 3] bit 0 reports an index i
+ *   past the end of that list.
+ * Randomness: a counter-based hash of (seed, image index, purpose, element): an image's rows depend only on the seed,
+ * its index and its own inputs.  The draws follow the reference's distributions, not its RNG streams.
+ * Rows: image i writes pairs / labels from row i * R, R = max(batch_size_per_image, 2), counts[4 * i] rows of them,
+ * foreground first; labels_all from row img_rel_offset[i] * num_sample_per_gt_rel + i * R, counts[4 * i + 1] foreground
+ * entries then counts[4 * i] - counts[4 * i + 2] zeros. */
+typedef struct veto_detect_relsample_args {
+  int32_t struct_size;
+  int32_t n_img, n_prp, n_tgt;
+  int32_t n_rel_cells;                /* sum of T_i^2: img_rel_offset[n_img] */
+  int32_t max_prp_per_image;          /* host-side maxima of the per-image counts, 0..256 (DETECTIONS_PER_IMG) */
+  int32_t max_tgt_per_image;          /* 0..256 */
+  int32_t require_overlap;            /* MODEL.ROI_RELATION_HEAD.REQUIRE_BOX_OVERLAP */
+  int32_t num_sample_per_gt_rel;      /* NUM_SAMPLE_PER_GT_REL, 1..16 */
+  int32_t batch_size_per_image;       /* BATCH_SIZE_PER_IMAGE, 1..2048 */
+  int32_t max_fg_per_image;           /* int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION), 0..batch_size_per_image */
+  float fg_thres;                     /* MODEL.ROI_HEADS.FG_IOU_THRESHOLD */
+  uint64_t seed;
+  const float* prp_boxes;             /* device [n_prp, 4] xyxy */
+  const int64_t* prp_labels;          /* device [n_prp] ('labels') */
+  const float* prp_scores;            /* device [n_prp] ('pred_scores') */
+  const float* tgt_boxes;             /* device [n_tgt, 4] xyxy */
+  const int64_t* tgt_labels;          /* device [n_tgt] */
+  const int64_t* relation;            /* device: image i [T_i, T_i] row-major from img_rel_offset[i] */
+  const int64_t* relation_non_masked; /* optional, same layout; NULL: labels_all is not written */
+  const int32_t* img_prp_offset;      /* device [n_img + 1] */
+  const int32_t* img_tgt_offset;      /* device [n_img + 1] */
+  const int32_t* img_rel_offset;      /* device [n_img + 1]: prefix sums of T_i^2 */
+  const int32_t* img_binary_offset;   /* device [n_img + 1]: prefix sums of P_i^2 */
+  int64_t* pairs;                     /* out device [n_img * R, 2] */
+  int64_t* labels;                    /* out device [n_img * R] */
+  int64_t* labels_all;                /* optional out device [n_rel_cells * num_sample_per_gt_rel + n_img * R] */
+  int64_t* binary_rel;                /* out device: image i [P_i, P_i] from img_binary_offset[i] */
+  float* locating_match;              /* out device [n_prp] */
+  int32_t* counts;                    /* out device [n_img, 4]: rows, foreground before the cap, foreground kept, status */
+} veto_detect_relsample_args_t;
+
+size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel);
+int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

@@ -79,4 +79,7 @@ def default_config():
     # the "mixed" mode and leave them in predictor.last_saturation (diagnostic: slower, synchronises the stream)
     c.VETO_AMD.COUNT_SATURATION = False
     c.VETO_AMD.TRAIN_FORWARD_ONLY = False         # True: .train() runs the forward + losses (no backward exists yet)
+    # True: training on detected boxes (USE_GT_BOX False) samples its relation pairs with veto_detect_relsample, which has the
+    # distribution of the reference's detect_relsample but not its draws for a given seed; False: sgdet training raises
+    c.VETO_AMD.DEVICE_DETECT_RELSAMPLE = False
     return c

@@ -314,6 +314,36 @@ struct PairArgs {
 int prepare_pairs_max_pairs();
 hipError_t launch_prepare_pairs(const PairArgs& a, hipStream_t s);
 
+// ---- sgdet training: detected-box relation sampling (relsample.hip) ---------------------------------
+struct RelSampleArgs {
+  const float* prp_boxes;        // [n_prp, 4] xyxy
+  const int64_t* prp_labels;     // [n_prp]
+  const float* prp_scores;       // [n_prp] pred_scores
+  const float* tgt_boxes;        // [n_tgt, 4] xyxy
+  const int64_t* tgt_labels;     // [n_tgt]
+  const int64_t* relation;       // image i: [T_i, T_i] row-major from rel_off[i]
+  const int64_t* relation_nm;    // optional, same layout ('relation_non_masked')
+  const int32_t* prp_off;        // [n_img + 1]
+  const int32_t* tgt_off;        // [n_img + 1]
+  const int32_t* rel_off;        // [n_img + 1]: prefix sums of T_i^2
+  const int32_t* bin_off;        // [n_img + 1]: prefix sums of P_i^2
+  int n_img, require_overlap, per_rel, max_fg, batch, out_rows;
+  float fg_thres;
+  uint64_t seed;
+  int64_t* ws_nm;                // [rel_off[n_img]]: labels of relation_nm's nonzeros in row-major order
+  uint32_t* ws_fg;               // [rel_off[n_img] * per_rel]: foreground triplets before the cap
+  int64_t* pairs;                // out [n_img * out_rows, 2]
+  int64_t* labels;               // out [n_img * out_rows]
+  int64_t* labels_all;           // optional out: image i from rel_off[i] * per_rel + i * out_rows
+  int64_t* binary;               // out: image i [P_i, P_i] from bin_off[i]
+  float* locating;               // out [n_prp]
+  int32_t* counts;               // out [n_img, 4]: rows, foreground before the cap, foreground kept, status
+};
+int relsample_max_objects();
+int relsample_max_batch();
+int relsample_max_per_rel();
+hipError_t launch_detect_relsample(const RelSampleArgs& a, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

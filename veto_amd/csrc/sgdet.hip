@@ -27,6 +27,7 @@
 //   [[0, 0]] when no pair is left.
 #include "common.h"
 #include "kernels.h"
+#include "selection.h"
 
 #pragma clang fp contract(off)   // the IoUs follow the reference operation for operation: a last-ulp change flips suppressions
 
@@ -184,44 +185,8 @@ __global__ __launch_bounds__(256) void obj_decode_kernel(ObjDecodeArgs a) {
 
 // ---- test pairs ------------------------------------------------------------------------------------
 
-// boxlist_iou(p, p)[i, j] > 0 (boxlist_ops.py:54-89): lt/rb, wh = clamp(rb - lt + 1, 0), inter / (area_i + area_j - inter)
-__device__ __forceinline__ bool boxes_overlap(const float* bi, const float* bj) {
-  const float w = fmaxf((fminf(bi[2], bj[2]) - fmaxf(bi[0], bj[0])) + 1.f, 0.f);
-  const float h = fmaxf((fminf(bi[3], bj[3]) - fmaxf(bi[1], bj[1])) + 1.f, 0.f);
-  const float inter = w * h;
-  const float area_i = ((bi[2] - bi[0]) + 1.f) * ((bi[3] - bi[1]) + 1.f);
-  const float area_j = ((bj[2] - bj[0]) + 1.f) * ((bj[3] - bj[1]) + 1.f);
-  return inter / ((area_i + area_j) - inter) > 0.f;
-}
-
-// order-preserving map of a float onto uint32 (larger float -> larger key)
-__device__ __forceinline__ uint32_t float_order(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// block-wide (256 threads) exclusive prefix sum; returns this thread's prefix, *total gets the sum
-__device__ __forceinline__ int block_exclusive_scan(int v, int* s_wave, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[wave] = x;
-  __syncthreads();
-  int base = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const int t = s_wave[w];
-    if (w < wave) base += t;
-    sum += t;
-  }
-  __syncthreads();   // s_wave is reused by the next call
-  *total = sum;
-  return base + x - v;
-}
+// boxlist_iou(p, p)[i, j] > 0 (boxlist_ops.py:54-89)
+__device__ __forceinline__ bool boxes_overlap(const float* bi, const float* bj) { return boxlist_iou(bi, bj) > 0.f; }
 
 __global__ __launch_bounds__(256) void prepare_pairs_kernel(PairArgs a) {
   __shared__ float s_box[kMaxObj][4];

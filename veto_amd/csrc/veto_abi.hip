@@ -1663,6 +1663,59 @@ int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* a) {
   return VETO_OK;
 }
 
+size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel) {
+  if (n_rel_cells <= 0 || num_sample_per_gt_rel <= 0) return 256;
+  return align_up((size_t)n_rel_cells * 8, 256) + align_up((size_t)n_rel_cells * num_sample_per_gt_rel * 4, 256);
+}
+
+int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_detect_relsample_args_t))
+    return fail(VETO_ERR_INVALID, "veto_detect_relsample_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_prp < 0 || a->n_tgt < 0 || a->n_rel_cells < 0)
+    return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d, n_tgt %d, n_rel_cells %d)", a->n_img, a->n_prp, a->n_tgt,
+                a->n_rel_cells);
+  const int lim = relsample_max_objects();
+  if (a->max_prp_per_image < 0 || a->max_prp_per_image > lim)
+    return fail(VETO_ERR_INVALID, "max_prp_per_image %d outside 0..%d (detections per image, DETECTIONS_PER_IMG)",
+                a->max_prp_per_image, lim);
+  if (a->max_tgt_per_image < 0 || a->max_tgt_per_image > lim)
+    return fail(VETO_ERR_INVALID, "max_tgt_per_image %d outside 0..%d (GT boxes per image)", a->max_tgt_per_image, lim);
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > relsample_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                relsample_max_batch());
+  if (a->num_sample_per_gt_rel < 1 || a->num_sample_per_gt_rel > relsample_max_per_rel())
+    return fail(VETO_ERR_INVALID, "num_sample_per_gt_rel %d outside 1..%d (NUM_SAMPLE_PER_GT_REL)", a->num_sample_per_gt_rel,
+                relsample_max_per_rel());
+  if (a->max_fg_per_image < 0 || a->max_fg_per_image > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "max_fg_per_image %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)",
+                a->max_fg_per_image, a->batch_size_per_image);
+  if ((a->n_prp > 0 && (!a->prp_boxes || !a->prp_labels || !a->prp_scores || !a->locating_match)) ||
+      (a->n_tgt > 0 && (!a->tgt_boxes || !a->tgt_labels)) || (a->n_rel_cells > 0 && !a->relation) ||
+      (a->relation_non_masked && !a->labels_all) || !a->img_prp_offset || !a->img_tgt_offset || !a->img_rel_offset ||
+      !a->img_binary_offset || !a->pairs || !a->labels || !a->binary_rel || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  const size_t need = veto_detect_relsample_workspace_bytes(a->n_rel_cells, a->num_sample_per_gt_rel);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
+                                                        workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  RelSampleArgs p{};
+  p.prp_boxes = a->prp_boxes; p.prp_labels = a->prp_labels; p.prp_scores = a->prp_scores;
+  p.tgt_boxes = a->tgt_boxes; p.tgt_labels = a->tgt_labels;
+  p.relation = a->relation; p.relation_nm = a->relation_non_masked;
+  p.prp_off = a->img_prp_offset; p.tgt_off = a->img_tgt_offset; p.rel_off = a->img_rel_offset; p.bin_off = a->img_binary_offset;
+  p.n_img = a->n_img; p.require_overlap = a->require_overlap != 0; p.per_rel = a->num_sample_per_gt_rel;
+  p.max_fg = a->max_fg_per_image; p.batch = a->batch_size_per_image;
+  p.out_rows = a->batch_size_per_image > 2 ? a->batch_size_per_image : 2;
+  p.fg_thres = a->fg_thres; p.seed = a->seed;
+  p.ws_nm = (int64_t*)workspace;
+  p.ws_fg = (uint32_t*)((char*)workspace + align_up((size_t)a->n_rel_cells * 8, 256));
+  p.pairs = a->pairs; p.labels = a->labels; p.labels_all = a->relation_non_masked ? a->labels_all : nullptr;
+  p.binary = a->binary_rel; p.locating = a->locating_match; p.counts = a->counts;
+  HIP_TRY(launch_detect_relsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 // shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
 static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
   if (!a) return fail(VETO_ERR_INVALID, "null argument");

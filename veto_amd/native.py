@@ -21,6 +21,7 @@ EXPORTS = [
     "veto_profile_reset", "veto_debug_gemm", "veto_debug_gemm_workspace_bytes", "veto_debug_gemm_forms", "veto_debug_ffn", "veto_debug_ffn_workspace_bytes", "veto_debug_outproj", "veto_debug_outproj_workspace_bytes", "veto_debug_layer_tail", "veto_debug_layer_tail_workspace_bytes", "veto_debug_qkv_attn", "veto_debug_qkv_attn_workspace_bytes",
     "veto_postprocess", "veto_postprocess_workspace_bytes", "veto_postprocess_meet", "veto_postprocess_vote",
     "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
+    "veto_detect_relsample", "veto_detect_relsample_workspace_bytes",
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
@@ -79,6 +80,17 @@ class VetoPairArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_obj", "max_obj_per_image", "max_pairs",
                                        "require_overlap")] + \
                [(n, c_void_p) for n in ("boxes", "scores", "img_obj_offset", "img_out_offset", "pairs", "counts")]
+
+
+class VetoDetectRelsampleArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_prp", "n_tgt", "n_rel_cells", "max_prp_per_image",
+                                       "max_tgt_per_image", "require_overlap", "num_sample_per_gt_rel",
+                                       "batch_size_per_image", "max_fg_per_image")] + \
+               [("fg_thres", ctypes.c_float), ("seed", ctypes.c_uint64)] + \
+               [(n, c_void_p) for n in ("prp_boxes", "prp_labels", "prp_scores", "tgt_boxes", "tgt_labels", "relation",
+                                        "relation_non_masked", "img_prp_offset", "img_tgt_offset", "img_rel_offset",
+                                        "img_binary_offset", "pairs", "labels", "labels_all", "binary_rel",
+                                        "locating_match", "counts")]
 
 
 class VetoPostMeetArgs(Structure):
@@ -189,6 +201,9 @@ def load_library():
     lib.veto_obj_decode_workspace_bytes.restype = c_size_t
     lib.veto_obj_decode.argtypes = [c_void_p, POINTER(VetoObjDecodeArgs), c_void_p, c_size_t]
     lib.veto_prepare_test_pairs.argtypes = [c_void_p, POINTER(VetoPairArgs)]
+    lib.veto_detect_relsample_workspace_bytes.argtypes = [c_int32, c_int32]
+    lib.veto_detect_relsample_workspace_bytes.restype = c_size_t
+    lib.veto_detect_relsample.argtypes = [c_void_p, POINTER(VetoDetectRelsampleArgs), c_void_p, c_size_t]
     lib.veto_train_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
     lib.veto_train_workspace_bytes.restype = c_size_t
     lib.veto_grad_floats.argtypes = [c_void_p]

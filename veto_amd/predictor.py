@@ -624,17 +624,15 @@ class VETOPredictor_MEET(nn.Module, _NativeForward):
             dist_labels = labels
         else:
             dist_labels = _cat_field(proposals, "pred_labels").detach().long()
-            if self.mode == "sgdet":
-                if self.training:
-                    raise NotImplementedError("veto_amd: MEET training on detected boxes (detect_relsample, sampling.py:109-) "
-                                              "is not built")
+            if self.mode == "sgdet" and not self.training:
                 # :3778-3781: the decoder's class-aware NMS over softmax(one_hot(pred_labels)), on the device
                 from .sgdet import decode_objects
                 boxes_per_cls = torch.cat([p.get_field("boxes_per_cls").reshape(len(p), -1, 4) for p in proposals], 0)
                 labels, _, _ = decode_objects(dist_labels, boxes_per_cls.to(dist_labels.device), [len(p) for p in proposals],
                                               self.nms_thresh, mode="meet", want_scores=False, want_boxes=False)
             else:
-                # obj_dists[:, 1:].max(1)[1] + 1 over a one-hot (:3776-3784): the label itself, or 1 for label 0
+                # obj_dists[:, 1:].max(1)[1] + 1 over a one-hot (:3776-3784): the label itself, or 1 for label 0 (sgcls, and
+                # sgdet in training, where the reference skips the decoder NMS)
                 labels = torch.where(dist_labels > 0, dist_labels, torch.ones_like(dist_labels))
         if self.training:
             # :3930-3969 expert sampling, :3806-3846 group label remap + per-group CE

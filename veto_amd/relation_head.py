@@ -14,7 +14,9 @@ test mode with GT boxes:
 and for sgdet (USE_GT_BOX False) at test time: the proposals are the detector's (fields predict_logits, pred_labels,
 pred_scores, boxes_per_cls), the pairs come from the detected-box branch of prepare_test_pairs (TEST.RELATION.REQUIRE_OVERLAP
 filter, capped by pred_scores products), and the post-processor decodes the objects with the class-aware NMS.
-Training on detected boxes (detect_relsample) is not built.
+Training on detected boxes (:112-131 with samp_processor.detect_relsample) runs when VETO_AMD.DEVICE_DETECT_RELSAMPLE is set:
+the pairs and labels come from veto_amd.sampling.DetectRelationSampler (one veto_detect_relsample launch per batch), which
+has the reference sampler's distribution but not its draws for a given seed.
 Everything numeric runs in libveto_amd.so; this file only moves fields around."""
 import torch
 from torch import nn
@@ -63,6 +65,8 @@ class VETORelationHead(nn.Module):
         self.samp_processor = samp_processor if samp_processor is not None else _host_samp_processor(cfg)
         self.num_obj_cls = self.predictor.num_obj_cls
         self.max_proposal_pairs = int(getattr(rh, "MAX_PROPOSAL_PAIR", 2048))
+        self.device_detect_relsample = bool(getattr(getattr(cfg, "VETO_AMD", None), "DEVICE_DETECT_RELSAMPLE", False))
+        self._detect_sampler = None
 
     def forward(self, features, proposals, depth_features=None, targets=None, logger=None, x=None):
         """The reference's signature, parameter for parameter (relation_head.py:90; called as `self.relation(features,
@@ -73,24 +77,35 @@ class VETORelationHead(nn.Module):
         if depth_features is None:
             raise ValueError("the VETO predictors need depth_features (relation_head.py:141)")
         if self.training:
-            if not self.use_gt_box:
+            if not self.use_gt_box and not self.device_detect_relsample:
                 raise NotImplementedError("veto_amd: training on detected boxes (sgdet relation sampling, "
-                                          "samp_processor.detect_relsample, sampling.py:109-) is not built")
-            # :112-121 GT-box relation sampling, :140-141 ROI features, :196-203 predictor -> losses, :247 return
+                                          "samp_processor.detect_relsample, sampling.py:109-) runs only on the device "
+                                          "sampler: set VETO_AMD.DEVICE_DETECT_RELSAMPLE = True")
+            # :112-121 relation sampling, :140-141 ROI features, :196-203 predictor -> losses, :247 return
             if targets is None:
                 raise ValueError("training needs the targets (GT BoxLists with a 'relation' matrix)")
+            if not self.use_gt_box:
+                if self._detect_sampler is None:
+                    from .sampling import DetectRelationSampler
+                    self._detect_sampler = DetectRelationSampler.from_config(self.cfg)
+                with torch.no_grad():
+                    proposals, rel_labels, _, rel_pair_idxs, _ = self._detect_sampler.detect_relsample(proposals, targets)
+                return self._train_tail(features, proposals, depth_features, rel_pair_idxs, rel_labels, logger)
             if self.samp_processor is None:
                 raise ValueError("training needs a relation sampler: pysgg's make_roi_relation_samp_processor(cfg) could not be "
                                  "imported in this process; pass VETORelationHead(cfg, in_channels, samp_processor=...)")
             self._overload_predcls_fields(proposals, features[0].device)
             with torch.no_grad():
                 proposals, rel_labels, rel_pair_idxs, _ = self.samp_processor.gtbox_relsample(proposals, targets)
-            roi_features, d_2d, _, _ = self.box_feature_extractor(features, proposals, depth_features=depth_features)
-            _, _, add_losses, _, _, _ = self.predictor(proposals, rel_pair_idxs, rel_labels, logger, roi_features=roi_features,
-                                                       roi_depth_features=d_2d)
-            return roi_features, proposals, add_losses
+            return self._train_tail(features, proposals, depth_features, rel_pair_idxs, rel_labels, logger)
         roi_features, d_2d, _, _ = self.box_feature_extractor(features, proposals, depth_features=depth_features)
         return self.forward_pooled(proposals, roi_features, d_2d, logger)
+
+    def _train_tail(self, features, proposals, depth_features, rel_pair_idxs, rel_labels, logger):
+        roi_features, d_2d, _, _ = self.box_feature_extractor(features, proposals, depth_features=depth_features)
+        _, _, add_losses, _, _, _ = self.predictor(proposals, rel_pair_idxs, rel_labels, logger, roi_features=roi_features,
+                                                   roi_depth_features=d_2d)
+        return roi_features, proposals, add_losses
 
     def _overload_predcls_fields(self, proposals, device):
         if self.mode != "predcls":

@@ -400,3 +400,58 @@ def synthetic_eval_images_sgdet(seed, num_objs, num_rel_cls=51):
                        "pred_rel_inds": pairs[srt], "rel_scores": rel_scores[srt], "pred_classes": classes.astype(np.int64),
                        "pred_boxes": boxes.astype(np.float32), "obj_scores": obj_scores})
     return images, zeroshot
+
+
+def synthetic_relsample_image(seed, n_gt, n_det, n_rel, num_obj_cls=151, num_rel_cls=51, max_copies=5, twin=False,
+                              clutter_bg=0.6, n_extra_non_masked=3, W=800, H=600):
+    """One training image for the detected-box relation sampler (detect_relsample): `n_gt` GT boxes with labels and a
+    relation matrix of `n_rel` distinct ordered pairs, `relation_non_masked` = that matrix plus `n_extra_non_masked` more
+    nonzero entries, and `n_det` detections: 0..max_copies jittered copies of every GT box (mostly with its label, so they
+    match it at IoU > 0.5), then clutter anywhere, labelled 0 with probability `clutter_bg`; shuffled.  twin=True makes GT
+    box 1 a shifted copy of box 0 with its label, so the copies of box 0 match both."""
+    tag = "relsample.%d.%d.%d" % (n_gt, n_det, n_rel)
+    cx = uniform(seed, tag + ".cx", (n_gt,), 0.1 * W, 0.9 * W).astype(np.float64)
+    cy = uniform(seed, tag + ".cy", (n_gt,), 0.1 * H, 0.9 * H).astype(np.float64)
+    bw = uniform(seed, tag + ".w", (n_gt,), 40.0, 260.0).astype(np.float64)
+    bh = uniform(seed, tag + ".h", (n_gt,), 40.0, 220.0).astype(np.float64)
+    gt = np.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], 1)
+    gt_lab = integers(seed, tag + ".gt_lab", (n_gt,), 1, num_obj_cls)
+    if twin and n_gt > 1:
+        gt[1] = gt[0] + np.array([6.0, 4.0, 6.0, 4.0])
+        gt_lab[1] = gt_lab[0]
+    copies = integers(seed, tag + ".copies", (n_gt,), 0, max_copies + 1)
+    src = np.repeat(np.arange(n_gt), copies)[:n_det]
+    m = len(src)
+    jit = normal(seed, tag + ".jit", (m, 4), 0.0, 6.0).astype(np.float64)
+    det = gt[src] + jit
+    relabel = uniform01(seed, tag + ".relabel", m) < 0.15
+    det_lab = np.where(relabel, integers(seed, tag + ".wrong", (m,), 0, num_obj_cls), gt_lab[src])
+    k = n_det - m
+    ccx = uniform(seed, tag + ".ccx", (k,), 0.0, W).astype(np.float64)
+    ccy = uniform(seed, tag + ".ccy", (k,), 0.0, H).astype(np.float64)
+    cw = uniform(seed, tag + ".cw", (k,), 20.0, 300.0).astype(np.float64)
+    ch = uniform(seed, tag + ".ch", (k,), 20.0, 300.0).astype(np.float64)
+    clutter = np.stack([ccx - cw / 2, ccy - ch / 2, ccx + cw / 2, ccy + ch / 2], 1)
+    clutter_lab = np.where(uniform01(seed, tag + ".bg", k) < clutter_bg, 0, integers(seed, tag + ".clab", (k,), 1, num_obj_cls))
+    boxes = np.concatenate([det, clutter], 0)
+    labels = np.concatenate([det_lab, clutter_lab]).astype(np.int64)
+    order = np.argsort(uniform01(seed, tag + ".shuffle", n_det), kind="stable")
+    boxes, labels = boxes[order], labels[order]
+    x1y1 = np.maximum(boxes[:, :2], 0.0)
+    boxes = np.concatenate([x1y1, np.maximum(boxes[:, 2:], x1y1 + 4.0)], 1)
+
+    def pick_pairs(name, count, exclude=()):
+        flat = [f for f in np.argsort(uniform01(seed, name, n_gt * n_gt), kind="stable")
+                if f // n_gt != f % n_gt and f not in exclude]
+        return np.asarray(flat[:count], np.int64)
+
+    rel = np.zeros(n_gt * n_gt, np.int64)
+    chosen = pick_pairs(tag + ".rel", n_rel)
+    rel[chosen] = integers(seed, tag + ".rel_lab", (len(chosen),), 1, num_rel_cls)
+    non_masked = rel.copy()
+    extra = pick_pairs(tag + ".extra", n_extra_non_masked, exclude=set(chosen.tolist()))
+    non_masked[extra] = integers(seed, tag + ".extra_lab", (len(extra),), 1, num_rel_cls)
+    return {"prp_boxes": boxes.astype(np.float32), "prp_labels": labels,
+            "pred_scores": uniform(seed, tag + ".score", (n_det,), 0.05, 1.0),
+            "tgt_boxes": gt.astype(np.float32), "tgt_labels": gt_lab.astype(np.int64),
+            "relation": rel.reshape(n_gt, n_gt), "relation_non_masked": non_masked.reshape(n_gt, n_gt), "image_size": (W, H)}
