@@ -13,6 +13,7 @@
  *   veto_enumerate_pairs   <- RelationSampling.prepare_test_pairs   sampling.py:31-52 (GT-box branch)
  *   veto_prepare_test_pairs <- the same, sgdet branch (box-overlap filter, capped pair order)   sampling.py:31-52
  *   veto_detect_relsample  <- RelationSampling.detect_relsample (sgdet training)   sampling.py:109-309
+ *   veto_gtbox_relsample   <- RelationSampling.gtbox_relsample (predcls / sgcls training)   sampling.py:54-107
  *   veto_obj_decode        <- obj_prediction_nms (PostProcessor)    utils_relation.py:94-128, inference.py:410-429
  *                             Ensemble.nms_per_cls (MEET decoder)   roi_relation_predictors.py:3855-3874
  *
@@ -354,6 +355,38 @@ typedef struct veto_detect_relsample_args {
 
 size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel);
 int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_gtbox_relsample: RelationSampling.gtbox_relsample (sampling.py:54-107), the training-time relation sampler on GT
+ * boxes (predcls, sgcls), for a ragged batch (one workgroup per image, one launch).  Per image, n objects:
+ *   Foreground candidates: the entries relation > 0 in row-major (torch.nonzero) order, label = the entry.  At most
+ *   num_pos_per_img of them: all, in that order.  More: a uniformly random num_pos_per_img of them in random order.
+ *   Background candidates: every ordered pair (i, j), i != j, whose relation[i, j] is not > 0.
+ *   min(candidates, batch_size_per_image - foreground rows) of them, a uniformly random subset in random order, label 0.
+ *   binary_rel: 1 at (head, tail) and (tail, head) of every entry relation > 0, before the cap.
+ * Randomness: every candidate gets the upper 32 bits of a counter-based hash of (seed, image index, purpose, row-major
+ * cell index); a random subset of size k is the k smallest (hash, cell index), written in ascending order.  An image's rows
+ * depend only on the seed, its index and its own matrix.  The draws follow the reference's distributions, not its RNG
+ * streams.
+ * Rows: image i writes pairs / labels from row i * batch_size_per_image: counts[2 * i] foreground rows, then
+ * counts[2 * i + 1] background rows.  No workspace; the call runs on `stream` and never synchronises. */
+typedef struct veto_gtbox_relsample_args {
+  int32_t struct_size;
+  int32_t n_img;
+  int32_t n_rel_cells;                /* sum of n_i^2: img_rel_offset[n_img] */
+  int32_t max_obj_per_image;          /* host-side maximum of n_i, 0..256 */
+  int32_t batch_size_per_image;       /* BATCH_SIZE_PER_IMAGE, 1..2048 */
+  int32_t num_pos_per_img;            /* int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION), 0..batch_size_per_image */
+  uint64_t seed;
+  const int64_t* relation;            /* device: image i [n_i, n_i] row-major from img_rel_offset[i] */
+  const int32_t* img_obj_offset;      /* device [n_img + 1]: prefix sums of n_i */
+  const int32_t* img_rel_offset;      /* device [n_img + 1]: prefix sums of n_i^2 */
+  int64_t* pairs;                     /* out device [n_img * batch_size_per_image, 2] */
+  int64_t* labels;                    /* out device [n_img * batch_size_per_image] */
+  int64_t* binary_rel;                /* out device: image i [n_i, n_i] from img_rel_offset[i] */
+  int32_t* counts;                    /* out device [n_img, 2]: foreground rows, background rows */
+} veto_gtbox_relsample_args_t;
+
+int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* args);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

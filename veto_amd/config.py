@@ -82,4 +82,8 @@ def default_config():
     # True: training on detected boxes (USE_GT_BOX False) samples its relation pairs with veto_detect_relsample, which has the
     # distribution of the reference's detect_relsample but not its draws for a given seed; False: sgdet training raises
     c.VETO_AMD.DEVICE_DETECT_RELSAMPLE = False
+    # True: training on GT boxes (USE_GT_BOX True: predcls, sgcls) samples its relation pairs with veto_gtbox_relsample, which
+    # has the distribution of the reference's gtbox_relsample but not its draws for a given seed, and needs no samp_processor;
+    # False: the head uses the host code base's sampler (or an explicit one) as before
+    c.VETO_AMD.DEVICE_GTBOX_RELSAMPLE = False
     return c

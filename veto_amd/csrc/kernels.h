@@ -344,6 +344,22 @@ int relsample_max_batch();
 int relsample_max_per_rel();
 hipError_t launch_detect_relsample(const RelSampleArgs& a, hipStream_t s);
 
+// ---- predcls / sgcls training: GT-box relation sampling (gtbox_relsample.hip) -------------------------
+struct GtboxRelSampleArgs {
+  const int64_t* relation;       // image i: [n_i, n_i] row-major from rel_off[i]
+  const int32_t* obj_off;        // [n_img + 1]: prefix sums of n_i
+  const int32_t* rel_off;        // [n_img + 1]: prefix sums of n_i^2
+  int n_img, batch, num_pos;
+  uint64_t seed;
+  int64_t* pairs;                // out [n_img * batch, 2]
+  int64_t* labels;               // out [n_img * batch]
+  int64_t* binary;               // out: image i [n_i, n_i] from rel_off[i]
+  int32_t* counts;               // out [n_img, 2]: foreground rows, background rows
+};
+int gtbox_relsample_max_objects();
+int gtbox_relsample_max_batch();
+hipError_t launch_gtbox_relsample(const GtboxRelSampleArgs& a, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

@@ -1,5 +1,6 @@
-// Device helpers shared by the per-image pair kernels of sgdet.hip (test pairs) and relsample.hip (training pairs):
-// the reference's box IoU arithmetic, the order-preserving float key and the block-wide scan of their radix selects.
+// Device helpers shared by the per-image pair kernels of sgdet.hip (test pairs), relsample.hip and gtbox_relsample.hip
+// (training pairs): the reference's box IoU arithmetic, the order-preserving float key, the block-wide scan of their radix
+// selects and, for the two training samplers, the counter-based hash, the radix select and the bitonic sort.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,6 +46,84 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* s_wave, int* tot
   __syncthreads();   // s_wave is reused by the next call
   *total = sum;
   return base + x - v;
+}
+
+// ---- counter-based random numbers and the random-subset machinery of the training samplers (relsample.hip,
+// gtbox_relsample.hip): a random subset of size K is the K elements with the smallest hash, in ascending (hash, index) order
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {   // splitmix64 finaliser
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ uint64_t rng64(uint64_t seed, int img, int purpose, uint32_t elem) {
+  const uint64_t stream = mix64(seed ^ mix64(((uint64_t)(uint32_t)img << 2) | (uint32_t)purpose));
+  return mix64(stream + (uint64_t)elem * 0x9E3779B97F4A7C15ull);
+}
+
+struct SelLds {
+  int hist[256];
+  int wave[4];
+  int digit, need;
+};
+
+// Radix select (8 bits a pass, most significant first) of the K-th largest 32-bit key among the elements `each`
+// visits: each(f) calls f(key) for this thread's elements in element order, threads owning consecutive ranges in
+// thread order.  Keys > T are all among the K; of the keys == T the first `need` in element order.  0 < K < count.
+template <class Each>
+__device__ inline void radix_select(Each each, int K, SelLds& s, uint32_t& T, int& need) {
+  uint32_t prefix = 0, pmask = 0;
+  need = K;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    s.hist[threadIdx.x] = 0;
+    __syncthreads();
+    each([&](uint32_t k) {
+      if ((k & pmask) == prefix) atomicAdd(&s.hist[(k >> shift) & 255], 1);
+    });
+    __syncthreads();
+    const int h = s.hist[255 - threadIdx.x];   // an ascending scan over descending digits
+    int dummy;
+    const int above = block_exclusive_scan(h, s.wave, &dummy);
+    if (above < need && above + h >= need) { s.digit = 255 - threadIdx.x; s.need = need - above; }
+    __syncthreads();
+    prefix |= (uint32_t)s.digit << shift;
+    pmask |= 255u << shift;
+    need = s.need;
+    __syncthreads();
+  }
+  T = prefix;
+}
+
+// this thread's rank among the keys == T (element order): the exclusive scan of its own count
+template <class Each>
+__device__ inline int equal_rank(Each each, uint32_t T, SelLds& s) {
+  int eq = 0;
+  each([&](uint32_t k) { eq += k == T; });
+  int dummy;
+  return block_exclusive_scan(eq, s.wave, &dummy);
+}
+
+// ascending bitonic sort of key[0..cnt) by the whole block; the array is padded to the next power of two with ~0, so it
+// must hold that many elements
+__device__ inline void bitonic_sort(unsigned long long* key, int cnt) {
+  int n2 = 1;
+  while (n2 < cnt) n2 <<= 1;
+  for (int t = cnt + threadIdx.x; t < n2; t += blockDim.x) key[t] = ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < n2; t += blockDim.x) {
+        const int l = t ^ j;
+        if (l > t) {
+          const unsigned long long kt = key[t], kl = key[l];
+          const bool up = (t & k) == 0;
+          if (up ? kt > kl : kt < kl) { key[t] = kl; key[l] = kt; }
+        }
+      }
+      __syncthreads();
+    }
+  }
 }
 
 }  // namespace veto

@@ -1716,6 +1716,31 @@ int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, v
   return VETO_OK;
 }
 
+int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_gtbox_relsample_args_t))
+    return fail(VETO_ERR_INVALID, "veto_gtbox_relsample_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_rel_cells < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_rel_cells %d)", a->n_img, a->n_rel_cells);
+  if (a->max_obj_per_image < 0 || a->max_obj_per_image > gtbox_relsample_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d (GT boxes per image)", a->max_obj_per_image,
+                gtbox_relsample_max_objects());
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > gtbox_relsample_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                gtbox_relsample_max_batch());
+  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
+                a->batch_size_per_image);
+  if ((a->n_rel_cells > 0 && (!a->relation || !a->binary_rel)) || !a->img_obj_offset || !a->img_rel_offset || !a->pairs ||
+      !a->labels || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  GtboxRelSampleArgs p{};
+  p.relation = a->relation; p.obj_off = a->img_obj_offset; p.rel_off = a->img_rel_offset;
+  p.n_img = a->n_img; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img; p.seed = a->seed;
+  p.pairs = a->pairs; p.labels = a->labels; p.binary = a->binary_rel; p.counts = a->counts;
+  HIP_TRY(launch_gtbox_relsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 // shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
 static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
   if (!a) return fail(VETO_ERR_INVALID, "null argument");

@@ -21,7 +21,7 @@ EXPORTS = [
     "veto_profile_reset", "veto_debug_gemm", "veto_debug_gemm_workspace_bytes", "veto_debug_gemm_forms", "veto_debug_ffn", "veto_debug_ffn_workspace_bytes", "veto_debug_outproj", "veto_debug_outproj_workspace_bytes", "veto_debug_layer_tail", "veto_debug_layer_tail_workspace_bytes", "veto_debug_qkv_attn", "veto_debug_qkv_attn_workspace_bytes",
     "veto_postprocess", "veto_postprocess_workspace_bytes", "veto_postprocess_meet", "veto_postprocess_vote",
     "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
-    "veto_detect_relsample", "veto_detect_relsample_workspace_bytes",
+    "veto_detect_relsample", "veto_detect_relsample_workspace_bytes", "veto_gtbox_relsample",
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
@@ -91,6 +91,14 @@ class VetoDetectRelsampleArgs(Structure):
                                         "relation_non_masked", "img_prp_offset", "img_tgt_offset", "img_rel_offset",
                                         "img_binary_offset", "pairs", "labels", "labels_all", "binary_rel",
                                         "locating_match", "counts")]
+
+
+class VetoGtboxRelsampleArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_rel_cells", "max_obj_per_image", "batch_size_per_image",
+                                       "num_pos_per_img")] + \
+               [("seed", ctypes.c_uint64)] + \
+               [(n, c_void_p) for n in ("relation", "img_obj_offset", "img_rel_offset", "pairs", "labels", "binary_rel",
+                                        "counts")]
 
 
 class VetoPostMeetArgs(Structure):
@@ -204,6 +212,7 @@ def load_library():
     lib.veto_detect_relsample_workspace_bytes.argtypes = [c_int32, c_int32]
     lib.veto_detect_relsample_workspace_bytes.restype = c_size_t
     lib.veto_detect_relsample.argtypes = [c_void_p, POINTER(VetoDetectRelsampleArgs), c_void_p, c_size_t]
+    lib.veto_gtbox_relsample.argtypes = [c_void_p, POINTER(VetoGtboxRelsampleArgs)]
     lib.veto_train_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
     lib.veto_train_workspace_bytes.restype = c_size_t
     lib.veto_grad_floats.argtypes = [c_void_p]

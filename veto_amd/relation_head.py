@@ -17,6 +17,9 @@ filter, capped by pred_scores products), and the post-processor decodes the obje
 Training on detected boxes (:112-131 with samp_processor.detect_relsample) runs when VETO_AMD.DEVICE_DETECT_RELSAMPLE is set:
 the pairs and labels come from veto_amd.sampling.DetectRelationSampler (one veto_detect_relsample launch per batch), which
 has the reference sampler's distribution but not its draws for a given seed.
+Training on GT boxes (:112-121 with samp_processor.gtbox_relsample) uses the sampler it is given (or pysgg's); with
+VETO_AMD.DEVICE_GTBOX_RELSAMPLE set and no explicit sampler it uses veto_amd.sampling.GTBoxRelationSampler (one
+veto_gtbox_relsample launch per batch) under the same caveat, and then needs no sampler from the host code base.
 Everything numeric runs in libveto_amd.so; this file only moves fields around."""
 import torch
 from torch import nn
@@ -48,7 +51,8 @@ class VETORelationHead(nn.Module):
     def __init__(self, cfg, in_channels=512, samp_processor=None):
         """samp_processor: the relation sampler; only the training branch uses it (gtbox_relsample).  Default (None): the host code
         base's own, built from cfg exactly as the reference does (relation_head.py:66-67), so `VETORelationHead(cfg, in_channels)`
-        trains inside pysgg like the head it replaces; outside pysgg pass one explicitly (pair sampling is not part of this package)."""
+        trains inside pysgg like the head it replaces; outside pysgg pass one explicitly (e.g. veto_amd.sampling's
+        make_roi_relation_samp_processor(cfg)) or set VETO_AMD.DEVICE_GTBOX_RELSAMPLE / DEVICE_DETECT_RELSAMPLE."""
         super().__init__()
         self.cfg = cfg
         rh = cfg.MODEL.ROI_RELATION_HEAD
@@ -67,6 +71,10 @@ class VETORelationHead(nn.Module):
         self.max_proposal_pairs = int(getattr(rh, "MAX_PROPOSAL_PAIR", 2048))
         self.device_detect_relsample = bool(getattr(getattr(cfg, "VETO_AMD", None), "DEVICE_DETECT_RELSAMPLE", False))
         self._detect_sampler = None
+        # the device GT-box sampler is opt-in, and an explicitly passed sampler still wins
+        self.device_gtbox_relsample = (bool(getattr(getattr(cfg, "VETO_AMD", None), "DEVICE_GTBOX_RELSAMPLE", False))
+                                       and self.use_gt_box and samp_processor is None)
+        self._gtbox_sampler = None
 
     def forward(self, features, proposals, depth_features=None, targets=None, logger=None, x=None):
         """The reference's signature, parameter for parameter (relation_head.py:90; called as `self.relation(features,
@@ -90,6 +98,14 @@ class VETORelationHead(nn.Module):
                     self._detect_sampler = DetectRelationSampler.from_config(self.cfg)
                 with torch.no_grad():
                     proposals, rel_labels, _, rel_pair_idxs, _ = self._detect_sampler.detect_relsample(proposals, targets)
+                return self._train_tail(features, proposals, depth_features, rel_pair_idxs, rel_labels, logger)
+            if self.device_gtbox_relsample:
+                if self._gtbox_sampler is None:
+                    from .sampling import GTBoxRelationSampler
+                    self._gtbox_sampler = GTBoxRelationSampler.from_config(self.cfg)
+                self._overload_predcls_fields(proposals, features[0].device)
+                with torch.no_grad():
+                    proposals, rel_labels, rel_pair_idxs, _ = self._gtbox_sampler.gtbox_relsample(proposals, targets)
                 return self._train_tail(features, proposals, depth_features, rel_pair_idxs, rel_labels, logger)
             if self.samp_processor is None:
                 raise ValueError("training needs a relation sampler: pysgg's make_roi_relation_samp_processor(cfg) could not be "

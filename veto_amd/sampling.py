@@ -1,11 +1,20 @@
-"""Training-time relation sampling on detected boxes (sgdet), the caller side of veto_detect_relsample.
+"""Training-time relation sampling, the caller side of veto_detect_relsample (sgdet) and veto_gtbox_relsample (predcls, sgcls).
+
+`RelationSampling` has the reference's interface (sampling.py:13-309) and delegates each method to the device path:
+prepare_test_pairs -> pairs.prepare_test_pairs, gtbox_relsample -> GTBoxRelationSampler, detect_relsample ->
+DetectRelationSampler.
+
+`GTBoxRelationSampler.gtbox_relsample` mirrors `RelationSampling.gtbox_relsample` (sampling.py:54-107): one launch for the
+batch picks the foreground rows (all of them in torch.nonzero order, or a random subset above the positive budget), the random
+background rows and `binary_rel`.  The only device->host copy is the batch's per-image counts.
 
 `DetectRelationSampler.detect_relsample` mirrors `RelationSampling.detect_relsample`
 (pysgg/modeling/roi_heads/relation_head/sampling.py:109-176) with `motif_rel_fg_bg_sampling` (:179-309): one launch for the
 batch does the IoU matching, the per-GT-relation foreground draws, the foreground cap, the background window and its
 random subset, `binary_rel` and `locating_match` (see include/veto_amd.h).  The draws have the reference's distributions;
 they are not the reference's draws for a given seed (it mixes numpy's and torch's generators).  The only device->host copy
-is the batch's per-image counts, which decide how the outputs are split."""
+is the batch's per-image counts, which decide how the outputs are split.  The same holds for the GT-box sampler: its subsets
+and orders are uniform like torch.randperm's, from a counter-based hash instead of torch's generator."""
 import ctypes
 
 import torch
@@ -16,6 +25,14 @@ _OFFSETS = {}     # batch shape -> int32 offset tensor on the device
 _WORKSPACE = {}   # (device, stream) -> workspace: launches on different streams never share one
 
 
+def _prefix_sums(sizes):
+    acc, row = 0, [0]
+    for v in sizes:
+        acc += v
+        row.append(acc)
+    return row
+
+
 def _offsets(n_prp, n_tgt, device):
     """[4, n_img + 1] int32 prefix sums of P_i, T_i, T_i^2, P_i^2, cached per batch shape (a pageable H2D copy stalls the
     host behind the queued GPU work, as predictor.cached_offsets notes)."""
@@ -24,13 +41,7 @@ def _offsets(n_prp, n_tgt, device):
     if hit is None:
         if len(_OFFSETS) >= 256:
             _OFFSETS.clear()
-        rows = []
-        for sizes in (n_prp, n_tgt, [t * t for t in n_tgt], [p * p for p in n_prp]):
-            acc, row = 0, [0]
-            for v in sizes:
-                acc += v
-                row.append(acc)
-            rows.append(row)
+        rows = [_prefix_sums(sizes) for sizes in (n_prp, n_tgt, [t * t for t in n_tgt], [p * p for p in n_prp])]
         hit = _OFFSETS[key] = torch.tensor(rows, dtype=torch.int32, device=device)
     return hit
 
@@ -148,3 +159,124 @@ class DetectRelationSampler:
         if not has_nm:
             rel_labels_all = rel_labels   # sampling.py:173-174
         return proposals, rel_labels, rel_labels_all, rel_pair_idxs, rel_sym_binarys
+
+
+_GT_OFFSETS = {}  # batch shape -> [2, n_img + 1] int32 offset tensor on the device
+
+
+def _gt_offsets(n_obj, device):
+    """[2, n_img + 1] int32 prefix sums of n_i and n_i^2, cached per batch shape like _offsets."""
+    key = (tuple(n_obj), str(device))
+    hit = _GT_OFFSETS.get(key)
+    if hit is None:
+        if len(_GT_OFFSETS) >= 256:
+            _GT_OFFSETS.clear()
+        rows = [_prefix_sums(sizes) for sizes in (n_obj, [n * n for n in n_obj])]
+        hit = _GT_OFFSETS[key] = torch.tensor(rows, dtype=torch.int32, device=device)
+    return hit
+
+
+class GTBoxRelationSampler:
+    def __init__(self, batch_size_per_image, positive_fraction):
+        self.batch_size_per_image = int(batch_size_per_image)
+        self.positive_fraction = float(positive_fraction)
+        self.num_pos_per_img = int(self.batch_size_per_image * self.positive_fraction)   # sampling.py:56
+
+    @classmethod
+    def from_config(cls, cfg):
+        rh = cfg.MODEL.ROI_RELATION_HEAD
+        return cls(rh.BATCH_SIZE_PER_IMAGE, rh.POSITIVE_FRACTION)
+
+    def gtbox_relsample(self, proposals, targets, seed=None):
+        """proposals: BoxLists of the GT boxes; targets: BoxLists with 'relation' [n, n].  Adds 'locating_match' (ones,
+        sampling.py:71-73) to every proposal and returns (proposals, rel_labels, rel_idx_pairs, rel_sym_binarys) as the
+        reference does.  seed: 64-bit; None draws one from torch's default generator, so torch.manual_seed makes a run
+        reproducible."""
+        if len(proposals) != len(targets) or not proposals:
+            raise ValueError("gtbox_relsample needs one target per proposal list (got %d and %d)" % (len(proposals), len(targets)))
+        n_obj = [len(p) for p in proposals]
+        for i, (n, t) in enumerate(zip(n_obj, targets)):
+            if len(t) != n:
+                raise ValueError("image %d: %d proposals but %d targets (GT-box sampling pairs them one to one, "
+                                 "sampling.py:66)" % (i, n, len(t)))
+            if tuple(t.get_field("relation").shape) != (n, n):
+                raise ValueError("a target's 'relation' must be [%d, %d], got %s" % (n, n, tuple(t.get_field("relation").shape)))
+        device = proposals[0].bbox.device
+        if device.type != "cuda":
+            raise RuntimeError("veto_amd gtbox_relsample runs on a HIP device only (got %s)" % device)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())   # the CPU generator: no device synchronisation
+        lib = native.load_library()
+        n_img, B = len(proposals), self.batch_size_per_image
+        n_cells = sum(n * n for n in n_obj)
+        i64 = dict(device=device, dtype=torch.int64)
+        parts = [t.get_field("relation").reshape(-1).to(**i64) for t in targets]
+        relation = torch.cat(parts).contiguous()
+        off = _gt_offsets(n_obj, device)
+        pairs = torch.empty((n_img * B, 2), **i64)
+        labels = torch.empty(n_img * B, **i64)
+        binary = torch.empty(n_cells, **i64)
+        counts = torch.empty((n_img, 2), dtype=torch.int32, device=device)
+        stream = torch.cuda.current_stream(device)
+
+        a = native.VetoGtboxRelsampleArgs()
+        a.struct_size = ctypes.sizeof(native.VetoGtboxRelsampleArgs)
+        a.n_img, a.n_rel_cells, a.max_obj_per_image = n_img, n_cells, max(n_obj)
+        a.batch_size_per_image, a.num_pos_per_img = B, self.num_pos_per_img
+        a.seed = seed & (2 ** 64 - 1)
+        a.relation = relation.data_ptr() if n_cells else None
+        a.img_obj_offset, a.img_rel_offset = off[0].data_ptr(), off[1].data_ptr()
+        a.pairs, a.labels, a.counts = pairs.data_ptr(), labels.data_ptr(), counts.data_ptr()
+        a.binary_rel = binary.data_ptr() if n_cells else None
+        native.check(lib.veto_gtbox_relsample(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
+        relation.record_stream(stream)
+        off.record_stream(stream)
+        cnt = counts.tolist()   # the one device->host copy: the per-image counts split the outputs
+        ones = torch.ones(sum(n_obj), device=device)
+        rel_labels, rel_idx_pairs, rel_sym_binarys = [], [], []
+        boff = ooff = 0
+        for i, (p, n) in enumerate(zip(proposals, n_obj)):
+            r = cnt[i][0] + cnt[i][1]
+            rel_idx_pairs.append(pairs[i * B:i * B + r])
+            rel_labels.append(labels[i * B:i * B + r])
+            rel_sym_binarys.append(binary[boff:boff + n * n].view(n, n))
+            p.add_field("locating_match", ones[ooff:ooff + n])
+            boff, ooff = boff + n * n, ooff + n
+        return proposals, rel_labels, rel_idx_pairs, rel_sym_binarys
+
+
+class RelationSampling(object):
+    """The reference's sampler interface (sampling.py:13-29) on the device paths of this package."""
+
+    def __init__(self, fg_thres, require_overlap, num_sample_per_gt_rel, batch_size_per_image, positive_fraction, max_proposal_pairs,
+                 use_gt_box, test_overlap):
+        self.fg_thres = fg_thres
+        self.require_overlap = require_overlap
+        self.num_sample_per_gt_rel = num_sample_per_gt_rel
+        self.batch_size_per_image = batch_size_per_image
+        self.positive_fraction = positive_fraction
+        self.use_gt_box = use_gt_box
+        self.max_proposal_pairs = max_proposal_pairs
+        self.test_overlap = test_overlap
+        self._gtbox = GTBoxRelationSampler(batch_size_per_image, positive_fraction)
+        self._detect = DetectRelationSampler(fg_thres, require_overlap, num_sample_per_gt_rel, batch_size_per_image, positive_fraction)
+
+    def prepare_test_pairs(self, device, proposals):
+        from .pairs import prepare_test_pairs
+        return prepare_test_pairs(device, proposals, self.max_proposal_pairs,
+                                  require_overlap=bool(self.test_overlap) and not self.use_gt_box, use_gt_box=bool(self.use_gt_box))
+
+    def gtbox_relsample(self, proposals, targets):
+        assert self.use_gt_box
+        return self._gtbox.gtbox_relsample(proposals, targets)
+
+    def detect_relsample(self, proposals, targets):
+        return self._detect.detect_relsample(proposals, targets)
+
+
+def make_roi_relation_samp_processor(cfg):
+    """sampling.py:312-324."""
+    rh = cfg.MODEL.ROI_RELATION_HEAD
+    return RelationSampling(cfg.MODEL.ROI_HEADS.FG_IOU_THRESHOLD, rh.REQUIRE_BOX_OVERLAP, rh.NUM_SAMPLE_PER_GT_REL,
+                            rh.BATCH_SIZE_PER_IMAGE, rh.POSITIVE_FRACTION, rh.MAX_PROPOSAL_PAIR, rh.USE_GT_BOX,
+                            cfg.TEST.RELATION.REQUIRE_OVERLAP)
