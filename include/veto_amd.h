@@ -16,6 +16,8 @@
  *   veto_gtbox_relsample   <- RelationSampling.gtbox_relsample (predcls / sgcls training)   sampling.py:54-107
  *   veto_obj_decode        <- obj_prediction_nms (PostProcessor)    utils_relation.py:94-128, inference.py:410-429
  *                             Ensemble.nms_per_cls (MEET decoder)   roi_relation_predictors.py:3855-3874
+ *   veto_nms               <- pysgg._C.nms / boxlist_nms            csrc/cuda/nms.cu, structures/boxlist_ops.py:10-32
+ *   veto_box_postprocess   <- PostProcessor (box head)              roi_heads/box_head/inference.py:51-238
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -300,6 +302,75 @@ typedef struct veto_pair_args {
 } veto_pair_args_t;
 
 int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* args);
+
+/* ---- sgdet box decoder: what produces predict_logits / pred_labels / pred_scores / boxes_per_cls ------------------
+ * veto_nms: pysgg._C.nms (csrc/cuda/nms.cu) for n_seg segments (one image x class, or one image x pyramid level) in ONE
+ * launch, nothing copied to the host.  Semantics of the reference's GPU kernel:
+ *   IoU = devIoU (nms.cu:13-21, +1 pixel convention, same operation order); a box is suppressed by an earlier kept box at
+ *   IoU STRICTLY GREATER than `threshold` (nms.cu:60 -- the reference's CPU twin, nms_cpu.cpp:60, uses >=; the GPU
+ *   results are what users have, so > it is); boxes are visited in the total order (score desc, index asc) -- the
+ *   reference's sort is unstable, equal scores are decided here; keep = the kept indices, LOCAL to the segment, in
+ *   ASCENDING index order (nms.cu:127-130) from keep[seg_offset[s]]; max_keep > 0 keeps the first max_keep of that
+ *   ascending list (boxlist_ops.py:29-30), not the best-scoring ones; an empty segment gives count 0.
+ * A segment may hold up to veto_nms_max_segment() = 6144 boxes (MODEL.RPN.PRE_NMS_TOP_N_TEST is 6000).  The host copy of the
+ * offsets is what the sizes are checked against before anything is launched. */
+typedef struct veto_nms_args {
+  int32_t struct_size;
+  int32_t n_box, n_seg;
+  int32_t max_keep;                   /* <= 0: no cap */
+  float threshold;
+  int32_t reserved0;
+  const float* boxes;                 /* device [n_box, 4] xyxy, 16-byte aligned */
+  const float* scores;                /* device [n_box] */
+  const int32_t* seg_offset;          /* device [n_seg + 1] */
+  const int32_t* seg_offset_host;     /* HOST [n_seg + 1], the same values: 0 = first, non-decreasing, last = n_box */
+  int64_t* keep;                      /* out device [n_box] */
+  int32_t* counts;                    /* out device [n_seg] */
+} veto_nms_args_t;
+
+int veto_nms_max_segment(void);
+int veto_nms(void* stream, const veto_nms_args_t* args);
+
+/* veto_box_postprocess: the box head's PostProcessor.forward + filter_results (box_head/inference.py:51-238) for a batch.
+ *   per proposal: softmax(class_logits); BoxCoder.decode (box_coder.py:62-95: reg_weights, dw / dh clamped at
+ *   bbox_xform_clip, the - 1 on x2 / y2) of every class -- cls_agnostic: the LAST four regression columns for every class;
+ *   clip_to_image(remove_empty=False): every coordinate clamped to [0, size - 1].
+ *   per image x class j >= 1: candidates prob > score_thresh, veto_nms at nms_thresh, at most post_nms_per_cls_topn.
+ *   per image: filter_duplicates -- a row survives when any class survived, score / label = its best surviving class (first
+ *   column on ties), box = its box of that class, rows ascending (:191-211); else class-major, rows ascending, a row
+ *   once per surviving class (:212-214).  With more than detections_per_img (> 0) detections: keep score >= the
+ *   (count - detections_per_img + 1)-th smallest; ties at that value stay, as in the reference (:216-226).
+ * Image i writes counts[i] rows from img_out_offset[i]; when its capacity img_out_offset[i + 1] - img_out_offset[i] is too
+ * small nothing is written for it and counts[i] = -(rows needed).  The decoded [n_box, n_cls, 4] lives in the workspace. */
+typedef struct veto_box_post_args {
+  int32_t struct_size;
+  int32_t n_img, n_box, n_cls;        /* n_cls 2..1024, background = class 0 */
+  int32_t reg_cols;                   /* columns of box_regression: 4 * n_cls, or any multiple of 4 with cls_agnostic */
+  int32_t cls_agnostic;               /* MODEL.CLS_AGNOSTIC_BBOX_REG */
+  int32_t post_nms_per_cls_topn;      /* MODEL.ROI_HEADS.POST_NMS_PER_CLS_TOPN, <= 0: none */
+  int32_t filter_duplicates;          /* MODEL.ROI_HEADS.NMS_FILTER_DUPLICATES */
+  int32_t detections_per_img;         /* MODEL.ROI_HEADS.DETECTIONS_PER_IMG, <= 0: none */
+  float score_thresh;                 /* MODEL.ROI_HEADS.SCORE_THRESH, >= 0 */
+  float nms_thresh;                   /* MODEL.ROI_HEADS.NMS */
+  float bbox_xform_clip;              /* log(1000 / 16) */
+  float reg_weights[4];               /* MODEL.ROI_HEADS.BBOX_REG_WEIGHTS */
+  const float* class_logits;          /* device [n_box, n_cls] */
+  const float* box_regression;        /* device [n_box, reg_cols], 16-byte aligned */
+  const float* proposals;             /* device [n_box, 4] xyxy, 16-byte aligned */
+  const float* image_sizes;           /* device [n_img, 2]: (width, height) */
+  const int32_t* img_offset;          /* device [n_img + 1]: proposals per image, at most veto_nms_max_segment() each */
+  const int32_t* img_offset_host;     /* HOST copy, checked before anything is launched */
+  const int32_t* img_out_offset;      /* device [n_img + 1] */
+  int64_t* orig_inds;                 /* out device [img_out_offset[n_img]]: proposal row, local to the image */
+  int64_t* pred_labels;               /* out device, same rows */
+  float* pred_scores;                 /* out device */
+  float* boxes;                       /* out device [.., 4], 16-byte aligned */
+  float* boxes_per_cls;               /* optional out device [.., n_cls, 4] = decoded[orig_inds] */
+  int32_t* counts;                    /* out device [n_img] */
+} veto_box_post_args_t;
+
+size_t veto_box_postprocess_workspace_bytes(int32_t n_box, int32_t n_cls, int32_t filter_duplicates);
+int veto_box_postprocess(void* stream, const veto_box_post_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* veto_detect_relsample: RelationSampling.detect_relsample (sampling.py:109-176) with motif_rel_fg_bg_sampling (:179-309),
  * the training-time relation sampler on detected boxes, for a ragged batch (one workgroup per image).  Per image:

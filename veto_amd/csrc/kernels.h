@@ -314,6 +314,43 @@ struct PairArgs {
 int prepare_pairs_max_pairs();
 hipError_t launch_prepare_pairs(const PairArgs& a, hipStream_t s);
 
+// ---- sgdet box decoder: segmented greedy NMS and the box head's PostProcessor (nms.hip) -----------------
+struct NmsArgs {
+  const float* boxes;            // [n_box, 4] xyxy, 16-byte aligned
+  const float* scores;           // [n_box]
+  const int32_t* seg_off;        // [n_seg + 1]
+  int n_seg, max_keep;           // max_keep <= 0: no cap
+  float thr;
+  int64_t* keep;                 // out [n_box]: segment s writes counts[s] local indices from seg_off[s]
+  int32_t* counts;               // out [n_seg]
+};
+int nms_max_segment();
+hipError_t launch_nms(const NmsArgs& a, int max_seg, hipStream_t s);
+struct BoxPostArgs {
+  const float* logits;           // [n_box, n_cls]
+  const float* regression;       // [n_box, reg_cols]
+  const float* proposals;        // [n_box, 4] xyxy
+  const float* image_sizes;      // [n_img, 2] (width, height)
+  const int32_t* img_off;        // [n_img + 1]
+  const int32_t* out_off;        // [n_img + 1]: image i writes its detections from row out_off[i]
+  int n_img, n_box, n_cls, reg_cols, cls_agnostic, topn, filter_dup, det_per_img;
+  float score_thresh, nms_thresh, wx, wy, ww, wh, xform_clip;
+  float* prob;                   // workspace [n_box, n_cls]: softmax, then dist_scores
+  float* dec;                    // workspace [n_box, n_cls, 4]: decoded, clipped boxes
+  float* row_score;              // workspace [n_box] (filter_dup)
+  int32_t* row_label;            // workspace [n_box] (filter_dup)
+  float* list_score;             // workspace: the detection list before the cut, [n_box] or [n_box * (n_cls - 1)]
+  int32_t* list_row;
+  int32_t* list_label;
+  int64_t* orig_inds;            // out [out_off[n_img]]
+  int64_t* labels;               // out
+  float* scores;                 // out
+  float* boxes;                  // out [.., 4]
+  float* boxes_per_cls;          // optional out [.., n_cls, 4]
+  int32_t* counts;               // out [n_img]; -count when an image's rows do not hold its detections
+};
+hipError_t launch_box_postprocess(const BoxPostArgs& a, int max_per_img, hipStream_t s);
+
 // ---- sgdet training: detected-box relation sampling (relsample.hip) ---------------------------------
 struct RelSampleArgs {
   const float* prp_boxes;        // [n_prp, 4] xyxy

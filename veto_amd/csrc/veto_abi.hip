@@ -1663,6 +1663,98 @@ int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* a) {
   return VETO_OK;
 }
 
+int veto_nms_max_segment(void) { return nms_max_segment(); }
+
+// host offsets: 0 = first, non-decreasing, last = total, no segment above `limit`; returns the largest segment or -1 (error set)
+static int check_host_offsets(const int32_t* off, int n_seg, int total, int limit, const char* name, const char* total_name) {
+  if (off[0] != 0) return fail(VETO_ERR_INVALID, "%s[0] must be 0, got %d", name, off[0]);
+  int largest = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    const int n = off[s + 1] - off[s];
+    if (n < 0) return fail(VETO_ERR_INVALID, "%s is not monotone: entry %d is %d after %d", name, s + 1, off[s + 1], off[s]);
+    if (n > limit) return fail(VETO_ERR_INVALID, "%s: segment %d holds %d boxes, the limit is %d", name, s, n, limit);
+    if (n > largest) largest = n;
+  }
+  if (off[n_seg] != total) return fail(VETO_ERR_INVALID, "%s ends at %d, %s is %d", name, off[n_seg], total_name, total);
+  return largest;
+}
+
+int veto_nms(void* stream, const veto_nms_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_nms_args_t)) return fail(VETO_ERR_INVALID, "veto_nms_args_t size mismatch");
+  if (a->n_seg <= 0 || a->n_box < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_seg %d, n_box %d)", a->n_seg, a->n_box);
+  if (!a->seg_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: seg_offset_host");
+  const int largest = check_host_offsets(a->seg_offset_host, a->n_seg, a->n_box, nms_max_segment(), "seg_offset_host", "n_box");
+  if (largest < 0) return largest;
+  if ((a->n_box > 0 && (!a->boxes || !a->scores || !a->keep)) || !a->seg_offset || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (((uintptr_t)a->boxes & 15) != 0) return fail(VETO_ERR_INVALID, "boxes must be 16-byte aligned");
+  NmsArgs p{};
+  p.boxes = a->boxes; p.scores = a->scores; p.seg_off = a->seg_offset; p.n_seg = a->n_seg; p.max_keep = a->max_keep;
+  p.thr = a->threshold; p.keep = a->keep; p.counts = a->counts;
+  HIP_TRY(launch_nms(p, largest, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// workspace: prob | dec | row_score | row_label | list_score | list_row | list_label
+static size_t box_post_list_rows(int32_t n_box, int32_t n_cls, int32_t filter_dup) {
+  return filter_dup ? (size_t)n_box : (size_t)n_box * (n_cls - 1);
+}
+
+size_t veto_box_postprocess_workspace_bytes(int32_t n_box, int32_t n_cls, int32_t filter_duplicates) {
+  if (n_box <= 0 || n_cls < 2) return 256;
+  const size_t rows = box_post_list_rows(n_box, n_cls, filter_duplicates);
+  return align_up((size_t)n_box * n_cls * 4, 256) + align_up((size_t)n_box * n_cls * 16, 256) + 2 * align_up((size_t)n_box * 4, 256) +
+         3 * align_up(rows * 4, 256);
+}
+
+int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_box_post_args_t)) return fail(VETO_ERR_INVALID, "veto_box_post_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_box <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_box %d)", a->n_img, a->n_box);
+  if (a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d above 65535", a->n_img);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->reg_cols < 4 || a->reg_cols % 4 != 0 || (!a->cls_agnostic && a->reg_cols != 4 * a->n_cls))
+    return fail(VETO_ERR_INVALID, "reg_cols %d: must be 4 * n_cls (%d), or a multiple of 4 with cls_agnostic", a->reg_cols, 4 * a->n_cls);
+  if (!(a->score_thresh >= 0.f)) return fail(VETO_ERR_INVALID, "score_thresh %g must be >= 0 (SCORE_THRESH)", a->score_thresh);
+  if (!(a->nms_thresh > 0.f)) return fail(VETO_ERR_INVALID, "nms_thresh %g must be > 0 (ROI_HEADS.NMS)", a->nms_thresh);
+  for (int k = 0; k < 4; ++k)
+    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0 (BBOX_REG_WEIGHTS)", k, a->reg_weights[k]);
+  if (!a->img_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_offset_host");
+  const int largest = check_host_offsets(a->img_offset_host, a->n_img, a->n_box, nms_max_segment(), "img_offset_host", "n_box");
+  if (largest < 0) return largest;
+  if (!a->class_logits || !a->box_regression || !a->proposals || !a->image_sizes || !a->img_offset || !a->img_out_offset ||
+      !a->orig_inds || !a->pred_labels || !a->pred_scores || !a->boxes || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if ((((uintptr_t)a->box_regression | (uintptr_t)a->proposals | (uintptr_t)a->boxes | (uintptr_t)a->boxes_per_cls) & 15) != 0)
+    return fail(VETO_ERR_INVALID, "box_regression, proposals, boxes and boxes_per_cls must be 16-byte aligned");
+  const size_t need = veto_box_postprocess_workspace_bytes(a->n_box, a->n_cls, a->filter_duplicates);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
+                                                        workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  BoxPostArgs p{};
+  p.logits = a->class_logits; p.regression = a->box_regression; p.proposals = a->proposals; p.image_sizes = a->image_sizes;
+  p.img_off = a->img_offset; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.n_box = a->n_box; p.n_cls = a->n_cls; p.reg_cols = a->reg_cols; p.cls_agnostic = a->cls_agnostic != 0;
+  p.topn = a->post_nms_per_cls_topn; p.filter_dup = a->filter_duplicates != 0; p.det_per_img = a->detections_per_img;
+  p.score_thresh = a->score_thresh; p.nms_thresh = a->nms_thresh;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.xform_clip = a->bbox_xform_clip;
+  const size_t rows = box_post_list_rows(a->n_box, a->n_cls, a->filter_duplicates);
+  char* base = (char*)workspace;
+  p.prob = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 4, 256);
+  p.dec = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 16, 256);
+  p.row_score = (float*)base; base += align_up((size_t)a->n_box * 4, 256);
+  p.row_label = (int32_t*)base; base += align_up((size_t)a->n_box * 4, 256);
+  p.list_score = (float*)base; base += align_up(rows * 4, 256);
+  p.list_row = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.list_label = (int32_t*)base;
+  p.orig_inds = a->orig_inds; p.labels = a->pred_labels; p.scores = a->pred_scores; p.boxes = a->boxes;
+  p.boxes_per_cls = a->boxes_per_cls; p.counts = a->counts;
+  HIP_TRY(launch_box_postprocess(p, largest, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel) {
   if (n_rel_cells <= 0 || num_sample_per_gt_rel <= 0) return 256;
   return align_up((size_t)n_rel_cells * 8, 256) + align_up((size_t)n_rel_cells * num_sample_per_gt_rel * 4, 256);

@@ -22,6 +22,7 @@ EXPORTS = [
     "veto_postprocess", "veto_postprocess_workspace_bytes", "veto_postprocess_meet", "veto_postprocess_vote",
     "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
     "veto_detect_relsample", "veto_detect_relsample_workspace_bytes", "veto_gtbox_relsample",
+    "veto_nms", "veto_nms_max_segment", "veto_box_postprocess", "veto_box_postprocess_workspace_bytes",
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
@@ -80,6 +81,22 @@ class VetoPairArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_obj", "max_obj_per_image", "max_pairs",
                                        "require_overlap")] + \
                [(n, c_void_p) for n in ("boxes", "scores", "img_obj_offset", "img_out_offset", "pairs", "counts")]
+
+
+class VetoNmsArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_box", "n_seg", "max_keep")] + \
+               [("threshold", ctypes.c_float), ("reserved0", c_int32)] + \
+               [(n, c_void_p) for n in ("boxes", "scores", "seg_offset", "seg_offset_host", "keep", "counts")]
+
+
+class VetoBoxPostArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_box", "n_cls", "reg_cols", "cls_agnostic",
+                                       "post_nms_per_cls_topn", "filter_duplicates", "detections_per_img")] + \
+               [(n, ctypes.c_float) for n in ("score_thresh", "nms_thresh", "bbox_xform_clip")] + \
+               [("reg_weights", ctypes.c_float * 4)] + \
+               [(n, c_void_p) for n in ("class_logits", "box_regression", "proposals", "image_sizes", "img_offset",
+                                        "img_offset_host", "img_out_offset", "orig_inds", "pred_labels", "pred_scores",
+                                        "boxes", "boxes_per_cls", "counts")]
 
 
 class VetoDetectRelsampleArgs(Structure):
@@ -209,6 +226,11 @@ def load_library():
     lib.veto_obj_decode_workspace_bytes.restype = c_size_t
     lib.veto_obj_decode.argtypes = [c_void_p, POINTER(VetoObjDecodeArgs), c_void_p, c_size_t]
     lib.veto_prepare_test_pairs.argtypes = [c_void_p, POINTER(VetoPairArgs)]
+    lib.veto_nms_max_segment.argtypes = []
+    lib.veto_nms.argtypes = [c_void_p, POINTER(VetoNmsArgs)]
+    lib.veto_box_postprocess_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    lib.veto_box_postprocess_workspace_bytes.restype = c_size_t
+    lib.veto_box_postprocess.argtypes = [c_void_p, POINTER(VetoBoxPostArgs), c_void_p, c_size_t]
     lib.veto_detect_relsample_workspace_bytes.argtypes = [c_int32, c_int32]
     lib.veto_detect_relsample_workspace_bytes.restype = c_size_t
     lib.veto_detect_relsample.argtypes = [c_void_p, POINTER(VetoDetectRelsampleArgs), c_void_p, c_size_t]

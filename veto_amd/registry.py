@@ -47,3 +47,25 @@ def install(target_registry=None):
     for name in ("VETOPredictor", "VETOPredictor_MEET"):
         dict.__setitem__(target_registry, name, ROI_RELATION_PREDICTOR[name])
     return target_registry
+
+
+def install_detector_ops():
+    """Point the reference's detector at the device decoder: `pysgg.layers.nms` and `boxlist_ops._box_nms` (boxlist_nms:
+    the box head's and the RPN's NMS) become veto_amd.layers.nms, and `box_head.inference.make_roi_box_post_processor`
+    returns veto_amd.boxhead.PostProcessor.  `pysgg` must be importable.  Independent of install().  Returns the patched
+    (module, name) pairs."""
+    import importlib
+    from . import boxhead, layers
+    patched = []
+    for mod, name, value in (("pysgg.layers", "nms", layers.nms),
+                             ("pysgg.structures.boxlist_ops", "_box_nms", layers.nms),
+                             ("pysgg.modeling.roi_heads.box_head.inference", "make_roi_box_post_processor",
+                              boxhead.make_roi_box_post_processor)):
+        setattr(importlib.import_module(mod), name, value)
+        patched.append((mod, name))
+    # box_head.py binds the factory by name when it is imported (box_head.py:8): re-point that binding too if it exists
+    import sys
+    head = sys.modules.get("pysgg.modeling.roi_heads.box_head.box_head")
+    if head is not None and hasattr(head, "make_roi_box_post_processor"):
+        head.make_roi_box_post_processor = boxhead.make_roi_box_post_processor
+    return patched

@@ -455,3 +455,70 @@ def synthetic_relsample_image(seed, n_gt, n_det, n_rel, num_obj_cls=151, num_rel
             "pred_scores": uniform(seed, tag + ".score", (n_det,), 0.05, 1.0),
             "tgt_boxes": gt.astype(np.float32), "tgt_labels": gt_lab.astype(np.int64),
             "relation": rel.reshape(n_gt, n_gt), "relation_non_masked": non_masked.reshape(n_gt, n_gt), "image_size": (W, H)}
+
+
+# ---------------------------------------------------------------------------
+# sgdet box decoder: the box head's raw outputs, and boxes + scores for NMS alone
+# ---------------------------------------------------------------------------
+
+def _clustered_boxes(seed, tag, n, W, H, per_cluster=8):
+    """n xyxy boxes in clusters on a jittered grid: boxes of one cluster overlap heavily (IoU mostly above 0.5), boxes of
+    neighbouring clusters barely (what a detector's proposals around objects look like, scaled to the grid)."""
+    k = max(1, n // per_cluster)
+    gx = max(1, int(math.ceil(math.sqrt(k * W / float(H)))))
+    gy = max(1, int(math.ceil(k / float(gx))))
+    cw, ch = W / float(gx), H / float(gy)
+    cell = np.arange(k)
+    cx = (cell % gx + 0.5) * cw + uniform(seed, tag + ".cx", (k,), -0.15, 0.15).astype(np.float64) * cw
+    cy = (cell // gx + 0.5) * ch + uniform(seed, tag + ".cy", (k,), -0.15, 0.15).astype(np.float64) * ch
+    bw = uniform(seed, tag + ".w", (k,), 0.55, 0.95).astype(np.float64) * cw
+    bh = uniform(seed, tag + ".h", (k,), 0.55, 0.95).astype(np.float64) * ch
+    cl = integers(seed, tag + ".cluster", (n,), 0, k)
+    jit = normal(seed, tag + ".jit", (n, 4), 0.0, 0.04).astype(np.float64)
+    x1 = cx[cl] - bw[cl] / 2 + jit[:, 0] * bw[cl]
+    y1 = cy[cl] - bh[cl] / 2 + jit[:, 1] * bh[cl]
+    x2 = cx[cl] + bw[cl] / 2 + jit[:, 2] * bw[cl]
+    y2 = cy[cl] + bh[cl] / 2 + jit[:, 3] * bh[cl]
+    x1, y1 = np.clip(x1, 0.0, W - 3.0), np.clip(y1, 0.0, H - 3.0)
+    x2, y2 = np.clip(np.maximum(x2, x1 + 2.0), 0.0, W - 1.0), np.clip(np.maximum(y2, y1 + 2.0), 0.0, H - 1.0)
+    return np.stack([x1, y1, x2, y2], 1).astype(np.float32), cl
+
+
+def synthetic_nms_boxes(seed, n, W=1333, H=800):
+    """(boxes [n, 4] xyxy, scores [n]) for NMS alone: clustered boxes, scores distinct by construction (a random permutation
+    of n slots of width 1/n, each with a jitter of less than half a slot)."""
+    tag = "nms.%d" % n
+    boxes, _ = _clustered_boxes(seed, tag, n, W, H)
+    rank = np.argsort(np.argsort(uniform01(seed, tag + ".perm", n), kind="stable"), kind="stable")
+    scores = ((rank + 0.25 + 0.5 * uniform01(seed, tag + ".u", n)) / max(n, 1)).astype(np.float32)
+    return boxes, scores
+
+
+def synthetic_box_head_outputs(seed, n, num_obj_cls=151, W=800, H=600, on_classes=(12, 36), marginal=2, cls_agnostic=False):
+    """What the box head's predictor hands the PostProcessor for one image of n proposals: `proposals` [n, 4] xyxy in clusters,
+    `class_logits` [n, C] and `box_regression` [n, 4C] ([n, 8] with cls_agnostic).  Per row, on_classes[0]..on_classes[1]
+    classes (the cluster's favourites among them) carry logits in [3.2, 5], `marginal` more sit around the usual score
+    threshold of 0.01 and the rest, the background included, lie below -1: a few dozen classes per row pass the threshold and
+    the probabilities in between are sparse.  Regressions are of the size a trained head emits: shifts of ~6 % of the box,
+    log-scale changes of ~8 % (after BBOX_REG_WEIGHTS (10, 10, 5, 5))."""
+    C = num_obj_cls
+    tag = "boxhead.%d.%d" % (n, C)
+    proposals, cl = _clustered_boxes(seed, tag, n, W, H)
+    k = int(cl.max()) + 1 if n else 1
+    logits = uniform(seed, tag + ".off", (n, C), -6.0, -1.0).astype(np.float64)
+    n_on = integers(seed, tag + ".n_on", (n,), on_classes[0], on_classes[1] + 1)
+    # a class is "on" for a row when its (cluster, class) or (row, class) draw is small enough: clusters share favourites
+    shared = uniform01(seed, tag + ".shared", k * C).reshape(k, C)[cl]
+    own = uniform01(seed, tag + ".own", n * C).reshape(n, C)
+    pick = np.minimum(shared, own * 2.0)
+    pick[:, 0] = 2.0
+    order = np.argsort(pick, axis=1, kind="stable")
+    rank = np.argsort(order, axis=1, kind="stable")
+    on = rank < n_on[:, None]
+    marg = (rank >= n_on[:, None]) & (rank < n_on[:, None] + marginal)
+    logits = np.where(on, uniform(seed, tag + ".on", (n, C), 3.2, 5.0).astype(np.float64), logits)
+    logits = np.where(marg, uniform(seed, tag + ".marg", (n, C), 2.0, 3.6).astype(np.float64), logits)
+    cols = 8 if cls_agnostic else 4 * C
+    reg = normal(seed, tag + ".reg", (n, cols // 4, 4), 0.0, 1.0).astype(np.float64) * np.array([0.6, 0.6, 0.4, 0.4])
+    return {"proposals": proposals, "class_logits": logits.astype(np.float32),
+            "box_regression": reg.reshape(n, cols).astype(np.float32), "image_size": (W, H)}
