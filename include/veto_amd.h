@@ -672,6 +672,30 @@ int veto_debug_gelu_backward(void* stream, const float* pre, const float* dh, fl
 int veto_debug_column_sums(void* stream, const float* dy, int64_t ld, int32_t rows, int32_t n_cols, float* out,
                            void* workspace, size_t workspace_bytes);
 
+/* ---- test hooks: the same blocks in the forms veto_backward runs ------------------------------------------------
+ * veto_debug_attention_backward_forms: `flags` selects
+ *   VETO_ATTN_BWD_CLS_ONLY   the last layer's form: dout is compact [n_pair, 576] (the CLS query's row); dq of token rows 1..18 is
+ *                            written as zero
+ *   VETO_ATTN_BWD_QKV_F24    qkv holds 3-byte floats (the top three bytes of the fp32 value rounded to nearest even, low address
+ *                            first; rows of 1728 x 3 bytes); head widths 72 and 96 only.  qkv_unpacked (optional, fp32
+ *                            [n_pair*19, 1728]) receives the values the kernel sees
+ *   VETO_ATTN_BWD_SPLIT_OUT  dqkv is written as split rows instead of fp32: per row 2 x 1728 bf16, in blocks of 32 columns
+ *                            [hi(c0..c0+31) | lo(c0..c0+31)], value = hi + lo
+ * veto_debug_layernorm_backward_split: veto_debug_layernorm_backward that also writes what the Linear behind the LayerNorm takes:
+ *   split_rows [rows, 2 x 576] bf16 (layout above) of dx with the dropout mask of site drop_seed applied (element (r, c) has index
+ *   r * 576 + c; kept iff the top 24 bits of its splitmix64 hash are >= drop_thresh = p * 2^24, scaled by drop_scale; 0 = no mask),
+ *   and col_partials [veto_debug_layernorm_backward_col_partial_rows(rows), 576]: the column sums of those rows per 32 rows. */
+#define VETO_ATTN_BWD_CLS_ONLY 1u
+#define VETO_ATTN_BWD_QKV_F24 2u
+#define VETO_ATTN_BWD_SPLIT_OUT 4u
+int veto_debug_attention_backward_forms(void* stream, const void* qkv, const float* dout, void* dqkv, float* qkv_unpacked,
+                                        int32_t n_pair, int32_t heads, uint32_t flags);
+int32_t veto_debug_layernorm_backward_col_partial_rows(int32_t rows);
+int veto_debug_layernorm_backward_split(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
+                                        float* dx, float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows,
+                                        uint64_t drop_seed, uint32_t drop_thresh, float drop_scale, void* workspace,
+                                        size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,12 +87,16 @@ def object_embeddings(sd, cfg, labels, predict_logits, pred_labels, dtype):
     return emb, obj_dists
 
 
-def position_embedding(sd, cfg, boxes_xyxy, dtype):
+def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False):
     """pos_embed = BatchNorm1d(4) (eval: running stats, eps 1e-5) -> Linear(4,128) -> ReLU;
-    roi_relation_predictors.py:4042-4047,4097-4102."""
+    roi_relation_predictors.py:4042-4047,4097-4102.  `batch_stats`: the training-mode BatchNorm, normalising with the
+    batch mean and the BIASED batch variance (the running update, which takes the unbiased one, is not part of the forward)."""
     p = cfg.prefix + "pos_embed."
     x = center_xywh_from_xyxy(_t(boxes_xyxy, dtype))
-    mean, var = _t(sd[p + "0.running_mean"], dtype), _t(sd[p + "0.running_var"], dtype)
+    if batch_stats:
+        mean, var = x.mean(0), x.var(0, unbiased=False)
+    else:
+        mean, var = _t(sd[p + "0.running_mean"], dtype), _t(sd[p + "0.running_var"], dtype)
     x = (x - mean) / torch.sqrt(var + 1e-5) * _t(sd[p + "0.weight"], dtype) + _t(sd[p + "0.bias"], dtype)
     x = x @ _t(sd[p + "1.weight"], dtype).t() + _t(sd[p + "1.bias"], dtype)
     return torch.relu(x)
@@ -153,6 +157,33 @@ def encoder_layer(sd, cfg, x, l, dtype):
     return y + x
 
 
+def head_weights(sd, cfg, dtype):
+    """(W [n_out, 576], b [n_out]) of the classifier: rel_out, or the MEET heads stacked (expert-major, then group)."""
+    pre = cfg.prefix
+    if cfg.meet_groups is None:
+        return _t(sd[pre + "rel_out.weight"], dtype), _t(sd[pre + "rel_out.bias"], dtype)
+    if cfg.experts:   # :3833-3837 rel_out_group[j][k]; columns expert-major, then group
+        names = [pre + "rel_out_group.%d.%d" % (e, k) for e in range(cfg.experts) for k in range(len(cfg.meet_groups))]
+    else:
+        names = [pre + "rel_out.%d" % k for k in range(len(cfg.meet_groups))]
+    return torch.cat([_t(sd[n + ".weight"], dtype) for n in names]), torch.cat([_t(sd[n + ".bias"], dtype) for n in names])
+
+
+def pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype):
+    """The [len(s), 19, 576] token rows of the pairs (s, o): the materialised pair gathers of :4118-4123 and
+    build_tokens."""
+    pre = cfg.prefix
+    rel_location = torch.cat([pos[s], pos[o]], dim=1)
+    rel_location = torch.relu(rel_location @ _t(sd[pre + "location_projection.0.weight"], dtype).t()
+                              + _t(sd[pre + "location_projection.0.bias"], dtype))
+    rel_class = torch.cat([emb[s], emb[o]], dim=1)
+    rel_class = torch.relu(rel_class @ _t(sd[pre + "class_projection.0.weight"], dtype).t()
+                           + _t(sd[pre + "class_projection.0.bias"], dtype))
+    rel_visual = torch.cat([rgb[s], rgb[o]], dim=1)
+    rel_depth = torch.cat([dep[s], dep[o]], dim=1)
+    return build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype)
+
+
 def forward(sd, cfg, batch, rel_pair_idxs=None, dtype=torch.float32, return_intermediates=False,
             pair_chunk=4096):
     """Eval forward of VETOPredictor (roi_relation_predictors.py:4074-4139) or, with
@@ -176,30 +207,12 @@ def forward(sd, cfg, batch, rel_pair_idxs=None, dtype=torch.float32, return_inte
     rgb = _t(batch["roi_features"], dtype)
     dep = _t(batch["roi_depth_features"], dtype)
 
-    if cfg.meet_groups is None:
-        Wh = _t(sd[pre + "rel_out.weight"], dtype)
-        bh = _t(sd[pre + "rel_out.bias"], dtype)
-    elif cfg.experts:   # :3833-3837 rel_out_group[j][k]; columns expert-major, then group
-        names = [pre + "rel_out_group.%d.%d" % (e, k) for e in range(cfg.experts) for k in range(len(cfg.meet_groups))]
-        Wh = torch.cat([_t(sd[n + ".weight"], dtype) for n in names])
-        bh = torch.cat([_t(sd[n + ".bias"], dtype) for n in names])
-    else:
-        Wh = torch.cat([_t(sd[pre + "rel_out.%d.weight" % k], dtype) for k in range(len(cfg.meet_groups))])
-        bh = torch.cat([_t(sd[pre + "rel_out.%d.bias" % k], dtype) for k in range(len(cfg.meet_groups))])
+    Wh, bh = head_weights(sd, cfg, dtype)
 
     logits, inter = [], {"tokens": [], "cls": []}
     for c0 in range(0, len(subj), pair_chunk):
         s, o = subj_t[c0:c0 + pair_chunk], obj_t[c0:c0 + pair_chunk]
-        # :4118-4123 -- the materialised pair gathers
-        rel_location = torch.cat([pos[s], pos[o]], dim=1)
-        rel_location = torch.relu(rel_location @ _t(sd[pre + "location_projection.0.weight"], dtype).t()
-                                  + _t(sd[pre + "location_projection.0.bias"], dtype))
-        rel_class = torch.cat([emb[s], emb[o]], dim=1)
-        rel_class = torch.relu(rel_class @ _t(sd[pre + "class_projection.0.weight"], dtype).t()
-                               + _t(sd[pre + "class_projection.0.bias"], dtype))
-        rel_visual = torch.cat([rgb[s], rgb[o]], dim=1)
-        rel_depth = torch.cat([dep[s], dep[o]], dim=1)
-        x = build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype)
+        x = pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype)
         if return_intermediates:
             inter["tokens"].append(x)
         for l in range(cfg.layers):

@@ -347,6 +347,40 @@ def test_relation_head_training_branch_end_to_end():
     # the chain veto_backward -> d roi maps -> veto_roi_pool_backward -> feature maps is connected
     assert depth.grad is not None and torch.isfinite(depth.grad).all() and float(depth.grad.abs().max()) > 0
     assert feats[1].grad is not None and torch.isfinite(feats[1].grad).all()
+    # the same branch once more with dropout off, against oracle/train_oracle.py on the pair lists and labels the head's sampler drew
+    # (taken from the predictor call itself): every element of every predictor parameter gradient
+    from oracle import train_oracle as to
+    from oracle import veto_oracle as vo
+    for m in head.predictor.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.p = 0.0
+    for p in head.predictor.parameters():
+        p.grad = None
+    seen = {}
+    hook = head.predictor.register_forward_pre_hook(lambda mod, args, kwargs: seen.update(args=args, kwargs=kwargs), with_kwargs=True)
+    _, _, losses = head(feats, props, targets=targets, depth_features=depth, logger=None, x=None)
+    hook.remove()
+    losses["rel_loss"].backward()
+    s_props, s_pairs, s_labels = seen["args"][0], seen["args"][1], seen["args"][2]
+    assert [int(p.shape[0]) for p in s_pairs] == [7 * 6, 5 * 4] and sum(int((l > 0).sum()) for l in s_labels) > 0
+    obatch = {"num_objs": [len(p) for p in s_props], "boxes": torch.cat([p.bbox for p in s_props]).cpu().numpy(),
+              "labels": torch.cat([p.get_field("labels") for p in s_props]).cpu().numpy(),
+              "roi_features": seen["kwargs"]["roi_features"].detach().cpu().numpy(),
+              "roi_depth_features": seen["kwargs"]["roi_depth_features"].detach().cpu().numpy()}
+    ref = to.train_step(synth.predictor_state_dict(3, layers=2), vo.OracleConfig(2, 8), obatch, [p.cpu().numpy() for p in s_pairs],
+                        torch.cat(list(s_labels)).cpu().numpy())
+    assert abs(float(losses["rel_loss"].detach()) - ref["losses"]["rel_loss"]) < 2e-4 * max(1.0, ref["losses"]["rel_loss"])
+    params = dict(head.predictor.named_parameters())
+    worst = 0.0
+    for name, want in ref["grads"].items():
+        got = params[name].grad.detach().cpu().double().reshape(-1)
+        want = want.reshape(-1)
+        scale = max(float(want.abs().max()), float(want.norm()) / want.numel() ** 0.5, 1e-8)
+        err = float((got - want).abs().max()) / scale
+        nerr = abs(float(got.norm()) - float(want.norm())) / max(float(want.norm()), 1e-8)
+        worst = max(worst, err, nerr)
+        assert err < 2e-3 and nerr < 2e-3, (name, err, nerr)
+    print("relation head training branch: worst relative gradient error against the oracle %.2e over %d parameters" % (worst, len(ref["grads"])))
 
 
 @pytest.mark.gpu

@@ -2413,6 +2413,22 @@ int veto_debug_attention_backward(void* stream, const float* qkv, const float* d
   return VETO_OK;
 }
 
+int veto_debug_attention_backward_forms(void* stream, const void* qkv, const float* dout, void* dqkv, float* qkv_unpacked, int32_t n_pair,
+                                        int32_t heads, uint32_t flags) {
+  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (flags & ~(uint32_t)(VETO_ATTN_BWD_CLS_ONLY | VETO_ATTN_BWD_QKV_F24 | VETO_ATTN_BWD_SPLIT_OUT)) return fail(VETO_ERR_INVALID, "unknown flag");
+  const bool f24 = (flags & VETO_ATTN_BWD_QKV_F24) != 0, split = (flags & VETO_ATTN_BWD_SPLIT_OUT) != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (qkv_unpacked) {
+    if (!f24) return fail(VETO_ERR_INVALID, "qkv_unpacked goes with VETO_ATTN_BWD_QKV_F24");
+    HIP_TRY(launch_unpack_f24(qkv, qkv_unpacked, (size_t)n_pair * kTokens * 3 * kDim, s));
+  }
+  hipError_t e = launch_attention_backward((const float*)qkv, dout, split ? nullptr : (float*)dqkv, split ? (__bf16*)dqkv : nullptr, n_pair, heads,
+                                           (flags & VETO_ATTN_BWD_CLS_ONLY) ? 1 : 0, s, f24);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (head width 72, 96 or 144; 3-byte q / k / v with 72 or 96 only)", hipGetErrorString(e));
+  return VETO_OK;
+}
+
 size_t veto_debug_layernorm_backward_workspace_bytes(int32_t rows) { return rows > 0 ? layernorm_backward_partial_floats(rows) * 4 : 0; }
 
 int veto_debug_layernorm_backward(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
@@ -2420,6 +2436,19 @@ int veto_debug_layernorm_backward(void* stream, const float* x, const float* dy,
   if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
   if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
   HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int32_t veto_debug_layernorm_backward_col_partial_rows(int32_t rows) { return rows > 0 ? layernorm_backward_col_partials(rows) : 0; }
+
+int veto_debug_layernorm_backward_split(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
+                                        float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
+                                        uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !split_rows || !col_partials || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
+                                    col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale));
   return VETO_OK;
 }
 

@@ -9,8 +9,8 @@ import os
 # mapped BEFORE libveto_amd.so so that the library's NEEDED libamdhip64.so.7 resolves to that same copy;
 # the other order maps two runtimes into the process and the second one finds no device.
 import torch  # noqa: F401
-from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32, c_int64,
-                    c_size_t, c_void_p)
+from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
+                    c_size_t, c_uint32, c_uint64, c_void_p)
 
 _LIB = None
 
@@ -26,6 +26,7 @@ EXPORTS = [
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
+    "veto_debug_attention_backward_forms", "veto_debug_layernorm_backward_split", "veto_debug_layernorm_backward_col_partial_rows",
     "veto_debug_wgrad", "veto_debug_wgrad_workspace_bytes", "veto_ce_loss", "veto_ce_loss_workspace_bytes", "veto_meet_sample",
     "veto_roi_pool", "veto_roi_pool_backward", "veto_sgg_eval", "veto_sgg_eval_workspace_bytes",
 ]
@@ -247,6 +248,11 @@ def load_library():
     lib.veto_debug_layernorm_backward_workspace_bytes.restype = c_size_t
     lib.veto_debug_layernorm_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                                   c_void_p, c_size_t]
+    lib.veto_debug_attention_backward_forms.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint32]
+    lib.veto_debug_layernorm_backward_col_partial_rows.argtypes = [c_int32]
+    lib.veto_debug_layernorm_backward_col_partial_rows.restype = c_int32
+    lib.veto_debug_layernorm_backward_split.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_int32, c_uint64, c_uint32, c_float, c_void_p, c_size_t]
     lib.veto_debug_gelu_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
     lib.veto_debug_column_sums.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t]
     lib.veto_ce_loss_workspace_bytes.argtypes = [c_int32]
