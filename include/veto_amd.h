@@ -18,6 +18,7 @@
  *                             Ensemble.nms_per_cls (MEET decoder)   roi_relation_predictors.py:3855-3874
  *   veto_nms               <- pysgg._C.nms / boxlist_nms            csrc/cuda/nms.cu, structures/boxlist_ops.py:10-32
  *   veto_box_postprocess   <- PostProcessor (box head)              roi_heads/box_head/inference.py:51-238
+ *   veto_rpn_proposals     <- RPNPostProcessor                      rpn/inference.py:13-183
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -371,6 +372,56 @@ typedef struct veto_box_post_args {
 
 size_t veto_box_postprocess_workspace_bytes(int32_t n_box, int32_t n_cls, int32_t filter_duplicates);
 int veto_box_postprocess(void* stream, const veto_box_post_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_rpn_proposals: RPNPostProcessor.forward (rpn/inference.py:78-183) for a batch of n_img images and n_lvl pyramid levels,
+ * three launches (four in per-batch mode) whatever n_img and n_lvl are, nothing copied to the host.  The RPN head's outputs are
+ * read in place: objectness[l] [n_img, A, H, W] logits, box_regression[l] [n_img, 4A, H, W], anchors[l] [A H W, 4] xyxy with
+ * anchor (h W + w) A + a (permute_and_flatten, rpn/utils.py:10-14) whose regression of coordinate c is channel 4a + c.
+ *   per image x level: the k = min(pre_nms_top_n, A H W) best anchors in the total order (logit desc, anchor index asc) -- one
+ *   of the orders sigmoid().topk(sorted=True) may give; BoxCoder.decode (box_coder.py:62-95: reg_weights, dw / dh clamped at
+ *   bbox_xform_clip, the - 1 on x2 / y2); every coordinate clamped to [0, size - 1]; candidates with x2 - x1 + 1 < min_size or
+ *   y2 - y1 + 1 < min_size dropped (remove_small_boxes); veto_nms at nms_thresh over the rest, the first post_nms_top_n (> 0)
+ *   survivors kept, best first.  nms_thresh <= 0: no NMS and no cap (boxlist_ops.py:22-23).
+ *   per image, n_lvl > 1 (select_over_all_levels, :156-183): per_batch 0 -- the min(fpn_post_nms_top_n, count) best of all
+ *   levels in the order (logit desc, level asc, rank asc); per_batch 1 (training with FPN_POST_NMS_PER_BATCH) -- one
+ *   top-fpn_post_nms_top_n over the whole batch (ties: image, level, rank), each image keeping its members level-major, rank
+ *   ascending.  n_lvl == 1: the level's survivors.
+ * objectness out = 1 / (1 + exp(-logit)).  Image i writes counts[i] rows from img_out_offset[i]; when its capacity
+ * img_out_offset[i + 1] - img_out_offset[i] is too small nothing is written for it and counts[i] = -(rows needed).
+ * Limits, checked before anything is launched: n_lvl 1..VETO_RPN_MAX_LEVELS; pre_nms_top_n 1..veto_nms_max_segment() (the
+ * reference default PRE_NMS_TOP_N_TRAIN = 12000 is above it, the VETO configuration's 6000 is not); per_batch 0 with
+ * n_lvl > 1: the levels' survivor bounds (min(post_nms_top_n, k), or k without NMS or cap) add up to at most 8192; per_batch 1:
+ * n_img <= 1024.  A level may hold up to 2^31 - 1 anchors. */
+#define VETO_RPN_MAX_LEVELS 8
+typedef struct veto_rpn_args {
+  int32_t struct_size;
+  int32_t n_img, n_lvl;
+  int32_t pre_nms_top_n;              /* MODEL.RPN.PRE_NMS_TOP_N_{TRAIN,TEST} */
+  int32_t post_nms_top_n;             /* MODEL.RPN.POST_NMS_TOP_N_*, <= 0: none */
+  int32_t fpn_post_nms_top_n;         /* MODEL.RPN.FPN_POST_NMS_TOP_N_*, > 0 when n_lvl > 1 */
+  int32_t per_batch;                  /* training && MODEL.RPN.FPN_POST_NMS_PER_BATCH */
+  float nms_thresh;                   /* MODEL.RPN.NMS_THRESH */
+  float min_size;                     /* MODEL.RPN.MIN_SIZE */
+  float bbox_xform_clip;              /* log(1000 / 16) */
+  float reg_weights[4];               /* (1, 1, 1, 1) */
+  int32_t level_a[VETO_RPN_MAX_LEVELS];   /* HOST: anchors per location, height and width of every level */
+  int32_t level_h[VETO_RPN_MAX_LEVELS];
+  int32_t level_w[VETO_RPN_MAX_LEVELS];
+  const float* objectness[VETO_RPN_MAX_LEVELS];      /* device [n_img, A, H, W] */
+  const float* box_regression[VETO_RPN_MAX_LEVELS];  /* device [n_img, 4A, H, W] */
+  const float* anchors[VETO_RPN_MAX_LEVELS];         /* device [A H W, 4] xyxy, 16-byte aligned */
+  const float* image_sizes;           /* device [n_img, 2]: (width, height) */
+  const int32_t* img_out_offset;      /* device [n_img + 1] */
+  float* boxes;                       /* out device [img_out_offset[n_img], 4], 16-byte aligned */
+  float* objectness_out;              /* out device, same rows */
+  int32_t* level;                     /* out device: pyramid level of the row */
+  int64_t* anchor_index;              /* out device: anchor index inside that level */
+  int32_t* counts;                    /* out device [n_img] */
+} veto_rpn_args_t;
+
+/* reads the host fields of `args` only (n_img, n_lvl, pre_nms_top_n, level_a / level_h / level_w); 0 when they are out of range */
+size_t veto_rpn_proposals_workspace_bytes(const veto_rpn_args_t* args);
+int veto_rpn_proposals(void* stream, const veto_rpn_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* veto_detect_relsample: RelationSampling.detect_relsample (sampling.py:109-176) with motif_rel_fg_bg_sampling (:179-309),
  * the training-time relation sampler on detected boxes, for a ragged batch (one workgroup per image).  Per image:

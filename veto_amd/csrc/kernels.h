@@ -350,6 +350,50 @@ struct BoxPostArgs {
   int32_t* counts;               // out [n_img]; -count when an image's rows do not hold its detections
 };
 hipError_t launch_box_postprocess(const BoxPostArgs& a, int max_per_img, hipStream_t s);
+// The same NMS for fixed-capacity segments: segment s owns rows s * capacity .. + capacity, of which the first live[s]
+// (device memory, clamped to the capacity) count.  The instantiation is picked from the capacity.
+struct NmsFixedArgs {
+  const float* boxes;            // [n_seg * capacity, 4] xyxy, 16-byte aligned
+  const float* scores;           // [n_seg * capacity]
+  const int32_t* live;           // [n_seg]
+  int n_seg, capacity, max_keep;
+  float thr;
+  int32_t* keep;                 // out [n_seg * capacity]: segment s writes counts[s] local indices from s * capacity
+  int32_t* counts;               // out [n_seg]
+};
+hipError_t launch_nms_fixed(const NmsFixedArgs& a, hipStream_t s);
+
+// ---- RPN proposal selection: top-k, decode, clip, small boxes, NMS, merge over the levels (rpn.hip) -----------------
+constexpr int kRpnMaxLevels = 8;
+constexpr int kRpnSortCap = 8192;   // 64-bit keys one workgroup sorts in LDS
+struct RpnLevel {
+  const float* objectness;       // [n_img, A, H, W]
+  const float* regression;       // [n_img, 4A, H, W]
+  const float* anchors;          // [A * H * W, 4] xyxy, anchor (h * W + w) * A + a
+  int A, HW, N, k;               // N = A * HW, k = min(pre_nms_top_n, N)
+};
+struct RpnArgs {
+  RpnLevel lvl[kRpnMaxLevels];   // the per-level descriptor table: every kernel serves all levels from one grid
+  const float* image_sizes;      // [n_img, 2] (width, height)
+  const int32_t* out_off;        // [n_img + 1]
+  int n_img, n_lvl, capacity;    // capacity = max k over the levels: rows of a segment (image x level) in the workspace
+  int post_top_n, fpn_top_n, per_batch, nms_on;
+  float nms_thresh, min_size, wx, wy, ww, wh, xform_clip;
+  float* cand_box;               // workspace [n_seg * capacity, 4]: decoded, clipped, filtered candidates, best first
+  float* cand_logit;             // workspace [n_seg * capacity]
+  int32_t* cand_anchor;          // workspace [n_seg * capacity]
+  int32_t* live;                 // workspace [n_seg]: candidates behind the small-box filter
+  int32_t* keep;                 // workspace [n_seg * capacity]: NMS survivors (candidate rows), ascending
+  int32_t* kept;                 // workspace [n_seg]
+  int32_t* cut;                  // workspace [4 + n_img] (per-batch mode): cut on, key, need, -, equal keys in earlier images
+  float* boxes;                  // out [.., 4]
+  float* objectness;             // out
+  int32_t* level;                // out
+  int64_t* anchor_index;         // out
+  int32_t* counts;               // out [n_img]
+};
+int rpn_batch_cut_max_images();
+hipError_t launch_rpn_proposals(const RpnArgs& a, hipStream_t s);
 
 // ---- sgdet training: detected-box relation sampling (relsample.hip) ---------------------------------
 struct RelSampleArgs {

@@ -14,6 +14,7 @@
 //   64 x 64 suppression words of the block itself (lane i: bits j > i), walks them serially (64 uniform steps) and
 //   appends the survivors to the kept list.  No n x n/64 mask is ever stored and nothing leaves the device.
 //   Three instantiations by capacity (LDS per workgroup): 256 boxes (6 KiB), 1024 (18 KiB), 6144 (113 KiB, 1024 threads).
+//   nms_fixed_kernel is the same for fixed-capacity segments whose live counts are known only on the device (rpn.hip).
 //
 // PostProcessor.forward + filter_results (box_head/inference.py:51-238) for a whole batch, four launches:
 //   box_decode_kernel   one wave per proposal: softmax(class_logits), BoxCoder.decode (box_coder.py:62-95) of every
@@ -164,6 +165,35 @@ __global__ __launch_bounds__(NT) void nms_kernel(NmsArgs a) {
   const int seg = blockIdx.x, tid = threadIdx.x;
   const int off = a.seg_off[seg], n = a.seg_off[seg + 1] - off;
   if (n <= 0 || n > CAP) {   // the ABI checked the sizes on the host; never index LDS past CAP
+    if (tid == 0) a.counts[seg] = 0;
+    return;
+  }
+  for (int t = tid; t < CAP / 32; t += NT) L.keep[t] = 0;
+  unsigned long long* keys = (unsigned long long*)L.raw;
+  for (int t = tid; t < n; t += NT) keys[t] = nms_key(a.scores[off + t], t);
+  const float4* boxes = (const float4*)a.boxes + off;
+  segment_nms<CAP, NT>(L, n, a.thr, [&](int i) { return boxes[i]; });
+  uint32_t word;
+  int total;
+  int rank = keep_ranks<CAP, NT>(L, &word, &total);
+  const int limit = a.max_keep > 0 ? min(a.max_keep, total) : total;
+  while (word && rank < limit) {
+    a.keep[off + rank] = tid * 32 + __ffs(word) - 1;
+    word &= word - 1;
+    ++rank;
+  }
+  if (tid == 0) a.counts[seg] = limit;
+}
+
+// The same for fixed-capacity segments whose live counts exist only on the device (the RPN's candidates behind its small-box
+// filter): rows s * capacity .. + live[s].
+template <int CAP, int NT>
+__global__ __launch_bounds__(NT) void nms_fixed_kernel(NmsFixedArgs a) {
+  __shared__ NmsLds<CAP, NT> L;
+  const int seg = blockIdx.x, tid = threadIdx.x;
+  const size_t off = (size_t)seg * a.capacity;
+  const int n = min(a.live[seg], min(a.capacity, CAP));   // never index LDS past CAP
+  if (n <= 0) {
     if (tid == 0) a.counts[seg] = 0;
     return;
   }
@@ -366,6 +396,13 @@ hipError_t launch_nms(const NmsArgs& a, int max_seg, hipStream_t s) {
   if (max_seg <= 256) VETO_LAUNCH((nms_kernel<256, 256>), dim3(a.n_seg), dim3(256), 0, s, a);
   else if (max_seg <= 1024) VETO_LAUNCH((nms_kernel<1024, 256>), dim3(a.n_seg), dim3(256), 0, s, a);
   else VETO_LAUNCH((nms_kernel<kNmsMaxSeg, 1024>), dim3(a.n_seg), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_nms_fixed(const NmsFixedArgs& a, hipStream_t s) {
+  if (a.capacity <= 256) VETO_LAUNCH((nms_fixed_kernel<256, 256>), dim3(a.n_seg), dim3(256), 0, s, a);
+  else if (a.capacity <= 1024) VETO_LAUNCH((nms_fixed_kernel<1024, 256>), dim3(a.n_seg), dim3(256), 0, s, a);
+  else VETO_LAUNCH((nms_fixed_kernel<kNmsMaxSeg, 1024>), dim3(a.n_seg), dim3(1024), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1755,6 +1755,95 @@ int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* work
   return VETO_OK;
 }
 
+// the host fields of the RPN arguments: capacity = the largest k of a level, or -1 (error set)
+static int rpn_check_shapes(const veto_rpn_args_t* a) {
+  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
+  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  if (a->pre_nms_top_n <= 0 || a->pre_nms_top_n > nms_max_segment())
+    return fail(VETO_ERR_INVALID, "pre_nms_top_n %d outside 1..%d (MODEL.RPN.PRE_NMS_TOP_N; the limit is veto_nms_max_segment())",
+                a->pre_nms_top_n, nms_max_segment());
+  int capacity = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
+      return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+    const int64_t n = (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+    if (n > INT32_MAX) return fail(VETO_ERR_INVALID, "level %d holds %lld anchors, the limit is %d", l, (long long)n, INT32_MAX);
+    const int k = n < a->pre_nms_top_n ? (int)n : a->pre_nms_top_n;
+    if (k > capacity) capacity = k;
+  }
+  return capacity;
+}
+
+// workspace: cand_box | cand_logit | cand_anchor | keep | live | kept | cut
+size_t veto_rpn_proposals_workspace_bytes(const veto_rpn_args_t* a) {
+  if (!a || a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return 0;
+  const int capacity = rpn_check_shapes(a);
+  if (capacity < 0) return 0;
+  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
+  return align_up(rows * 16, 256) + 3 * align_up(rows * 4, 256) + 2 * align_up(n_seg * 4, 256) + align_up((4 + (size_t)a->n_img) * 4, 256);
+}
+
+int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return fail(VETO_ERR_INVALID, "veto_rpn_args_t size mismatch");
+  const int capacity = rpn_check_shapes(a);
+  if (capacity < 0) return capacity;
+  const bool nms_on = a->nms_thresh > 0.f, merge = a->n_lvl > 1;
+  if (merge && a->fpn_post_nms_top_n <= 0) return fail(VETO_ERR_INVALID, "fpn_post_nms_top_n %d must be > 0 with %d levels", a->fpn_post_nms_top_n, a->n_lvl);
+  for (int k = 0; k < 4; ++k)
+    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0", k, a->reg_weights[k]);
+  if (merge && a->per_batch) {
+    if (a->n_img > rpn_batch_cut_max_images())
+      return fail(VETO_ERR_INVALID, "per_batch: n_img %d above %d", a->n_img, rpn_batch_cut_max_images());
+  } else if (merge) {   // the per-image merge sorts every survivor of the image in one workgroup
+    int64_t bound = 0;
+    for (int l = 0; l < a->n_lvl; ++l) {
+      const int64_t n = (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+      const int64_t k = n < a->pre_nms_top_n ? n : a->pre_nms_top_n;
+      bound += nms_on && a->post_nms_top_n > 0 && a->post_nms_top_n < k ? a->post_nms_top_n : k;
+    }
+    if (bound > kRpnSortCap)
+      return fail(VETO_ERR_INVALID, "the levels may leave %lld proposals per image, the merge takes %d (lower post_nms_top_n)", (long long)bound,
+                  kRpnSortCap);
+  }
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (!a->objectness[l] || !a->box_regression[l] || !a->anchors[l]) return fail(VETO_ERR_INVALID, "missing pointer: level %d", l);
+    if (((uintptr_t)a->anchors[l] & 15) != 0) return fail(VETO_ERR_INVALID, "anchors[%d] must be 16-byte aligned", l);
+    if ((((uintptr_t)a->objectness[l] | (uintptr_t)a->box_regression[l]) & 3) != 0) return fail(VETO_ERR_INVALID, "level %d: misaligned floats", l);
+  }
+  if (!a->image_sizes || !a->img_out_offset || !a->boxes || !a->objectness_out || !a->level || !a->anchor_index || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (((uintptr_t)a->boxes & 15) != 0) return fail(VETO_ERR_INVALID, "boxes must be 16-byte aligned");
+  const size_t need = veto_rpn_proposals_workspace_bytes(a);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  RpnArgs p{};
+  for (int l = 0; l < a->n_lvl; ++l) {
+    RpnLevel& v = p.lvl[l];
+    v.objectness = a->objectness[l]; v.regression = a->box_regression[l]; v.anchors = a->anchors[l];
+    v.A = a->level_a[l]; v.HW = a->level_h[l] * a->level_w[l]; v.N = v.A * v.HW;
+    v.k = v.N < a->pre_nms_top_n ? v.N : a->pre_nms_top_n;
+  }
+  p.image_sizes = a->image_sizes; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.n_lvl = a->n_lvl; p.capacity = capacity;
+  p.post_top_n = a->post_nms_top_n; p.fpn_top_n = a->fpn_post_nms_top_n; p.per_batch = a->per_batch != 0; p.nms_on = nms_on;
+  p.nms_thresh = a->nms_thresh; p.min_size = a->min_size;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.xform_clip = a->bbox_xform_clip;
+  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
+  char* base = (char*)workspace;
+  p.cand_box = (float*)base; base += align_up(rows * 16, 256);
+  p.cand_logit = (float*)base; base += align_up(rows * 4, 256);
+  p.cand_anchor = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.keep = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.live = (int32_t*)base; base += align_up(n_seg * 4, 256);
+  p.kept = (int32_t*)base; base += align_up(n_seg * 4, 256);
+  p.cut = (int32_t*)base;
+  p.boxes = a->boxes; p.objectness = a->objectness_out; p.level = a->level; p.anchor_index = a->anchor_index; p.counts = a->counts;
+  HIP_TRY(launch_rpn_proposals(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel) {
   if (n_rel_cells <= 0 || num_sample_per_gt_rel <= 0) return 256;
   return align_up((size_t)n_rel_cells * 8, 256) + align_up((size_t)n_rel_cells * num_sample_per_gt_rel * 4, 256);

@@ -23,6 +23,7 @@ EXPORTS = [
     "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
     "veto_detect_relsample", "veto_detect_relsample_workspace_bytes", "veto_gtbox_relsample",
     "veto_nms", "veto_nms_max_segment", "veto_box_postprocess", "veto_box_postprocess_workspace_bytes",
+    "veto_rpn_proposals", "veto_rpn_proposals_workspace_bytes",
     "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
     "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
     "veto_debug_gelu_backward", "veto_debug_column_sums",
@@ -98,6 +99,20 @@ class VetoBoxPostArgs(Structure):
                [(n, c_void_p) for n in ("class_logits", "box_regression", "proposals", "image_sizes", "img_offset",
                                         "img_offset_host", "img_out_offset", "orig_inds", "pred_labels", "pred_scores",
                                         "boxes", "boxes_per_cls", "counts")]
+
+
+RPN_MAX_LEVELS = 8   # VETO_RPN_MAX_LEVELS
+
+
+class VetoRpnArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_lvl", "pre_nms_top_n", "post_nms_top_n", "fpn_post_nms_top_n",
+                                       "per_batch")] + \
+               [(n, ctypes.c_float) for n in ("nms_thresh", "min_size", "bbox_xform_clip")] + \
+               [("reg_weights", ctypes.c_float * 4)] + \
+               [(n, c_int32 * RPN_MAX_LEVELS) for n in ("level_a", "level_h", "level_w")] + \
+               [(n, c_void_p * RPN_MAX_LEVELS) for n in ("objectness", "box_regression", "anchors")] + \
+               [(n, c_void_p) for n in ("image_sizes", "img_out_offset", "boxes", "objectness_out", "level", "anchor_index",
+                                        "counts")]
 
 
 class VetoDetectRelsampleArgs(Structure):
@@ -232,6 +247,9 @@ def load_library():
     lib.veto_box_postprocess_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
     lib.veto_box_postprocess_workspace_bytes.restype = c_size_t
     lib.veto_box_postprocess.argtypes = [c_void_p, POINTER(VetoBoxPostArgs), c_void_p, c_size_t]
+    lib.veto_rpn_proposals_workspace_bytes.argtypes = [POINTER(VetoRpnArgs)]
+    lib.veto_rpn_proposals_workspace_bytes.restype = c_size_t
+    lib.veto_rpn_proposals.argtypes = [c_void_p, POINTER(VetoRpnArgs), c_void_p, c_size_t]
     lib.veto_detect_relsample_workspace_bytes.argtypes = [c_int32, c_int32]
     lib.veto_detect_relsample_workspace_bytes.restype = c_size_t
     lib.veto_detect_relsample.argtypes = [c_void_p, POINTER(VetoDetectRelsampleArgs), c_void_p, c_size_t]

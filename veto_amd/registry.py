@@ -69,3 +69,20 @@ def install_detector_ops():
     if head is not None and hasattr(head, "make_roi_box_post_processor"):
         head.make_roi_box_post_processor = boxhead.make_roi_box_post_processor
     return patched
+
+
+def install_rpn_ops():
+    """Point the reference's RPN at the device proposal selector: `pysgg.modeling.rpn.inference.make_rpn_postprocessor`
+    returns veto_amd.rpn.RPNPostProcessor.  `pysgg` must be importable.  Independent of install() and
+    install_detector_ops().  Returns the patched (module, name) pairs."""
+    import importlib
+    import sys
+    from . import rpn
+    setattr(importlib.import_module("pysgg.modeling.rpn.inference"), "make_rpn_postprocessor", rpn.make_rpn_postprocessor)
+    patched = [("pysgg.modeling.rpn.inference", "make_rpn_postprocessor")]
+    # rpn.py binds the factory by name when it is imported (rpn.py:10): re-point that binding too if it exists
+    head = sys.modules.get("pysgg.modeling.rpn.rpn")
+    if head is not None and hasattr(head, "make_rpn_postprocessor"):
+        head.make_rpn_postprocessor = rpn.make_rpn_postprocessor
+        patched.append(("pysgg.modeling.rpn.rpn", "make_rpn_postprocessor"))
+    return patched

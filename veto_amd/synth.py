@@ -522,3 +522,56 @@ def synthetic_box_head_outputs(seed, n, num_obj_cls=151, W=800, H=600, on_classe
     reg = normal(seed, tag + ".reg", (n, cols // 4, 4), 0.0, 1.0).astype(np.float64) * np.array([0.6, 0.6, 0.4, 0.4])
     return {"proposals": proposals, "class_logits": logits.astype(np.float32),
             "box_regression": reg.reshape(n, cols).astype(np.float32), "image_size": (W, H)}
+
+
+# ---------------------------------------------------------------------------
+# RPN proposal selection: anchors and the RPN head's raw outputs
+# ---------------------------------------------------------------------------
+
+def _cell_anchors(stride, sizes, aspect_ratios):
+    """The A = len(aspect_ratios) * len(sizes) anchors of one cell, ratio-major: windows around the centre of the
+    (0, 0, stride - 1, stride - 1) cell whose area is about size^2, with integer-rounded sides before scaling."""
+    ctr = 0.5 * (stride - 1)
+    out = []
+    for ratio in aspect_ratios:
+        w = float(np.round(np.sqrt(stride * stride / float(ratio))))
+        h = float(np.round(w * ratio))
+        for size in sizes:
+            scale = float(size) / stride
+            ws, hs = w * scale, h * scale
+            out.append([ctr - 0.5 * (ws - 1), ctr - 0.5 * (hs - 1), ctr + 0.5 * (ws - 1), ctr + 0.5 * (hs - 1)])
+    return np.asarray(out, np.float64)
+
+
+def anchor_grid(sizes, strides, aspect_ratios, grid_sizes):
+    """Per level l the [A * H * W, 4] xyxy float32 anchors of a (H, W) = grid_sizes[l] feature map with stride strides[l] and
+    anchor size(s) sizes[l]: anchor (h * W + w) * A + a is cell anchor a shifted by (w, h) * stride."""
+    out = []
+    for size, stride, (H, W) in zip(sizes, strides, grid_sizes):
+        cell = _cell_anchors(stride, size if isinstance(size, (tuple, list)) else (size,), aspect_ratios).astype(np.float32)
+        sx = (np.arange(W, dtype=np.float32) * np.float32(stride))[None, :].repeat(H, 0).reshape(-1)
+        sy = (np.arange(H, dtype=np.float32) * np.float32(stride))[:, None].repeat(W, 1).reshape(-1)
+        shifts = np.stack([sx, sy, sx, sy], 1)
+        out.append((shifts[:, None, :] + cell[None, :, :]).reshape(-1, 4).astype(np.float32))
+    return out
+
+
+def synthetic_rpn_outputs(seed, n_img, grid_sizes, A=3, W=800, H=608, peaks=6, background=-4.0, delta=(0.25, 0.25, 0.2, 0.2)):
+    """What the RPN head hands its post-processor: per level `objectness` [n_img, A, H_l, W_l] logits and `box_regression`
+    [n_img, 4A, H_l, W_l].  Every image has `peaks` objects; a cell's logits rise towards the nearest of them on every level (so
+    anchors of neighbouring cells and of several levels compete in NMS) over a noisy background, and the regression deltas
+    are small (shifts of a quarter of the anchor, log-scale changes of a fifth).  W, H: the image extent the peaks live in."""
+    objectness, regression = [], []
+    for l, (gh, gw) in enumerate(grid_sizes):
+        tag = "rpn.%d.%dx%d" % (l, gh, gw)
+        px = uniform(seed, "rpn.px", (n_img, peaks), 0.1, 0.9).astype(np.float64) * gw
+        py = uniform(seed, "rpn.py", (n_img, peaks), 0.1, 0.9).astype(np.float64) * gh
+        rad = uniform(seed, "rpn.rad", (n_img, peaks), 0.08, 0.2).astype(np.float64) * max(gw, gh) + 0.7
+        ys, xs = np.mgrid[0:gh, 0:gw]
+        d2 = (xs[None, None] + 0.5 - px[:, :, None, None]) ** 2 + (ys[None, None] + 0.5 - py[:, :, None, None]) ** 2
+        bump = (7.0 / (1.0 + d2 / rad[:, :, None, None] ** 2)).max(1)                           # [n_img, gh, gw]
+        noise = normal(seed, tag + ".noise", (n_img, A, gh, gw), 0.0, 1.0).astype(np.float64)
+        objectness.append((background + bump[:, None] + noise).astype(np.float32))
+        reg = normal(seed, tag + ".reg", (n_img, A, 4, gh, gw), 0.0, 1.0).astype(np.float64) * np.asarray(delta)[None, None, :, None, None]
+        regression.append(reg.reshape(n_img, 4 * A, gh, gw).astype(np.float32))
+    return {"objectness": objectness, "box_regression": regression}
