@@ -72,7 +72,7 @@ def default_config():
     # veto_amd extensions (absent from the reference config; read with getattr defaults)
     c.VETO_AMD = CfgNode()
     # what the token-row Linears compute in: "mixed" (fp16 main product + e4m3 correction terms, default: 2/3 of the matrix-pipe
-    # time of "precise" at 5-9e-5 logit error) | "precise" (3-term split bf16, 2-3e-5) | "fast" (single bf16 pass, ~1e-2: reported only)
+    # time of "precise" at 5-9e-5 logit error) | "precise" (3-term split bf16, 2-3e-5) | "fast" ("mixed" with the correction stages of the fused launches skipped, ~1.5e-3: reported only)
     c.VETO_AMD.PRECISION = "mixed"
     c.VETO_AMD.MAX_CHUNK_PAIRS = 0
     # True: eval forwards count, per layer and operand, the mixed-row elements that hit the e4m3 (448) / fp16 (65504) clamps of

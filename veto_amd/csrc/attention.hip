@@ -11,15 +11,6 @@
 // probabilities are already the A operand of the PV product (accumulator-as-operand, no LDS trip).
 // V is transposed on its way into LDS so the PV B operand is two 8-byte reads.
 // attention_kernel (generic head dim): fp32 on the vector ALU, LDS staged.
-// the attention output rows (mixed rows, read next by the layer tail) leave through non-temporal stores: table attention 0.60 -> 0.57 ms
-#ifndef ACT8_NT
-#define ACT8_NT 1
-#endif
-// folded CLS attention: bit 1 = the residual rows (read once) through non-temporal loads (0.254 -> 0.242 ms, adopted), bit 2 = the abar rows through
-// non-temporal stores (the GEMM behind reads them: 0.268 ms, not adopted)
-#ifndef CLS_NT
-#define CLS_NT 1
-#endif
 #include "common.h"
 #include "kernels.h"
 
@@ -109,15 +100,11 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a, int dh, int 
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 // Two fp32 values -> packed 16-bit hi and lo parts, x ~= hi + lo: the operand planes of the attention products (three MFMA terms hi hi + hi lo + lo hi).
-// ATT_F16_SPLIT (round 5, as qkv_attn_fused.hip): fp16 hi (11 significant bits) + fp16 lo, 22 bits in all, FOUR vector instructions per value pair
+// As in qkv_attn_fused.hip: fp16 hi (11 significant bits) + fp16 lo, 22 bits in all, FOUR vector instructions per value pair
 // (v_cvt_pk_f16_f32, two v_fma_mix_f32 that read the packed halves in place, v_cvt_pk_f16_f32); q / k / v are O(10) (LayerNorm'ed rows times weights), far
 // inside the fp16 range (the conversions saturate: MODE.FP16_OVFL is set), a lo part below 2^-24 is lost -- less than a bf16 lo keeps of such a value.
-// 0: bf16 hi + bf16 lo (16 bits, six instructions; rounds 1-4).
-#ifndef ATT_F16_SPLIT
-#define ATT_F16_SPLIT 1
-#endif
+// (bf16 hi + bf16 lo, 16 bits and six instructions, measured the same 0.532-0.537 ms at 1300 instead of 1226 vector instructions per item.)
 __device__ __forceinline__ void att_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-#if ATT_F16_SPLIT
   uint32_t h, l;
   float l0, l1;
   asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));      // (volatile: reads MODE, see mixed_pack4 in common.h)
@@ -126,21 +113,10 @@ __device__ __forceinline__ void att_split2(float a, float b, uint32_t& hi, uint3
   asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(l) : "v"(l0), "v"(l1));
   hi = h;
   lo = l;
-#else
-  __bf16 h0, l0, h1, l1;
-  split_bf16(a, h0, l0);
-  split_bf16(b, h1, l1);
-  hi = (uint32_t)__builtin_bit_cast(unsigned short, h0) | ((uint32_t)__builtin_bit_cast(unsigned short, h1) << 16);
-  lo = (uint32_t)__builtin_bit_cast(unsigned short, l0) | ((uint32_t)__builtin_bit_cast(unsigned short, l1) << 16);
-#endif
 }
 typedef _Float16 att_f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x16 att_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-#if ATT_F16_SPLIT
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(att_f16x8, a), __builtin_bit_cast(att_f16x8, b), c, 0, 0, 0);
-#else
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-#endif
 }
 typedef short att_s16x4 __attribute__((ext_vector_type(4)));
 typedef short att_s16x8 __attribute__((ext_vector_type(8)));
@@ -157,13 +133,7 @@ __device__ __forceinline__ void att_static_for(F&& f) {
     att_static_for<I + 1, N>(f);
   }
 }
-// waves (= items) per workgroup of attention_mfma_kernel
-#ifndef ATT_WPB
-#define ATT_WPB 2
-#endif
-#ifndef TAB_SPLIT_LOADS
-#define TAB_SPLIT_LOADS 1      // 0: every chunk of the table form requested up front (round 4; two waves per SIMD)
-#endif
+constexpr int kAttWpb = 2;      // waves (= items) per workgroup of attention_mfma_kernel (1 / 2 / 4 measured within noise: 0.475-0.534 ms)
 // -DVETO_ATT_STAMPS: a diagnostic build that sums s_memtime deltas per phase over all waves (tools/att_stamps.py prints them): where an
 // item's time goes -- issue of the gathers, the wait for their first use, conversion, S^T, softmax, V conversion, P V, the output stores
 #ifdef VETO_ATT_STAMPS
@@ -174,7 +144,7 @@ __device__ unsigned long long g_att_stamps[8192 * 10];      // one slot per item
 #define ATT_T(k)
 #endif
 template <int DH, bool TAB = false, bool F24 = false>
-__global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) ? 2 : 3) void attention_mfma_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64 * kAttWpb, TAB && DH > 72 ? 2 : 3) void attention_mfma_kernel(AttnArgs a) {
   static_assert(!(TAB && F24), "the per-object form reads fp32 tables");
   saturating_conversions_on();   // (the mixed-row output path converts without clamps, common.h)
 #ifdef VETO_ATT_STAMPS
@@ -207,7 +177,7 @@ __global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) 
   constexpr int PER_MAT = kTokens * CH;
   constexpr int ROUNDS = (3 * PER_MAT + 63) / 64;
   static_assert(DH % 8 == 0 && QK_PLANE % 16 == 0 && V_PLANE % 16 == 0, "layout");
-  __shared__ __attribute__((aligned(16))) char smem[ATT_WPB * WAVE_LDS];
+  __shared__ __attribute__((aligned(16))) char smem[kAttWpb * WAVE_LDS];
 
   // A wave works on its own LDS region: no workgroup barrier anywhere (LDS operations of one wave complete in order; the two
   // barriers of the first version cost 3 % of the launch).  Every wave has ONE item (persistent waves that prefetch their next
@@ -216,7 +186,7 @@ __global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) 
   // (the wave index as a SCALAR: item, pair, head and the table rows of the pair's objects are then wave-uniform to the compiler -- scalar loads of the
   // indices, SGPR base + 32-bit lane offset for every gather instead of 64-bit vector address arithmetic per load)
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long item = (long)blockIdx.x * ATT_WPB + w;
+  const long item = (long)blockIdx.x * kAttWpb + w;
   if (item >= (long)a.n_pair * a.heads) return;
   char* base = smem + w * WAVE_LDS;
   char* q_hi = base;
@@ -237,14 +207,11 @@ __global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) 
   constexpr int ROUNDS4 = (3 * PER_MAT4 + 63) / 64;
   f32x4 ld[TAB ? 1 : ROUNDS][2];      // (not TAB) a lane's 32-byte chunk of round r
   f32x4 lt[TAB ? ROUNDS4 : 1], lo_[TAB ? ROUNDS4 : 1];      // TAB: subject-side piece (or the plain row's), object-side piece
-  // item -> (pair, head), head fastest: neighbouring waves read adjacent 288-byte slices of the SAME table rows.  ATT_PAIR_FASTEST=1 (TAB only;
-  // measured SLOWER in round 6: 0.50 against 0.44 ms per launch): consecutive items = consecutive pairs of one head, i.e. the same subject-side
-  // rows for a run of pairs but a head's slice alone of every row
-#ifndef ATT_PAIR_FASTEST
-#define ATT_PAIR_FASTEST 0
-#endif
-  const int pair = TAB && ATT_PAIR_FASTEST ? (int)(item % a.n_pair) : (int)(item / a.heads);
-  const int head = TAB && ATT_PAIR_FASTEST ? (int)(item / a.n_pair) : (int)(item % a.heads);
+  // item -> (pair, head), head fastest: neighbouring waves read adjacent 288-byte slices of the SAME table rows.  (Pair fastest -- consecutive items =
+  // consecutive pairs of one head, i.e. the same subject-side rows for a run of pairs but a head's slice alone of every row -- measured SLOWER:
+  // 0.50 against 0.44 ms per launch)
+  const int pair = (int)(item / a.heads);
+  const int head = (int)(item % a.heads);
   const float* src0 = a.qkv + (size_t)pair * kTokens * (3 * kDim) + head * DH;
   const float* tab_s = nullptr;
   const float* tab_o = nullptr;
@@ -255,7 +222,7 @@ __global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) 
   // TAB: two table rows per piece are twice the registers in flight, so the pieces go out in two groups: the rounds that hold a Q or K
   // piece now, the V-only rounds behind the Q / K conversion (their latency then lies under S^T and the softmax) -- the kernel runs three
   // waves per SIMD without spilling (round 4 had two).
-  constexpr int kLateFrom = TAB ? (TAB_SPLIT_LOADS ? (2 * PER_MAT4 + 63) / 64 : ROUNDS4) : ROUNDS;     // first round without a Q / K piece
+  constexpr int kLateFrom = TAB ? (2 * PER_MAT4 + 63) / 64 : ROUNDS;     // first round without a Q / K piece
   constexpr int kRounds = TAB ? ROUNDS4 : ROUNDS;
   float* const c2_lds = (float*)(base + kImgBytes);                 // TAB: [3 DH] c2 of this head | [32] rstd of the pair's token rows
   float* const rs_lds = c2_lds + 3 * DH;
@@ -500,8 +467,8 @@ __global__ __launch_bounds__(64 * ATT_WPB, TAB && (!TAB_SPLIT_LOADS || DH > 72) 
     const f32x4 v0 = *(const f32x4*)(o_lds + i * DH + c * 8);
     const f32x4 v1 = *(const f32x4*)(o_lds + i * DH + c * 8 + 4);
     const size_t row = a.cls_only ? (size_t)pair : (size_t)pair * kTokens + i;
-    if (a.o_fmt == FMT_MIXED) {   // wave-uniform
-      store_act8_mixed<ACT8_NT != 0>(a.o + row * (2 * kDim), head * DH + c * 8, v0, v1);
+    if (a.o_fmt == FMT_MIXED) {   // wave-uniform; non-temporal stores (the layer tail reads the rows next): table attention 0.60 -> 0.57 ms
+      store_act8_mixed<true>(a.o + row * (2 * kDim), head * DH + c * 8, v0, v1);
       continue;
     }
     bf16x8 hi, lo;
@@ -725,11 +692,8 @@ __global__ __launch_bounds__(256, 3) void cls_fold_attention_mfma_kernel(const f
   f32x4 vrow[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
-#if CLS_NT & 1
+    // (read once: non-temporal loads, 0.254 -> 0.242 ms)
     vrow[i] = __builtin_nontemporal_load((const f32x4*)(xp + (size_t)j0 * kDim + 4 * (q + 16 * i)));
-#else
-    vrow[i] = *(const f32x4*)(xp + (size_t)j0 * kDim + 4 * (q + 16 * i));
-#endif
   }
   float vx[9];
   if (16 + w < kTokens) {
@@ -918,13 +882,8 @@ __global__ __launch_bounds__(256, 3) void cls_fold_attention_mfma_kernel(const f
       lo[t] = ll;
     }
     __bf16* d = dst + split_index(e);
-#if CLS_NT & 2
-    __builtin_nontemporal_store(hi, (bf16x4*)d);
-    __builtin_nontemporal_store(lo, (bf16x4*)(d + 32));
-#else
-    *(bf16x4*)d = hi;
+    *(bf16x4*)d = hi;      // (plain stores: the GEMM behind reads the rows; non-temporal measured 0.268 against 0.254 ms)
     *(bf16x4*)(d + 32) = lo;
-#endif
   }
   CST(12);
 }
@@ -975,11 +934,11 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   const int dh = kDim / a.heads;
   if (dh == 72 || dh == 96) {
     const long items = (long)a.n_pair * a.heads;
-    unsigned blocks = (unsigned)((items + ATT_WPB - 1) / ATT_WPB);
+    unsigned blocks = (unsigned)((items + kAttWpb - 1) / kAttWpb);
     if (a.sw) {
       if (!a.ow || !a.stats || !a.vec || !a.subj || !a.obj || a.cls_only) return hipErrorInvalidValue;
-      if (dh == 72) VETO_LAUNCH((attention_mfma_kernel<72, true>), dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
-      else VETO_LAUNCH((attention_mfma_kernel<96, true>), dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
+      if (dh == 72) VETO_LAUNCH((attention_mfma_kernel<72, true>), dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
+      else VETO_LAUNCH((attention_mfma_kernel<96, true>), dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
 #ifdef VETO_ATT_STAMPS
       {
         static unsigned long long all[8192 * 10];
@@ -1000,10 +959,10 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
       }
 #endif
     } else if (a.qkv_f24) {
-      if (dh == 72) VETO_LAUNCH((attention_mfma_kernel<72, false, true>), dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
-      else VETO_LAUNCH((attention_mfma_kernel<96, false, true>), dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
-    } else if (dh == 72) VETO_LAUNCH(attention_mfma_kernel<72>, dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
-    else VETO_LAUNCH(attention_mfma_kernel<96>, dim3(blocks), dim3(64 * ATT_WPB), 0, s, a);
+      if (dh == 72) VETO_LAUNCH((attention_mfma_kernel<72, false, true>), dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
+      else VETO_LAUNCH((attention_mfma_kernel<96, false, true>), dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
+    } else if (dh == 72) VETO_LAUNCH(attention_mfma_kernel<72>, dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
+    else VETO_LAUNCH(attention_mfma_kernel<96>, dim3(blocks), dim3(64 * kAttWpb), 0, s, a);
     return hipGetLastError();
   }
   if (a.sw || a.qkv_f24) return hipErrorInvalidValue;

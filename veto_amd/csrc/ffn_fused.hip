@@ -43,7 +43,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-// timing ablations (tools/ffn_variants.sh; results are WRONG with any of them set): 1 = no DMA, 2 = no MFMA, 4 = no fragment
+// timing ablations (tools/variants.sh; results are WRONG with any of them set): 1 = no DMA, 2 = no MFMA, 4 = no fragment
 // reads, 8 = no hidden conversion, 16 = no panel epilogue, 32 = the e4m3 stages move 3/5 (activation + weight slice) or 2/3 (weight slice)
 // of their bytes: the DMA volume of 3-byte operand rows (fp16 + ONE e4m3 plane) without their conversion work,
 // 256 = no residual-row loads (the accumulators start at zero: what the read burst at the top of a panel costs),
@@ -53,57 +53,13 @@
 #ifndef FFN_ABLATE
 #define FFN_ABLATE 0
 #endif
-// micro-variants (A/B with tools/ffn_variants.sh)
 // the wait states in front of every inline-asm MFMA (see mma() below).  -DFFN_MMA_NOP='""' builds the kernel WITHOUT them: the
 // negative control of tests/test_ffn_asm.py (the audit must then report hazards)
 #ifndef FFN_MMA_NOP
 #define FFN_MMA_NOP "s_nop 1\n\t"
 #endif
-// 1: odd hidden chunks walk the 64-k blocks of the panel backwards (see issue_fc1; -1.5 % on the layer tail; 0 = every chunk forwards)
-#ifndef FFN_SNAKE
-#define FFN_SNAKE 1
-#endif
 #ifndef FFN_CONV_G0
 #define FFN_CONV_G0 0       // first of the three MFMA groups of a sub-stage that carry a piece of the hidden conversion (0..3)
-#endif
-#ifndef FFN_DMA_EARLY
-#define FFN_DMA_EARLY 1     // DMA instructions issued before the first MFMA group of a stage (the rest follow groups 0, 1, ...)
-#endif
-
-
-#ifndef FFN_PRIO
-#define FFN_PRIO 0
-#endif
-#ifndef FFN_NT
-#define FFN_NT 0
-#endif
-#ifndef FFN_PINGPONG
-#define FFN_PINGPONG 0
-#endif
-// 1: the LayerNorm rows of both epilogues leave as ONE 16-byte store per lane and 4 columns instead of two 8-byte stores (fp16 part, e4m3
-// part): the lane pair that holds 8 adjacent columns of a row exchanges halves (a quad-permute DPP move in the final epilogue, where the
-// pair is adjacent lanes; v_permlane16_swap in the mid-panel one, where it is 16 lanes apart), the even lane stores the 16 bytes of fp16
-// values, the odd one the 16 bytes of e4m3 planes -- 36 instead of 72 store instructions per wave and epilogue.  Measured (round 6, same
-// box, 287 280 rows): 2.229 / 2.222 / 2.224 ms with 8-byte stores, 2.234 / 2.202 / 2.208 with these: -0.5 % at best -- the panel
-// boundary is bound neither by its store-instruction count (this) nor by its bytes (VETO_X_F24).  Kept: fewer instructions, same results
-#ifndef FFN_LN16
-#define FFN_LN16 1
-#endif
-// 1 (layer tail on fp32 residual rows; round 6, measured NULL, not the default): the accumulators start at ZERO and the panel's residual rows are
-// added during the out projection, a column third at a time: twelve 16-byte loads per lane into the registers the FeedForward's fc1 accumulators
-// will use (idle until then), issued at the top of an interval in front of its LDS-DMA instructions -- so the next interval's own vmcnt wait
-// covers them -- and added at the top of a later interval of their column third (that third's MFMAs are three intervals old: no hazard).  The
-// 36-load burst at the top of a panel becomes three trickles.  2.215 / 2.187 / 2.192 ms with the burst, 2.202 / 2.178 / 2.191 with the trickles
-// (same box, parity-green, audit clean, 256 registers): the bytes have to come either way.  0: the accumulators start as the residual rows.
-#ifndef FFN_MIDRES
-#define FFN_MIDRES 0
-#endif
-// TIMING PROBE (results are WRONG): the correction stages of the FeedForward (fc1, fc2; not the out projection) as block-scaled fp6
-// (e2m3) operands -- the K = 128 MFMA in its fp6 form (6 registers per operand, half the cycles of the e4m3 form), 96 instead of 128 bytes
-// of every row per correction stage through the LDS-DMA (12 + 18 instead of 16 + 24 pieces of an fc1 stage, 18 instead of 24 of an fc2
-// sub-stage), plus stand-ins for the block-scale traffic (3 / 1 small DMA instructions per stage, three scale reads per stage and wave)
-#ifndef FFN_FP6_PROBE
-#define FFN_FP6_PROBE 0
 #endif
 
 namespace veto {
@@ -121,6 +77,9 @@ constexpr int kAB = FR * 128;               // activation part of a ring slot: 1
 constexpr int kWB = FC * 128;               // weight part: 24 KiB
 constexpr int kSlot = kAB + kWB;
 constexpr int kRing = 3;
+// DMA instructions issued before the first MFMA group of a stage (the rest follow groups 0, 1, ...): 0 / 1 / 2 / 3 / 5 measured
+// 1.643-1.675 ms per launch, 1 the fastest
+constexpr int kDmaEarly = 1;
 constexpr int kHidOff = kRing * kSlot;      // hidden block: fp16 image [128 x 128 B], e4m3 image behind it
 constexpr int kB1Off = kHidOff + 2 * kAB;
 constexpr int kB2Off = kB1Off + FH * 4;
@@ -142,16 +101,6 @@ template <int V> struct Tag { static constexpr int value = V; };
 __device__ __forceinline__ void glds16(const char* base, unsigned voff, unsigned lds_addr) {
   if (FFN_ABLATE & 1) return;
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory");
-}
-// the same for rows that are read exactly once (the attention output rows of the out projection): non-temporal
-__device__ __forceinline__ void glds16_nt(const char* base, unsigned voff, unsigned lds_addr) {
-  if (FFN_ABLATE & 1) return;
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2 nt" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory");
-}
-// a 16-byte global load the compiler does not count (see glds16): the caller's own s_waitcnt vmcnt covers it before the value is used
-template <int OFF>
-__device__ __forceinline__ void gload16(f32x4& dst, const float* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF) : "memory");
 }
 __device__ __forceinline__ void wg_barrier() {
   asm volatile("" ::: "memory");
@@ -207,7 +156,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
   constexpr int kS2 = FC / 64 * NK * 3;      // fc2 sub-stages per chunk: 18 / 9
   constexpr int kPer = kS1 + kS2;            // a multiple of the ring length either way
   constexpr int kOutPos = kDim / 64 * NK * 3;   // positions of the out projection: 54 / 27
-  constexpr bool kMidRes = FFN_MIDRES && MODE == 2 && !RF24 && !FAST && !(FFN_ABLATE & 256);   // residual rows added during the out projection
   static_assert(kPer % kRing == 0 && kOutPos % kRing == 0, "a position's ring slot is a compile-time constant");
   saturating_conversions_on();   // (the hidden and LayerNorm conversions to mixed rows carry no clamps, common.h)
   __shared__ __attribute__((aligned(16))) char smem[kLds];
@@ -221,11 +169,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
     return l;
   };
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if FFN_PRIO == 1
-  if (w >= 4) __builtin_amdgcn_s_setprio(1);
-#elif FFN_PRIO == 2
-  if (w < 4) __builtin_amdgcn_s_setprio(1);
-#endif
   const int wm = w >> 1, wn = w & 1;          // 4 x 2 waves: rows 32 wm .., of every 64 weight rows of a stage the 32 at 32 wn
   const int G = gridDim.x, b = blockIdx.x;
   const int my_panels = g.n_panels > b ? (g.n_panels - b + G - 1) / G : 0;   // panels b, b + G, ...
@@ -259,22 +202,11 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
   auto ffn_base = [&](int it) { return (MODE == 2 ? (const char*)g.ln_out : g.a) + ((FFN_ABLATE & 64) ? (size_t)0 : (size_t)(b + (size_t)it * G) * ((size_t)FR * kRow1)); };
   // instruction k (of 5) of fc1 stage ks of hidden chunk c: 16 KiB of activation rows (k = 0, 1) + 24 KiB of W1 rows (2..4)
   auto issue_fc1 = [&](const char* a_panel, int c, int ks, int slot, int k) {
-#if FFN_SNAKE
     // odd chunks walk the 64-k blocks of the panel from the last to the first: the LayerNorm2 rows an XCD's 32 workgroups re-read
     // per hidden chunk (9.4 MB) do not fit its 4 MB L2, but the blocks a chunk reads last are the ones the next chunk then reads first
+    // (-1.5 % on the layer tail against every chunk forwards)
     if (c & 1) ks = 2 * (8 - (ks >> 1)) + (ks & 1);
-#endif
     const unsigned dst = lds0 + slot * kSlot + w * 1024;
-#if FFN_FP6_PROBE
-    if (ks & 1) {
-      if (k == 1 && w >= 4) {      // (waves 4-6: the stand-in of a scale DMA: 2 x 256 B of activation scales, 1 KiB of weight scales)
-        if (w < 6) asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dword %1, %2" ::"s"(lds0 + slot * kSlot + 12288 + (w - 4) * 256), "v"((unsigned)(lane_now() * 4)), "s"(a_panel) : "memory");
-        else if (w == 6) glds16(g.w1, (unsigned)(lane_now() * 16), lds0 + slot * kSlot + kAB + 18432);
-        return;
-      }
-      if (k == 4 && w >= 2) return;
-    }
-#endif
     if ((FFN_ABLATE & 32) && (ks & 1) && (k == 1 || k == 4)) return;
     if ((FFN_ABLATE & 128) && (ks & 1) && k == 1) return;   // (the activation half of ablation 32 alone)
     if (k < 2) glds16(a_panel + ks * 128 + k * 64 * kRow1, voff1, dst + k * 8 * 1024);
@@ -283,12 +215,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
   // instruction k (of 3) of an fc2 sub-stage: 24 KiB of W2 rows (column third t, 128-byte slice `slice` of the row)
   auto issue_fc2 = [&](int slice, int t, int slot, int k) {
     const unsigned dst = lds0 + slot * kSlot + w * 1024 + kAB;
-#if FFN_FP6_PROBE
-    if ((slice & 1) && k == 2 && w >= 2) {
-      if (w == 7) glds16(g.w2, (unsigned)(lane_now() * 16), lds0 + slot * kSlot + kAB + 18432);
-      return;
-    }
-#endif
     if ((FFN_ABLATE & 32) && (slice & 1) && k == 2) return;
     glds16(g.w2 + (size_t)t * ((size_t)FC * kRow2) + slice * 128 + (size_t)k * 64 * kRow2, voff2, dst + k * 8 * 1024);
   };
@@ -298,11 +224,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
   auto issue_out = [&](const char* a_panel, int ks, int t, int slot, int k) {
     const int kw = t == 0 ? k - 2 : k;
     if ((FFN_ABLATE & 32) && (ks & 1) && (t == 0 ? (k == 1 || k == 4) : k == 2)) return;
-#if FFN_NT & 8
-    if (t == 0 && k < 2) glds16_nt(a_panel + ks * 128 + k * 64 * kRow1, voff1, lds0 + w * 1024 + k * 8 * 1024);
-#else
     if (t == 0 && k < 2) glds16(a_panel + ks * 128 + k * 64 * kRow1, voff1, lds0 + w * 1024 + k * 8 * 1024);
-#endif
     else if (kw >= 0 && kw < 3)
       glds16(w_out + (size_t)t * ((size_t)FC * kRow1) + ks * 128 + kw * 64 * kRow1, voff1, lds0 + slot * kSlot + kAB + w * 1024 + kw * 8 * 1024);
   };
@@ -327,17 +249,13 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
   //  * the first VALU / LDS read of an accumulator behind its last MFMA: mfma_drain*() below, tied to those accumulators;
   //  * an accumulator chain needs none; operands come from ds_read (waited for through the register dependency).
   // tools/audit_ffn_asm.py checks the generated code for compiler instructions that touch accumulator registers near an MFMA.
-  auto mma = [&](auto kind_tag, f32x4& acc, const i32x4& fw0, const i32x4& fw1, const i32x4& fa0, const i32x4& fa1, int scale, int scale_b = 0x7f7f7f7f) {
+  auto mma = [&](auto kind_tag, f32x4& acc, const i32x4& fw0, const i32x4& fw1, const i32x4& fa0, const i32x4& fa1, int scale) {
     constexpr int KIND = decltype(kind_tag)::value;
     if (FFN_ABLATE & 2) {
       asm volatile("" : "+v"(acc) : "v"(fw0), "v"(fw1), "v"(fa0), "v"(fa1));
       return;
     }
-    if constexpr (KIND == 2) {      // (FFN_FP6_PROBE) the fp6 form: 24 bytes per operand and lane
-      typedef int i32x6 __attribute__((ext_vector_type(6)));
-      const i32x6 w6 = __builtin_shufflevector(fw0, fw1, 0, 1, 2, 3, 4, 5), a6 = __builtin_shufflevector(fa0, fa1, 0, 1, 2, 3, 4, 5);
-      asm(FFN_MMA_NOP "v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:2" : "+v"(acc) : "v"(w6), "v"(a6), "v"(scale), "v"(scale_b));
-    } else if constexpr (KIND == 0) {
+    if constexpr (KIND == 0) {
       asm(FFN_MMA_NOP "v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(fw0), "v"(fa0));
       asm(FFN_MMA_NOP "v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(fw1), "v"(fa1));
     } else {
@@ -370,25 +288,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
     const unsigned a0 = lds0 + AB + wm * 4096 + fo, a1 = lds0 + AB + wm * 4096 + (fo ^ 64);
     const unsigned w0 = lds0 + SB + kAB + wn * 4096 + fo, w1 = lds0 + SB + kAB + wn * 4096 + (fo ^ 64);
     i32x4 fw0[2], fw1[2];
-    typedef __attribute__((address_space(3))) u32x2 lds_u32x2_t;
-    constexpr int KIND_S = decltype(kind_tag)::value;
-    // second half of a fragment: 16 bytes, or (fp6 probe) 8
-    auto half2 = [&](unsigned addr) {
-      if constexpr (KIND_S == 2) {
-        const u32x2 v = *(const lds_u32x2_t*)(size_t)addr;
-        i32x4 r;
-        r[0] = (int)v[0]; r[1] = (int)v[1];
-        return r;
-      } else {
-        return (i32x4)*(lds_frag_t)(size_t)addr;
-      }
-    };
-    int scale_a = 0x7f7f7f7f;
-    if constexpr (KIND_S == 2) {     // stand-ins of the block-scale reads: one dword of activation scales, one of weight scales per lane
-      typedef __attribute__((address_space(3))) int lds_int_t;
-      scale_a = *(const lds_int_t*)(size_t)(lds0 + SB + 12288 + (fo & 0xffc));
-      scale = *(const lds_int_t*)(size_t)(lds0 + SB + kAB + 18432 + (fo & 0xffc));
-    }
     if (FFN_ABLATE & 4) {
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
@@ -410,47 +309,29 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         fa0[m] = *(lds_frag_t)(size_t)(a0 + m * 2048);
-        fa1[m] = half2(a1 + m * 2048);
+        fa1[m] = *(lds_frag_t)(size_t)(a1 + m * 2048);
       }
     }
     fw0[0] = *(lds_frag_t)(size_t)(w0);
-    fw1[0] = half2(w1);
-    // the first two DMA instructions go out while the first fragments are on their way from the LDS (their issue back-pressure
-    // and the LDS latency overlap instead of adding up); the others follow groups 0, 1, 2
-#if FFN_PINGPONG
-    // SIMD partners take turns (qkv_attn_fused.hip): waves 0-3 issue their whole DMA share in front of their MFMA groups, waves 4-7 (raised
-    // priority, FFN_PRIO 1) multiply first and issue behind them
-    if (w < 4) {
+    fw1[0] = *(lds_frag_t)(size_t)(w1);
+    // the first DMA instruction goes out while the first fragments are on their way from the LDS (its issue back-pressure
+    // and the LDS latency overlap instead of adding up); the others follow groups 0, 1, ...
 #pragma unroll
-      for (int k = 0; k < 5; ++k) dma(k);
-    }
-#else
-#pragma unroll
-    for (int k = 0; k < FFN_DMA_EARLY; ++k) dma(k);
-#endif
+    for (int k = 0; k < kDmaEarly; ++k) dma(k);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       if (i < 5) {
         fw0[(i + 1) & 1] = *(lds_frag_t)(size_t)(w0 + ((i + 1) >> 1) * 8192 + ((i + 1) & 1) * 2048);
-        fw1[(i + 1) & 1] = half2(w1 + ((i + 1) >> 1) * 8192 + ((i + 1) & 1) * 2048);
+        fw1[(i + 1) & 1] = *(lds_frag_t)(size_t)(w1 + ((i + 1) >> 1) * 8192 + ((i + 1) & 1) * 2048);
       }
 #pragma unroll
-      for (int m = 0; m < 2; ++m) mma(kind_tag, acc[i][m], fw0[i & 1], fw1[i & 1], fa0[m], fa1[m], scale, scale_a);
-#if !FFN_PINGPONG
-      dma(i + FFN_DMA_EARLY);
-#endif
+      for (int m = 0; m < 2; ++m) mma(kind_tag, acc[i][m], fw0[i & 1], fw1[i & 1], fa0[m], fa1[m], scale);
+      dma(i + kDmaEarly);
       valu(i);
       mark(i);
       __builtin_amdgcn_sched_barrier(0);
     }
-#if FFN_PINGPONG
-    if (w >= 4) {
-#pragma unroll
-      for (int k = 0; k < 5; ++k) dma(k);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#endif
   };
   // The hidden images of block j of a chunk: blocks 0 and 2 in the dedicated area, block 1 in the activation parts of ring
   // slots 0 and 1 (idle between the last fc1 stage and the prefetch of the next chunk's first stages at positions 34 / 35), so
@@ -586,11 +467,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
           for (int t = 0; t < 3; ++t)
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
-#if FFN_NT & 1
-              __builtin_nontemporal_store(acc2[t][i][m], (f32x4*)(op + t * FC + (i >> 1) * 64 + (i & 1) * 16));
-#else
               *(f32x4*)(op + t * FC + (i >> 1) * 64 + (i & 1) * 16) = acc2[t][i][m];
-#endif
             }
           }
         }
@@ -635,7 +512,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
       // (one 64-bit row pointer per row group, computed here: inside the loop the compiler re-derived it per store from a 64-bit
       // multiply; every column offset below is a compile-time constant that folds into the store's immediate)
       typedef __attribute__((address_space(1))) char gchar_t;          // (explicitly global: a pointer that went through an asm is generic)
-      typedef __attribute__((address_space(1))) u32x2 gu32x2_t;
       gchar_t* lrow[2];
       f32x2 nmean[2], rstd2[2];
 #pragma unroll
@@ -645,13 +521,9 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
         asm volatile("" : "+v"(nmean[m]), "+v"(rstd2[m]));   // (also keeps the compiler from carrying the 144 differences x - mean of
                                                              // pass 2 into the loop below: it did, and spilled them)
         const int row = row0 + m * 16;
-#if FFN_LN16
         // (even lane of a pair: the fp16 part at its own columns; odd lane: the e4m3 part, starting at its partner's group -- the column
         // offset of a later block adds the same number of bytes to both: mixed_h_offset(cofs) == mixed_x_offset(cofs) - 128 for cofs % 4 == 0)
         const int lbase = (q & 1) ? mixed_x_offset(col0) - 8 : mixed_h_offset(col0);
-#else
-        const int lbase = mixed_h_offset(col0);
-#endif
         lrow[m] = (gchar_t*)((!MID && MODE == 2 && g.ln1_out ? g.ln1_out : g.ln_out) + (size_t)(row < g.M ? row : g.M - 1) * kRow1 + lbase);
         asm volatile("" : "+v"(lrow[m]));
       }
@@ -670,38 +542,25 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
             const f32x4 y = {ylo[0], ylo[1], yhi[0], yhi[1]};
             u32x2 h, xy;
             mixed_pack4(y, h, xy);
-#if FFN_LN16
-            {
-              const bool odd = (q & 1) != 0;
-              const uint32_t s0 = odd ? h[0] : xy[0], s1 = odd ? h[1] : xy[1];      // what the partner stores
-              uint32_t r0, r1;
-              if constexpr (MID) {      // partner = lane ^ 16: rows of 16 lanes swapped pairwise
-                typedef unsigned u2v __attribute__((ext_vector_type(2)));
-                const u2v a0 = __builtin_amdgcn_permlane16_swap(s0, s0, false, false), a1 = __builtin_amdgcn_permlane16_swap(s1, s1, false, false);
-                r0 = odd ? a0[0] : a0[1];
-                r1 = odd ? a1[0] : a1[1];
-              } else {                  // partner = lane ^ 1
-                r0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)s0, 0xB1, 0xf, 0xf, true);
-                r1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xf, 0xf, true);
-              }
-              const u32x4 v16 = odd ? u32x4{r0, r1, xy[0], xy[1]} : u32x4{h[0], h[1], r0, r1};
-              typedef __attribute__((address_space(1))) u32x4 gu32x4_t;
-              if (row0 + m * 16 < g.M) *(gu32x4_t*)(lrow[m] + mixed_h_offset(cofs)) = v16;
-              continue;
+            // the rows leave as ONE 16-byte store per lane and 4 columns: the lane pair that holds 8 adjacent columns of a row exchanges halves,
+            // the even lane stores the 16 bytes of fp16 values, the odd one the 16 bytes of e4m3 planes -- 36 instead of 72 store instructions per
+            // wave and epilogue.  Measured (287 280 rows): 2.229 / 2.222 / 2.224 ms with two 8-byte stores, 2.234 / 2.202 / 2.208 with these:
+            // -0.5 % at best -- the panel boundary is not bound by its store-instruction count.  Kept: fewer instructions, same results
+            const bool odd = (q & 1) != 0;
+            const uint32_t s0 = odd ? h[0] : xy[0], s1 = odd ? h[1] : xy[1];      // what the partner stores
+            uint32_t r0, r1;
+            if constexpr (MID) {      // partner = lane ^ 16: rows of 16 lanes swapped pairwise (v_permlane16_swap)
+              typedef unsigned u2v __attribute__((ext_vector_type(2)));
+              const u2v a0 = __builtin_amdgcn_permlane16_swap(s0, s0, false, false), a1 = __builtin_amdgcn_permlane16_swap(s1, s1, false, false);
+              r0 = odd ? a0[0] : a0[1];
+              r1 = odd ? a1[0] : a1[1];
+            } else {                  // partner = lane ^ 1 (a quad-permute DPP move)
+              r0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)s0, 0xB1, 0xf, 0xf, true);
+              r1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xf, 0xf, true);
             }
-#endif
-            if (row0 + m * 16 < g.M) {
-#if FFN_NT & 2
-              if constexpr (!MID) {
-                __builtin_nontemporal_store(h, (gu32x2_t*)(lrow[m] + mixed_h_offset(cofs)));
-                __builtin_nontemporal_store(xy, (gu32x2_t*)(lrow[m] + mixed_x_offset(cofs)));
-              } else
-#endif
-              {
-              *(gu32x2_t*)(lrow[m] + mixed_h_offset(cofs)) = h;       // (col0 < 48 is a multiple of 4 and cofs % 64 is 0 or 16: both byte
-              *(gu32x2_t*)(lrow[m] + mixed_x_offset(cofs)) = xy;      // offsets of column col0 + cofs are those of cofs plus 2 col0)
-              }
-            }
+            const u32x4 v16 = odd ? u32x4{r0, r1, xy[0], xy[1]} : u32x4{h[0], h[1], r0, r1};
+            typedef __attribute__((address_space(1))) u32x4 gu32x4_t;
+            if (row0 + m * 16 < g.M) *(gu32x4_t*)(lrow[m] + mixed_h_offset(cofs)) = v16;
           }
         }
       EP(5);
@@ -730,22 +589,17 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
           for (int m = 0; m < 2; ++m) {
             int row = panel * FR + wm * 32 + m * 16 + r;
             if (row >= g.M) row = g.M - 1;          // clamp: rows past the end are never stored
-            if ((FFN_ABLATE & 256) || kMidRes) {
+            if (FFN_ABLATE & 256) {
               acc2[t][i][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-              // (opaque zeros: knowing them, the compiler would peel the first stages into MFMAs with a constant C operand in fresh registers)
-              if (kMidRes) asm volatile("" : "+v"(acc2[t][i][m]));
             } else if constexpr (RF24) {
               const u32x3 d = *(const u32x3*)((const char*)g.resid + ((size_t)row * kDim + wn * 32 + q * 4 + t * FC + (i >> 1) * 64 + (i & 1) * 16) * 3);
               acc2[t][i][m] = unpack_f24x4(d[0], d[1], d[2]);
+            } else {
+              acc2[t][i][m] = *(const f32x4*)(g.resid + (size_t)row * g.ldr + wn * 32 + q * 4 + t * FC + (i >> 1) * 64 + (i & 1) * 16);
             }
-#if FFN_NT & 4
-            else acc2[t][i][m] = __builtin_nontemporal_load((const f32x4*)(g.resid + (size_t)row * g.ldr + wn * 32 + q * 4 + t * FC + (i >> 1) * 64 + (i & 1) * 16));
-#else
-            else acc2[t][i][m] = *(const f32x4*)(g.resid + (size_t)row * g.ldr + wn * 32 + q * 4 + t * FC + (i >> 1) * 64 + (i & 1) * 16);
-#endif
           }
       if (it == 0) {
-        if ((FFN_ABLATE & 256) || kMidRes) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (FFN_ABLATE & 256) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(36)" ::: "memory");   // the prologue's stages 0 and 1 have landed (they are older than the 36 loads)
         skip = 2;
       }
@@ -758,12 +612,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
       const bool stream_ends = MODE == 2 || it == my_panels - 1;
       const char* a_next = panel_base(it + 1);          // (not dereferenced when the stream ends)
       i32x4 fa0[2], fa1[2];
-      // kMidRes: the residual rows of column third t are requested at the top of position kResLoad(t) and added at the top of position
-      // kResAdd(t) (a position of that third; the requests of the next third follow the add: one set of 48 registers)
-      f32x4 rres[6][2];
-      (void)rres;
-      auto res_load_pos = [](int t) { return t == 0 ? 0 : t == 1 ? 7 : 17; };
-      auto res_add_pos = [](int t) { return t == 0 ? 6 : t == 1 ? 16 : 26; };
       static_for<0, kOutPos>([&](auto p_tag) {
         constexpr int P = decltype(p_tag)::value, KS = P / 3, T = P % 3;
         STAMP(t0);
@@ -777,40 +625,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
         wg_barrier();
         STAMP(t2);
         ACC(s_wait, t1, t0); ACC(s_bar, t2, t1);
-        if constexpr (kMidRes) {
-          static_for<0, 3>([&](auto t_tag) {
-            constexpr int TT = decltype(t_tag)::value;
-            if constexpr (P == res_add_pos(TT)) {
-              static_assert(res_add_pos(TT) % 3 == TT && res_add_pos(TT) >= res_load_pos(TT) + 2, "an interval of the third, two waits behind the requests");
-              // (the requests are two of this wave's vmcnt waits old -- each covers everything older than the next stage's DMA instructions --;
-              // the launder ties the values to THIS point: the compiler must not move the adds in front of the waits, which it cannot see)
-#pragma unroll
-              for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                  asm volatile("" : "+v"(rres[i][m]));
-                  acc2[TT][i][m] += rres[i][m];
-                }
-            }
-          });
-          static_for<0, 3>([&](auto t_tag) {
-            constexpr int TT = decltype(t_tag)::value;
-            if constexpr (P == res_load_pos(TT)) {
-              static_assert(TT == 0 || res_load_pos(TT) > res_add_pos(TT - 1), "the registers are free again");
-              const int lane_r = lane_now();
-              const int rr_ = lane_r & 15, qq_ = lane_r >> 4;
-#pragma unroll
-              for (int m = 0; m < 2; ++m) {
-                int row = panel * FR + wm * 32 + m * 16 + rr_;
-                if (row >= g.M) row = g.M - 1;          // clamp: rows past the end are never stored
-                const float* rp = g.resid + (size_t)row * g.ldr + wn * 32 + qq_ * 4 + TT * FC;
-                // (inline asm: invisible to the compiler's wait counting, like the LDS-DMA; the kernel's own waits cover them)
-                gload16<0>(rres[0][m], rp); gload16<64>(rres[1][m], rp); gload16<256>(rres[2][m], rp);
-                gload16<320>(rres[3][m], rp); gload16<512>(rres[4][m], rp); gload16<576>(rres[5][m], rp);
-              }
-            }
-          });
-        }
         auto dma = [&](int k) {
           constexpr int P2 = P + 2;
           if constexpr (P2 < kOutPos) issue_out(a_panel, P2 / 3 * SL, P2 % 3, P2 % 3, k);
@@ -881,17 +695,6 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
           if (stream_ends) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         }
-#if FFN_FP6_PROBE
-        // (this wave's DMA instructions of stage P + 1 -- fewer in a correction stage, and they differ per wave)
-        else if (P + 1 < kS1 && ((P + 1) & 1)) {
-          if (w < 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-          else if (w < 7) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        } else if (P + 1 >= kS1 && ((P + 1 - kS1) % 6) >= 3) {
-          if (w < 2 || w == 7) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        }
-#endif
         else if (P + 1 < kS1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         if (P >= kS1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's hidden-image stores are in the LDS
@@ -918,7 +721,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
         constexpr int SB = (P % kRing) * kSlot;
         auto mark = [&](int i) { (void)i; TL(P, 3 + i); };
         if constexpr (P < kS1) {
-          stage(Tag<(FAST ? 0 : (P % 2) * (FFN_FP6_PROBE ? 2 : 1))>(), Tag<SB>(), Tag<SB>(), acc1, sc1, dma, Tag<0>(), fa0, fa1, [](int) {}, mark);
+          stage(Tag<(FAST ? 0 : P % 2)>(), Tag<SB>(), Tag<SB>(), acc1, sc1, dma, Tag<0>(), fa0, fa1, [](int) {}, mark);
         } else {
           // beside the MFMAs of sub-stages 0..3 of block J: bias + GELU + conversion of one (16 columns x 16 rows) unit of block
           // J + 1, a value per group, packed and stored in group 4
@@ -958,7 +761,7 @@ __global__ __launch_bounds__(512, 2) void ffn_fused_kernel(FfnArgs g) {
               }
             }
           };
-          stage(Tag<(FAST ? 0 : KIND2 * (FFN_FP6_PROBE ? 2 : 1))>(), Tag<(KIND2 == 0 ? (J == 1 ? 0 : kHidOff) : (J == 1 ? kSlot : kHidOff + kAB))>(), Tag<SB>(), acc2[T], sc2, dma,
+          stage(Tag<(FAST ? 0 : KIND2)>(), Tag<(KIND2 == 0 ? (J == 1 ? 0 : kHidOff) : (J == 1 ? kSlot : kHidOff + kAB))>(), Tag<SB>(), acc2[T], sc2, dma,
                 Tag<(T > 0)>(), fa0, fa1, valu, mark);
         }
         STAMP(t0);

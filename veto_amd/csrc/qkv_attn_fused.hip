@@ -23,7 +23,7 @@
 //                three and receives stage s + 2 too.  Everything gets two intervals of flight.  (Six heads: 36 KiB weight images,
 //                two of them: W(s + 1) has one interval.)
 //                Wave (wm, wn) of 4 x 2 owns row blocks 5 wm .. 5 wm + 4 (block 19 does not exist: wm = 3 multiplies a dummy whose
-//                result is never read -- its SIMD would idle otherwise) and column blocks NB wn .. NB wn + NB - 1 (QA_COL_INTERLEAVE: 2 n + wn).
+//                result is never read -- its SIMD would idle otherwise) and column blocks NB wn .. NB wn + NB - 1.
 //   attention    behind the last stage the buffers are dead, except the first activation / weight image, which already holds the
 //                NEXT tile's first stage where the geometry allows: the waves convert their accumulators to packed fp16 hi / lo once,
 //                then twice (pairs in two batches of 8): the owners write the batch's Q / K rows into eight per-pair LDS regions in
@@ -58,43 +58,6 @@
 #ifndef QA_MMA_NOP
 #define QA_MMA_NOP "s_nop 1\n\t"
 #endif
-// activation pieces the lower half issues beside the weight pieces (three weight images; measured: 4 / 10 / 16 within 1 % of one another,
-// 0 -- the upper half issues every activation piece -- 6 % slower)
-#ifndef QA_ASPLIT
-#define QA_ASPLIT 10
-#endif
-// weight-fragment buffers of the main loop: fragment n + QA_WBUF - 1 is requested while fragment n is multiplied (3 measured equal to 2:
-// 1.315 vs 1.304-1.314 ms; six heads have no registers for a third buffer)
-#ifndef QA_WBUF
-#define QA_WBUF 2
-#endif
-// column blocks of the two wave columns: 0 = contiguous halves (wn = 0: q and the first part of k), 1 = interleaved (wave column wn owns the
-// blocks 2 n + wn: both columns hold a share of q, k AND v, so the row writes of the attention phase are spread over all eight waves --
-// measured 1.340-1.347 against 1.325-1.338 ms: the unbalanced row writes are not what the phase waits for)
-// wave priority in the main loop: 1 = the upper half (which multiplies first and issues its DMA share behind its MFMA groups) runs at priority 1,
-// i.e. wins the matrix pipe of its SIMD whenever both partners want it: it is through with its MFMAs early and its DMA issue falls under the
-// lower half's matrix work instead of behind the stage (1.27-1.29 -> 1.21-1.24 ms; level 3 equal; priority only while it multiplies 1.25; kept
-// through the attention phase 1.25); 2 = the lower half raised instead (null: 1.28); 0 = no priorities
-#ifndef QA_PRIO
-#define QA_PRIO 1
-#endif
-// row blocks of the four wave rows and the pairs of a batch: 1 = wave row wm owns the blocks wm, wm + 4, ... and batch bt holds the pairs 8 bt .. 8 bt + 7
-// (a block's rows then belong to ONE batch, but for the block that holds the batch boundary: 20 block visits of row writes per tile instead of 26, all eight
-// waves in every batch); 0 = contiguous blocks 5 wm .., pairs alternating between the batches two by two
-#ifndef QA_ROW_INTERLEAVE
-#define QA_ROW_INTERLEAVE 1
-#endif
-#ifndef QA_PITCH_PAD
-#define QA_PITCH_PAD 16
-#endif
-#ifndef QA_COL_INTERLEAVE
-#define QA_COL_INTERLEAVE 0
-#endif
-// TIMING PROBE (results are WRONG): the correction stages as block-scaled fp6 (e2m3) operands -- the K = 128 MFMA in its fp6 form, three
-// quarters of the pieces of a correction stage through the LDS-DMA, stand-ins for the block-scale traffic (ffn_fused.hip, FFN_FP6_PROBE)
-#ifndef QA_FP6_PROBE
-#define QA_FP6_PROBE 0
-#endif
 
 namespace veto {
 
@@ -109,6 +72,12 @@ constexpr int kABytes = TM * 128;          // activation part of a ring slot
 constexpr int APIECES = TM / 8;            // 38 LDS-DMA instructions (8 rows x 128 B each) per activation stage
 constexpr int kLdsTotal = 163840;
 constexpr int VROW = 40;                   // bytes per row of a transposed V image: 20 keys (19 + one zero)
+// activation pieces the lower half issues beside the weight pieces (three weight images; measured: 4 / 10 / 16 within 1 % of one another,
+// 0 -- the upper half issues every activation piece -- 6 % slower)
+constexpr int kASplit3 = 10;
+// weight-fragment buffers of the main loop: fragment n + kWBuf - 1 is requested while fragment n is multiplied (3 measured equal to 2:
+// 1.315 vs 1.304-1.314 ms; six heads have no registers for a third buffer)
+constexpr int kWBuf = 2;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -133,7 +102,7 @@ struct Geo {
   // zero and stands in for keys 19..31) + fp32 output rows
   // bytes per image row (no contraction padding: masked in registers).  A pitch that is a multiple of 64 bytes puts the 16 rows a half wave
   // writes or reads on only 4 bank groups: six heads (192 B) get 16 bytes of padding (1.35 -> 1.22 ms per launch)
-  static constexpr int QP = DH * 2 + (DH % 32 == 0 ? QA_PITCH_PAD : 0);
+  static constexpr int QP = DH * 2 + (DH % 32 == 0 ? 16 : 0);
   static constexpr int PLANE = kTokens * QP;
   static constexpr int VPLANE = (kTokens + 1) * QP;
   static constexpr int PH1 = 4 * PLANE, PH2 = 2 * VPLANE + kTokens * DH * 4;
@@ -167,25 +136,13 @@ __device__ __forceinline__ void lds_barrier() {
   wg_barrier();
 }
 
-// Four fp32 values -> bf16 hi and bf16 lo (x ~= hi + lo, common.h), both PACKED: {v0 | v1 << 16, v2 | v3 << 16}.  Written on dwords and
-// pinned by an empty asm: left to the vector types, the compiler keeps every 16-bit element of the 8 x 35 values in a register of its own
-// next to the packed form (the element-wise V^T stores below index them), and spills a few hundred registers.
 // Two fp32 values -> packed 16-bit hi and lo parts, x ~= hi + lo (the operands of the attention products: three MFMA terms hi hi + hi lo +
-// lo hi).  QA_F16_SPLIT (default): fp16 hi (11 significant bits) + fp16 lo: 22 bits in all, FOUR vector instructions per value pair
-// (v_cvt_pk_f16_f32, two v_fma_mix_f32 that read the packed halves in place, v_cvt_pk_f16_f32) -- the attention phase is bound by vector
-// instruction issue.  q / k / v are O(10) here (LayerNorm'ed rows times weights), far inside the fp16 range (the conversions saturate at
-// 65 504: MODE.FP16_OVFL is set), and a lo part below 2^-14 loses at most what a bf16 lo would have lost.  0: bf16 hi + bf16 lo (16 bits,
-// six instructions; the split of attention.hip).  The packed value is pinned by an empty asm: the compiler otherwise converts the first value
-// a second time, alone, to get at its half.
-#ifndef QA_F16_SPLIT
-#define QA_F16_SPLIT 1
-#endif
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-  const bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
+// lo hi): fp16 hi (11 significant bits) + fp16 lo: 22 bits in all, FOUR vector instructions per value pair (v_cvt_pk_f16_f32, two
+// v_fma_mix_f32 that read the packed halves in place, v_cvt_pk_f16_f32) -- the attention phase is bound by vector instruction issue.
+// q / k / v are O(10) here (LayerNorm'ed rows times weights), far inside the fp16 range (the conversions saturate at 65 504:
+// MODE.FP16_OVFL is set), and a lo part below 2^-14 loses at most what a bf16 lo would have lost.  (bf16 hi + bf16 lo, 16 bits and six
+// instructions, measured 1.294-1.300 against 1.290-1.295 ms.)
 __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-#if QA_F16_SPLIT
   uint32_t h, l;
   float l0, l1;
   asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));      // (volatile: reads MODE, see mixed_pack4 in common.h)
@@ -194,12 +151,6 @@ __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t&
   asm volatile("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(l) : "v"(l0), "v"(l1));
   hi = h;
   lo = l;
-#else
-  uint32_t h = pk_bf16(a, b);
-  asm("" : "+v"(h));
-  hi = h;
-  lo = pk_bf16(a - __uint_as_float(h << 16), b - __uint_as_float(h & 0xffff0000u));
-#endif
 }
 // Four fp32 values -> packed hi and lo: {v0 | v1 << 16, v2 | v3 << 16}.  Written on dwords and pinned by an empty asm: left to the vector
 // types, the compiler keeps every 16-bit element of the 8 x 35 values in a register of its own next to the packed form (the element-wise
@@ -216,11 +167,7 @@ __device__ __forceinline__ void split4(const f32x4& v, u32x2& hi, u32x2& lo) {
 typedef _Float16 qa_f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((ext_vector_type(16))) float qa_f32x16;
 __device__ __forceinline__ qa_f32x16 mfma16(const u32x4& a, const u32x4& b, const qa_f32x16& c) {
-#if QA_F16_SPLIT
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(qa_f16x8, a), __builtin_bit_cast(qa_f16x8, b), c, 0, 0, 0);
-#else
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-#endif
 }
 
 template <int I, int N, class F>
@@ -296,8 +243,13 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w & 3, wn = w >> 2;
-  constexpr int kColBase = QA_COL_INTERLEAVE ? 2048 : NB * 2048, kColStep = QA_COL_INTERLEAVE ? 4096 : 2048;   // LDS bytes: wave column, block n -> n + 1
-  constexpr int kRowBase = QA_ROW_INTERLEAVE ? 2048 : MB * 2048, kRowStep = QA_ROW_INTERLEAVE ? 4 * 2048 : 2048;   // the same for the wave rows: block m -> m + 1
+  // LDS bytes: wave column, block n -> n + 1.  Wave column wn owns the contiguous blocks NB wn ..: interleaved (2 n + wn: both columns hold a share of
+  // q, k AND v, the row writes of the attention phase spread over all eight waves) measured 1.340-1.347 against 1.325-1.338 ms
+  constexpr int kColBase = NB * 2048, kColStep = 2048;
+  // the same for the wave rows, block m -> m + 1.  Wave row wm owns the blocks wm, wm + 4, ... and batch bt of the attention phase holds the
+  // pairs 8 bt .. 8 bt + 7: a block's rows then belong to ONE batch, but for the block that holds the batch boundary -- 20 block visits of
+  // row writes per tile instead of 26 with contiguous blocks, all eight waves in every batch (-1.2 % on eight heads)
+  constexpr int kRowBase = 2048, kRowStep = 4 * 2048;
   const int b = blockIdx.x;
   const int H = g.heads;
   const int groups = (g.n_pair + TP - 1) / TP;
@@ -329,9 +281,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
     if (kRederiveLower) asm volatile("" : "+s"(t));
     return t != 0;
   };
-#define lower is_lower()
-  constexpr int kASplit = NWB == 3 ? QA_ASPLIT : 0;      // (even: a piece's swizzle parity is its index's)
-  const int a_begin = lower ? 0 : kASplit, a_end = lower ? kASplit : APIECES;    // this wave's activation pieces: a_begin + wl + 4 k < a_end
+  constexpr int kASplit = NWB == 3 ? kASplit3 : 0;      // (even: a piece's swizzle parity is its index's)
+  const int a_begin = is_lower() ? 0 : kASplit, a_end = is_lower() ? kASplit : APIECES;    // this wave's activation pieces: a_begin + wl + 4 k < a_end
   // Lane-dependent offsets are re-derived from the lane id where they are used (laundered through an empty asm: a few vector instructions
   // per stage) instead of living in registers through the main loop: at 180 accumulators (six heads) the allocator spills exactly those,
   // and a scratch reload inside the main loop waits for vmcnt(0), i.e. drains the wave's DMA queue.
@@ -354,7 +305,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
   };
   constexpr int NPA = ((APIECES - kASplit > kASplit ? APIECES - kASplit : kASplit) + 3) / 4, NPW = (G::WPIECES + 3) / 4;      // pieces per wave at most (either half)
   const int n_acts = a_end - a_begin > wl ? (a_end - a_begin - wl + 3) / 4 : 0;
-  const int n_weights = lower ? (G::WPIECES - wl + 3) / 4 : 0;
+  const int n_weights = is_lower() ? (G::WPIECES - wl + 3) / 4 : 0;
   struct TileSrc {
     const char* a;      // first activation row of the tile's pair group
     const char* w;      // first weight row of the tile's head: q rows; k rows 576 rows on, v rows 1152 rows on
@@ -371,37 +322,22 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
   auto issue_acts = [&](const TileSrc& t, int s, int buf, int p_lo = 0, int p_hi = APIECES) {
     const unsigned voff_a = piece_voff(lane_now(), wl * 8);
     int issued = 0;
-    int a_end_s = a_end;
-#if QA_FP6_PROBE
-    if (s & 1) a_end_s = a_begin + (a_end - a_begin) * 3 / 4;      // three quarters of this half's pieces
-#endif
 #pragma unroll
     for (int k = 0; k < NPA; ++k)
-      if (a_begin + wl + 4 * k < a_end_s && a_begin + wl + 4 * k >= p_lo && a_begin + wl + 4 * k < p_hi) {
+      if (a_begin + wl + 4 * k < a_end && a_begin + wl + 4 * k >= p_lo && a_begin + wl + 4 * k < p_hi) {
         ++issued;
         glds16(t.a + (size_t)(a_begin * 8 + 32 * k) * kRowB + s * (SL * 128), voff_a, lds0 + buf * G::kPair + (a_begin + wl + 4 * k) * 1024);
       }
-#if QA_FP6_PROBE
-    if ((s & 1) && (w == 0 || w >= 3) && p_lo == 0) {      // stand-ins of the scale DMAs: 5 x 256 B of activation scales, 1 KiB of weight scales
-      ++issued;
-      if (w == 0) glds16(t.w, (unsigned)(lane_now() * 16), lds0 + buf * G::kPair + 30720);
-      else asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dword %1, %2" ::"s"(lds0 + buf * G::kPair + 31744 + (w - 3) * 256), "v"((unsigned)(lane_now() * 4)), "s"(t.a) : "memory");
-    }
-#endif
     return issued;      // (wave-uniform)
   };
   auto issue_weights = [&](const TileSrc& t, int s, int buf) {
-    if (!lower) return 0;
+    if (!is_lower()) return 0;
     const unsigned voff_w = piece_voff(lane_now(), 0);
     int issued = 0;
-    int wp = G::WPIECES;
-#if QA_FP6_PROBE
-    if (s & 1) wp = G::WPIECES * 3 / 4;
-#endif
 #pragma unroll
     for (int k = 0; k < NPW; ++k) {
       const int c = wl + 4 * k;          // piece c of the head's q | k | v rows: matrix c / PM, rows 8 (c % PM) .. of that matrix's head slice
-      if (c < wp) {
+      if (c < G::WPIECES) {
         ++issued;
         const int mat = c / G::PM, cm = c - mat * G::PM;
         glds16(t.w + (size_t)(mat * kDim + 8 * cm) * kRowB + s * (SL * 128), voff_w, lds0 + (buf < 2 ? kABytes + buf * G::kPair : 2 * G::kPair) + c * 1024);
@@ -477,17 +413,13 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
     // DMA queue (scratch traffic shares vmcnt).  The compiler then pads no MFMA hazard: `s_nop 1` opens every MFMA (operand written by a
     // vector instruction right in front of it), the first non-MFMA readers of the accumulators sit behind mfma_drain() below, and
     // veto_amd/asmcheck.py audits the generated code after every build.
-    auto mma = [&](auto kind_tag, f32x4& c, const i32x4& w0, const i32x4& w1, const i32x4& a0, const i32x4& a1, int scale, int scale_b = 0x7f7f7f7f) {
+    auto mma = [&](auto kind_tag, f32x4& c, const i32x4& w0, const i32x4& w1, const i32x4& a0, const i32x4& a1, int scale) {
       constexpr int KIND = decltype(kind_tag)::value;
       if (QA_ABLATE & 4) {
         asm volatile("" : "+v"(c) : "v"(w0), "v"(w1), "v"(a0), "v"(a1));
       } else if constexpr (KIND == 0) {
         asm(QA_MMA_NOP "v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w0), "v"(a0));
         asm(QA_MMA_NOP "v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(w1), "v"(a1));
-      } else if constexpr (QA_FP6_PROBE != 0) {
-        typedef int i32x6 __attribute__((ext_vector_type(6)));
-        const i32x6 w6 = __builtin_shufflevector(w0, w1, 0, 1, 2, 3, 4, 5), a6 = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5);
-        asm(QA_MMA_NOP "v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:2 blgp:2" : "+v"(c) : "v"(w6), "v"(a6), "v"(scale), "v"(scale_b));
       } else {
         const i32x8 w8 = __builtin_shufflevector(w0, w1, 0, 1, 2, 3, 4, 5, 6, 7), a8 = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
         asm(QA_MMA_NOP "v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(w8), "v"(a8), "v"(scale), "v"(0x7f7f7f7f));
@@ -530,25 +462,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
       } else {
         a_lo = ab_[AB]; a_hi = ab64_[AB]; w_lo = wv_[WB]; w_hi = wv64_[WB];
       }
-      constexpr int WBUF = kRederive ? 2 : QA_WBUF;
+      constexpr int WBUF = kRederive ? 2 : kWBuf;
       i32x4 fa0[MB], fa1[MB], fw0[WBUF], fw1[WBUF];
-      // second half of a fragment: 16 bytes, or (fp6 probe, correction stage) 8
-      auto half2 = [&](int off) {
-        if constexpr (QA_FP6_PROBE != 0 && KIND == 1) {
-          const u32x2 v = *(const u32x2*)(smem + off);
-          i32x4 r;
-          r[0] = (int)v[0]; r[1] = (int)v[1];
-          return r;
-        } else {
-          return *(const i32x4*)(smem + off);
-        }
-      };
-      int sc_w = mix_scale, sc_a = 0x7f7f7f7f;
-      if constexpr (QA_FP6_PROBE != 0 && KIND == 1) {      // stand-ins of the block-scale reads
-        const u32x2 sa2 = *(const u32x2*)(smem + G::a_buf(AB) + 30720 + ((a_lo * 2) & 0x3f8));
-        sc_w = *(const int*)(smem + G::a_buf(AB) + 31744 + (w_lo & 0x3fc));
-        sc_a = (int)(sa2[0] ^ sa2[1]);
-      }
       if ((QA_ABLATE & 16) || !real) {
 #pragma unroll
         for (int m = 0; m < MB; ++m) { fa0[m] = fa1[m] = i32x4{0, 0, 0, 0}; asm volatile("" : "+v"(fa0[m]), "+v"(fa1[m])); }
@@ -558,16 +473,16 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
 #pragma unroll
       for (int m = 0; m < MB; ++m) {
         fa0[m] = *(const i32x4*)(smem + a_lo + m * kRowStep);
-        fa1[m] = half2(a_hi + m * kRowStep);
+        fa1[m] = *(const i32x4*)(smem + a_hi + m * kRowStep);
       }
 #pragma unroll
       for (int i = 0; i < WBUF - 1; ++i) {
         fw0[i] = *(const i32x4*)(smem + w_lo + i * kColStep);
-        fw1[i] = half2(w_hi + i * kColStep);
+        fw1[i] = *(const i32x4*)(smem + w_hi + i * kColStep);
       }
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (lower) {
+      if (is_lower()) {
         // early release of the activation image: every wave has its fragments in registers.  (The barrier comes in front of the weight
         // pieces too, which do not need it: the upper half waits at it behind its first MFMA group.)
         if (do_a) {
@@ -583,18 +498,18 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
       __builtin_amdgcn_sched_barrier(0);
       if (!real) {
         // an empty interval: no fragments, no MFMAs; the upper half joins the release barrier right away
-        if (!lower && do_a) wg_barrier();
+        if (!is_lower() && do_a) wg_barrier();
       } else
 #pragma unroll
       for (int n = 0; n < NB; ++n) {
         if (n + WBUF - 1 < NB && !(QA_ABLATE & 16)) {
           fw0[(n + WBUF - 1) % WBUF] = *(const i32x4*)(smem + w_lo + (n + WBUF - 1) * kColStep);
-          fw1[(n + WBUF - 1) % WBUF] = half2(w_hi + (n + WBUF - 1) * kColStep);
+          fw1[(n + WBUF - 1) % WBUF] = *(const i32x4*)(smem + w_hi + (n + WBUF - 1) * kColStep);
         }
 #pragma unroll
-        for (int m = 0; m < MB; ++m) mma(kind_tag, acc[n][m], fw0[n % WBUF], fw1[n % WBUF], fa0[m], fa1[m], sc_w, sc_a);
+        for (int m = 0; m < MB; ++m) mma(kind_tag, acc[n][m], fw0[n % WBUF], fw1[n % WBUF], fa0[m], fa1[m], mix_scale);
         __builtin_amdgcn_sched_barrier(0);
-        if (n == 0 && !lower && do_a) {
+        if (n == 0 && !is_lower() && do_a) {
           // (the upper half joins the release barrier behind its first group: its fragments are in registers by then, and its matrix
           // work starts without waiting for the lower half)
           QST(t4);
@@ -603,17 +518,17 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
           QACC(s_bar2, t5, t4);
         }
       }
-      if (!lower && do_a) n_issued = issue_acts(ta, st_a, AB, 0, a_limit);
+      if (!is_lower() && do_a) n_issued = issue_acts(ta, st_a, AB, 0, a_limit);
       younger = n_issued + (NWB == 3 && do_w ? n_w_issued : 0);
       QST(t2);
       QACC(s_wait, t3, t0); QACC(s_bar1, t1, t3); QACC(s_main, t2, t1);
     };
     static_assert(kStages % 6 == 0, "the stage loop is unrolled over the 2 x 3 image indices");
-#if QA_PRIO == 1
-    if (!lower) __builtin_amdgcn_s_setprio(1);
-#elif QA_PRIO == 2
-    if (lower) __builtin_amdgcn_s_setprio(1);
-#endif
+    // the upper half (which multiplies first and issues its DMA share behind its MFMA groups) runs the main loop at priority 1, i.e. wins the
+    // matrix pipe of its SIMD whenever both partners want it: it is through with its MFMAs early and its DMA issue falls under the lower half's
+    // matrix work instead of behind the stage (1.27-1.29 -> 1.21-1.24 ms; level 3 equal; priority only while it multiplies 1.25; kept through the
+    // attention phase 1.25; the lower half raised instead: null, 1.28)
+    if (!is_lower()) __builtin_amdgcn_s_setprio(1);
     constexpr int K1 = FAST ? 0 : 1;      // kind of the odd stages: the e4m3 part of a block, or (FAST) the next block's fp16 part
     for (int s = 0; s < kStages; s += 6) {
       stage(Tag<0>(), Tag<0>(), Tag<0>(), s);
@@ -625,9 +540,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
     }
 
     // ---- attention phase -----------------------------------------------------------------------------------------------------------
-#if QA_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     QST(t0);
 #ifdef VETO_QA_STAMPS
     unsigned long long t_att = t0;
@@ -657,12 +570,12 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
     char* const region = smem + G::kScratch + w * G::REGION;
 #pragma unroll 1
     for (int bt = 0; bt < ((QA_ABLATE & 2) ? 0 : 2); ++bt) {
-      const int my_pair = group * TP + (QA_ROW_INTERLEAVE ? 8 * bt + w : 4 * (w >> 1) + 2 * bt + (w & 1));     // the pair whose attention this wave runs in this batch
+      const int my_pair = group * TP + (8 * bt + w);     // the pair whose attention this wave runs in this batch
       const bool active = my_pair < g.n_pair;
       // -- the owners write the batch's rows: lane (fr, fq) of block (n, m) holds token row 16 (5 wm + m) + fr, columns 16 (NB wn + n) + 4 fq ..
       // of q | k | v.  PHASE 0: the Q / K images (hi, lo planes); PHASE 1: the V images.  Everything but the row part of the address
       // is a compile-time constant per (wn, n): the stores carry it in their offset field.
-      auto batch_of = [](int pr) { return QA_ROW_INTERLEAVE ? pr >> 3 : (pr >> 1) & 1; };     // batch of pair pr of the tile
+      auto batch_of = [](int pr) { return pr >> 3; };     // batch of pair pr of the tile
       auto write_rows = [&](auto wn_tag, auto phase_tag) {
         constexpr int WN = decltype(wn_tag)::value, PHASE = decltype(phase_tag)::value;
         constexpr int LO = PHASE == 0 ? G::PLANE : G::VPLANE;                  // distance hi plane -> lo plane
@@ -673,17 +586,17 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
         const int fr_w = lane_w & 15, fq_w = lane_w >> 4;
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
-          const int r0 = 16 * (QA_ROW_INTERLEAVE ? wm + 4 * m : wm * MB + m);  // wave-uniform: skip blocks without a row of this batch
+          const int r0 = 16 * (wm + 4 * m);  // wave-uniform: skip blocks without a row of this batch
           const int pa = (r0 * 27) >> 9, pb = ((r0 + 15) * 27) >> 9;           // (r / 19 for r < 513)
           if (r0 >= TM || !(batch_of(pa) == bt || batch_of(pb) == bt)) continue;
           const int r = r0 + fr_w;
           const int p = (r * 27) >> 9, t = r - 19 * p;                         // pair inside the tile, token
           const bool mine = r < TM && batch_of(p) == bt;
-          char* const rowp = smem + G::kScratch + (QA_ROW_INTERLEAVE ? p & 7 : ((p >> 2) << 1) | (p & 1)) * G::REGION + t * G::QP + 8 * fq_w;
+          char* const rowp = smem + G::kScratch + (p & 7) * G::REGION + t * G::QP + 8 * fq_w;
           if (mine) {
             static_for_n<NB>([&](auto n_tag) {
               constexpr int n = decltype(n_tag)::value;
-              constexpr int c0 = 16 * (QA_COL_INTERLEAVE ? 2 * n + WN : WN * NB + n);   // first column of the block; this lane: c0 + 4 fq ..
+              constexpr int c0 = 16 * (WN * NB + n);   // first column of the block; this lane: c0 + 4 fq ..
               constexpr int m_lo = c0 / DH, m_hi = (c0 + 15) / DH;               // matrix of the block's first / last column (3 = padding)
               auto in_phase = [](int mat) { return PHASE == 0 ? mat < 2 : mat == 2; };
               auto off_of = [](int mat) { return (PHASE == 0 ? mat * 2 * G::PLANE : 0) + (c0 - mat * DH) * 2; };   // (+ 8 fq: in rowp)
@@ -861,8 +774,6 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_fused_kernel(QkvAttnArgs g) {
   }
 #endif
 }
-
-#undef lower
 
 }  // namespace
 

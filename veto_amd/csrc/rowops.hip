@@ -15,11 +15,6 @@
 #include "common.h"
 #include "kernels.h"
 
-// token assembly: the fp32 token rows leave through non-temporal stores (they are next read by the layer tail, a whole attention launch later:
-// 0.239 -> 0.215 ms, and the table attention behind it 0.60 -> 0.57 ms -- its per-object tables stay cached)
-#ifndef ASM_NT
-#define ASM_NT 1
-#endif
 namespace veto {
 
 namespace {
@@ -487,18 +482,12 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs a) {
       }
       r.v[j] = v;
       if (a.x_f24) {      // (the statistics below are those of the fp32 row: the tables of layer 0 are normalised with them)
-#if ASM_NT
         __builtin_nontemporal_store(pack_f24x4(v), (u32x3*)(xr24 + 3 * c));
-#else
-        *(u32x3*)(xr24 + 3 * c) = pack_f24x4(v);
-#endif
         continue;
       }
-#if ASM_NT
+      // non-temporal stores (the rows are next read by the layer tail, a whole attention launch later): 0.239 -> 0.215 ms, and the table
+      // attention behind it 0.60 -> 0.57 ms -- its per-object tables stay cached
       __builtin_nontemporal_store(v, (f32x4*)(xr + c));
-#else
-      *(f32x4*)(xr + c) = v;
-#endif
     }
     asm volatile("" ::: "memory");   // keeps the next group's loads behind this group's stores (bounds the registers)
   }

@@ -623,16 +623,13 @@ static int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, 
   const bool mixed = h->cfg.precision != VETO_PRECISE;
   const bool fast = h->cfg.precision == VETO_FAST;
   const bool mixed_out = mixed && attention_reads_tables(H);
-#ifndef VETO_CLS_FFN_MIXED
-#define VETO_CLS_FFN_MIXED 1
-#endif
   // the CLS rows' FeedForward of the last layer on mixed operands too (round 5; rounds 2-4 kept it on split-bf16 because those rows ARE the
   // classifier's input): 0.141 -> 0.119 ms for the two launches, logit error against the CPU oracle 6.2e-5 -> 6.6e-5 on the bench batch -- inside
-  // the 3e-4 the parity tests hold the mode to (-DVETO_CLS_FFN_MIXED=0: the split-bf16 form)
-  const bool cls_mixed = mixed && VETO_CLS_FFN_MIXED;
+  // the 3e-4 the parity tests hold the mode to
+  const bool cls_mixed = mixed;
   // VETO_MIXED runs everything of a layer behind its attention as ONE panel launch (ffn_fused.hip MODE 2); VETO_TAIL_FUSED=0 (a knob
   // the parity tests compare against) splits it into the out projection + LayerNorm2 launch and the FeedForward + LayerNorm1 launch
-  // of the same kernel.  VETO_PRECISE / VETO_FAST take the launch-per-Linear GEMMs and LayerNorm launches.
+  // of the same kernel.  VETO_PRECISE takes the launch-per-Linear GEMMs and LayerNorm launches; VETO_FAST is VETO_MIXED's launches.
   static const bool tail_off = env_knob_is("VETO_TAIL_FUSED", "0");
   const bool tail_fused = !tail_off && !sat;
   const bool panel = !sat;        // (the saturation audit needs the LayerNorm2 rows and the hidden activation in memory)
