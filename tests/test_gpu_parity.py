@@ -315,7 +315,7 @@ def test_fused_qkv_attention(n_pair, sharp, heads):
 def test_gemm_block_diagonal_and_output_forms(m, n, k, kb_tiles, kb_steps):
     """The round-3 forms of the split-row GEMM (veto_debug_gemm_forms): block-diagonal weights -- column tile j multiplies only the
     k-steps of its block, the rest of w (here: garbage) is ignored -- and the split-row / 3-byte-float epilogues, against fp64.
-    The second and third shapes are the two block products of the folded last layer (veto_abi.hip)."""
+    The second and third shapes are the two block products of the folded last layer (abi_forward.hip)."""
     from veto_amd import native
     lib = native.load_library()
     dev = _dev()

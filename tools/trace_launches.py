@@ -2,7 +2,7 @@
 average mixes shapes.  This prints, for each GEMM dispatch position inside a forward step (steps start at
 pair_indices_kernel), the instantiation and the mean duration over the steps of the trace -- the rocprof-side numbers
 that bench.py's per-launch hipEvent times (kernels_ms_per_step / launches) are to be compared with.
-usage: python tools/trace_launches.py <kernel_trace.csv>   (launch order = the run_gemm calls of veto_forward, veto_abi.hip)"""
+usage: python tools/trace_launches.py <kernel_trace.csv>   (launch order = the run_gemm calls of veto_forward, abi_forward.hip)"""
 import csv
 import re
 import sys

@@ -1,0 +1,301 @@
+// Test and measurement hooks of the inference path's GEMM and fused launches (include/veto_amd.h, veto_debug_*): each builds its
+// operands from fp32 inputs and makes the launch with the argument set the forward builds (abi_internal.h).
+#include "abi_internal.h"
+
+namespace {
+
+// Optional device timing of a hook's launches from a hipEvent pair on its stream; without init() every call does nothing
+struct EventTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipStream_t s = nullptr;
+  float total_ms = 0.f;      // over every start() .. stop() span so far
+  hipError_t init(hipStream_t stream) {
+    s = stream;
+    hipError_t e = hipEventCreate(&e0);
+    return e != hipSuccess ? e : hipEventCreate(&e1);
+  }
+  hipError_t start() { return e1 ? hipEventRecord(e0, s) : hipSuccess; }
+  hipError_t stop() {      // waits for the span to finish
+    if (!e1) return hipSuccess;
+    float ms = 0.f;
+    hipError_t e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    total_ms += ms;
+    return e;
+  }
+  ~EventTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t veto_debug_gemm_workspace_bytes(int32_t m, int32_t n, int32_t k) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  return align_up(mp * k * 4, 256) + align_up((size_t)n * k * 4, 256) + 256;
+}
+
+int veto_debug_gemm(void* stream, const float* a, const float* w, const float* bias, float* c, int32_t m, int32_t n,
+                    int32_t k, int32_t precision, void* workspace, size_t workspace_bytes) {
+  if (!a || !w || !c || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (workspace_bytes < veto_debug_gemm_workspace_bytes(m, n, k)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  char* base = (char*)workspace;
+  __bf16* a_s = (__bf16*)base;
+  __bf16* w_s = (__bf16*)(base + align_up(mp * k * 4, 256));
+  int* w_exp = (int*)(base + align_up(mp * k * 4, 256) + align_up((size_t)n * k * 4, 256));
+  HIP_TRY(hipMemsetAsync(base, 0, align_up(mp * k * 4, 256), s));
+  GemmArgs g{};
+  if (precision == VETO_MIXED) {
+    if (k % 64 != 0) return fail(VETO_ERR_INVALID, "mixed rows need K %% 64 == 0");
+    HIP_TRY(launch_mixed_act_rows(a, a_s, (size_t)m, k, s));
+    HIP_TRY(launch_mixed_weight_rows(w, w_s, (size_t)n, k, w_exp, s));
+    g.fmt = FMT_MIXED; g.w_exp = w_exp;
+  } else {
+    HIP_TRY(launch_split_rows(a, a_s, (size_t)m, k, s));
+    HIP_TRY(launch_split_rows(w, w_s, (size_t)n, k, s));
+  }
+  g.a = a_s; g.w = w_s; g.bias = bias; g.c = c;
+  g.M = m; g.N = n; g.K = k; g.ldc = n;
+  hipError_t e = launch_gemm_split(g, EPI_F32, precision == VETO_FAST ? 1 : 0, s);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP,
+                                   "gemm launch failed (N must be a multiple of 192, K of 32): %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+// Test hook of the round-3 forms of the split-row GEMM: block-diagonal weights (kb_tiles > 0: column tile n multiplies only the
+// k-steps [(n / kb_tiles) * kb_steps, + kb_steps) -- everything outside those blocks of w is ignored) and the output forms:
+// out_form 0 = fp32 rows [m, n], 1 = split rows (m x 2n bf16: per 32 columns 32 hi then 32 lo), 2 = 3-byte floats (m x 3n bytes).
+// Workspace as for veto_debug_gemm.
+int veto_debug_gemm_forms(void* stream, const float* a, const float* w, void* c, int32_t m, int32_t n, int32_t k, int32_t kb_tiles,
+                          int32_t kb_steps, int32_t out_form, void* workspace, size_t workspace_bytes) {
+  if (!a || !w || !c || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (out_form < 0 || out_form > 2) return fail(VETO_ERR_INVALID, "out_form must be 0, 1 or 2");
+  if (workspace_bytes < veto_debug_gemm_workspace_bytes(m, n, k)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  char* base = (char*)workspace;
+  __bf16* a_s = (__bf16*)base;
+  __bf16* w_s = (__bf16*)(base + align_up(mp * k * 4, 256));
+  HIP_TRY(hipMemsetAsync(base, 0, align_up(mp * k * 4, 256), s));
+  HIP_TRY(launch_split_rows(a, a_s, (size_t)m, k, s));
+  HIP_TRY(launch_split_rows(w, w_s, (size_t)n, k, s));
+  GemmArgs g{};
+  g.a = a_s; g.w = w_s; g.M = m; g.N = n; g.K = k;
+  g.kb_tiles = kb_tiles; g.kb_steps = kb_steps;
+  if (out_form == 1) { g.c_split = (__bf16*)c; g.ldc = 2L * n; }
+  else { g.c = (float*)c; g.ldc = n; }
+  hipError_t e = launch_gemm_split(g, out_form == 1 ? EPI_SPLIT : out_form == 2 ? EPI_F24 : EPI_F32, 0, s);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP,
+                                   "gemm launch failed (N a multiple of 192, K of 32, the blocks must tile K): %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+// Test / measurement hook of the FeedForward block (model_veto.py:137-143 + the residual of :21) on VETO_MIXED operands:
+// x <- x + W2 . gelu(W1 . a + b1) + b2 for m token rows.  mode 0 = the two GEMM launches (fc1 with the GELU epilogue writing
+// the hidden activation as mixed rows, fc2 with the residual epilogue), mode 1 = the fused kernel (ffn_fused.hip).
+// flags & 1: (re)build the mixed operands from a / w1 / w2 first.  The block runs `reps` times (x accumulates: timing only when
+// reps > 1); *ms_per_rep (host, optional) receives the mean device time of one run from hipEvents on `stream`.
+size_t veto_debug_ffn_workspace_bytes(int32_t m) {
+  if (m <= 0) return 0;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  return align_up(mp * kDim * 4, 256) + align_up(mp * 2 * kDim * 4, 256) + 2 * align_up((size_t)2 * kDim * kDim * 4, 256) + 256;
+}
+
+int veto_debug_ffn(void* stream, const float* a, const float* w1, const float* b1, const float* w2, const float* b2, float* x,
+                   int32_t m, int32_t mode, int32_t flags, int32_t reps, float* ms_per_rep, void* workspace, size_t workspace_bytes,
+                   const float* ln_w, const float* ln_b, void* ln_rows) {
+  if (!a || !w1 || !b1 || !w2 || !b2 || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
+  if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
+  if (workspace_bytes < veto_debug_ffn_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  char* base = (char*)workspace;
+  __bf16* a_m = (__bf16*)base;
+  __bf16* hid = (__bf16*)(base + align_up(mp * kDim * 4, 256));
+  __bf16* w1_m = (__bf16*)((char*)hid + align_up(mp * 2 * kDim * 4, 256));
+  __bf16* w2_m = (__bf16*)((char*)w1_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  int* exps = (int*)((char*)w2_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  if (flags & 1) {
+    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+    HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
+    HIP_TRY(launch_mixed_weight_rows(w1, w1_m, (size_t)2 * kDim, kDim, exps + 0, s));
+    HIP_TRY(launch_mixed_weight_rows(w2, w2_m, (size_t)kDim, 2 * kDim, exps + 1, s));
+  }
+  EventTimer timer;      // the whole rep loop
+  if (ms_per_rep) HIP_TRY(timer.init(s));
+  HIP_TRY(timer.start());
+  for (int r = 0; r < reps; ++r) {
+    if (mode == 1) {
+      HIP_TRY(launch_ffn_fused(ffn_panel_args(a_m, MixedLinear{w1_m, b1, exps + 0}, MixedLinear{w2_m, b2, exps + 1}, x, m,
+                                              ln_rows ? RowNorm{ln_w, ln_b, ln_rows} : RowNorm()), s));
+    } else {
+      GemmArgs g1{};
+      g1.fmt = FMT_MIXED; g1.w_exp = exps + 0; g1.a = a_m; g1.w = w1_m; g1.bias = b1; g1.c_split = hid;
+      g1.M = m; g1.N = 2 * kDim; g1.K = kDim; g1.ldc = 4 * kDim;
+      HIP_TRY(launch_gemm_split(g1, EPI_GELU_SPLIT, 0, s));
+      GemmArgs g2{};
+      g2.fmt = FMT_MIXED; g2.w_exp = exps + 1; g2.a = hid; g2.w = w2_m; g2.bias = b2; g2.resid = x; g2.c = x;
+      g2.M = m; g2.N = kDim; g2.K = 2 * kDim; g2.ldr = kDim; g2.ldc = kDim;
+      HIP_TRY(launch_gemm_split(g2, EPI_RESID, 0, s));
+      if (ln_rows) HIP_TRY(launch_layernorm(x, kDim, ln_w, ln_b, (__bf16*)ln_rows, m, s, FMT_MIXED));
+    }
+  }
+  HIP_TRY(timer.stop());
+  if (ms_per_rep) *ms_per_rep = timer.total_ms / reps;
+  return VETO_OK;
+}
+
+// Test / measurement hook of the attention out projection + residual (model_veto.py:96 `to_out`, :20) on VETO_MIXED operands:
+// x <- x + a W^T + b for m token rows, optionally followed by LayerNorm rows (the FeedForward PreNorm, :125-132).  mode 0 = the GEMM
+// launch with the residual epilogue (+ a LayerNorm launch), mode 1 = the full-row panel kernel (ffn_fused.hip, MODE 1).
+size_t veto_debug_outproj_workspace_bytes(int32_t m) {
+  if (m <= 0) return 0;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  return align_up(mp * kDim * 4, 256) + align_up((size_t)kDim * kDim * 4, 256) + 256;
+}
+
+int veto_debug_outproj(void* stream, const float* a, const float* w, const float* b, float* x, int32_t m, int32_t mode, int32_t flags,
+                       int32_t reps, float* ms_per_rep, void* workspace, size_t workspace_bytes, const float* ln_w, const float* ln_b,
+                       void* ln_rows) {
+  if (!a || !w || !b || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
+  if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
+  if (workspace_bytes < veto_debug_outproj_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  char* base = (char*)workspace;
+  __bf16* a_m = (__bf16*)base;
+  __bf16* w_m = (__bf16*)(base + align_up(mp * kDim * 4, 256));
+  int* exps = (int*)((char*)w_m + align_up((size_t)kDim * kDim * 4, 256));
+  if (flags & 1) HIP_TRY(launch_mixed_weight_rows(w, w_m, (size_t)kDim, kDim, exps, s));
+  EventTimer timer;      // every rep by itself
+  if (ms_per_rep) HIP_TRY(timer.init(s));
+  for (int r = 0; r < reps; ++r) {
+    // the fused form writes its LayerNorm rows over its input rows: rebuild them for every run (outside the timed span)
+    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+    HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
+    HIP_TRY(timer.start());
+    if (mode == 1) {
+      HIP_TRY(launch_out_fused(out_panel_args(a_m, MixedLinear{w_m, b, exps}, x, m, ln_rows ? RowNorm{ln_w, ln_b, ln_rows} : RowNorm()), s));
+    } else {
+      GemmArgs g{};
+      g.fmt = FMT_MIXED; g.w_exp = exps; g.a = a_m; g.w = w_m; g.bias = b; g.resid = x; g.c = x;
+      g.M = m; g.N = kDim; g.K = kDim; g.ldr = kDim; g.ldc = kDim;
+      HIP_TRY(launch_gemm_split(g, EPI_RESID, 0, s));
+      if (ln_rows) HIP_TRY(launch_layernorm(x, kDim, ln_w, ln_b, (__bf16*)ln_rows, m, s, FMT_MIXED));
+    }
+    HIP_TRY(timer.stop());
+  }
+  if (ms_per_rep) *ms_per_rep = timer.total_ms / reps;
+  return VETO_OK;
+}
+
+// Test / measurement hook of everything behind the attention of one layer (model_veto.py:96, :20-21, :125-143): x1 = x + a Wo^T +
+// bo, h = LayerNorm2(x1), x2 = x1 + W2 gelu(W1 h + b1) + b2 (+ LayerNorm rows of x2) on VETO_MIXED operands.  mode 0 = the
+// out-projection panel launch + the FeedForward panel launch, mode 1 = ONE launch (ffn_fused.hip MODE 2).
+size_t veto_debug_layer_tail_workspace_bytes(int32_t m) {
+  if (m <= 0) return 0;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  return align_up(mp * kDim * 4, 256) + align_up((size_t)kDim * kDim * 4, 256) + 2 * align_up((size_t)2 * kDim * kDim * 4, 256) + 256;
+}
+
+int veto_debug_layer_tail(void* stream, const float* a, const float* wo, const float* bo, const float* ln2_w, const float* ln2_b,
+                          const float* w1, const float* b1, const float* w2, const float* b2, float* x, int32_t m, int32_t mode,
+                          int32_t reps, float* ms_per_rep, void* workspace, size_t workspace_bytes, const float* ln_w, const float* ln_b,
+                          void* ln_rows) {
+  if (!a || !wo || !bo || !ln2_w || !ln2_b || !w1 || !b1 || !w2 || !b2 || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
+  if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
+  if (workspace_bytes < veto_debug_layer_tail_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t mp = (size_t)gemm_rows_padded(m);
+  char* base = (char*)workspace;
+  __bf16* a_m = (__bf16*)base;
+  __bf16* wo_m = (__bf16*)(base + align_up(mp * kDim * 4, 256));
+  __bf16* w1_m = (__bf16*)((char*)wo_m + align_up((size_t)kDim * kDim * 4, 256));
+  __bf16* w2_m = (__bf16*)((char*)w1_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  int* exps = (int*)((char*)w2_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  HIP_TRY(launch_mixed_weight_rows(wo, wo_m, (size_t)kDim, kDim, exps + 0, s));
+  HIP_TRY(launch_mixed_weight_rows(w1, w1_m, (size_t)2 * kDim, kDim, exps + 1, s));
+  HIP_TRY(launch_mixed_weight_rows(w2, w2_m, (size_t)kDim, 2 * kDim, exps + 2, s));
+  EventTimer timer;      // every rep by itself
+  if (ms_per_rep) HIP_TRY(timer.init(s));
+  for (int r = 0; r < reps; ++r) {
+    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));       // the activation rows are overwritten in place: rebuilt per run, untimed
+    HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
+    HIP_TRY(timer.start());
+    // (every LayerNorm goes over the activation rows in place, as in the forward)
+    const MixedLinear out{wo_m, bo, exps + 0}, fc1{w1_m, b1, exps + 1}, fc2{w2_m, b2, exps + 2};
+    const RowNorm ln2{ln2_w, ln2_b, a_m};
+    if (mode == 1) {
+      HIP_TRY(launch_layer_tail(layer_tail_args(a_m, out, ln2, fc1, fc2, x, m, ln_rows ? RowNorm{ln_w, ln_b, nullptr} : RowNorm()), s));
+    } else {
+      HIP_TRY(launch_out_fused(out_panel_args(a_m, out, x, m, ln2), s));
+      HIP_TRY(launch_ffn_fused(ffn_panel_args(a_m, fc1, fc2, x, m, ln_rows ? RowNorm{ln_w, ln_b, a_m} : RowNorm()), s));
+    }
+    HIP_TRY(timer.stop());
+  }
+  if (ln_rows) HIP_TRY(hipMemcpyAsync(ln_rows, a_m, (size_t)m * kDim * 4, hipMemcpyDeviceToDevice, s));
+  if (ms_per_rep) *ms_per_rep = timer.total_ms / reps;
+  return VETO_OK;
+}
+
+// Test / bench hook of the fused QKV + attention launch: a = LayerNorm1 rows fp32 [19 n_pair, 576], wqkv fp32 [1728, 576]; out_rows receives
+// the attention output as mixed rows [19 n_pair, 4*576 B].  mode 1 = qkv_attn_fused.hip, mode 0 = the two launches it replaces (QKV GEMM
+// with 3-byte q / k / v + attention_mfma_kernel).
+size_t veto_debug_qkv_attn_workspace_bytes(int32_t n_pair) {
+  if (n_pair <= 0) return 0;
+  const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens;
+  const size_t mp = (size_t)gemm_rows_padded((int)(tile_rows > m ? tile_rows : m));
+  return 2 * align_up(mp * kDim * 4, 256) + align_up(mp * 3 * kDim * 3, 256) + align_up((size_t)3 * kDim * kDim * 4, 256) + 256;
+}
+
+int veto_debug_qkv_attn(void* stream, const float* a, const float* wqkv, int32_t n_pair, int32_t heads, int32_t mode, int32_t reps,
+                        float* ms_per_rep, void* workspace, size_t workspace_bytes, void* out_rows) {
+  if (!a || !wqkv || !workspace || !out_rows) return fail(VETO_ERR_INVALID, "null argument");
+  if (n_pair <= 0 || reps <= 0 || (mode != 0 && mode != 1) || !qkv_attn_fused_supports(heads)) return fail(VETO_ERR_INVALID, "bad n_pair / reps / mode / heads");
+  if (workspace_bytes < veto_debug_qkv_attn_workspace_bytes(n_pair)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens;
+  const size_t mp = (size_t)gemm_rows_padded((int)(tile_rows > m ? tile_rows : m));
+  char* base = (char*)workspace;
+  __bf16* a_m = (__bf16*)base;
+  char* o_m = base + align_up(mp * kDim * 4, 256);
+  char* qkv = o_m + align_up(mp * kDim * 4, 256);
+  __bf16* w_m = (__bf16*)(qkv + align_up(mp * 3 * kDim * 3, 256));
+  int* exps = (int*)((char*)w_m + align_up((size_t)3 * kDim * kDim * 4, 256));
+  HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+  HIP_TRY(launch_mixed_act_rows(a, a_m, m, kDim, s));
+  HIP_TRY(launch_mixed_weight_rows(wqkv, w_m, (size_t)3 * kDim, kDim, exps, s));
+  EventTimer timer;      // the whole rep loop
+  if (ms_per_rep) HIP_TRY(timer.init(s));
+  HIP_TRY(timer.start());
+  for (int r = 0; r < reps; ++r) {
+    if (mode == 1) {
+      QkvAttnArgs q{};
+      q.a = (const char*)a_m; q.w = (const char*)w_m; q.w_exp = exps; q.o = o_m; q.n_pair = n_pair; q.heads = heads;
+      HIP_TRY(launch_qkv_attn_fused(q, s));
+    } else {
+      GemmArgs g{};
+      g.fmt = FMT_MIXED; g.w_exp = exps; g.a = a_m; g.w = w_m; g.c = (float*)qkv; g.M = (int)m; g.N = 3 * kDim; g.K = kDim; g.ldc = 3 * kDim;
+      HIP_TRY(launch_gemm_split(g, EPI_F24, 0, s));
+      AttnArgs t{};
+      t.qkv = (const float*)qkv; t.o = (__bf16*)o_m; t.n_pair = n_pair; t.heads = heads; t.cls_only = 0; t.qkv_f24 = 1; t.o_fmt = FMT_MIXED;
+      HIP_TRY(launch_attention(t, s));
+    }
+  }
+  HIP_TRY(timer.stop());
+  if (ms_per_rep) *ms_per_rep = timer.total_ms / reps;
+  HIP_TRY(hipMemcpyAsync(out_rows, o_m, m * kDim * 4, hipMemcpyDeviceToDevice, s));
+  return VETO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,554 @@
+// Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
+// box-head and RPN post-processing, the relation samplers, ROI pooling and the evaluator.  Each checks its argument struct,
+// carves its workspace and makes one launch (kernels.h).
+#include <cmath>
+
+#include "abi_internal.h"
+
+extern "C" {
+
+int veto_enumerate_pairs(void* stream, int32_t n, int64_t* out) {
+  if (n < 0 || !out) return fail(VETO_ERR_INVALID, "bad argument");
+  HIP_TRY(launch_enumerate_pairs(n, out, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+size_t veto_postprocess_workspace_bytes(int32_t n_pair, int32_t n_rel_cls) {
+  if (n_pair <= 0 || n_rel_cls <= 0) return 0;
+  return align_up((size_t)n_pair * n_rel_cls * 4, 256) + 3 * align_up((size_t)n_pair * 4, 256);
+}
+
+int veto_postprocess(void* stream, const veto_post_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_post_args_t)) return fail(VETO_ERR_INVALID, "veto_post_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_obj <= 0 || a->n_pair <= 0 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
+    return fail(VETO_ERR_INVALID, "bad sizes");
+  if (!a->rel_logits || !a->rel_pairs || !a->img_obj_offset || !a->img_pair_offset || !a->obj_scores ||
+      !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (a->max_pairs_per_image < 1 || a->max_pairs_per_image > postprocess_max_pairs_per_image())
+    return fail(VETO_ERR_INVALID, "max_pairs_per_image %d outside 1..%d (MAX_PROPOSAL_PAIR is 2048 at test time)",
+                a->max_pairs_per_image, postprocess_max_pairs_per_image());
+  if (workspace_bytes < veto_postprocess_workspace_bytes(a->n_pair, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  char* base = (char*)workspace;
+  PostArgs p{};
+  p.rel_logits = a->rel_logits; p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
+  p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset;
+  p.n_img = a->n_img; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
+  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
+  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
+  p.prob_tmp = (float*)base;
+  base += align_up((size_t)a->n_pair * a->n_rel_cls * 4, 256);
+  p.triple = (float*)base; base += align_up((size_t)a->n_pair * 4, 256);
+  p.label_tmp = (int32_t*)base; base += align_up((size_t)a->n_pair * 4, 256);
+  p.perm = (int32_t*)base;
+  HIP_TRY(launch_postprocess(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_post_meet_args_t)) return fail(VETO_ERR_INVALID, "veto_post_meet_args_t size mismatch");
+  if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
+    return fail(VETO_ERR_INVALID, "bad sizes");
+  if (!a->group_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
+      !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  const long total = (long)a->n_groups * a->n_pair;
+  if (total > postprocess_max_pairs_per_image())
+    return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
+  if (workspace_bytes < veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  std::vector<MeetGroup> groups(a->n_groups);
+  for (int k = 0; k < a->n_groups; ++k) {
+    MeetGroup& g = groups[k];
+    g.logits = a->group_logits[k];
+    g.width = a->group_widths[k];
+    g.row0 = k * a->n_pair;
+    if (!g.logits || g.width < 3 || g.width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
+    int n = 0;
+    g.cols[n++] = 0;
+    for (int c = 0; c < a->n_rel_cls; ++c)
+      if (a->incre_idx_list[c] == k + 1) {
+        if (n >= g.width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
+        g.cols[n++] = c;
+      }
+    if (n != g.width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, g.width);
+  }
+  char* base = (char*)workspace;
+  PostArgs p{};
+  p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
+  p.n_img = 1; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
+  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
+  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
+  p.prob_tmp = (float*)base;
+  base += align_up((size_t)total * a->n_rel_cls * 4, 256);
+  p.triple = (float*)base; base += align_up((size_t)total * 4, 256);
+  p.label_tmp = (int32_t*)base; base += align_up((size_t)total * 4, 256);
+  p.perm = (int32_t*)base;
+  HIP_TRY(launch_postprocess_meet(p, groups.data(), a->n_groups, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_post_vote_args_t)) return fail(VETO_ERR_INVALID, "veto_post_vote_args_t size mismatch");
+  if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
+    return fail(VETO_ERR_INVALID, "bad sizes");
+  if (a->voting != 0 && a->voting != 1) return fail(VETO_ERR_INVALID, "voting must be 0 ('C') or 1 ('U')");
+  if (!a->expert_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
+      !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted || !a->kept_count)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  const long total = (long)a->n_groups * a->n_pair;
+  if (total > postprocess_max_pairs_per_image())
+    return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
+  if (workspace_bytes < veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  std::vector<VoteGroup> groups(a->n_groups);
+  for (int k = 0; k < a->n_groups; ++k) {
+    VoteGroup& g = groups[k];
+    for (int e = 0; e < 3; ++e) {
+      g.logits[e] = a->expert_logits[3 * k + e];
+      if (!g.logits[e]) return fail(VETO_ERR_INVALID, "group %d expert %d: null logits", k, e + 1);
+    }
+    g.width = a->group_widths[k];
+    g.row0 = k * a->n_pair;
+    if (g.width < 3 || g.width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
+    int n = 0;
+    g.cols[n++] = 0;
+    for (int c = 0; c < a->n_rel_cls; ++c)
+      if (a->incre_idx_list[c] == k + 1) {
+        if (n >= g.width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
+        g.cols[n++] = c;
+      }
+    if (n != g.width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, g.width);
+  }
+  char* base = (char*)workspace;
+  PostArgs p{};
+  p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
+  p.n_img = 1; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
+  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
+  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
+  p.kept_count = a->kept_count;
+  p.prob_tmp = (float*)base;
+  base += align_up((size_t)total * a->n_rel_cls * 4, 256);
+  p.triple = (float*)base; base += align_up((size_t)total * 4, 256);
+  p.label_tmp = (int32_t*)base; base += align_up((size_t)total * 4, 256);
+  p.perm = (int32_t*)base;
+  HIP_TRY(launch_postprocess_vote(p, groups.data(), a->n_groups, a->voting, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+size_t veto_obj_decode_workspace_bytes(int32_t n_obj, int32_t n_cls) {
+  if (n_obj <= 0 || n_cls <= 0) return 0;
+  return align_up((size_t)n_obj * n_cls * 4, 256);
+}
+
+int veto_obj_decode(void* stream, const veto_obj_decode_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_obj_decode_args_t)) return fail(VETO_ERR_INVALID, "veto_obj_decode_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_obj <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->max_obj_per_image < 1 || a->max_obj_per_image > obj_decode_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 1..%d (DETECTIONS_PER_IMG)", a->max_obj_per_image,
+                obj_decode_max_objects());
+  if (a->mode != 0 && a->mode != 1) return fail(VETO_ERR_INVALID, "mode must be 0 (PostProcessor) or 1 (MEET decoder)");
+  if (!a->boxes_per_cls || !a->img_obj_offset || !a->obj_pred || (a->mode == 0 && !a->logits) || (a->mode == 1 && !a->labels) ||
+      (a->obj_scores && !a->logits))
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (!workspace || workspace_bytes < veto_obj_decode_workspace_bytes(a->n_obj, a->n_cls))
+    return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ObjDecodeArgs p{};
+  p.logits = a->logits; p.labels = a->labels; p.boxes_per_cls = a->boxes_per_cls; p.img_off = a->img_obj_offset;
+  p.n_img = a->n_img; p.n_cls = a->n_cls; p.mode = a->mode; p.thr = a->nms_thres;
+  p.prob_ws = (float*)workspace;
+  p.obj_pred = a->obj_pred; p.obj_scores = a->obj_scores; p.out_boxes = a->boxes;
+  HIP_TRY(launch_obj_decode(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_pair_args_t)) return fail(VETO_ERR_INVALID, "veto_pair_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_obj < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
+  if (a->max_obj_per_image < 0 || a->max_obj_per_image > obj_decode_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d", a->max_obj_per_image, obj_decode_max_objects());
+  if (a->max_pairs < 1 || a->max_pairs > prepare_pairs_max_pairs())
+    return fail(VETO_ERR_INVALID, "max_pairs %d outside 1..%d (MAX_PROPOSAL_PAIR)", a->max_pairs, prepare_pairs_max_pairs());
+  if ((a->n_obj > 0 && (!a->boxes || !a->scores)) || !a->img_obj_offset || !a->img_out_offset || !a->pairs || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  PairArgs p{};
+  p.boxes = a->boxes; p.scores = a->scores; p.img_off = a->img_obj_offset; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.max_pairs = a->max_pairs; p.require_overlap = a->require_overlap != 0;
+  p.pairs = a->pairs; p.counts = a->counts;
+  HIP_TRY(launch_prepare_pairs(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_nms_max_segment(void) { return nms_max_segment(); }
+
+// host offsets: 0 = first, non-decreasing, last = total, no segment above `limit`; returns the largest segment or -1 (error set)
+static int check_host_offsets(const int32_t* off, int n_seg, int total, int limit, const char* name, const char* total_name) {
+  if (off[0] != 0) return fail(VETO_ERR_INVALID, "%s[0] must be 0, got %d", name, off[0]);
+  int largest = 0;
+  for (int s = 0; s < n_seg; ++s) {
+    const int n = off[s + 1] - off[s];
+    if (n < 0) return fail(VETO_ERR_INVALID, "%s is not monotone: entry %d is %d after %d", name, s + 1, off[s + 1], off[s]);
+    if (n > limit) return fail(VETO_ERR_INVALID, "%s: segment %d holds %d boxes, the limit is %d", name, s, n, limit);
+    if (n > largest) largest = n;
+  }
+  if (off[n_seg] != total) return fail(VETO_ERR_INVALID, "%s ends at %d, %s is %d", name, off[n_seg], total_name, total);
+  return largest;
+}
+
+int veto_nms(void* stream, const veto_nms_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_nms_args_t)) return fail(VETO_ERR_INVALID, "veto_nms_args_t size mismatch");
+  if (a->n_seg <= 0 || a->n_box < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_seg %d, n_box %d)", a->n_seg, a->n_box);
+  if (!a->seg_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: seg_offset_host");
+  const int largest = check_host_offsets(a->seg_offset_host, a->n_seg, a->n_box, nms_max_segment(), "seg_offset_host", "n_box");
+  if (largest < 0) return largest;
+  if ((a->n_box > 0 && (!a->boxes || !a->scores || !a->keep)) || !a->seg_offset || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (((uintptr_t)a->boxes & 15) != 0) return fail(VETO_ERR_INVALID, "boxes must be 16-byte aligned");
+  NmsArgs p{};
+  p.boxes = a->boxes; p.scores = a->scores; p.seg_off = a->seg_offset; p.n_seg = a->n_seg; p.max_keep = a->max_keep;
+  p.thr = a->threshold; p.keep = a->keep; p.counts = a->counts;
+  HIP_TRY(launch_nms(p, largest, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// workspace: prob | dec | row_score | row_label | list_score | list_row | list_label
+static size_t box_post_list_rows(int32_t n_box, int32_t n_cls, int32_t filter_dup) {
+  return filter_dup ? (size_t)n_box : (size_t)n_box * (n_cls - 1);
+}
+
+size_t veto_box_postprocess_workspace_bytes(int32_t n_box, int32_t n_cls, int32_t filter_duplicates) {
+  if (n_box <= 0 || n_cls < 2) return 256;
+  const size_t rows = box_post_list_rows(n_box, n_cls, filter_duplicates);
+  return align_up((size_t)n_box * n_cls * 4, 256) + align_up((size_t)n_box * n_cls * 16, 256) + 2 * align_up((size_t)n_box * 4, 256) +
+         3 * align_up(rows * 4, 256);
+}
+
+int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_box_post_args_t)) return fail(VETO_ERR_INVALID, "veto_box_post_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_box <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_box %d)", a->n_img, a->n_box);
+  if (a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d above 65535", a->n_img);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->reg_cols < 4 || a->reg_cols % 4 != 0 || (!a->cls_agnostic && a->reg_cols != 4 * a->n_cls))
+    return fail(VETO_ERR_INVALID, "reg_cols %d: must be 4 * n_cls (%d), or a multiple of 4 with cls_agnostic", a->reg_cols, 4 * a->n_cls);
+  if (!(a->score_thresh >= 0.f)) return fail(VETO_ERR_INVALID, "score_thresh %g must be >= 0 (SCORE_THRESH)", a->score_thresh);
+  if (!(a->nms_thresh > 0.f)) return fail(VETO_ERR_INVALID, "nms_thresh %g must be > 0 (ROI_HEADS.NMS)", a->nms_thresh);
+  for (int k = 0; k < 4; ++k)
+    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0 (BBOX_REG_WEIGHTS)", k, a->reg_weights[k]);
+  if (!a->img_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_offset_host");
+  const int largest = check_host_offsets(a->img_offset_host, a->n_img, a->n_box, nms_max_segment(), "img_offset_host", "n_box");
+  if (largest < 0) return largest;
+  if (!a->class_logits || !a->box_regression || !a->proposals || !a->image_sizes || !a->img_offset || !a->img_out_offset ||
+      !a->orig_inds || !a->pred_labels || !a->pred_scores || !a->boxes || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if ((((uintptr_t)a->box_regression | (uintptr_t)a->proposals | (uintptr_t)a->boxes | (uintptr_t)a->boxes_per_cls) & 15) != 0)
+    return fail(VETO_ERR_INVALID, "box_regression, proposals, boxes and boxes_per_cls must be 16-byte aligned");
+  const size_t need = veto_box_postprocess_workspace_bytes(a->n_box, a->n_cls, a->filter_duplicates);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
+                                                        workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  BoxPostArgs p{};
+  p.logits = a->class_logits; p.regression = a->box_regression; p.proposals = a->proposals; p.image_sizes = a->image_sizes;
+  p.img_off = a->img_offset; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.n_box = a->n_box; p.n_cls = a->n_cls; p.reg_cols = a->reg_cols; p.cls_agnostic = a->cls_agnostic != 0;
+  p.topn = a->post_nms_per_cls_topn; p.filter_dup = a->filter_duplicates != 0; p.det_per_img = a->detections_per_img;
+  p.score_thresh = a->score_thresh; p.nms_thresh = a->nms_thresh;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.xform_clip = a->bbox_xform_clip;
+  const size_t rows = box_post_list_rows(a->n_box, a->n_cls, a->filter_duplicates);
+  char* base = (char*)workspace;
+  p.prob = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 4, 256);
+  p.dec = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 16, 256);
+  p.row_score = (float*)base; base += align_up((size_t)a->n_box * 4, 256);
+  p.row_label = (int32_t*)base; base += align_up((size_t)a->n_box * 4, 256);
+  p.list_score = (float*)base; base += align_up(rows * 4, 256);
+  p.list_row = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.list_label = (int32_t*)base;
+  p.orig_inds = a->orig_inds; p.labels = a->pred_labels; p.scores = a->pred_scores; p.boxes = a->boxes;
+  p.boxes_per_cls = a->boxes_per_cls; p.counts = a->counts;
+  HIP_TRY(launch_box_postprocess(p, largest, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// the host fields of the RPN arguments: capacity = the largest k of a level, or -1 (error set)
+static int rpn_check_shapes(const veto_rpn_args_t* a) {
+  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
+  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  if (a->pre_nms_top_n <= 0 || a->pre_nms_top_n > nms_max_segment())
+    return fail(VETO_ERR_INVALID, "pre_nms_top_n %d outside 1..%d (MODEL.RPN.PRE_NMS_TOP_N; the limit is veto_nms_max_segment())",
+                a->pre_nms_top_n, nms_max_segment());
+  int capacity = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
+      return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+    const int64_t n = (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+    if (n > INT32_MAX) return fail(VETO_ERR_INVALID, "level %d holds %lld anchors, the limit is %d", l, (long long)n, INT32_MAX);
+    const int k = n < a->pre_nms_top_n ? (int)n : a->pre_nms_top_n;
+    if (k > capacity) capacity = k;
+  }
+  return capacity;
+}
+
+// workspace: cand_box | cand_logit | cand_anchor | keep | live | kept | cut
+size_t veto_rpn_proposals_workspace_bytes(const veto_rpn_args_t* a) {
+  if (!a || a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return 0;
+  const int capacity = rpn_check_shapes(a);
+  if (capacity < 0) return 0;
+  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
+  return align_up(rows * 16, 256) + 3 * align_up(rows * 4, 256) + 2 * align_up(n_seg * 4, 256) + align_up((4 + (size_t)a->n_img) * 4, 256);
+}
+
+int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return fail(VETO_ERR_INVALID, "veto_rpn_args_t size mismatch");
+  const int capacity = rpn_check_shapes(a);
+  if (capacity < 0) return capacity;
+  const bool nms_on = a->nms_thresh > 0.f, merge = a->n_lvl > 1;
+  if (merge && a->fpn_post_nms_top_n <= 0) return fail(VETO_ERR_INVALID, "fpn_post_nms_top_n %d must be > 0 with %d levels", a->fpn_post_nms_top_n, a->n_lvl);
+  for (int k = 0; k < 4; ++k)
+    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0", k, a->reg_weights[k]);
+  if (merge && a->per_batch) {
+    if (a->n_img > rpn_batch_cut_max_images())
+      return fail(VETO_ERR_INVALID, "per_batch: n_img %d above %d", a->n_img, rpn_batch_cut_max_images());
+  } else if (merge) {   // the per-image merge sorts every survivor of the image in one workgroup
+    int64_t bound = 0;
+    for (int l = 0; l < a->n_lvl; ++l) {
+      const int64_t n = (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+      const int64_t k = n < a->pre_nms_top_n ? n : a->pre_nms_top_n;
+      bound += nms_on && a->post_nms_top_n > 0 && a->post_nms_top_n < k ? a->post_nms_top_n : k;
+    }
+    if (bound > kRpnSortCap)
+      return fail(VETO_ERR_INVALID, "the levels may leave %lld proposals per image, the merge takes %d (lower post_nms_top_n)", (long long)bound,
+                  kRpnSortCap);
+  }
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (!a->objectness[l] || !a->box_regression[l] || !a->anchors[l]) return fail(VETO_ERR_INVALID, "missing pointer: level %d", l);
+    if (((uintptr_t)a->anchors[l] & 15) != 0) return fail(VETO_ERR_INVALID, "anchors[%d] must be 16-byte aligned", l);
+    if ((((uintptr_t)a->objectness[l] | (uintptr_t)a->box_regression[l]) & 3) != 0) return fail(VETO_ERR_INVALID, "level %d: misaligned floats", l);
+  }
+  if (!a->image_sizes || !a->img_out_offset || !a->boxes || !a->objectness_out || !a->level || !a->anchor_index || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (((uintptr_t)a->boxes & 15) != 0) return fail(VETO_ERR_INVALID, "boxes must be 16-byte aligned");
+  const size_t need = veto_rpn_proposals_workspace_bytes(a);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  RpnArgs p{};
+  for (int l = 0; l < a->n_lvl; ++l) {
+    RpnLevel& v = p.lvl[l];
+    v.objectness = a->objectness[l]; v.regression = a->box_regression[l]; v.anchors = a->anchors[l];
+    v.A = a->level_a[l]; v.HW = a->level_h[l] * a->level_w[l]; v.N = v.A * v.HW;
+    v.k = v.N < a->pre_nms_top_n ? v.N : a->pre_nms_top_n;
+  }
+  p.image_sizes = a->image_sizes; p.out_off = a->img_out_offset;
+  p.n_img = a->n_img; p.n_lvl = a->n_lvl; p.capacity = capacity;
+  p.post_top_n = a->post_nms_top_n; p.fpn_top_n = a->fpn_post_nms_top_n; p.per_batch = a->per_batch != 0; p.nms_on = nms_on;
+  p.nms_thresh = a->nms_thresh; p.min_size = a->min_size;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.xform_clip = a->bbox_xform_clip;
+  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
+  char* base = (char*)workspace;
+  p.cand_box = (float*)base; base += align_up(rows * 16, 256);
+  p.cand_logit = (float*)base; base += align_up(rows * 4, 256);
+  p.cand_anchor = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.keep = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.live = (int32_t*)base; base += align_up(n_seg * 4, 256);
+  p.kept = (int32_t*)base; base += align_up(n_seg * 4, 256);
+  p.cut = (int32_t*)base;
+  p.boxes = a->boxes; p.objectness = a->objectness_out; p.level = a->level; p.anchor_index = a->anchor_index; p.counts = a->counts;
+  HIP_TRY(launch_rpn_proposals(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel) {
+  if (n_rel_cells <= 0 || num_sample_per_gt_rel <= 0) return 256;
+  return align_up((size_t)n_rel_cells * 8, 256) + align_up((size_t)n_rel_cells * num_sample_per_gt_rel * 4, 256);
+}
+
+int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_detect_relsample_args_t))
+    return fail(VETO_ERR_INVALID, "veto_detect_relsample_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_prp < 0 || a->n_tgt < 0 || a->n_rel_cells < 0)
+    return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d, n_tgt %d, n_rel_cells %d)", a->n_img, a->n_prp, a->n_tgt,
+                a->n_rel_cells);
+  const int lim = relsample_max_objects();
+  if (a->max_prp_per_image < 0 || a->max_prp_per_image > lim)
+    return fail(VETO_ERR_INVALID, "max_prp_per_image %d outside 0..%d (detections per image, DETECTIONS_PER_IMG)",
+                a->max_prp_per_image, lim);
+  if (a->max_tgt_per_image < 0 || a->max_tgt_per_image > lim)
+    return fail(VETO_ERR_INVALID, "max_tgt_per_image %d outside 0..%d (GT boxes per image)", a->max_tgt_per_image, lim);
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > relsample_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                relsample_max_batch());
+  if (a->num_sample_per_gt_rel < 1 || a->num_sample_per_gt_rel > relsample_max_per_rel())
+    return fail(VETO_ERR_INVALID, "num_sample_per_gt_rel %d outside 1..%d (NUM_SAMPLE_PER_GT_REL)", a->num_sample_per_gt_rel,
+                relsample_max_per_rel());
+  if (a->max_fg_per_image < 0 || a->max_fg_per_image > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "max_fg_per_image %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)",
+                a->max_fg_per_image, a->batch_size_per_image);
+  if ((a->n_prp > 0 && (!a->prp_boxes || !a->prp_labels || !a->prp_scores || !a->locating_match)) ||
+      (a->n_tgt > 0 && (!a->tgt_boxes || !a->tgt_labels)) || (a->n_rel_cells > 0 && !a->relation) ||
+      (a->relation_non_masked && !a->labels_all) || !a->img_prp_offset || !a->img_tgt_offset || !a->img_rel_offset ||
+      !a->img_binary_offset || !a->pairs || !a->labels || !a->binary_rel || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  const size_t need = veto_detect_relsample_workspace_bytes(a->n_rel_cells, a->num_sample_per_gt_rel);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
+                                                        workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  RelSampleArgs p{};
+  p.prp_boxes = a->prp_boxes; p.prp_labels = a->prp_labels; p.prp_scores = a->prp_scores;
+  p.tgt_boxes = a->tgt_boxes; p.tgt_labels = a->tgt_labels;
+  p.relation = a->relation; p.relation_nm = a->relation_non_masked;
+  p.prp_off = a->img_prp_offset; p.tgt_off = a->img_tgt_offset; p.rel_off = a->img_rel_offset; p.bin_off = a->img_binary_offset;
+  p.n_img = a->n_img; p.require_overlap = a->require_overlap != 0; p.per_rel = a->num_sample_per_gt_rel;
+  p.max_fg = a->max_fg_per_image; p.batch = a->batch_size_per_image;
+  p.out_rows = a->batch_size_per_image > 2 ? a->batch_size_per_image : 2;
+  p.fg_thres = a->fg_thres; p.seed = a->seed;
+  p.ws_nm = (int64_t*)workspace;
+  p.ws_fg = (uint32_t*)((char*)workspace + align_up((size_t)a->n_rel_cells * 8, 256));
+  p.pairs = a->pairs; p.labels = a->labels; p.labels_all = a->relation_non_masked ? a->labels_all : nullptr;
+  p.binary = a->binary_rel; p.locating = a->locating_match; p.counts = a->counts;
+  HIP_TRY(launch_detect_relsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_gtbox_relsample_args_t))
+    return fail(VETO_ERR_INVALID, "veto_gtbox_relsample_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_rel_cells < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_rel_cells %d)", a->n_img, a->n_rel_cells);
+  if (a->max_obj_per_image < 0 || a->max_obj_per_image > gtbox_relsample_max_objects())
+    return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d (GT boxes per image)", a->max_obj_per_image,
+                gtbox_relsample_max_objects());
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > gtbox_relsample_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                gtbox_relsample_max_batch());
+  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
+                a->batch_size_per_image);
+  if ((a->n_rel_cells > 0 && (!a->relation || !a->binary_rel)) || !a->img_obj_offset || !a->img_rel_offset || !a->pairs ||
+      !a->labels || !a->counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  GtboxRelSampleArgs p{};
+  p.relation = a->relation; p.obj_off = a->img_obj_offset; p.rel_off = a->img_rel_offset;
+  p.n_img = a->n_img; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img; p.seed = a->seed;
+  p.pairs = a->pairs; p.labels = a->labels; p.binary = a->binary_rel; p.counts = a->counts;
+  HIP_TRY(launch_gtbox_relsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
+static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_roi_pool_args_t)) return fail(VETO_ERR_INVALID, "veto_roi_pool_args_t size mismatch");
+  if (a->n_levels < 1 || a->n_levels > 4) return fail(VETO_ERR_INVALID, "n_levels must be 1..4, got %d", a->n_levels);
+  if (a->n_img <= 0 || a->n_roi <= 0 || a->channels <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_roi %d, channels %d)", a->n_img, a->n_roi, a->channels);
+  if (a->pooled < 1 || a->pooled > 8) return fail(VETO_ERR_INVALID, "pooled must be 1..8, got %d", a->pooled);
+  if (a->sampling_ratio < 1 || a->sampling_ratio > 4)
+    return fail(VETO_ERR_INVALID, "sampling_ratio must be 1..4 (adaptive sampling is not built), got %d", a->sampling_ratio);
+  if (!a->rois || (forward && !a->out_rgb)) return fail(VETO_ERR_INVALID, "missing pointer");
+  const bool has_depth = forward ? a->depth_feat != nullptr : a->depth_h > 0;
+  if (has_depth && ((forward && !a->out_depth) || a->depth_channels <= 0 || a->depth_h <= 0 || a->depth_w <= 0))
+    return fail(VETO_ERR_INVALID, "depth map given without out_depth / sizes");
+  RoiPoolArgs p{};
+  for (int l = 0; l < a->n_levels; ++l) {
+    if ((forward && !a->level_feat[l]) || a->level_h[l] <= 0 || a->level_w[l] <= 0 || !(a->level_scale[l] > 0.f))
+      return fail(VETO_ERR_INVALID, "bad pyramid level %d", l);
+    p.lv[l] = RoiLevel{a->level_feat[l], a->level_h[l], a->level_w[l], a->level_scale[l]};
+  }
+  p.n_levels = a->n_levels;
+  // poolers.py:86-88: the level range follows from the first and last scale
+  p.k_min = (int)lroundf(-log2f(a->level_scale[0]));
+  p.k_max = (int)lroundf(-log2f(a->level_scale[a->n_levels - 1]));
+  if (has_depth) {
+    const int dl = a->n_levels > 1 ? 2 : 0;  // poolers.py:146-149
+    if (dl >= a->n_levels) return fail(VETO_ERR_INVALID, "the depth pooler is level 2; need at least 3 levels or exactly 1");
+    p.depth = RoiLevel{a->depth_feat, a->depth_h, a->depth_w, a->level_scale[dl]};
+  }
+  p.n_roi = a->n_roi; p.channels = a->channels; p.depth_channels = has_depth ? a->depth_channels : 0;
+  p.pooled = a->pooled; p.sampling_ratio = a->sampling_ratio;
+  p.rois = a->rois; p.out_rgb = a->out_rgb; p.out_depth = a->out_depth; p.out_levels = a->out_levels;
+  *out = p;
+  return VETO_OK;
+}
+
+int veto_roi_pool(void* stream, const veto_roi_pool_args_t* a) {
+  RoiPoolArgs p{};
+  const int rc = roi_pool_args(a, true, &p);
+  if (rc != VETO_OK) return rc;
+  HIP_TRY(launch_roi_pool(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
+                           float* const* level_grad, float* depth_grad) {
+  RoiPoolArgs p{};
+  const int rc = roi_pool_args(a, false, &p);
+  if (rc != VETO_OK) return rc;
+  if (!grad_rgb || !level_grad) return fail(VETO_ERR_INVALID, "missing gradient pointer");
+  for (int l = 0; l < p.n_levels; ++l) {
+    if (!level_grad[l]) return fail(VETO_ERR_INVALID, "level_grad[%d] is null", l);
+    p.lv_grad[l] = level_grad[l];
+  }
+  if ((grad_depth != nullptr) != (depth_grad != nullptr)) return fail(VETO_ERR_INVALID, "grad_depth and depth_grad go together");
+  if (grad_depth && p.depth.H <= 0) return fail(VETO_ERR_INVALID, "depth gradient without depth sizes in args");
+  if (grad_depth) p.depth.feat = grad_depth;   // only its non-null-ness and the sizes are used
+  else p.depth.feat = nullptr;
+  p.gout_rgb = grad_rgb; p.gout_depth = grad_depth; p.depth_grad = depth_grad;
+  HIP_TRY(launch_roi_pool_backward(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_t n_gt_total, int32_t n_rel_cls) {
+  if (n_img <= 0 || n_pair_total < 0 || n_gt_total < 0 || n_rel_cls < 2) return 0;
+  return 5 * align_up((size_t)n_pair_total * 4 + 4, 256) + align_up((size_t)n_gt_total * 4 + 4, 256) +
+         align_up((size_t)n_img * 7 * n_rel_cls * 4, 256);
+}
+
+int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_total, int32_t n_gt_total, void* workspace,
+                  size_t workspace_bytes) {
+  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  // the struct before pred_obj_offset was appended is still accepted (GT-box modes, pred_obj_offset = NULL)
+  const bool has_pred_off = a->struct_size == (int32_t)sizeof(veto_sgg_eval_args_t);
+  if (!has_pred_off && a->struct_size != (int32_t)offsetof(veto_sgg_eval_args_t, pred_obj_offset))
+    return fail(VETO_ERR_INVALID, "veto_sgg_eval_args_t size mismatch");
+  if (a->reserved0 != 0 && a->reserved0 != 1) return fail(VETO_ERR_INVALID, "mode (reserved0) must be 0 (GT boxes) or 1 (sgdet)");
+  const int32_t* pred_off = has_pred_off ? a->pred_obj_offset : nullptr;
+  if (a->reserved0 == 1 && !pred_off) return fail(VETO_ERR_INVALID, "sgdet needs pred_obj_offset");
+  if (a->n_img <= 0 || a->n_rel_cls < 2 || a->n_rel_cls > 4096 || a->n_zeroshot < 0 || n_pair_total < 0 || n_gt_total < 0)
+    return fail(VETO_ERR_INVALID, "bad sizes");
+  if (!(a->iou_thres >= 0.f && a->iou_thres <= 1.f)) return fail(VETO_ERR_INVALID, "iou_thres must be in [0, 1]");
+  if (!a->gt_offset || !a->obj_offset || !a->pair_offset || !a->gt_rels || !a->gt_classes || !a->gt_boxes || !a->pred_pairs ||
+      !a->rel_scores || !a->pred_classes || !a->pred_boxes || !a->obj_scores || (a->n_zeroshot > 0 && !a->zeroshot) ||
+      !a->gc_rank || !a->ng_rank || !a->acc_rank || !a->zeroshot_flag || !a->ng_rows || !a->ng_cols || !a->ng_count || !a->metrics)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if (workspace_bytes < veto_sgg_eval_workspace_bytes(a->n_img, n_pair_total, n_gt_total, a->n_rel_cls))
+    return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  SggEvalArgs p{};
+  p.n_img = a->n_img; p.n_rel_cls = a->n_rel_cls; p.n_zeroshot = a->n_zeroshot; p.iou_thres = a->iou_thres;
+  p.gt_off = a->gt_offset; p.obj_off = a->obj_offset; p.pair_off = a->pair_offset;
+  p.pred_obj_off = pred_off; p.mode = a->reserved0;
+  p.gt_rels = a->gt_rels; p.gt_classes = a->gt_classes; p.gt_boxes = a->gt_boxes;
+  p.pred_pairs = a->pred_pairs; p.rel_scores = a->rel_scores; p.pred_classes = a->pred_classes;
+  p.pred_boxes = a->pred_boxes; p.obj_scores = a->obj_scores; p.zeroshot = a->zeroshot;
+  p.gc_rank = a->gc_rank; p.ng_rank = a->ng_rank; p.acc_rank = a->acc_rank; p.zeroshot_flag = a->zeroshot_flag;
+  p.ng_rows = a->ng_rows; p.ng_cols = a->ng_cols; p.ng_count = a->ng_count; p.metrics = a->metrics;
+  char* base = (char*)workspace;
+  const size_t per_pair = align_up((size_t)n_pair_total * 4 + 4, 256);
+  p.label_tmp = (int32_t*)base; base += per_pair;
+  p.flag_tmp = (int32_t*)base; base += per_pair;
+  p.flag_before = (int32_t*)base; base += per_pair;
+  p.pair_score = (float*)base; base += per_pair;
+  p.row_key = (uint32_t*)base; base += per_pair;
+  p.acc_first = (int32_t*)base; base += align_up((size_t)n_gt_total * 4 + 4, 256);
+  p.cls_table = (int32_t*)base;
+  HIP_TRY(launch_sgg_eval(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,267 @@
+// What the host-side translation units of the C ABI (abi_core / abi_forward / abi_train / abi_detect / abi_debug .hip) share: the
+// error string, the handle with its weight store and profiler, the GEMM launch helper and the argument builders of the launches
+// that both a forward and a test hook of it make.  Host only; no kernel source includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/veto_amd.h"
+#include "kernels.h"
+
+using namespace veto;
+
+#pragma GCC visibility push(hidden)      // nothing below is part of the library's interface
+
+extern thread_local std::string g_abi_err;      // what veto_last_error returns: ONE object per thread (defined in abi_core.hip)
+
+inline int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_abi_err = buf;
+  return code;
+}
+
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t e__ = (expr);                                                                       \
+    if (e__ != hipSuccess) return fail(VETO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
+  } while (0)
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+struct Param {
+  std::string name;
+  size_t numel = 0;
+  size_t offset = 0;  // floats into the raw arena
+  bool loaded = false;
+};
+
+typedef __bf16* SplitW;  // [N, 2K] split rows (common.h)
+
+// The four Linears of a transformer layer, in the order of LayerW::exp_m: state-dict names behind "layers.<l>." and the shape [N, K]
+enum { LIN_QKV = 0, LIN_OUT = 1, LIN_FC1 = 2, LIN_FC2 = 3 };
+struct LayerLinear { const char* weight; const char* bias; int N, K; };
+const LayerLinear kLayerLinears[4] = {{"0.fn.to_qkv.weight", nullptr, 3 * kDim, kDim},
+                                      {"0.fn.to_out.0.weight", "0.fn.to_out.0.bias", kDim, kDim},
+                                      {"1.fn.net.0.weight", "1.fn.net.0.bias", 2 * kDim, kDim},
+                                      {"1.fn.net.3.weight", "1.fn.net.3.bias", kDim, 2 * kDim}};
+
+struct MixedLinear {   // one Linear on mixed rows (common.h): weight rows, fp32 bias, the device int holding the e4m3 exponent
+  const void* w;
+  const float* b;
+  const int* exp;
+};
+
+struct LayerW {
+  const float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *out_b, *fc1_b, *fc2_b;
+  SplitW qkv = nullptr, out = nullptr, fc1 = nullptr, fc2 = nullptr;
+  // VETO_MIXED: the same four weights as mixed rows (common.h) and their e4m3 exponents (device ints: qkv, out, fc1, fc2)
+  SplitW qkv_m = nullptr, out_m = nullptr, fc1_m = nullptr, fc2_m = nullptr;
+  int* exp_m = nullptr;
+  SplitW split(int lin) const { return lin == LIN_QKV ? qkv : lin == LIN_OUT ? out : lin == LIN_FC1 ? fc1 : fc2; }
+  SplitW mixed_rows(int lin) const { return lin == LIN_QKV ? qkv_m : lin == LIN_OUT ? out_m : lin == LIN_FC1 ? fc1_m : fc2_m; }
+  MixedLinear mixed(int lin) const {
+    const float* const bias[4] = {nullptr, out_b, fc1_b, fc2_b};
+    return MixedLinear{mixed_rows(lin), bias[lin], exp_m + lin};
+  }
+};
+
+struct ProfRec {
+  int name_id;
+  hipEvent_t start, stop;
+  double flops, bytes;
+};
+
+struct veto_handle_s {
+  veto_config_t cfg;
+  int dh = 0;
+  int chunk = 0;
+  std::vector<Param> params;
+  std::map<std::string, int> index;
+  float* raw = nullptr;      // fp32 copies of every state-dict tensor
+  char* derived = nullptr;   // split planes, transposes, folded tables
+  bool dirty = true;         // a weight was uploaded since the derived operands were built
+  bool infer_dirty = false;  // ... the training-side operands are current, the inference-only ones (mixed rows, layer-0 tables, folded last layer) are not
+  // generation of the derived weight operands (bumped by every finalize_weights) and, per training workspace, the generation its
+  // saved activations were computed with: veto_backward refuses a workspace whose forward saw other weights
+  uint64_t weight_gen = 0;
+  // (a handful of workspaces at most: a training loop re-uses one; the table is cleared by every weight upload and bounded besides)
+  static constexpr size_t kMaxTrainWorkspaces = 8;
+  std::map<const void*, uint64_t> train_gen;
+  void stamp_train_workspace(const void* ws) {
+    if (train_gen.size() >= kMaxTrainWorkspaces && !train_gen.count(ws)) {   // evict the entry of the oldest generation
+      auto old = train_gen.begin();
+      for (auto it = train_gen.begin(); it != train_gen.end(); ++it)
+        if (it->second < old->second) old = it;
+      train_gen.erase(old);
+    }
+    train_gen[ws] = weight_gen;
+  }
+  std::vector<LayerW> layers;
+  SplitW patch_w = nullptr;
+  // last layer, folded CLS attention (attention.hip): Mcat [heads*576, 2*576], Ncat [576, 2*heads*576], and their fp32 staging
+  SplitW fold_m = nullptr, fold_n = nullptr;
+  float* fold_tmp = nullptr;
+  // ... in block form (fold_dhp > 0: the head width padded to 32 k's divides a 192-column tile): Mcat = Wq^T Wk and Ncat = Wo Wv
+  // are products of rank dh per head, so u = (a0 Wq_pad^T) . blockdiag(Wk) and out = (abar . blockdiag(Wv)^T) Wo_pad^T take four
+  // GEMMs of 67 GF in all (zero blocks skipped: GemmArgs::kb_tiles) instead of two of 80 GF each
+  SplitW fold_q = nullptr, fold_k = nullptr, fold_v = nullptr, fold_o = nullptr;
+  int fold_dhp = 0;
+  // layer 0, per-object form of LayerNorm + QKV (rowops.hip): Wqkv diag(gamma) as a GEMM operand, vec = [c2 | b0 | qkv_cls]
+  SplitW q0_w = nullptr;
+  float* q0_vec = nullptr;
+  float* patch_bias = nullptr;
+  float* loc_wt = nullptr;
+  float* cls_wt = nullptr;
+  float* head_wt = nullptr;
+  // veto_forward_saturation: device counters [layers][VETO_SAT_SITES][4], allocated by veto_create (VETO_MIXED handles).  The call
+  // hands them to forward_impl as an argument -- no handle state changes, so a concurrent veto_forward on the same handle is unaffected --
+  // and forward_impl then takes the launch-per-stage form of the mixed path (every mixed-row operand exists in memory) and counts
+  // behind every producer
+  unsigned long long* sat_buf = nullptr;
+  // profiling
+  bool prof_on = false;
+  std::vector<std::string> prof_names;
+  std::vector<ProfRec> prof_recs;
+  std::vector<hipEvent_t> event_pool;
+  struct Agg { double ms = 0; int64_t n = 0; double flops = 0, bytes = 0; };
+  std::vector<Agg> prof_agg;
+
+  const float* p(const std::string& name) const { return raw + params[index.at(name)].offset; }
+  void add(const std::string& name, size_t numel) {
+    Param q;
+    q.name = name;
+    q.numel = numel;
+    index[name] = (int)params.size();
+    params.push_back(q);
+  }
+};
+
+constexpr const char* kT = "fusion_transformer.transformer.";
+
+inline std::string lname(int l, const char* rest) {
+  char buf[160];
+  snprintf(buf, sizeof(buf), "%slayers.%d.%s", kT, l, rest);
+  return buf;
+}
+
+inline int prof_id(veto_handle_t h, const char* name) {
+  for (size_t i = 0; i < h->prof_names.size(); ++i)
+    if (h->prof_names[i] == name) return (int)i;
+  h->prof_names.push_back(name);
+  h->prof_agg.emplace_back();
+  return (int)h->prof_names.size() - 1;
+}
+
+struct ProfScope {
+  veto_handle_t h;
+  hipStream_t s;
+  int rec = -1;
+  ProfScope(veto_handle_t h_, hipStream_t s_, const char* name, double flops, double bytes) : h(h_), s(s_) {
+    if (!h || !h->prof_on) return;
+    ProfRec r;
+    r.name_id = prof_id(h, name);
+    r.flops = flops;
+    r.bytes = bytes;
+    for (hipEvent_t* e : {&r.start, &r.stop}) {
+      if (!h->event_pool.empty()) { *e = h->event_pool.back(); h->event_pool.pop_back(); }
+      else if (hipEventCreate(e) != hipSuccess) return;
+    }
+    (void)hipEventRecord(r.start, s);      // profiling is best effort: a failed record shows up as a missing timing
+    h->prof_recs.push_back(r);
+    rec = (int)h->prof_recs.size() - 1;
+  }
+  ~ProfScope() {
+    if (rec >= 0) (void)hipEventRecord(h->prof_recs[rec].stop, s);
+  }
+};
+
+// abi_core.hip.  train_only: just the operands the training path reads (split rows of the Linears, the patch / pair-projection / head
+// re-layouts).  A training loop uploads every weight after every optimizer step; the mixed rows (a max-|w| reduction per tensor), the
+// table form of layer 0 and the folded last layer are the inference path's, and are built when an inference forward next needs them
+// (infer_dirty).
+int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only = false);
+
+struct DropSite {   // one dropout site of the training path: threshold p * 2^24 (0 = off), scale 1 / (1 - p)
+  unsigned long long seed = 0;
+  unsigned thresh = 0;
+  float scale = 1.f;
+};
+
+// (abi_core.hip) lda / ldc of split operands are in bf16 elements (2K / 2N for contiguous rows).
+int run_gemm(veto_handle_t h, hipStream_t s, const char* name, const __bf16* a, SplitW w, const float* bias, const float* resid, long ldr,
+             float* c, __bf16* c_split, long ldc, int M, int N, int K, int epi, long lda = 0, int w_row0 = 0, DropSite drop = DropSite(),
+             const int* w_exp = nullptr, int kb_tiles = 0, int kb_steps = 0);
+
+// ---- argument builders of the launches that the inference forward, the training forward and the test hooks share ---------------
+// Per-object embeddings (everything but the training path's dropout site).  bn_batch_stats given: training-mode BatchNorm on this
+// batch's statistics (biased variance), which the caller has launch_bn_batch_stats fill first
+inline ObjPrepArgs obj_prep_args(veto_handle_t h, const veto_inputs_t* in, float* lc) {
+  ObjPrepArgs a{};
+  a.boxes = in->boxes; a.box_mode = in->box_mode; a.labels = in->obj_labels; a.obj_logits = in->obj_logits;
+  a.embed = h->p("obj_embed.weight"); a.num_obj_cls = h->cfg.num_obj_cls; a.embed_dim = h->cfg.embed_dim;
+  a.bn_w = h->p("pos_embed.0.weight"); a.bn_b = h->p("pos_embed.0.bias");
+  a.bn_mean = in->bn_batch_stats ? in->bn_batch_stats : h->p("pos_embed.0.running_mean");
+  a.bn_var = in->bn_batch_stats ? in->bn_batch_stats + 4 : h->p("pos_embed.0.running_var");
+  a.pos_w = h->p("pos_embed.1.weight"); a.pos_b = h->p("pos_embed.1.bias");
+  a.loc_wt = h->loc_wt; a.loc_b = h->p("location_projection.0.bias");
+  a.cls_wt = h->cls_wt; a.cls_b = h->p("class_projection.0.bias");
+  a.lc = lc; a.pos_out = nullptr; a.n_obj = in->n_obj;
+  return a;
+}
+
+// Token assembly of n_pair pairs into x and the layer-0 LayerNorm1 rows a (split rows; the caller sets stats / a_fmt / x_f24 / dropout)
+inline AssembleArgs assemble_args(veto_handle_t h, const float* patch_tab, const float* lc, const int32_t* subj, const int32_t* obj, float* x,
+                                  __bf16* a_rows, int n_pair) {
+  AssembleArgs a{};
+  a.patch_tab = patch_tab; a.lc = lc; a.cls_token = h->p(std::string(kT) + "cls_token");
+  a.pos_embedding = h->p(std::string(kT) + "pos_embedding");
+  a.ln_w = h->layers[0].ln1_w; a.ln_b = h->layers[0].ln1_b;
+  a.subj = subj; a.obj = obj; a.x = x; a.a = a_rows; a.n_pair = n_pair;
+  return a;
+}
+
+struct RowNorm {   // optional LayerNorm of a panel launch's result rows (FfnArgs::ln_w / ln_b), written as mixed rows to `rows`
+  const float* w = nullptr;
+  const float* b = nullptr;
+  void* rows = nullptr;
+};
+
+// FeedForward panel (launch_ffn_fused): x <- x + fc2(gelu(fc1(a))) on M rows; next: LayerNorm rows of the result
+inline FfnArgs ffn_panel_args(const void* a, MixedLinear fc1, MixedLinear fc2, float* x, int M, RowNorm next = RowNorm()) {
+  FfnArgs f{};
+  f.a = (const char*)a; f.w1 = (const char*)fc1.w; f.w2 = (const char*)fc2.w; f.b1 = fc1.b; f.b2 = fc2.b;
+  f.resid = x; f.out = x; f.ldr = kDim; f.ldo = kDim; f.M = M; f.exp1 = fc1.exp; f.exp2 = fc2.exp;
+  f.ln_w = next.w; f.ln_b = next.b; f.ln_out = (char*)next.rows;
+  return f;
+}
+
+// Out-projection panel (launch_out_fused): x <- x + out(a) on M rows; ln2: LayerNorm rows of the result
+inline FfnArgs out_panel_args(const void* a, MixedLinear out, float* x, int M, RowNorm ln2 = RowNorm()) {
+  FfnArgs f{};
+  f.a = (const char*)a; f.w2 = (const char*)out.w; f.b2 = out.b; f.resid = x; f.out = x; f.ldr = kDim; f.ldo = kDim;
+  f.M = M; f.exp2 = out.exp; f.ln_w = ln2.w; f.ln_b = ln2.b; f.ln_out = (char*)ln2.rows;
+  return f;
+}
+
+// Full layer tail (launch_layer_tail): x1 = x + out(a), LayerNorm2 (ln2.w / ln2.b) of x1 written to ln2.rows, x <- x1 + fc2(gelu(fc1(.)));
+// next: LayerNorm of the result with next.w / next.b, to next.rows or (rows == nullptr) in place over ln2.rows
+inline FfnArgs layer_tail_args(const void* a, MixedLinear out, RowNorm ln2, MixedLinear fc1, MixedLinear fc2, float* x, int M,
+                               RowNorm next = RowNorm()) {
+  FfnArgs f = ffn_panel_args(a, fc1, fc2, x, M);
+  f.wo = (const char*)out.w; f.bo = out.b; f.expo = out.exp; f.lnm_w = ln2.w; f.lnm_b = ln2.b; f.ln_out = (char*)ln2.rows;
+  f.ln_w = next.w; f.ln_b = next.b; f.ln1_out = (char*)next.rows;
+  return f;
+}
+
+#pragma GCC visibility pop

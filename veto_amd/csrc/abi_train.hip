@@ -1,0 +1,683 @@
+// ================================================================================================================
+// Training path: forward that keeps every activation the backward needs, and the
+// backward itself.  One pass over all pairs (no chunking), precise mode, no dropout (the caller refuses p > 0).
+// Every layer runs on all 19 tokens (the CLS-only shortcut of the inference path would complicate the backward).
+// ================================================================================================================
+#include "abi_internal.h"
+
+namespace {
+
+struct TrainLayer {
+  float* xin;    // [mpad, 576]   input of the layer (residual stream)
+  __bf16* a1;    // split LN1(xin)
+  float* qkv;    // [mpad, 1728]
+  __bf16* ao;    // split attention output
+  float* xmid;   // [mpad, 576]   after the attention residual
+  __bf16* a2;    // split LN2(xmid)
+  float* pre;    // [mpad, 1152]  fc1 pre-activation
+  __bf16* hid;   // split gelu(pre)
+};
+
+struct TrainWs {
+  int32_t *subj, *obj;
+  float *lc, *patch_tab, *xout;
+  __bf16* pa;
+  std::vector<TrainLayer> layers;
+  // backward scratch
+  float *dx, *dmid, *dtmp, *dbig;
+  __bf16 *dsplit, *wdg, *zero;
+  __bf16* dsplit_b;   // the last two thirds of dsplit: rows of 2 * 1152 bf16 (the fc2 input-gradient epilogue writes fc1's gradient rows there
+                      // while its own operand, rows of 2 * 576 bf16, occupies the first third)
+  float *ln_partial, *col_partial, *colp, *dgb, *head_partial;
+  float *dpatch, *dlc, *dpos, *dpre, *xhat, *bn_out, *dbn_out, *emb, *demb, *prob, *dloc_wt, *dcls_wt, *dwcat_t;
+  __bf16* wcat_t;   // Wcat^T [2112, 2*1152] split rows: weight operand of the patch projection's input gradient
+  float* dpa;       // dPA [prow, 2112] fp32: gradient w.r.t. the patch rows
+  size_t mp2;    // padded reduction length of the weight-gradient GEMMs
+  size_t total;
+};
+
+// q / k / v of the training path as 3-byte floats (common.h) between the QKV projection, the attention and the attention backward: all
+// three split them into 16-bit hi + lo parts anyway, so the 16-bit significand in memory is what they would have kept -- 1.7 KB per token
+// row and layer less to keep and to move (round 6).  MFMA head widths only; VETO_TRAIN_QKV_F24=0: fp32.
+bool train_qkv_f24(veto_handle_t h) {
+  static const bool off = env_knob_is("VETO_TRAIN_QKV_F24", "0");
+  return !off && (h->dh == 72 || h->dh == 96);
+}
+
+// VETO_TRAIN_RECOMPUTE=1 (off by default): the LayerNorm1 / LayerNorm2 rows and the GELU rows of a layer are not kept for the backward but
+// recomputed there from the residual rows and the pre-activation that ARE kept (the same kernels on the same inputs: bit-identical operands,
+// bit-identical gradients): 8.6 GB less workspace at cfg-2 for three more passes per layer (~3 ms per step).  With 288 GB of HBM the default keeps them.
+bool train_recompute() {
+  static const bool on = env_knob_is("VETO_TRAIN_RECOMPUTE", "1");
+  return on;
+}
+
+// dpre = dh * gelu'(pre) in the epilogue of fc2's input-gradient GEMM (round 6); VETO_TRAIN_GELU_EPI=0: inside the operand preparation of
+// the fc1 backward, a pass of its own over an fp32 copy of dh (rounds 1-5)
+bool train_gelu_epilogue() {
+  static const bool off = env_knob_is("VETO_TRAIN_GELU_EPI", "0");
+  return !off;
+}
+
+// VETO_TRAIN_LN_SPLIT=1 (off by default; round 6, measured SLOWER): the LayerNorm backward kernels emit the split rows and bias partials of the
+// Linear behind them instead of a preparation pass per Linear reading the fp32 gradient rows back.  63.0 ms per step with, 61.6 without on one
+// box: the kernel is at its register limit (two statistics passes over 18 values per lane and tensor) and spills with the extra column
+// sums, split conversion and dropout hash, and its 4-byte split stores are slower than the pass they replace.  Kept as a tested variant.
+bool train_ln_emits_split() {
+  static const bool on = env_knob_is("VETO_TRAIN_LN_SPLIT", "1");
+  return on;
+}
+
+TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair) {
+  TrainWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* ptr = base ? base + off : nullptr;
+    off += align_up(bytes, 256);
+    return ptr;
+  };
+  const int L = h->cfg.layers, E = h->cfg.embed_dim;
+  const size_t M = (size_t)n_pair * kTokens;
+  const size_t mpad = (size_t)gemm_rows_padded((int)M);
+  const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
+  w.subj = (int32_t*)take((size_t)n_pair * 4);
+  w.obj = (int32_t*)take((size_t)n_pair * 4);
+  w.lc = (float*)take((size_t)n_obj * 2 * 2 * kDim * 4);
+  w.pa = (__bf16*)take(prow * 2 * 2048 * 2);
+  w.patch_tab = (float*)take((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.layers.resize(L);
+  const size_t cpad = (size_t)gemm_rows_padded(n_pair);
+  const bool recompute = train_recompute();
+  __bf16* a_scr = recompute ? (__bf16*)take(mpad * 2 * kDim * 2) : nullptr;      // LayerNorm rows of whichever Linear is next (forward) / being differentiated (backward)
+  __bf16* hid_scr = recompute ? (__bf16*)take(mpad * 4 * kDim * 2) : nullptr;    // the same for the GELU rows
+  for (int l = 0; l < L; ++l) {
+    TrainLayer& t = w.layers[l];
+    // (the last layer runs on the pairs' CLS rows behind its attention: those buffers are compact, one row per pair -- sized for every token
+    // row until round 6, 4.4 GB too many at cfg-2)
+    const size_t rows = l == L - 1 ? cpad : mpad;
+    t.xin = (float*)take(mpad * kDim * 4);
+    t.a1 = recompute ? a_scr : (__bf16*)take(mpad * 2 * kDim * 2);
+    t.qkv = (float*)take(mpad * 3 * kDim * (train_qkv_f24(h) ? 3 : 4));
+    t.ao = (__bf16*)take(rows * 2 * kDim * 2);
+    t.xmid = (float*)take(rows * kDim * 4);
+    t.a2 = recompute ? a_scr : (__bf16*)take(rows * 2 * kDim * 2);
+    t.pre = (float*)take(rows * 2 * kDim * 4);
+    t.hid = recompute ? hid_scr : (__bf16*)take(rows * 4 * kDim * 2);
+  }
+  w.xout = (float*)take(cpad * kDim * 4);      // (compact: the last layer's CLS rows)
+  w.dx = (float*)take(mpad * kDim * 4);
+  w.dmid = (float*)take(mpad * kDim * 4);
+  w.dtmp = (float*)take(mpad * kDim * 4);
+  // (fc2's input gradient as fp32 rows [M, 1152]: only the VETO_TRAIN_GELU_EPI=0 form writes it; sized [M, 1728] until round 6, 2 GB at cfg-2)
+  w.dbig = (float*)take(train_gelu_epilogue() ? 256 : mpad * 2 * kDim * 4);
+  {   // the token-row gradients (6 * 576 bf16 per row) and, for the input gradient of the patch projection, the split rows of
+      // dpatch (prow rows x 2 * 1152 bf16) share this buffer: size it for the larger (n_obj * 16 can exceed 19 * n_pair / 1.5)
+    const size_t tok = mpad * 6 * kDim * 2, obj = prow * 4 * kDim * 2;
+    w.dsplit = (__bf16*)take(tok > obj ? tok : obj);
+    w.dsplit_b = (__bf16*)((char*)w.dsplit + mpad * 2 * kDim * 2);
+  }
+  w.mp2 = (M + 32 * 64 + 31) / 32 * 32;   // room for any split count up to 64
+  w.zero = (__bf16*)take(1024);           // what the weight-gradient GEMM reads for reduction rows past the last one
+  w.wdg = (__bf16*)take((size_t)3 * kDim * kDim * 4);
+  w.ln_partial = (float*)take(layernorm_backward_partial_floats((int)M) * 4);
+  w.col_partial = (float*)take((size_t)column_sums_chunks() * 3 * kDim * 4);
+  w.colp = (float*)take((w.mp2 / 32) * 3 * kDim * 4);
+  w.dgb = (float*)take(2 * kDim * 4);
+  w.head_partial = (float*)take(head_backward_partial_floats(h->cfg.num_out) * 4);
+  w.dpatch = (float*)take((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.dlc = (float*)take((size_t)n_obj * 2 * 2 * kDim * 4);
+  w.dpos = (float*)take((size_t)n_obj * kPosDim * 4);
+  w.dpre = (float*)take((size_t)n_obj * kPosDim * 4);
+  w.xhat = (float*)take((size_t)n_obj * 4 * 4);
+  w.bn_out = (float*)take((size_t)n_obj * 4 * 4);
+  w.dbn_out = (float*)take((size_t)n_obj * 4 * 4);
+  w.emb = (float*)take((size_t)n_obj * E * 4);
+  w.demb = (float*)take((size_t)n_obj * E * 4);
+  w.prob = (float*)take((size_t)n_obj * 256 * 4);
+  w.dloc_wt = (float*)take((size_t)kPosDim * 2 * kDim * 4);
+  w.dcls_wt = (float*)take((size_t)E * 2 * kDim * 4);
+  w.dwcat_t = (float*)take((size_t)2048 * 2 * kDim * 4);
+  w.wcat_t = (__bf16*)take((size_t)kPatchTRows * 2 * 2 * kDim * 2);
+  w.dpa = (float*)take((size_t)gemm_rows_padded(n_obj * 16) * kPatchTRows * 4);
+  w.total = off;
+  return w;
+}
+
+// dw[N,K] = dy[M,N]^T . x[M,K]: the weight-gradient shape (reduction over the M rows).  Both operands are
+// transposed into split rows ([N, 2*Mp] and [K, 2*Mp]) and the persistent GEMM runs split-K with atomic adds.
+int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps = 64) {
+  if (k_splits > 0) return k_splits;
+  const int out_tiles = ((n + 255) / 256) * (k / 192);
+  int ks = 2 * 256 / out_tiles;                         // just under 2 full rounds of the 256 persistent workgroups
+  const int max_ks = (m + 32 * min_ksteps - 1) / (32 * min_ksteps);     // at least min_ksteps k-steps per tile
+  if (ks > max_ks) ks = max_ks;
+  return ks < 1 ? 1 : ks;
+}
+
+size_t wgrad_mp(int m, int ks) { return ((size_t)m + 32 * (size_t)ks - 1) / (32 * (size_t)ks) * 32 * (size_t)ks; }
+
+// Backward of y = x W^T (+ b) over the token rows: dW[N, K] = dY^T x, db[N] = column sums of dY (if db), dX[M, K] = dY W.
+// One pass over dY (prep_grad_kernel) produces its split rows -- the A operand of the input-gradient GEMM AND, read through
+// transposing LDS loads, of the weight-gradient GEMM (GemmArgs::tn; the saved activation x_split is its other operand as it
+// is) -- and the bias partials.  No transposed copies of dY or x exist.
+// dy == nullptr: the producer (attention backward) has already written the split rows into w.dsplit; no bias then.
+// presplit / presplit_partials: the producer wrote the split rows itself (to `presplit`; nullptr = w.dsplit) together with
+// `presplit_partials` rows of column sums in w.colp (0 = none: no bias gradient then).
+// gelu_pre (fc2 only): the input gradient is not written as fp32 rows: the GEMM's epilogue multiplies it by gelu'(gelu_pre) and writes the
+// split rows of fc1's backward to w.dsplit_b and their column-sum partials to w.colp (*next_partials rows): the pass that read dH and the
+// pre-activation back (0.9 ms per layer) is gone.
+int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const float* dy, int M, int N, const __bf16* x_split, int K,
+                        const float* weight, float* dw, float* db, float* dx, const GradXform& xf = GradXform(),
+                        const __bf16* presplit = nullptr, int presplit_partials = 0, const float* gelu_pre = nullptr, int* next_partials = nullptr) {
+  if (!dy && db && presplit_partials <= 0) return fail(VETO_ERR_INVALID, "a pre-split gradient without column partials cannot feed a bias gradient");
+  const __bf16* gsplit = !dy && presplit ? presplit : w.dsplit;
+  int ks = wgrad_splits(N, K, M, 0);
+  if (ks > 64) ks = 64;      // (w.mp2 has room for 64 splits)
+  const size_t mp = wgrad_mp(M, ks);
+  if (mp > w.mp2) return fail(VETO_ERR_WORKSPACE, "weight-gradient partial buffer too small");
+  if (dy) HIP_TRY(launch_prep_grad(dy, N, M, N, w.dsplit, (int)mp, db ? w.colp : nullptr, xf, s));
+  if (db) HIP_TRY(launch_column_sums(w.colp, N, dy ? (int)(mp / 32) : presplit_partials, N, db, w.col_partial, column_sums_chunks(), s));
+  HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
+  {
+    GemmArgs g{};
+    g.a = gsplit; g.w = x_split; g.c = dw;
+    g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
+    g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = M; g.zero = w.zero;
+    ProfScope ps(h, s, "bwd_wgrad", 2.0 * M * (double)N * K, 0);
+    HIP_TRY(launch_gemm_split(g, EPI_ATOMIC, 0, s));
+  }
+  HIP_TRY(launch_transpose_split(weight, K, N, K, w.wdg, N, s));     // W [N, K] -> W^T split rows [K, 2N]
+  {
+    GemmArgs g{};
+    g.a = gsplit; g.w = w.wdg; g.c = dx;
+    g.M = M; g.N = K; g.K = N; g.ldc = K;
+    ProfScope ps(h, s, "bwd_dgrad", 2.0 * M * (double)N * K, 0);
+    if (gelu_pre) {
+      if (gsplit == w.dsplit_b || !next_partials) return fail(VETO_ERR_INVALID, "internal: the fused gelu' epilogue writes w.dsplit_b");
+      g.c = nullptr; g.c_split = w.dsplit_b; g.ldc = 2L * K; g.resid = gelu_pre; g.ldr = K; g.col_partial = w.colp;
+      *next_partials = (M + 255) / 256 * 4;      // one partial row per 64-row slice of every 256-row tile
+      HIP_TRY(launch_gemm_split(g, EPI_GELU_BWD, 0, s));
+    } else {
+      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
+    }
+  }
+  return VETO_OK;
+}
+
+// dropout sites of the training path: 1 = pos_embed Dropout(0.1), 2 = pos_drop on the tokens, 3 + l = to_out of layer l
+DropSite drop_site(const veto_train_opts_t* o, int site) {
+  DropSite d;
+  if (!o) return d;
+  const float p = site == 1 ? o->p_pos : site == 2 ? o->p_emb : o->p_attn;
+  if (!(p > 0.f)) return d;
+  d.seed = o->seed + (unsigned long long)site * 0x632BE59BD9B4E019ull;
+  d.thresh = (unsigned)(p * 16777216.0f);
+  d.scale = 1.f / (1.f - p);
+  return d;
+}
+
+int check_train_opts(const veto_train_opts_t* o) {
+  if (!o) return VETO_OK;
+  if (o->struct_size != (int32_t)sizeof(veto_train_opts_t)) return fail(VETO_ERR_INVALID, "veto_train_opts_t size mismatch");
+  for (float p : {o->p_pos, o->p_emb, o->p_attn})
+    if (!(p >= 0.f && p < 1.f)) return fail(VETO_ERR_INVALID, "dropout probabilities must be in [0, 1)");
+  return VETO_OK;
+}
+
+int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, void* workspace, size_t workspace_bytes) {
+  if (!h || !in || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (in->struct_size != (int32_t)sizeof(veto_inputs_t)) return fail(VETO_ERR_INVALID, "veto_inputs_t size mismatch");
+  if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch");
+  if (!in->roi_rgb || !in->roi_depth || !in->boxes || !in->rel_pairs || !in->img_obj_offset || !in->img_pair_offset)
+    return fail(VETO_ERR_INVALID, "missing input pointer");
+  if (!in->obj_labels && !in->obj_logits) return fail(VETO_ERR_INVALID, "neither obj_labels nor obj_logits given");
+  if (!in->bn_batch_stats) return fail(VETO_ERR_INVALID, "the training path needs bn_batch_stats (training-mode BatchNorm)");
+  if (h->cfg.precision == VETO_FAST) return fail(VETO_ERR_INVALID, "the training path runs on split-bf16 operands (precise / mixed handles) only");
+  if (workspace_bytes < veto_train_workspace_bytes(h, in->n_obj, in->n_pair)) return fail(VETO_ERR_WORKSPACE, "training workspace too small");
+  return VETO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t veto_train_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair) {
+  if (!h || n_obj <= 0 || n_pair <= 0) return 0;
+  return carve_train(nullptr, h, n_obj, n_pair).total;
+}
+
+int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
+                       size_t workspace_bytes, float* out_logits) {
+  int rc = check_train_inputs(h, in, workspace, workspace_bytes);
+  if (rc) return rc;
+  if ((rc = check_train_opts(opts))) return rc;
+  if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (h->dirty) { rc = finalize_weights(h, s, true); if (rc) return rc; }
+  h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
+  const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out;
+  const int M = n_pair * kTokens;
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair);
+  HIP_TRY(launch_pair_indices(in->rel_pairs, in->img_obj_offset, in->img_pair_offset, in->n_img, n_pair, ws.subj, ws.obj, nullptr,
+                              nullptr, s));
+  {
+    HIP_TRY(launch_bn_batch_stats(in->boxes, in->box_mode, n_obj, in->bn_batch_stats, s));
+    ObjPrepArgs a = obj_prep_args(h, in, ws.lc);
+    const DropSite d = drop_site(opts, 1);
+    a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale;
+    HIP_TRY(launch_obj_prep(a, s));
+  }
+  HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
+  rc = run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16,
+                2 * kDim, 2048, EPI_F32);
+  if (rc) return rc;
+  {
+    AssembleArgs a = assemble_args(h, ws.patch_tab, ws.lc, ws.subj, ws.obj, ws.layers[0].xin, ws.layers[0].a1, n_pair);
+    const DropSite d = drop_site(opts, 2);
+    a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale;
+    HIP_TRY(launch_assemble(a, s));
+  }
+  const bool q24 = train_qkv_f24(h);
+  const int qepi = q24 ? EPI_F24 : EPI_F32;
+  for (int l = 0; l < L; ++l) {
+    const LayerW& w = h->layers[l];
+    TrainLayer& t = ws.layers[l];
+    if (l == L - 1) {
+      // Last layer: only x[:, 0] reaches the loss (model_veto.py:23), so -- as at inference -- keys / values cover the 19
+      // tokens, everything behind the attention runs on the CLS row of each pair.  The saved activations of this layer
+      // (ao, xmid, a2, pre, hid, ws.xout) are COMPACT: row p = pair p.  The backward mirrors this.
+      rc = run_gemm(h, s, "gemm_kv_last", t.a1, w.qkv, nullptr, nullptr, 0, q24 ? (float*)((char*)t.qkv + 3 * kDim) : t.qkv + kDim, nullptr,
+                    3 * kDim, M, 2 * kDim, kDim, qepi, 0, kDim);
+      if (rc) return rc;
+      rc = run_gemm(h, s, "gemm_q_cls", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, (long)kTokens * 3 * kDim, n_pair, kDim, kDim,
+                    qepi, (long)kTokens * 2 * kDim, 0);
+      if (rc) return rc;
+      {
+        AttnArgs a{};
+        a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 1; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
+        HIP_TRY(launch_attention(a, s));
+      }
+      rc = run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
+                    EPI_RESID, 0, 0, drop_site(opts, 3 + l));
+      if (rc) return rc;
+      HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
+      rc = run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU);
+      if (rc) return rc;
+      rc = run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID);
+      if (rc) return rc;
+      break;
+    }
+    float* xnext = ws.layers[l + 1].xin;
+    rc = run_gemm(h, s, "gemm_qkv", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, 3 * kDim, M, 3 * kDim, kDim, qepi);
+    if (rc) return rc;
+    {
+      AttnArgs a{};
+      a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 0; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
+      HIP_TRY(launch_attention(a, s));
+    }
+    rc = run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0,
+                  drop_site(opts, 3 + l));
+    if (rc) return rc;
+    HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, M, s));
+    // (the epilogue writes the fp32 pre-activation -- gelu' needs it -- AND its exact-erf GELU as fc2's split rows: round 6; before, a pass
+    // of its own read the pre-activation back, 0.55 ms per layer)
+    rc = run_gemm(h, s, "gemm_fc1", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, M, 2 * kDim, kDim, EPI_PRE_GELU);
+    if (rc) return rc;
+    rc = run_gemm(h, s, "gemm_fc2", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, xnext, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID);
+    if (rc) return rc;
+    HIP_TRY(launch_layernorm(xnext, kDim, h->layers[l + 1].ln1_w, h->layers[l + 1].ln1_b, ws.layers[l + 1].a1, M, s));
+  }
+  HIP_TRY(launch_head(ws.xout, h->head_wt, h->p("rel_out.bias"), out_logits, n_pair, n_out, s, (long)kDim));
+  h->stamp_train_workspace(workspace);
+  return VETO_OK;
+}
+
+int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
+                  size_t workspace_bytes, const float* dlogits, float* grads) {
+  int rc = check_train_inputs(h, in, workspace, workspace_bytes);
+  if (rc) return rc;
+  if ((rc = check_train_opts(opts))) return rc;
+  if (!dlogits || !grads) return fail(VETO_ERR_INVALID, "null gradient pointer");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  // the backward reads the derived operands the matching forward used: a weight upload in between would pair this
+  // workspace's activations with different weights
+  if (h->dirty) return fail(VETO_ERR_WEIGHTS, "weights were reloaded between veto_forward_train and veto_backward");
+  {
+    auto it = h->train_gen.find(workspace);
+    if (it == h->train_gen.end()) return fail(VETO_ERR_INVALID, "veto_backward: this workspace holds no veto_forward_train activations");
+    if (it->second != h->weight_gen)
+      return fail(VETO_ERR_WEIGHTS, "veto_backward: the weights were refreshed (by a later forward) since this workspace's veto_forward_train");
+  }
+  const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out, E = h->cfg.embed_dim;
+  const int M = n_pair * kTokens;
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair);
+  const std::string T = kT;
+  auto G = [&](const std::string& name) { return grads + h->params[h->index.at(name)].offset; };
+  struct LinGrad { const float* w; float *dw, *db; int N, K; };      // a layer's Linear (kLayerLinears): weight, its and the bias's gradient
+  auto lin = [&](int l, int i) {
+    const LayerLinear& q = kLayerLinears[i];
+    return LinGrad{h->p(lname(l, q.weight)), G(lname(l, q.weight)), q.bias ? G(lname(l, q.bias)) : nullptr, q.N, q.K};
+  };
+  HIP_TRY(hipMemsetAsync(grads, 0, veto_grad_floats(h) * 4, s));
+  HIP_TRY(hipMemsetAsync(ws.zero, 0, 1024, s));
+
+  // ---- classifier head: gradient of the compact CLS rows ------------------------------------------------------------
+  HIP_TRY(launch_head_backward(dlogits, h->p("rel_out.weight"), ws.xout, ws.dx, G("rel_out.weight"), G("rel_out.bias"), ws.head_partial,
+                               n_pair, n_out, (long)kDim, s));
+
+  // ---- transformer layers, last to first -------------------------------------------------------------------------
+  int dx_presplit = 0;      // > 0: ws.dsplit / ws.colp already hold the split rows / that many rows of column partials of ws.dx
+  for (int l = L - 1; l >= 0; --l) {
+    const LayerW& w = h->layers[l];
+    TrainLayer& t = ws.layers[l];
+    const bool last = l == L - 1;
+    const int R = last ? n_pair : M;     // rows behind the attention: the CLS rows only in the last layer (compact buffers)
+    // x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2
+    // dpre = dh * gelu'(pre): in the epilogue of fc2's input-gradient GEMM (round 6; VETO_TRAIN_GELU_EPI=0: a pass of its own inside the
+    // operand preparation of the fc1 backward, rounds 1-5)
+    // (the gradient of this layer's output: compact CLS rows from the head in the last layer, else the rows the LayerNorm1 backward of the
+    // layer above left -- with their split rows and bias partials when it emitted them)
+    const float* dy2 = dx_presplit ? nullptr : ws.dx;
+    const bool recompute = train_recompute();
+    const LinGrad qkv = lin(l, LIN_QKV), out = lin(l, LIN_OUT), fc1 = lin(l, LIN_FC1), fc2 = lin(l, LIN_FC2);
+    if (recompute) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
+    if (train_gelu_epilogue()) {
+      int partials = 0;
+      rc = run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit, t.pre, &partials);
+      if (rc) return rc;
+      if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));      // LayerNorm2 rows: fc1's operand
+      rc = run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, GradXform(), ws.dsplit_b, partials);
+      if (rc) return rc;
+    } else {
+      rc = run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, ws.dbig, GradXform(), nullptr, dx_presplit);
+      if (rc) return rc;
+      GradXform gelu;              // dpre = dh * gelu'(pre), folded into the operand preparation of the fc1 backward
+      gelu.mode = XF_GELU;
+      gelu.pre = t.pre;
+      if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));
+      rc = run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, gelu);
+      if (rc) return rc;
+    }
+    // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
+    const DropSite dsite = drop_site(opts, 3 + l);
+    const bool ln_split = train_ln_emits_split();
+    if (ln_split)
+      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, ws.dsplit, ws.colp,
+                                        dsite.seed, dsite.thresh, dsite.scale));
+    else
+      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s));
+    HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.bias")), ws.dgb + kDim, kDim * 4, hipMemcpyDeviceToDevice, s));
+    GradXform drop;
+    if (dsite.thresh) {
+      drop.mode = XF_DROP;
+      drop.seed = dsite.seed;
+      drop.thresh = dsite.thresh;
+      drop.scale = dsite.scale;
+    }
+    rc = run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, ws.dtmp, drop, nullptr,
+                             ln_split ? layernorm_backward_col_partials(R) : 0);
+    if (rc) return rc;
+    HIP_TRY(launch_attention_backward(t.qkv, ws.dtmp, nullptr, ws.dsplit, n_pair, H, last ? 1 : 0, s, train_qkv_f24(h)));
+    const float* dres = ws.dmid;
+    if (last) {
+      // the residual gradient d x_mid lives on the CLS rows only: spread the compact rows over a zeroed token matrix
+      HIP_TRY(hipMemsetAsync(ws.dx, 0, (size_t)M * kDim * 4, s));
+      HIP_TRY(hipMemcpy2DAsync(ws.dx, (size_t)kTokens * kDim * 4, ws.dmid, (size_t)kDim * 4, (size_t)kDim * 4, (size_t)n_pair,
+                               hipMemcpyDeviceToDevice, s));
+      dres = ws.dx;
+    }
+    if (recompute) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
+    rc = run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, ws.dtmp);
+    if (rc) return rc;
+    // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
+    if (ln_split && l > 0) {      // (its result is the gradient matrix of fc2 of the layer below)
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, ws.dsplit, ws.colp));
+      dx_presplit = layernorm_backward_col_partials(M);
+    } else {
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s));
+      dx_presplit = 0;
+    }
+    HIP_TRY(hipMemcpyAsync(G(lname(l, "0.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(G(lname(l, "0.norm.bias")), ws.dgb + kDim, kDim * 4, hipMemcpyDeviceToDevice, s));
+  }
+
+  // ---- token assembly: cls_token, pos_embedding, per-object tables -----------------------------------------------
+  // x0[p, t] = token + pos_embedding (ONE 576-vector broadcast over all tokens, model_veto.py:43,62): its gradient is
+  // the sum over every token row; the cls_token's is the sum over row 0 of every pair
+  {
+    const DropSite d = drop_site(opts, 2);   // pos_drop sits between (token + pos_embedding) and the first layer
+    if (d.thresh) HIP_TRY(launch_dropout_apply(ws.dx, ws.dx, (size_t)M, kDim, d.seed, d.thresh, d.scale, s));
+  }
+  HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, G(T + "pos_embedding"), ws.col_partial, column_sums_chunks(), s));
+  HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, G(T + "cls_token"), ws.col_partial, column_sums_chunks(), s));
+  HIP_TRY(hipMemsetAsync(ws.dpatch, 0, (size_t)n_obj * 16 * 2 * kDim * 4, s));
+  HIP_TRY(hipMemsetAsync(ws.dlc, 0, (size_t)n_obj * 2 * 2 * kDim * 4, s));
+  HIP_TRY(launch_assemble_backward(ws.dx, ws.subj, ws.obj, ws.lc, ws.dpatch, ws.dlc, n_pair, s));
+
+  // ---- patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half) ------------------------
+  {
+    const std::string pe = T + "patch_embed.";
+    const int R = n_obj * 16;
+    // dWcat^T [2048, 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch (fp32) in run_wgrad's roles swapped,
+    // so that the output width (1152) is a multiple of 192
+    {
+      const int N = 2048, K = 2 * kDim;
+      const int ks = wgrad_splits(N, K, R, 0, 8);      // (few object rows: tiles of 8 k-steps already)
+      const size_t mp = wgrad_mp(R, ks);
+      HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, K, s));
+      HIP_TRY(hipMemsetAsync(ws.dwcat_t, 0, (size_t)N * K * 4, s));
+      GemmArgs g{};
+      g.a = ws.pa; g.w = ws.dsplit; g.c = ws.dwcat_t;
+      g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
+      g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = R; g.zero = ws.zero;
+      HIP_TRY(launch_gemm_split(g, EPI_ATOMIC, 0, s));
+    }
+    HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
+    // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
+    HIP_TRY(launch_column_sums(ws.dpatch, 2 * kDim, R, kDim, ws.dgb, ws.col_partial, column_sums_chunks(), s));
+    HIP_TRY(hipMemcpyAsync(G(pe + "proj_d.bias"), ws.dgb, 512 * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(G(pe + "proj_v.bias"), ws.dgb + 512, 64 * 4, hipMemcpyDeviceToDevice, s));
+    // input gradient (optional): dPA = dpatch . Wcat, i.e. the forward GEMM kernel on split(dpatch) (still in ws.dsplit) and
+    // Wcat^T as the weight operand; then the inverse of patchify onto the ROI maps.  The reference's depth backbone is
+    // trained through roi_depth_features (tools/relation_train_net.py:166-170).
+    if (opts && (opts->d_roi_rgb || opts->d_roi_depth)) {
+      HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, s));
+      GemmArgs g{};
+      g.a = ws.dsplit; g.w = ws.wcat_t; g.c = ws.dpa;
+      g.M = R; g.N = kPatchTRows; g.K = 2 * kDim; g.ldc = kPatchTRows;
+      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
+      HIP_TRY(launch_unpatchify(ws.dpa, kPatchTRows, opts->d_roi_depth, opts->d_roi_rgb, n_obj, s));
+    }
+  }
+
+  // ---- location / class projections and what feeds them -----------------------------------------------------------
+  {
+    const long ldlc = 2 * 2 * kDim;   // dlc row n = [location 1152 | class 1152]
+    // biases sit on the subject half
+    HIP_TRY(launch_column_sums(ws.dlc, ldlc, n_obj, kDim, G("location_projection.0.bias"), ws.col_partial, column_sums_chunks(), s));
+    HIP_TRY(launch_column_sums(ws.dlc + 2 * kDim, ldlc, n_obj, kDim, G("class_projection.0.bias"), ws.col_partial, column_sums_chunks(), s));
+    // position branch: recompute pos (post-ReLU) through the masked gradient path
+    //   dpos = dlc_loc . loc_wt^T ; obj_pos_backward -> dpre (ReLU'), BatchNorm affine gradients
+    HIP_TRY(launch_sgemm_nt(ws.dlc, ldlc, h->loc_wt, 2 * kDim, ws.dpos, kPosDim, n_obj, kPosDim, 2 * kDim, s));
+    const DropSite dpos_site = drop_site(opts, 1);   // Dropout(0.1) behind the ReLU of pos_embed
+    if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
+    HIP_TRY(launch_obj_pos_backward(in->boxes, in->box_mode, in->bn_batch_stats, h->p("pos_embed.0.weight"), h->p("pos_embed.0.bias"),
+                                    h->p("pos_embed.1.weight"), h->p("pos_embed.1.bias"), ws.dpos, ws.dpre, ws.xhat, ws.bn_out, ws.dbn_out,
+                                    G("pos_embed.0.weight"), G("pos_embed.0.bias"), n_obj, s));
+    // pos_embed.1: Linear(4, 128): dW[k, c] = sum_n dpre[n, k] bn_out[n, c]; db = column sums of dpre
+    HIP_TRY(launch_sgemm_tn(ws.dpre, kPosDim, ws.bn_out, 4, G("pos_embed.1.weight"), 4, n_obj, kPosDim, 4, s));
+    HIP_TRY(launch_column_sums(ws.dpre, kPosDim, n_obj, kPosDim, G("pos_embed.1.bias"), ws.col_partial, column_sums_chunks(), s));
+    // location_projection weight: d loc_wt[k, j] = sum_n pos[n, k] dlc_loc[n, j], pos = relu(pre): recompute pos = the
+    // forward's value; it equals (dpre != 0 ? ... ) no -- recompute it from bn_out
+    // pos[n, k] = relu(pos_b[k] + sum_c pos_w[k, c] bn_out[n, c]): one small product + ReLU, done by reusing dpos as storage
+    HIP_TRY(launch_sgemm_nt(ws.bn_out, 4, h->p("pos_embed.1.weight"), 4, ws.dpos, kPosDim, n_obj, kPosDim, 4, s));
+    HIP_TRY(launch_bias_relu(ws.dpos, h->p("pos_embed.1.bias"), n_obj, kPosDim, s));
+    if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
+    HIP_TRY(launch_sgemm_tn(ws.dpos, kPosDim, ws.dlc, ldlc, ws.dloc_wt, 2 * kDim, n_obj, kPosDim, 2 * kDim, s));
+    HIP_TRY(launch_untranspose_pair_proj(ws.dloc_wt, G("location_projection.0.weight"), kPosDim, s));
+    // class branch: emb = E[label] (hard labels) or softmax(logits) . E (sgcls, :4092-4095);
+    // d cls_wt[k, j] = sum_n emb[n, k] dlc_cls[n, j]; demb = dlc_cls . cls_wt^T
+    const int C_obj = h->cfg.num_obj_cls;
+    if (in->obj_logits) {
+      HIP_TRY(launch_softmax_rows(in->obj_logits, ws.prob, n_obj, C_obj, s));
+      HIP_TRY(launch_sgemm_nn(ws.prob, C_obj, h->p("obj_embed.weight"), E, ws.emb, E, n_obj, E, C_obj, s));
+    } else {
+      HIP_TRY(launch_gather_rows(h->p("obj_embed.weight"), in->obj_labels, E, ws.emb, n_obj, s));
+    }
+    HIP_TRY(launch_sgemm_tn(ws.emb, E, ws.dlc + 2 * kDim, ldlc, ws.dcls_wt, 2 * kDim, n_obj, E, 2 * kDim, s));
+    HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
+    HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, ldlc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
+    if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, G("obj_embed.weight"), E, n_obj, C_obj, E, s));
+    else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, G("obj_embed.weight"), n_obj, s));
+  }
+  return VETO_OK;
+}
+
+size_t veto_ce_loss_workspace_bytes(int32_t n) { return n > 0 ? 3 * align_up((size_t)n * 4, 256) + 256 : 0; }
+
+int veto_ce_loss(void* stream, const float* logits, int64_t ld, const int64_t* labels, const float* weight,
+                 const int64_t* rows, int32_t n, int32_t n_cls, float* loss, float* grad, void* workspace,
+                 size_t workspace_bytes) {
+  if (!logits || !labels || !loss || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (n <= 0 || n_cls < 2 || ld < n_cls) return fail(VETO_ERR_INVALID, "bad sizes (n %d, n_cls %d, ld %lld)", n, n_cls, (long long)ld);
+  if (workspace_bytes < veto_ce_loss_workspace_bytes(n)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  CeLossArgs a{};
+  a.logits = logits; a.ld = ld; a.labels = labels; a.weight = weight; a.rows = rows; a.n = n; a.C = n_cls;
+  char* base = (char*)workspace;
+  const size_t per = align_up((size_t)n * 4, 256);
+  a.lse = (float*)base; a.nll_w = (float*)(base + per); a.w_row = (float*)(base + 2 * per); a.inv_wsum = (float*)(base + 3 * per);
+  a.loss = loss; a.grad = grad;
+  HIP_TRY(launch_ce_loss(a, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint32_t* words, int32_t n_words,
+                     const int32_t* incre_idx_list, const int32_t* pos_in_group, const int32_t* group_size,
+                     const double* sample_rates, int32_t n_groups, int32_t n_cls, int64_t* chosen,
+                     int64_t* group_labels, int32_t* counts, int32_t* words_used) {
+  if (!labels || !words || !incre_idx_list || !pos_in_group || !group_size || !sample_rates || !chosen || !group_labels ||
+      !counts || !words_used)
+    return fail(VETO_ERR_INVALID, "null argument");
+  if (n <= 0 || n_words <= 0 || n_groups < 1 || n_groups > 64 || n_cls < 2) return fail(VETO_ERR_INVALID, "bad sizes");
+  MeetSampleArgs a{};
+  a.labels = labels; a.n = n; a.n_groups = n_groups; a.n_cls = n_cls; a.n_words = n_words; a.words = words;
+  a.incre = incre_idx_list; a.pos_in_group = pos_in_group; a.group_size = group_size; a.rates = sample_rates;
+  a.chosen = chosen; a.group_labels = group_labels; a.counts = counts; a.words_used = words_used;
+  HIP_TRY(launch_meet_sample(a, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// n % 32 == 0 (every Linear of the transformer): the row-major form, both operands as the split rows the backward holds
+// anyway, transposed on their way out of LDS (GemmArgs::tn).  Otherwise: explicit transposed split copies.
+static size_t wgrad_tn_bytes(int m, int n, int k) {
+  return align_up(((size_t)m + 1) * n * 4, 256) + align_up(((size_t)m + 1) * k * 4, 256) + 1024;
+}
+
+size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  if (n % 32 == 0) return wgrad_tn_bytes(m, n, k);
+  const size_t mp = wgrad_mp(m, wgrad_splits(n, k, m, k_splits));
+  return align_up((size_t)gemm_rows_padded(n) * mp * 4, 256) + align_up((size_t)k * mp * 4, 256);
+}
+
+int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
+                     int32_t k_splits, void* workspace, size_t workspace_bytes) {
+  if (!dy || !x || !dw || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (m <= 0 || n <= 0 || k <= 0 || k % 192 != 0) return fail(VETO_ERR_INVALID, "k must be a positive multiple of 192");
+  if (workspace_bytes < veto_debug_wgrad_workspace_bytes(m, n, k, k_splits)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int ks = wgrad_splits(n, k, m, k_splits);
+  const size_t mp = wgrad_mp(m, ks);
+  char* base = (char*)workspace;
+  HIP_TRY(hipMemsetAsync(dw, 0, (size_t)n * k * 4, s));
+  GemmArgs g{};
+  g.c = dw;
+  g.M = n; g.N = k; g.K = (int)mp; g.ldc = k; g.k_splits = ks;
+  if (n % 32 == 0) {
+    const size_t a_bytes = align_up(((size_t)m + 1) * n * 4, 256), w_bytes = align_up(((size_t)m + 1) * k * 4, 256);
+    __bf16* a_s = (__bf16*)base;
+    __bf16* w_s = (__bf16*)(base + a_bytes);
+    HIP_TRY(hipMemsetAsync(base, 0, a_bytes + w_bytes + 1024, s));   // the row behind the last one is read (never used) by partial tiles
+    HIP_TRY(launch_split_rows(dy, a_s, (size_t)m, n, s));
+    HIP_TRY(launch_split_rows(x, w_s, (size_t)m, k, s));
+    g.a = a_s; g.w = w_s;
+    g.tn = 1; g.lda = 2 * (long)n; g.ldw = 2 * (long)k; g.k_valid = m;
+    g.zero = (const __bf16*)(base + a_bytes + w_bytes);
+  } else {
+    const size_t a_bytes = align_up((size_t)gemm_rows_padded(n) * mp * 4, 256);
+    __bf16* a_s = (__bf16*)base;
+    __bf16* w_s = (__bf16*)(base + a_bytes);
+    HIP_TRY(hipMemsetAsync(base, 0, a_bytes, s));   // rows n..padded stay zero
+    HIP_TRY(launch_transpose_split(dy, n, m, n, a_s, (int)mp, s));
+    HIP_TRY(launch_transpose_split(x, k, m, k, w_s, (int)mp, s));
+    g.a = a_s; g.w = w_s;
+  }
+  hipError_t e = launch_gemm_split(g, EPI_ATOMIC, 0, s);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "wgrad gemm launch failed: %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+int veto_debug_attention_backward(void* stream, const float* qkv, const float* dout, float* dqkv, int32_t n_pair, int32_t heads) {
+  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  hipError_t e = launch_attention_backward(qkv, dout, dqkv, nullptr, n_pair, heads, 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (heads must give a head width of 72, 96 or 144)", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+int veto_debug_attention_backward_forms(void* stream, const void* qkv, const float* dout, void* dqkv, float* qkv_unpacked, int32_t n_pair,
+                                        int32_t heads, uint32_t flags) {
+  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (flags & ~(uint32_t)(VETO_ATTN_BWD_CLS_ONLY | VETO_ATTN_BWD_QKV_F24 | VETO_ATTN_BWD_SPLIT_OUT)) return fail(VETO_ERR_INVALID, "unknown flag");
+  const bool f24 = (flags & VETO_ATTN_BWD_QKV_F24) != 0, split = (flags & VETO_ATTN_BWD_SPLIT_OUT) != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (qkv_unpacked) {
+    if (!f24) return fail(VETO_ERR_INVALID, "qkv_unpacked goes with VETO_ATTN_BWD_QKV_F24");
+    HIP_TRY(launch_unpack_f24(qkv, qkv_unpacked, (size_t)n_pair * kTokens * 3 * kDim, s));
+  }
+  hipError_t e = launch_attention_backward((const float*)qkv, dout, split ? nullptr : (float*)dqkv, split ? (__bf16*)dqkv : nullptr, n_pair, heads,
+                                           (flags & VETO_ATTN_BWD_CLS_ONLY) ? 1 : 0, s, f24);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (head width 72, 96 or 144; 3-byte q / k / v with 72 or 96 only)", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+size_t veto_debug_layernorm_backward_workspace_bytes(int32_t rows) { return rows > 0 ? layernorm_backward_partial_floats(rows) * 4 : 0; }
+
+int veto_debug_layernorm_backward(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
+                                  float* dx, float* dgamma_dbeta, int32_t rows, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int32_t veto_debug_layernorm_backward_col_partial_rows(int32_t rows) { return rows > 0 ? layernorm_backward_col_partials(rows) : 0; }
+
+int veto_debug_layernorm_backward_split(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
+                                        float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
+                                        uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !split_rows || !col_partials || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
+                                    col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale));
+  return VETO_OK;
+}
+
+int veto_debug_gelu_backward(void* stream, const float* pre, const float* dh, float* dpre, size_t n) {
+  if (!pre || !dh || !dpre || n == 0 || n % 4 != 0) return fail(VETO_ERR_INVALID, "bad argument (n must be a positive multiple of 4)");
+  HIP_TRY(launch_gelu_backward(pre, dh, dpre, n, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_debug_column_sums(void* stream, const float* dy, int64_t ld, int32_t rows, int32_t n_cols, float* out, void* workspace,
+                           size_t workspace_bytes) {
+  if (!dy || !out || !workspace || rows <= 0 || n_cols <= 0 || ld < n_cols) return fail(VETO_ERR_INVALID, "bad argument");
+  if (workspace_bytes < (size_t)column_sums_chunks() * n_cols * 4) return fail(VETO_ERR_WORKSPACE, "workspace too small (256 * n_cols floats)");
+  HIP_TRY(launch_column_sums(dy, ld, rows, n_cols, out, (float*)workspace, column_sums_chunks(), (hipStream_t)stream));
+  return VETO_OK;
+}
+
+}  // extern "C"

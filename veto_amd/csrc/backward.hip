@@ -1,5 +1,5 @@
 // Backward building blocks of the relation transformer; chained by veto_backward
-// (veto_abi.hip) and exposed one by one through test hooks that are checked against autograd.
+// (abi_train.hip) and exposed one by one through test hooks that are checked against autograd.
 //   attention_backward   model_veto.py:85-96   (dQ, dK, dV) from dOut and the saved q, k, v of one (pair, head)
 //   layernorm_backward   model_veto.py:125-132 dx, and per-block partial sums of dgamma / dbeta
 //   gelu_backward        model_veto.py:140     dpre = dh * gelu'(pre), exact-erf GELU

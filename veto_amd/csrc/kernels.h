@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI host code (veto_abi.hip) and the kernels.
+// Internal launch interface between the C-ABI host code (abi_*.hip) and the kernels.
 #pragma once
 #include "common.h"
 
@@ -39,7 +39,7 @@ struct GemmArgs {
   // on the device, and an EPI_GELU_SPLIT output is written as mixed rows too.  Inference forms only (no tn / split-K).
   int fmt;
   // Block-diagonal weights (kb_tiles > 0; split rows, no split-K, not tn): column tile n multiplies only the k-steps
-  // [(n / kb_tiles) * kb_steps, + kb_steps) of the rows -- the products of the folded last layer (veto_abi.hip) are block-diagonal
+  // [(n / kb_tiles) * kb_steps, + kb_steps) of the rows -- the products of the folded last layer (abi_core.hip) are block-diagonal
   // over the heads, and the zero blocks are skipped instead of multiplied.
   int kb_tiles, kb_steps;
   const int* w_exp;
@@ -49,7 +49,7 @@ struct GemmArgs {
   const __bf16* zero;
 };
 
-// Environment knobs (veto_abi.hip): every one selects a path that a parity test compares against the default (INTEGRATION.md
+// Environment knobs (abi_core.hip): every one selects a path that a parity test compares against the default (INTEGRATION.md
 // lists them); call sites cache the answer in a function-local static.
 bool env_knob_is(const char* name, const char* value);   // the variable is set to exactly `value`
 int env_knob_int(const char* name, int dflt);

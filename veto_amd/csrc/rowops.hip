@@ -691,7 +691,7 @@ hipError_t launch_split_rows(const float* src, __bf16* dst, size_t rows, int K, 
   return hipGetLastError();
 }
 
-// Weights of the folded last layer in their block form (veto_abi.hip): `which` = 0 Wq with every head's dh rows padded to dhp
+// Weights of the folded last layer in their block form (abi_core.hip): `which` = 0 Wq with every head's dh rows padded to dhp
 // [H dhp, 576]; 1 the per-head transposes of Wk, block-diagonal [H 576, H dhp] (row (h, c), column (h, d) = Wk[h dh + d][c]);
 // 2 Wv, block-diagonal [H dhp, H 576] (row (h, d), column (h, c) = Wv[h dh + d][c]); 3 Wo with every head's dh columns padded
 // [576, H dhp].  qkv = the layer's to_qkv weight [1728, 576] (q rows, k rows, v rows), wo = to_out weight [576, 576].  fp32 out.
