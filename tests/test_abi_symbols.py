@@ -81,3 +81,62 @@ def test_public_header_is_plain_c(tmp_path):
     src.write_text('#include "veto_amd.h"\nint main(void) { veto_config_t c; c.struct_size = (int32_t)sizeof(c); return c.struct_size == 0; }\n')
     inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
     subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-fsyntax-only", "-I", inc, str(src)], check=True)
+
+
+def test_struct_mirrors_and_constants_match_the_header(tmp_path):
+    """Every ctypes mirror against include/veto_amd.h as the host C compiler lays it out: struct size, and offset and size of
+    every field (a field the header lacks does not compile; two swapped fields of one width change an offset).  Plus the
+    constants the binding repeats."""
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc")
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert set(re.findall(r"\}\s*(veto_\w+_t)\s*;", text)) == set(native.STRUCTS)
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "veto_amd.h"', 'int main(void) {']
+    for cname, mirror in native.STRUCTS.items():
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        for field, _ in mirror._fields_:
+            lines.append('  printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (cname, field, cname, field, cname, field))
+    consts = {"VETO_PRECISE": native.VETO_PRECISE, "VETO_FAST": native.VETO_FAST, "VETO_MIXED": native.VETO_MIXED,
+              "VETO_SAT_SITES": len(native.SATURATION_SITES), "VETO_RPN_MAX_LEVELS": native.RPN_MAX_LEVELS,
+              "VETO_ATTN_BWD_CLS_ONLY": native.VETO_ATTN_BWD_CLS_ONLY, "VETO_ATTN_BWD_QKV_F24": native.VETO_ATTN_BWD_QKV_F24,
+              "VETO_ATTN_BWD_SPLIT_OUT": native.VETO_ATTN_BWD_SPLIT_OUT}
+    for name in consts:
+        lines.append('  printf("%s %%ld\\n", (long)%s);' % (name, name))
+    lines += ['  return 0;', '}']
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), "-o", str(exe), str(src)], check=True)
+    got = {}
+    for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        key, *nums = line.split()
+        got[key] = tuple(int(n) for n in nums)
+    want = {name: (value,) for name, value in consts.items()}
+    for cname, mirror in native.STRUCTS.items():
+        want[cname] = (ctypes.sizeof(mirror),)
+        for field, _ in mirror._fields_:
+            d = getattr(mirror, field)
+            want["%s.%s" % (cname, field)] = (d.offset, d.size)
+    assert got == want, sorted(k for k in want if got.get(k) != want[k])
+
+
+def test_wrappers_name_only_fields_their_struct_has():
+    """A ctypes Structure accepts any attribute, so a misspelt keyword of Launch.args() would reach the ABI as a silent NULL: every
+    literal keyword of every `<launch>.args(native.VetoX, ...)` call in the package must be a field of VetoX."""
+    import ast
+    import glob
+    pkg = os.path.dirname(os.path.abspath(native.__file__))
+    checked = 0
+    for path in sorted(glob.glob(os.path.join(pkg, "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read())):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "args" and node.args \
+                    and isinstance(node.args[0], ast.Attribute) and node.args[0].attr in {m.__name__ for m in native.STRUCTS.values()}:
+                names = {f for f, _ in getattr(native, node.args[0].attr)._fields_}
+                for kw in node.keywords:
+                    if kw.arg is not None:
+                        assert kw.arg in names, (os.path.basename(path), node.lineno, node.args[0].attr, kw.arg)
+                        checked += 1
+    assert checked > 100

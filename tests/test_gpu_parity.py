@@ -1107,3 +1107,54 @@ def test_gemm_bias_slices_with_single_kstep_tiles():
     torch.cuda.synchronize()
     ref = a.double() @ w.double().t() + bias.double()
     assert ((c.double() - ref).abs().max().item()) < 1e-2
+
+
+def test_workspace_is_one_per_device_and_stream_and_only_grows():
+    """The call path's scratch memory (native.Launch.workspace): calls on two side streams give the default stream's bits, each
+    stream has its own workspace tensor, and a smaller call on a stream re-uses that stream's tensor.  Vanilla PostProcessor
+    (1 image, 3 objects, 6 pairs, 51 predicates) and SGGEvaluator.evaluate (1 image, 2 GT relations, 6 predictions)."""
+    from veto_amd import native, synth
+    from veto_amd.evaluation import SGGEvaluator
+    from veto_amd.postprocess import PostProcessor
+    from veto_amd.structures import BoxList
+    dev = _dev()
+    pair_list = [(a, b) for a in range(3) for b in range(3) if a != b]
+    rel = torch.from_numpy(synth.normal(11, "ws.rel", (6, 51), 0.0, 2.0)).to(dev)
+    obj = torch.from_numpy(synth.normal(11, "ws.obj", (3, 151), 0.0, 3.0)).to(dev)
+    pairs = torch.tensor(pair_list, dtype=torch.int64, device=dev)
+    image = {"gt_rels": np.array([[0, 1, 5], [2, 0, 17]]), "gt_classes": np.array([3, 7, 9]),
+             "gt_boxes": np.array([[0, 0, 50, 50], [60, 10, 120, 90], [20, 100, 80, 160]], dtype=np.float32),
+             "pred_rel_inds": np.array(pair_list), "rel_scores": torch.softmax(rel, 1).cpu().numpy(),
+             "pred_classes": np.array([3, 7, 9]), "obj_scores": np.ones(3, dtype=np.float32)}
+    image["pred_boxes"] = image["gt_boxes"]
+    evaluator = SGGEvaluator("sgcls", 51, np.array([[9, 3, 17]]), device=dev)
+
+    def post(n_pair=6):
+        box = BoxList(torch.zeros(3, 4), (800, 600)).to(dev)
+        r = PostProcessor(False, use_gt_box=True)((rel[:n_pair], obj), [pairs[:n_pair]], [box])[0]
+        return [r.get_field(k) for k in ("pred_labels", "pred_scores", "rel_pair_idxs", "pred_rel_scores", "pred_rel_labels")]
+
+    def evaluate():
+        res = evaluator.evaluate([image])
+        flat = [np.array([res[k][n] for n in (20, 50, 100)]) for k in ("recall", "recall_nogc", "zeroshot_recall", "accuracy",
+                                                                       "mean_recall", "ng_mean_recall")]
+        return flat + [res["per_image"][0][k] for k in ("gc_rank", "ng_rank", "acc_rank", "zeroshot")]
+
+    want_post, want_eval = post(), evaluate()
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    for s in streams:
+        with torch.cuda.stream(s):
+            got_post, got_eval = post(), evaluate()
+        s.synchronize()
+        assert all(torch.equal(g, w) for g, w in zip(got_post, want_post))
+        assert all(np.array_equal(g, w, equal_nan=True) for g, w in zip(got_eval, want_eval))
+    keys = [(s.device_index, s.cuda_stream) for s in streams]
+    ws = [native._WORKSPACES[k] for k in keys]
+    assert ws[0] is not ws[1] and ws[0].data_ptr() != ws[1].data_ptr()
+    assert (dev.index, 0) in native._WORKSPACES and native._WORKSPACES[(dev.index, 0)] is not ws[0]   # the default stream's own
+    with torch.cuda.stream(streams[0]):
+        small = post(n_pair=2)
+    streams[0].synchronize()
+    assert native._WORKSPACES[keys[0]] is ws[0]
+    assert small[2].shape == (2, 2)

@@ -17,7 +17,7 @@ for imgs in (1, 2, 12):
     with torch.no_grad():
         ref = torch.cat(list(model(props, pairs, None, None, roi_features=rgb, roi_depth_features=dep)[1]))
     labels = torch.cat([p.get_field("labels") for p in props])       # predcls: hard labels, no logits
-    inp, keep, n_objs, n_pairs, device, eng = model._prepare_inputs(props, pairs, rgb, dep, labels, None)
+    call, inp, n_objs, n_pairs, eng = model._prepare_inputs(props, pairs, rgb, dep, labels, None)   # (call keeps inp's tensors)
     ws = torch.empty(eng.workspace_bytes(inp.n_obj, inp.n_pair), dtype=torch.uint8, device=dev)
     out = torch.empty((inp.n_pair, model._num_out), dtype=torch.float32, device=dev)
     side = torch.cuda.Stream(dev)

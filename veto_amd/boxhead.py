@@ -13,9 +13,7 @@ import torch
 from torch import nn
 
 from . import native
-from .predictor import cached_offsets
 
-_WORKSPACE = {}   # (device, stream) -> workspace: launches on different streams never share one
 _SIZES = {}       # (device, image sizes) -> device tensor [n_img, 2]
 
 
@@ -46,9 +44,7 @@ def box_postprocess(class_logits, box_regression, proposals, n_per_img, image_si
     Returns per image a dict of device tensors: orig_inds int64 [K], pred_labels int64 [K], pred_scores [K], boxes [K, 4],
     boxes_per_cls [K, C, 4]."""
     device = class_logits.device
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd box-head post-processing runs on a HIP device only (got %s)" % device)
-    lib = native.load_library()
+    call = native.Launch(device, "veto_amd box-head post-processing runs on a HIP device only")
     f32 = dict(device=device, dtype=torch.float32)
     n_box, n_cls = int(class_logits.shape[0]), int(class_logits.shape[1])
     n_per_img = [int(n) for n in n_per_img]
@@ -63,19 +59,14 @@ def box_postprocess(class_logits, box_regression, proposals, n_per_img, image_si
     proposals = proposals.detach().to(**f32).reshape(n_box, 4).contiguous()
     sizes = _image_sizes([(float(w), float(h)) for w, h in image_sizes], device)
     host_off = np.concatenate([[0], np.cumsum(n_per_img)]).astype(np.int32)
-    stream = torch.cuda.current_stream(device)
-    need = lib.veto_box_postprocess_workspace_bytes(n_box, n_cls, int(bool(nms_filter_duplicates)))
-    key = (str(device), stream.cuda_stream)
-    ws = _WORKSPACE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    ws = call.workspace(call.lib.veto_box_postprocess_workspace_bytes(n_box, n_cls, int(bool(nms_filter_duplicates))))
     # rows reserved per image: every detection when there is no cut, else the cut plus as many ties again (a batch whose
     # ties exceed that reports the rows it needs and is run once more with exactly those)
     bound = [n if nms_filter_duplicates else
              (min(n, post_nms_per_cls_topn) if post_nms_per_cls_topn > 0 else n) * (n_cls - 1) for n in n_per_img]
     caps = [min(b, 2 * detections_per_img) if detections_per_img > 0 else b for b in bound]
     for attempt in range(2):
-        img_off, out_off = cached_offsets(n_per_img, caps, device)
+        off = native.device_offsets(n_per_img, caps, device=device)
         rows = sum(caps)
         orig = torch.empty(rows, dtype=torch.int64, device=device)
         labels = torch.empty(rows, dtype=torch.int64, device=device)
@@ -83,29 +74,21 @@ def box_postprocess(class_logits, box_regression, proposals, n_per_img, image_si
         boxes = torch.empty((rows, 4), **f32)
         bpc = torch.empty((rows, n_cls, 4), **f32) if want_boxes_per_cls else None
         counts = torch.empty(len(n_per_img), dtype=torch.int32, device=device)
-        a = native.VetoBoxPostArgs()
-        a.struct_size = ctypes.sizeof(native.VetoBoxPostArgs)
-        a.n_img, a.n_box, a.n_cls, a.reg_cols = len(n_per_img), n_box, n_cls, int(box_regression.shape[1])
-        a.cls_agnostic, a.post_nms_per_cls_topn = int(bool(cls_agnostic_bbox_reg)), int(post_nms_per_cls_topn)
-        a.filter_duplicates, a.detections_per_img = int(bool(nms_filter_duplicates)), int(detections_per_img)
-        a.score_thresh, a.nms_thresh, a.bbox_xform_clip = float(score_thresh), float(nms), float(bbox_xform_clip)
-        a.reg_weights = (ctypes.c_float * 4)(*[float(w) for w in reg_weights])
-        a.class_logits, a.box_regression, a.proposals = class_logits.data_ptr(), box_regression.data_ptr(), proposals.data_ptr()
-        a.image_sizes, a.img_offset, a.img_offset_host = sizes.data_ptr(), img_off.data_ptr(), host_off.ctypes.data
-        a.img_out_offset = out_off.data_ptr()
-        a.orig_inds, a.pred_labels, a.pred_scores, a.boxes = orig.data_ptr(), labels.data_ptr(), scores.data_ptr(), boxes.data_ptr()
-        a.boxes_per_cls = bpc.data_ptr() if bpc is not None and rows else None
-        a.counts = counts.data_ptr()
-        native.check(lib.veto_box_postprocess(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()),
-                                              ws.numel()))
+        a = call.args(native.VetoBoxPostArgs, n_img=len(n_per_img), n_box=n_box, n_cls=n_cls, reg_cols=int(box_regression.shape[1]),
+                      cls_agnostic=int(bool(cls_agnostic_bbox_reg)), post_nms_per_cls_topn=int(post_nms_per_cls_topn),
+                      filter_duplicates=int(bool(nms_filter_duplicates)), detections_per_img=int(detections_per_img),
+                      score_thresh=float(score_thresh), nms_thresh=float(nms), bbox_xform_clip=float(bbox_xform_clip),
+                      reg_weights=(ctypes.c_float * 4)(*[float(w) for w in reg_weights]), class_logits=class_logits,
+                      box_regression=box_regression, proposals=proposals, image_sizes=sizes, img_offset=off[0],
+                      img_offset_host=host_off.ctypes.data, img_out_offset=off[1], orig_inds=orig, pred_labels=labels,
+                      pred_scores=scores, boxes=boxes, boxes_per_cls=bpc, counts=counts)
+        call.run("veto_box_postprocess", ctypes.byref(a), ws.data_ptr(), ws.numel())
         kept = counts.tolist()   # the one device->host copy of the batch: the counts decide the split
         if min(kept) >= 0:
             break
         if attempt:
             raise native.VetoError("veto_box_postprocess: detections %s do not fit the rows %s" % (kept, caps))
         caps = [max(c, -k) for c, k in zip(caps, kept)]
-    for t in (class_logits, box_regression, proposals, sizes, img_off, out_off, ws):
-        t.record_stream(stream)
     out, row = [], 0
     for cap, k in zip(caps, kept):
         sl = slice(row, row + k)

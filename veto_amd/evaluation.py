@@ -19,7 +19,6 @@ import numpy as np
 import torch
 
 from . import native
-from .predictor import cached_offsets
 
 KS = (20, 50, 100)
 NO_MATCH = 0x3fffffff
@@ -40,7 +39,6 @@ class SGGEvaluator:
         if self.device.type != "cuda":
             raise RuntimeError("veto_amd.SGGEvaluator runs only on a HIP device (got %s)" % self.device)
         self.zeroshot = _t(zeroshot_triplet, torch.int64, self.device).reshape(-1, 3).contiguous()
-        self._workspace = None
         self.reset()
 
     # ---- dataset-level accumulation (the reference's evaluators keep per-image lists over the WHOLE split and fold them once,
@@ -118,7 +116,8 @@ class SGGEvaluator:
         return self.evaluate(images)
 
     def evaluate(self, images):
-        dev, lib = self.device, native.load_library()
+        dev = self.device
+        call = native.Launch(dev, "veto_amd.SGGEvaluator runs only on a HIP device")
         i64, f32, i32 = torch.int64, torch.float32, torch.int32
         def cat(key, dtype, shape):
             t = torch.cat([_t(im[key], dtype, dev).reshape(shape) for im in images], 0).contiguous()
@@ -139,39 +138,27 @@ class SGGEvaluator:
         n_g = [rows(im["gt_rels"], 3) for im in images]
         n_o = [int(len(im["gt_classes"])) for im in images]
         n_p = [rows(im["pred_rel_inds"], 2) for im in images]
-        obj_off, pair_off = cached_offsets(n_o, n_p, dev)
         pred_off = None
         if self.mode == "sgdet":   # the detector's objects: their own count per image (vg_eval.py:491-495)
             n_q = [rows(im["pred_classes"], 1) for im in images]
             if [rows(im["pred_boxes"], 4) for im in images] != n_q or [rows(im["obj_scores"], 1) for im in images] != n_q:
                 raise ValueError("sgdet: pred_classes, pred_boxes and obj_scores must have one row per predicted object")
-            pred_off = cached_offsets(n_q, n_q, dev)[0]
-        gt_off = cached_offsets(n_g, n_g, dev)[0]
+            pred_off = native.device_offsets(n_q, device=dev)[0]
+        off = native.device_offsets(n_g, n_o, n_p, device=dev)
         n_img, sum_g, sum_p, C = len(images), sum(n_g), sum(n_p), self.num_rel
         out = {k: torch.empty(max(sum_g, 1), dtype=i32, device=dev) for k in ("gc_rank", "ng_rank", "acc_rank", "zeroshot_flag")}
         ng_rows = torch.zeros((n_img, 100), dtype=i32, device=dev)
         ng_cols = torch.zeros((n_img, 100), dtype=i32, device=dev)
         ng_count = torch.zeros(n_img, dtype=i32, device=dev)
         metrics = torch.empty(18 + 6 * (C - 1) + 2, dtype=torch.float64, device=dev)
-        need = lib.veto_sgg_eval_workspace_bytes(n_img, sum_p, sum_g, C)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        a = native.VetoSggEvalArgs()
-        a.struct_size = ctypes.sizeof(native.VetoSggEvalArgs)
-        a.n_img, a.n_rel_cls, a.n_zeroshot, a.iou_thres = n_img, C, int(self.zeroshot.shape[0]), self.iou_thres
-        a.gt_offset, a.obj_offset, a.pair_offset = gt_off.data_ptr(), obj_off.data_ptr(), pair_off.data_ptr()
-        a.gt_rels, a.gt_classes, a.gt_boxes = gt_rels.data_ptr(), gt_classes.data_ptr(), gt_boxes.data_ptr()
-        a.pred_pairs, a.rel_scores = pred_pairs.data_ptr(), rel_scores.data_ptr()
-        a.pred_classes, a.pred_boxes, a.obj_scores = pred_classes.data_ptr(), pred_boxes.data_ptr(), obj_scores.data_ptr()
-        a.zeroshot = self.zeroshot.data_ptr() if self.zeroshot.shape[0] else None
-        a.reserved0 = 1 if pred_off is not None else 0
-        a.pred_obj_offset = pred_off.data_ptr() if pred_off is not None else None
-        a.gc_rank, a.ng_rank, a.acc_rank = out["gc_rank"].data_ptr(), out["ng_rank"].data_ptr(), out["acc_rank"].data_ptr()
-        a.zeroshot_flag = out["zeroshot_flag"].data_ptr()
-        a.ng_rows, a.ng_cols, a.ng_count, a.metrics = ng_rows.data_ptr(), ng_cols.data_ptr(), ng_count.data_ptr(), metrics.data_ptr()
-        stream = torch.cuda.current_stream(dev)
-        native.check(lib.veto_sgg_eval(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), sum_p, sum_g,
-                                       ctypes.c_void_p(self._workspace.data_ptr()), self._workspace.numel()))
+        a = call.args(native.VetoSggEvalArgs, n_img=n_img, n_rel_cls=C, n_zeroshot=int(self.zeroshot.shape[0]), iou_thres=self.iou_thres,
+                      gt_offset=off[0], obj_offset=off[1], pair_offset=off[2], gt_rels=gt_rels, gt_classes=gt_classes,
+                      gt_boxes=gt_boxes, pred_pairs=pred_pairs, rel_scores=rel_scores, pred_classes=pred_classes,
+                      pred_boxes=pred_boxes, obj_scores=obj_scores, zeroshot=self.zeroshot,
+                      reserved0=1 if pred_off is not None else 0, pred_obj_offset=pred_off, ng_rows=ng_rows, ng_cols=ng_cols,
+                      ng_count=ng_count, metrics=metrics, **out)
+        ws = call.workspace(call.lib.veto_sgg_eval_workspace_bytes(n_img, sum_p, sum_g, C))
+        call.run("veto_sgg_eval", ctypes.byref(a), sum_p, sum_g, ws.data_ptr(), ws.numel())
         m = metrics.cpu().numpy()
         Cf = C - 1
         res = {"images_evaluated": int(m[18 + 6 * Cf]), "images_with_zeroshot": int(m[18 + 6 * Cf + 1])}

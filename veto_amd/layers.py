@@ -13,7 +13,6 @@ import numpy as np
 import torch
 
 from . import native
-from .predictor import cached_offsets
 
 
 def max_segment():
@@ -26,9 +25,7 @@ def batched_nms(boxes, scores, offsets, threshold, max_keep=-1):
     M).  Returns (keep int64 [M], counts int32 [S]) on the device: segment s kept counts[s] boxes, whose indices LOCAL to
     the segment are keep[offsets[s] : offsets[s] + counts[s]], ascending."""
     device = boxes.device
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd.layers.nms runs on a HIP device only (got %s)" % device)
-    lib = native.load_library()
+    call = native.Launch(device, "veto_amd.layers.nms runs on a HIP device only")
     host = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
     if host.size < 2:
         raise ValueError("offsets must hold at least two boundaries, got %d" % host.size)
@@ -38,19 +35,12 @@ def batched_nms(boxes, scores, offsets, threshold, max_keep=-1):
     sizes = np.diff(host).tolist()
     if min(sizes) < 0:   # (the ABI checks again; a prefix sum of these sizes would hide it)
         raise native.VetoError("veto_amd native call failed (-1): seg_offset_host is not monotone: %s" % host.tolist())
-    dev_off, _ = cached_offsets(sizes, [0] * len(sizes), device)
     keep = torch.empty(n_box, dtype=torch.int64, device=device)
     counts = torch.empty(len(sizes), dtype=torch.int32, device=device)
-    a = native.VetoNmsArgs()
-    a.struct_size = ctypes.sizeof(native.VetoNmsArgs)
-    a.n_box, a.n_seg, a.max_keep, a.threshold = n_box, len(sizes), int(max_keep), float(threshold)
-    a.boxes, a.scores = boxes.data_ptr(), scores.data_ptr()
-    a.seg_offset, a.seg_offset_host = dev_off.data_ptr(), host.ctypes.data
-    a.keep, a.counts = keep.data_ptr(), counts.data_ptr()
-    stream = torch.cuda.current_stream(device)
-    native.check(lib.veto_nms(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
-    for t in (boxes, scores, dev_off):
-        t.record_stream(stream)
+    a = call.args(native.VetoNmsArgs, n_box=n_box, n_seg=len(sizes), max_keep=int(max_keep), threshold=float(threshold), boxes=boxes,
+                  scores=scores, seg_offset=native.device_offsets(sizes, device=device)[0], seg_offset_host=host.ctypes.data,
+                  keep=keep, counts=counts)
+    call.run("veto_nms", ctypes.byref(a))
     return keep, counts
 
 

@@ -9,7 +9,6 @@ and backward of the transformer itself are not built, so the predictors still re
                         generator, the device consumes them exactly as randint / random would, and the host generator
                         is advanced by what was used, so a run stays in lock-step with the reference's stream.
 """
-import ctypes
 import random
 
 import numpy as np
@@ -20,10 +19,8 @@ from . import meet_tables, native
 
 def relation_ce_loss(logits, labels, weight=None, rows=None, want_grad=False):
     """Returns (loss [1] float32 device tensor, grad [n, C] or None)."""
-    lib = native.load_library()
     dev = logits.device
-    if dev.type != "cuda":
-        raise RuntimeError("veto_amd losses run only on a HIP device (got %s)" % dev)
+    call = native.Launch(dev, "veto_amd losses run only on a HIP device")
     logits = logits.detach().to(torch.float32).contiguous()
     labels = labels.to(device=dev, dtype=torch.int64).contiguous()
     n, C = int(labels.shape[0]), int(logits.shape[1])
@@ -42,14 +39,9 @@ def relation_ce_loss(logits, labels, weight=None, rows=None, want_grad=False):
                 torch.zeros((0, C), dtype=torch.float32, device=dev) if want_grad else None)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     grad = torch.empty((n, C), dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(lib.veto_ce_loss_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    native.check(lib.veto_ce_loss(
-        ctypes.c_void_p(stream.cuda_stream), logits.data_ptr(), logits.stride(0), labels.data_ptr(),
-        weight.data_ptr() if weight is not None else None, rows.data_ptr() if rows is not None else None, n, C,
-        loss.data_ptr(), grad.data_ptr() if grad is not None else None, ws.data_ptr(), ws.numel()))
-    for t in (logits, labels, ws):
-        t.record_stream(stream)
+    ws = call.workspace(call.lib.veto_ce_loss_workspace_bytes(n))
+    call.run("veto_ce_loss", call.ptr(logits), logits.stride(0), call.ptr(labels), call.ptr(weight), call.ptr(rows), n, C,
+             loss.data_ptr(), call.ptr(grad), ws.data_ptr(), ws.numel())
     return loss, grad
 
 
@@ -107,8 +99,8 @@ class MeetTrainingSampler:
         """rel_labels: [n] int64.  Returns (chosen, group_labels): per group the selected row indices (the reference's
         cur_chosen_matrix[0][k]) and their group-local labels.  Advances Python's `random` exactly as the reference's
         loop would have."""
-        lib = native.load_library()
         dev, G = self.device, len(self.sizes)
+        call = native.Launch(dev, "veto_amd losses run only on a HIP device")
         labels = rel_labels.to(device=dev, dtype=torch.int64).contiguous()
         n = int(labels.shape[0])
         n_words = 4 * n + 64      # 2 words per foreground relation; background: 1 + rejections (p < 1/2 each)
@@ -118,11 +110,9 @@ class MeetTrainingSampler:
             chosen = torch.empty((G, n), dtype=torch.int64, device=dev)
             glabels = torch.empty((G, n), dtype=torch.int64, device=dev)
             meta = torch.empty(G + 1, dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev)
-            native.check(lib.veto_meet_sample(
-                ctypes.c_void_p(stream.cuda_stream), labels.data_ptr(), n, words.data_ptr(), n_words, self.incre.data_ptr(),
-                self.pos_in_group.data_ptr(), self.group_size.data_ptr(), self.rates.data_ptr(), G, self.n_cls,
-                chosen.data_ptr(), glabels.data_ptr(), meta.data_ptr(), meta[G:].data_ptr()))
+            call.run("veto_meet_sample", call.ptr(labels), n, call.ptr(words), n_words, self.incre.data_ptr(),
+                     self.pos_in_group.data_ptr(), self.group_size.data_ptr(), self.rates.data_ptr(), G, self.n_cls,
+                     chosen.data_ptr(), glabels.data_ptr(), meta.data_ptr(), meta[G:].data_ptr())
             host = meta.cpu().tolist()       # the list lengths are data dependent: one small read-back
             if host[G] >= 0:
                 break

@@ -1,8 +1,10 @@
-"""ctypes binding of the C ABI declared in include/veto_amd.h (libveto_amd.so).
+"""ctypes binding of the C ABI declared in include/veto_amd.h (libveto_amd.so), and the one call path the wrappers share
+(Launch, device_offsets).
 
 There is no fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes
+import itertools
 import os
 
 # PyTorch bundles its own HIP runtime (torch/lib/libamdhip64.so, SONAME libamdhip64.so.7).  It must be
@@ -14,25 +16,8 @@ from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_float, c_in
 
 _LIB = None
 
-EXPORTS = [
-    "veto_last_error", "veto_version", "veto_create", "veto_destroy", "veto_num_weights",
-    "veto_weight_info", "veto_load_weights", "veto_workspace_bytes", "veto_forward", "veto_forward_saturation",
-    "veto_enumerate_pairs", "veto_profile_enable", "veto_profile_collect", "veto_profile_entry",
-    "veto_profile_reset", "veto_debug_gemm", "veto_debug_gemm_workspace_bytes", "veto_debug_gemm_forms", "veto_debug_ffn", "veto_debug_ffn_workspace_bytes", "veto_debug_outproj", "veto_debug_outproj_workspace_bytes", "veto_debug_layer_tail", "veto_debug_layer_tail_workspace_bytes", "veto_debug_qkv_attn", "veto_debug_qkv_attn_workspace_bytes",
-    "veto_postprocess", "veto_postprocess_workspace_bytes", "veto_postprocess_meet", "veto_postprocess_vote",
-    "veto_obj_decode", "veto_obj_decode_workspace_bytes", "veto_prepare_test_pairs",
-    "veto_detect_relsample", "veto_detect_relsample_workspace_bytes", "veto_gtbox_relsample",
-    "veto_nms", "veto_nms_max_segment", "veto_box_postprocess", "veto_box_postprocess_workspace_bytes",
-    "veto_rpn_proposals", "veto_rpn_proposals_workspace_bytes",
-    "veto_train_workspace_bytes", "veto_grad_floats", "veto_weight_offset", "veto_forward_train", "veto_backward",
-    "veto_debug_attention_backward", "veto_debug_layernorm_backward", "veto_debug_layernorm_backward_workspace_bytes",
-    "veto_debug_gelu_backward", "veto_debug_column_sums",
-    "veto_debug_attention_backward_forms", "veto_debug_layernorm_backward_split", "veto_debug_layernorm_backward_col_partial_rows",
-    "veto_debug_wgrad", "veto_debug_wgrad_workspace_bytes", "veto_ce_loss", "veto_ce_loss_workspace_bytes", "veto_meet_sample",
-    "veto_roi_pool", "veto_roi_pool_backward", "veto_sgg_eval", "veto_sgg_eval_workspace_bytes",
-]
-
 VETO_PRECISE, VETO_FAST, VETO_MIXED = 0, 1, 2
+VETO_ATTN_BWD_CLS_ONLY, VETO_ATTN_BWD_QKV_F24, VETO_ATTN_BWD_SPLIT_OUT = 1, 2, 4   # veto_debug_attention_backward_forms flags
 
 
 class VetoConfig(Structure):
@@ -172,6 +157,91 @@ class VetoTrainOpts(Structure):
                 ("seed", ctypes.c_uint64), ("d_roi_rgb", c_void_p), ("d_roi_depth", c_void_p)]
 
 
+STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_abi_symbols.py compares every field's offset and size)
+    "veto_config_t": VetoConfig, "veto_inputs_t": VetoInputs, "veto_debug_outputs_t": VetoDebugOutputs,
+    "veto_saturation_t": VetoSaturation, "veto_post_args_t": VetoPostArgs, "veto_post_meet_args_t": VetoPostMeetArgs,
+    "veto_post_vote_args_t": VetoPostVoteArgs, "veto_obj_decode_args_t": VetoObjDecodeArgs, "veto_pair_args_t": VetoPairArgs,
+    "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
+    "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
+    "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
+}
+
+_P, _I, _Z = c_void_p, c_int32, c_size_t
+
+
+def _sig(*argtypes, ret=c_int):
+    return ret, list(argtypes)
+
+
+SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies all of it, so no export goes without a signature
+    "veto_last_error": _sig(ret=c_char_p),
+    "veto_version": _sig(ret=c_char_p),
+    "veto_create": _sig(POINTER(VetoConfig), POINTER(_P)),
+    "veto_destroy": _sig(_P),
+    "veto_num_weights": _sig(_P),
+    "veto_weight_info": _sig(_P, _I, POINTER(c_char_p), POINTER(_Z)),
+    "veto_load_weights": _sig(_P, c_char_p, _P, _Z, _P),
+    "veto_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
+    "veto_forward": _sig(_P, _P, POINTER(VetoInputs), _P, _Z, _P, POINTER(VetoDebugOutputs)),
+    "veto_forward_saturation": _sig(_P, _P, POINTER(VetoInputs), _P, _Z, _P, POINTER(VetoSaturation), _I),
+    "veto_enumerate_pairs": _sig(_P, _I, _P),
+    "veto_profile_enable": _sig(_P, _I),
+    "veto_profile_collect": _sig(_P),
+    "veto_profile_entry": _sig(_P, _I, POINTER(c_char_p), POINTER(c_double), POINTER(c_int64), POINTER(c_double), POINTER(c_double)),
+    "veto_profile_reset": _sig(_P),
+    "veto_debug_gemm": _sig(_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z),
+    "veto_debug_gemm_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
+    "veto_debug_gemm_forms": _sig(_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z),
+    "veto_debug_ffn": _sig(_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, POINTER(c_float), _P, _Z, _P, _P, _P),
+    "veto_debug_ffn_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_debug_outproj": _sig(_P, _P, _P, _P, _P, _I, _I, _I, _I, POINTER(c_float), _P, _Z, _P, _P, _P),
+    "veto_debug_outproj_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_debug_layer_tail": _sig(_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, POINTER(c_float), _P, _Z, _P, _P, _P),
+    "veto_debug_layer_tail_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_debug_qkv_attn": _sig(_P, _P, _P, _I, _I, _I, _I, POINTER(c_float), _P, _Z, _P),
+    "veto_debug_qkv_attn_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_postprocess": _sig(_P, POINTER(VetoPostArgs), _P, _Z),
+    "veto_postprocess_workspace_bytes": _sig(_I, _I, ret=_Z),
+    "veto_postprocess_meet": _sig(_P, POINTER(VetoPostMeetArgs), _P, _Z),
+    "veto_postprocess_vote": _sig(_P, POINTER(VetoPostVoteArgs), _P, _Z),
+    "veto_obj_decode": _sig(_P, POINTER(VetoObjDecodeArgs), _P, _Z),
+    "veto_obj_decode_workspace_bytes": _sig(_I, _I, ret=_Z),
+    "veto_prepare_test_pairs": _sig(_P, POINTER(VetoPairArgs)),
+    "veto_detect_relsample": _sig(_P, POINTER(VetoDetectRelsampleArgs), _P, _Z),
+    "veto_detect_relsample_workspace_bytes": _sig(_I, _I, ret=_Z),
+    "veto_gtbox_relsample": _sig(_P, POINTER(VetoGtboxRelsampleArgs)),
+    "veto_nms": _sig(_P, POINTER(VetoNmsArgs)),
+    "veto_nms_max_segment": _sig(),
+    "veto_box_postprocess": _sig(_P, POINTER(VetoBoxPostArgs), _P, _Z),
+    "veto_box_postprocess_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
+    "veto_rpn_proposals": _sig(_P, POINTER(VetoRpnArgs), _P, _Z),
+    "veto_rpn_proposals_workspace_bytes": _sig(POINTER(VetoRpnArgs), ret=_Z),
+    "veto_train_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
+    "veto_grad_floats": _sig(_P, ret=_Z),
+    "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),
+    "veto_forward_train": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), _P, _Z, _P),
+    "veto_backward": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), _P, _Z, _P, _P),
+    "veto_debug_attention_backward": _sig(_P, _P, _P, _P, _I, _I),
+    "veto_debug_layernorm_backward": _sig(_P, _P, _P, _P, _P, _P, _P, _I, _P, _Z),
+    "veto_debug_layernorm_backward_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_debug_gelu_backward": _sig(_P, _P, _P, _P, _Z),
+    "veto_debug_column_sums": _sig(_P, _P, c_int64, _I, _I, _P, _P, _Z),
+    "veto_debug_attention_backward_forms": _sig(_P, _P, _P, _P, _P, _I, _I, c_uint32),
+    "veto_debug_layernorm_backward_split": _sig(_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, c_uint64, c_uint32, c_float, _P, _Z),
+    "veto_debug_layernorm_backward_col_partial_rows": _sig(_I, ret=_I),
+    "veto_debug_wgrad": _sig(_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z),
+    "veto_debug_wgrad_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+    "veto_ce_loss": _sig(_P, _P, c_int64, _P, _P, _P, _I, _I, _P, _P, _P, _Z),
+    "veto_ce_loss_workspace_bytes": _sig(_I, ret=_Z),
+    "veto_meet_sample": _sig(_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P),
+    "veto_roi_pool": _sig(_P, POINTER(VetoRoiPoolArgs)),
+    "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
+    "veto_sgg_eval": _sig(_P, POINTER(VetoSggEvalArgs), _I, _I, _P, _Z),
+    "veto_sgg_eval_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+}
+EXPORTS = list(SIGNATURES)   # what include/veto_amd.h declares
+
+
 class VetoError(RuntimeError):
     pass
 
@@ -192,101 +262,9 @@ def load_library():
         from .build import build_native
         build_native()
     lib = ctypes.CDLL(path)
-    lib.veto_last_error.restype = c_char_p
-    lib.veto_version.restype = c_char_p
-    lib.veto_create.argtypes = [POINTER(VetoConfig), POINTER(c_void_p)]
-    lib.veto_destroy.argtypes = [c_void_p]
-    lib.veto_num_weights.argtypes = [c_void_p]
-    lib.veto_weight_info.argtypes = [c_void_p, c_int, POINTER(c_char_p), POINTER(c_size_t)]
-    lib.veto_load_weights.argtypes = [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p]
-    lib.veto_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
-    lib.veto_workspace_bytes.restype = c_size_t
-    lib.veto_forward.argtypes = [c_void_p, c_void_p, POINTER(VetoInputs), c_void_p, c_size_t, c_void_p,
-                                 POINTER(VetoDebugOutputs)]
-    lib.veto_forward_saturation.argtypes = [c_void_p, c_void_p, POINTER(VetoInputs), c_void_p, c_size_t, c_void_p,
-                                            POINTER(VetoSaturation), c_int32]
-    lib.veto_enumerate_pairs.argtypes = [c_void_p, c_int32, c_void_p]
-    lib.veto_profile_enable.argtypes = [c_void_p, c_int32]
-    lib.veto_profile_collect.argtypes = [c_void_p]
-    lib.veto_profile_entry.argtypes = [c_void_p, c_int, POINTER(c_char_p), POINTER(c_double), POINTER(c_int64),
-                                       POINTER(c_double), POINTER(c_double)]
-    lib.veto_profile_reset.argtypes = [c_void_p]
-    lib.veto_debug_gemm.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
-                                    c_int32, c_void_p, c_size_t]
-    lib.veto_debug_gemm_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    lib.veto_debug_gemm_workspace_bytes.restype = c_size_t
-    lib.veto_debug_gemm_forms.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                          c_void_p, c_size_t]
-    lib.veto_debug_ffn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
-                                   c_int32, POINTER(ctypes.c_float), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
-    lib.veto_debug_outproj.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
-                                       POINTER(ctypes.c_float), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
-    lib.veto_debug_outproj_workspace_bytes.argtypes = [c_int32]
-    lib.veto_debug_outproj_workspace_bytes.restype = c_size_t
-    lib.veto_debug_layer_tail.argtypes = [c_void_p] + [c_void_p] * 10 + [c_int32, c_int32, c_int32, POINTER(ctypes.c_float), c_void_p, c_size_t,
-                                                                         c_void_p, c_void_p, c_void_p]
-    lib.veto_debug_layer_tail_workspace_bytes.argtypes = [c_int32]
-    lib.veto_debug_layer_tail_workspace_bytes.restype = c_size_t
-    lib.veto_debug_qkv_attn.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(ctypes.c_float), c_void_p,
-                                        c_size_t, c_void_p]
-    lib.veto_debug_qkv_attn_workspace_bytes.argtypes = [c_int32]
-    lib.veto_debug_qkv_attn_workspace_bytes.restype = c_size_t
-    lib.veto_debug_ffn_workspace_bytes.argtypes = [c_int32]
-    lib.veto_debug_ffn_workspace_bytes.restype = c_size_t
-    lib.veto_postprocess_workspace_bytes.argtypes = [c_int32, c_int32]
-    lib.veto_postprocess_workspace_bytes.restype = c_size_t
-    lib.veto_postprocess.argtypes = [c_void_p, POINTER(VetoPostArgs), c_void_p, c_size_t]
-    lib.veto_postprocess_meet.argtypes = [c_void_p, POINTER(VetoPostMeetArgs), c_void_p, c_size_t]
-    lib.veto_postprocess_vote.argtypes = [c_void_p, POINTER(VetoPostVoteArgs), c_void_p, c_size_t]
-    lib.veto_obj_decode_workspace_bytes.argtypes = [c_int32, c_int32]
-    lib.veto_obj_decode_workspace_bytes.restype = c_size_t
-    lib.veto_obj_decode.argtypes = [c_void_p, POINTER(VetoObjDecodeArgs), c_void_p, c_size_t]
-    lib.veto_prepare_test_pairs.argtypes = [c_void_p, POINTER(VetoPairArgs)]
-    lib.veto_nms_max_segment.argtypes = []
-    lib.veto_nms.argtypes = [c_void_p, POINTER(VetoNmsArgs)]
-    lib.veto_box_postprocess_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    lib.veto_box_postprocess_workspace_bytes.restype = c_size_t
-    lib.veto_box_postprocess.argtypes = [c_void_p, POINTER(VetoBoxPostArgs), c_void_p, c_size_t]
-    lib.veto_rpn_proposals_workspace_bytes.argtypes = [POINTER(VetoRpnArgs)]
-    lib.veto_rpn_proposals_workspace_bytes.restype = c_size_t
-    lib.veto_rpn_proposals.argtypes = [c_void_p, POINTER(VetoRpnArgs), c_void_p, c_size_t]
-    lib.veto_detect_relsample_workspace_bytes.argtypes = [c_int32, c_int32]
-    lib.veto_detect_relsample_workspace_bytes.restype = c_size_t
-    lib.veto_detect_relsample.argtypes = [c_void_p, POINTER(VetoDetectRelsampleArgs), c_void_p, c_size_t]
-    lib.veto_gtbox_relsample.argtypes = [c_void_p, POINTER(VetoGtboxRelsampleArgs)]
-    lib.veto_train_workspace_bytes.argtypes = [c_void_p, c_int32, c_int32]
-    lib.veto_train_workspace_bytes.restype = c_size_t
-    lib.veto_grad_floats.argtypes = [c_void_p]
-    lib.veto_grad_floats.restype = c_size_t
-    lib.veto_weight_offset.argtypes = [c_void_p, c_int, POINTER(c_size_t)]
-    lib.veto_forward_train.argtypes = [c_void_p, c_void_p, POINTER(VetoInputs), POINTER(VetoTrainOpts), c_void_p, c_size_t, c_void_p]
-    lib.veto_backward.argtypes = [c_void_p, c_void_p, POINTER(VetoInputs), POINTER(VetoTrainOpts), c_void_p, c_size_t, c_void_p, c_void_p]
-    lib.veto_debug_attention_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32]
-    lib.veto_debug_layernorm_backward_workspace_bytes.argtypes = [c_int32]
-    lib.veto_debug_layernorm_backward_workspace_bytes.restype = c_size_t
-    lib.veto_debug_layernorm_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
-                                                  c_void_p, c_size_t]
-    lib.veto_debug_attention_backward_forms.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint32]
-    lib.veto_debug_layernorm_backward_col_partial_rows.argtypes = [c_int32]
-    lib.veto_debug_layernorm_backward_col_partial_rows.restype = c_int32
-    lib.veto_debug_layernorm_backward_split.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                        c_int32, c_uint64, c_uint32, c_float, c_void_p, c_size_t]
-    lib.veto_debug_gelu_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
-    lib.veto_debug_column_sums.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t]
-    lib.veto_ce_loss_workspace_bytes.argtypes = [c_int32]
-    lib.veto_ce_loss_workspace_bytes.restype = c_size_t
-    lib.veto_ce_loss.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
-                                 c_void_p, c_size_t]
-    lib.veto_meet_sample.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.veto_debug_wgrad_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    lib.veto_debug_wgrad_workspace_bytes.restype = c_size_t
-    lib.veto_debug_wgrad.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t]
-    lib.veto_roi_pool.argtypes = [c_void_p, POINTER(VetoRoiPoolArgs)]
-    lib.veto_roi_pool_backward.argtypes = [c_void_p, POINTER(VetoRoiPoolArgs), c_void_p, c_void_p, POINTER(c_void_p), c_void_p]
-    lib.veto_sgg_eval_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    lib.veto_sgg_eval_workspace_bytes.restype = c_size_t
-    lib.veto_sgg_eval.argtypes = [c_void_p, POINTER(VetoSggEvalArgs), c_int32, c_int32, c_void_p, c_size_t]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib
     return lib
 
@@ -295,6 +273,82 @@ def check(rc):
     if rc < 0:
         raise VetoError("veto_amd native call failed (%d): %s" % (rc, load_library().veto_last_error().decode()))
     return rc
+
+
+_OFFSETS = {}      # (device, size lists) -> the rows of an int32 [len(size_lists), n + 1] device tensor
+_PLAIN = (int, float, type(None))
+_WORKSPACES = {}   # (device index, stream) -> uint8 scratch tensor, grow-only: calls on different streams never share one
+
+
+def device_offsets(*size_lists, device):
+    """Exclusive prefix sums of equally long per-image size lists: the rows of ONE int32 [len(size_lists), n + 1] device tensor,
+    as a tuple (row r belongs to size_lists[r]; the row views are made once, a slice per call costs microseconds).
+    torch.tensor(list, device=...) is a synchronous pageable H2D copy that stalls the host behind all queued GPU work, so
+    batch shapes seen before (the common case in an eval or training loop) re-use their tensor.  The one offset cache of the
+    package; it is emptied when it reaches 256 shapes."""
+    key = (str(device),) + tuple(tuple(sizes) for sizes in size_lists)
+    hit = _OFFSETS.get(key)
+    if hit is None:
+        if len(_OFFSETS) >= 256:
+            _OFFSETS.clear()
+        rows = [[0] + list(itertools.accumulate(sizes)) for sizes in key[1:]]
+        hit = _OFFSETS[key] = torch.tensor(rows, dtype=torch.int32, device=device).unbind(0)
+    return hit
+
+
+class Launch:
+    """One stream-ordered C-ABI call from a wrapper: the device check, the library, the current stream, the struct's pointer
+    fields, the scratch workspace and, after the call, record_stream on every tensor the call was handed."""
+
+    def __init__(self, device, what):
+        """what: the refusal for a non-HIP device, e.g. 'veto_amd.PostProcessor runs only on a HIP device'."""
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("%s (got %s)" % (what, device))
+        self.lib = load_library()
+        self.stream = torch.cuda.current_stream(self.device)
+        self._tensors = []
+
+    def ptr(self, t):
+        """NULL for None or an empty tensor, else the tensor's address; the tensor is kept for record_stream."""
+        if t is None or t.numel() == 0:
+            return None
+        self._tensors.append(t)
+        return t.data_ptr()
+
+    def args(self, struct_cls, **fields):
+        """A struct_cls with struct_size set; tensor (or None) fields go through ptr(), everything else as it is."""
+        a = struct_cls(struct_size=ctypes.sizeof(struct_cls))
+        keep = self._tensors.append
+        for name, v in fields.items():   # (ptr() inlined: this loop is the host cost of a call)
+            if type(v) not in _PLAIN and isinstance(v, torch.Tensor):   # (isinstance on Tensor's metaclass is slow for an int)
+                if v.numel():
+                    keep(v)
+                    v = v.data_ptr()
+                else:
+                    v = None
+            setattr(a, name, v)
+        return a
+
+    def workspace(self, need):
+        """The scratch tensor of this (device, stream), at least `need` bytes."""
+        key = (self.stream.device_index, self.stream.cuda_stream)
+        ws = _WORKSPACES.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _WORKSPACES[key] = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def run(self, name, *tail, handle=None):
+        """check(lib.<name>([handle,] stream, *tail)), then record()."""
+        head = (c_void_p(self.stream.cuda_stream),) if handle is None else (handle, c_void_p(self.stream.cuda_stream))
+        rc = check(getattr(self.lib, name)(*head, *tail))
+        self.record()
+        return rc
+
+    def record(self):
+        """The tensors handed to ptr() are referenced by enqueued kernels: keep them alive on this stream."""
+        for t in self._tensors:
+            t.record_stream(self.stream)
 
 
 class Engine:

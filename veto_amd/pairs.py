@@ -19,19 +19,16 @@ from . import native
 
 
 def prepare_test_pairs(device, proposals, max_proposal_pairs=2048, require_overlap=False, use_gt_box=True):
-    lib = native.load_library()
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd.prepare_test_pairs runs on a HIP device only (got %s)" % device)
+    call = native.Launch(device, "veto_amd.prepare_test_pairs runs on a HIP device only")
+    device = call.device
     if not use_gt_box:
-        return _prepare_detected_pairs(lib, device, proposals, max_proposal_pairs, require_overlap)
-    stream = torch.cuda.current_stream(device).cuda_stream
+        return _prepare_detected_pairs(call, proposals, max_proposal_pairs, require_overlap)
     out = []
     for p in proposals:
         n = len(p)
         total = n * (n - 1) if n > 1 else 1
         idxs = torch.empty((total, 2), dtype=torch.int64, device=device)
-        native.check(lib.veto_enumerate_pairs(ctypes.c_void_p(stream), n, ctypes.c_void_p(idxs.data_ptr())))
+        call.run("veto_enumerate_pairs", n, idxs.data_ptr())
         if total > max_proposal_pairs:
             # sampling.py:41-45: keep the MAX_PROPOSAL_PAIR best pairs by pred_scores product
             q = p.get_field("pred_scores").to(device)
@@ -46,27 +43,20 @@ def pair_capacity(n, max_proposal_pairs):
     return min(max(n * (n - 1), 1), max_proposal_pairs)
 
 
-def _prepare_detected_pairs(lib, device, proposals, max_proposal_pairs, require_overlap):
-    from .predictor import cached_offsets
+def _prepare_detected_pairs(call, proposals, max_proposal_pairs, require_overlap):
+    device = call.device
     n_objs = [len(p) for p in proposals]
     caps = [pair_capacity(n, max_proposal_pairs) for n in n_objs]
     f32 = dict(device=device, dtype=torch.float32)
     boxes = torch.cat([p.convert("xyxy").bbox.reshape(-1, 4) for p in proposals], 0).to(**f32).contiguous()
     scores = torch.cat([p.get_field("pred_scores").reshape(-1) for p in proposals], 0).to(**f32).contiguous()
-    obj_off, out_off = cached_offsets(n_objs, caps, device)
+    off = native.device_offsets(n_objs, caps, device=device)
     pairs = torch.empty((sum(caps), 2), dtype=torch.int64, device=device)
     counts = torch.empty(len(proposals), dtype=torch.int32, device=device)
-    a = native.VetoPairArgs()
-    a.struct_size = ctypes.sizeof(native.VetoPairArgs)
-    a.n_img, a.n_obj, a.max_obj_per_image = len(proposals), sum(n_objs), max(n_objs)
-    a.max_pairs, a.require_overlap = int(max_proposal_pairs), int(bool(require_overlap))
-    a.boxes, a.scores = boxes.data_ptr(), scores.data_ptr()
-    a.img_obj_offset, a.img_out_offset = obj_off.data_ptr(), out_off.data_ptr()
-    a.pairs, a.counts = pairs.data_ptr(), counts.data_ptr()
-    stream = torch.cuda.current_stream(device)
-    native.check(lib.veto_prepare_test_pairs(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
-    for t in (boxes, scores, obj_off, out_off):
-        t.record_stream(stream)
+    a = call.args(native.VetoPairArgs, n_img=len(proposals), n_obj=sum(n_objs), max_obj_per_image=max(n_objs),
+                  max_pairs=int(max_proposal_pairs), require_overlap=int(bool(require_overlap)), boxes=boxes, scores=scores,
+                  img_obj_offset=off[0], img_out_offset=off[1], pairs=pairs, counts=counts)
+    call.run("veto_prepare_test_pairs", ctypes.byref(a))
     rows = pairs.split(caps)
     if not require_overlap:
         return list(rows)

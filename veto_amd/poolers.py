@@ -19,24 +19,23 @@ from torch import nn
 from . import native
 
 
-def _fill_args(feats, scales, rois, n_img, pooled, sampling_ratio, depth_shape):
-    a = native.VetoRoiPoolArgs()
-    a.struct_size = ctypes.sizeof(native.VetoRoiPoolArgs)
-    a.n_levels, a.n_img, a.n_roi, a.channels = len(feats), n_img, rois.shape[0], feats[0][1]
-    a.pooled, a.sampling_ratio = pooled, sampling_ratio
-    for l, (shape, sc) in enumerate(zip(feats, scales)):
+def _pool_args(call, feats, scales, rois, n_img, pooled, sampling_ratio, depth_shape, **pointers):
+    """feats: per level the map or its shape (the backward has only the shapes)."""
+    shapes = [tuple(getattr(f, "shape", f)) for f in feats]
+    a = call.args(native.VetoRoiPoolArgs, n_levels=len(shapes), n_img=n_img, n_roi=rois.shape[0], channels=shapes[0][1], pooled=pooled,
+                  sampling_ratio=sampling_ratio, rois=rois, **pointers)
+    for l, (f, shape, sc) in enumerate(zip(feats, shapes, scales)):
         a.level_h[l], a.level_w[l], a.level_scale[l] = shape[2], shape[3], float(sc)
+        if isinstance(f, torch.Tensor):
+            a.level_feat[l] = call.ptr(f)
     if depth_shape is not None:
         a.depth_channels, a.depth_h, a.depth_w = depth_shape[1], depth_shape[2], depth_shape[3]
-    a.rois = rois.data_ptr()
     return a
 
 
 def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=None, want_levels=False):
-    lib = native.load_library()
     device = rois.device
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd ROI pooling runs only on a HIP device (got %s)" % device)
+    call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
     feats = [f.detach().to(**f32).contiguous() for f in level_feats]
     rois = rois.detach().to(**f32).contiguous()
@@ -46,33 +45,24 @@ def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=No
             raise ValueError("pyramid level %d has shape %s, expected [%d, %d, H, W]" % (l, tuple(f.shape), n_img, C))
     if depth is not None:
         depth = depth.detach().to(**f32).contiguous()
-    a = _fill_args([tuple(f.shape) for f in feats], scales, rois, n_img, pooled, sampling_ratio,
-                   tuple(depth.shape) if depth is not None else None)
-    for l, f in enumerate(feats):
-        a.level_feat[l] = f.data_ptr()
     out_rgb = torch.empty((n_roi, C, pooled, pooled), **f32)
     out_depth = None
     if depth is not None:
-        a.depth_feat = depth.data_ptr()
         out_depth = torch.empty((n_roi, depth.shape[1], pooled, pooled), **f32)
-        a.out_depth = out_depth.data_ptr()
     levels = torch.empty(n_roi, dtype=torch.int32, device=device) if want_levels else None
-    a.out_rgb = out_rgb.data_ptr()
-    a.out_levels = levels.data_ptr() if want_levels else None
-    stream = torch.cuda.current_stream(device)
-    native.check(lib.veto_roi_pool(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
-    for t in feats + [rois] + ([depth] if depth is not None else []):
-        t.record_stream(stream)
+    a = _pool_args(call, feats, scales, rois, n_img, pooled, sampling_ratio, tuple(depth.shape) if depth is not None else None,
+                   depth_feat=depth, out_rgb=out_rgb, out_depth=out_depth, out_levels=levels)
+    call.run("veto_roi_pool", ctypes.byref(a))
     return out_rgb, out_depth, levels
 
 
 def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb, depth_shape, grad_depth):
     """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None)."""
-    lib = native.load_library()
     device = rois.device
+    call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
     rois = rois.detach().to(**f32).contiguous()
-    a = _fill_args(shapes, scales, rois, n_img, pooled, sampling_ratio, depth_shape if grad_depth is not None else None)
+    a = _pool_args(call, shapes, scales, rois, n_img, pooled, sampling_ratio, depth_shape if grad_depth is not None else None)
     grad_rgb = grad_rgb.detach().to(**f32).contiguous()
     level_grads = [torch.zeros(shape, **f32) for shape in shapes]
     ptrs = (ctypes.c_void_p * 4)(*[g.data_ptr() for g in level_grads])
@@ -80,13 +70,7 @@ def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad
     if grad_depth is not None:
         grad_depth = grad_depth.detach().to(**f32).contiguous()
         depth_grad = torch.zeros(depth_shape, **f32)
-    stream = torch.cuda.current_stream(device)
-    native.check(lib.veto_roi_pool_backward(
-        ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), ctypes.c_void_p(grad_rgb.data_ptr()),
-        ctypes.c_void_p(grad_depth.data_ptr()) if grad_depth is not None else None, ptrs,
-        ctypes.c_void_p(depth_grad.data_ptr()) if depth_grad is not None else None))
-    for t in [rois, grad_rgb] + ([grad_depth] if grad_depth is not None else []):
-        t.record_stream(stream)
+    call.run("veto_roi_pool_backward", ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
     return level_grads, depth_grad
 
 

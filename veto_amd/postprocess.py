@@ -21,7 +21,6 @@ import torch
 from torch import nn
 
 from . import native
-from .predictor import cached_offsets
 
 
 class PostProcessor(nn.Module):
@@ -31,7 +30,6 @@ class PostProcessor(nn.Module):
         self.attribute_on = attribute_on
         self.use_gt_box = use_gt_box
         self.later_nms_pred_thres = later_nms_pred_thres
-        self._workspace = None
 
     def forward(self, x, rel_pair_idxs, boxes, custom_rel_labels=None, cur_chosen_matrix=None, incre_idx_list=None,
                 ensemble=False):
@@ -45,59 +43,28 @@ class PostProcessor(nn.Module):
         rel = torch.cat(list(relation_logits), 0) if isinstance(relation_logits, (list, tuple)) else relation_logits
         obj = torch.cat(list(refine_logits), 0) if isinstance(refine_logits, (list, tuple)) else refine_logits
         device = rel.device
-        if device.type != "cuda":
-            raise RuntimeError("veto_amd.PostProcessor runs only on a HIP device (got %s)" % device)
-        lib = native.load_library()
+        call = native.Launch(device, "veto_amd.PostProcessor runs only on a HIP device")
         n_objs = [len(b) for b in boxes]
         n_pairs = [int(p.shape[0]) for p in rel_pair_idxs]
         n_obj, n_pair = sum(n_objs), sum(n_pairs)
-        f32 = dict(device=device, dtype=torch.float32)
-        rel = rel.detach().to(**f32).contiguous()
-        obj = obj.detach().to(**f32).contiguous()
+        rel = rel.detach().to(device=device, dtype=torch.float32).contiguous()
+        obj = obj.detach().to(device=device, dtype=torch.float32).contiguous()
         if rel.shape[0] != n_pair or obj.shape[0] != n_obj:
             raise ValueError("logit rows (%d, %d) do not match pairs/objects (%d, %d)" % (rel.shape[0], obj.shape[0], n_pair, n_obj))
         pairs = torch.cat([p.reshape(-1, 2) for p in rel_pair_idxs], 0).to(device=device, dtype=torch.int64).contiguous()
-        obj_off, pair_off = cached_offsets(n_objs, n_pairs, device)   # no host-blocking H2D copy in the steady state
-        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes)
-        out = {
-            "obj_scores": obj_scores, "obj_pred": obj_pred,
-            "prob": torch.empty((n_pair, rel.shape[1]), **f32),
-            "pairs": torch.empty((n_pair, 2), dtype=torch.int64, device=device),
-            "labels": torch.empty(n_pair, dtype=torch.int64, device=device), "triple": torch.empty(n_pair, **f32),
-        }
-        need = lib.veto_postprocess_workspace_bytes(n_pair, rel.shape[1])
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        a = native.VetoPostArgs()
-        a.struct_size = ctypes.sizeof(native.VetoPostArgs)
-        a.n_img, a.n_obj, a.n_pair = len(boxes), n_obj, n_pair
-        a.n_rel_cls, a.n_obj_cls, a.max_pairs_per_image = rel.shape[1], obj.shape[1], max(n_pairs)
-        a.rel_logits, a.rel_pairs = rel.data_ptr(), pairs.data_ptr()
-        a.obj_logits = obj.data_ptr() if reg_boxes is None else None   # sgdet: labels / scores are the decoder's
-        a.img_obj_offset, a.img_pair_offset = obj_off.data_ptr(), pair_off.data_ptr()
-        a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
-        a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
-        a.rel_labels_sorted, a.triple_sorted = out["labels"].data_ptr(), out["triple"].data_ptr()
-        stream = torch.cuda.current_stream(device)
-        native.check(lib.veto_postprocess(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a),
-                                          ctypes.c_void_p(self._workspace.data_ptr()), self._workspace.numel()))
-        for t in (rel, obj, pairs, obj_off, pair_off):
-            t.record_stream(stream)
+        off = native.device_offsets(n_objs, n_pairs, device=device)   # no host-blocking H2D copy in the steady state
+        out, reg_boxes = self._outputs(obj, boxes, n_pair, rel.shape[1])
+        a = call.args(native.VetoPostArgs, n_img=len(boxes), n_obj=n_obj, n_pair=n_pair, n_rel_cls=rel.shape[1],
+                      n_obj_cls=obj.shape[1], max_pairs_per_image=max(n_pairs), rel_logits=rel, rel_pairs=pairs,
+                      img_obj_offset=off[0], img_pair_offset=off[1], **self._shared_fields(obj, out, reg_boxes))
+        ws = call.workspace(call.lib.veto_postprocess_workspace_bytes(n_pair, rel.shape[1]))
+        call.run("veto_postprocess", ctypes.byref(a), ws.data_ptr(), ws.numel())
         self.last_triple_scores = out["triple"].split(n_pairs)
-        results = []
         regs = reg_boxes.split(n_objs) if reg_boxes is not None else [None] * len(boxes)
-        for box, reg, sc, pr, prob, pidx, lab in zip(boxes, regs, out["obj_scores"].split(n_objs), out["obj_pred"].split(n_objs),
-                                                     out["prob"].split(n_pairs), out["pairs"].split(n_pairs),
-                                                     out["labels"].split(n_pairs)):
-            box = self._result_box(box, reg)
-            box.add_field("pred_labels", pr)       # inference.py:431-432 (the GT-box branch re-uses `box`)
-            box.add_field("pred_scores", sc)
-            box.add_field("rel_pair_idxs", pidx)   # :450-452
-            box.add_field("pred_rel_scores", prob)
-            box.add_field("pred_rel_labels", lab)
-            results.append(box)
-        return results
-
+        return [self._fill(box, reg, sc, pr, pidx, prob, lab)    # inference.py:431-432 (the GT-box branch re-uses `box`), :450-452
+                for box, reg, sc, pr, pidx, prob, lab in zip(boxes, regs, out["obj_scores"].split(n_objs), out["obj_pred"].split(n_objs),
+                                                             out["pairs"].split(n_pairs), out["prob"].split(n_pairs),
+                                                             out["labels"].split(n_pairs))]
 
     def _forward_meet(self, relation_logits, refine_logits, rel_pair_idxs, boxes, incre_idx_list):
         if incre_idx_list is None:
@@ -105,52 +72,9 @@ class PostProcessor(nn.Module):
         if len(boxes) != 1:
             raise ValueError("the MEET merge (inference.py:303-306) pairs the batch-wide group logits with the first "
                              "image only; call it with one image per batch, got %d" % len(boxes))
-        lib = native.load_library()
         keys = ["group_%d" % k for k in range(len(relation_logits))]
-        device = relation_logits[keys[0]].device
-        if device.type != "cuda":
-            raise RuntimeError("veto_amd.PostProcessor runs only on a HIP device (got %s)" % device)
-        f32 = dict(device=device, dtype=torch.float32)
-        groups = [relation_logits[k].detach().to(**f32).contiguous() for k in keys]
-        obj = (refine_logits[0] if isinstance(refine_logits, (list, tuple)) else refine_logits).detach().to(**f32).contiguous()
-        pairs = rel_pair_idxs[0].reshape(-1, 2).to(device=device, dtype=torch.int64).contiguous()
-        n_obj, n_pair, K, n_rel = obj.shape[0], pairs.shape[0], len(groups), len(incre_idx_list)
-        total = K * n_pair
-        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes[:1])
-        out = {"obj_scores": obj_scores, "obj_pred": obj_pred,
-               "prob": torch.empty((total, n_rel), **f32), "pairs": torch.empty((total, 2), dtype=torch.int64, device=device),
-               "labels": torch.empty(total, dtype=torch.int64, device=device), "triple": torch.empty(total, **f32)}
-        need = lib.veto_postprocess_workspace_bytes(total, n_rel)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        ptrs = (ctypes.c_void_p * K)(*[g.data_ptr() for g in groups])
-        widths = (ctypes.c_int32 * K)(*[g.shape[1] for g in groups])
-        incre = (ctypes.c_int32 * n_rel)(*[int(x) for x in incre_idx_list])
-        a = native.VetoPostMeetArgs()
-        a.struct_size = ctypes.sizeof(native.VetoPostMeetArgs)
-        a.n_obj, a.n_pair, a.n_groups, a.n_rel_cls, a.n_obj_cls = n_obj, n_pair, K, n_rel, obj.shape[1]
-        a.group_logits = ctypes.cast(ptrs, ctypes.c_void_p)
-        a.group_widths = ctypes.cast(widths, ctypes.c_void_p)
-        a.incre_idx_list = ctypes.cast(incre, ctypes.c_void_p)
-        a.obj_logits = obj.data_ptr() if reg_boxes is None else None
-        a.rel_pairs = pairs.data_ptr()
-        a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
-        a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
-        a.rel_labels_sorted, a.triple_sorted = out["labels"].data_ptr(), out["triple"].data_ptr()
-        stream = torch.cuda.current_stream(device)
-        native.check(lib.veto_postprocess_meet(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a),
-                                               ctypes.c_void_p(self._workspace.data_ptr()), self._workspace.numel()))
-        for t in groups + [obj, pairs]:
-            t.record_stream(stream)
-        self.last_triple_scores = [out["triple"]]
-        box = self._result_box(boxes[0], reg_boxes)
-        box.add_field("pred_labels", out["obj_pred"])
-        box.add_field("pred_scores", out["obj_scores"])
-        box.add_field("rel_pair_idxs", out["pairs"].to(torch.float32))  # torch.zeros(total, 2) in the reference (:381)
-        box.add_field("pred_rel_scores", out["prob"])
-        box.add_field("pred_rel_labels", out["labels"])                 # group-local labels, as the reference (:388)
-        return [box]
-
+        return self._forward_groups(relation_logits, keys, 1, refine_logits, rel_pair_idxs, boxes, incre_idx_list,
+                                    native.VetoPostMeetArgs, "veto_postprocess_meet", "group_logits")
 
     def _forward_vote(self, relation_logits, refine_logits, rel_pair_idxs, boxes, incre_idx_list):
         if incre_idx_list is None:
@@ -163,56 +87,72 @@ class PostProcessor(nn.Module):
             raise ValueError("ENSEMBLE_LEARNING.VOTING must be 'C' or 'U', got %r" % voting)
         if len(relation_logits) % 3:
             raise ValueError("expected three expert heads per group, got %d heads" % len(relation_logits))
-        lib = native.load_library()
-        K = len(relation_logits) // 3
-        keys = ["group_%d%d" % (k, e + 1) for k in range(K) for e in range(3)]
+        keys = ["group_%d%d" % (k, e + 1) for k in range(len(relation_logits) // 3) for e in range(3)]
+        return self._forward_groups(relation_logits, keys, 3, refine_logits, rel_pair_idxs, boxes, incre_idx_list,
+                                    native.VetoPostVoteArgs, "veto_postprocess_vote", "expert_logits",
+                                    voting=0 if voting == "C" else 1)
+
+    def _forward_groups(self, relation_logits, keys, per_group, refine_logits, rel_pair_idxs, boxes, incre_idx_list, struct_cls,
+                        entry, heads_field, voting=None):
+        """The MEET merge (per_group 1) and the expert vote (per_group 3, `voting` set) of the first image: K groups of
+        per_group heads each.  The vote's row count is data dependent and is read back; the merge keeps all K * n_pair rows."""
         device = relation_logits[keys[0]].device
-        if device.type != "cuda":
-            raise RuntimeError("veto_amd.PostProcessor runs only on a HIP device (got %s)" % device)
-        f32 = dict(device=device, dtype=torch.float32)
-        heads = [relation_logits[k].detach().to(**f32).contiguous() for k in keys]
-        obj = (refine_logits[0] if isinstance(refine_logits, (list, tuple)) else refine_logits).detach().to(**f32).contiguous()
+        call = native.Launch(device, "veto_amd.PostProcessor runs only on a HIP device")
+        heads = [relation_logits[k].detach().to(device=device, dtype=torch.float32).contiguous() for k in keys]
+        obj = (refine_logits[0] if isinstance(refine_logits, (list, tuple)) else refine_logits)
+        obj = obj.detach().to(device=device, dtype=torch.float32).contiguous()
         pairs = rel_pair_idxs[0].reshape(-1, 2).to(device=device, dtype=torch.int64).contiguous()
-        n_obj, n_pair, n_rel = obj.shape[0], pairs.shape[0], len(incre_idx_list)
-        total = K * n_pair
-        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes[:1])
-        out = {"obj_scores": obj_scores, "obj_pred": obj_pred,
-               "prob": torch.empty((total, n_rel), **f32), "pairs": torch.empty((total, 2), dtype=torch.int64, device=device),
-               "labels": torch.empty(total, dtype=torch.int64, device=device), "triple": torch.empty(total, **f32),
-               "kept": torch.zeros(1, dtype=torch.int32, device=device)}
-        need = lib.veto_postprocess_workspace_bytes(total, n_rel)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-        ptrs = (ctypes.c_void_p * (3 * K))(*[h.data_ptr() for h in heads])
-        widths = (ctypes.c_int32 * K)(*[heads[3 * k].shape[1] for k in range(K)])
+        K, n_rel = len(heads) // per_group, len(incre_idx_list)
+        total = K * pairs.shape[0]
+        out, reg_boxes = self._outputs(obj, boxes[:1], total, n_rel)
+        fields = self._shared_fields(obj, out, reg_boxes)
+        kept = None
+        if voting is not None:
+            kept = torch.zeros(1, dtype=torch.int32, device=device)
+            fields.update(voting=voting, kept_count=kept)
+        # host arrays: the ABI reads them before it returns
+        ptrs = (ctypes.c_void_p * len(heads))(*[call.ptr(h) for h in heads])
+        widths = (ctypes.c_int32 * K)(*[heads[per_group * k].shape[1] for k in range(K)])
         incre = (ctypes.c_int32 * n_rel)(*[int(x) for x in incre_idx_list])
-        a = native.VetoPostVoteArgs()
-        a.struct_size = ctypes.sizeof(native.VetoPostVoteArgs)
-        a.n_obj, a.n_pair, a.n_groups, a.n_rel_cls, a.n_obj_cls = n_obj, n_pair, K, n_rel, obj.shape[1]
-        a.voting = 0 if voting == "C" else 1
-        a.expert_logits = ctypes.cast(ptrs, ctypes.c_void_p)
-        a.group_widths = ctypes.cast(widths, ctypes.c_void_p)
-        a.incre_idx_list = ctypes.cast(incre, ctypes.c_void_p)
-        a.obj_logits = obj.data_ptr() if reg_boxes is None else None
-        a.rel_pairs = pairs.data_ptr()
-        a.obj_scores, a.obj_pred = out["obj_scores"].data_ptr(), out["obj_pred"].data_ptr()
-        a.rel_prob_sorted, a.rel_pairs_sorted = out["prob"].data_ptr(), out["pairs"].data_ptr()
-        a.rel_labels_sorted, a.triple_sorted = out["labels"].data_ptr(), out["triple"].data_ptr()
-        a.kept_count = out["kept"].data_ptr()
-        stream = torch.cuda.current_stream(device)
-        native.check(lib.veto_postprocess_vote(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a),
-                                               ctypes.c_void_p(self._workspace.data_ptr()), self._workspace.numel()))
-        for t in heads + [obj, pairs]:
-            t.record_stream(stream)
-        kept = int(out["kept"].item())   # the one device read-back: the result's row count is data dependent
-        self.last_triple_scores = [out["triple"][:kept]]
-        box = self._result_box(boxes[0], reg_boxes)
-        box.add_field("pred_labels", out["obj_pred"])
-        box.add_field("pred_scores", out["obj_scores"])
-        box.add_field("rel_pair_idxs", out["pairs"][:kept].to(torch.float32))  # float, as the reference (:267)
-        box.add_field("pred_rel_scores", out["prob"][:kept])
-        box.add_field("pred_rel_labels", out["labels"][:kept])                 # group-local labels
-        return [box]
+        fields[heads_field] = ctypes.cast(ptrs, ctypes.c_void_p)
+        a = call.args(struct_cls, n_obj=obj.shape[0], n_pair=pairs.shape[0], n_groups=K, n_rel_cls=n_rel, n_obj_cls=obj.shape[1],
+                      group_widths=ctypes.cast(widths, ctypes.c_void_p), incre_idx_list=ctypes.cast(incre, ctypes.c_void_p),
+                      rel_pairs=pairs, **fields)
+        ws = call.workspace(call.lib.veto_postprocess_workspace_bytes(total, n_rel))
+        call.run(entry, ctypes.byref(a), ws.data_ptr(), ws.numel())
+        rows = slice(None)
+        if kept is not None:
+            rows = slice(int(kept.item()))   # the one device read-back: the result's row count is data dependent
+        self.last_triple_scores = [out["triple"][rows]]
+        # float pair indices (torch.zeros(total, 2) in the reference, inference.py:381 / :267) and group-local labels (:388)
+        return [self._fill(boxes[0], reg_boxes, out["obj_scores"], out["obj_pred"], out["pairs"][rows].to(torch.float32),
+                           out["prob"][rows], out["labels"][rows])]
+
+    def _outputs(self, obj, boxes, rows, n_rel):
+        """(the output tensors of `rows` relation rows, the regressed boxes or None)."""
+        device = obj.device
+        obj_pred, obj_scores, reg_boxes = self._decode_objects(obj, boxes)
+        return {"obj_scores": obj_scores, "obj_pred": obj_pred,
+                "prob": torch.empty((rows, n_rel), dtype=torch.float32, device=device),
+                "pairs": torch.empty((rows, 2), dtype=torch.int64, device=device),
+                "labels": torch.empty(rows, dtype=torch.int64, device=device),
+                "triple": torch.empty(rows, dtype=torch.float32, device=device)}, reg_boxes
+
+    @staticmethod
+    def _shared_fields(obj, out, reg_boxes):
+        """The struct fields the three entry points have in common.  sgdet: labels / scores are the decoder's (obj_logits NULL)."""
+        return dict(obj_logits=obj if reg_boxes is None else None, obj_scores=out["obj_scores"], obj_pred=out["obj_pred"],
+                    rel_prob_sorted=out["prob"], rel_pairs_sorted=out["pairs"], rel_labels_sorted=out["labels"],
+                    triple_sorted=out["triple"])
+
+    def _fill(self, box, reg, obj_scores, obj_pred, pair_idxs, prob, labels):
+        box = self._result_box(box, reg)
+        box.add_field("pred_labels", obj_pred)
+        box.add_field("pred_scores", obj_scores)
+        box.add_field("rel_pair_idxs", pair_idxs)
+        box.add_field("pred_rel_scores", prob)
+        box.add_field("pred_rel_labels", labels)
+        return box
 
     def _decode_objects(self, obj_logits, boxes):
         """(obj_pred, obj_scores, regressed boxes) of the concatenated images.  GT boxes: two empty outputs that the

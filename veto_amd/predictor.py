@@ -166,20 +166,10 @@ def _build_trunk(m, config, num_obj_cls, with_embed2):
 _TRUNK_KEYS = None
 
 
-_OFFSET_CACHE = {}
-
-
 def cached_offsets(n_objs, n_pairs, device):
-    """Per-image exclusive prefix sums (objects, pairs) as int32 device tensors.  torch.tensor(list, device=...) is a
-    synchronous pageable H2D copy that stalls the host behind all queued GPU work, so batch shapes seen before (the
-    common case in an eval loop) re-use their tensors.  Shared by the predictor, the PostProcessor and the evaluator."""
-    key = (tuple(n_objs), tuple(n_pairs), str(device))
-    hit = _OFFSET_CACHE.get(key)
-    if hit is None:
-        if len(_OFFSET_CACHE) >= 256:
-            _OFFSET_CACHE.clear()
-        hit = _OFFSET_CACHE[key] = _offset_tensors(tuple(n_objs), tuple(n_pairs), device)
-    return hit
+    """Per-image exclusive prefix sums (objects, pairs) as int32 device tensors: two rows of native.device_offsets."""
+    off = native.device_offsets(n_objs, n_pairs, device=device)
+    return off[0], off[1]
 
 
 class _NativeForward:
@@ -255,16 +245,12 @@ class _NativeForward:
             self._uploaded = ver
         return self._engine
 
-    def _offsets(self, n_objs, n_pairs, device):
-        return cached_offsets(n_objs, n_pairs, device)
-
     def _train_opts(self):
         """Dropout probabilities of the three sites the training path implements, read from the mirror modules (so that
         `module.p = 0` behaves as in torch), plus a fresh seed drawn from torch's generator."""
         t = self._trunk
         tr = t.fusion_transformer.transformer
-        o = native.VetoTrainOpts()
-        o.struct_size = ctypes.sizeof(native.VetoTrainOpts)
+        o = native.VetoTrainOpts(struct_size=ctypes.sizeof(native.VetoTrainOpts))
         o.p_pos = float(t.pos_embed[3].p)
         o.p_emb = float(tr.pos_drop.p)
         ps = {float(layer[0].fn.to_out[1].p) for layer in tr.layers}
@@ -297,47 +283,39 @@ class _NativeForward:
         return out
 
     def _prepare_inputs(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits, bn_batch_stats=None):
-        """Validates the call and flattens it into a veto_inputs_t.  Returns (inp, keep, n_objs, n_pairs, device, eng);
-        `keep` are the tensors the struct points into."""
+        """Validates the call and flattens it into a veto_inputs_t.  Returns (call, inp, n_objs, n_pairs, eng); `call` keeps the
+        tensors the struct points into."""
         device = roi_features.device
         eng = self._ensure_engine(device)
+        call = native.Launch(device, "veto_amd: the predictor runs only on a HIP device")
         n_objs = [len(p) for p in proposals]
         n_pairs = [int(p.shape[0]) for p in rel_pair_idxs]
-        n_obj, n_pair = sum(n_objs), sum(n_pairs)
         if tuple(roi_features.shape[1:]) != (256, 8, 8) or tuple(roi_depth_features.shape[1:]) != (256, 8, 8):
             raise ValueError("roi features must be [N, 256, 8, 8], got %s / %s"
                              % (tuple(roi_features.shape), tuple(roi_depth_features.shape)))
-        if roi_features.shape[0] != n_obj or roi_depth_features.shape[0] != n_obj:
-            raise ValueError("roi feature rows (%d) != total proposals (%d)" % (roi_features.shape[0], n_obj))
+        if roi_features.shape[0] != sum(n_objs) or roi_depth_features.shape[0] != sum(n_objs):
+            raise ValueError("roi feature rows (%d) != total proposals (%d)" % (roi_features.shape[0], sum(n_objs)))
         f32 = dict(device=device, dtype=torch.float32)
         rgb = roi_features.detach().to(**f32).contiguous()
         dep = roi_depth_features.detach().to(**f32).contiguous()
         boxes = torch.cat([p.bbox for p in proposals], 0).to(**f32).contiguous()
-        mode = proposals[0].mode
         pairs = torch.cat([p.reshape(-1, 2) for p in rel_pair_idxs], 0).to(device=device, dtype=torch.int64).contiguous()
-        obj_off, pair_off = self._offsets(tuple(n_objs), tuple(n_pairs), device)
+        off = native.device_offsets(n_objs, n_pairs, device=device)
         lab = labels.to(device=device, dtype=torch.int64).contiguous() if labels is not None else None
         lg = logits.detach().to(**f32).contiguous() if logits is not None else None
-        inp = native.VetoInputs()
-        inp.struct_size = ctypes.sizeof(native.VetoInputs)
-        inp.n_obj, inp.n_pair, inp.n_img = n_obj, n_pair, len(proposals)
-        inp.roi_rgb, inp.roi_depth, inp.boxes = rgb.data_ptr(), dep.data_ptr(), boxes.data_ptr()
-        inp.box_mode = 0 if mode == "xyxy" else 1
-        inp.obj_labels = lab.data_ptr() if lab is not None else None
-        inp.obj_logits = lg.data_ptr() if lg is not None else None
-        inp.rel_pairs = pairs.data_ptr()
-        inp.img_obj_offset, inp.img_pair_offset = obj_off.data_ptr(), pair_off.data_ptr()
-        inp.bn_batch_stats = bn_batch_stats.data_ptr() if bn_batch_stats is not None else None
-        keep = [t for t in (rgb, dep, boxes, pairs, lab, lg, obj_off, pair_off, bn_batch_stats) if t is not None]
-        return inp, keep, n_objs, n_pairs, device, eng
+        inp = call.args(native.VetoInputs, n_obj=sum(n_objs), n_pair=sum(n_pairs), n_img=len(proposals), roi_rgb=rgb, roi_depth=dep,
+                        boxes=boxes, box_mode=0 if proposals[0].mode == "xyxy" else 1, obj_labels=lab, obj_logits=lg, rel_pairs=pairs,
+                        img_obj_offset=off[0], img_pair_offset=off[1], bn_batch_stats=bn_batch_stats)
+        return call, inp, n_objs, n_pairs, eng
 
     def _run_native(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits,
                     debug=False, bn_batch_stats=None):
-        inp, keep, n_objs, n_pairs, device, eng = self._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
-                                                                       labels, logits, bn_batch_stats)
-        n_obj, n_pair = inp.n_obj, inp.n_pair
+        call, inp, n_objs, n_pairs, eng = self._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
+                                                               labels, logits, bn_batch_stats)
+        device, n_pair = call.device, inp.n_pair
         f32 = dict(device=device, dtype=torch.float32)
-        need = eng.workspace_bytes(n_obj, n_pair)
+        # the workspace follows the module's lifetime (it is large), not the shared per-stream cache
+        need = eng.workspace_bytes(inp.n_obj, n_pair)
         if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
             self._workspace = None
             self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
@@ -348,19 +326,14 @@ class _NativeForward:
                       "obj_inds": torch.empty(n_pair, dtype=torch.int64, device=device),
                       "tokens": torch.empty((n_pair, 19, 576), **f32),
                       "cls": torch.empty((n_pair, 576), **f32)}
-            dbg = native.VetoDebugOutputs()
-            dbg.struct_size = ctypes.sizeof(native.VetoDebugOutputs)
-            dbg.subj_inds, dbg.obj_inds = extras["subj_inds"].data_ptr(), extras["obj_inds"].data_ptr()
-            dbg.tokens, dbg.cls = extras["tokens"].data_ptr(), extras["cls"].data_ptr()
-        stream = torch.cuda.current_stream(device).cuda_stream
+            dbg = call.args(native.VetoDebugOutputs, **extras)
+        stream = call.stream.cuda_stream
         # (the audit is of the VETO_MIXED operands: the ABI refuses it on a handle that computes in another mode)
         if self._count_saturation and self._precision == native.VETO_MIXED and bn_batch_stats is None and not debug:
             self.last_saturation = eng.forward_saturation(stream, inp, self._workspace.data_ptr(), self._workspace.numel(), out.data_ptr())
         else:
             eng.forward(stream, inp, self._workspace.data_ptr(), self._workspace.numel(), out.data_ptr(), dbg)
-        # the inputs above are referenced by enqueued kernels: keep them alive on this stream
-        for t in keep:
-            t.record_stream(torch.cuda.current_stream(device))
+        call.record()
         self.last_debug = extras
         return out, n_objs, n_pairs
 
@@ -404,11 +377,10 @@ class _TrainFn(torch.autograd.Function):
         proposals, rel_pair_idxs, labels, obj_logits = call
         device = roi_features.device
         stats = torch.empty(12, dtype=torch.float32, device=device)
-        inp, keep, n_objs, n_pairs, device, eng = owner._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
-                                                                        labels, obj_logits, stats)
-        lib = native.load_library()
+        launch, inp, n_objs, n_pairs, eng = owner._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
+                                                                labels, obj_logits, stats)
         opts = owner._train_opts()
-        need = lib.veto_train_workspace_bytes(eng.handle, inp.n_obj, inp.n_pair)
+        need = launch.lib.veto_train_workspace_bytes(eng.handle, inp.n_obj, inp.n_pair)
         # tens of GB: keep one workspace on the module and hand it to the next step once its backward has run (an
         # allocation of this size goes to the driver every time, and releasing it synchronises the device)
         # The cached workspace belongs to at most one forward whose backward has not run yet.  Ownership is a token held by
@@ -427,9 +399,7 @@ class _TrainFn(torch.autograd.Function):
             ctx.ws_token = _WsToken()
             owner.__dict__["_train_ws_owner"] = weakref.ref(ctx.ws_token)
         out = torch.empty((inp.n_pair, owner._num_out), dtype=torch.float32, device=device)
-        stream = torch.cuda.current_stream(device)
-        native.check(lib.veto_forward_train(eng.handle, ctypes.c_void_p(stream.cuda_stream), ctypes.byref(inp), ctypes.byref(opts),
-                                            ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(out.data_ptr())))
+        launch.run("veto_forward_train", ctypes.byref(inp), ctypes.byref(opts), ws.data_ptr(), ws.numel(), out.data_ptr(), handle=eng.handle)
         ctx.opts = opts
         bn = owner._trunk.pos_embed[0]
         with torch.no_grad():    # nn.BatchNorm1d(momentum=0.001) running statistics
@@ -437,29 +407,26 @@ class _TrainFn(torch.autograd.Function):
             bn.running_mean.mul_(1 - m).add_(stats[0:4].to(bn.running_mean.device), alpha=m)
             bn.running_var.mul_(1 - m).add_(stats[8:12].to(bn.running_var.device), alpha=m)
             bn.num_batches_tracked += 1
-        ctx.owner, ctx.inp, ctx.keep, ctx.ws, ctx.eng = owner, inp, keep, ws, eng
+        ctx.owner, ctx.inp, ctx.launch, ctx.ws, ctx.eng = owner, inp, launch, ws, eng   # (launch: the tensors `inp` points into)
         ctx.spec = owner._train_param_spec()
         return out
 
     @staticmethod
     def backward(ctx, dlogits):
-        owner, eng, lib = ctx.owner, ctx.eng, native.load_library()
+        owner, eng = ctx.owner, ctx.eng
         device = dlogits.device
+        launch = native.Launch(device, "veto_amd: the predictor runs only on a HIP device")
         dlogits = dlogits.detach().to(torch.float32).contiguous()
-        n_floats = lib.veto_grad_floats(eng.handle)
-        flat = torch.empty(n_floats, dtype=torch.float32, device=device)
-        stream = torch.cuda.current_stream(device)
+        flat = torch.empty(launch.lib.veto_grad_floats(eng.handle), dtype=torch.float32, device=device)
         d_rgb = d_dep = None
         n_obj = ctx.inp.n_obj
         if ctx.needs_input_grad[2]:
             d_rgb = torch.empty((n_obj, 256, 8, 8), dtype=torch.float32, device=device)
         if ctx.needs_input_grad[3]:
             d_dep = torch.empty((n_obj, 256, 8, 8), dtype=torch.float32, device=device)
-        ctx.opts.d_roi_rgb = d_rgb.data_ptr() if d_rgb is not None else None
-        ctx.opts.d_roi_depth = d_dep.data_ptr() if d_dep is not None else None
-        native.check(lib.veto_backward(eng.handle, ctypes.c_void_p(stream.cuda_stream), ctypes.byref(ctx.inp), ctypes.byref(ctx.opts),
-                                       ctypes.c_void_p(ctx.ws.data_ptr()), ctx.ws.numel(), ctypes.c_void_p(dlogits.data_ptr()),
-                                       ctypes.c_void_p(flat.data_ptr())))
+        ctx.opts.d_roi_rgb, ctx.opts.d_roi_depth = launch.ptr(d_rgb), launch.ptr(d_dep)
+        launch.run("veto_backward", ctypes.byref(ctx.inp), ctypes.byref(ctx.opts), ctx.ws.data_ptr(), ctx.ws.numel(),
+                 launch.ptr(dlogits), flat.data_ptr(), handle=eng.handle)
         if ctx.ws_token is not None:
             ctx.ws_token.done = True
         offsets = eng.weight_offsets()
@@ -473,19 +440,6 @@ class _TrainFn(torch.autograd.Function):
                 g = flat[off + row0 * per_row: off + (row0 + rows) * per_row]
             grads.append(g.view_as(prm).to(prm.device))
         return (None, None, d_rgb, d_dep) + tuple(grads)
-
-
-def _offset_tensors(n_objs, n_pairs, device):
-    obj_off = torch.tensor([0] + list(_cumsum(n_objs)), dtype=torch.int32, device=device)
-    pair_off = torch.tensor([0] + list(_cumsum(n_pairs)), dtype=torch.int32, device=device)
-    return obj_off, pair_off
-
-
-def _cumsum(xs):
-    s = 0
-    for x in xs:
-        s += x
-        yield s
 
 
 def _cat_field(proposals, name):

@@ -13,9 +13,6 @@ from torch import nn
 
 from . import native
 from .boxhead import BoxCoder, _image_sizes
-from .predictor import cached_offsets
-
-_WORKSPACE = {}   # (device, stream) -> workspace: launches on different streams never share one
 
 
 def _check_shapes(objectness, box_regression, anchors, image_sizes, pre_nms_top_n):
@@ -59,9 +56,7 @@ def rpn_proposals_padded(objectness, box_regression, anchors, image_sizes, *, pr
     whose rows are too few reports -(rows needed) and leaves its rows as they were (`out`: the tensors to write into)."""
     n_img, shapes = _check_shapes(objectness, box_regression, anchors, image_sizes, pre_nms_top_n)
     device = objectness[0].device
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd RPN proposal selection runs on a HIP device only (got %s)" % device)
-    lib = native.load_library()
+    call = native.Launch(device, "veto_amd RPN proposal selection runs on a HIP device only")
     if fpn_post_nms_top_n is None:
         fpn_post_nms_top_n = post_nms_top_n
     f32 = dict(device=device, dtype=torch.float32)
@@ -72,38 +67,25 @@ def rpn_proposals_padded(objectness, box_regression, anchors, image_sizes, *, pr
     if rows_per_image is None:
         rows_per_image = [_row_bound(shapes, pre_nms_top_n, post_nms_top_n, nms_thresh, fpn_post_nms_top_n)] * n_img
     rows_per_image = [int(r) for r in rows_per_image]
-    _, out_off = cached_offsets([0] * n_img, rows_per_image, device)
     rows = sum(rows_per_image)
     if out is None:
         out = dict(boxes=torch.empty((rows, 4), **f32), objectness=torch.empty(rows, **f32),
                    level=torch.empty(rows, dtype=torch.int32, device=device),
                    anchor_index=torch.empty(rows, dtype=torch.int64, device=device))
     counts = torch.empty(n_img, dtype=torch.int32, device=device)
-    a = native.VetoRpnArgs()
-    a.struct_size = ctypes.sizeof(native.VetoRpnArgs)
-    a.n_img, a.n_lvl = n_img, len(shapes)
-    a.pre_nms_top_n, a.post_nms_top_n, a.fpn_post_nms_top_n = int(pre_nms_top_n), int(post_nms_top_n), int(fpn_post_nms_top_n)
-    a.per_batch = int(bool(per_batch))
-    a.nms_thresh, a.min_size, a.bbox_xform_clip = float(nms_thresh), float(min_size), float(bbox_xform_clip)
-    a.reg_weights = (ctypes.c_float * 4)(*[float(w) for w in weights])
+    a = call.args(native.VetoRpnArgs, n_img=n_img, n_lvl=len(shapes), pre_nms_top_n=int(pre_nms_top_n),
+                  post_nms_top_n=int(post_nms_top_n), fpn_post_nms_top_n=int(fpn_post_nms_top_n), per_batch=int(bool(per_batch)),
+                  nms_thresh=float(nms_thresh), min_size=float(min_size), bbox_xform_clip=float(bbox_xform_clip),
+                  reg_weights=(ctypes.c_float * 4)(*[float(w) for w in weights]), image_sizes=sizes,
+                  img_out_offset=native.device_offsets(rows_per_image, device=device)[0], boxes=out["boxes"],
+                  objectness_out=out["objectness"], level=out["level"], anchor_index=out["anchor_index"], counts=counts)
     for l, (A, H, W) in enumerate(shapes):
         a.level_a[l], a.level_h[l], a.level_w[l] = A, H, W
-        a.objectness[l], a.box_regression[l], a.anchors[l] = objectness[l].data_ptr(), box_regression[l].data_ptr(), anchors[l].data_ptr()
-    a.image_sizes, a.img_out_offset = sizes.data_ptr(), out_off.data_ptr()
-    a.boxes, a.objectness_out = out["boxes"].data_ptr(), out["objectness"].data_ptr()
-    a.level, a.anchor_index, a.counts = out["level"].data_ptr(), out["anchor_index"].data_ptr(), counts.data_ptr()
-    stream = torch.cuda.current_stream(device)
-    need = lib.veto_rpn_proposals_workspace_bytes(ctypes.byref(a))
-    if need == 0:   # the shapes are out of range: the call below says which
-        need = 256
-    key = (str(device), stream.cuda_stream)
-    ws = _WORKSPACE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=device)
-    native.check(lib.veto_rpn_proposals(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()), ws.numel()))
+        a.objectness[l], a.box_regression[l], a.anchors[l] = call.ptr(objectness[l]), call.ptr(box_regression[l]), call.ptr(anchors[l])
+    need = call.lib.veto_rpn_proposals_workspace_bytes(ctypes.byref(a))   # (0: the shapes are out of range, the call says which)
+    ws = call.workspace(need)
+    call.run("veto_rpn_proposals", ctypes.byref(a), ws.data_ptr(), ws.numel())
     kept = counts.tolist()   # the one device->host copy of the batch: the counts decide the split
-    for t in objectness + box_regression + anchors + [sizes, out_off, ws]:
-        t.record_stream(stream)
     return rows_per_image, out, kept
 
 

@@ -21,31 +21,6 @@ import torch
 
 from . import native
 
-_OFFSETS = {}     # batch shape -> int32 offset tensor on the device
-_WORKSPACE = {}   # (device, stream) -> workspace: launches on different streams never share one
-
-
-def _prefix_sums(sizes):
-    acc, row = 0, [0]
-    for v in sizes:
-        acc += v
-        row.append(acc)
-    return row
-
-
-def _offsets(n_prp, n_tgt, device):
-    """[4, n_img + 1] int32 prefix sums of P_i, T_i, T_i^2, P_i^2, cached per batch shape (a pageable H2D copy stalls the
-    host behind the queued GPU work, as predictor.cached_offsets notes)."""
-    key = (tuple(n_prp), tuple(n_tgt), str(device))
-    hit = _OFFSETS.get(key)
-    if hit is None:
-        if len(_OFFSETS) >= 256:
-            _OFFSETS.clear()
-        rows = [_prefix_sums(sizes) for sizes in (n_prp, n_tgt, [t * t for t in n_tgt], [p * p for p in n_prp])]
-        hit = _OFFSETS[key] = torch.tensor(rows, dtype=torch.int32, device=device)
-    return hit
-
-
 class DetectRelationSampler:
     def __init__(self, fg_thres, require_overlap, num_sample_per_gt_rel, batch_size_per_image, positive_fraction):
         self.fg_thres = float(fg_thres)
@@ -69,16 +44,14 @@ class DetectRelationSampler:
         seed: 64-bit; None draws one from torch's default generator, so torch.manual_seed makes a run reproducible."""
         if len(proposals) != len(targets) or not proposals:
             raise ValueError("detect_relsample needs one target per proposal list (got %d and %d)" % (len(proposals), len(targets)))
-        device = proposals[0].bbox.device
-        if device.type != "cuda":
-            raise RuntimeError("veto_amd detect_relsample runs on a HIP device only (got %s)" % device)
         has_nm = [t.has_field("relation_non_masked") for t in targets]
         if any(has_nm) and not all(has_nm):
             raise ValueError("'relation_non_masked' must be on every target or on none")
         has_nm = all(has_nm)
+        device = proposals[0].bbox.device
+        call = native.Launch(device, "veto_amd detect_relsample runs on a HIP device only")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())   # the CPU generator: no device synchronisation
-        lib = native.load_library()
         n_prp = [len(p) for p in proposals]
         n_tgt = [len(t) for t in targets]
         n_img, k, B = len(proposals), self.num_sample_per_gt_rel, self.batch_size_per_image
@@ -103,42 +76,24 @@ class DetectRelationSampler:
                 raise ValueError("a target's 'relation' must be [%d, %d], got %s" % (n, n, tuple(t.get_field("relation").shape)))
             if has_nm and tuple(t.get_field("relation_non_masked").shape) != (n, n):
                 raise ValueError("a target's 'relation_non_masked' must be [%d, %d]" % (n, n))
-        off = _offsets(n_prp, n_tgt, device)
+        # prefix sums of P_i, T_i, T_i^2, P_i^2
+        off = native.device_offsets(n_prp, n_tgt, [t * t for t in n_tgt], [p * p for p in n_prp], device=device)
         pairs = torch.empty((n_img * rows, 2), **i64)
         labels = torch.empty(n_img * rows, **i64)
         labels_all = torch.empty(n_cells * k + n_img * rows, **i64) if has_nm else None
         binary = torch.empty(sum(p * p for p in n_prp), **i64)
         locating = torch.empty(sum(n_prp), **f32)
         counts = torch.empty((n_img, 4), dtype=torch.int32, device=device)
-        need = lib.veto_detect_relsample_workspace_bytes(n_cells, k)
-        stream = torch.cuda.current_stream(device)
-        key = (str(device), stream.cuda_stream)
-        ws = _WORKSPACE.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _WORKSPACE[key] = torch.empty(need, dtype=torch.uint8, device=device)
-
-        a = native.VetoDetectRelsampleArgs()
-        a.struct_size = ctypes.sizeof(native.VetoDetectRelsampleArgs)
-        a.n_img, a.n_prp, a.n_tgt, a.n_rel_cells = n_img, sum(n_prp), sum(n_tgt), n_cells
-        a.max_prp_per_image, a.max_tgt_per_image = max(n_prp), max(n_tgt)
-        a.require_overlap, a.num_sample_per_gt_rel = int(self.require_overlap), k
-        a.batch_size_per_image, a.max_fg_per_image = B, self.num_pos_per_img
-        a.fg_thres, a.seed = self.fg_thres, seed & (2 ** 64 - 1)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None and t.numel() else None
-
-        a.prp_boxes, a.prp_labels, a.prp_scores = ptr(prp_boxes), ptr(prp_labels), ptr(prp_scores)
-        a.tgt_boxes, a.tgt_labels, a.relation, a.relation_non_masked = ptr(tgt_boxes), ptr(tgt_labels), ptr(relation), ptr(rel_nm)
-        a.img_prp_offset, a.img_tgt_offset = off[0].data_ptr(), off[1].data_ptr()
-        a.img_rel_offset, a.img_binary_offset = off[2].data_ptr(), off[3].data_ptr()
-        a.pairs, a.labels, a.labels_all = pairs.data_ptr(), labels.data_ptr(), ptr(labels_all)
-        a.binary_rel, a.locating_match, a.counts = ptr(binary) or pairs.data_ptr(), ptr(locating), counts.data_ptr()
-        native.check(lib.veto_detect_relsample(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()),
-                                               ws.numel()))
-        for t in (prp_boxes, prp_labels, prp_scores, tgt_boxes, tgt_labels, relation, rel_nm, off, ws):
-            if t is not None:
-                t.record_stream(stream)
+        a = call.args(native.VetoDetectRelsampleArgs, n_img=n_img, n_prp=sum(n_prp), n_tgt=sum(n_tgt), n_rel_cells=n_cells,
+                      max_prp_per_image=max(n_prp), max_tgt_per_image=max(n_tgt), require_overlap=int(self.require_overlap),
+                      num_sample_per_gt_rel=k, batch_size_per_image=B, max_fg_per_image=self.num_pos_per_img,
+                      fg_thres=self.fg_thres, seed=seed & (2 ** 64 - 1), prp_boxes=prp_boxes, prp_labels=prp_labels,
+                      prp_scores=prp_scores, tgt_boxes=tgt_boxes, tgt_labels=tgt_labels, relation=relation,
+                      relation_non_masked=rel_nm, img_prp_offset=off[0], img_tgt_offset=off[1], img_rel_offset=off[2],
+                      img_binary_offset=off[3], pairs=pairs, labels=labels, labels_all=labels_all,
+                      binary_rel=binary if binary.numel() else pairs, locating_match=locating, counts=counts)
+        ws = call.workspace(call.lib.veto_detect_relsample_workspace_bytes(n_cells, k))
+        call.run("veto_detect_relsample", ctypes.byref(a), ws.data_ptr(), ws.numel())
         cnt = counts.tolist()   # the one device->host copy: the per-image counts split the outputs
         bad = [i for i, c in enumerate(cnt) if c[3] & 1]
         if bad:
@@ -159,21 +114,6 @@ class DetectRelationSampler:
         if not has_nm:
             rel_labels_all = rel_labels   # sampling.py:173-174
         return proposals, rel_labels, rel_labels_all, rel_pair_idxs, rel_sym_binarys
-
-
-_GT_OFFSETS = {}  # batch shape -> [2, n_img + 1] int32 offset tensor on the device
-
-
-def _gt_offsets(n_obj, device):
-    """[2, n_img + 1] int32 prefix sums of n_i and n_i^2, cached per batch shape like _offsets."""
-    key = (tuple(n_obj), str(device))
-    hit = _GT_OFFSETS.get(key)
-    if hit is None:
-        if len(_GT_OFFSETS) >= 256:
-            _GT_OFFSETS.clear()
-        rows = [_prefix_sums(sizes) for sizes in (n_obj, [n * n for n in n_obj])]
-        hit = _GT_OFFSETS[key] = torch.tensor(rows, dtype=torch.int32, device=device)
-    return hit
 
 
 class GTBoxRelationSampler:
@@ -202,35 +142,23 @@ class GTBoxRelationSampler:
             if tuple(t.get_field("relation").shape) != (n, n):
                 raise ValueError("a target's 'relation' must be [%d, %d], got %s" % (n, n, tuple(t.get_field("relation").shape)))
         device = proposals[0].bbox.device
-        if device.type != "cuda":
-            raise RuntimeError("veto_amd gtbox_relsample runs on a HIP device only (got %s)" % device)
+        call = native.Launch(device, "veto_amd gtbox_relsample runs on a HIP device only")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())   # the CPU generator: no device synchronisation
-        lib = native.load_library()
         n_img, B = len(proposals), self.batch_size_per_image
         n_cells = sum(n * n for n in n_obj)
         i64 = dict(device=device, dtype=torch.int64)
         parts = [t.get_field("relation").reshape(-1).to(**i64) for t in targets]
         relation = torch.cat(parts).contiguous()
-        off = _gt_offsets(n_obj, device)
+        off = native.device_offsets(n_obj, [n * n for n in n_obj], device=device)
         pairs = torch.empty((n_img * B, 2), **i64)
         labels = torch.empty(n_img * B, **i64)
         binary = torch.empty(n_cells, **i64)
         counts = torch.empty((n_img, 2), dtype=torch.int32, device=device)
-        stream = torch.cuda.current_stream(device)
-
-        a = native.VetoGtboxRelsampleArgs()
-        a.struct_size = ctypes.sizeof(native.VetoGtboxRelsampleArgs)
-        a.n_img, a.n_rel_cells, a.max_obj_per_image = n_img, n_cells, max(n_obj)
-        a.batch_size_per_image, a.num_pos_per_img = B, self.num_pos_per_img
-        a.seed = seed & (2 ** 64 - 1)
-        a.relation = relation.data_ptr() if n_cells else None
-        a.img_obj_offset, a.img_rel_offset = off[0].data_ptr(), off[1].data_ptr()
-        a.pairs, a.labels, a.counts = pairs.data_ptr(), labels.data_ptr(), counts.data_ptr()
-        a.binary_rel = binary.data_ptr() if n_cells else None
-        native.check(lib.veto_gtbox_relsample(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a)))
-        relation.record_stream(stream)
-        off.record_stream(stream)
+        a = call.args(native.VetoGtboxRelsampleArgs, n_img=n_img, n_rel_cells=n_cells, max_obj_per_image=max(n_obj),
+                      batch_size_per_image=B, num_pos_per_img=self.num_pos_per_img, seed=seed & (2 ** 64 - 1), relation=relation,
+                      img_obj_offset=off[0], img_rel_offset=off[1], pairs=pairs, labels=labels, binary_rel=binary, counts=counts)
+        call.run("veto_gtbox_relsample", ctypes.byref(a))
         cnt = counts.tolist()   # the one device->host copy: the per-image counts split the outputs
         ones = torch.ones(sum(n_obj), device=device)
         rel_labels, rel_idx_pairs, rel_sym_binarys = [], [], []

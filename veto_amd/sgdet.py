@@ -12,52 +12,34 @@ import ctypes
 import torch
 
 from . import native
-from .predictor import cached_offsets
 
 MODES = {"post": 0, "meet": 1}
-_WORKSPACE = {}   # (device, stream) -> workspace: launches on different streams never share one
 
 
 def decode_objects(logits, boxes_per_cls, n_objs, nms_thres, mode="post", want_scores=True, want_boxes=True):
     """logits [sum N, C] and boxes_per_cls [sum N, C, 4] (xyxy) on the HIP device; n_objs = per-image counts.
     Returns (labels int64 [sum N], scores fp32 [sum N] or None, boxes fp32 [sum N, 4] or None)."""
     device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("veto_amd sgdet decoding runs on a HIP device only (got %s)" % device)
     n_obj = int(logits.shape[0])
     n_cls = int(boxes_per_cls.shape[1])
     if tuple(boxes_per_cls.shape) != (n_obj, n_cls, 4):
         raise ValueError("boxes_per_cls must be [%d, %d, 4], got %s" % (n_obj, n_cls, tuple(boxes_per_cls.shape)))
     if sum(n_objs) != n_obj:
         raise ValueError("per-image counts %s do not add up to %d rows" % (list(n_objs), n_obj))
-    lib = native.load_library()
+    call = native.Launch(device, "veto_amd sgdet decoding runs on a HIP device only")
     f32 = dict(device=device, dtype=torch.float32)
     meet = mode == "meet"
     logits = logits.detach().to(device=device, dtype=torch.int64 if meet else torch.float32).contiguous()
     if meet and want_scores:
         raise ValueError("the MEET decoder's labels come without scores")
     boxes_per_cls = boxes_per_cls.detach().to(**f32).contiguous()
-    obj_off, _ = cached_offsets(list(n_objs), [0] * len(n_objs), device)
     pred = torch.empty(n_obj, dtype=torch.int64, device=device)
     scores = torch.empty(n_obj, **f32) if want_scores else None
     boxes = torch.empty((n_obj, 4), **f32) if want_boxes else None
-    need = lib.veto_obj_decode_workspace_bytes(n_obj, n_cls)
-    stream = torch.cuda.current_stream(device)
-    key = (str(device), stream.cuda_stream)
-    ws = _WORKSPACE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACE[key] = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    a = native.VetoObjDecodeArgs()
-    a.struct_size = ctypes.sizeof(native.VetoObjDecodeArgs)
-    a.n_img, a.n_obj, a.n_cls = len(n_objs), n_obj, n_cls
-    a.max_obj_per_image, a.mode, a.nms_thres = max(n_objs), MODES[mode], float(nms_thres)
-    a.labels, a.logits = (logits.data_ptr(), None) if meet else (None, logits.data_ptr())
-    a.boxes_per_cls, a.img_obj_offset = boxes_per_cls.data_ptr(), obj_off.data_ptr()
-    a.obj_pred = pred.data_ptr()
-    a.obj_scores = scores.data_ptr() if scores is not None else None
-    a.boxes = boxes.data_ptr() if boxes is not None else None
-    native.check(lib.veto_obj_decode(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a), ctypes.c_void_p(ws.data_ptr()),
-                                     ws.numel()))
-    for t in (logits, boxes_per_cls, obj_off, ws):
-        t.record_stream(stream)
+    a = call.args(native.VetoObjDecodeArgs, n_img=len(n_objs), n_obj=n_obj, n_cls=n_cls, max_obj_per_image=max(n_objs),
+                  mode=MODES[mode], nms_thres=float(nms_thres), labels=logits if meet else None, logits=None if meet else logits,
+                  boxes_per_cls=boxes_per_cls, img_obj_offset=native.device_offsets(n_objs, device=device)[0], obj_pred=pred,
+                  obj_scores=scores, boxes=boxes)
+    ws = call.workspace(call.lib.veto_obj_decode_workspace_bytes(n_obj, n_cls))
+    call.run("veto_obj_decode", ctypes.byref(a), ws.data_ptr(), ws.numel())
     return pred, scores, boxes
