@@ -19,6 +19,8 @@
  *   veto_nms               <- pysgg._C.nms / boxlist_nms            csrc/cuda/nms.cu, structures/boxlist_ops.py:10-32
  *   veto_box_postprocess   <- PostProcessor (box head)              roi_heads/box_head/inference.py:51-238
  *   veto_rpn_proposals     <- RPNPostProcessor                      rpn/inference.py:13-183
+ *   veto_box_match         <- FastRCNNSampling.assign_label_to_proposals / prepare_targets   roi_heads/box_head/sampling.py:34-82, 118-133
+ *   veto_box_subsample     <- BalancedPositiveNegativeSampler + FastRCNNSampling.subsample    balanced_positive_negative_sampler.py:37-66
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -509,6 +511,66 @@ typedef struct veto_gtbox_relsample_args {
 } veto_gtbox_relsample_args_t;
 
 int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* args);
+
+/* veto_box_match: the matching half of FastRCNNSampling (roi_heads/box_head/sampling.py:34-82 and :118-133) for a ragged
+ * batch, one launch.  Per proposal of image i: the maximum of boxlist_iou(target, proposal) (TO_REMOVE 1, fp32, bit-equal to
+ * the reference's matrix, which is never stored) over the image's GT boxes and the lowest GT index that reaches it; Matcher
+ * (matcher.py:66-76, allow_low_quality_matches False): matched_idxs = that index when the maximum >= high_threshold, -2 when it
+ * lies in [low_threshold, high_threshold), -1 below.
+ *   labels, mode 0 (assign_label_to_proposals): tgt_labels of the matched box, 0 for every negative match.
+ *   labels, mode 1 (prepare_targets): the same, but -2 gives -1 (ignored by the sampler).
+ *   regression_targets (optional): BoxCoder.encode (box_coder.py:22-50) of the proposal against GT box max(matched_idxs, 0).
+ *   matched_rows (optional): img_tgt_offset[i] + max(matched_idxs, 0), the row of that box in the concatenated targets.
+ * Limits, checked on the host offsets before the launch: 1..256 GT boxes and 1..6144 proposals per image.  No workspace; the
+ * call runs on `stream` and never synchronises. */
+typedef struct veto_box_match_args {
+  int32_t struct_size;
+  int32_t n_img, n_prp, n_tgt;
+  int32_t mode;                       /* 0: assign_label_to_proposals, 1: prepare_targets */
+  float high_threshold;               /* MODEL.ROI_HEADS.FG_IOU_THRESHOLD */
+  float low_threshold;                /* MODEL.ROI_HEADS.BG_IOU_THRESHOLD, <= high_threshold */
+  float reg_weights[4];               /* MODEL.ROI_HEADS.BBOX_REG_WEIGHTS; read with regression_targets only */
+  int32_t reserved0;
+  const float* prp_boxes;             /* device [n_prp, 4] xyxy, 16-byte aligned */
+  const float* tgt_boxes;             /* device [n_tgt, 4] xyxy, 16-byte aligned */
+  const int64_t* tgt_labels;          /* device [n_tgt] */
+  const int32_t* img_prp_offset;      /* device [n_img + 1] */
+  const int32_t* img_tgt_offset;      /* device [n_img + 1] */
+  const int32_t* img_prp_offset_host; /* HOST copies of the two offset arrays: the limits are checked on them */
+  const int32_t* img_tgt_offset_host;
+  int64_t* matched_idxs;              /* out device [n_prp] */
+  int64_t* labels;                    /* out device [n_prp] */
+  int64_t* matched_rows;              /* optional out device [n_prp] */
+  float* regression_targets;          /* optional out device [n_prp, 4], 16-byte aligned */
+} veto_box_match_args_t;
+
+int veto_box_match(void* stream, const veto_box_match_args_t* args);
+
+/* veto_box_subsample: BalancedPositiveNegativeSampler (balanced_positive_negative_sampler.py:37-66) and the
+ * nonzero(pos | neg) of FastRCNNSampling.subsample (sampling.py:111-114) for a ragged batch, one workgroup per image, one
+ * launch.  Per image: positives are labels >= 1, negatives labels == 0, everything else is ignored;
+ * num_pos = min(positives, num_pos_per_img), num_neg = min(negatives, batch_size_per_image - num_pos).  A class above its
+ * quota keeps a uniformly random subset of that size: the members with the smallest (hash, proposal index), hash = the upper
+ * 32 bits of a counter-based hash of (seed, image index, class, proposal index).  An image's rows depend only on the seed,
+ * its index and its own labels.  The draws follow the reference's distribution (randperm(m)[:k] as a set), not its RNG stream.
+ * Rows: image i writes counts[i] = num_pos + num_neg proposal indices (inside the image, ascending) from
+ * sampled_inds[i * batch_size_per_image].  Limits, checked before the launch: 1..6144 proposals per image,
+ * batch_size_per_image 1..2048.  No workspace; never synchronises. */
+typedef struct veto_box_subsample_args {
+  int32_t struct_size;
+  int32_t n_img, n_prp;
+  int32_t batch_size_per_image;       /* MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE, 1..2048 */
+  int32_t num_pos_per_img;            /* int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION), 0..batch_size_per_image */
+  int32_t reserved0;
+  uint64_t seed;
+  const int64_t* labels;              /* device [n_prp]: the labels of veto_box_match, mode 1 */
+  const int32_t* img_prp_offset;      /* device [n_img + 1] */
+  const int32_t* img_prp_offset_host; /* HOST copy: the limits are checked on it */
+  int64_t* sampled_inds;              /* out device [n_img, batch_size_per_image] */
+  int32_t* counts;                    /* out device [n_img] */
+} veto_box_subsample_args_t;
+
+int veto_box_subsample(void* stream, const veto_box_subsample_args_t* args);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

@@ -46,6 +46,10 @@ def default_config():
     vt.T_DROPOUT = 0.35
     c.MODEL.ROI_HEADS = CfgNode()
     c.MODEL.ROI_HEADS.FG_IOU_THRESHOLD = 0.5      # defaults.py:202
+    c.MODEL.ROI_HEADS.BG_IOU_THRESHOLD = 0.3      # defaults.py:205
+    c.MODEL.ROI_HEADS.BBOX_REG_WEIGHTS = (10., 10., 5., 5.)   # defaults.py:209
+    c.MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE = 256  # defaults.py:214 (the box head's budget, not the relation head's)
+    c.MODEL.ROI_HEADS.POSITIVE_FRACTION = 0.25    # defaults.py:216
     bh = c.MODEL.ROI_BOX_HEAD = CfgNode()
     bh.FEATURE_EXTRACTOR = "FPN2MLPFeatureExtractor"       # VETO_final.yaml:41 (the detector's own box head)
     bh.POOLER_SCALES = (0.25, 0.125, 0.0625, 0.03125)      # VETO_final.yaml:39

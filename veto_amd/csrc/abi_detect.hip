@@ -1,5 +1,5 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
-// box-head and RPN post-processing, the relation samplers, ROI pooling and the evaluator.  Each checks its argument struct,
+// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, ROI pooling and the evaluator.  Each checks its argument struct,
 // carves its workspace and makes one launch (kernels.h).
 #include <cmath>
 
@@ -439,6 +439,75 @@ int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* a) {
   p.n_img = a->n_img; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img; p.seed = a->seed;
   p.pairs = a->pairs; p.labels = a->labels; p.binary = a->binary_rel; p.counts = a->counts;
   HIP_TRY(launch_gtbox_relsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// check_host_offsets for the box-head sampler, which also refuses an empty image as the reference does (matcher.py:53-62)
+static int check_box_sample_offsets(const int32_t* off, int n_img, int total, int limit, const char* name, const char* total_name,
+                                    const char* empty_message) {
+  const int largest = check_host_offsets(off, n_img, total, limit, name, total_name);
+  for (int i = 0; largest >= 0 && i < n_img; ++i)
+    if (off[i + 1] == off[i]) return fail(VETO_ERR_INVALID, "%s (image %d)", empty_message, i);
+  return largest;
+}
+
+static const char* const kNoGtBoxes = "No ground-truth boxes available for one of the images during training";
+static const char* const kNoProposals = "No proposal boxes available for one of the images during training";
+
+int veto_box_match(void* stream, const veto_box_match_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_box_match_args_t)) return fail(VETO_ERR_INVALID, "veto_box_match_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_img > 65535 || a->n_prp < 0 || a->n_tgt < 0)
+    return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d, n_tgt %d)", a->n_img, a->n_prp, a->n_tgt);
+  if (a->mode != 0 && a->mode != 1) return fail(VETO_ERR_INVALID, "mode must be 0 (assign_label_to_proposals) or 1 (prepare_targets)");
+  if (!(a->low_threshold <= a->high_threshold))
+    return fail(VETO_ERR_INVALID, "low_threshold %g must be <= high_threshold %g (BG_IOU_THRESHOLD, FG_IOU_THRESHOLD)", a->low_threshold,
+                a->high_threshold);
+  if (!a->img_prp_offset_host || !a->img_tgt_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: host offsets");
+  // the reference meets the empty GT list first (matcher.py:55)
+  if (check_box_sample_offsets(a->img_tgt_offset_host, a->n_img, a->n_tgt, box_match_max_gt(), "img_tgt_offset_host", "n_tgt",
+                               kNoGtBoxes) < 0)
+    return VETO_ERR_INVALID;
+  const int largest = check_box_sample_offsets(a->img_prp_offset_host, a->n_img, a->n_prp, box_subsample_max_proposals(),
+                                               "img_prp_offset_host", "n_prp", kNoProposals);
+  if (largest < 0) return largest;
+  if (a->regression_targets)
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(a->reg_weights[k])) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g (BBOX_REG_WEIGHTS)", k, a->reg_weights[k]);
+  if (!a->prp_boxes || !a->tgt_boxes || !a->tgt_labels || !a->img_prp_offset || !a->img_tgt_offset || !a->matched_idxs || !a->labels)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  if ((((uintptr_t)a->prp_boxes | (uintptr_t)a->tgt_boxes | (uintptr_t)a->regression_targets) & 15) != 0)
+    return fail(VETO_ERR_INVALID, "prp_boxes, tgt_boxes and regression_targets must be 16-byte aligned");
+  BoxMatchArgs p{};
+  p.prp_boxes = a->prp_boxes; p.tgt_boxes = a->tgt_boxes; p.tgt_labels = a->tgt_labels;
+  p.prp_off = a->img_prp_offset; p.tgt_off = a->img_tgt_offset;
+  p.n_img = a->n_img; p.mode = a->mode; p.high = a->high_threshold; p.low = a->low_threshold;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.matched = a->matched_idxs; p.labels = a->labels; p.matched_rows = a->matched_rows; p.targets = a->regression_targets;
+  HIP_TRY(launch_box_match(p, largest, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_box_subsample(void* stream, const veto_box_subsample_args_t* a) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_box_subsample_args_t)) return fail(VETO_ERR_INVALID, "veto_box_subsample_args_t size mismatch");
+  if (a->n_img <= 0 || a->n_prp < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d)", a->n_img, a->n_prp);
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > box_subsample_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                box_subsample_max_batch());
+  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
+                a->batch_size_per_image);
+  if (!a->img_prp_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_prp_offset_host");
+  if (check_box_sample_offsets(a->img_prp_offset_host, a->n_img, a->n_prp, box_subsample_max_proposals(), "img_prp_offset_host", "n_prp",
+                               kNoProposals) < 0)
+    return VETO_ERR_INVALID;
+  if (!a->labels || !a->img_prp_offset || !a->sampled_inds || !a->counts) return fail(VETO_ERR_INVALID, "missing pointer");
+  BoxSubsampleArgs p{};
+  p.labels = a->labels; p.prp_off = a->img_prp_offset;
+  p.n_img = a->n_img; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img; p.seed = a->seed;
+  p.sampled = a->sampled_inds; p.counts = a->counts;
+  HIP_TRY(launch_box_subsample(p, (hipStream_t)stream));
   return VETO_OK;
 }
 

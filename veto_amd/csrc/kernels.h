@@ -441,6 +441,34 @@ int gtbox_relsample_max_objects();
 int gtbox_relsample_max_batch();
 hipError_t launch_gtbox_relsample(const GtboxRelSampleArgs& a, hipStream_t s);
 
+// ---- sgdet training: the box head's proposal matching and fg/bg sampling (boxsample.hip) ---------------
+struct BoxMatchArgs {
+  const float* prp_boxes;        // [n_prp, 4] xyxy, 16-byte aligned
+  const float* tgt_boxes;        // [n_tgt, 4] xyxy, 16-byte aligned
+  const int64_t* tgt_labels;     // [n_tgt]
+  const int32_t* prp_off;        // [n_img + 1]
+  const int32_t* tgt_off;        // [n_img + 1]
+  int n_img, mode;               // mode 0: assign_label_to_proposals' labels, 1: prepare_targets'
+  float high, low, wx, wy, ww, wh;
+  int64_t* matched;              // out [n_prp]: GT index, -1 below low, -2 in [low, high)
+  int64_t* labels;               // out [n_prp]
+  int64_t* matched_rows;         // optional out [n_prp]: tgt_off[img] + max(matched, 0)
+  float* targets;                // optional out [n_prp, 4], 16-byte aligned
+};
+struct BoxSubsampleArgs {
+  const int64_t* labels;         // [n_prp]: >= 1 positive, 0 negative, anything else ignored
+  const int32_t* prp_off;        // [n_img + 1]
+  int n_img, batch, num_pos;
+  uint64_t seed;
+  int64_t* sampled;              // out [n_img, batch]: proposal indices inside the image, ascending
+  int32_t* counts;               // out [n_img]
+};
+int box_match_max_gt();
+int box_subsample_max_proposals();
+int box_subsample_max_batch();
+hipError_t launch_box_match(const BoxMatchArgs& a, int largest_prp, hipStream_t s);
+hipError_t launch_box_subsample(const BoxSubsampleArgs& a, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

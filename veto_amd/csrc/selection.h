@@ -1,6 +1,7 @@
 // Device helpers shared by the per-image pair kernels of sgdet.hip (test pairs), relsample.hip and gtbox_relsample.hip
-// (training pairs): the reference's box IoU arithmetic, the order-preserving float key, the block-wide scan of their radix
-// selects and, for the two training samplers, the counter-based hash, the radix select and the bitonic sort.
+// (training pairs) and the box head's sampler of boxsample.hip: the reference's box IoU arithmetic, the order-preserving float
+// key, the block-wide scan of their radix selects and, for the training samplers, the counter-based hash, the radix select and
+// the bitonic sort.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

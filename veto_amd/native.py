@@ -119,6 +119,21 @@ class VetoGtboxRelsampleArgs(Structure):
                                         "counts")]
 
 
+class VetoBoxMatchArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_prp", "n_tgt", "mode")] + \
+               [("high_threshold", ctypes.c_float), ("low_threshold", ctypes.c_float), ("reg_weights", ctypes.c_float * 4),
+                ("reserved0", c_int32)] + \
+               [(n, c_void_p) for n in ("prp_boxes", "tgt_boxes", "tgt_labels", "img_prp_offset", "img_tgt_offset",
+                                        "img_prp_offset_host", "img_tgt_offset_host", "matched_idxs", "labels", "matched_rows",
+                                        "regression_targets")]
+
+
+class VetoBoxSubsampleArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_prp", "batch_size_per_image", "num_pos_per_img", "reserved0")] + \
+               [("seed", ctypes.c_uint64)] + \
+               [(n, c_void_p) for n in ("labels", "img_prp_offset", "img_prp_offset_host", "sampled_inds", "counts")]
+
+
 class VetoPostMeetArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_obj", "n_pair", "n_groups", "n_rel_cls", "n_obj_cls")] + \
                [(n, c_void_p) for n in ("group_logits", "group_widths", "incre_idx_list", "obj_logits", "rel_pairs",
@@ -163,6 +178,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_post_vote_args_t": VetoPostVoteArgs, "veto_obj_decode_args_t": VetoObjDecodeArgs, "veto_pair_args_t": VetoPairArgs,
     "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
+    "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
 }
 
@@ -210,6 +226,8 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_detect_relsample": _sig(_P, POINTER(VetoDetectRelsampleArgs), _P, _Z),
     "veto_detect_relsample_workspace_bytes": _sig(_I, _I, ret=_Z),
     "veto_gtbox_relsample": _sig(_P, POINTER(VetoGtboxRelsampleArgs)),
+    "veto_box_match": _sig(_P, POINTER(VetoBoxMatchArgs)),
+    "veto_box_subsample": _sig(_P, POINTER(VetoBoxSubsampleArgs)),
     "veto_nms": _sig(_P, POINTER(VetoNmsArgs)),
     "veto_nms_max_segment": _sig(),
     "veto_box_postprocess": _sig(_P, POINTER(VetoBoxPostArgs), _P, _Z),

@@ -86,3 +86,22 @@ def install_rpn_ops():
         head.make_rpn_postprocessor = rpn.make_rpn_postprocessor
         patched.append(("pysgg.modeling.rpn.rpn", "make_rpn_postprocessor"))
     return patched
+
+
+def install_box_sampling_ops():
+    """Point the reference's box head at the device sampler: `pysgg.modeling.roi_heads.box_head.sampling.make_roi_box_samp_processor`
+    returns veto_amd.boxsampling.FastRCNNSampling (assign_label_to_proposals, prepare_targets, subsample).  `pysgg` must be
+    importable.  Independent of install(), install_detector_ops() and install_rpn_ops().  Returns the patched (module, name)
+    pairs."""
+    import importlib
+    import sys
+    from . import boxsampling
+    setattr(importlib.import_module("pysgg.modeling.roi_heads.box_head.sampling"), "make_roi_box_samp_processor",
+            boxsampling.make_roi_box_samp_processor)
+    patched = [("pysgg.modeling.roi_heads.box_head.sampling", "make_roi_box_samp_processor")]
+    # box_head.py binds the factory by name when it is imported (box_head.py:9): re-point that binding too if it exists
+    head = sys.modules.get("pysgg.modeling.roi_heads.box_head.box_head")
+    if head is not None and hasattr(head, "make_roi_box_samp_processor"):
+        head.make_roi_box_samp_processor = boxsampling.make_roi_box_samp_processor
+        patched.append(("pysgg.modeling.roi_heads.box_head.box_head", "make_roi_box_samp_processor"))
+    return patched

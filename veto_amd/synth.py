@@ -457,6 +457,16 @@ def synthetic_relsample_image(seed, n_gt, n_det, n_rel, num_obj_cls=151, num_rel
             "relation": rel.reshape(n_gt, n_gt), "relation_non_masked": non_masked.reshape(n_gt, n_gt), "image_size": (W, H)}
 
 
+def synthetic_box_sampling_image(seed, n_gt, n_det, num_obj_cls=151, n_attr=3, W=800, H=600):
+    """One training image for the box head's sampler (FastRCNNSampling): the GT boxes and clustered detections of
+    synthetic_relsample_image with the GT boxes appended to the proposals (as ADD_GTBOX_TO_PROPOSAL_IN_TRAIN does), GT labels
+    and an `attributes` matrix [n_gt, n_attr]."""
+    d = synthetic_relsample_image(seed, n_gt, n_det, min(2, n_gt * (n_gt - 1)), num_obj_cls=num_obj_cls, W=W, H=H)
+    return {"prp_boxes": np.concatenate([d["prp_boxes"], d["tgt_boxes"]], 0), "tgt_boxes": d["tgt_boxes"],
+            "tgt_labels": d["tgt_labels"], "image_size": (W, H),
+            "attributes": integers(seed, "boxsample.attr.%d.%d" % (n_gt, n_det), (n_gt, n_attr), 0, 20)}
+
+
 # ---------------------------------------------------------------------------
 # sgdet box decoder: the box head's raw outputs, and boxes + scores for NMS alone
 # ---------------------------------------------------------------------------
