@@ -746,7 +746,19 @@ int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint3
  * transformer's pos_drop (EMB_DROPOUT, model_veto.py:44,63) and the Dropout behind every attention out projection
  * (T_DROPOUT, model_veto.py:80-83).  Masks come from a counter-based hash of (seed, site, element index), recomputed in
  * the backward: the same opts must be given to both calls.  The masks are this library's own (the reference draws from
- * torch's generator), i.e. equal in distribution, not bit for bit. */
+ * torch's generator), i.e. equal in distribution, not bit for bit.
+ *
+ * The contract, element by element (oracle/dropout.py restates it on the host; tests/test_train_dropout_gpu.py holds the step to it):
+ *   y = keep ? x * (1.f / (1.f - p)) : 0 in float32; a site with p == 0 is the identity (no mask, no scale).
+ *   keep(element) = (splitmix64(site_seed + index * 0x9E3779B97F4A7C15) >> 40) >= (uint32_t)(p * 16777216.0f),
+ *   site_seed = seed + site * 0x632BE59BD9B4E019 (mod 2^64), with
+ *     site 1      p_pos,  behind the ReLU of pos_embed:            element (n, k) of [n_obj, 128]  -> index n * 128 + k
+ *     site 2      p_emb,  pos_drop on the tokens, after the positional embedding is added:
+ *                                                                  element (row, col) of [n_pair * 19, 576] -> index row * 576 + col,
+ *                                                                  row = pair * 19 + token, pair = the row of the batch's pair list
+ *     site 3 + l  p_attn, on (attn_out Wo^T + bo) of layer l, before the residual add:          numbered as site 2
+ *   The numbering is by token row whatever rows the implementation computes: the last layer runs on the CLS rows only, and its
+ *   CLS row of pair p uses the elements of token row 19 p. */
 typedef struct veto_train_opts {
   int32_t struct_size;
   float p_pos, p_emb, p_attn;

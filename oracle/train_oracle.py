@@ -15,6 +15,7 @@ autograd produced (norm and a strided sample per parameter and per ROI input): t
 import numpy as np
 import torch
 
+from . import dropout as od
 from . import veto_oracle as vo
 
 
@@ -124,11 +125,19 @@ def _loss_plan(cfg, labels, loss, dtype):
     return plan
 
 
-def train_step(sd, cfg, batch, rel_pair_idxs, labels, loss=None, dtype=torch.float64, pair_chunk=256):
+def train_step(sd, cfg, batch, rel_pair_idxs, labels, loss=None, dtype=torch.float64, pair_chunk=256, dropout=None):
     """One training step of VETOPredictor / VETOPredictor_MEET (roi_relation_predictors.py:4074-4136, :3752-3853,
-    :3909-3995) with dropout off: the forward of veto_oracle.forward except that pos_embed.0 normalises with the BATCH
-    statistics (biased variance), the losses, and autograd of their sum (the trainer sums the loss dict).
+    :3909-3995): the forward of veto_oracle.forward except that pos_embed.0 normalises with the BATCH statistics (biased
+    variance) and that the three dropout sites of the path carry the masks `dropout` names, the losses, and autograd of their
+    sum (the trainer sums the loss dict).
 
+    dropout: None (dropout off: every golden and tests/test_train_oracle.py), or an oracle.dropout.Dropout with the meaning of
+            veto_train_opts_t (include/veto_amd.h): p_pos / p_emb / p_attn and the step's 64-bit seed.  The masks are the
+            LIBRARY's counter-based ones, element for element (the reference draws from torch's generator and cannot be matched
+            bit for bit): keep * x / (1 - p) behind the ReLU of pos_embed (site 1, element n * 128 + k), on the assembled tokens
+            (pos_drop, site 2, element row * 576 + col with row = GLOBAL pair row * 19 + token: not the chunk's) and on
+            (attn_out Wo^T + bo) of layer l before the residual add (site 3 + l, numbered as site 2); a site with p == 0 leaves
+            x untouched.
     labels: relation label per pair row, concatenated over the images.
     loss:   None (plain CE), {"weight": class weights} (BETA_LOSS), or for cfg.meet_groups
             {"chosen": per-group row lists (cur_chosen_matrix), "incre_idx_list": ...}.
@@ -156,7 +165,9 @@ def train_step(sd, cfg, batch, rel_pair_idxs, labels, loss=None, dtype=torch.flo
     dep = vo._t(batch["roi_depth_features"], dtype).clone().requires_grad_(True)
 
     emb, _ = vo.object_embeddings(p, cfg, batch["labels"], batch.get("predict_logits"), batch.get("pred_labels"), dtype)
-    pos = vo.position_embedding(p, cfg, batch["boxes"], dtype, batch_stats=True)
+    n_obj = len(np.asarray(batch["boxes"]))
+    pos = vo.position_embedding(p, cfg, batch["boxes"], dtype, batch_stats=True,
+                                drop=None if dropout is None else dropout.factor(od.SITE_POS, n_obj, 128, dtype))
     emb_c, pos_c = emb.detach().requires_grad_(True), pos.detach().requires_grad_(True)
 
     plan = _loss_plan(cfg, labels, loss, dtype)
@@ -175,9 +186,12 @@ def train_step(sd, cfg, batch, rel_pair_idxs, labels, loss=None, dtype=torch.flo
     logits_out = []
     for a in range(0, P, pair_chunk):
         s, o = subj_t[a:a + pair_chunk], obj_t[a:a + pair_chunk]
-        x = vo.pair_tokens(p, cfg, emb_c, pos_c, rgb, dep, s, o, dtype)
+        def site(k):      # the factor of token-row site k for this chunk's pairs: rows a * 19 .. of the whole step's numbering
+            f = None if dropout is None else dropout.factor(k, len(s) * 19, cfg.dim, dtype, row0=a * 19)
+            return None if f is None else f.reshape(len(s), 19, cfg.dim)
+        x = vo.pair_tokens(p, cfg, emb_c, pos_c, rgb, dep, s, o, dtype, drop=site(od.SITE_EMB))
         for l in range(cfg.layers):
-            x = vo.encoder_layer(p, cfg, x, l, dtype)
+            x = vo.encoder_layer(p, cfg, x, l, dtype, drop=site(od.SITE_ATTN0 + l))
         Wh, bh = vo.head_weights(p, cfg, dtype)
         z = x[:, 0] @ Wh.t() + bh
         logits_out.append(z.detach())

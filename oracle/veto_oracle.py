@@ -87,10 +87,11 @@ def object_embeddings(sd, cfg, labels, predict_logits, pred_labels, dtype):
     return emb, obj_dists
 
 
-def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False):
+def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False, drop=None):
     """pos_embed = BatchNorm1d(4) (eval: running stats, eps 1e-5) -> Linear(4,128) -> ReLU;
     roi_relation_predictors.py:4042-4047,4097-4102.  `batch_stats`: the training-mode BatchNorm, normalising with the
-    batch mean and the BIASED batch variance (the running update, which takes the unbiased one, is not part of the forward)."""
+    batch mean and the BIASED batch variance (the running update, which takes the unbiased one, is not part of the forward).
+    `drop` (training, optional): the [n_obj, 128] factor keep / (1 - p) of the Dropout behind the ReLU (oracle/dropout.py, site 1)."""
     p = cfg.prefix + "pos_embed."
     x = center_xywh_from_xyxy(_t(boxes_xyxy, dtype))
     if batch_stats:
@@ -99,7 +100,8 @@ def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False):
         mean, var = _t(sd[p + "0.running_mean"], dtype), _t(sd[p + "0.running_var"], dtype)
     x = (x - mean) / torch.sqrt(var + 1e-5) * _t(sd[p + "0.weight"], dtype) + _t(sd[p + "0.bias"], dtype)
     x = x @ _t(sd[p + "1.weight"], dtype).t() + _t(sd[p + "1.bias"], dtype)
-    return torch.relu(x)
+    x = torch.relu(x)
+    return x if drop is None else x * drop
 
 
 def patchify(x, p):
@@ -121,10 +123,11 @@ def gelu_erf(x):
     return 0.5 * x * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
 
 
-def build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype):
+def build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype, drop=None):
     """PatchEmbed.forward + Transformer.forward, model_veto.py:52-64,108-115.
     NB the crossed naming: the FIRST argument (depth) goes through proj_d (512 wide),
-    the second (rgb) through proj_v (64 wide); roi_relation_predictors.py:4124."""
+    the second (rgb) through proj_v (64 wide); roi_relation_predictors.py:4124.
+    `drop` (training, optional): the [pairs, 19, 576] factor keep / (1 - p) of pos_drop (model_veto.py:63; oracle/dropout.py, site 2)."""
     t = cfg.prefix + "fusion_transformer.transformer."
     d = patchify(rel_depth, cfg.patch)
     v = patchify(rel_visual, cfg.patch)
@@ -133,12 +136,14 @@ def build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype)
     x = torch.cat([d, v], dim=2)
     cls = _t(sd[t + "cls_token"], dtype).expand(x.shape[0], -1, -1)
     x = torch.cat([cls, x, rel_location.unsqueeze(1), rel_class.unsqueeze(1)], dim=1)
-    return x + _t(sd[t + "pos_embedding"], dtype)
+    x = x + _t(sd[t + "pos_embedding"], dtype)
+    return x if drop is None else x * drop
 
 
-def encoder_layer(sd, cfg, x, l, dtype):
+def encoder_layer(sd, cfg, x, l, dtype, drop=None):
     """One (PreNorm Attention + residual, PreNorm FeedForward + residual) block;
-    model_veto.py:18-21,85-96,125-146."""
+    model_veto.py:18-21,85-96,125-146.  `drop` (training, optional): the [pairs, 19, 576] factor keep / (1 - p) of the Dropout
+    behind to_out (model_veto.py:80-83), applied to the projection's output before the residual add (oracle/dropout.py, site 3 + l)."""
     t = cfg.prefix + "fusion_transformer.transformer.layers.%d." % l
     H = cfg.heads
     b, n, D = x.shape
@@ -150,6 +155,8 @@ def encoder_layer(sd, cfg, x, l, dtype):
     attn = torch.softmax(dots, dim=-1)
     out = (attn @ v).permute(0, 2, 1, 3).reshape(b, n, D)
     out = out @ _t(sd[t + "0.fn.to_out.0.weight"], dtype).t() + _t(sd[t + "0.fn.to_out.0.bias"], dtype)
+    if drop is not None:
+        out = out * drop
     x = out + x
     y = layer_norm(x, _t(sd[t + "1.norm.weight"], dtype), _t(sd[t + "1.norm.bias"], dtype))
     h = gelu_erf(y @ _t(sd[t + "1.fn.net.0.weight"], dtype).t() + _t(sd[t + "1.fn.net.0.bias"], dtype))
@@ -169,9 +176,9 @@ def head_weights(sd, cfg, dtype):
     return torch.cat([_t(sd[n + ".weight"], dtype) for n in names]), torch.cat([_t(sd[n + ".bias"], dtype) for n in names])
 
 
-def pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype):
+def pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype, drop=None):
     """The [len(s), 19, 576] token rows of the pairs (s, o): the materialised pair gathers of :4118-4123 and
-    build_tokens."""
+    build_tokens (`drop`: its pos_drop factor)."""
     pre = cfg.prefix
     rel_location = torch.cat([pos[s], pos[o]], dim=1)
     rel_location = torch.relu(rel_location @ _t(sd[pre + "location_projection.0.weight"], dtype).t()
@@ -181,7 +188,7 @@ def pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype):
                            + _t(sd[pre + "class_projection.0.bias"], dtype))
     rel_visual = torch.cat([rgb[s], rgb[o]], dim=1)
     rel_depth = torch.cat([dep[s], dep[o]], dim=1)
-    return build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype)
+    return build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype, drop)
 
 
 def forward(sd, cfg, batch, rel_pair_idxs=None, dtype=torch.float32, return_intermediates=False,

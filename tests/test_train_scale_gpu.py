@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN_DIR, VG_MEET_GROUPS
+from oracle.dropout import keep_mask      # the one host restatement of the device's masks
 
 pytestmark = pytest.mark.gpu
 
@@ -49,17 +50,6 @@ def unsplit(buf, rows, n):
     """Split rows [rows, 2n] bf16, blocks of 32 columns [hi | lo] -> hi + lo in float64."""
     t = buf.view(torch.bfloat16).reshape(rows, n // 32, 2, 32).cpu()
     return (t[:, :, 0].double() + t[:, :, 1].double()).reshape(rows, n)
-
-
-def keep_mask(seed, rows, thresh):
-    """The training path's counter-based dropout mask (csrc/common.h, dropout_keep) on the host: element (r, c) has index r * 576 + c."""
-    idx = np.arange(rows * DIM, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = np.uint64(seed) + idx * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z ^= z >> np.uint64(31)
-    return torch.from_numpy(((z >> np.uint64(40)) >= np.uint64(thresh)).reshape(rows, DIM))
 
 
 # ---- attention backward -----------------------------------------------------------------------------------------------
@@ -247,7 +237,7 @@ def test_layernorm_backward_split_form_applies_the_dropout_mask(rows, p):
     ref_dx, ref_dg, ref_db = _ln_reference(x, dy, gamma, dres)
     tol_dx, tol_dg, tol_db = _ln_bounds("plain", ref_dx, ref_dg, ref_db)
     seed, thresh, scale = 0x1234567890ABCDEF, int(p * 2 ** 24), float(np.float32(1.0 / (1.0 - p)))
-    keep = keep_mask(seed, rows, thresh)
+    keep = keep_mask(seed, rows, DIM, thresh)
     assert abs(float(keep.double().mean()) - (1 - p)) < 4 * (p * (1 - p) / keep.numel()) ** 0.5 + 2.0 ** -24
     x_d, dy_d, gamma_d, dres_d = x.to(dev), dy.to(dev), gamma.to(dev), dres.to(dev)
     ws = torch.empty(lib.veto_debug_layernorm_backward_workspace_bytes(rows), dtype=torch.uint8, device=dev)
@@ -361,11 +351,26 @@ def sampled_pairs(num_objs, seed=0):
     return [p.numpy() for p in pairs], [l.numpy() for l in labels]
 
 
+REFERENCE_RATES = (0.1, 0.35, 0.35)      # pos_embed's Dropout, pos_drop, the attention out projections: the reference's, the modules' defaults
+
+
+def _dropout_modules(model):
+    tr = model._trunk.fusion_transformer.transformer
+    return [model._trunk.pos_embed[3]], [tr.pos_drop], [layer[0].fn.to_out[1] for layer in tr.layers]
+
+
 def run_step_case(tag, layers, heads, num_objs, pairs, labels, mode="predcls", meet=False, weighted=False, precision="mixed",
-                  oracle_dtype=torch.float64, yardstick=None, perturb=None):
+                  oracle_dtype=torch.float64, yardstick=None, perturb=None, dropout=False, torch_seed=0, rates=None, batch_seed=13,
+                  wrong_masks=None, collect=None):
     """One training step on the device and in the oracle; returns {name: (element error, norm error)} after asserting GRAD_TOL on all.
     yardstick {name: float32-oracle error}: parameters in BIG_REDUCTIONS may use 4 x that where it exceeds GRAD_TOL.
-    perturb(oracle result): the deliberately wrong reference of the self-check (see the pull request)."""
+    perturb(oracle result): the deliberately wrong reference of the self-check (see the pull request).
+    dropout: False sets every nn.Dropout to p = 0.  True leaves the modules as configured (asserted to be REFERENCE_RATES; `rates`, if
+    given, then overrides the three sites on the modules), runs the step under torch.manual_seed(torch_seed), records the seed and the
+    rates the step REALLY handed to the library (VETOPredictor._train_opts, wrapped for the call) and gives exactly those to the oracle,
+    which applies the library's counter-based masks (oracle/dropout.py).  wrong_masks(Dropout): the self-check's wrong reference.
+    collect: a dict that receives "res" (every error) and "seed" before anything is asserted."""
+    from oracle import dropout as od
     from oracle import train_oracle as to
     from oracle import veto_oracle as vo
     from veto_amd import synth, testing
@@ -379,29 +384,52 @@ def run_step_case(tag, layers, heads, num_objs, pairs, labels, mode="predcls", m
     if weighted:
         sd.pop("criterion_loss_rel.weight")
     model = testing.make_predictor(cfg, sd, dev).train()
-    for m in model.modules():
-        if isinstance(m, torch.nn.Dropout):
-            m.p = 0.0
-    batch = synth.synthetic_batch(13, len(num_objs), list(num_objs))
+    used_opts = []
+    if dropout:
+        sites = _dropout_modules(model)
+        assert tuple(float(m.p) for mods in sites for m in mods) == (REFERENCE_RATES[0], REFERENCE_RATES[1]) + (REFERENCE_RATES[2],) * layers
+        for mods, p in zip(sites, rates if rates is not None else REFERENCE_RATES):
+            for m in mods:
+                m.p = p
+        inner_opts = model._train_opts
+
+        def recording_opts():
+            used_opts.append(inner_opts())
+            return used_opts[-1]
+        model._train_opts = recording_opts
+    else:
+        for m in model.modules():
+            if isinstance(m, torch.nn.Dropout):
+                m.p = 0.0
+    batch = synth.synthetic_batch(batch_seed, len(num_objs), list(num_objs))
     props = testing.make_proposals(batch, mode, dev)
     roi = {k: torch.from_numpy(batch[k]).to(dev).requires_grad_(True) for k in ("roi_features", "roi_depth_features")}
     random.seed(1)
-    out = model(props, [torch.from_numpy(p).to(dev) for p in pairs], [torch.from_numpy(l).to(dev) for l in labels], None, **roi)
+    pairs_d, labels_d = [torch.from_numpy(p).to(dev) for p in pairs], [torch.from_numpy(l).to(dev) for l in labels]
+    if dropout:
+        torch.manual_seed(torch_seed)
+    out = model(props, pairs_d, labels_d, None, **roi)
     trainable = {k: v for k, v in out[2].items() if v.requires_grad}
     sum(trainable.values()).backward()
     torch.cuda.synchronize()
+    drop = None
+    if dropout:
+        del model._train_opts      # (the instance attribute: the class's method is back)
+        assert len(used_opts) == 1, "one step, one draw of the dropout seed"
+        o = used_opts[0]
+        drop = od.Dropout(o.p_pos, o.p_emb, o.p_attn, seed=o.seed)
+        if wrong_masks is not None:
+            drop = wrong_masks(drop)
     ocfg = vo.OracleConfig(layers, heads, mode=mode, meet_groups=VG_MEET_GROUPS if meet else None, prefix="model." if meet else "")
     if meet:
         loss = {"chosen": [c.cpu().numpy() for c in out[4][0]], "incre_idx_list": model.incre_idx_list}
     else:
         loss = {"weight": model.criterion_loss_rel.weight.detach().cpu().numpy()} if weighted else None
     t0 = time.time()
-    ref = to.train_step(sd, ocfg, batch, pairs, np.concatenate(labels), loss, dtype=oracle_dtype)
+    ref = to.train_step(sd, ocfg, batch, pairs, np.concatenate(labels), loss, dtype=oracle_dtype, dropout=drop)
     wall = time.time() - t0
     if perturb is not None:
         perturb(ref)
-    for k, v in trainable.items():
-        assert abs(float(v.detach()) - ref["losses"][k]) < 2e-4 * max(1.0, abs(ref["losses"][k])), (k, float(v.detach()), ref["losses"][k])
     params = dict(model.named_parameters(remove_duplicate=False))
     res = {}
     for name, want in ref["grads"].items():
@@ -409,6 +437,10 @@ def run_step_case(tag, layers, heads, num_objs, pairs, labels, mode="predcls", m
         res[name] = _errors(params[name].grad.detach().cpu(), want)
     for k in roi:
         res["d_" + k] = _errors(roi[k].grad.detach().cpu(), ref["d_" + k])
+    if collect is not None:
+        collect.update(res=res, seed=used_opts[0].seed if dropout else None)
+    for k, v in trainable.items():
+        assert abs(float(v.detach()) - ref["losses"][k]) < 2e-4 * max(1.0, abs(ref["losses"][k])), (k, float(v.detach()), ref["losses"][k])
     used = {id(params[n]) for n in ref["grads"]}
     assert all(p.grad is None or float(p.grad.abs().max()) == 0.0 for p in params.values() if id(p) not in used)
     groups = {}
@@ -417,8 +449,9 @@ def run_step_case(tag, layers, heads, num_objs, pairs, labels, mode="predcls", m
         groups[grp] = (max(groups.get(grp, (0, 0))[0], e), max(groups.get(grp, (0, 0))[1], ne))
     n_pair = sum(len(p) for p in pairs)
     worst = max(res.items(), key=lambda kv: max(kv[1]))
-    _report("step %s L%d H%d %s %s %s %d pairs (oracle %s, %.1f s): worst element %.2e norm %.2e at %s | per group (element, norm): %s"
-            % (tag, layers, heads, mode, "meet" if meet else ("weighted-ce" if weighted else "ce"), precision, n_pair,
+    how = "" if not dropout else " dropout %g/%g/%g" % (drop.p_pos, drop.p_emb, drop.p_attn)
+    _report("step %s L%d H%d %s %s %s%s %d pairs (oracle %s, %.1f s): worst element %.2e norm %.2e at %s | per group (element, norm): %s"
+            % (tag, layers, heads, mode, "meet" if meet else ("weighted-ce" if weighted else "ce"), precision, how, n_pair,
                str(oracle_dtype).replace("torch.", ""), wall, worst[1][0], worst[1][1], worst[0],
                "  ".join("%s %.1e %.1e" % (k, v[0], v[1]) for k, v in sorted(groups.items()))))
     for name, (e, ne) in res.items():
@@ -469,9 +502,7 @@ def test_step_gradients_ragged_batch_sampled_pairs(layers, heads, mode, meet):
 def test_step_gradients_hand_made_pair_list():
     """Object 2 of the first image is in no pair, object 4 only ever on the object side, the ordered pair (0, 1) is listed twice, the
     second image has one pair: the scatter into the per-object gradient rows sees gaps, one-sided objects and repeats."""
-    num_objs = [6, 3]
-    pairs = [np.array([[0, 1], [0, 1], [1, 0], [3, 4], [0, 4], [5, 4], [5, 3], [1, 5], [3, 0]], dtype=np.int64), np.array([[2, 0]], dtype=np.int64)]
-    labels = [np.array([3, 3, 0, 17, 0, 50, 1, 0, 9], dtype=np.int64), np.array([4], dtype=np.int64)]
+    from train_dropout_cases import HAND_LABELS as labels, HAND_OBJS as num_objs, HAND_PAIRS as pairs      # (shared with the dropout-on step)
     res, ref, (model, roi, batch) = run_step_case("hand-made", 2, 8, num_objs, pairs, labels)
     for k in roi:
         assert float(roi[k].grad[2].abs().max()) == 0.0 and float(ref["d_" + k][2].abs().max()) == 0.0      # the unused object

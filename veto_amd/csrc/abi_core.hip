@@ -117,7 +117,7 @@ int run_gemm(veto_handle_t h, hipStream_t s, const char* name, const __bf16* a, 
   if (drop.thresh) {
     if (epi != EPI_RESID) return fail(VETO_ERR_INVALID, "dropout is fused into the residual epilogue only");
     epi = EPI_RESID_DROP;
-    g.drop_seed = drop.seed; g.drop_thresh = drop.thresh; g.drop_scale = drop.scale;
+    g.drop_seed = drop.seed; g.drop_thresh = drop.thresh; g.drop_scale = drop.scale; g.drop_row_step = drop.row_step;
   }
   g.a = a; g.lda = lda;
   g.w = w + (size_t)w_row0 * 2 * K;

@@ -196,6 +196,7 @@ struct DropSite {   // one dropout site of the training path: threshold p * 2^24
   unsigned long long seed = 0;
   unsigned thresh = 0;
   float scale = 1.f;
+  int row_step = 1;   // row r of the matrix the site is applied to is token row r * row_step (the last layer's compact CLS rows: 19)
 };
 
 // (abi_core.hip) lda / ldc of split operands are in bf16 elements (2K / 2N for contiguous rows).

@@ -204,9 +204,12 @@ int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const 
   return VETO_OK;
 }
 
-// dropout sites of the training path: 1 = pos_embed Dropout(0.1), 2 = pos_drop on the tokens, 3 + l = to_out of layer l
-DropSite drop_site(const veto_train_opts_t* o, int site) {
+// dropout sites of the training path: 1 = pos_embed Dropout(0.1), 2 = pos_drop on the tokens, 3 + l = to_out of layer l.  Elements are
+// numbered as include/veto_amd.h says, sites 2 and up by TOKEN row: where a site is applied to the last layer's compact CLS rows, row p is
+// token row 19 p (row_step), so that the masks do not depend on which rows the implementation chooses to compute.
+DropSite drop_site(const veto_train_opts_t* o, int site, int row_step = 1) {
   DropSite d;
+  d.row_step = row_step;
   if (!o) return d;
   const float p = site == 1 ? o->p_pos : site == 2 ? o->p_emb : o->p_attn;
   if (!(p > 0.f)) return d;
@@ -299,7 +302,7 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
         HIP_TRY(launch_attention(a, s));
       }
       rc = run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
-                    EPI_RESID, 0, 0, drop_site(opts, 3 + l));
+                    EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens));
       if (rc) return rc;
       HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
       rc = run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU);
@@ -401,11 +404,11 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       if (rc) return rc;
     }
     // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
-    const DropSite dsite = drop_site(opts, 3 + l);
+    const DropSite dsite = drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1);      // (last layer: compact CLS rows, as in the forward)
     const bool ln_split = train_ln_emits_split();
     if (ln_split)
       HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, ws.dsplit, ws.colp,
-                                        dsite.seed, dsite.thresh, dsite.scale));
+                                        dsite.seed, dsite.thresh, dsite.scale, dsite.row_step));
     else
       HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s));
     HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
@@ -416,6 +419,7 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       drop.seed = dsite.seed;
       drop.thresh = dsite.thresh;
       drop.scale = dsite.scale;
+      drop.row_step = dsite.row_step;
     }
     rc = run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, ws.dtmp, drop, nullptr,
                              ln_split ? layernorm_backward_col_partials(R) : 0);

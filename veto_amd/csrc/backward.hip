@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                                                                  const float* __restrict__ gamma, const float* dres,
                                                                  float* dx, float* __restrict__ partial, int rows,      // dres may be dx
                                                                  __bf16* __restrict__ split_out, float* __restrict__ colp,
-                                                                 unsigned long long drop_seed, unsigned drop_thresh, float drop_scale) {
+                                                                 unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step) {
   __shared__ float s_dg[kDim], s_db[kDim], s_w[kDim];
   __shared__ float s_cs[SPLIT ? 2 : 1][SPLIT ? kDim : 1];
   for (int c = threadIdx.x; c < kDim; c += 256) {
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const int c = 2 * (q + kLnLanes * j);
         if (drop_thresh) {
 #pragma unroll
-          for (int e = 0; e < 2; ++e) o[e] = dropout_keep(drop_seed, (unsigned long long)row * kDim + c + e, drop_thresh) ? o[e] * drop_scale : 0.f;
+          for (int e = 0; e < 2; ++e) o[e] = dropout_keep(drop_seed, (unsigned long long)row * drop_row_step * kDim + c + e, drop_thresh) ? o[e] * drop_scale : 0.f;
         }
         acc_c[j] += o;
         __bf16 h0, l0, h1, l1;
@@ -691,12 +691,12 @@ int layernorm_backward_col_partials(int rows) { return (rows + kLnRowsPerBlock -
 
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
                                      float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out, float* colp,
-                                     unsigned long long drop_seed, unsigned drop_thresh, float drop_scale) {
+                                     unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step) {
   const int blocks = (rows + kLnRowsPerBlock - 1) / kLnRowsPerBlock;
   if (!split_out != !colp) return hipErrorInvalidValue;
   if (split_out) VETO_LAUNCH(layernorm_backward_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
-                             drop_seed, drop_thresh, drop_scale);
-  else VETO_LAUNCH(layernorm_backward_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f);
+                             drop_seed, drop_thresh, drop_scale, drop_row_step);
+  else VETO_LAUNCH(layernorm_backward_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_column_sums(partial, 2 * kDim, blocks, 2 * kDim, dgamma_dbeta, partial + (size_t)blocks * 2 * kDim, kColChunks, s);

@@ -493,7 +493,7 @@ __global__ __launch_bounds__(64 * (NCONS + NLOAD), 3) void gemm_split_ps_kernel(
           if (kDrop) {   // training: Dropout behind the attention out projection
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-              v[e] = dropout_keep(g.drop_seed, (unsigned long long)row * g.N + col + e, g.drop_thresh) ? v[e] * g.drop_scale : 0.f;
+              v[e] = dropout_keep(g.drop_seed, (unsigned long long)row * g.drop_row_step * g.N + col + e, g.drop_thresh) ? v[e] * g.drop_scale : 0.f;
           }
           if (EPI == EPI_RESID) v += res[u & 1][j];
           if (EPI == EPI_GELU_SPLIT || EPI == EPI_SPLIT) {   // the operand format of the next GEMM = this one's

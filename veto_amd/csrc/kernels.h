@@ -26,10 +26,12 @@ struct GemmArgs {
   int k_splits;          // EPI_ATOMIC: the reduction K is cut into this many equal ranges (K/32 % k_splits == 0), each a
                          // tile of its own that ADDS into c with fp32 atomics (c zero-initialised); 0/1 = one range
   // EPI_RESID_DROP (training only): EPI_RESID with dropout on (A.W^T + bias) before the residual is added; element (row, col) uses index
-  // row * N + col of site drop_seed.  drop_thresh = p * 2^24 (0 = off), drop_scale = 1 / (1 - p)
+  // (row * drop_row_step) * N + col of site drop_seed.  drop_thresh = p * 2^24 (0 = off), drop_scale = 1 / (1 - p); drop_row_step: 1, or 19
+  // where the rows are the compact CLS rows of the last layer (row p = token row 19 p: the numbering of include/veto_amd.h)
   unsigned long long drop_seed;
   unsigned drop_thresh;
   float drop_scale;
+  int drop_row_step;
   int tiles_m, tiles_n;  // filled by the launcher
   // tn (EPI_ATOMIC only, weight gradients): C[M, N] += A^T B with BOTH operands row-major in the reduction index, i.e. the
   // split rows the backward already holds: a = dY split rows [k_valid, lda] (M = its column count), w = X split rows
@@ -565,12 +567,13 @@ hipError_t launch_attention_backward(const float* qkv, const float* dout, float*
 // layernorm_backward_partial_floats(rows) floats
 size_t layernorm_backward_partial_floats(int rows);
 // split_out / colp (both or neither): also write the result's split rows [rows, 2 * 576] (with the dropout mask of site drop_seed applied
-// when drop_thresh != 0: element (row, col) -> index row * 576 + col) and layernorm_backward_col_partials(rows) rows of column sums [*, 576]
+// when drop_thresh != 0: element (row, col) -> index (row * drop_row_step) * 576 + col) and layernorm_backward_col_partials(rows) rows of column sums [*, 576]
 // of those rows -- what launch_prep_grad would produce from dx, for the Linear behind this LayerNorm in the backward chain
 int layernorm_backward_col_partials(int rows);
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
                                      float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out = nullptr,
-                                     float* colp = nullptr, unsigned long long drop_seed = 0, unsigned drop_thresh = 0, float drop_scale = 1.f);
+                                     float* colp = nullptr, unsigned long long drop_seed = 0, unsigned drop_thresh = 0, float drop_scale = 1.f,
+                                     int drop_row_step = 1);
 // out[c] = sum_r dy[r][c]; partial: workspace [n_chunks, n_cols]; column_sums_chunks() chunks keep every stage short
 int column_sums_chunks();
 hipError_t launch_column_sums(const float* dy, long ld, int rows, int n_cols, float* out, float* partial, int n_chunks, hipStream_t s);
@@ -584,9 +587,10 @@ enum GradXformMode { XF_NONE = 0, XF_GELU = 1, XF_DROP = 2 };
 struct GradXform {
   int mode = XF_NONE;
   const float* pre = nullptr;           // XF_GELU: pre-activation [M, ld]
-  unsigned long long seed = 0;          // XF_DROP
+  unsigned long long seed = 0;          // XF_DROP: element (m, n) -> index (m * row_step) * N + n
   unsigned thresh = 0;
   float scale = 1.f;
+  int row_step = 1;
 };
 hipError_t launch_prep_grad(const float* src, long ld, int M, int N, __bf16* rows_out, int Mp, float* col_partial,
                             const GradXform& xf, hipStream_t s);

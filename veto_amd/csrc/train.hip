@@ -15,7 +15,7 @@ namespace {
 // transposing LDS loads, of the weight-gradient GEMM) and, optionally, per-block column sums (bias gradient, folded later).
 // 32 (m) x 64 (n) tile through LDS.
 // XF folds the elementwise op that precedes the Linear's output in the backward chain into the load: XF_GELU multiplies by
-// gelu'(pre) (model_veto.py:140, exact erf), XF_DROP applies the counter-based dropout mask of the forward (element m * N + n).
+// gelu'(pre) (model_veto.py:140, exact erf), XF_DROP applies the counter-based dropout mask of the forward (element (m * row_step) * N + n).
 template <int XF>
 __global__ __launch_bounds__(256) void prep_grad_kernel(const float* __restrict__ src, long ld, int M, int N, __bf16* __restrict__ rows_out,
                                                         float* __restrict__ col_partial, GradXform xf) {
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void prep_grad_kernel(const float* __restrict_
         const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
         v = v * (cdf + x * pdf);
       }
-      if constexpr (XF == XF_DROP) v = dropout_keep(xf.seed, (size_t)m * N + n, xf.thresh) ? v * xf.scale : 0.f;
+      if constexpr (XF == XF_DROP) v = dropout_keep(xf.seed, (size_t)m * xf.row_step * N + n, xf.thresh) ? v * xf.scale : 0.f;
     }
     t[ty * 8 + i][tx] = v;
   }
