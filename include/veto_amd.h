@@ -21,6 +21,7 @@
  *   veto_rpn_proposals     <- RPNPostProcessor                      rpn/inference.py:13-183
  *   veto_box_match         <- FastRCNNSampling.assign_label_to_proposals / prepare_targets   roi_heads/box_head/sampling.py:34-82, 118-133
  *   veto_box_subsample     <- BalancedPositiveNegativeSampler + FastRCNNSampling.subsample    balanced_positive_negative_sampler.py:37-66
+ *   veto_rpn_loss          <- RPNLossComputation (prepare_targets, __call__) and its backward   rpn/loss.py:21-157
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -571,6 +572,79 @@ typedef struct veto_box_subsample_args {
 } veto_box_subsample_args_t;
 
 int veto_box_subsample(void* stream, const veto_box_subsample_args_t* args);
+
+/* veto_rpn_loss: RPNLossComputation (rpn/loss.py:21-157) for a batch of n_img images over n_lvl pyramid levels: anchor matching,
+ * fg/bg sampling, both losses and their gradients w.r.t. the RPN head's outputs.  Seven launches whatever n_img and n_lvl are, three
+ * when only the per-anchor outputs are asked for; nothing is copied to the host and nothing synchronises.  The [n_gt, n_anchor] IoU
+ * matrix is never stored and nothing is permuted or concatenated.  Levels as in veto_rpn_proposals: anchors[l] [A H W, 4] xyxy with
+ * anchor (h W + w) A + a, shared by the images; an image's anchor index is the level's offset plus the index in the level (the
+ * order of cat_boxlist, loss.py:104, and concat_box_prediction_layers, rpn/utils.py:17-45); n_anchor = the sum of A H W.
+ *   Matching (match_targets_to_anchors, loss.py:42-54; matcher.py:42-112): per anchor the maximum of boxlist_iou(target, anchor)
+ *   (TO_REMOVE 1, fp32, bit-equal to the reference's matrix) over the image's GT boxes and the lowest GT index that reaches it;
+ *   matched_idxs = that index when the maximum >= high_threshold, -2 in [low_threshold, high_threshold), -1 below.  With
+ *   allow_low_quality_matches (set_low_quality_matches_, :83-112) an anchor whose IoU with any GT j equals the largest IoU any
+ *   anchor has with j gets its argmax back; a GT that overlaps no anchor (largest IoU 0) restores every anchor that has IoU 0
+ *   with it, as the reference's equality mask does.
+ *   labels (loss.py:65-79, generate_rpn_labels): 1 where matched_idxs >= 0, 0 where -1, then -1 where the anchor is not visible,
+ *   then -1 where -2.  Visible (anchor_generator.py:97-110): x1 >= -straddle_thresh, y1 >= -straddle_thresh,
+ *   x2 < width + straddle_thresh, y2 < height + straddle_thresh with the image's own size; straddle_thresh < 0: every anchor.
+ *   regression_targets: BoxCoder.encode (box_coder.py:22-50) of the anchor against GT box max(matched_idxs, 0).
+ *   Sampling (balanced_positive_negative_sampler.py:37-66), the convention of veto_box_subsample: positives are labels >= 1,
+ *   negatives labels == 0; num_pos = min(positives, num_pos_per_img), num_neg = min(negatives, batch_size_per_image - num_pos);
+ *   a class above its quota keeps the members with the smallest (hash, anchor index), hash = the upper 32 bits of a counter-based
+ *   hash of (seed, image index, class, anchor index).  For one label vector, this call and veto_box_subsample pick the same rows
+ *   from the same seed.  An image's rows depend only on the seed, its index and its own labels.  Image i writes counts[2 i] +
+ *   counts[2 i + 1] anchor indices (inside the image, ascending) from sampled_inds[i * batch_size_per_image].
+ *   Losses (loss.py:107-131), S = the sampled anchors of the batch, P its sampled positives: losses[0] = objectness_loss = the
+ *   mean over S of max(x, 0) - x y + log1p(exp(-|x|)); losses[1] = box_loss = the sum over P and the four coordinates of
+ *   smooth-L1 (layers/smooth_l1_loss.py: 0.5 d^2 / beta below beta, |d| - 0.5 beta from beta on) divided by S.  The logit of anchor
+ *   (h W + w) A + a of level l is objectness[l][img, a, h, w], its deltas box_regression[l][img, 4 a + c, h, w].  The terms are
+ *   evaluated in double from the fp32 inputs and summed in a fixed order: two calls give the same bits.  P = 0: box_loss 0;
+ *   S = 0: both NaN (the mean of nothing).
+ *   Gradients for an upstream gradient of 1, into tensors of the head outputs' own shapes, which the call fills itself:
+ *   (sigmoid(x) - y) / S at the sampled logits, the smooth-L1 derivative / S at the sampled positives' deltas, 0 elsewhere.
+ * The call stops after the last stage a requested output needs: losses or gradients -> all of it; else sampled_inds or counts ->
+ * matching and sampling; else matching alone (prepare_targets).  At least one output must be given.
+ * Limits, checked on the host fields before anything is launched: n_lvl 1..VETO_RPN_MAX_LEVELS; 1..256 GT boxes per image (an
+ * empty image is refused with the reference's message); 1..1048576 anchors per image; batch_size_per_image 1..2048. */
+typedef struct veto_rpn_loss_args {
+  int32_t struct_size;
+  int32_t n_img, n_lvl, n_tgt;
+  int32_t batch_size_per_image;       /* MODEL.RPN.BATCH_SIZE_PER_IMAGE, 1..2048 */
+  int32_t num_pos_per_img;            /* int(BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION), 0..batch_size_per_image */
+  int32_t allow_low_quality_matches;  /* Matcher(..., allow_low_quality_matches): True in make_rpn_loss_evaluator */
+  int32_t reserved0;
+  float high_threshold;               /* MODEL.RPN.FG_IOU_THRESHOLD */
+  float low_threshold;                /* MODEL.RPN.BG_IOU_THRESHOLD, <= high_threshold */
+  float straddle_thresh;              /* MODEL.RPN.STRADDLE_THRESH; < 0: every anchor is visible */
+  float reserved1;
+  float reg_weights[4];               /* the RPN's BoxCoder weights, (1, 1, 1, 1) */
+  double beta;                        /* smooth-L1 beta, 1 / 9 (loss.py:123) */
+  uint64_t seed;
+  int32_t level_a[VETO_RPN_MAX_LEVELS];   /* HOST: anchors per location, height and width of every level */
+  int32_t level_h[VETO_RPN_MAX_LEVELS];
+  int32_t level_w[VETO_RPN_MAX_LEVELS];
+  const float* objectness[VETO_RPN_MAX_LEVELS];      /* device [n_img, A, H, W]; read by the loss stage only */
+  const float* box_regression[VETO_RPN_MAX_LEVELS];  /* device [n_img, 4A, H, W]; read by the loss stage only */
+  const float* anchors[VETO_RPN_MAX_LEVELS];         /* device [A H W, 4] xyxy, 16-byte aligned */
+  float* d_objectness[VETO_RPN_MAX_LEVELS];          /* optional out device, the shape of objectness[l]; all levels or none */
+  float* d_box_regression[VETO_RPN_MAX_LEVELS];      /* optional out device, the shape of box_regression[l]; with d_objectness */
+  const float* image_sizes;           /* device [n_img, 2]: (width, height) */
+  const float* tgt_boxes;             /* device [n_tgt, 4] xyxy, 16-byte aligned */
+  const int32_t* img_tgt_offset;      /* device [n_img + 1] */
+  const int32_t* img_tgt_offset_host; /* HOST copy: the limits are checked on it */
+  float* losses;                      /* out device [2]: objectness_loss, box_loss; required with the gradients */
+  float* labels;                      /* optional out device [n_img, n_anchor] */
+  int64_t* matched_idxs;              /* optional out device [n_img, n_anchor] */
+  float* regression_targets;          /* optional out device [n_img, n_anchor, 4], 16-byte aligned */
+  int64_t* sampled_inds;              /* optional out device [n_img, batch_size_per_image] */
+  int32_t* counts;                    /* optional out device [n_img, 2]: sampled positives, sampled negatives */
+} veto_rpn_loss_args_t;
+
+/* reads the host fields of `args` only (n_img, n_lvl, n_tgt, batch_size_per_image, level_a / level_h / level_w); 0 when they are
+ * out of range */
+size_t veto_rpn_loss_workspace_bytes(const veto_rpn_loss_args_t* args);
+int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

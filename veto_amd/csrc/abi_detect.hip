@@ -1,6 +1,6 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
-// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, ROI pooling and the evaluator.  Each checks its argument struct,
-// carves its workspace and makes one launch (kernels.h).
+// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, ROI pooling and the evaluator.
+// Each checks its argument struct, carves its workspace and makes one launch call (kernels.h).
 #include <cmath>
 
 #include "abi_internal.h"
@@ -508,6 +508,111 @@ int veto_box_subsample(void* stream, const veto_box_subsample_args_t* a) {
   p.n_img = a->n_img; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img; p.seed = a->seed;
   p.sampled = a->sampled_inds; p.counts = a->counts;
   HIP_TRY(launch_box_subsample(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// the host fields of the RPN loss arguments: anchors per image, or -1 (error set)
+static int rpn_loss_check_shapes(const veto_rpn_loss_args_t* a) {
+  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
+  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  if (a->n_tgt < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_tgt %d)", a->n_tgt);
+  if (a->batch_size_per_image < 1 || a->batch_size_per_image > rpn_loss_max_batch())
+    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (MODEL.RPN.BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
+                rpn_loss_max_batch());
+  int64_t n_anchor = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
+      return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+    n_anchor += (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+    if (n_anchor > rpn_loss_max_anchors())
+      return fail(VETO_ERR_INVALID, "levels 0..%d: an image holds %lld anchors, the limit is %d", l, (long long)n_anchor, rpn_loss_max_anchors());
+  }
+  return (int)n_anchor;
+}
+
+// workspace: gtmax | labels | matched | sampled | counts | partial | hist
+size_t veto_rpn_loss_workspace_bytes(const veto_rpn_loss_args_t* a) {
+  if (!a || a->struct_size != (int32_t)sizeof(veto_rpn_loss_args_t)) return 0;
+  const int n_anchor = rpn_loss_check_shapes(a);
+  if (n_anchor < 0) return 0;
+  const size_t rows = (size_t)a->n_img * n_anchor;
+  return align_up((size_t)a->n_tgt * 4 + 4, 256) + 2 * align_up(rows * 4, 256) + align_up((size_t)a->n_img * a->batch_size_per_image * 4, 256) +
+         align_up((size_t)a->n_img * 8, 256) + align_up((size_t)a->n_img * 16, 256) + align_up((size_t)a->n_img * 2048, 256);
+}
+
+int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_rpn_loss_args_t)) return fail(VETO_ERR_INVALID, "veto_rpn_loss_args_t size mismatch");
+  const int n_anchor = rpn_loss_check_shapes(a);
+  if (n_anchor < 0) return n_anchor;
+  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
+    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
+                a->batch_size_per_image);
+  if (!(a->low_threshold <= a->high_threshold))
+    return fail(VETO_ERR_INVALID, "low_threshold %g must be <= high_threshold %g (BG_IOU_THRESHOLD, FG_IOU_THRESHOLD)", a->low_threshold,
+                a->high_threshold);
+  if (!a->img_tgt_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_tgt_offset_host");
+  if (check_box_sample_offsets(a->img_tgt_offset_host, a->n_img, a->n_tgt, rpn_loss_max_gt(), "img_tgt_offset_host", "n_tgt", kNoGtBoxes) < 0)
+    return VETO_ERR_INVALID;
+  int n_grad = 0;
+  for (int l = 0; l < a->n_lvl; ++l) n_grad += (a->d_objectness[l] != nullptr) + (a->d_box_regression[l] != nullptr);
+  if (n_grad != 0 && n_grad != 2 * a->n_lvl)
+    return fail(VETO_ERR_INVALID, "d_objectness and d_box_regression: every level of both or none (%d of %d given)", n_grad, 2 * a->n_lvl);
+  if (n_grad && !a->losses) return fail(VETO_ERR_INVALID, "missing pointer: losses (required with the gradients)");
+  const int last_stage = a->losses ? kRpnLossLoss : (a->sampled_inds || a->counts) ? kRpnLossSample : kRpnLossMatch;
+  if (last_stage == kRpnLossMatch && !a->labels && !a->matched_idxs && !a->regression_targets)
+    return fail(VETO_ERR_INVALID, "no output requested");
+  if (last_stage == kRpnLossLoss || a->regression_targets) {
+    if (!(a->beta > 0.0) && last_stage == kRpnLossLoss) return fail(VETO_ERR_INVALID, "beta %g must be > 0", a->beta);
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(a->reg_weights[k])) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g", k, a->reg_weights[k]);
+  }
+  for (int l = 0; l < a->n_lvl; ++l) {
+    if (!a->anchors[l] || (last_stage == kRpnLossLoss && (!a->objectness[l] || !a->box_regression[l])))
+      return fail(VETO_ERR_INVALID, "missing pointer: level %d", l);
+    if (((uintptr_t)a->anchors[l] & 15) != 0) return fail(VETO_ERR_INVALID, "anchors[%d] must be 16-byte aligned", l);
+    if ((((uintptr_t)a->objectness[l] | (uintptr_t)a->box_regression[l] | (uintptr_t)a->d_objectness[l] | (uintptr_t)a->d_box_regression[l]) & 3) != 0)
+      return fail(VETO_ERR_INVALID, "level %d: misaligned floats", l);
+  }
+  if (!a->image_sizes || !a->tgt_boxes || !a->img_tgt_offset) return fail(VETO_ERR_INVALID, "missing pointer");
+  if ((((uintptr_t)a->tgt_boxes | (uintptr_t)a->regression_targets) & 15) != 0)
+    return fail(VETO_ERR_INVALID, "tgt_boxes and regression_targets must be 16-byte aligned");
+  const size_t need = veto_rpn_loss_workspace_bytes(a);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  RpnLossArgs p{};
+  RpnFillArgs fill{};
+  const size_t rows = (size_t)a->n_img * n_anchor;
+  char* base = (char*)workspace;
+  p.gtmax = (uint32_t*)base; base += align_up((size_t)a->n_tgt * 4 + 4, 256);
+  p.labels_ws = a->labels ? a->labels : (float*)base; base += align_up(rows * 4, 256);
+  p.matched_ws = (int32_t*)base; base += align_up(rows * 4, 256);
+  p.sampled_ws = (int32_t*)base; base += align_up((size_t)a->n_img * a->batch_size_per_image * 4, 256);
+  p.counts_ws = (int32_t*)base; base += align_up((size_t)a->n_img * 8, 256);
+  p.partial = (double*)base; base += align_up((size_t)a->n_img * 16, 256);
+  p.hist = (int32_t*)base;
+  fill.ptr[0] = (float*)p.gtmax; fill.n[0] = a->n_tgt; fill.n_seg = 1;
+  if (last_stage >= kRpnLossSample) { fill.ptr[1] = (float*)p.hist; fill.n[1] = (long long)a->n_img * 512; fill.n_seg = 2; }
+  int off = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    RpnLossLevel& v = p.lvl[l];
+    v.objectness = a->objectness[l]; v.regression = a->box_regression[l]; v.anchors = a->anchors[l];
+    v.d_objectness = a->d_objectness[l]; v.d_regression = a->d_box_regression[l];
+    v.A = a->level_a[l]; v.HW = a->level_h[l] * a->level_w[l]; v.N = v.A * v.HW; v.off = off;
+    off += v.N;
+    if (n_grad) {
+      fill.ptr[fill.n_seg] = v.d_objectness; fill.n[fill.n_seg++] = (long long)a->n_img * v.N;
+      fill.ptr[fill.n_seg] = v.d_regression; fill.n[fill.n_seg++] = (long long)a->n_img * v.N * 4;
+    }
+  }
+  p.image_sizes = a->image_sizes; p.tgt_boxes = a->tgt_boxes; p.tgt_off = a->img_tgt_offset;
+  p.n_img = a->n_img; p.n_lvl = a->n_lvl; p.n_anchor = n_anchor; p.batch = a->batch_size_per_image; p.num_pos = a->num_pos_per_img;
+  p.allow_lowq = a->allow_low_quality_matches != 0;
+  p.high = a->high_threshold; p.low = a->low_threshold; p.straddle = a->straddle_thresh;
+  p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
+  p.beta = a->beta; p.seed = a->seed;
+  p.losses = a->losses; p.matched = a->matched_idxs; p.targets = a->regression_targets; p.sampled = a->sampled_inds; p.counts = a->counts;
+  HIP_TRY(launch_rpn_loss(p, fill, last_stage, (hipStream_t)stream));
   return VETO_OK;
 }
 

@@ -31,16 +31,6 @@ constexpr int kTile = 256;
 enum { kPickPos = 0, kPickNeg = 1 };
 enum : uint8_t { kIgnore = 0, kPos = 1, kNeg = 2 };
 
-// BoxCoder.encode of one proposal against one GT box (TO_REMOVE = 1), in the reference's order of operations
-__device__ __forceinline__ float4 encode_box(const float4 g, const float4 p, float wx, float wy, float ww, float wh) {
-#pragma clang fp contract(off)
-  const float ex_w = (p.z - p.x) + 1.f, ex_h = (p.w - p.y) + 1.f;
-  const float ex_cx = p.x + 0.5f * ex_w, ex_cy = p.y + 0.5f * ex_h;
-  const float gt_w = (g.z - g.x) + 1.f, gt_h = (g.w - g.y) + 1.f;
-  const float gt_cx = g.x + 0.5f * gt_w, gt_cy = g.y + 0.5f * gt_h;
-  return make_float4((wx * (gt_cx - ex_cx)) / ex_w, (wy * (gt_cy - ex_cy)) / ex_h, ww * logf(gt_w / ex_w), wh * logf(gt_h / ex_h));
-}
-
 __global__ __launch_bounds__(kTile) void box_match_kernel(BoxMatchArgs a) {
   __shared__ float4 s_gt[kMaxGt];
   const int img = blockIdx.y, tid = threadIdx.x;

@@ -471,6 +471,48 @@ int box_subsample_max_batch();
 hipError_t launch_box_match(const BoxMatchArgs& a, int largest_prp, hipStream_t s);
 hipError_t launch_box_subsample(const BoxSubsampleArgs& a, hipStream_t s);
 
+// ---- detector training: the RPN loss -- anchor matching, sampling, both losses and their gradients (rpnloss.hip) ------
+struct RpnLossLevel {
+  const float* objectness;       // [n_img, A, H, W]; read by the loss stage only
+  const float* regression;       // [n_img, 4A, H, W]
+  const float* anchors;          // [A * H * W, 4] xyxy, anchor (h * W + w) * A + a, 16-byte aligned
+  float* d_objectness;           // optional out, the shape of objectness
+  float* d_regression;           // optional out, the shape of regression
+  int A, HW, N, off;             // N = A * HW; off = the image-anchor index of the level's first anchor
+};
+struct RpnLossArgs {
+  RpnLossLevel lvl[kRpnMaxLevels];
+  const float* image_sizes;      // [n_img, 2] (width, height)
+  const float* tgt_boxes;        // [n_tgt, 4] xyxy, 16-byte aligned
+  const int32_t* tgt_off;        // [n_img + 1]
+  int n_img, n_lvl, n_anchor, batch, num_pos, allow_lowq;
+  float high, low, straddle, wx, wy, ww, wh;
+  double beta;
+  uint64_t seed;
+  uint32_t* gtmax;               // workspace [n_tgt]: highest_quality_foreach_gt as bit patterns, zeroed by the call
+  float* labels_ws;              // [n_img, n_anchor]: the labels output when it is given, else workspace
+  int32_t* matched_ws;           // workspace [n_img, n_anchor]
+  int32_t* hist;                 // workspace [n_img, 2, 256]: per class the histogram of the sampler keys' top 8 bits, zeroed by the call
+  int32_t* sampled_ws;           // workspace [n_img, batch]
+  int32_t* counts_ws;            // workspace [n_img, 2]
+  double* partial;               // workspace [n_img, 2]: the image's two sums
+  float* losses;                 // out [2]: objectness_loss, box_loss
+  int64_t* matched;              // optional out [n_img, n_anchor]
+  float* targets;                // optional out [n_img, n_anchor, 4], 16-byte aligned
+  int64_t* sampled;              // optional out [n_img, batch]: anchor indices inside the image, ascending
+  int32_t* counts;               // optional out [n_img, 2]: sampled positives, sampled negatives
+};
+struct RpnFillArgs {             // the tensors the call zeroes first, as floats
+  float* ptr[2 * kRpnMaxLevels + 2];
+  long long n[2 * kRpnMaxLevels + 2];
+  int n_seg;
+};
+enum { kRpnLossMatch = 0, kRpnLossSample = 1, kRpnLossLoss = 2 };   // the stage a call stops after
+int rpn_loss_max_gt();
+int rpn_loss_max_anchors();
+int rpn_loss_max_batch();
+hipError_t launch_rpn_loss(const RpnLossArgs& a, const RpnFillArgs& fill, int last_stage, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

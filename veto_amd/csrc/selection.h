@@ -1,7 +1,7 @@
 // Device helpers shared by the per-image pair kernels of sgdet.hip (test pairs), relsample.hip and gtbox_relsample.hip
-// (training pairs) and the box head's sampler of boxsample.hip: the reference's box IoU arithmetic, the order-preserving float
-// key, the block-wide scan of their radix selects and, for the training samplers, the counter-based hash, the radix select and
-// the bitonic sort.
+// (training pairs), the box head's sampler of boxsample.hip and the RPN loss of rpnloss.hip: the reference's box IoU and box
+// encoding arithmetic, the order-preserving float key, the block-wide scan of their radix selects and, for the training
+// samplers, the counter-based hash, the radix select and the bitonic sort.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +18,16 @@ __device__ __forceinline__ float boxlist_iou(const float* bi, const float* bj) {
   const float area_i = ((bi[2] - bi[0]) + 1.f) * ((bi[3] - bi[1]) + 1.f);
   const float area_j = ((bj[2] - bj[0]) + 1.f) * ((bj[3] - bj[1]) + 1.f);
   return inter / ((area_i + area_j) - inter);
+}
+
+// BoxCoder.encode of one proposal (or anchor) against one GT box (TO_REMOVE = 1), in the reference's order of operations
+__device__ __forceinline__ float4 encode_box(const float4 g, const float4 p, float wx, float wy, float ww, float wh) {
+#pragma clang fp contract(off)
+  const float ex_w = (p.z - p.x) + 1.f, ex_h = (p.w - p.y) + 1.f;
+  const float ex_cx = p.x + 0.5f * ex_w, ex_cy = p.y + 0.5f * ex_h;
+  const float gt_w = (g.z - g.x) + 1.f, gt_h = (g.w - g.y) + 1.f;
+  const float gt_cx = g.x + 0.5f * gt_w, gt_cy = g.y + 0.5f * gt_h;
+  return make_float4((wx * (gt_cx - ex_cx)) / ex_w, (wy * (gt_cy - ex_cy)) / ex_h, ww * logf(gt_w / ex_w), wh * logf(gt_h / ex_h));
 }
 
 // order-preserving map of a float onto uint32 (larger float -> larger key)

@@ -134,6 +134,18 @@ class VetoBoxSubsampleArgs(Structure):
                [(n, c_void_p) for n in ("labels", "img_prp_offset", "img_prp_offset_host", "sampled_inds", "counts")]
 
 
+class VetoRpnLossArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_lvl", "n_tgt", "batch_size_per_image", "num_pos_per_img",
+                                       "allow_low_quality_matches", "reserved0")] + \
+               [(n, ctypes.c_float) for n in ("high_threshold", "low_threshold", "straddle_thresh", "reserved1")] + \
+               [("reg_weights", ctypes.c_float * 4), ("beta", c_double), ("seed", ctypes.c_uint64)] + \
+               [(n, c_int32 * RPN_MAX_LEVELS) for n in ("level_a", "level_h", "level_w")] + \
+               [(n, c_void_p * RPN_MAX_LEVELS) for n in ("objectness", "box_regression", "anchors", "d_objectness",
+                                                         "d_box_regression")] + \
+               [(n, c_void_p) for n in ("image_sizes", "tgt_boxes", "img_tgt_offset", "img_tgt_offset_host", "losses", "labels",
+                                        "matched_idxs", "regression_targets", "sampled_inds", "counts")]
+
+
 class VetoPostMeetArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_obj", "n_pair", "n_groups", "n_rel_cls", "n_obj_cls")] + \
                [(n, c_void_p) for n in ("group_logits", "group_widths", "incre_idx_list", "obj_logits", "rel_pairs",
@@ -179,6 +191,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
     "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
+    "veto_rpn_loss_args_t": VetoRpnLossArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
 }
 
@@ -234,6 +247,8 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_box_postprocess_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
     "veto_rpn_proposals": _sig(_P, POINTER(VetoRpnArgs), _P, _Z),
     "veto_rpn_proposals_workspace_bytes": _sig(POINTER(VetoRpnArgs), ret=_Z),
+    "veto_rpn_loss": _sig(_P, POINTER(VetoRpnLossArgs), _P, _Z),
+    "veto_rpn_loss_workspace_bytes": _sig(POINTER(VetoRpnLossArgs), ret=_Z),
     "veto_train_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
     "veto_grad_floats": _sig(_P, ret=_Z),
     "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),

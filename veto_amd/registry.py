@@ -105,3 +105,21 @@ def install_box_sampling_ops():
         head.make_roi_box_samp_processor = boxsampling.make_roi_box_samp_processor
         patched.append(("pysgg.modeling.roi_heads.box_head.box_head", "make_roi_box_samp_processor"))
     return patched
+
+
+def install_rpn_loss_ops():
+    """Point the reference's RPN at the device loss: `pysgg.modeling.rpn.loss.make_rpn_loss_evaluator` returns
+    veto_amd.rpnloss.RPNLossComputation (anchor matching, fg/bg sampling, both losses and their gradients in one call).  `pysgg`
+    must be importable.  Independent of install(), install_detector_ops(), install_rpn_ops() and install_box_sampling_ops().
+    Returns the patched (module, name) pairs."""
+    import importlib
+    import sys
+    from . import rpnloss
+    setattr(importlib.import_module("pysgg.modeling.rpn.loss"), "make_rpn_loss_evaluator", rpnloss.make_rpn_loss_evaluator)
+    patched = [("pysgg.modeling.rpn.loss", "make_rpn_loss_evaluator")]
+    # rpn.py binds the factory by name when it is imported (rpn.py:9): re-point that binding too if it exists
+    head = sys.modules.get("pysgg.modeling.rpn.rpn")
+    if head is not None and hasattr(head, "make_rpn_loss_evaluator"):
+        head.make_rpn_loss_evaluator = rpnloss.make_rpn_loss_evaluator
+        patched.append(("pysgg.modeling.rpn.rpn", "make_rpn_loss_evaluator"))
+    return patched

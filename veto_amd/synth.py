@@ -585,3 +585,29 @@ def synthetic_rpn_outputs(seed, n_img, grid_sizes, A=3, W=800, H=608, peaks=6, b
         reg = normal(seed, tag + ".reg", (n_img, A, 4, gh, gw), 0.0, 1.0).astype(np.float64) * np.asarray(delta)[None, None, :, None, None]
         regression.append(reg.reshape(n_img, 4 * A, gh, gw).astype(np.float32))
     return {"objectness": objectness, "box_regression": regression}
+
+
+# ---------------------------------------------------------------------------
+# RPN training: GT boxes per image and the RPN head's raw outputs per level
+# ---------------------------------------------------------------------------
+
+def synthetic_rpn_training_batch(seed, image_sizes, level_shapes, n_gt, min_side=24.0, logit_std=2.0, delta_std=0.5):
+    """What one RPN training step is given besides its anchors (anchor_grid): per image `tgt_boxes` [n_gt[i], 4] xyxy inside
+    the image ((width, height) = image_sizes[i]; sides between min_side and 0.6 of the image's), per level (A, H, W) =
+    level_shapes[l] `objectness` [n_img, A, H, W] logits and `box_regression` [n_img, 4A, H, W].  The deltas are of the size of
+    the regression targets of matched anchors, so the smooth-L1 residuals fall on both sides of beta."""
+    n_img = len(image_sizes)
+    tgt = []
+    for i, ((W, H), m) in enumerate(zip(image_sizes, n_gt)):
+        tag = "rpntrain.%d.%d" % (i, m)
+        w = uniform(seed, tag + ".w", (m,), min_side, 0.6 * W).astype(np.float64)
+        h = uniform(seed, tag + ".h", (m,), min_side, 0.6 * H).astype(np.float64)
+        x1 = uniform01(seed, tag + ".x", m) * (W - 1 - w)
+        y1 = uniform01(seed, tag + ".y", m) * (H - 1 - h)
+        tgt.append(np.stack([x1, y1, x1 + w, y1 + h], 1).astype(np.float32))
+    objectness, regression = [], []
+    for l, (A, H, W) in enumerate(level_shapes):
+        tag = "rpntrain.%d.%dx%dx%d" % (l, A, H, W)
+        objectness.append(normal(seed, tag + ".obj", (n_img, A, H, W), 0.0, logit_std))
+        regression.append(normal(seed, tag + ".reg", (n_img, 4 * A, H, W), 0.0, delta_std))
+    return {"tgt_boxes": tgt, "objectness": objectness, "box_regression": regression}
