@@ -9,7 +9,8 @@ them targets torch 1.4 and is replaced by a ctypes binding) into oracle/_ref/lib
 tests/golden/make_golden.py::run_roialign drives it through the reference's own ROIAlign layer (layers/roi_align.py) and Pooler
 (modeling/poolers.py: LevelMapper, convert_to_roi_format, per-level dispatch, fixed 1/16 depth pooler) ->
 tests/golden/roialign_single.npz / roialign_pooler.npz.  tests/test_roi_align.py checks this file against them BIT FOR BIT
-(five (pooled, sampling ratio) shapes incl. the adaptive grid, out-of-map / sub-pixel / malformed ROIs, all four FPN levels).
+(five (pooled, sampling ratio) shapes incl. the adaptive grid, out-of-map / sub-pixel / malformed ROIs, all four FPN levels), and
+tests/test_roi_pool_cases_host.py does for the seven shapes of synth.ROI_SINGLE_CASES_MORE (every sampling ratio 1-4, pooled 1-8).
 The backward exists in the reference only as CUDA (cuda/ROIAlign_cuda.cu:178-262; ROIAlign.h:44 "Not implemented on the CPU"):
 its restatement below is pinned by the adjoint identity <pool(f), g> = <f, pool_backward(g)> against the pinned forward.
 Kept next to the goldens:
@@ -102,14 +103,19 @@ def roi_align(feat, rois, spatial_scale, pooled=8, sampling_ratio=2):
     return out
 
 
-def roi_align_backward(grad_out, rois, spatial_scale, feat_shape, pooled=8, sampling_ratio=2):
+def roi_align_backward(grad_out, rois, spatial_scale, feat_shape, pooled=8, sampling_ratio=2, stats=False):
     """RoIAlignBackwardFeature (ROIAlign_cuda.cu:178-262): every output gradient goes to the 4 taps of each of
     its samples as top_diff * w / count (:236-243).  The reference accumulates with float32 atomics in arbitrary
-    order; here the products are float32 as there and the accumulation is float64 (the order-free value)."""
+    order; here the products are float32 as there and the accumulation is float64 (the order-free value).
+    With stats=True returns (grad, K, A): K [B, H, W] int64 is the number of contributions a pixel of every plane
+    receives (a tap with weight 0 counts: the kernel adds it), A [B, C, H, W] float64 the sum of their absolute
+    values -- what an error bound of a float32 accumulation in arbitrary order is made of."""
     grad_out = np.asarray(grad_out, dtype=F)
     rois = np.asarray(rois, dtype=F)
     B, C, H, W = feat_shape
     grad = np.zeros((B, C, H, W), dtype=np.float64)
+    K = np.zeros((B, H, W), dtype=np.int64) if stats else None
+    A = np.zeros((B, C, H, W), dtype=np.float64) if stats else None
     scale = F(spatial_scale)
     for r in range(rois.shape[0]):
         b = int(rois[r, 0])
@@ -133,8 +139,12 @@ def roi_align_backward(grad_out, rois, spatial_scale, feat_shape, pooled=8, samp
                         w = (F(hy[ky] * hx[kx]), F(hy[ky] * lx[kx]), F(ly[ky] * hx[kx]), F(ly[ky] * lx[kx]))
                         taps = ((ylo[ky], xlo[kx]), (ylo[ky], xhi[kx]), (yhi[ky], xlo[kx]), (yhi[ky], xhi[kx]))
                         for wk, (yy, xx) in zip(w, taps):
-                            grad[b, :, yy, xx] += (g * wk / count).astype(np.float64)
-    return grad
+                            term = (g * wk / count).astype(np.float64)
+                            grad[b, :, yy, xx] += term
+                            if stats:
+                                K[b, yy, xx] += 1
+                                A[b, :, yy, xx] += np.abs(term)
+    return (grad, K, A) if stats else grad
 
 
 def box_area(boxes):
@@ -162,17 +172,23 @@ def to_rois(boxes_per_image):
 
 
 def pooler_forward(features, boxes_per_image, depth_features=None, scales=(0.25, 0.125, 0.0625, 0.03125), pooled=8,
-                   sampling_ratio=2):
+                   sampling_ratio=2, return_levels=False):
     """Pooler.forward with cat_all_levels=False (poolers.py:109-171), the way VETOFeatureExtractor calls it
     (roi_box_feature_extractors.py:75-121; relation_head.py:53 builds it without cat_all_levels).
     features: list of per-level [B, C, H_l, W_l]; every ROI is pooled from ITS level (LevelMapper) with that
     level's scale; the depth map is always pooled with poolers[2] (scale 1/16, :144-153) when there are
-    several levels, with poolers[0] otherwise.  Returns (rgb [R, C, 8, 8], depth [R, Cd, 8, 8] or None)."""
+    several levels, with poolers[0] otherwise.  The level range follows from the first and the last scale (:86-88), so
+    three scales clamp at k_max = 4; two scales have no poolers[2] and cannot take a depth map.
+    Returns (rgb [R, C, 8, 8], depth [R, Cd, 8, 8] or None), with return_levels=True also the level index per ROI."""
     rois = to_rois(boxes_per_image)
+    if len(features) != len(scales):
+        raise ValueError("%d feature levels for %d scales" % (len(features), len(scales)))
+    if depth_features is not None and len(scales) == 2:
+        raise ValueError("the depth pooler is level 2: two scales cannot pool a depth map")
     if len(scales) == 1:
         rgb = roi_align(features[0], rois, scales[0], pooled, sampling_ratio)
         dep = roi_align(depth_features, rois, scales[0], pooled, sampling_ratio) if depth_features is not None else None
-        return rgb, dep
+        return (rgb, dep, np.zeros(len(rois), dtype=np.int64)) if return_levels else (rgb, dep)
     k_min = int(round(-np.log2(scales[0])))
     k_max = int(round(-np.log2(scales[-1])))
     levels = map_levels(np.concatenate([np.asarray(b, dtype=F) for b in boxes_per_image]), k_min, k_max)
@@ -185,4 +201,4 @@ def pooler_forward(features, boxes_per_image, depth_features=None, scales=(0.25,
     dep = None
     if depth_features is not None:
         dep = roi_align(depth_features, rois, scales[2], pooled, sampling_ratio)
-    return rgb, dep
+    return (rgb, dep, levels) if return_levels else (rgb, dep)

@@ -561,7 +561,7 @@ def run_roialign(BoxList):
     from pysgg.layers.roi_align import ROIAlign
     from pysgg.modeling.poolers import LevelMapper, Pooler
     out = {}
-    for pooled, ratio in synth.ROI_SINGLE_CASES:
+    for pooled, ratio in synth.ROI_SINGLE_CASES + synth.ROI_SINGLE_CASES_MORE:
         feat, rois = synth.synthetic_roi_single(pooled, ratio, channels=ROI_KEEP_CHANNELS)
         y = ROIAlign((pooled, pooled), 1.0 / 16, ratio)(torch.from_numpy(feat), torch.from_numpy(rois))
         out["rois_p%d_r%d" % (pooled, ratio)] = rois
