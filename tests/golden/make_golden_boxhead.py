@@ -19,7 +19,7 @@ on either side of the DETECTIONS_PER_IMG cut are closer than 1e-6.  The delibera
 
 Per decoder fixture, ref_fp32_err_boxes / ref_fp32_err_scores = the largest absolute difference between the reference's fp32
 outputs and the fp64 recomputation (test_boxhead_host.np_box_postprocess in float64): the GPU tests allow 4x that.
-Usage: python tests/golden/make_golden_boxhead.py"""
+Usage: python tests/golden/make_golden_boxhead.py [case ... | nms]   (no argument: every fixture)"""
 import os
 import sys
 
@@ -48,6 +48,11 @@ CASES = {
     "nothing": (151, [(1600, 30, "synth"), (-1, 10, "nothing")], {}, False),
     "below_cap": (151, [(1700, 30, "synth")], {}, False),
     "tie_cap": (151, [(-1, 3, "tie_cap")], dict(det_per_img=1), False),
+    # branches of filter_results no seeded case enters: a binding POST_NMS_PER_CLS_TOPN, and the class-major list at 300 classes
+    "topn_bind": (2, [(-1, 10, "topn_bind")], dict(topn=3, det_per_img=0), False),
+    "topn_bind_nodup": (2, [(-1, 10, "topn_bind")], dict(topn=3, det_per_img=0, filter_dup=False), False),
+    "class_major_wide": (300, [(-1, 6, "class_major")], dict(filter_dup=False, det_per_img=0), False),
+    "class_major_wide_cut": (300, [(-1, 6, "class_major")], dict(filter_dup=False, det_per_img=4), False),
 }
 NMS_SIZES = (0, 1, 2, 63, 64, 65, 1000, 6000)
 
@@ -105,7 +110,10 @@ def main():
     import pysgg.structures.boxlist_ops as ops
     pysgg.layers.nms = ops._box_nms = torch_nms
     os.makedirs(OUT, exist_ok=True)
+    only = sys.argv[1:]
     for name, (C, images, over, full) in CASES.items():
+        if only and name not in only:
+            continue
         prm = dict(VETO, **over)
         seeds, outs, err_b, err_s, dec_full = [], [], 0.0, 0.0, None
         for seed, n, kind in images:
@@ -113,6 +121,11 @@ def main():
                 got = check(BoxList, hand_built_image(kind, C), prm)
                 if kind == "nothing":   # every probability is 1 / C: not near the threshold, nothing to consult
                     assert got[3] and len(got[0]["orig_inds"]) == 0
+                elif kind == "topn_bind":   # rows 0, 1, 2 although row 9 scores best
+                    assert got[3] and got[0]["orig_inds"].tolist() == [0, 1, 2]
+                elif kind == "class_major":   # class-major, rows ascending; the cut of 4 drops row 0 and the three entries of row 5
+                    assert got[3] and got[0]["pred_labels"].tolist() == ([1, 1, 255, 256, 257, 257, 299, 299] if prm["det_per_img"] == 0
+                                                                         else [1, 255, 256, 257])
                 else:                   # the tie at the cut is the point of this image: exempt from the cut-gap rule only
                     assert len(got[0]["orig_inds"]) == 2 and prm["det_per_img"] == 1
                 s = -1
@@ -141,6 +154,8 @@ def main():
         np.savez_compressed(path, **z)
         print(name, "seeds", seeds, "counts", z["counts"].tolist(), "err boxes %.3g scores %.3g" % (err_b, err_s),
               os.path.getsize(path), "bytes")
+    if only and "nms" not in only:
+        return
     z = {}
     cases = []
     for thr in (0.7, 0.3):

@@ -21,11 +21,12 @@ different counts.
 
 `ties` is hand-built (test_rpn_host.ties_inputs); its expected output is the restatement's, i.e. the orders this project fixes
 where the reference's topk leaves ties open.  It is checked against the reference only as a set, on the rows whose membership
-the reference determines (everything but the tied logits).
+the reference determines (everything but the tied logits).  `min_size_exact` is hand-built too (min_size_exact_inputs: sides
+exactly min_size and one below it), with distinct logits: the reference determines every row and is compared row by row.
 
 Per fixture, ref_fp32_err_boxes / ref_fp32_err_objectness = the largest absolute difference between the reference's float32
 outputs and the float64 restatement: the GPU tests allow 4x that.
-Usage: python tests/golden/make_golden_rpn.py"""
+Usage: python tests/golden/make_golden_rpn.py [case ...]   (no case: all of them)"""
 import os
 import sys
 
@@ -44,7 +45,7 @@ from test_rpn_host import CASES, RATIOS, anchor_checksum, case_inputs, np_rpn_pr
 
 OUT = os.path.join(HERE, "rpn")
 FIRST_SEED = {"small5": 3000, "below_cap": 3100, "min_size": 3200, "one_level": 3300, "per_batch": 3400, "add_gt": 3500,
-              "full_level": 3600, "ties": -1}
+              "full_level": 3600, "ties": -1, "min_size_exact": -1}
 
 
 def ref_forward(BoxList, d, c, targets):
@@ -80,7 +81,7 @@ def attempt(BoxList, name, seed):
     ref = ref_forward(BoxList, d, c, targets)
     diag32, diag64 = {}, {}
     m32, m64 = np_rpn_proposals(d, c, np.float32, diag32), np_rpn_proposals(d, c, np.float64, diag64)
-    hand = bool(c.get("hand_built"))
+    hand = bool(c.get("hand_built")) and not c.get("determinate")   # (a determinate hand-built case is compared row by row)
     for r, a, b in zip(ref, m32, m64):
         k = len(r["boxes"]) - n_gt
         if len(a["boxes"]) != k or len(b["boxes"]) != k:
@@ -94,7 +95,7 @@ def attempt(BoxList, name, seed):
         elif np.abs(r["boxes"][:k] - a["boxes"]).max(initial=0) > 1e-3 or np.abs(r["objectness"][:k] - a["objectness"]).max(initial=0) > 1e-6:
             return None, False
     robust = True
-    if not hand:
+    if not c.get("hand_built"):
         for dg in (diag32, diag64):
             robust &= not np.any(np.abs(dg["consulted"].astype(np.float64) - c["thr"]) < 1e-5)
             if c["min_size"] > 0:
@@ -139,9 +140,13 @@ def main():
     pysgg.layers.nms = ops._box_nms = torch_nms
     os.makedirs(OUT, exist_ok=True)
     for name, c in CASES.items():
+        if sys.argv[1:] and name not in sys.argv[1:]:
+            continue
         if c.get("hand_built"):
             z, _ = attempt(BoxList, name, -1)
             assert z is not None
+            if name == "min_size_exact":   # the kept anchors are those of min_size_exact_inputs' docstring, best logit first
+                assert z["anchor_index"].tolist() == [5, 0, 3, 6] and float(z["ref_fp32_err_boxes"]) == 0.0
         else:
             check_anchors(c)
             for seed in range(FIRST_SEED[name], FIRST_SEED[name] + 200):

@@ -127,12 +127,32 @@ def fixture_params(z):
 def hand_built_image(kind, C):
     """The deliberate exact cases (not seeded).  'nothing': equal logits, every probability 1 / C < SCORE_THRESH.
     'tie_cap': rows 0 and 1 are identical (far apart as boxes), row 2 scores lower; with DETECTIONS_PER_IMG = 1 the cut value
-    is the shared score of rows 0 and 1 and BOTH stay (score >= cut, inference.py:223)."""
+    is the shared score of rows 0 and 1 and BOTH stay (score >= cut, inference.py:223).  'topn_bind' and 'class_major': the two
+    branches of filter_results that no seeded fixture enters (see below)."""
     if kind == "nothing":
         n = 10
         prop = np.stack([np.arange(n) * 20.0, np.arange(n) * 10.0, np.arange(n) * 20.0 + 50, np.arange(n) * 10.0 + 40], 1)
         return {"proposals": prop.astype(np.float32), "class_logits": np.zeros((n, C), np.float32),
                 "box_regression": np.zeros((n, 4 * C), np.float32), "image_size": (800, 600)}
+    if kind == "topn_bind":   # C = 2: ten disjoint boxes, all survive the NMS, the score rises with the row (the best is row 9);
+        n = 10               # a binding POST_NMS_PER_CLS_TOPN keeps the FIRST rows of the ascending keep list (inference.py:191-193)
+        x0 = np.arange(n) * 40.0
+        prop = np.stack([x0, x0 * 0 + 10, x0 + 29, x0 * 0 + 39], 1)
+        logits = np.zeros((n, C), np.float32)
+        logits[:, 1] = 0.25 * np.arange(n)
+        return {"proposals": prop.astype(np.float32), "class_logits": logits, "box_regression": np.zeros((n, 4 * C), np.float32),
+                "image_size": (800, 600)}
+    if kind == "class_major":   # C = 300, duplicates kept: the detection list is class-major; survivors in columns 1, 255, 256, 257, 299
+        assert C == 300
+        n = 6
+        x0 = np.arange(n) * 50.0
+        prop = np.stack([x0, x0 * 0 + 20, x0 + 39, x0 * 0 + 59], 1)
+        logits = np.full((n, C), -2.0, np.float32)
+        for r, (c, v) in enumerate(((299, 4.0), (257, 4.5), (256, 5.0), (255, 5.5), (1, 6.0))):
+            logits[r, c] = v
+        logits[5, 1], logits[5, 299], logits[5, 257] = 5.25, 4.75, 4.25   # one row in three columns, both rounds of columns
+        return {"proposals": prop.astype(np.float32), "class_logits": logits, "box_regression": np.zeros((n, 4 * C), np.float32),
+                "image_size": (800, 600)}
     assert kind == "tie_cap"
     prop = np.array([[10, 10, 60, 60], [300, 300, 350, 350], [600, 100, 650, 150]], np.float32)
     logits = np.full((3, C), -4.0, np.float32)

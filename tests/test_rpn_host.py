@@ -38,6 +38,8 @@ CASES = {
     "full_level": dict(grids=((152, 200),), images=((800, 608),), pre=6000, post=1000, fpn=1000, thr=0.7, min_size=0,
                        strides=(4,), sizes=(32,)),
     "ties": dict(grids=((4, 4), (4, 4)), images=((200, 240),), pre=10, post=100, fpn=17, thr=0.5, min_size=0, hand_built=True),
+    "min_size_exact": dict(grids=((2, 4),), images=((100, 60),), pre=8, post=8, fpn=8, thr=0.7, min_size=8, hand_built=True,
+                           determinate=True),
 }
 
 
@@ -64,6 +66,20 @@ def ties_inputs():
     return {"anchors": anchors, "objectness": obj, "box_regression": reg}
 
 
+def min_size_exact_inputs():
+    """min_size met exactly (remove_small_boxes keeps a side >= min_size, boxlist_ops.py:35-49).  One level of 8 hand-placed
+    anchors (A = 1, 2 x 4 cells), zero regressions, an image 100 wide and 60 high, min_size 8, distinct logits.  Kept: 0 (8 x 8),
+    3 (9 x 8), 5 (reaches to x = 110, clipped at 99 to exactly 8 wide), 6 (clipped at y = 59 to exactly 8 high).  Removed: 1 (7
+    wide), 2 (7 high), 4 (clipped to 7 wide: narrow only by the clip), 7 (clipped to 7 high)."""
+    a = np.array([[0, 0, 7, 7], [20, 0, 26, 7], [40, 0, 47, 6], [60, 0, 68, 7],
+                  [93, 20, 110, 30], [92, 40, 110, 50], [0, 52, 10, 70], [20, 53, 30, 70]], np.float32)
+    obj = np.array([1.0, 3.0, 2.5, 0.5, 2.0, 1.5, -0.5, 0.75], np.float32).reshape(1, 1, 2, 4)
+    return {"anchors": [a], "objectness": [obj], "box_regression": [np.zeros((1, 4, 2, 4), np.float32)]}
+
+
+HAND_BUILT = {"ties": ties_inputs, "min_size_exact": min_size_exact_inputs}
+
+
 def rpn_targets(seed, image_sizes, n):
     """n ground-truth boxes per image (xyxy) for the add_gt case."""
     out = []
@@ -78,7 +94,7 @@ def case_inputs(name, seed):
     """anchors / objectness / box_regression (lists over the levels) of a case, regenerated from its seed."""
     c = CASES[name]
     if c.get("hand_built"):
-        return ties_inputs()
+        return HAND_BUILT[name]()
     d = synth.synthetic_rpn_outputs(int(seed), len(c["images"]), c["grids"], A=len(RATIOS))
     d["anchors"] = synth.anchor_grid(c["sizes"], c["strides"], RATIOS, c["grids"])
     return d

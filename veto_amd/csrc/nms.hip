@@ -5,6 +5,7 @@
 //   * a box is suppressed by an earlier KEPT box at IoU STRICTLY GREATER than the threshold (nms.cu:60; the reference's
 //     CPU twin nms_cpu.cpp:60 uses >=, its GPU results -- what users have -- use >);
 //   * boxes are visited in the total order (score desc, index asc): the reference's sort is unstable, this one is not;
+//     equal means equal as floats: -0.0 and +0.0 are one score (float_order gives them one key);
 //   * the kept indices come back in ASCENDING index order (nms.cu:127-130), local to the segment; a cap keeps the first
 //     max_keep of that ascending list (boxlist_ops.py:29-30).
 //   Structure: 64-bit keys (~score key, index) are bitonic-sorted in LDS; the order moves to 16-bit indices and the key

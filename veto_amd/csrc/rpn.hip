@@ -3,7 +3,8 @@
 // A segment is one image x level.  Three launches (four in per-batch mode), whatever the number of images or levels; the levels'
 // shapes and pointers travel as a descriptor table inside the kernel arguments, so one grid serves all of them.
 //   rpn_select_kernel   one workgroup per segment, reading objectness / regression in place (NCHW; anchor (h W + w) A + a):
-//                       the k = min(PRE_NMS_TOP_N, A H W) best anchors by (logit desc, anchor index asc) -- radix select of the
+//                       the k = min(PRE_NMS_TOP_N, A H W) best anchors by (logit desc, anchor index asc; -0.0 and +0.0 are one
+//                       logit and leave the selector as +0.0) -- radix select of the
 //                       k-th largest logit over global memory, the candidates at or above it sorted in LDS --, then in that
 //                       order BoxCoder.decode (box_coder.py:62-95), clip_to_image(remove_empty=False) and remove_small_boxes
 //                       (boxlist_ops.py:35-49); the survivors go to the workspace, best first, with their count

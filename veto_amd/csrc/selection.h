@@ -30,9 +30,13 @@ __device__ __forceinline__ float4 encode_box(const float4 g, const float4 p, flo
   return make_float4((wx * (gt_cx - ex_cx)) / ex_w, (wy * (gt_cy - ex_cy)) / ex_h, ww * logf(gt_w / ex_w), wh * logf(gt_h / ex_h));
 }
 
-// order-preserving map of a float onto uint32 (larger float -> larger key)
+// order-preserving map of a float onto uint32 (larger float -> larger key, equal floats -> equal keys: -0.0 and +0.0 share the
+// key of +0.0, as they compare equal in the reference's sorts and in every order documented here, which then falls through to
+// the index; the raw bit pattern would put +0.0 above -0.0).  Callers: the NMS scores and RPN logits of nms.hip / rpn.hip, and
+// the pair-quality products of sgdet.hip and relsample.hip, which multiply two class probabilities (>= 0) and so never see -0.0.
 __device__ __forceinline__ uint32_t float_order(float f) {
   const uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) return 0x80000000u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
