@@ -22,6 +22,7 @@
  *   veto_box_match         <- FastRCNNSampling.assign_label_to_proposals / prepare_targets   roi_heads/box_head/sampling.py:34-82, 118-133
  *   veto_box_subsample     <- BalancedPositiveNegativeSampler + FastRCNNSampling.subsample    balanced_positive_negative_sampler.py:37-66
  *   veto_rpn_loss          <- RPNLossComputation (prepare_targets, __call__) and its backward   rpn/loss.py:21-157
+ *   veto_box_loss          <- FastRCNNLossComputation.__call__ and its backward   roi_heads/box_head/loss.py:42-84
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -645,6 +646,53 @@ typedef struct veto_rpn_loss_args {
  * out of range */
 size_t veto_rpn_loss_workspace_bytes(const veto_rpn_loss_args_t* args);
 int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_box_loss: FastRCNNLossComputation.__call__ (roi_heads/box_head/loss.py:42-84) over the n_rows proposals that
+ * FastRCNNSampling.subsample kept, all images concatenated: both losses and their gradients w.r.t. the predictor's outputs.  Two
+ * launches whatever n_rows, n_cls and the number of images; nothing is copied to the host and nothing synchronises (the
+ * reference's nonzero over labels > 0 reads its count back).  class_logits and box_regression are read in place through a row
+ * stride in elements (ld_logits, ld_reg), so a column slice of a wider tensor needs no copy; the outputs are contiguous.
+ *   losses[0] = classification_loss = F.cross_entropy(class_logits, labels): the mean over the rows of logsumexp(z) - z[y], the
+ *   row maximum subtracted before any exponential.
+ *   losses[1] = box_loss = the sum over the rows with y > 0 and the four coordinates of smooth-L1 with beta 1
+ *   (layers/smooth_l1_loss.py: n = |input - target|; 0.5 n^2 below 1, n - 0.5 from 1 on) between box_regression[r, 4y .. 4y+3]
+ *   (columns 4 .. 7 with cls_agnostic, MODEL.CLS_AGNOSTIC_BBOX_REG) and regression_targets[r], divided by n_rows -- by every
+ *   row, not by the positives (loss.py:82).  No row with y > 0: exactly 0.
+ *   The terms are evaluated in double from the fp32 inputs; each row leaves two doubles, and one workgroup folds them in row order
+ *   (thread t the rows [t ceil(n_rows / 256), (t + 1) ceil(n_rows / 256)), then the 256 sums in thread order): two calls give
+ *   the same bits.
+ *   Gradients for an upstream gradient of 1, written by the same pass, every element of both outputs:
+ *   d_class_logits[r, :] = (softmax(z) - onehot(y)) / n_rows; d_box_regression[r, :] = 0 except clamp(d, -1, 1) / n_rows at the
+ *   row's four columns when y > 0 (d = input - target; d / beta and sign(d) agree at |d| = beta).
+ *   NaN: n_rows = 0 gives both losses NaN (the mean of nothing; the reference gives NaN and 0 / 0).  A label outside [0, n_cls)
+ *   reads nothing out of bounds; it makes both losses NaN and the row's two gradient rows NaN, other rows' gradients are
+ *   unaffected (veto_ce_loss does the same for a label >= n_cls; torch raises).  That includes -100: the box head never
+ *   produces an ignored row, so no label is an ignore_index here.
+ * Limits, refused with a message before anything is launched: n_cls 2..1024 (the decoder's limit); n_rows 0..1048576;
+ * n_reg_cols a multiple of 4 and >= 4 n_cls (>= 8 with cls_agnostic); ld_logits >= n_cls, ld_reg >= n_reg_cols; the gradient
+ * outputs both or neither; regression_targets and the gradient outputs 16-byte aligned. */
+typedef struct veto_box_loss_args {
+  int32_t struct_size;
+  int32_t n_rows;                     /* labels.numel(), 0..1048576 */
+  int32_t n_cls;                      /* columns of class_logits, 2..1024 */
+  int32_t n_reg_cols;                 /* columns of box_regression: 4 n_cls, or 8 with cls_agnostic (more are allowed) */
+  int32_t cls_agnostic;               /* MODEL.CLS_AGNOSTIC_BBOX_REG */
+  int32_t reserved0;
+  int64_t ld_logits;                  /* row stride of class_logits in elements, >= n_cls */
+  int64_t ld_reg;                     /* row stride of box_regression in elements, >= n_reg_cols */
+  const float* class_logits;          /* device [n_rows, n_cls], read in place */
+  const float* box_regression;        /* device [n_rows, n_reg_cols], read in place */
+  const int64_t* labels;              /* device [n_rows] */
+  const float* regression_targets;    /* device [n_rows, 4], 16-byte aligned */
+  float* losses;                      /* out device [2]: classification_loss, box_loss */
+  float* d_class_logits;              /* optional out device [n_rows, n_cls], contiguous, 16-byte aligned; with d_box_regression */
+  float* d_box_regression;            /* optional out device [n_rows, n_reg_cols], contiguous, 16-byte aligned */
+} veto_box_loss_args_t;
+
+/* reads the host fields of `args` only (n_rows, n_cls, n_reg_cols, cls_agnostic, ld_logits, ld_reg); 0 when they are out of
+ * range */
+size_t veto_box_loss_workspace_bytes(const veto_box_loss_args_t* args);
+int veto_box_loss(void* stream, const veto_box_loss_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

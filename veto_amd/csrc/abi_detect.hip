@@ -1,5 +1,6 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
-// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, ROI pooling and the evaluator.
+// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, the box head's loss, ROI pooling and
+// the evaluator.
 // Each checks its argument struct, carves its workspace and makes one launch call (kernels.h).
 #include <cmath>
 
@@ -613,6 +614,54 @@ int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* a, void* workspace, 
   p.beta = a->beta; p.seed = a->seed;
   p.losses = a->losses; p.matched = a->matched_idxs; p.targets = a->regression_targets; p.sampled = a->sampled_inds; p.counts = a->counts;
   HIP_TRY(launch_rpn_loss(p, fill, last_stage, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// the host fields of the box loss arguments: 0, or an error (set)
+static int box_loss_check_shapes(const veto_box_loss_args_t* a) {
+  if (a->n_cls < 2 || a->n_cls > box_loss_max_cls()) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..%d", a->n_cls, box_loss_max_cls());
+  if (a->n_rows < 0 || a->n_rows > box_loss_max_rows()) return fail(VETO_ERR_INVALID, "n_rows %d outside 0..%d", a->n_rows, box_loss_max_rows());
+  const int need_cols = a->cls_agnostic ? 8 : 4 * a->n_cls;
+  if (a->n_reg_cols < need_cols || a->n_reg_cols % 4 != 0)
+    return fail(VETO_ERR_INVALID, "n_reg_cols %d must be a multiple of 4 and >= %d (%s)", a->n_reg_cols, need_cols,
+                a->cls_agnostic ? "cls_agnostic: columns 4..7" : "4 n_cls");
+  if (a->ld_logits < a->n_cls) return fail(VETO_ERR_INVALID, "ld_logits %lld is below the row width %d", (long long)a->ld_logits, a->n_cls);
+  if (a->ld_reg < a->n_reg_cols) return fail(VETO_ERR_INVALID, "ld_reg %lld is below the row width %d", (long long)a->ld_reg, a->n_reg_cols);
+  return VETO_OK;
+}
+
+// workspace: the rows' partial pairs
+size_t veto_box_loss_workspace_bytes(const veto_box_loss_args_t* a) {
+  if (!a || a->struct_size != (int32_t)sizeof(veto_box_loss_args_t)) return 0;
+  if (box_loss_check_shapes(a) != VETO_OK) return 0;
+  return align_up((size_t)a->n_rows * 16 + 16, 256);
+}
+
+int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, size_t workspace_bytes) {
+  if (!a) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(veto_box_loss_args_t)) return fail(VETO_ERR_INVALID, "veto_box_loss_args_t size mismatch");
+  const int rc = box_loss_check_shapes(a);
+  if (rc != VETO_OK) return rc;
+  if (!a->losses) return fail(VETO_ERR_INVALID, "missing pointer: losses");
+  if (a->n_rows > 0 && (!a->class_logits || !a->box_regression || !a->labels || !a->regression_targets))
+    return fail(VETO_ERR_INVALID, "missing pointer: class_logits, box_regression, labels and regression_targets are required");
+  if ((a->d_class_logits != nullptr) != (a->d_box_regression != nullptr))
+    return fail(VETO_ERR_INVALID, "d_class_logits and d_box_regression: both or neither");
+  if (((uintptr_t)a->regression_targets & 15) != 0) return fail(VETO_ERR_INVALID, "regression_targets must be 16-byte aligned");
+  if ((((uintptr_t)a->d_class_logits | (uintptr_t)a->d_box_regression) & 15) != 0)
+    return fail(VETO_ERR_INVALID, "d_class_logits and d_box_regression must be 16-byte aligned");
+  if ((((uintptr_t)a->class_logits | (uintptr_t)a->box_regression | (uintptr_t)a->losses) & 3) != 0 || ((uintptr_t)a->labels & 7) != 0)
+    return fail(VETO_ERR_INVALID, "misaligned class_logits, box_regression, losses or labels");
+  const size_t need = veto_box_loss_workspace_bytes(a);
+  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  BoxLossArgs p{};
+  p.logits = a->class_logits; p.reg = a->box_regression; p.labels = a->labels; p.targets = a->regression_targets;
+  p.n_rows = a->n_rows; p.n_cls = a->n_cls; p.n_reg_cols = a->n_reg_cols; p.cls_agnostic = a->cls_agnostic != 0;
+  p.ld_logits = a->ld_logits; p.ld_reg = a->ld_reg;
+  p.partial = (double*)workspace;
+  p.losses = a->losses; p.d_logits = a->d_class_logits; p.d_reg = a->d_box_regression;
+  HIP_TRY(launch_box_loss(p, (hipStream_t)stream));
   return VETO_OK;
 }
 

@@ -513,6 +513,23 @@ int rpn_loss_max_anchors();
 int rpn_loss_max_batch();
 hipError_t launch_rpn_loss(const RpnLossArgs& a, const RpnFillArgs& fill, int last_stage, hipStream_t s);
 
+// ---- detector training: the box head's loss -- both losses and their gradients (boxloss.hip) ------
+struct BoxLossArgs {
+  const float* logits;           // [n_rows, n_cls], row stride ld_logits elements: read in place
+  const float* reg;              // [n_rows, n_reg_cols], row stride ld_reg elements: read in place
+  const int64_t* labels;         // [n_rows]; outside [0, n_cls): the row is NaN
+  const float* targets;          // [n_rows, 4], 16-byte aligned
+  int n_rows, n_cls, n_reg_cols, cls_agnostic;
+  long long ld_logits, ld_reg;
+  double* partial;               // workspace [n_rows, 2]: the row's cross-entropy term and its box terms
+  float* losses;                 // out [2]: classification_loss, box_loss
+  float* d_logits;               // optional out [n_rows, n_cls], contiguous
+  float* d_reg;                  // with d_logits: out [n_rows, n_reg_cols], contiguous, 16-byte aligned
+};
+int box_loss_max_cls();
+int box_loss_max_rows();
+hipError_t launch_box_loss(const BoxLossArgs& a, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

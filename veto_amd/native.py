@@ -146,6 +146,13 @@ class VetoRpnLossArgs(Structure):
                                         "matched_idxs", "regression_targets", "sampled_inds", "counts")]
 
 
+class VetoBoxLossArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_rows", "n_cls", "n_reg_cols", "cls_agnostic", "reserved0")] + \
+               [("ld_logits", c_int64), ("ld_reg", c_int64)] + \
+               [(n, c_void_p) for n in ("class_logits", "box_regression", "labels", "regression_targets", "losses",
+                                        "d_class_logits", "d_box_regression")]
+
+
 class VetoPostMeetArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_obj", "n_pair", "n_groups", "n_rel_cls", "n_obj_cls")] + \
                [(n, c_void_p) for n in ("group_logits", "group_widths", "incre_idx_list", "obj_logits", "rel_pairs",
@@ -191,7 +198,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
     "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
-    "veto_rpn_loss_args_t": VetoRpnLossArgs,
+    "veto_rpn_loss_args_t": VetoRpnLossArgs, "veto_box_loss_args_t": VetoBoxLossArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
 }
 
@@ -249,6 +256,8 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_rpn_proposals_workspace_bytes": _sig(POINTER(VetoRpnArgs), ret=_Z),
     "veto_rpn_loss": _sig(_P, POINTER(VetoRpnLossArgs), _P, _Z),
     "veto_rpn_loss_workspace_bytes": _sig(POINTER(VetoRpnLossArgs), ret=_Z),
+    "veto_box_loss": _sig(_P, POINTER(VetoBoxLossArgs), _P, _Z),
+    "veto_box_loss_workspace_bytes": _sig(POINTER(VetoBoxLossArgs), ret=_Z),
     "veto_train_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
     "veto_grad_floats": _sig(_P, ret=_Z),
     "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),

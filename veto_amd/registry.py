@@ -123,3 +123,22 @@ def install_rpn_loss_ops():
         head.make_rpn_loss_evaluator = rpnloss.make_rpn_loss_evaluator
         patched.append(("pysgg.modeling.rpn.rpn", "make_rpn_loss_evaluator"))
     return patched
+
+
+def install_box_loss_ops():
+    """Point the reference's box head at the device loss: `pysgg.modeling.roi_heads.box_head.loss.make_roi_box_loss_evaluator`
+    returns veto_amd.boxloss.FastRCNNLossComputation (both losses and their gradients in one call).  `pysgg` must be importable.
+    Independent of install(), install_detector_ops(), install_rpn_ops(), install_box_sampling_ops() and install_rpn_loss_ops().
+    Returns the patched (module, name) pairs."""
+    import importlib
+    import sys
+    from . import boxloss
+    setattr(importlib.import_module("pysgg.modeling.roi_heads.box_head.loss"), "make_roi_box_loss_evaluator",
+            boxloss.make_roi_box_loss_evaluator)
+    patched = [("pysgg.modeling.roi_heads.box_head.loss", "make_roi_box_loss_evaluator")]
+    # box_head.py binds the factory by name when it is imported (box_head.py:6): re-point that binding too if it exists
+    head = sys.modules.get("pysgg.modeling.roi_heads.box_head.box_head")
+    if head is not None and hasattr(head, "make_roi_box_loss_evaluator"):
+        head.make_roi_box_loss_evaluator = boxloss.make_roi_box_loss_evaluator
+        patched.append(("pysgg.modeling.roi_heads.box_head.box_head", "make_roi_box_loss_evaluator"))
+    return patched
