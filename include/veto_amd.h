@@ -23,6 +23,7 @@
  *   veto_box_subsample     <- BalancedPositiveNegativeSampler + FastRCNNSampling.subsample    balanced_positive_negative_sampler.py:37-66
  *   veto_rpn_loss          <- RPNLossComputation (prepare_targets, __call__) and its backward   rpn/loss.py:21-157
  *   veto_box_loss          <- FastRCNNLossComputation.__call__ and its backward   roi_heads/box_head/loss.py:42-84
+ *   veto_optim_step        <- clip_grad_norm and the step of make_optimizer's Adam   utils/checkpoint.py:180-219, solver/build.py:7-34
  *
  * Conventions: every pointer marked "device" is a HIP device pointer valid on cfg.device;
  * `stream` is a hipStream_t passed as void* (NULL = default stream); all work is enqueued on that
@@ -693,6 +694,79 @@ typedef struct veto_box_loss_args {
  * range */
 size_t veto_box_loss_workspace_bytes(const veto_box_loss_args_t* args);
 int veto_box_loss(void* stream, const veto_box_loss_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_optim_step: the optimizer side of a training iteration over every parameter tensor at once: clip_grad_norm
+ * (pysgg/utils/checkpoint.py:180-219) and the step of the torch.optim.Adam that make_optimizer returns (solver/build.py:7-34,
+ * one param group, so one lr and weight_decay, per tensor).  Four modes through this one entry point; nothing is copied to the
+ * host and nothing synchronises in any of them (the reference's `if clip_coef < 1` reads the coefficient back).
+ *   VETO_OPTIM_NORMS      the norms, the total and the coefficient; gradients are not written.                    1 launch
+ *   VETO_OPTIM_CLIP       ... and every gradient is multiplied IN PLACE by the applied coefficient.  When that is exactly 1 the
+ *                         gradients are not touched, as the reference skips its mul_.                              2 launches
+ *   VETO_OPTIM_STEP       the Adam step alone; norms, total_norm, coef and max_norm are not read or written.        1 launch
+ *   VETO_OPTIM_CLIP_STEP  norms, clip and step fused: gradients are READ-ONLY, each is scaled in registers by the
+ *                         coefficient, which the step reads from device memory, and stays unscaled in memory.      2 launches
+ *   The launch counts hold whatever n_tensors is; each call also makes one host-to-device copy of its tables (below).
+ * The norm: a tensor is cut into chunks of VETO_OPTIM_CHUNK elements.  A chunk's sum of g^2 is taken by 256 threads, thread t the
+ * 16-byte groups t, t + 256, ... (the elements t, t + 256, ... where the gradient is only 4-byte aligned, and of the tail) in
+ * that order, every g converted to double BEFORE it is squared and every add in double; then a butterfly over each 64-lane wave
+ * and the four wave sums in wave order.  A tensor's sum is its chunks' in chunk order; the total is the tensors' sums, thread t
+ * the tensors [t ceil(n / 256), (t + 1) ceil(n / 256)), then the 256 sums in thread order.  No floating-point atomic: two calls
+ * on the same inputs and addresses give the same bits.  norms[i] = sqrt(sum_i) and total_norm = sqrt(total), rounded to fp32
+ * once; a tensor without a gradient or with no element has norms[i] = 0 and adds nothing.
+ * The coefficient: max_norm / (total + 1e-6) in double, rounded to fp32 once (checkpoint.py:207); coef[0], the APPLIED
+ * coefficient, is that value where it is < 1 and exactly 1.0f otherwise (checkpoint.py:208).
+ * The step, per element (torch.optim.Adam's single-tensor form without amsgrad, maximize, capturable, differentiable); g', m and v
+ * are formed in double from the fp32 operands and rounded to fp32 once each, the last line is fp32 arithmetic on those fp32 values:
+ *   g' = coef g + weight_decay p   (the second term only where weight_decay != 0, as torch skips the add)
+ *   m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2
+ *   p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)),  bc_i = 1 - beta_i^step
+ *   1 - beta_i, lr / bc1 and sqrt(bc2) are formed on the host in double from this tensor's own step and rounded to fp32 once.
+ *   `step` is the count INCLUDING this update (torch increments before it computes); the call does not change it.
+ * A tensor whose grad is NULL takes no part: not in the norm, not updated, its state not read (param, exp_avg, exp_avg_sq may be
+ * NULL and step may be anything).  numel 0 likewise.
+ * Non-finite values follow the arithmetic; nothing is skipped or sanitised.  A NaN gradient makes its tensor's norm, the total
+ * and the unrounded coefficient NaN; NaN < 1 is false, so the applied coefficient is exactly 1 and only that element's p, m, v
+ * become NaN.  An Inf gradient makes the total Inf and the coefficient 0: that element's g' is Inf * 0 = NaN, every other
+ * element's g' is weight_decay p (VETO_OPTIM_CLIP: the Inf gradient becomes NaN in memory, the others 0).
+ * The tables: `tensors` is a HOST array.  The call copies what it needs of it into pinned staging memory that the library owns
+ * before it returns, one buffer per call in flight (a buffer is used again only once the event recorded behind its call has
+ * completed; more than 256 calls in flight wait for the oldest), so the caller may rewrite or free the array as soon as the
+ * call returns, and gradient pointers may change from call to call.
+ * Limits, refused with a message before anything is launched: n_tensors 1..4096; numel 0..2^31 - 1; at most 1 048 576 chunks in
+ * all; an unknown mode; in the modes that clip, max_norm not > 0 (NaN included); in the modes that step, for a tensor with a
+ * gradient and elements: step < 1, a missing param, exp_avg or exp_avg_sq, lr or eps or weight_decay negative or NaN, a beta
+ * outside [0, 1); pointers not 4-byte aligned; in the modes that take norms, a missing norms, total_norm or coef. */
+#define VETO_OPTIM_CHUNK 8192
+#define VETO_OPTIM_NORMS 0
+#define VETO_OPTIM_CLIP 1
+#define VETO_OPTIM_STEP 2
+#define VETO_OPTIM_CLIP_STEP 3
+
+typedef struct veto_optim_tensor {
+  float* param;                       /* device [numel] */
+  const float* grad;                  /* device [numel], or NULL: the tensor takes no part */
+  float* exp_avg;                     /* device [numel] */
+  float* exp_avg_sq;                  /* device [numel] */
+  int64_t numel;                      /* 0..2^31 - 1 */
+  int64_t step;                       /* >= 1: the number of updates including this one */
+  double lr, weight_decay, beta1, beta2, eps;
+} veto_optim_tensor_t;
+
+typedef struct veto_optim_args {
+  int32_t struct_size;
+  int32_t tensor_size;                /* sizeof(veto_optim_tensor_t) */
+  int32_t n_tensors;                  /* 1..4096 */
+  int32_t mode;                       /* VETO_OPTIM_* */
+  double max_norm;                    /* > 0 in the modes that clip; in VETO_OPTIM_NORMS it only enters coef */
+  const veto_optim_tensor_t* tensors; /* HOST [n_tensors]; reusable as soon as the call returns */
+  float* norms;                       /* out device [n_tensors] */
+  float* total_norm;                  /* out device [1] */
+  float* coef;                        /* out device [1]: the applied coefficient */
+} veto_optim_args_t;
+
+/* reads the host fields of `args` and of its tensors (numel, grad); 0 when they are out of range */
+size_t veto_optim_step_workspace_bytes(const veto_optim_args_t* args);
+int veto_optim_step(void* stream, const veto_optim_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* ---- ROI feature extraction -------------------------------------------
  * VETOFeatureExtractor.forward -> Pooler.forward with cat_all_levels=False

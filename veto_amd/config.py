@@ -73,6 +73,12 @@ def default_config():
     c.TEST.RELATION.LATER_NMS_PREDICTION_THRES = 0.3
     c.TEST.RELATION.REQUIRE_OVERLAP = False       # VETO_final.yaml:133
     c.GLOVE_DIR = ""
+    so = c.SOLVER = CfgNode()                      # what veto_amd.solver reads, as VETO_final.yaml:95-96, 101, 125-126 sets it
+    so.BASE_LR = 0.0001
+    so.BIAS_LR_FACTOR = 1
+    so.WEIGHT_DECAY = 1.0e-05
+    so.WEIGHT_DECAY_BIAS = 0.0
+    so.GRAD_NORM_CLIP = 5.0
     # veto_amd extensions (absent from the reference config; read with getattr defaults)
     c.VETO_AMD = CfgNode()
     # what the token-row Linears compute in: "mixed" (fp16 main product + e4m3 correction terms, default: 2/3 of the matrix-pipe

@@ -530,6 +530,39 @@ int box_loss_max_cls();
 int box_loss_max_rows();
 hipError_t launch_box_loss(const BoxLossArgs& a, hipStream_t s);
 
+// ---- the optimizer: global-norm clip and the Adam step over many tensors (optim.hip) ---------------
+constexpr int kOptimChunk = 8192;        // elements of one tensor that one workgroup handles (a multiple of 4)
+constexpr int kOptimMaxTensors = 4096;
+constexpr int kOptimMaxChunks = 1 << 20;
+struct OptimTensor {             // one row of the device table, as the host builds it for every call
+  float* p;                      // [numel]
+  const float* g;                // [numel]; NULL: the tensor has no chunk and takes no part
+  float* m;                      // exp_avg
+  float* v;                      // exp_avg_sq
+  int numel;
+  int chunk0, n_chunks;          // its rows of the chunk table
+  int reserved;
+  float wd, beta1, omb1, beta2, omb2, eps;   // omb = 1 - beta, rounded once from double
+  float step_size;               // lr / (1 - beta1^step), rounded once from double
+  float bc2_sqrt;                // sqrt(1 - beta2^step), rounded once from double
+};
+struct OptimChunk { int tensor, index; };   // elements [index * kOptimChunk, min(numel, (index + 1) * kOptimChunk)) of the tensor
+struct OptimArgs {
+  const OptimTensor* tensors;    // device [n_tensors]
+  const OptimChunk* chunks;      // device [n_chunks]
+  unsigned* counter;             // device, zero when the call starts: the norm pass's workgroups count themselves out on it
+  double* partial;               // workspace [n_chunks]: the sum of g^2 of the chunk
+  double* tensor_sq;             // workspace [n_tensors]
+  int n_tensors, n_chunks;
+  double max_norm;
+  float* norms;                  // out [n_tensors]
+  float* total;                  // out [1]
+  float* coef;                   // out [1]: the applied coefficient
+};
+// norms: the norm pass.  apply: 0 nothing more, 1 scale the gradients in place by coef[0], 2 the Adam step.  use_coef: the step
+// scales each gradient in registers by coef[0] (written by the norm pass of the same call); otherwise by exactly 1.
+hipError_t launch_optim(const OptimArgs& a, bool norms, int apply, bool use_coef, hipStream_t s);
+
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
   const float* feat;             // [n_img, C, H, W]

@@ -153,6 +153,20 @@ class VetoBoxLossArgs(Structure):
                                         "d_class_logits", "d_box_regression")]
 
 
+class VetoOptimTensor(Structure):
+    _fields_ = [(n, c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("numel", c_int64), ("step", c_int64)] + \
+               [(n, c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps")]
+
+
+class VetoOptimArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "tensor_size", "n_tensors", "mode")] + [("max_norm", c_double)] + \
+               [("tensors", POINTER(VetoOptimTensor))] + [(n, c_void_p) for n in ("norms", "total_norm", "coef")]
+
+
+VETO_OPTIM_NORMS, VETO_OPTIM_CLIP, VETO_OPTIM_STEP, VETO_OPTIM_CLIP_STEP = 0, 1, 2, 3   # veto_optim_args_t.mode
+VETO_OPTIM_CHUNK = 8192
+
+
 class VetoPostMeetArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_obj", "n_pair", "n_groups", "n_rel_cls", "n_obj_cls")] + \
                [(n, c_void_p) for n in ("group_logits", "group_widths", "incre_idx_list", "obj_logits", "rel_pairs",
@@ -199,6 +213,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
     "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
     "veto_rpn_loss_args_t": VetoRpnLossArgs, "veto_box_loss_args_t": VetoBoxLossArgs,
+    "veto_optim_tensor_t": VetoOptimTensor, "veto_optim_args_t": VetoOptimArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
 }
 
@@ -258,6 +273,8 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_rpn_loss_workspace_bytes": _sig(POINTER(VetoRpnLossArgs), ret=_Z),
     "veto_box_loss": _sig(_P, POINTER(VetoBoxLossArgs), _P, _Z),
     "veto_box_loss_workspace_bytes": _sig(POINTER(VetoBoxLossArgs), ret=_Z),
+    "veto_optim_step": _sig(_P, POINTER(VetoOptimArgs), _P, _Z),
+    "veto_optim_step_workspace_bytes": _sig(POINTER(VetoOptimArgs), ret=_Z),
     "veto_train_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
     "veto_grad_floats": _sig(_P, ret=_Z),
     "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),

@@ -142,3 +142,44 @@ def install_box_loss_ops():
         head.make_roi_box_loss_evaluator = boxloss.make_roi_box_loss_evaluator
         patched.append(("pysgg.modeling.roi_heads.box_head.box_head", "make_roi_box_loss_evaluator"))
     return patched
+
+
+_SOLVER_ORIGINALS = []   # (module, name, what install_solver_ops replaced), for uninstall_solver_ops
+
+
+def install_solver_ops():
+    """Point the reference's training loop at the device optimizer: `pysgg.solver.build.make_optimizer` and
+    `pysgg.solver.make_optimizer` return veto_amd.solver.Adam, and `pysgg.utils.checkpoint.clip_grad_norm` is
+    veto_amd.solver.clip_grad_norm.  Modules that bound one of the originals by name when they were imported
+    (`from pysgg.solver import make_optimizer`, tools/relation_train_net.py:27-29) are re-pointed too.  `pysgg` must be
+    importable.  Independent of the other installers.  Returns the patched (module, name) pairs; uninstall_solver_ops() puts
+    the originals back."""
+    import importlib
+    import sys
+    import types
+    from . import solver
+    patched = []
+    for mod, name, value in (("pysgg.solver.build", "make_optimizer", solver.make_optimizer),
+                             ("pysgg.solver", "make_optimizer", solver.make_optimizer),
+                             ("pysgg.utils.checkpoint", "clip_grad_norm", solver.clip_grad_norm)):
+        module = importlib.import_module(mod)
+        original = getattr(module, name)
+        if original is value:
+            continue
+        targets = [(mod, module)] + sorted((n, m) for n, m in list(sys.modules.items())
+                                           if isinstance(m, types.ModuleType) and m is not module and vars(m).get(name) is original)
+        for n, m in targets:
+            if vars(m).get(name) is original:
+                setattr(m, name, value)
+                _SOLVER_ORIGINALS.append((m, name, original))
+                patched.append((n, name))
+    return patched
+
+
+def uninstall_solver_ops():
+    """Undo install_solver_ops: every name it replaced gets its original back.  Returns how many."""
+    n = len(_SOLVER_ORIGINALS)
+    while _SOLVER_ORIGINALS:
+        module, name, original = _SOLVER_ORIGINALS.pop()
+        setattr(module, name, original)
+    return n
