@@ -132,14 +132,53 @@ int run_gemm(veto_handle_t h, hipStream_t s, const char* name, const __bf16* a, 
   return VETO_OK;
 }
 
+// The derived operands of the handle (split planes, mixed rows, transposes, folded tables) in one allocation: points them into `base`,
+// or with base == nullptr only sizes it; h->layers has its L entries
+static size_t carve_derived(veto_handle_t h, char* base) {
+  Carver c{base};
+  const veto_config_t& cfg = h->cfg;
+  const int L = cfg.layers, E = cfg.embed_dim;
+  const bool mixed = cfg.precision != VETO_PRECISE;
+  for (LayerW& w : h->layers) {
+    w.qkv = c.take<__bf16>((size_t)3 * kDim * kDim * 4);
+    w.out = c.take<__bf16>((size_t)kDim * kDim * 4);
+    w.fc1 = c.take<__bf16>((size_t)2 * kDim * kDim * 4);
+    w.fc2 = c.take<__bf16>((size_t)2 * kDim * kDim * 4);
+    if (!mixed) continue;
+    w.qkv_m = c.take<__bf16>((size_t)3 * kDim * kDim * 4);
+    w.out_m = c.take<__bf16>((size_t)kDim * kDim * 4);
+    w.fc1_m = c.take<__bf16>((size_t)2 * kDim * kDim * 4);
+    w.fc2_m = c.take<__bf16>((size_t)2 * kDim * kDim * 4);
+  }
+  int* exps = c.take<int>((size_t)L * 4 * sizeof(int));
+  for (int l = 0; l < L && mixed && exps; ++l) h->layers[l].exp_m = exps + 4 * l;
+  h->patch_w = c.take<__bf16>((size_t)2 * kDim * 2048 * 4);
+  h->patch_bias = c.take<float>((size_t)2 * kDim * 4);
+  h->loc_wt = c.take<float>((size_t)kPosDim * 2 * kDim * 4);
+  h->cls_wt = c.take<float>((size_t)E * 2 * kDim * 4);
+  h->head_wt = c.take<float>((size_t)kDim * cfg.num_out * 4);
+  const int fold_dhp = h->fold_dhp = fold_block_width(cfg.heads);
+  const size_t fold_np = (size_t)cfg.heads * (fold_dhp > 0 ? fold_dhp : 0);
+  const size_t fold_el = fold_dhp > 0 ? (size_t)cfg.heads * kDim * fold_np : (size_t)cfg.heads * kDim * kDim;   // largest staged matrix
+  h->fold_m = c.take<__bf16>(fold_dhp > 0 ? 256 : fold_el * 4);
+  h->fold_n = c.take<__bf16>(fold_dhp > 0 ? 256 : fold_el * 4);
+  h->fold_tmp = c.take<float>(fold_el * 4);
+  h->fold_q = c.take<__bf16>(fold_np * kDim * 4 + 256);
+  h->fold_k = c.take<__bf16>((size_t)cfg.heads * kDim * fold_np * 4 + 256);
+  h->fold_v = c.take<__bf16>((size_t)cfg.heads * kDim * fold_np * 4 + 256);
+  h->fold_o = c.take<__bf16>(fold_np * kDim * 4 + 256);
+  h->q0_w = c.take<__bf16>((size_t)3 * kDim * kDim * 4);
+  h->q0_vec = c.take<float>((size_t)3 * 3 * kDim * 4);
+  return c.off;
+}
+
 extern "C" {
 
 const char* veto_last_error(void) { return g_abi_err.c_str(); }
 const char* veto_version(void) { return "veto_amd 0.1 (gfx950)"; }
 
 int veto_create(const veto_config_t* cfg, veto_handle_t* out) {
-  if (!cfg || !out) return fail(VETO_ERR_INVALID, "null argument");
-  if (cfg->struct_size != (int32_t)sizeof(veto_config_t)) return fail(VETO_ERR_INVALID, "veto_config_t size mismatch");
+  CHECK_STRUCT_AND(veto_config_t, cfg, out != nullptr);
   if (cfg->dim != kDim) return fail(VETO_ERR_INVALID, "T_INPUT_DIM must be 576 (proj_d 512 + proj_v 64), got %d", cfg->dim);
   if (cfg->patch != 2 || cfg->channels != 256 || cfg->resolution != 8)
     return fail(VETO_ERR_INVALID, "only PATCH_SIZE 2, 256 channels, POOLER_RESOLUTION 8 are supported");
@@ -189,81 +228,26 @@ int veto_create(const veto_config_t* cfg, veto_handle_t* out) {
   }
   h->add("rel_out.weight", (size_t)cfg->num_out * kDim);
   h->add("rel_out.bias", cfg->num_out);
-  size_t off = 0;
   for (Param& q : h->params) {
-    q.offset = off;
-    off += align_up(q.numel, 64);
+    q.offset = h->raw_floats;
+    h->raw_floats += align_up(q.numel, 64);
   }
-  hipError_t e = hipMalloc((void**)&h->raw, off * sizeof(float));
+  hipError_t e = hipMalloc((void**)&h->raw, h->raw_floats * sizeof(float));
   if (e != hipSuccess) { delete h; return fail(VETO_ERR_HIP, "hipMalloc(raw weights): %s", hipGetErrorString(e)); }
 
   // derived weights
-  size_t doff = 0;
-  auto dtake = [&](size_t bytes) { size_t o = doff; doff += align_up(bytes, 256); return o; };
-  std::vector<size_t> lo_(L * 8);
-  for (int l = 0; l < L; ++l) {
-    lo_[l * 8 + 0] = dtake((size_t)3 * kDim * kDim * 4);
-    lo_[l * 8 + 2] = dtake((size_t)kDim * kDim * 4);
-    lo_[l * 8 + 4] = dtake((size_t)2 * kDim * kDim * 4);
-    lo_[l * 8 + 6] = dtake((size_t)2 * kDim * kDim * 4);
-    if (cfg->precision != VETO_PRECISE) {
-      lo_[l * 8 + 1] = dtake((size_t)3 * kDim * kDim * 4);
-      lo_[l * 8 + 3] = dtake((size_t)kDim * kDim * 4);
-      lo_[l * 8 + 5] = dtake((size_t)2 * kDim * kDim * 4);
-      lo_[l * 8 + 7] = dtake((size_t)2 * kDim * kDim * 4);
-    }
-  }
-  const size_t o_exp = dtake((size_t)L * 4 * sizeof(int));
-  const size_t o_pw = dtake((size_t)2 * kDim * 2048 * 4);
-  const size_t o_pb = dtake((size_t)2 * kDim * 4);
-  const size_t o_loc = dtake((size_t)kPosDim * 2 * kDim * 4);
-  const size_t o_cls = dtake((size_t)E * 2 * kDim * 4);
-  const size_t o_head = dtake((size_t)kDim * cfg->num_out * 4);
-  const int fold_dhp = fold_block_width(cfg->heads);
-  const size_t fold_np = (size_t)cfg->heads * (fold_dhp > 0 ? fold_dhp : 0);
-  const size_t fold_el = fold_dhp > 0 ? (size_t)cfg->heads * kDim * fold_np : (size_t)cfg->heads * kDim * kDim;   // largest staged matrix
-  const size_t o_fm = dtake(fold_dhp > 0 ? 256 : fold_el * 4), o_fn = dtake(fold_dhp > 0 ? 256 : fold_el * 4), o_ft = dtake(fold_el * 4);
-  const size_t o_fq = dtake(fold_np * kDim * 4 + 256), o_fk = dtake((size_t)cfg->heads * kDim * fold_np * 4 + 256),
-               o_fv = dtake((size_t)cfg->heads * kDim * fold_np * 4 + 256), o_fo = dtake(fold_np * kDim * 4 + 256);
-  const size_t o_q0w = dtake((size_t)3 * kDim * kDim * 4), o_q0v = dtake((size_t)3 * 3 * kDim * 4);
-  e = hipMalloc((void**)&h->derived, doff);
-  if (e != hipSuccess) { (void)hipFree(h->raw); delete h; return fail(VETO_ERR_HIP, "hipMalloc(derived weights): %s", hipGetErrorString(e)); }
   h->layers.resize(L);
+  e = hipMalloc((void**)&h->derived, carve_derived(h, nullptr));
+  if (e != hipSuccess) { (void)hipFree(h->raw); delete h; return fail(VETO_ERR_HIP, "hipMalloc(derived weights): %s", hipGetErrorString(e)); }
+  carve_derived(h, h->derived);
   for (int l = 0; l < L; ++l) {
     LayerW& w = h->layers[l];
-    char* d = h->derived;
-    w.qkv = (__bf16*)(d + lo_[l * 8 + 0]);
-    w.out = (__bf16*)(d + lo_[l * 8 + 2]);
-    w.fc1 = (__bf16*)(d + lo_[l * 8 + 4]);
-    w.fc2 = (__bf16*)(d + lo_[l * 8 + 6]);
-    if (cfg->precision != VETO_PRECISE) {
-      w.qkv_m = (__bf16*)(d + lo_[l * 8 + 1]);
-      w.out_m = (__bf16*)(d + lo_[l * 8 + 3]);
-      w.fc1_m = (__bf16*)(d + lo_[l * 8 + 5]);
-      w.fc2_m = (__bf16*)(d + lo_[l * 8 + 7]);
-      w.exp_m = (int*)(d + o_exp) + 4 * l;
-    }
     w.ln1_w = h->p(lname(l, "0.norm.weight")); w.ln1_b = h->p(lname(l, "0.norm.bias"));
     w.ln2_w = h->p(lname(l, "1.norm.weight")); w.ln2_b = h->p(lname(l, "1.norm.bias"));
     w.out_b = h->p(lname(l, "0.fn.to_out.0.bias"));
     w.fc1_b = h->p(lname(l, "1.fn.net.0.bias"));
     w.fc2_b = h->p(lname(l, "1.fn.net.3.bias"));
   }
-  h->patch_w = (__bf16*)(h->derived + o_pw);
-  h->patch_bias = (float*)(h->derived + o_pb);
-  h->loc_wt = (float*)(h->derived + o_loc);
-  h->cls_wt = (float*)(h->derived + o_cls);
-  h->head_wt = (float*)(h->derived + o_head);
-  h->fold_m = (__bf16*)(h->derived + o_fm);
-  h->fold_n = (__bf16*)(h->derived + o_fn);
-  h->fold_tmp = (float*)(h->derived + o_ft);
-  h->fold_q = (__bf16*)(h->derived + o_fq);
-  h->fold_k = (__bf16*)(h->derived + o_fk);
-  h->fold_v = (__bf16*)(h->derived + o_fv);
-  h->fold_o = (__bf16*)(h->derived + o_fo);
-  h->fold_dhp = fold_dhp;
-  h->q0_w = (__bf16*)(h->derived + o_q0w);
-  h->q0_vec = (float*)(h->derived + o_q0v);
   if (cfg->precision == VETO_MIXED) {
     e = hipMalloc((void**)&h->sat_buf, (size_t)L * VETO_SAT_SITES * 4 * sizeof(unsigned long long));
     if (e != hipSuccess) { (void)hipFree(h->raw); (void)hipFree(h->derived); delete h; return fail(VETO_ERR_HIP, "hipMalloc(saturation counters): %s", hipGetErrorString(e)); }
@@ -306,11 +290,7 @@ int veto_load_weights(veto_handle_t h, const char* name, const float* src, size_
   return VETO_OK;
 }
 
-size_t veto_grad_floats(veto_handle_t h) {
-  if (!h || h->params.empty()) return 0;
-  const Param& q = h->params.back();
-  return q.offset + align_up(q.numel, 64);
-}
+size_t veto_grad_floats(veto_handle_t h) { return h ? h->raw_floats : 0; }
 
 int veto_weight_offset(veto_handle_t h, int index, size_t* offset_floats) {
   if (!h || index < 0 || index >= (int)h->params.size() || !offset_floats) return fail(VETO_ERR_INVALID, "bad weight index");

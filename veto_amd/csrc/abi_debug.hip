@@ -30,27 +30,57 @@ struct EventTimer {
   }
 };
 
+// ---- the hooks' workspaces: operand rows built from the fp32 inputs (activation rows padded to whole GEMM tiles), then 256 bytes for the
+// mixed weights' exponents.  (A braced list evaluates left to right: the members are carved in their order.)
+const size_t kW = (size_t)kDim * kDim * 4;      // bytes of a 576 x 576 weight as split or mixed rows
+size_t act_bytes(size_t rows, size_t k) { return (size_t)gemm_rows_padded((int)rows) * k * 4; }
+
+struct GemmWs { __bf16 *a, *w; int* w_exp; size_t total; };       // veto_debug_gemm, veto_debug_gemm_forms
+GemmWs carve_gemm(Carver c, int m, int n, int k) {
+  return GemmWs{c.take<__bf16>(act_bytes(m, k)), c.take<__bf16>((size_t)n * k * 4), c.take<int>(256), c.off};
+}
+
+struct FfnWs { __bf16 *a, *hid, *w1, *w2; int* exps; size_t total; };
+FfnWs carve_ffn(Carver c, int m) {
+  return FfnWs{c.take<__bf16>(act_bytes(m, kDim)), c.take<__bf16>(act_bytes(m, 2 * kDim)), c.take<__bf16>(2 * kW), c.take<__bf16>(2 * kW),
+               c.take<int>(256), c.off};
+}
+
+struct OutprojWs { __bf16 *a, *w; int* exps; size_t total; };
+OutprojWs carve_outproj(Carver c, int m) {
+  return OutprojWs{c.take<__bf16>(act_bytes(m, kDim)), c.take<__bf16>(kW), c.take<int>(256), c.off};
+}
+
+struct LayerTailWs { __bf16 *a, *wo, *w1, *w2; int* exps; size_t total; };
+LayerTailWs carve_layer_tail(Carver c, int m) {
+  return LayerTailWs{c.take<__bf16>(act_bytes(m, kDim)), c.take<__bf16>(kW), c.take<__bf16>(2 * kW), c.take<__bf16>(2 * kW), c.take<int>(256),
+                     c.off};
+}
+
+struct QkvAttnWs { __bf16* a; char *o, *qkv; __bf16* w; int* exps; size_t total; };
+QkvAttnWs carve_qkv_attn(Carver c, int n_pair) {
+  // (the fused launch reads whole tiles of 16 pairs: the rows are padded to those too; q / k / v are 3-byte floats)
+  const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens, rows = tile_rows > m ? tile_rows : m;
+  return QkvAttnWs{c.take<__bf16>(act_bytes(rows, kDim)), c.take(act_bytes(rows, kDim)), c.take((size_t)gemm_rows_padded((int)rows) * 3 * kDim * 3),
+                   c.take<__bf16>(3 * kW), c.take<int>(256), c.off};
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t veto_debug_gemm_workspace_bytes(int32_t m, int32_t n, int32_t k) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  return align_up(mp * k * 4, 256) + align_up((size_t)n * k * 4, 256) + 256;
+  return carve_gemm(Carver{nullptr}, m, n, k).total;
 }
 
 int veto_debug_gemm(void* stream, const float* a, const float* w, const float* bias, float* c, int32_t m, int32_t n,
                     int32_t k, int32_t precision, void* workspace, size_t workspace_bytes) {
   if (!a || !w || !c || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (workspace_bytes < veto_debug_gemm_workspace_bytes(m, n, k)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_gemm_workspace_bytes(m, n, k), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  char* base = (char*)workspace;
-  __bf16* a_s = (__bf16*)base;
-  __bf16* w_s = (__bf16*)(base + align_up(mp * k * 4, 256));
-  int* w_exp = (int*)(base + align_up(mp * k * 4, 256) + align_up((size_t)n * k * 4, 256));
-  HIP_TRY(hipMemsetAsync(base, 0, align_up(mp * k * 4, 256), s));
+  const auto [a_s, w_s, w_exp, ws_bytes] = carve_gemm(Carver{(char*)workspace}, m, n, k);
+  HIP_TRY(hipMemsetAsync(a_s, 0, (char*)w_s - (char*)a_s, s));      // (the rows m..padded stay zero)
   GemmArgs g{};
   if (precision == VETO_MIXED) {
     if (k % 64 != 0) return fail(VETO_ERR_INVALID, "mixed rows need K %% 64 == 0");
@@ -77,13 +107,10 @@ int veto_debug_gemm_forms(void* stream, const float* a, const float* w, void* c,
                           int32_t kb_steps, int32_t out_form, void* workspace, size_t workspace_bytes) {
   if (!a || !w || !c || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (out_form < 0 || out_form > 2) return fail(VETO_ERR_INVALID, "out_form must be 0, 1 or 2");
-  if (workspace_bytes < veto_debug_gemm_workspace_bytes(m, n, k)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_gemm_workspace_bytes(m, n, k), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  char* base = (char*)workspace;
-  __bf16* a_s = (__bf16*)base;
-  __bf16* w_s = (__bf16*)(base + align_up(mp * k * 4, 256));
-  HIP_TRY(hipMemsetAsync(base, 0, align_up(mp * k * 4, 256), s));
+  const auto [a_s, w_s, w_exp, ws_bytes] = carve_gemm(Carver{(char*)workspace}, m, n, k);
+  HIP_TRY(hipMemsetAsync(a_s, 0, (char*)w_s - (char*)a_s, s));
   HIP_TRY(launch_split_rows(a, a_s, (size_t)m, k, s));
   HIP_TRY(launch_split_rows(w, w_s, (size_t)n, k, s));
   GemmArgs g{};
@@ -103,9 +130,7 @@ int veto_debug_gemm_forms(void* stream, const float* a, const float* w, void* c,
 // flags & 1: (re)build the mixed operands from a / w1 / w2 first.  The block runs `reps` times (x accumulates: timing only when
 // reps > 1); *ms_per_rep (host, optional) receives the mean device time of one run from hipEvents on `stream`.
 size_t veto_debug_ffn_workspace_bytes(int32_t m) {
-  if (m <= 0) return 0;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  return align_up(mp * kDim * 4, 256) + align_up(mp * 2 * kDim * 4, 256) + 2 * align_up((size_t)2 * kDim * kDim * 4, 256) + 256;
+  return m > 0 ? carve_ffn(Carver{nullptr}, m).total : 0;
 }
 
 int veto_debug_ffn(void* stream, const float* a, const float* w1, const float* b1, const float* w2, const float* b2, float* x,
@@ -114,17 +139,11 @@ int veto_debug_ffn(void* stream, const float* a, const float* w1, const float* b
   if (!a || !w1 || !b1 || !w2 || !b2 || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
   if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
-  if (workspace_bytes < veto_debug_ffn_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_ffn_workspace_bytes(m), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  char* base = (char*)workspace;
-  __bf16* a_m = (__bf16*)base;
-  __bf16* hid = (__bf16*)(base + align_up(mp * kDim * 4, 256));
-  __bf16* w1_m = (__bf16*)((char*)hid + align_up(mp * 2 * kDim * 4, 256));
-  __bf16* w2_m = (__bf16*)((char*)w1_m + align_up((size_t)2 * kDim * kDim * 4, 256));
-  int* exps = (int*)((char*)w2_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  const auto [a_m, hid, w1_m, w2_m, exps, ws_bytes] = carve_ffn(Carver{(char*)workspace}, m);
   if (flags & 1) {
-    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+    HIP_TRY(hipMemsetAsync(a_m, 0, (char*)hid - (char*)a_m, s));
     HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
     HIP_TRY(launch_mixed_weight_rows(w1, w1_m, (size_t)2 * kDim, kDim, exps + 0, s));
     HIP_TRY(launch_mixed_weight_rows(w2, w2_m, (size_t)kDim, 2 * kDim, exps + 1, s));
@@ -157,9 +176,7 @@ int veto_debug_ffn(void* stream, const float* a, const float* w1, const float* b
 // x <- x + a W^T + b for m token rows, optionally followed by LayerNorm rows (the FeedForward PreNorm, :125-132).  mode 0 = the GEMM
 // launch with the residual epilogue (+ a LayerNorm launch), mode 1 = the full-row panel kernel (ffn_fused.hip, MODE 1).
 size_t veto_debug_outproj_workspace_bytes(int32_t m) {
-  if (m <= 0) return 0;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  return align_up(mp * kDim * 4, 256) + align_up((size_t)kDim * kDim * 4, 256) + 256;
+  return m > 0 ? carve_outproj(Carver{nullptr}, m).total : 0;
 }
 
 int veto_debug_outproj(void* stream, const float* a, const float* w, const float* b, float* x, int32_t m, int32_t mode, int32_t flags,
@@ -168,19 +185,15 @@ int veto_debug_outproj(void* stream, const float* a, const float* w, const float
   if (!a || !w || !b || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
   if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
-  if (workspace_bytes < veto_debug_outproj_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_outproj_workspace_bytes(m), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  char* base = (char*)workspace;
-  __bf16* a_m = (__bf16*)base;
-  __bf16* w_m = (__bf16*)(base + align_up(mp * kDim * 4, 256));
-  int* exps = (int*)((char*)w_m + align_up((size_t)kDim * kDim * 4, 256));
+  const auto [a_m, w_m, exps, ws_bytes] = carve_outproj(Carver{(char*)workspace}, m);
   if (flags & 1) HIP_TRY(launch_mixed_weight_rows(w, w_m, (size_t)kDim, kDim, exps, s));
   EventTimer timer;      // every rep by itself
   if (ms_per_rep) HIP_TRY(timer.init(s));
   for (int r = 0; r < reps; ++r) {
     // the fused form writes its LayerNorm rows over its input rows: rebuild them for every run (outside the timed span)
-    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+    HIP_TRY(hipMemsetAsync(a_m, 0, (char*)w_m - (char*)a_m, s));
     HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
     HIP_TRY(timer.start());
     if (mode == 1) {
@@ -202,9 +215,7 @@ int veto_debug_outproj(void* stream, const float* a, const float* w, const float
 // bo, h = LayerNorm2(x1), x2 = x1 + W2 gelu(W1 h + b1) + b2 (+ LayerNorm rows of x2) on VETO_MIXED operands.  mode 0 = the
 // out-projection panel launch + the FeedForward panel launch, mode 1 = ONE launch (ffn_fused.hip MODE 2).
 size_t veto_debug_layer_tail_workspace_bytes(int32_t m) {
-  if (m <= 0) return 0;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  return align_up(mp * kDim * 4, 256) + align_up((size_t)kDim * kDim * 4, 256) + 2 * align_up((size_t)2 * kDim * kDim * 4, 256) + 256;
+  return m > 0 ? carve_layer_tail(Carver{nullptr}, m).total : 0;
 }
 
 int veto_debug_layer_tail(void* stream, const float* a, const float* wo, const float* bo, const float* ln2_w, const float* ln2_b,
@@ -214,22 +225,16 @@ int veto_debug_layer_tail(void* stream, const float* a, const float* wo, const f
   if (!a || !wo || !bo || !ln2_w || !ln2_b || !w1 || !b1 || !w2 || !b2 || !x || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (m <= 0 || reps <= 0 || (mode != 0 && mode != 1)) return fail(VETO_ERR_INVALID, "bad m / reps / mode");
   if (ln_rows && (!ln_w || !ln_b)) return fail(VETO_ERR_INVALID, "ln_rows needs ln_w and ln_b");
-  if (workspace_bytes < veto_debug_layer_tail_workspace_bytes(m)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_layer_tail_workspace_bytes(m), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t mp = (size_t)gemm_rows_padded(m);
-  char* base = (char*)workspace;
-  __bf16* a_m = (__bf16*)base;
-  __bf16* wo_m = (__bf16*)(base + align_up(mp * kDim * 4, 256));
-  __bf16* w1_m = (__bf16*)((char*)wo_m + align_up((size_t)kDim * kDim * 4, 256));
-  __bf16* w2_m = (__bf16*)((char*)w1_m + align_up((size_t)2 * kDim * kDim * 4, 256));
-  int* exps = (int*)((char*)w2_m + align_up((size_t)2 * kDim * kDim * 4, 256));
+  const auto [a_m, wo_m, w1_m, w2_m, exps, ws_bytes] = carve_layer_tail(Carver{(char*)workspace}, m);
   HIP_TRY(launch_mixed_weight_rows(wo, wo_m, (size_t)kDim, kDim, exps + 0, s));
   HIP_TRY(launch_mixed_weight_rows(w1, w1_m, (size_t)2 * kDim, kDim, exps + 1, s));
   HIP_TRY(launch_mixed_weight_rows(w2, w2_m, (size_t)kDim, 2 * kDim, exps + 2, s));
   EventTimer timer;      // every rep by itself
   if (ms_per_rep) HIP_TRY(timer.init(s));
   for (int r = 0; r < reps; ++r) {
-    HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));       // the activation rows are overwritten in place: rebuilt per run, untimed
+    HIP_TRY(hipMemsetAsync(a_m, 0, (char*)wo_m - (char*)a_m, s));       // the activation rows are overwritten in place: rebuilt per run, untimed
     HIP_TRY(launch_mixed_act_rows(a, a_m, (size_t)m, kDim, s));
     HIP_TRY(timer.start());
     // (every LayerNorm goes over the activation rows in place, as in the forward)
@@ -252,27 +257,18 @@ int veto_debug_layer_tail(void* stream, const float* a, const float* wo, const f
 // the attention output as mixed rows [19 n_pair, 4*576 B].  mode 1 = qkv_attn_fused.hip, mode 0 = the two launches it replaces (QKV GEMM
 // with 3-byte q / k / v + attention_mfma_kernel).
 size_t veto_debug_qkv_attn_workspace_bytes(int32_t n_pair) {
-  if (n_pair <= 0) return 0;
-  const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens;
-  const size_t mp = (size_t)gemm_rows_padded((int)(tile_rows > m ? tile_rows : m));
-  return 2 * align_up(mp * kDim * 4, 256) + align_up(mp * 3 * kDim * 3, 256) + align_up((size_t)3 * kDim * kDim * 4, 256) + 256;
+  return n_pair > 0 ? carve_qkv_attn(Carver{nullptr}, n_pair).total : 0;
 }
 
 int veto_debug_qkv_attn(void* stream, const float* a, const float* wqkv, int32_t n_pair, int32_t heads, int32_t mode, int32_t reps,
                         float* ms_per_rep, void* workspace, size_t workspace_bytes, void* out_rows) {
   if (!a || !wqkv || !workspace || !out_rows) return fail(VETO_ERR_INVALID, "null argument");
   if (n_pair <= 0 || reps <= 0 || (mode != 0 && mode != 1) || !qkv_attn_fused_supports(heads)) return fail(VETO_ERR_INVALID, "bad n_pair / reps / mode / heads");
-  if (workspace_bytes < veto_debug_qkv_attn_workspace_bytes(n_pair)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_qkv_attn_workspace_bytes(n_pair), false));
   hipStream_t s = (hipStream_t)stream;
-  const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens;
-  const size_t mp = (size_t)gemm_rows_padded((int)(tile_rows > m ? tile_rows : m));
-  char* base = (char*)workspace;
-  __bf16* a_m = (__bf16*)base;
-  char* o_m = base + align_up(mp * kDim * 4, 256);
-  char* qkv = o_m + align_up(mp * kDim * 4, 256);
-  __bf16* w_m = (__bf16*)(qkv + align_up(mp * 3 * kDim * 3, 256));
-  int* exps = (int*)((char*)w_m + align_up((size_t)3 * kDim * kDim * 4, 256));
-  HIP_TRY(hipMemsetAsync(a_m, 0, mp * kDim * 4, s));
+  const size_t m = (size_t)n_pair * kTokens;
+  const auto [a_m, o_m, qkv, w_m, exps, ws_bytes] = carve_qkv_attn(Carver{(char*)workspace}, n_pair);
+  HIP_TRY(hipMemsetAsync(a_m, 0, o_m - (char*)a_m, s));      // (the rows m..padded stay zero)
   HIP_TRY(launch_mixed_act_rows(a, a_m, m, kDim, s));
   HIP_TRY(launch_mixed_weight_rows(wqkv, w_m, (size_t)3 * kDim, kDim, exps, s));
   EventTimer timer;      // the whole rep loop

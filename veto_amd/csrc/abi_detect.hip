@@ -1,7 +1,9 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
 // box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, the box head's loss, ROI pooling and
 // the evaluator.
-// Each checks its argument struct, carves its workspace and makes one launch call (kernels.h).
+// Each checks its argument struct (the checks several of them make are in abi_internal.h), fills the launch struct and makes one
+// launch call (kernels.h).  An entry point with a workspace has ONE carve_*() that walks the layout and sets the launch struct's
+// workspace pointers: veto_X_workspace_bytes runs it on a null base, veto_X on the caller's buffer.
 #include <cmath>
 
 #include "abi_internal.h"
@@ -14,14 +16,23 @@ int veto_enumerate_pairs(void* stream, int32_t n, int64_t* out) {
   return VETO_OK;
 }
 
+// workspace of the three relation post-processors over `rows` (merged) rows: prob_tmp | triple | label_tmp | perm
+static size_t carve_post(Carver c, size_t rows, int n_rel_cls, PostArgs* p) {
+  p->prob_tmp = c.take<float>(rows * n_rel_cls * 4);
+  p->triple = c.take<float>(rows * 4);
+  p->label_tmp = c.take<int32_t>(rows * 4);
+  p->perm = c.take<int32_t>(rows * 4);
+  return c.off;
+}
+
 size_t veto_postprocess_workspace_bytes(int32_t n_pair, int32_t n_rel_cls) {
   if (n_pair <= 0 || n_rel_cls <= 0) return 0;
-  return align_up((size_t)n_pair * n_rel_cls * 4, 256) + 3 * align_up((size_t)n_pair * 4, 256);
+  PostArgs p{};
+  return carve_post(Carver{nullptr}, n_pair, n_rel_cls, &p);
 }
 
 int veto_postprocess(void* stream, const veto_post_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_post_args_t)) return fail(VETO_ERR_INVALID, "veto_post_args_t size mismatch");
+  CHECK_STRUCT_AND(veto_post_args_t, a, workspace != nullptr);
   if (a->n_img <= 0 || a->n_obj <= 0 || a->n_pair <= 0 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
   if (!a->rel_logits || !a->rel_pairs || !a->img_obj_offset || !a->img_pair_offset || !a->obj_scores ||
@@ -30,26 +41,16 @@ int veto_postprocess(void* stream, const veto_post_args_t* a, void* workspace, s
   if (a->max_pairs_per_image < 1 || a->max_pairs_per_image > postprocess_max_pairs_per_image())
     return fail(VETO_ERR_INVALID, "max_pairs_per_image %d outside 1..%d (MAX_PROPOSAL_PAIR is 2048 at test time)",
                 a->max_pairs_per_image, postprocess_max_pairs_per_image());
-  if (workspace_bytes < veto_postprocess_workspace_bytes(a->n_pair, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
-  char* base = (char*)workspace;
-  PostArgs p{};
-  p.rel_logits = a->rel_logits; p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
-  p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset;
-  p.n_img = a->n_img; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
-  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
-  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
-  p.prob_tmp = (float*)base;
-  base += align_up((size_t)a->n_pair * a->n_rel_cls * 4, 256);
-  p.triple = (float*)base; base += align_up((size_t)a->n_pair * 4, 256);
-  p.label_tmp = (int32_t*)base; base += align_up((size_t)a->n_pair * 4, 256);
-  p.perm = (int32_t*)base;
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes(a->n_pair, a->n_rel_cls), false));
+  PostArgs p = post_args(a);
+  p.rel_logits = a->rel_logits; p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset; p.n_img = a->n_img;
+  carve_post(Carver{(char*)workspace}, a->n_pair, a->n_rel_cls, &p);
   HIP_TRY(launch_postprocess(p, (hipStream_t)stream));
   return VETO_OK;
 }
 
 int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_post_meet_args_t)) return fail(VETO_ERR_INVALID, "veto_post_meet_args_t size mismatch");
+  CHECK_STRUCT_AND(veto_post_meet_args_t, a, workspace != nullptr);
   if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
   if (!a->group_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
@@ -58,41 +59,25 @@ int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* wo
   const long total = (long)a->n_groups * a->n_pair;
   if (total > postprocess_max_pairs_per_image())
     return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
-  if (workspace_bytes < veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls), false));
   std::vector<MeetGroup> groups(a->n_groups);
   for (int k = 0; k < a->n_groups; ++k) {
     MeetGroup& g = groups[k];
     g.logits = a->group_logits[k];
     g.width = a->group_widths[k];
     g.row0 = k * a->n_pair;
-    if (!g.logits || g.width < 3 || g.width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
-    int n = 0;
-    g.cols[n++] = 0;
-    for (int c = 0; c < a->n_rel_cls; ++c)
-      if (a->incre_idx_list[c] == k + 1) {
-        if (n >= g.width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
-        g.cols[n++] = c;
-      }
-    if (n != g.width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, g.width);
+    if (!g.logits) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
+    ABI_TRY(fill_group_cols(g.cols, g.width, k, a->incre_idx_list, a->n_rel_cls));
   }
-  char* base = (char*)workspace;
-  PostArgs p{};
-  p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
-  p.n_img = 1; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
-  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
-  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
-  p.prob_tmp = (float*)base;
-  base += align_up((size_t)total * a->n_rel_cls * 4, 256);
-  p.triple = (float*)base; base += align_up((size_t)total * 4, 256);
-  p.label_tmp = (int32_t*)base; base += align_up((size_t)total * 4, 256);
-  p.perm = (int32_t*)base;
+  PostArgs p = post_args(a);
+  p.n_img = 1;
+  carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
   HIP_TRY(launch_postprocess_meet(p, groups.data(), a->n_groups, (hipStream_t)stream));
   return VETO_OK;
 }
 
 int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_post_vote_args_t)) return fail(VETO_ERR_INVALID, "veto_post_vote_args_t size mismatch");
+  CHECK_STRUCT_AND(veto_post_vote_args_t, a, workspace != nullptr);
   if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes");
   if (a->voting != 0 && a->voting != 1) return fail(VETO_ERR_INVALID, "voting must be 0 ('C') or 1 ('U')");
@@ -102,7 +87,7 @@ int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* wo
   const long total = (long)a->n_groups * a->n_pair;
   if (total > postprocess_max_pairs_per_image())
     return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
-  if (workspace_bytes < veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls), false));
   std::vector<VoteGroup> groups(a->n_groups);
   for (int k = 0; k < a->n_groups; ++k) {
     VoteGroup& g = groups[k];
@@ -112,40 +97,28 @@ int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* wo
     }
     g.width = a->group_widths[k];
     g.row0 = k * a->n_pair;
-    if (g.width < 3 || g.width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
-    int n = 0;
-    g.cols[n++] = 0;
-    for (int c = 0; c < a->n_rel_cls; ++c)
-      if (a->incre_idx_list[c] == k + 1) {
-        if (n >= g.width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
-        g.cols[n++] = c;
-      }
-    if (n != g.width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, g.width);
+    ABI_TRY(fill_group_cols(g.cols, g.width, k, a->incre_idx_list, a->n_rel_cls));
   }
-  char* base = (char*)workspace;
-  PostArgs p{};
-  p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
-  p.n_img = 1; p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
-  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
-  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
-  p.kept_count = a->kept_count;
-  p.prob_tmp = (float*)base;
-  base += align_up((size_t)total * a->n_rel_cls * 4, 256);
-  p.triple = (float*)base; base += align_up((size_t)total * 4, 256);
-  p.label_tmp = (int32_t*)base; base += align_up((size_t)total * 4, 256);
-  p.perm = (int32_t*)base;
+  PostArgs p = post_args(a);
+  p.n_img = 1; p.kept_count = a->kept_count;
+  carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
   HIP_TRY(launch_postprocess_vote(p, groups.data(), a->n_groups, a->voting, (hipStream_t)stream));
   return VETO_OK;
 }
 
+static size_t carve_obj_decode(Carver c, int n_obj, int n_cls, ObjDecodeArgs* p) {
+  p->prob_ws = c.take<float>((size_t)n_obj * n_cls * 4);
+  return c.off;
+}
+
 size_t veto_obj_decode_workspace_bytes(int32_t n_obj, int32_t n_cls) {
   if (n_obj <= 0 || n_cls <= 0) return 0;
-  return align_up((size_t)n_obj * n_cls * 4, 256);
+  ObjDecodeArgs p{};
+  return carve_obj_decode(Carver{nullptr}, n_obj, n_cls, &p);
 }
 
 int veto_obj_decode(void* stream, const veto_obj_decode_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_obj_decode_args_t)) return fail(VETO_ERR_INVALID, "veto_obj_decode_args_t size mismatch");
+  CHECK_STRUCT(veto_obj_decode_args_t, a);
   if (a->n_img <= 0 || a->n_obj <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
   if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
   if (a->max_obj_per_image < 1 || a->max_obj_per_image > obj_decode_max_objects())
@@ -155,20 +128,18 @@ int veto_obj_decode(void* stream, const veto_obj_decode_args_t* a, void* workspa
   if (!a->boxes_per_cls || !a->img_obj_offset || !a->obj_pred || (a->mode == 0 && !a->logits) || (a->mode == 1 && !a->labels) ||
       (a->obj_scores && !a->logits))
     return fail(VETO_ERR_INVALID, "missing pointer");
-  if (!workspace || workspace_bytes < veto_obj_decode_workspace_bytes(a->n_obj, a->n_cls))
-    return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_obj_decode_workspace_bytes(a->n_obj, a->n_cls), false));
   ObjDecodeArgs p{};
   p.logits = a->logits; p.labels = a->labels; p.boxes_per_cls = a->boxes_per_cls; p.img_off = a->img_obj_offset;
   p.n_img = a->n_img; p.n_cls = a->n_cls; p.mode = a->mode; p.thr = a->nms_thres;
-  p.prob_ws = (float*)workspace;
+  carve_obj_decode(Carver{(char*)workspace}, a->n_obj, a->n_cls, &p);
   p.obj_pred = a->obj_pred; p.obj_scores = a->obj_scores; p.out_boxes = a->boxes;
   HIP_TRY(launch_obj_decode(p, (hipStream_t)stream));
   return VETO_OK;
 }
 
 int veto_prepare_test_pairs(void* stream, const veto_pair_args_t* a) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_pair_args_t)) return fail(VETO_ERR_INVALID, "veto_pair_args_t size mismatch");
+  CHECK_STRUCT(veto_pair_args_t, a);
   if (a->n_img <= 0 || a->n_obj < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_obj %d)", a->n_img, a->n_obj);
   if (a->max_obj_per_image < 0 || a->max_obj_per_image > obj_decode_max_objects())
     return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d", a->max_obj_per_image, obj_decode_max_objects());
@@ -201,8 +172,7 @@ static int check_host_offsets(const int32_t* off, int n_seg, int total, int limi
 }
 
 int veto_nms(void* stream, const veto_nms_args_t* a) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_nms_args_t)) return fail(VETO_ERR_INVALID, "veto_nms_args_t size mismatch");
+  CHECK_STRUCT(veto_nms_args_t, a);
   if (a->n_seg <= 0 || a->n_box < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_seg %d, n_box %d)", a->n_seg, a->n_box);
   if (!a->seg_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: seg_offset_host");
   const int largest = check_host_offsets(a->seg_offset_host, a->n_seg, a->n_box, nms_max_segment(), "seg_offset_host", "n_box");
@@ -218,20 +188,26 @@ int veto_nms(void* stream, const veto_nms_args_t* a) {
 }
 
 // workspace: prob | dec | row_score | row_label | list_score | list_row | list_label
-static size_t box_post_list_rows(int32_t n_box, int32_t n_cls, int32_t filter_dup) {
-  return filter_dup ? (size_t)n_box : (size_t)n_box * (n_cls - 1);
+static size_t carve_box_post(Carver c, size_t n_box, int n_cls, bool filter_dup, BoxPostArgs* p) {
+  const size_t list_rows = filter_dup ? n_box : n_box * (n_cls - 1);
+  p->prob = c.take<float>(n_box * n_cls * 4);
+  p->dec = c.take<float>(n_box * n_cls * 16);
+  p->row_score = c.take<float>(n_box * 4);
+  p->row_label = c.take<int32_t>(n_box * 4);
+  p->list_score = c.take<float>(list_rows * 4);
+  p->list_row = c.take<int32_t>(list_rows * 4);
+  p->list_label = c.take<int32_t>(list_rows * 4);
+  return c.off;
 }
 
 size_t veto_box_postprocess_workspace_bytes(int32_t n_box, int32_t n_cls, int32_t filter_duplicates) {
   if (n_box <= 0 || n_cls < 2) return 256;
-  const size_t rows = box_post_list_rows(n_box, n_cls, filter_duplicates);
-  return align_up((size_t)n_box * n_cls * 4, 256) + align_up((size_t)n_box * n_cls * 16, 256) + 2 * align_up((size_t)n_box * 4, 256) +
-         3 * align_up(rows * 4, 256);
+  BoxPostArgs p{};
+  return carve_box_post(Carver{nullptr}, n_box, n_cls, filter_duplicates != 0, &p);
 }
 
 int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_box_post_args_t)) return fail(VETO_ERR_INVALID, "veto_box_post_args_t size mismatch");
+  CHECK_STRUCT(veto_box_post_args_t, a);
   if (a->n_img <= 0 || a->n_box <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_box %d)", a->n_img, a->n_box);
   if (a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d above 65535", a->n_img);
   if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
@@ -239,8 +215,7 @@ int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* work
     return fail(VETO_ERR_INVALID, "reg_cols %d: must be 4 * n_cls (%d), or a multiple of 4 with cls_agnostic", a->reg_cols, 4 * a->n_cls);
   if (!(a->score_thresh >= 0.f)) return fail(VETO_ERR_INVALID, "score_thresh %g must be >= 0 (SCORE_THRESH)", a->score_thresh);
   if (!(a->nms_thresh > 0.f)) return fail(VETO_ERR_INVALID, "nms_thresh %g must be > 0 (ROI_HEADS.NMS)", a->nms_thresh);
-  for (int k = 0; k < 4; ++k)
-    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0 (BBOX_REG_WEIGHTS)", k, a->reg_weights[k]);
+  ABI_TRY(check_reg_weights(a->reg_weights, true, " (BBOX_REG_WEIGHTS)"));
   if (!a->img_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_offset_host");
   const int largest = check_host_offsets(a->img_offset_host, a->n_img, a->n_box, nms_max_segment(), "img_offset_host", "n_box");
   if (largest < 0) return largest;
@@ -249,10 +224,7 @@ int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* work
     return fail(VETO_ERR_INVALID, "missing pointer");
   if ((((uintptr_t)a->box_regression | (uintptr_t)a->proposals | (uintptr_t)a->boxes | (uintptr_t)a->boxes_per_cls) & 15) != 0)
     return fail(VETO_ERR_INVALID, "box_regression, proposals, boxes and boxes_per_cls must be 16-byte aligned");
-  const size_t need = veto_box_postprocess_workspace_bytes(a->n_box, a->n_cls, a->filter_duplicates);
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
-                                                        workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_box_postprocess_workspace_bytes(a->n_box, a->n_cls, a->filter_duplicates), true));
   BoxPostArgs p{};
   p.logits = a->class_logits; p.regression = a->box_regression; p.proposals = a->proposals; p.image_sizes = a->image_sizes;
   p.img_off = a->img_offset; p.out_off = a->img_out_offset;
@@ -261,15 +233,7 @@ int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* work
   p.score_thresh = a->score_thresh; p.nms_thresh = a->nms_thresh;
   p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
   p.xform_clip = a->bbox_xform_clip;
-  const size_t rows = box_post_list_rows(a->n_box, a->n_cls, a->filter_duplicates);
-  char* base = (char*)workspace;
-  p.prob = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 4, 256);
-  p.dec = (float*)base; base += align_up((size_t)a->n_box * a->n_cls * 16, 256);
-  p.row_score = (float*)base; base += align_up((size_t)a->n_box * 4, 256);
-  p.row_label = (int32_t*)base; base += align_up((size_t)a->n_box * 4, 256);
-  p.list_score = (float*)base; base += align_up(rows * 4, 256);
-  p.list_row = (int32_t*)base; base += align_up(rows * 4, 256);
-  p.list_label = (int32_t*)base;
+  carve_box_post(Carver{(char*)workspace}, a->n_box, a->n_cls, p.filter_dup, &p);
   p.orig_inds = a->orig_inds; p.labels = a->pred_labels; p.scores = a->pred_scores; p.boxes = a->boxes;
   p.boxes_per_cls = a->boxes_per_cls; p.counts = a->counts;
   HIP_TRY(launch_box_postprocess(p, largest, (hipStream_t)stream));
@@ -278,15 +242,13 @@ int veto_box_postprocess(void* stream, const veto_box_post_args_t* a, void* work
 
 // the host fields of the RPN arguments: capacity = the largest k of a level, or -1 (error set)
 static int rpn_check_shapes(const veto_rpn_args_t* a) {
-  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
-  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  ABI_TRY(check_rpn_counts(a));
   if (a->pre_nms_top_n <= 0 || a->pre_nms_top_n > nms_max_segment())
     return fail(VETO_ERR_INVALID, "pre_nms_top_n %d outside 1..%d (MODEL.RPN.PRE_NMS_TOP_N; the limit is veto_nms_max_segment())",
                 a->pre_nms_top_n, nms_max_segment());
   int capacity = 0;
   for (int l = 0; l < a->n_lvl; ++l) {
-    if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
-      return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+    ABI_TRY(check_rpn_level(a, l));
     const int64_t n = (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
     if (n > INT32_MAX) return fail(VETO_ERR_INVALID, "level %d holds %lld anchors, the limit is %d", l, (long long)n, INT32_MAX);
     const int k = n < a->pre_nms_top_n ? (int)n : a->pre_nms_top_n;
@@ -296,23 +258,33 @@ static int rpn_check_shapes(const veto_rpn_args_t* a) {
 }
 
 // workspace: cand_box | cand_logit | cand_anchor | keep | live | kept | cut
+static size_t carve_rpn(Carver c, size_t n_img, size_t n_lvl, size_t capacity, RpnArgs* p) {
+  const size_t n_seg = n_img * n_lvl, rows = n_seg * capacity;
+  p->cand_box = c.take<float>(rows * 16);
+  p->cand_logit = c.take<float>(rows * 4);
+  p->cand_anchor = c.take<int32_t>(rows * 4);
+  p->keep = c.take<int32_t>(rows * 4);
+  p->live = c.take<int32_t>(n_seg * 4);
+  p->kept = c.take<int32_t>(n_seg * 4);
+  p->cut = c.take<int32_t>((4 + n_img) * 4);
+  return c.off;
+}
+
 size_t veto_rpn_proposals_workspace_bytes(const veto_rpn_args_t* a) {
   if (!a || a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return 0;
   const int capacity = rpn_check_shapes(a);
   if (capacity < 0) return 0;
-  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
-  return align_up(rows * 16, 256) + 3 * align_up(rows * 4, 256) + 2 * align_up(n_seg * 4, 256) + align_up((4 + (size_t)a->n_img) * 4, 256);
+  RpnArgs p{};
+  return carve_rpn(Carver{nullptr}, a->n_img, a->n_lvl, capacity, &p);
 }
 
 int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_rpn_args_t)) return fail(VETO_ERR_INVALID, "veto_rpn_args_t size mismatch");
+  CHECK_STRUCT(veto_rpn_args_t, a);
   const int capacity = rpn_check_shapes(a);
   if (capacity < 0) return capacity;
   const bool nms_on = a->nms_thresh > 0.f, merge = a->n_lvl > 1;
   if (merge && a->fpn_post_nms_top_n <= 0) return fail(VETO_ERR_INVALID, "fpn_post_nms_top_n %d must be > 0 with %d levels", a->fpn_post_nms_top_n, a->n_lvl);
-  for (int k = 0; k < 4; ++k)
-    if (!(a->reg_weights[k] > 0.f)) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g must be > 0", k, a->reg_weights[k]);
+  ABI_TRY(check_reg_weights(a->reg_weights, true, ""));
   if (merge && a->per_batch) {
     if (a->n_img > rpn_batch_cut_max_images())
       return fail(VETO_ERR_INVALID, "per_batch: n_img %d above %d", a->n_img, rpn_batch_cut_max_images());
@@ -335,9 +307,7 @@ int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, 
   if (!a->image_sizes || !a->img_out_offset || !a->boxes || !a->objectness_out || !a->level || !a->anchor_index || !a->counts)
     return fail(VETO_ERR_INVALID, "missing pointer");
   if (((uintptr_t)a->boxes & 15) != 0) return fail(VETO_ERR_INVALID, "boxes must be 16-byte aligned");
-  const size_t need = veto_rpn_proposals_workspace_bytes(a);
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_rpn_proposals_workspace_bytes(a), true));
   RpnArgs p{};
   for (int l = 0; l < a->n_lvl; ++l) {
     RpnLevel& v = p.lvl[l];
@@ -351,29 +321,27 @@ int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, 
   p.nms_thresh = a->nms_thresh; p.min_size = a->min_size;
   p.wx = a->reg_weights[0]; p.wy = a->reg_weights[1]; p.ww = a->reg_weights[2]; p.wh = a->reg_weights[3];
   p.xform_clip = a->bbox_xform_clip;
-  const size_t n_seg = (size_t)a->n_img * a->n_lvl, rows = n_seg * capacity;
-  char* base = (char*)workspace;
-  p.cand_box = (float*)base; base += align_up(rows * 16, 256);
-  p.cand_logit = (float*)base; base += align_up(rows * 4, 256);
-  p.cand_anchor = (int32_t*)base; base += align_up(rows * 4, 256);
-  p.keep = (int32_t*)base; base += align_up(rows * 4, 256);
-  p.live = (int32_t*)base; base += align_up(n_seg * 4, 256);
-  p.kept = (int32_t*)base; base += align_up(n_seg * 4, 256);
-  p.cut = (int32_t*)base;
+  carve_rpn(Carver{(char*)workspace}, a->n_img, a->n_lvl, capacity, &p);
   p.boxes = a->boxes; p.objectness = a->objectness_out; p.level = a->level; p.anchor_index = a->anchor_index; p.counts = a->counts;
   HIP_TRY(launch_rpn_proposals(p, (hipStream_t)stream));
   return VETO_OK;
 }
 
+// workspace: ws_nm | ws_fg
+static size_t carve_relsample(Carver c, size_t n_rel_cells, int per_rel, RelSampleArgs* p) {
+  p->ws_nm = c.take<int64_t>(n_rel_cells * 8);
+  p->ws_fg = c.take<uint32_t>(n_rel_cells * per_rel * 4);
+  return c.off;
+}
+
 size_t veto_detect_relsample_workspace_bytes(int32_t n_rel_cells, int32_t num_sample_per_gt_rel) {
   if (n_rel_cells <= 0 || num_sample_per_gt_rel <= 0) return 256;
-  return align_up((size_t)n_rel_cells * 8, 256) + align_up((size_t)n_rel_cells * num_sample_per_gt_rel * 4, 256);
+  RelSampleArgs p{};
+  return carve_relsample(Carver{nullptr}, n_rel_cells, num_sample_per_gt_rel, &p);
 }
 
 int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_detect_relsample_args_t))
-    return fail(VETO_ERR_INVALID, "veto_detect_relsample_args_t size mismatch");
+  CHECK_STRUCT(veto_detect_relsample_args_t, a);
   if (a->n_img <= 0 || a->n_prp < 0 || a->n_tgt < 0 || a->n_rel_cells < 0)
     return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d, n_tgt %d, n_rel_cells %d)", a->n_img, a->n_prp, a->n_tgt,
                 a->n_rel_cells);
@@ -383,24 +351,17 @@ int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, v
                 a->max_prp_per_image, lim);
   if (a->max_tgt_per_image < 0 || a->max_tgt_per_image > lim)
     return fail(VETO_ERR_INVALID, "max_tgt_per_image %d outside 0..%d (GT boxes per image)", a->max_tgt_per_image, lim);
-  if (a->batch_size_per_image < 1 || a->batch_size_per_image > relsample_max_batch())
-    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
-                relsample_max_batch());
+  ABI_TRY(check_batch_size(a->batch_size_per_image, relsample_max_batch(), "BATCH_SIZE_PER_IMAGE"));
   if (a->num_sample_per_gt_rel < 1 || a->num_sample_per_gt_rel > relsample_max_per_rel())
     return fail(VETO_ERR_INVALID, "num_sample_per_gt_rel %d outside 1..%d (NUM_SAMPLE_PER_GT_REL)", a->num_sample_per_gt_rel,
                 relsample_max_per_rel());
-  if (a->max_fg_per_image < 0 || a->max_fg_per_image > a->batch_size_per_image)
-    return fail(VETO_ERR_INVALID, "max_fg_per_image %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)",
-                a->max_fg_per_image, a->batch_size_per_image);
+  ABI_TRY(check_positives("max_fg_per_image", a->max_fg_per_image, a->batch_size_per_image));
   if ((a->n_prp > 0 && (!a->prp_boxes || !a->prp_labels || !a->prp_scores || !a->locating_match)) ||
       (a->n_tgt > 0 && (!a->tgt_boxes || !a->tgt_labels)) || (a->n_rel_cells > 0 && !a->relation) ||
       (a->relation_non_masked && !a->labels_all) || !a->img_prp_offset || !a->img_tgt_offset || !a->img_rel_offset ||
       !a->img_binary_offset || !a->pairs || !a->labels || !a->binary_rel || !a->counts)
     return fail(VETO_ERR_INVALID, "missing pointer");
-  const size_t need = veto_detect_relsample_workspace_bytes(a->n_rel_cells, a->num_sample_per_gt_rel);
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need,
-                                                        workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_detect_relsample_workspace_bytes(a->n_rel_cells, a->num_sample_per_gt_rel), true));
   RelSampleArgs p{};
   p.prp_boxes = a->prp_boxes; p.prp_labels = a->prp_labels; p.prp_scores = a->prp_scores;
   p.tgt_boxes = a->tgt_boxes; p.tgt_labels = a->tgt_labels;
@@ -410,8 +371,7 @@ int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, v
   p.max_fg = a->max_fg_per_image; p.batch = a->batch_size_per_image;
   p.out_rows = a->batch_size_per_image > 2 ? a->batch_size_per_image : 2;
   p.fg_thres = a->fg_thres; p.seed = a->seed;
-  p.ws_nm = (int64_t*)workspace;
-  p.ws_fg = (uint32_t*)((char*)workspace + align_up((size_t)a->n_rel_cells * 8, 256));
+  carve_relsample(Carver{(char*)workspace}, a->n_rel_cells, a->num_sample_per_gt_rel, &p);
   p.pairs = a->pairs; p.labels = a->labels; p.labels_all = a->relation_non_masked ? a->labels_all : nullptr;
   p.binary = a->binary_rel; p.locating = a->locating_match; p.counts = a->counts;
   HIP_TRY(launch_detect_relsample(p, (hipStream_t)stream));
@@ -419,19 +379,13 @@ int veto_detect_relsample(void* stream, const veto_detect_relsample_args_t* a, v
 }
 
 int veto_gtbox_relsample(void* stream, const veto_gtbox_relsample_args_t* a) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_gtbox_relsample_args_t))
-    return fail(VETO_ERR_INVALID, "veto_gtbox_relsample_args_t size mismatch");
+  CHECK_STRUCT(veto_gtbox_relsample_args_t, a);
   if (a->n_img <= 0 || a->n_rel_cells < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_rel_cells %d)", a->n_img, a->n_rel_cells);
   if (a->max_obj_per_image < 0 || a->max_obj_per_image > gtbox_relsample_max_objects())
     return fail(VETO_ERR_INVALID, "max_obj_per_image %d outside 0..%d (GT boxes per image)", a->max_obj_per_image,
                 gtbox_relsample_max_objects());
-  if (a->batch_size_per_image < 1 || a->batch_size_per_image > gtbox_relsample_max_batch())
-    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
-                gtbox_relsample_max_batch());
-  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
-    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
-                a->batch_size_per_image);
+  ABI_TRY(check_batch_size(a->batch_size_per_image, gtbox_relsample_max_batch(), "BATCH_SIZE_PER_IMAGE"));
+  ABI_TRY(check_positives("num_pos_per_img", a->num_pos_per_img, a->batch_size_per_image));
   if ((a->n_rel_cells > 0 && (!a->relation || !a->binary_rel)) || !a->img_obj_offset || !a->img_rel_offset || !a->pairs ||
       !a->labels || !a->counts)
     return fail(VETO_ERR_INVALID, "missing pointer");
@@ -456,8 +410,7 @@ static const char* const kNoGtBoxes = "No ground-truth boxes available for one o
 static const char* const kNoProposals = "No proposal boxes available for one of the images during training";
 
 int veto_box_match(void* stream, const veto_box_match_args_t* a) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_box_match_args_t)) return fail(VETO_ERR_INVALID, "veto_box_match_args_t size mismatch");
+  CHECK_STRUCT(veto_box_match_args_t, a);
   if (a->n_img <= 0 || a->n_img > 65535 || a->n_prp < 0 || a->n_tgt < 0)
     return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d, n_tgt %d)", a->n_img, a->n_prp, a->n_tgt);
   if (a->mode != 0 && a->mode != 1) return fail(VETO_ERR_INVALID, "mode must be 0 (assign_label_to_proposals) or 1 (prepare_targets)");
@@ -472,9 +425,7 @@ int veto_box_match(void* stream, const veto_box_match_args_t* a) {
   const int largest = check_box_sample_offsets(a->img_prp_offset_host, a->n_img, a->n_prp, box_subsample_max_proposals(),
                                                "img_prp_offset_host", "n_prp", kNoProposals);
   if (largest < 0) return largest;
-  if (a->regression_targets)
-    for (int k = 0; k < 4; ++k)
-      if (!std::isfinite(a->reg_weights[k])) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g (BBOX_REG_WEIGHTS)", k, a->reg_weights[k]);
+  if (a->regression_targets) ABI_TRY(check_reg_weights(a->reg_weights, false, " (BBOX_REG_WEIGHTS)"));
   if (!a->prp_boxes || !a->tgt_boxes || !a->tgt_labels || !a->img_prp_offset || !a->img_tgt_offset || !a->matched_idxs || !a->labels)
     return fail(VETO_ERR_INVALID, "missing pointer");
   if ((((uintptr_t)a->prp_boxes | (uintptr_t)a->tgt_boxes | (uintptr_t)a->regression_targets) & 15) != 0)
@@ -490,15 +441,10 @@ int veto_box_match(void* stream, const veto_box_match_args_t* a) {
 }
 
 int veto_box_subsample(void* stream, const veto_box_subsample_args_t* a) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_box_subsample_args_t)) return fail(VETO_ERR_INVALID, "veto_box_subsample_args_t size mismatch");
+  CHECK_STRUCT(veto_box_subsample_args_t, a);
   if (a->n_img <= 0 || a->n_prp < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_prp %d)", a->n_img, a->n_prp);
-  if (a->batch_size_per_image < 1 || a->batch_size_per_image > box_subsample_max_batch())
-    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
-                box_subsample_max_batch());
-  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
-    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
-                a->batch_size_per_image);
+  ABI_TRY(check_batch_size(a->batch_size_per_image, box_subsample_max_batch(), "BATCH_SIZE_PER_IMAGE"));
+  ABI_TRY(check_positives("num_pos_per_img", a->num_pos_per_img, a->batch_size_per_image));
   if (!a->img_prp_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: img_prp_offset_host");
   if (check_box_sample_offsets(a->img_prp_offset_host, a->n_img, a->n_prp, box_subsample_max_proposals(), "img_prp_offset_host", "n_prp",
                                kNoProposals) < 0)
@@ -514,16 +460,12 @@ int veto_box_subsample(void* stream, const veto_box_subsample_args_t* a) {
 
 // the host fields of the RPN loss arguments: anchors per image, or -1 (error set)
 static int rpn_loss_check_shapes(const veto_rpn_loss_args_t* a) {
-  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
-  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  ABI_TRY(check_rpn_counts(a));
   if (a->n_tgt < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_tgt %d)", a->n_tgt);
-  if (a->batch_size_per_image < 1 || a->batch_size_per_image > rpn_loss_max_batch())
-    return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (MODEL.RPN.BATCH_SIZE_PER_IMAGE)", a->batch_size_per_image,
-                rpn_loss_max_batch());
+  ABI_TRY(check_batch_size(a->batch_size_per_image, rpn_loss_max_batch(), "MODEL.RPN.BATCH_SIZE_PER_IMAGE"));
   int64_t n_anchor = 0;
   for (int l = 0; l < a->n_lvl; ++l) {
-    if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
-      return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+    ABI_TRY(check_rpn_level(a, l));
     n_anchor += (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
     if (n_anchor > rpn_loss_max_anchors())
       return fail(VETO_ERR_INVALID, "levels 0..%d: an image holds %lld anchors, the limit is %d", l, (long long)n_anchor, rpn_loss_max_anchors());
@@ -532,23 +474,31 @@ static int rpn_loss_check_shapes(const veto_rpn_loss_args_t* a) {
 }
 
 // workspace: gtmax | labels | matched | sampled | counts | partial | hist
+static size_t carve_rpn_loss(Carver c, const veto_rpn_loss_args_t* a, size_t n_anchor, RpnLossArgs* p) {
+  const size_t n_img = a->n_img, rows = n_img * n_anchor;
+  p->gtmax = c.take<uint32_t>((size_t)a->n_tgt * 4 + 4);
+  p->labels_ws = c.take<float>(rows * 4);      // (reserved also when the caller's `labels` takes its place)
+  p->matched_ws = c.take<int32_t>(rows * 4);
+  p->sampled_ws = c.take<int32_t>(n_img * a->batch_size_per_image * 4);
+  p->counts_ws = c.take<int32_t>(n_img * 8);
+  p->partial = c.take<double>(n_img * 16);
+  p->hist = c.take<int32_t>(n_img * 2048);
+  return c.off;
+}
+
 size_t veto_rpn_loss_workspace_bytes(const veto_rpn_loss_args_t* a) {
   if (!a || a->struct_size != (int32_t)sizeof(veto_rpn_loss_args_t)) return 0;
   const int n_anchor = rpn_loss_check_shapes(a);
   if (n_anchor < 0) return 0;
-  const size_t rows = (size_t)a->n_img * n_anchor;
-  return align_up((size_t)a->n_tgt * 4 + 4, 256) + 2 * align_up(rows * 4, 256) + align_up((size_t)a->n_img * a->batch_size_per_image * 4, 256) +
-         align_up((size_t)a->n_img * 8, 256) + align_up((size_t)a->n_img * 16, 256) + align_up((size_t)a->n_img * 2048, 256);
+  RpnLossArgs p{};
+  return carve_rpn_loss(Carver{nullptr}, a, n_anchor, &p);
 }
 
 int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_rpn_loss_args_t)) return fail(VETO_ERR_INVALID, "veto_rpn_loss_args_t size mismatch");
+  CHECK_STRUCT(veto_rpn_loss_args_t, a);
   const int n_anchor = rpn_loss_check_shapes(a);
   if (n_anchor < 0) return n_anchor;
-  if (a->num_pos_per_img < 0 || a->num_pos_per_img > a->batch_size_per_image)
-    return fail(VETO_ERR_INVALID, "num_pos_per_img %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", a->num_pos_per_img,
-                a->batch_size_per_image);
+  ABI_TRY(check_positives("num_pos_per_img", a->num_pos_per_img, a->batch_size_per_image));
   if (!(a->low_threshold <= a->high_threshold))
     return fail(VETO_ERR_INVALID, "low_threshold %g must be <= high_threshold %g (BG_IOU_THRESHOLD, FG_IOU_THRESHOLD)", a->low_threshold,
                 a->high_threshold);
@@ -565,8 +515,7 @@ int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* a, void* workspace, 
     return fail(VETO_ERR_INVALID, "no output requested");
   if (last_stage == kRpnLossLoss || a->regression_targets) {
     if (!(a->beta > 0.0) && last_stage == kRpnLossLoss) return fail(VETO_ERR_INVALID, "beta %g must be > 0", a->beta);
-    for (int k = 0; k < 4; ++k)
-      if (!std::isfinite(a->reg_weights[k])) return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g", k, a->reg_weights[k]);
+    ABI_TRY(check_reg_weights(a->reg_weights, false, ""));
   }
   for (int l = 0; l < a->n_lvl; ++l) {
     if (!a->anchors[l] || (last_stage == kRpnLossLoss && (!a->objectness[l] || !a->box_regression[l])))
@@ -578,20 +527,11 @@ int veto_rpn_loss(void* stream, const veto_rpn_loss_args_t* a, void* workspace, 
   if (!a->image_sizes || !a->tgt_boxes || !a->img_tgt_offset) return fail(VETO_ERR_INVALID, "missing pointer");
   if ((((uintptr_t)a->tgt_boxes | (uintptr_t)a->regression_targets) & 15) != 0)
     return fail(VETO_ERR_INVALID, "tgt_boxes and regression_targets must be 16-byte aligned");
-  const size_t need = veto_rpn_loss_workspace_bytes(a);
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_rpn_loss_workspace_bytes(a), true));
   RpnLossArgs p{};
   RpnFillArgs fill{};
-  const size_t rows = (size_t)a->n_img * n_anchor;
-  char* base = (char*)workspace;
-  p.gtmax = (uint32_t*)base; base += align_up((size_t)a->n_tgt * 4 + 4, 256);
-  p.labels_ws = a->labels ? a->labels : (float*)base; base += align_up(rows * 4, 256);
-  p.matched_ws = (int32_t*)base; base += align_up(rows * 4, 256);
-  p.sampled_ws = (int32_t*)base; base += align_up((size_t)a->n_img * a->batch_size_per_image * 4, 256);
-  p.counts_ws = (int32_t*)base; base += align_up((size_t)a->n_img * 8, 256);
-  p.partial = (double*)base; base += align_up((size_t)a->n_img * 16, 256);
-  p.hist = (int32_t*)base;
+  carve_rpn_loss(Carver{(char*)workspace}, a, n_anchor, &p);
+  if (a->labels) p.labels_ws = a->labels;
   fill.ptr[0] = (float*)p.gtmax; fill.n[0] = a->n_tgt; fill.n_seg = 1;
   if (last_stage >= kRpnLossSample) { fill.ptr[1] = (float*)p.hist; fill.n[1] = (long long)a->n_img * 512; fill.n_seg = 2; }
   int off = 0;
@@ -631,17 +571,21 @@ static int box_loss_check_shapes(const veto_box_loss_args_t* a) {
 }
 
 // workspace: the rows' partial pairs
+static size_t carve_box_loss(Carver c, size_t n_rows, BoxLossArgs* p) {
+  p->partial = c.take<double>(n_rows * 16 + 16);
+  return c.off;
+}
+
 size_t veto_box_loss_workspace_bytes(const veto_box_loss_args_t* a) {
   if (!a || a->struct_size != (int32_t)sizeof(veto_box_loss_args_t)) return 0;
   if (box_loss_check_shapes(a) != VETO_OK) return 0;
-  return align_up((size_t)a->n_rows * 16 + 16, 256);
+  BoxLossArgs p{};
+  return carve_box_loss(Carver{nullptr}, a->n_rows, &p);
 }
 
 int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_box_loss_args_t)) return fail(VETO_ERR_INVALID, "veto_box_loss_args_t size mismatch");
-  const int rc = box_loss_check_shapes(a);
-  if (rc != VETO_OK) return rc;
+  CHECK_STRUCT(veto_box_loss_args_t, a);
+  ABI_TRY(box_loss_check_shapes(a));
   if (!a->losses) return fail(VETO_ERR_INVALID, "missing pointer: losses");
   if (a->n_rows > 0 && (!a->class_logits || !a->box_regression || !a->labels || !a->regression_targets))
     return fail(VETO_ERR_INVALID, "missing pointer: class_logits, box_regression, labels and regression_targets are required");
@@ -652,14 +596,12 @@ int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, 
     return fail(VETO_ERR_INVALID, "d_class_logits and d_box_regression must be 16-byte aligned");
   if ((((uintptr_t)a->class_logits | (uintptr_t)a->box_regression | (uintptr_t)a->losses) & 3) != 0 || ((uintptr_t)a->labels & 7) != 0)
     return fail(VETO_ERR_INVALID, "misaligned class_logits, box_regression, losses or labels");
-  const size_t need = veto_box_loss_workspace_bytes(a);
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_box_loss_workspace_bytes(a), true));
   BoxLossArgs p{};
   p.logits = a->class_logits; p.reg = a->box_regression; p.labels = a->labels; p.targets = a->regression_targets;
   p.n_rows = a->n_rows; p.n_cls = a->n_cls; p.n_reg_cols = a->n_reg_cols; p.cls_agnostic = a->cls_agnostic != 0;
   p.ld_logits = a->ld_logits; p.ld_reg = a->ld_reg;
-  p.partial = (double*)workspace;
+  carve_box_loss(Carver{(char*)workspace}, a->n_rows, &p);
   p.losses = a->losses; p.d_logits = a->d_class_logits; p.d_reg = a->d_box_regression;
   HIP_TRY(launch_box_loss(p, (hipStream_t)stream));
   return VETO_OK;
@@ -667,8 +609,7 @@ int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, 
 
 // shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
 static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_roi_pool_args_t)) return fail(VETO_ERR_INVALID, "veto_roi_pool_args_t size mismatch");
+  CHECK_STRUCT(veto_roi_pool_args_t, a);
   if (a->n_levels < 1 || a->n_levels > 4) return fail(VETO_ERR_INVALID, "n_levels must be 1..4, got %d", a->n_levels);
   if (a->n_img <= 0 || a->n_roi <= 0 || a->channels <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_roi %d, channels %d)", a->n_img, a->n_roi, a->channels);
   if (a->pooled < 1 || a->pooled > 8) return fail(VETO_ERR_INVALID, "pooled must be 1..8, got %d", a->pooled);
@@ -702,8 +643,7 @@ static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArg
 
 int veto_roi_pool(void* stream, const veto_roi_pool_args_t* a) {
   RoiPoolArgs p{};
-  const int rc = roi_pool_args(a, true, &p);
-  if (rc != VETO_OK) return rc;
+  ABI_TRY(roi_pool_args(a, true, &p));
   HIP_TRY(launch_roi_pool(p, (hipStream_t)stream));
   return VETO_OK;
 }
@@ -711,8 +651,7 @@ int veto_roi_pool(void* stream, const veto_roi_pool_args_t* a) {
 int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
                            float* const* level_grad, float* depth_grad) {
   RoiPoolArgs p{};
-  const int rc = roi_pool_args(a, false, &p);
-  if (rc != VETO_OK) return rc;
+  ABI_TRY(roi_pool_args(a, false, &p));
   if (!grad_rgb || !level_grad) return fail(VETO_ERR_INVALID, "missing gradient pointer");
   for (int l = 0; l < p.n_levels; ++l) {
     if (!level_grad[l]) return fail(VETO_ERR_INVALID, "level_grad[%d] is null", l);
@@ -727,10 +666,23 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const fl
   return VETO_OK;
 }
 
+// workspace: label_tmp | flag_tmp | flag_before | pair_score | row_key | acc_first | cls_table
+static size_t carve_sgg_eval(Carver c, size_t n_img, size_t n_pair_total, size_t n_gt_total, int n_rel_cls, SggEvalArgs* p) {
+  const size_t per_pair = n_pair_total * 4 + 4;
+  p->label_tmp = c.take<int32_t>(per_pair);
+  p->flag_tmp = c.take<int32_t>(per_pair);
+  p->flag_before = c.take<int32_t>(per_pair);
+  p->pair_score = c.take<float>(per_pair);
+  p->row_key = c.take<uint32_t>(per_pair);
+  p->acc_first = c.take<int32_t>(n_gt_total * 4 + 4);
+  p->cls_table = c.take<int32_t>(n_img * 7 * n_rel_cls * 4);
+  return c.off;
+}
+
 size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_t n_gt_total, int32_t n_rel_cls) {
   if (n_img <= 0 || n_pair_total < 0 || n_gt_total < 0 || n_rel_cls < 2) return 0;
-  return 5 * align_up((size_t)n_pair_total * 4 + 4, 256) + align_up((size_t)n_gt_total * 4 + 4, 256) +
-         align_up((size_t)n_img * 7 * n_rel_cls * 4, 256);
+  SggEvalArgs p{};
+  return carve_sgg_eval(Carver{nullptr}, n_img, n_pair_total, n_gt_total, n_rel_cls, &p);
 }
 
 int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_total, int32_t n_gt_total, void* workspace,
@@ -750,8 +702,7 @@ int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_to
       !a->rel_scores || !a->pred_classes || !a->pred_boxes || !a->obj_scores || (a->n_zeroshot > 0 && !a->zeroshot) ||
       !a->gc_rank || !a->ng_rank || !a->acc_rank || !a->zeroshot_flag || !a->ng_rows || !a->ng_cols || !a->ng_count || !a->metrics)
     return fail(VETO_ERR_INVALID, "missing pointer");
-  if (workspace_bytes < veto_sgg_eval_workspace_bytes(a->n_img, n_pair_total, n_gt_total, a->n_rel_cls))
-    return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_sgg_eval_workspace_bytes(a->n_img, n_pair_total, n_gt_total, a->n_rel_cls), false));
   SggEvalArgs p{};
   p.n_img = a->n_img; p.n_rel_cls = a->n_rel_cls; p.n_zeroshot = a->n_zeroshot; p.iou_thres = a->iou_thres;
   p.gt_off = a->gt_offset; p.obj_off = a->obj_offset; p.pair_off = a->pair_offset;
@@ -761,15 +712,7 @@ int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_to
   p.pred_boxes = a->pred_boxes; p.obj_scores = a->obj_scores; p.zeroshot = a->zeroshot;
   p.gc_rank = a->gc_rank; p.ng_rank = a->ng_rank; p.acc_rank = a->acc_rank; p.zeroshot_flag = a->zeroshot_flag;
   p.ng_rows = a->ng_rows; p.ng_cols = a->ng_cols; p.ng_count = a->ng_count; p.metrics = a->metrics;
-  char* base = (char*)workspace;
-  const size_t per_pair = align_up((size_t)n_pair_total * 4 + 4, 256);
-  p.label_tmp = (int32_t*)base; base += per_pair;
-  p.flag_tmp = (int32_t*)base; base += per_pair;
-  p.flag_before = (int32_t*)base; base += per_pair;
-  p.pair_score = (float*)base; base += per_pair;
-  p.row_key = (uint32_t*)base; base += per_pair;
-  p.acc_first = (int32_t*)base; base += align_up((size_t)n_gt_total * 4 + 4, 256);
-  p.cls_table = (int32_t*)base;
+  carve_sgg_eval(Carver{(char*)workspace}, a->n_img, n_pair_total, n_gt_total, a->n_rel_cls, &p);
   HIP_TRY(launch_sgg_eval(p, (hipStream_t)stream));
   return VETO_OK;
 }

@@ -24,36 +24,31 @@ struct Workspace {
 // Carves (or, with base == nullptr, just sizes) the workspace.
 Workspace carve(char* base, int n_obj, int n_pair, int chunk) {
   Workspace w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* ptr = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return ptr;
-  };
+  Carver c{base};
   const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
   // (the fused QKV + attention launch reads whole tiles of 16 pairs: the activation rows are padded to those too)
   const size_t tile_rows = qkv_attn_rows_padded(chunk);
   const size_t mpad = (size_t)gemm_rows_padded((int)(tile_rows > (size_t)chunk * kTokens ? tile_rows : (size_t)chunk * kTokens));
   const size_t cpad = (size_t)gemm_rows_padded(chunk);
-  w.subj = (int32_t*)take((size_t)n_pair * 4);
-  w.obj = (int32_t*)take((size_t)n_pair * 4);
-  w.lc = (float*)take((size_t)n_obj * 2 * 2 * kDim * 4);
-  w.pa = (__bf16*)take(prow * 2 * 2048 * 2);
-  w.patch_tab = (float*)take((size_t)n_obj * 16 * 2 * kDim * 4);
-  w.x = (float*)take(mpad * kDim * 4);
-  w.a = (__bf16*)take(mpad * 2 * kDim * 2);
+  w.subj = c.take<int32_t>((size_t)n_pair * 4);
+  w.obj = c.take<int32_t>((size_t)n_pair * 4);
+  w.lc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
+  w.pa = c.take<__bf16>(prow * 2 * 2048 * 2);
+  w.patch_tab = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.x = c.take<float>(mpad * kDim * 4);
+  w.a = c.take<__bf16>(mpad * 2 * kDim * 2);
   {   // qkv of a chunk; in the last layer instead u [cpad, H*576] fp32 + abar [cpad, 2*H*576] split (folded CLS attention)
     const size_t qkv_bytes = mpad * 3 * kDim * 4, fold_bytes = 2 * (align_up(cpad * (size_t)cls_fold_max_heads() * kDim * 4, 256));
-    w.big = take(qkv_bytes > fold_bytes ? qkv_bytes : fold_bytes);
+    w.big = c.take(qkv_bytes > fold_bytes ? qkv_bytes : fold_bytes);
   }
-  w.xc = (float*)take(cpad * kDim * 4);
-  w.ptab_split = (__bf16*)take(prow * 2 * 2 * kDim * 2);
-  w.sw = (float*)take(prow * 3 * kDim * 4);
-  w.ow = (float*)take(prow * 3 * kDim * 4);
-  w.stats = (float*)take(mpad * 2 * 4);
-  w.ac = (__bf16*)take(cpad * 2 * kDim * 2);
-  w.hc = (__bf16*)take(cpad * 4 * kDim * 2);
-  w.total = off;
+  w.xc = c.take<float>(cpad * kDim * 4);
+  w.ptab_split = c.take<__bf16>(prow * 2 * 2 * kDim * 2);
+  w.sw = c.take<float>(prow * 3 * kDim * 4);
+  w.ow = c.take<float>(prow * 3 * kDim * 4);
+  w.stats = c.take<float>(mpad * 2 * 4);
+  w.ac = c.take<__bf16>(cpad * 2 * kDim * 2);
+  w.hc = c.take<__bf16>(cpad * 4 * kDim * 2);
+  w.total = c.off;
   return w;
 }
 
@@ -140,9 +135,8 @@ int object_side(veto_handle_t h, hipStream_t s, const Workspace& ws, const Forwa
   if (rc || !p.qkv0_tables) return rc;
   const int R = n_obj * 16;
   HIP_TRY(launch_centre_split(ws.patch_tab, ws.ptab_split, R, s));
-  rc = run_gemm(h, s, "gemm_qkv0_tab", ws.ptab_split, h->q0_w, h->q0_vec + 3 * kDim, nullptr, 0, ws.sw, nullptr, 3 * kDim, R, 3 * kDim, kDim,
-                EPI_F32, (long)2 * 2 * kDim, 0);
-  if (rc) return rc;
+  ABI_TRY(run_gemm(h, s, "gemm_qkv0_tab", ws.ptab_split, h->q0_w, h->q0_vec + 3 * kDim, nullptr, 0, ws.sw, nullptr, 3 * kDim, R, 3 * kDim, kDim,
+                   EPI_F32, (long)2 * 2 * kDim, 0));
   return run_gemm(h, s, "gemm_qkv0_tab", ws.ptab_split + 2 * kDim, h->q0_w, nullptr, nullptr, 0, ws.ow, nullptr, 3 * kDim, R, 3 * kDim, kDim,
                   EPI_F32, (long)2 * 2 * kDim, 0);
 }
@@ -193,10 +187,9 @@ struct Chunk {
     }
     for (int t = kTokens - 2; t < kTokens; ++t) {   // the ReLU'd location / class rows: LayerNorm'ed rows x Wqkv as usual (VETO_MIXED: mixed operands)
       if (mixed) HIP_TRY(count_sat(0, VETO_SAT_QKV_IN, ws.a + (size_t)t * 2 * kDim, (long)kTokens * kDim * 4, np, kDim));
-      int rc = run_gemm(h, s, "gemm_qkv0_lc", ws.a + (size_t)t * 2 * kDim, mixed ? w.qkv_m : w.qkv, nullptr, nullptr, 0,
-                        qkv() + (size_t)t * 3 * kDim, nullptr, (long)kTokens * 3 * kDim, np, 3 * kDim, kDim, EPI_F32, (long)kTokens * 2 * kDim, 0,
-                        DropSite(), mixed ? w.exp_m + LIN_QKV : nullptr);
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_qkv0_lc", ws.a + (size_t)t * 2 * kDim, mixed ? w.qkv_m : w.qkv, nullptr, nullptr, 0,
+                       qkv() + (size_t)t * 3 * kDim, nullptr, (long)kTokens * 3 * kDim, np, 3 * kDim, kDim, EPI_F32, (long)kTokens * 2 * kDim, 0,
+                       DropSite(), mixed ? w.exp_m + LIN_QKV : nullptr));
     }
     return VETO_OK;
   }
@@ -281,9 +274,8 @@ struct Chunk {
       HIP_TRY(launch_out_fused(f, s));
       return VETO_OK;
     }
-    int rc = run_gemm(h, s, "gemm_out", ws.a, p.mixed_out ? w.out_m : w.out, w.out_b, ws.x, kDim, ws.x, nullptr, kDim, M, kDim, kDim, EPI_RESID,
-                      0, 0, DropSite(), p.mixed_out ? w.exp_m + LIN_OUT : nullptr);
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_out", ws.a, p.mixed_out ? w.out_m : w.out, w.out_b, ws.x, kDim, ws.x, nullptr, kDim, M, kDim, kDim, EPI_RESID,
+                     0, 0, DropSite(), p.mixed_out ? w.exp_m + LIN_OUT : nullptr));
     {
       ProfScope ps(h, s, "layernorm", 0, (double)M * kDim * 8);
       HIP_TRY(launch_layernorm(ws.x, kDim, w.ln2_w, w.ln2_b, ws.a, M, s, p.mixed ? FMT_MIXED : FMT_SPLIT));
@@ -307,9 +299,8 @@ struct Chunk {
       HIP_TRY(launch_ffn_fused(f, s));
       return VETO_OK;
     }
-    int rc = run_gemm(h, s, "gemm_fc1", ws.a, mixed ? w.fc1_m : w.fc1, w.fc1_b, nullptr, 0, nullptr, hid(), 4 * kDim, M, 2 * kDim, kDim,
-                      EPI_GELU_SPLIT, 0, 0, DropSite(), mixed ? w.exp_m + LIN_FC1 : nullptr);
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_fc1", ws.a, mixed ? w.fc1_m : w.fc1, w.fc1_b, nullptr, 0, nullptr, hid(), 4 * kDim, M, 2 * kDim, kDim,
+                     EPI_GELU_SPLIT, 0, 0, DropSite(), mixed ? w.exp_m + LIN_FC1 : nullptr));
     if (mixed) HIP_TRY(count_sat(l, VETO_SAT_HIDDEN, hid(), (long)2 * kDim * 4, M, 2 * kDim));
     return run_gemm(h, s, "gemm_fc2", hid(), mixed ? w.fc2_m : w.fc2, w.fc2_b, ws.x, kDim, ws.x, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID,
                     0, 0, DropSite(), mixed ? w.exp_m + LIN_FC2 : nullptr);
@@ -339,8 +330,9 @@ struct Chunk {
     const LayerW& w = h->layers[p.L - 1];
     const int H = p.H;
     int rc;
-    float* u = (float*)ws.big;
-    __bf16* abar = (__bf16*)(ws.big + align_up((size_t)gemm_rows_padded(np) * H * kDim * 4, 256));
+    Carver fold{ws.big};      // u fp32 [rows, H*576] | abar split [rows, 2*H*576]: carve() reserved both for cls_fold_max_heads() heads
+    float* u = fold.take<float>((size_t)gemm_rows_padded(np) * H * kDim * 4);
+    __bf16* abar = fold.take<__bf16>((size_t)gemm_rows_padded(np) * 2 * H * kDim * 2);
     {   // LayerNorm1 of the CLS rows (row p*19 of x -> compact split row p): the A operand of the u GEMM
       ProfScope ps(h, s, "layernorm_cls", 0, (double)np * kDim * 8);
       HIP_TRY(launch_layernorm(xlast, (long)kTokens * kDim, w.ln1_w, w.ln1_b, ws.ac, np, s));
@@ -350,8 +342,7 @@ struct Chunk {
     if (dhp > 0) {
       // q0 = a0 Wq_pad^T as split rows (every head's dh columns padded to dhp), then u = q0 . blockdiag(Wk): column tile n of u
       // belongs to head n / 3 and multiplies that head's dhp / 32 k-steps only
-      rc = run_gemm(h, s, "gemm_q_cls", ws.ac, h->fold_q, nullptr, nullptr, 0, nullptr, ws.hc, 2L * npad, np, npad, kDim, EPI_SPLIT);
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_q_cls", ws.ac, h->fold_q, nullptr, nullptr, 0, nullptr, ws.hc, 2L * npad, np, npad, kDim, EPI_SPLIT));
       u24 = cls_fold_reads_f24();      // u as 3-byte floats: its consumer splits it into bf16 hi + lo, a 16-bit significand
       rc = run_gemm(h, s, "gemm_u_cls", ws.hc, h->fold_k, nullptr, nullptr, 0, u, nullptr, (long)H * kDim, np, H * kDim, npad,
                     u24 ? EPI_F24 : EPI_F32, 0, 0, DropSite(), nullptr, 3, dhp / 32);
@@ -367,9 +358,8 @@ struct Chunk {
       // vbar = abar . blockdiag(Wv)^T as split rows (column tile n covers the 192 / dhp heads whose 576-wide k blocks it needs),
       // then out = vbar Wo_pad^T + b_o + x_0
       const int hpt = 192 / dhp;
-      rc = run_gemm(h, s, "gemm_v_cls", abar, h->fold_v, nullptr, nullptr, 0, nullptr, ws.hc, 2L * npad, np, npad, H * kDim, EPI_SPLIT,
-                    0, 0, DropSite(), nullptr, 1, hpt * kDim / 32);
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_v_cls", abar, h->fold_v, nullptr, nullptr, 0, nullptr, ws.hc, 2L * npad, np, npad, H * kDim, EPI_SPLIT,
+                       0, 0, DropSite(), nullptr, 1, hpt * kDim / 32));
       return run_gemm(h, s, "gemm_out_cls", ws.hc, h->fold_o, w.out_b, xlast, (long)kTokens * kDim, ws.xc, nullptr, kDim, np, kDim, npad,
                       EPI_RESID);
     }
@@ -381,13 +371,11 @@ struct Chunk {
   // projection + residual on the CLS rows (row p*19 of x -> compact row p) leave x_mid in ws.xc
   int last_layer_plain() {
     const LayerW& w = h->layers[p.L - 1];
-    int rc = run_gemm(h, s, "gemm_kv_last", ws.a, w.qkv, nullptr, nullptr, 0, qkv() + kDim, nullptr, 3 * kDim, M, 2 * kDim,
-                      kDim, EPI_F32, 0, kDim);
-    if (rc) return rc;
-    rc = run_gemm(h, s, "gemm_q_cls", ws.a, w.qkv, nullptr, nullptr, 0, qkv(), nullptr, (long)kTokens * 3 * kDim, np, kDim,
-                  kDim, EPI_F32, (long)kTokens * 2 * kDim, 0);
-    if (rc) return rc;
-    if ((rc = attention(p.L - 1, false))) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_kv_last", ws.a, w.qkv, nullptr, nullptr, 0, qkv() + kDim, nullptr, 3 * kDim, M, 2 * kDim,
+                     kDim, EPI_F32, 0, kDim));
+    ABI_TRY(run_gemm(h, s, "gemm_q_cls", ws.a, w.qkv, nullptr, nullptr, 0, qkv(), nullptr, (long)kTokens * 3 * kDim, np, kDim,
+                     kDim, EPI_F32, (long)kTokens * 2 * kDim, 0));
+    ABI_TRY(attention(p.L - 1, false));
     return run_gemm(h, s, "gemm_out_cls", ws.ac, w.out, w.out_b, ws.x, (long)kTokens * kDim, ws.xc, nullptr, kDim, np,
                     kDim, kDim, EPI_RESID);
   }
@@ -404,9 +392,8 @@ struct Chunk {
     }
     // (the CLS rows' FeedForward takes mixed operands too, and those rows are the classifier's input: audited like every other site)
     if (cls_mixed) HIP_TRY(count_sat(l, VETO_SAT_FFN_IN, ws.ac, (long)kDim * 4, np, kDim));
-    int rc = run_gemm(h, s, "gemm_fc1_cls", ws.ac, cls_mixed ? w.fc1_m : w.fc1, w.fc1_b, nullptr, 0, nullptr, ws.hc, 4 * kDim, np, 2 * kDim, kDim,
-                      EPI_GELU_SPLIT, 0, 0, DropSite(), cls_mixed ? w.exp_m + LIN_FC1 : nullptr);
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_fc1_cls", ws.ac, cls_mixed ? w.fc1_m : w.fc1, w.fc1_b, nullptr, 0, nullptr, ws.hc, 4 * kDim, np, 2 * kDim, kDim,
+                     EPI_GELU_SPLIT, 0, 0, DropSite(), cls_mixed ? w.exp_m + LIN_FC1 : nullptr));
     if (cls_mixed) HIP_TRY(count_sat(l, VETO_SAT_HIDDEN, ws.hc, (long)2 * kDim * 4, np, 2 * kDim));
     return run_gemm(h, s, "gemm_fc2_cls", ws.hc, cls_mixed ? w.fc2_m : w.fc2, w.fc2_b, ws.xc, kDim, ws.xc, nullptr, kDim, np, kDim, 2 * kDim,
                     EPI_RESID, 0, 0, DropSite(), cls_mixed ? w.exp_m + LIN_FC2 : nullptr);
@@ -426,9 +413,8 @@ struct Chunk {
 // sat != nullptr (veto_forward_saturation): device counters [layers][VETO_SAT_SITES][4]
 int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* workspace, size_t workspace_bytes, float* out_logits,
                  const veto_debug_outputs_t* dbg, unsigned long long* sat) {
-  if (!h || !in || !out_logits) return fail(VETO_ERR_INVALID, "null argument");
-  if (in->struct_size != (int32_t)sizeof(veto_inputs_t)) return fail(VETO_ERR_INVALID, "veto_inputs_t size mismatch");
-  if (dbg && dbg->struct_size != (int32_t)sizeof(veto_debug_outputs_t)) return fail(VETO_ERR_INVALID, "veto_debug_outputs_t size mismatch");
+  CHECK_STRUCT_AND(veto_inputs_t, in, h && out_logits);
+  if (dbg) CHECK_STRUCT(veto_debug_outputs_t, dbg);
   if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch (n_obj=%d n_pair=%d n_img=%d)", in->n_obj, in->n_pair, in->n_img);
   if (!in->roi_rgb || !in->roi_depth || !in->boxes || !in->rel_pairs || !in->img_obj_offset || !in->img_pair_offset)
     return fail(VETO_ERR_INVALID, "missing input pointer");
@@ -437,25 +423,19 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
     return fail(VETO_ERR_INVALID, "batch too large");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (h->dirty || h->infer_dirty) {
-    int rc = finalize_weights(h, s);
-    if (rc != VETO_OK) return rc;
-  }
+  if (h->dirty || h->infer_dirty) ABI_TRY(finalize_weights(h, s));
   const int n_obj = in->n_obj, n_pair = in->n_pair;
   const int chunk = n_pair < h->chunk ? n_pair : h->chunk;
-  const size_t need = carve(nullptr, n_obj, n_pair, chunk).total;
-  if (!workspace || workspace_bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, carve(nullptr, n_obj, n_pair, chunk).total, true));
   const Workspace ws = carve((char*)workspace, n_obj, n_pair, chunk);
   const ForwardPlan p = make_plan(h, sat != nullptr);
 
-  int rc = object_side(h, s, ws, p, in, dbg);
-  if (rc) return rc;
+  ABI_TRY(object_side(h, s, ws, p, in, dbg));
   // ---- pairs, in chunks that bound the workspace ----------------------------------------------
   for (int c0 = 0; c0 < n_pair; c0 += chunk) {
     const int np = (n_pair - c0 < chunk) ? n_pair - c0 : chunk;
     Chunk c{h, s, ws, p, c0, np, np * kTokens, sat, ws.x};
-    if ((rc = c.assemble_tokens(dbg ? dbg->tokens : nullptr))) return rc;
+    int rc = c.assemble_tokens(dbg ? dbg->tokens : nullptr);
     for (int l = 0; l < p.L - 1 && !rc; ++l) {
       bool attn_in_big = false;      // this layer's attention output is in ws.big (fused QKV + attention launch)
       if (l == 0 && p.qkv0_tables) {
@@ -499,8 +479,7 @@ int veto_forward_saturation(veto_handle_t h, void* stream, const veto_inputs_t* 
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (!h->sat_buf) return fail(VETO_ERR_INVALID, "no saturation counters (handle not created in VETO_MIXED)");
   HIP_TRY(hipMemsetAsync(h->sat_buf, 0, (size_t)n * 4 * sizeof(unsigned long long), s));
-  const int rc = forward_impl(h, stream, in, workspace, workspace_bytes, out_logits, nullptr, h->sat_buf);
-  if (rc != VETO_OK) return rc;
+  ABI_TRY(forward_impl(h, stream, in, workspace, workspace_bytes, out_logits, nullptr, h->sat_buf));
   std::vector<unsigned long long> host((size_t)n * 4);
   HIP_TRY(hipMemcpyAsync(host.data(), h->sat_buf, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

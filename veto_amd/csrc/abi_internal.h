@@ -1,9 +1,11 @@
 // What the host-side translation units of the C ABI (abi_core / abi_forward / abi_train / abi_detect / abi_debug .hip) share: the
-// error string, the handle with its weight store and profiler, the GEMM launch helper and the argument builders of the launches
-// that both a forward and a test hook of it make.  Host only; no kernel source includes it.
+// error string, the argument checks that several entry points make, the workspace carver, the handle with its weight store and
+// profiler, the GEMM launch helper and the argument builders of the launches that both a forward and a test hook of it make.
+// Host only; no kernel source includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -37,7 +39,109 @@ inline int fail(int code, const char* fmt, ...) {
     if (e__ != hipSuccess) return fail(VETO_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
   } while (0)
 
+#define ABI_TRY(expr)       /* a check or step that has set the error itself */ \
+  do {                                                                             \
+    const int rc__ = (expr);                                                       \
+    if (rc__ != VETO_OK) return rc__;                                              \
+  } while (0)
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// A workspace layout is ONE function that walks a Carver over its regions, each starting at a multiple of 256 bytes, and returns
+// Carver::off behind the last: on the caller's buffer it hands out the pointers, on base == nullptr the same walk only sizes, so
+// the size an entry point asks for and the bytes it uses cannot disagree.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  size_t take_offset(size_t bytes) {
+    const size_t at = off;
+    off += align_up(bytes, 256);
+    return at;
+  }
+  template <class T = char>
+  T* take(size_t bytes) {
+    const size_t at = take_offset(bytes);
+    return base ? (T*)(base + at) : nullptr;
+  }
+};
+
+// ---- the checks several entry points make: each returns VETO_OK or the code of the error it has set ------------------------------
+// The head of an entry point that takes an argument struct: "null argument" (also_given: the other pointers that message covers),
+// then "<type> size mismatch"
+template <class T>
+inline int check_struct(const T* a, const char* type_name, bool also_given) {
+  if (!a || !also_given) return fail(VETO_ERR_INVALID, "null argument");
+  if (a->struct_size != (int32_t)sizeof(T)) return fail(VETO_ERR_INVALID, "%s size mismatch", type_name);
+  return VETO_OK;
+}
+#define CHECK_STRUCT_AND(type, a, also_given) ABI_TRY(check_struct<type>(a, #type, also_given))
+#define CHECK_STRUCT(type, a) CHECK_STRUCT_AND(type, a, true)
+
+// (a null workspace is VETO_ERR_INVALID where the entry point's "null argument" has covered it before, VETO_ERR_WORKSPACE here)
+inline int check_workspace(const void* workspace, size_t bytes, size_t need, bool must_be_aligned) {
+  if (!workspace || bytes < need) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, bytes);
+  if (must_be_aligned && ((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  return VETO_OK;
+}
+
+// veto_rpn_args_t / veto_rpn_loss_args_t: the image and level counts, and the shape of pyramid level l
+template <class T>
+inline int check_rpn_counts(const T* a) {
+  if (a->n_img <= 0 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535", a->n_img);
+  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  return VETO_OK;
+}
+template <class T>
+inline int check_rpn_level(const T* a, int l) {
+  if (a->level_a[l] <= 0 || a->level_h[l] <= 0 || a->level_w[l] <= 0)
+    return fail(VETO_ERR_INVALID, "level %d: bad shape (A %d, H %d, W %d)", l, a->level_a[l], a->level_h[l], a->level_w[l]);
+  return VETO_OK;
+}
+
+// A sampler's rows per image (config_key: where the reference's configuration keeps it) and the positives among them
+inline int check_batch_size(int batch, int cap, const char* config_key) {
+  if (batch < 1 || batch > cap) return fail(VETO_ERR_INVALID, "batch_size_per_image %d outside 1..%d (%s)", batch, cap, config_key);
+  return VETO_OK;
+}
+inline int check_positives(const char* field, int n_pos, int batch) {
+  if (n_pos < 0 || n_pos > batch)
+    return fail(VETO_ERR_INVALID, "%s %d outside 0..%d (BATCH_SIZE_PER_IMAGE * POSITIVE_FRACTION)", field, n_pos, batch);
+  return VETO_OK;
+}
+
+// The box coder's weights: a decoder divides by them (positive), an encoder only multiplies (finite)
+inline int check_reg_weights(const float* w, bool positive, const char* suffix) {
+  for (int k = 0; k < 4; ++k)
+    if (positive ? !(w[k] > 0.f) : !std::isfinite(w[k]))
+      return fail(VETO_ERR_INVALID, "reg_weights[%d] = %g%s%s", k, w[k], positive ? " must be > 0" : "", suffix);
+  return VETO_OK;
+}
+
+// The columns of MEET / vote group k (MeetGroup::cols, VoteGroup::cols): the background, then every class c of the group
+// (incre_idx_list[c] == k + 1); the group's head must be exactly that wide
+inline int fill_group_cols(int* cols, int width, int k, const int32_t* incre_idx_list, int n_rel_cls) {
+  if (width < 3 || width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, width);
+  int n = 0;
+  cols[n++] = 0;
+  for (int c = 0; c < n_rel_cls; ++c)
+    if (incre_idx_list[c] == k + 1) {
+      if (n >= width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
+      cols[n++] = c;
+    }
+  if (n != width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, width);
+  return VETO_OK;
+}
+
+// What the argument structs of the three relation post-processors have in common (the caller adds n_img and its own inputs)
+template <class T>
+inline PostArgs post_args(const T* a) {
+  PostArgs p{};
+  p.obj_logits = a->obj_logits; p.rel_pairs = a->rel_pairs;
+  p.n_obj = a->n_obj; p.n_pair = a->n_pair; p.n_rel_cls = a->n_rel_cls; p.n_obj_cls = a->n_obj_cls;
+  p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
+  p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
+  return p;
+}
 
 struct Param {
   std::string name;
@@ -88,7 +192,8 @@ struct veto_handle_s {
   int chunk = 0;
   std::vector<Param> params;
   std::map<std::string, int> index;
-  float* raw = nullptr;      // fp32 copies of every state-dict tensor
+  float* raw = nullptr;      // fp32 copies of every state-dict tensor, each at a multiple of 64 floats (Param::offset)
+  size_t raw_floats = 0;     // ... and their end: the floats of the arena, and of a gradient buffer laid out like it
   char* derived = nullptr;   // split planes, transposes, folded tables
   bool dirty = true;         // a weight was uploaded since the derived operands were built
   bool infer_dirty = false;  // ... the training-side operands are current, the inference-only ones (mixed rows, layer-0 tables, folded last layer) are not

@@ -74,76 +74,71 @@ bool train_ln_emits_split() {
 
 TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair) {
   TrainWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* ptr = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return ptr;
-  };
+  Carver c{base};
   const int L = h->cfg.layers, E = h->cfg.embed_dim;
   const size_t M = (size_t)n_pair * kTokens;
   const size_t mpad = (size_t)gemm_rows_padded((int)M);
   const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
-  w.subj = (int32_t*)take((size_t)n_pair * 4);
-  w.obj = (int32_t*)take((size_t)n_pair * 4);
-  w.lc = (float*)take((size_t)n_obj * 2 * 2 * kDim * 4);
-  w.pa = (__bf16*)take(prow * 2 * 2048 * 2);
-  w.patch_tab = (float*)take((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.subj = c.take<int32_t>((size_t)n_pair * 4);
+  w.obj = c.take<int32_t>((size_t)n_pair * 4);
+  w.lc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
+  w.pa = c.take<__bf16>(prow * 2 * 2048 * 2);
+  w.patch_tab = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
   w.layers.resize(L);
   const size_t cpad = (size_t)gemm_rows_padded(n_pair);
   const bool recompute = train_recompute();
-  __bf16* a_scr = recompute ? (__bf16*)take(mpad * 2 * kDim * 2) : nullptr;      // LayerNorm rows of whichever Linear is next (forward) / being differentiated (backward)
-  __bf16* hid_scr = recompute ? (__bf16*)take(mpad * 4 * kDim * 2) : nullptr;    // the same for the GELU rows
+  __bf16* a_scr = recompute ? c.take<__bf16>(mpad * 2 * kDim * 2) : nullptr;      // LayerNorm rows of whichever Linear is next (forward) / being differentiated (backward)
+  __bf16* hid_scr = recompute ? c.take<__bf16>(mpad * 4 * kDim * 2) : nullptr;    // the same for the GELU rows
   for (int l = 0; l < L; ++l) {
     TrainLayer& t = w.layers[l];
     // (the last layer runs on the pairs' CLS rows behind its attention: those buffers are compact, one row per pair -- sized for every token
     // row until round 6, 4.4 GB too many at cfg-2)
     const size_t rows = l == L - 1 ? cpad : mpad;
-    t.xin = (float*)take(mpad * kDim * 4);
-    t.a1 = recompute ? a_scr : (__bf16*)take(mpad * 2 * kDim * 2);
-    t.qkv = (float*)take(mpad * 3 * kDim * (train_qkv_f24(h) ? 3 : 4));
-    t.ao = (__bf16*)take(rows * 2 * kDim * 2);
-    t.xmid = (float*)take(rows * kDim * 4);
-    t.a2 = recompute ? a_scr : (__bf16*)take(rows * 2 * kDim * 2);
-    t.pre = (float*)take(rows * 2 * kDim * 4);
-    t.hid = recompute ? hid_scr : (__bf16*)take(rows * 4 * kDim * 2);
+    t.xin = c.take<float>(mpad * kDim * 4);
+    t.a1 = recompute ? a_scr : c.take<__bf16>(mpad * 2 * kDim * 2);
+    t.qkv = c.take<float>(mpad * 3 * kDim * (train_qkv_f24(h) ? 3 : 4));
+    t.ao = c.take<__bf16>(rows * 2 * kDim * 2);
+    t.xmid = c.take<float>(rows * kDim * 4);
+    t.a2 = recompute ? a_scr : c.take<__bf16>(rows * 2 * kDim * 2);
+    t.pre = c.take<float>(rows * 2 * kDim * 4);
+    t.hid = recompute ? hid_scr : c.take<__bf16>(rows * 4 * kDim * 2);
   }
-  w.xout = (float*)take(cpad * kDim * 4);      // (compact: the last layer's CLS rows)
-  w.dx = (float*)take(mpad * kDim * 4);
-  w.dmid = (float*)take(mpad * kDim * 4);
-  w.dtmp = (float*)take(mpad * kDim * 4);
+  w.xout = c.take<float>(cpad * kDim * 4);      // (compact: the last layer's CLS rows)
+  w.dx = c.take<float>(mpad * kDim * 4);
+  w.dmid = c.take<float>(mpad * kDim * 4);
+  w.dtmp = c.take<float>(mpad * kDim * 4);
   // (fc2's input gradient as fp32 rows [M, 1152]: only the VETO_TRAIN_GELU_EPI=0 form writes it; sized [M, 1728] until round 6, 2 GB at cfg-2)
-  w.dbig = (float*)take(train_gelu_epilogue() ? 256 : mpad * 2 * kDim * 4);
+  w.dbig = c.take<float>(train_gelu_epilogue() ? 256 : mpad * 2 * kDim * 4);
   {   // the token-row gradients (6 * 576 bf16 per row) and, for the input gradient of the patch projection, the split rows of
       // dpatch (prow rows x 2 * 1152 bf16) share this buffer: size it for the larger (n_obj * 16 can exceed 19 * n_pair / 1.5)
     const size_t tok = mpad * 6 * kDim * 2, obj = prow * 4 * kDim * 2;
-    w.dsplit = (__bf16*)take(tok > obj ? tok : obj);
+    w.dsplit = c.take<__bf16>(tok > obj ? tok : obj);
     w.dsplit_b = (__bf16*)((char*)w.dsplit + mpad * 2 * kDim * 2);
   }
   w.mp2 = (M + 32 * 64 + 31) / 32 * 32;   // room for any split count up to 64
-  w.zero = (__bf16*)take(1024);           // what the weight-gradient GEMM reads for reduction rows past the last one
-  w.wdg = (__bf16*)take((size_t)3 * kDim * kDim * 4);
-  w.ln_partial = (float*)take(layernorm_backward_partial_floats((int)M) * 4);
-  w.col_partial = (float*)take((size_t)column_sums_chunks() * 3 * kDim * 4);
-  w.colp = (float*)take((w.mp2 / 32) * 3 * kDim * 4);
-  w.dgb = (float*)take(2 * kDim * 4);
-  w.head_partial = (float*)take(head_backward_partial_floats(h->cfg.num_out) * 4);
-  w.dpatch = (float*)take((size_t)n_obj * 16 * 2 * kDim * 4);
-  w.dlc = (float*)take((size_t)n_obj * 2 * 2 * kDim * 4);
-  w.dpos = (float*)take((size_t)n_obj * kPosDim * 4);
-  w.dpre = (float*)take((size_t)n_obj * kPosDim * 4);
-  w.xhat = (float*)take((size_t)n_obj * 4 * 4);
-  w.bn_out = (float*)take((size_t)n_obj * 4 * 4);
-  w.dbn_out = (float*)take((size_t)n_obj * 4 * 4);
-  w.emb = (float*)take((size_t)n_obj * E * 4);
-  w.demb = (float*)take((size_t)n_obj * E * 4);
-  w.prob = (float*)take((size_t)n_obj * 256 * 4);
-  w.dloc_wt = (float*)take((size_t)kPosDim * 2 * kDim * 4);
-  w.dcls_wt = (float*)take((size_t)E * 2 * kDim * 4);
-  w.dwcat_t = (float*)take((size_t)2048 * 2 * kDim * 4);
-  w.wcat_t = (__bf16*)take((size_t)kPatchTRows * 2 * 2 * kDim * 2);
-  w.dpa = (float*)take((size_t)gemm_rows_padded(n_obj * 16) * kPatchTRows * 4);
-  w.total = off;
+  w.zero = c.take<__bf16>(1024);           // what the weight-gradient GEMM reads for reduction rows past the last one
+  w.wdg = c.take<__bf16>((size_t)3 * kDim * kDim * 4);
+  w.ln_partial = c.take<float>(layernorm_backward_partial_floats((int)M) * 4);
+  w.col_partial = c.take<float>((size_t)column_sums_chunks() * 3 * kDim * 4);
+  w.colp = c.take<float>((w.mp2 / 32) * 3 * kDim * 4);
+  w.dgb = c.take<float>(2 * kDim * 4);
+  w.head_partial = c.take<float>(head_backward_partial_floats(h->cfg.num_out) * 4);
+  w.dpatch = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.dlc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
+  w.dpos = c.take<float>((size_t)n_obj * kPosDim * 4);
+  w.dpre = c.take<float>((size_t)n_obj * kPosDim * 4);
+  w.xhat = c.take<float>((size_t)n_obj * 4 * 4);
+  w.bn_out = c.take<float>((size_t)n_obj * 4 * 4);
+  w.dbn_out = c.take<float>((size_t)n_obj * 4 * 4);
+  w.emb = c.take<float>((size_t)n_obj * E * 4);
+  w.demb = c.take<float>((size_t)n_obj * E * 4);
+  w.prob = c.take<float>((size_t)n_obj * 256 * 4);
+  w.dloc_wt = c.take<float>((size_t)kPosDim * 2 * kDim * 4);
+  w.dcls_wt = c.take<float>((size_t)E * 2 * kDim * 4);
+  w.dwcat_t = c.take<float>((size_t)2048 * 2 * kDim * 4);
+  w.wcat_t = c.take<__bf16>((size_t)kPatchTRows * 2 * 2 * kDim * 2);
+  w.dpa = c.take<float>((size_t)gemm_rows_padded(n_obj * 16) * kPatchTRows * 4);
+  w.total = c.off;
   return w;
 }
 
@@ -225,15 +220,14 @@ DropSite drop_site(const veto_train_opts_t* o, int site, int row_step = 1) {
 
 int check_train_opts(const veto_train_opts_t* o) {
   if (!o) return VETO_OK;
-  if (o->struct_size != (int32_t)sizeof(veto_train_opts_t)) return fail(VETO_ERR_INVALID, "veto_train_opts_t size mismatch");
+  CHECK_STRUCT(veto_train_opts_t, o);
   for (float p : {o->p_pos, o->p_emb, o->p_attn})
     if (!(p >= 0.f && p < 1.f)) return fail(VETO_ERR_INVALID, "dropout probabilities must be in [0, 1)");
   return VETO_OK;
 }
 
 int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, void* workspace, size_t workspace_bytes) {
-  if (!h || !in || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (in->struct_size != (int32_t)sizeof(veto_inputs_t)) return fail(VETO_ERR_INVALID, "veto_inputs_t size mismatch");
+  CHECK_STRUCT_AND(veto_inputs_t, in, h && workspace);
   if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch");
   if (!in->roi_rgb || !in->roi_depth || !in->boxes || !in->rel_pairs || !in->img_obj_offset || !in->img_pair_offset)
     return fail(VETO_ERR_INVALID, "missing input pointer");
@@ -255,13 +249,12 @@ size_t veto_train_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair
 
 int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
                        size_t workspace_bytes, float* out_logits) {
-  int rc = check_train_inputs(h, in, workspace, workspace_bytes);
-  if (rc) return rc;
-  if ((rc = check_train_opts(opts))) return rc;
+  ABI_TRY(check_train_inputs(h, in, workspace, workspace_bytes));
+  ABI_TRY(check_train_opts(opts));
   if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (h->dirty) { rc = finalize_weights(h, s, true); if (rc) return rc; }
+  if (h->dirty) ABI_TRY(finalize_weights(h, s, true));
   h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
   const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out;
   const int M = n_pair * kTokens;
@@ -276,9 +269,8 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
     HIP_TRY(launch_obj_prep(a, s));
   }
   HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
-  rc = run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16,
-                2 * kDim, 2048, EPI_F32);
-  if (rc) return rc;
+  ABI_TRY(run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16,
+                   2 * kDim, 2048, EPI_F32));
   {
     AssembleArgs a = assemble_args(h, ws.patch_tab, ws.lc, ws.subj, ws.obj, ws.layers[0].xin, ws.layers[0].a1, n_pair);
     const DropSite d = drop_site(opts, 2);
@@ -294,45 +286,36 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
       // Last layer: only x[:, 0] reaches the loss (model_veto.py:23), so -- as at inference -- keys / values cover the 19
       // tokens, everything behind the attention runs on the CLS row of each pair.  The saved activations of this layer
       // (ao, xmid, a2, pre, hid, ws.xout) are COMPACT: row p = pair p.  The backward mirrors this.
-      rc = run_gemm(h, s, "gemm_kv_last", t.a1, w.qkv, nullptr, nullptr, 0, q24 ? (float*)((char*)t.qkv + 3 * kDim) : t.qkv + kDim, nullptr,
-                    3 * kDim, M, 2 * kDim, kDim, qepi, 0, kDim);
-      if (rc) return rc;
-      rc = run_gemm(h, s, "gemm_q_cls", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, (long)kTokens * 3 * kDim, n_pair, kDim, kDim,
-                    qepi, (long)kTokens * 2 * kDim, 0);
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_kv_last", t.a1, w.qkv, nullptr, nullptr, 0, q24 ? (float*)((char*)t.qkv + 3 * kDim) : t.qkv + kDim, nullptr,
+                       3 * kDim, M, 2 * kDim, kDim, qepi, 0, kDim));
+      ABI_TRY(run_gemm(h, s, "gemm_q_cls", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, (long)kTokens * 3 * kDim, n_pair, kDim, kDim,
+                       qepi, (long)kTokens * 2 * kDim, 0));
       {
         AttnArgs a{};
         a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 1; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
         HIP_TRY(launch_attention(a, s));
       }
-      rc = run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
-                    EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens));
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
+                       EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens)));
       HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
-      rc = run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU);
-      if (rc) return rc;
-      rc = run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID);
-      if (rc) return rc;
+      ABI_TRY(run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU));
+      ABI_TRY(run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID));
       break;
     }
     float* xnext = ws.layers[l + 1].xin;
-    rc = run_gemm(h, s, "gemm_qkv", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, 3 * kDim, M, 3 * kDim, kDim, qepi);
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_qkv", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, 3 * kDim, M, 3 * kDim, kDim, qepi));
     {
       AttnArgs a{};
       a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 0; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
       HIP_TRY(launch_attention(a, s));
     }
-    rc = run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0,
-                  drop_site(opts, 3 + l));
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0,
+                     drop_site(opts, 3 + l)));
     HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, M, s));
     // (the epilogue writes the fp32 pre-activation -- gelu' needs it -- AND its exact-erf GELU as fc2's split rows: round 6; before, a pass
     // of its own read the pre-activation back, 0.55 ms per layer)
-    rc = run_gemm(h, s, "gemm_fc1", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, M, 2 * kDim, kDim, EPI_PRE_GELU);
-    if (rc) return rc;
-    rc = run_gemm(h, s, "gemm_fc2", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, xnext, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID);
-    if (rc) return rc;
+    ABI_TRY(run_gemm(h, s, "gemm_fc1", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, M, 2 * kDim, kDim, EPI_PRE_GELU));
+    ABI_TRY(run_gemm(h, s, "gemm_fc2", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, xnext, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID));
     HIP_TRY(launch_layernorm(xnext, kDim, h->layers[l + 1].ln1_w, h->layers[l + 1].ln1_b, ws.layers[l + 1].a1, M, s));
   }
   HIP_TRY(launch_head(ws.xout, h->head_wt, h->p("rel_out.bias"), out_logits, n_pair, n_out, s, (long)kDim));
@@ -342,9 +325,8 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
 
 int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
                   size_t workspace_bytes, const float* dlogits, float* grads) {
-  int rc = check_train_inputs(h, in, workspace, workspace_bytes);
-  if (rc) return rc;
-  if ((rc = check_train_opts(opts))) return rc;
+  ABI_TRY(check_train_inputs(h, in, workspace, workspace_bytes));
+  ABI_TRY(check_train_opts(opts));
   if (!dlogits || !grads) return fail(VETO_ERR_INVALID, "null gradient pointer");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -392,20 +374,16 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     if (recompute) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
     if (train_gelu_epilogue()) {
       int partials = 0;
-      rc = run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit, t.pre, &partials);
-      if (rc) return rc;
+      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit, t.pre, &partials));
       if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));      // LayerNorm2 rows: fc1's operand
-      rc = run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, GradXform(), ws.dsplit_b, partials);
-      if (rc) return rc;
+      ABI_TRY(run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, GradXform(), ws.dsplit_b, partials));
     } else {
-      rc = run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, ws.dbig, GradXform(), nullptr, dx_presplit);
-      if (rc) return rc;
+      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, ws.dbig, GradXform(), nullptr, dx_presplit));
       GradXform gelu;              // dpre = dh * gelu'(pre), folded into the operand preparation of the fc1 backward
       gelu.mode = XF_GELU;
       gelu.pre = t.pre;
       if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));
-      rc = run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, gelu);
-      if (rc) return rc;
+      ABI_TRY(run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, gelu));
     }
     // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
     const DropSite dsite = drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1);      // (last layer: compact CLS rows, as in the forward)
@@ -425,9 +403,8 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       drop.scale = dsite.scale;
       drop.row_step = dsite.row_step;
     }
-    rc = run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, ws.dtmp, drop, nullptr,
-                             ln_split ? layernorm_backward_col_partials(R) : 0);
-    if (rc) return rc;
+    ABI_TRY(run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, ws.dtmp, drop, nullptr,
+                                ln_split ? layernorm_backward_col_partials(R) : 0));
     HIP_TRY(launch_attention_backward(t.qkv, ws.dtmp, nullptr, ws.dsplit, n_pair, H, last ? 1 : 0, s, train_qkv_f24(h)));
     const float* dres = ws.dmid;
     if (last) {
@@ -438,8 +415,7 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       dres = ws.dx;
     }
     if (recompute) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
-    rc = run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, ws.dtmp);
-    if (rc) return rc;
+    ABI_TRY(run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, ws.dtmp));
     // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
     if (ln_split && l > 0) {      // (its result is the gradient matrix of fc2 of the layer below)
       HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, ws.dsplit, ws.colp));
@@ -544,19 +520,30 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
   return VETO_OK;
 }
 
-size_t veto_ce_loss_workspace_bytes(int32_t n) { return n > 0 ? 3 * align_up((size_t)n * 4, 256) + 256 : 0; }
+// workspace: lse | nll_w | w_row | inv_wsum
+static size_t carve_ce_loss(Carver c, size_t n, CeLossArgs* a) {
+  a->lse = c.take<float>(n * 4);
+  a->nll_w = c.take<float>(n * 4);
+  a->w_row = c.take<float>(n * 4);
+  a->inv_wsum = c.take<float>(256);
+  return c.off;
+}
+
+size_t veto_ce_loss_workspace_bytes(int32_t n) {
+  if (n <= 0) return 0;
+  CeLossArgs a{};
+  return carve_ce_loss(Carver{nullptr}, n, &a);
+}
 
 int veto_ce_loss(void* stream, const float* logits, int64_t ld, const int64_t* labels, const float* weight,
                  const int64_t* rows, int32_t n, int32_t n_cls, float* loss, float* grad, void* workspace,
                  size_t workspace_bytes) {
   if (!logits || !labels || !loss || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (n <= 0 || n_cls < 2 || ld < n_cls) return fail(VETO_ERR_INVALID, "bad sizes (n %d, n_cls %d, ld %lld)", n, n_cls, (long long)ld);
-  if (workspace_bytes < veto_ce_loss_workspace_bytes(n)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_ce_loss_workspace_bytes(n), false));
   CeLossArgs a{};
   a.logits = logits; a.ld = ld; a.labels = labels; a.weight = weight; a.rows = rows; a.n = n; a.C = n_cls;
-  char* base = (char*)workspace;
-  const size_t per = align_up((size_t)n * 4, 256);
-  a.lse = (float*)base; a.nll_w = (float*)(base + per); a.w_row = (float*)(base + 2 * per); a.inv_wsum = (float*)(base + 3 * per);
+  carve_ce_loss(Carver{(char*)workspace}, n, &a);
   a.loss = loss; a.grad = grad;
   HIP_TRY(launch_ce_loss(a, (hipStream_t)stream));
   return VETO_OK;
@@ -579,49 +566,43 @@ int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint3
 }
 
 // n % 32 == 0 (every Linear of the transformer): the row-major form, both operands as the split rows the backward holds
-// anyway, transposed on their way out of LDS (GemmArgs::tn).  Otherwise: explicit transposed split copies.
-static size_t wgrad_tn_bytes(int m, int n, int k) {
-  return align_up(((size_t)m + 1) * n * 4, 256) + align_up(((size_t)m + 1) * k * 4, 256) + 1024;
+// anyway, transposed on their way out of LDS (GemmArgs::tn), one row more than m each (partial tiles read, never use, the row behind
+// the last) and the zero row of GemmArgs::zero.  Otherwise: explicit transposed split copies, dy's padded to whole row tiles.
+struct WgradWs { __bf16 *a, *w, *zero; size_t total; };
+static WgradWs carve_wgrad(Carver c, int m, int n, int k, int k_splits) {      // (a braced list evaluates left to right)
+  if (n % 32 == 0) return WgradWs{c.take<__bf16>(((size_t)m + 1) * n * 4), c.take<__bf16>(((size_t)m + 1) * k * 4), c.take<__bf16>(1024), c.off};
+  const size_t mp = wgrad_mp(m, wgrad_splits(n, k, m, k_splits));
+  return WgradWs{c.take<__bf16>((size_t)gemm_rows_padded(n) * mp * 4), c.take<__bf16>((size_t)k * mp * 4), nullptr, c.off};
 }
 
 size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
-  if (n % 32 == 0) return wgrad_tn_bytes(m, n, k);
-  const size_t mp = wgrad_mp(m, wgrad_splits(n, k, m, k_splits));
-  return align_up((size_t)gemm_rows_padded(n) * mp * 4, 256) + align_up((size_t)k * mp * 4, 256);
+  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits).total;
 }
 
 int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
                      int32_t k_splits, void* workspace, size_t workspace_bytes) {
   if (!dy || !x || !dw || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (m <= 0 || n <= 0 || k <= 0 || k % 192 != 0) return fail(VETO_ERR_INVALID, "k must be a positive multiple of 192");
-  if (workspace_bytes < veto_debug_wgrad_workspace_bytes(m, n, k, k_splits)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_wgrad_workspace_bytes(m, n, k, k_splits), false));
+  const WgradWs ws = carve_wgrad(Carver{(char*)workspace}, m, n, k, k_splits);
   hipStream_t s = (hipStream_t)stream;
   const int ks = wgrad_splits(n, k, m, k_splits);
   const size_t mp = wgrad_mp(m, ks);
-  char* base = (char*)workspace;
   HIP_TRY(hipMemsetAsync(dw, 0, (size_t)n * k * 4, s));
   GemmArgs g{};
-  g.c = dw;
+  g.a = ws.a; g.w = ws.w; g.c = dw;
   g.M = n; g.N = k; g.K = (int)mp; g.ldc = k; g.k_splits = ks;
   if (n % 32 == 0) {
-    const size_t a_bytes = align_up(((size_t)m + 1) * n * 4, 256), w_bytes = align_up(((size_t)m + 1) * k * 4, 256);
-    __bf16* a_s = (__bf16*)base;
-    __bf16* w_s = (__bf16*)(base + a_bytes);
-    HIP_TRY(hipMemsetAsync(base, 0, a_bytes + w_bytes + 1024, s));   // the row behind the last one is read (never used) by partial tiles
-    HIP_TRY(launch_split_rows(dy, a_s, (size_t)m, n, s));
-    HIP_TRY(launch_split_rows(x, w_s, (size_t)m, k, s));
-    g.a = a_s; g.w = w_s;
+    HIP_TRY(hipMemsetAsync(ws.a, 0, ws.total, s));   // the row behind the last one is read (never used) by partial tiles
+    HIP_TRY(launch_split_rows(dy, ws.a, (size_t)m, n, s));
+    HIP_TRY(launch_split_rows(x, ws.w, (size_t)m, k, s));
     g.tn = 1; g.lda = 2 * (long)n; g.ldw = 2 * (long)k; g.k_valid = m;
-    g.zero = (const __bf16*)(base + a_bytes + w_bytes);
+    g.zero = ws.zero;
   } else {
-    const size_t a_bytes = align_up((size_t)gemm_rows_padded(n) * mp * 4, 256);
-    __bf16* a_s = (__bf16*)base;
-    __bf16* w_s = (__bf16*)(base + a_bytes);
-    HIP_TRY(hipMemsetAsync(base, 0, a_bytes, s));   // rows n..padded stay zero
-    HIP_TRY(launch_transpose_split(dy, n, m, n, a_s, (int)mp, s));
-    HIP_TRY(launch_transpose_split(x, k, m, k, w_s, (int)mp, s));
-    g.a = a_s; g.w = w_s;
+    HIP_TRY(hipMemsetAsync(ws.a, 0, (char*)ws.w - (char*)ws.a, s));   // rows n..padded stay zero
+    HIP_TRY(launch_transpose_split(dy, n, m, n, ws.a, (int)mp, s));
+    HIP_TRY(launch_transpose_split(x, k, m, k, ws.w, (int)mp, s));
   }
   hipError_t e = launch_gemm_split(g, EPI_ATOMIC, 0, s);
   if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "wgrad gemm launch failed: %s", hipGetErrorString(e));
@@ -713,15 +694,18 @@ static int optim_check_shapes(const veto_optim_args_t* a, long long* n_chunks) {
 
 // The tables as the device reads them: [counter, 256 bytes][OptimTensor x n_tensors][OptimChunk x n_chunks], each part at a multiple
 // of 256 bytes; this prefix of the workspace is what the call uploads.  Behind it: partial [n_chunks] and tensor_sq [n_tensors] doubles.
+// (offsets, not pointers: the pinned staging copy of the prefix has the same layout)
 struct OptimLayout { size_t tensors, chunks, upload, partial, tensor_sq, total; };
 static OptimLayout optim_layout(int n_tensors, long long n_chunks) {
   OptimLayout l;
-  l.tensors = 256;
-  l.chunks = l.tensors + align_up((size_t)n_tensors * sizeof(OptimTensor), 256);
-  l.upload = l.chunks + (size_t)n_chunks * sizeof(OptimChunk);
-  l.partial = align_up(l.upload, 256);
-  l.tensor_sq = l.partial + align_up((size_t)n_chunks * 8, 256);
-  l.total = l.tensor_sq + align_up((size_t)n_tensors * 8, 256);
+  Carver c{nullptr};
+  c.take_offset(256);      // the counter
+  l.tensors = c.take_offset((size_t)n_tensors * sizeof(OptimTensor));
+  l.chunks = c.take_offset((size_t)n_chunks * sizeof(OptimChunk));
+  l.upload = l.chunks + (size_t)n_chunks * sizeof(OptimChunk);      // (the upload ends with the table's last row, not with its region)
+  l.partial = c.take_offset((size_t)n_chunks * 8);
+  l.tensor_sq = c.take_offset((size_t)n_tensors * 8);
+  l.total = c.off;
   return l;
 }
 
@@ -773,11 +757,9 @@ static int optim_stage_acquire(size_t need, int device, OptimStage** out) {
 }
 
 int veto_optim_step(void* stream, const veto_optim_args_t* a, void* workspace, size_t workspace_bytes) {
-  if (!a) return fail(VETO_ERR_INVALID, "null argument");
-  if (a->struct_size != (int32_t)sizeof(veto_optim_args_t)) return fail(VETO_ERR_INVALID, "veto_optim_args_t size mismatch");
+  CHECK_STRUCT(veto_optim_args_t, a);
   long long n_chunks = 0;
-  const int rc = optim_check_shapes(a, &n_chunks);
-  if (rc != VETO_OK) return rc;
+  ABI_TRY(optim_check_shapes(a, &n_chunks));
   const bool norms = a->mode != VETO_OPTIM_STEP, steps = a->mode == VETO_OPTIM_STEP || a->mode == VETO_OPTIM_CLIP_STEP;
   const bool clips = a->mode == VETO_OPTIM_CLIP || a->mode == VETO_OPTIM_CLIP_STEP;
   if (clips && !(a->max_norm > 0.0)) return fail(VETO_ERR_INVALID, "max_norm %g must be > 0 in a mode that clips", a->max_norm);
@@ -798,15 +780,13 @@ int veto_optim_step(void* stream, const veto_optim_args_t* a, void* workspace, s
     if (!(t.beta2 >= 0.0 && t.beta2 < 1.0)) return fail(VETO_ERR_INVALID, "tensor %d: beta2 %g outside [0, 1)", i, t.beta2);
   }
   const OptimLayout lay = optim_layout(a->n_tensors, n_chunks);
-  if (!workspace || workspace_bytes < lay.total) return fail(VETO_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", lay.total, workspace_bytes);
-  if (((uintptr_t)workspace & 255) != 0) return fail(VETO_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, lay.total, true));
 
   int device = 0;
   HIP_TRY(hipGetDevice(&device));
   std::lock_guard<std::mutex> lock(g_optim_mutex);
   OptimStage* st = nullptr;
-  const int rs = optim_stage_acquire(lay.upload, device, &st);
-  if (rs != VETO_OK) return rs;
+  ABI_TRY(optim_stage_acquire(lay.upload, device, &st));
   char* host = (char*)st->host;
   memset(host, 0, 256);   // the counter
   OptimTensor* rows = (OptimTensor*)(host + lay.tensors);
