@@ -852,6 +852,115 @@ size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_
 int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* args, int32_t n_pair_total, int32_t n_gt_total,
                   void* workspace, size_t workspace_bytes);
 
+/* ---- detection (box mAP) evaluator ------------------------------------------------------------------
+ * The "bbox" branch of do_vg_evaluation (pysgg/data/datasets/evaluation/vg/vg_eval.py:67-182): COCOeval.evaluate()
+ * and accumulate() as that code drives them -- iouType 'bbox', no crowd boxes, the ten IoU thresholds
+ * np.linspace(.5, .95, 10), the 101 recall thresholds np.linspace(0, 1, 101), maxDets [1, 10, 100], the area ranges
+ * [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10], categories 1 .. n_cls-1 -- and summarize()'s twelve numbers.
+ * A split is fed batch by batch: veto_det_eval_match appends one record per detection to three caller-owned device
+ * buffers and adds the batch's non-ignored GT counts into a caller-owned table; veto_det_eval_accumulate, once per
+ * split, sorts the records and forms precision / recall / stats.  Neither call copies anything to the host, and each
+ * makes a number of launches that does not depend on the number of images, classes or records.
+ *
+ * Arithmetic is the reference's, in double: a detection's w, h are x2 - x1 + 1 rounded in float32 (BoxList.convert('xywh'))
+ * and then widened, a GT box's are formed in double from its float32 coordinates (vg_eval.py:72-76); areas are w * h;
+ * IoU is maskUtils.bbIou's (iw = min(dx+dw, gx+gw) - max(dx, gx), likewise ih, 0 if either is <= 0, else
+ * i = iw*ih, u = dw*dh + gw*gh - i, i / u).  The thresholds and the area ranges are given as doubles so that they are numpy's bits.
+ *
+ * Per image the detections of each class are ordered by score descending, ties by index ascending (np.argsort(-score,
+ * kind='mergesort')) and cut at 100.  For each (threshold, area range) COCOeval's greedy matching runs in that order over the
+ * class's GT boxes, non-ignored ones (area inside the range) first, then ignored ones, each group in the given order: a GT box
+ * already taken is skipped, the ignored group is not visited once a non-ignored match is held, a candidate needs
+ * iou >= min(threshold, 1 - 1e-10) and then >= the best so far (of two equal IoUs the later GT box wins).  A detection
+ * inherits its GT box's ignore flag; an unmatched detection whose area is outside the range is ignored.
+ *
+ * first_gt_id: vg_eval.py:78 numbers the annotations of the split from 0, and COCOeval tests the stored id for truth, so a
+ * detection matched to annotation 0 occupies that GT box but counts as unmatched (a false positive, or ignored when its own
+ * area is outside the range).  Pass the annotation id of THIS batch's first GT box: 0 for the first batch of a split
+ * reproduces the reference, 1 gives the COCO-correct count; later batches add the GT boxes seen so far.
+ *
+ * Limits, refused before any launch: n_cls 2..1024; veto_det_eval_limits() GT boxes and detections per image (1024 and 1024);
+ * row_offset + n_det below 2^31.  Preconditions: scores are finite; boxes are finite.  A label outside 1..n_cls-1 cannot be
+ * seen from the host: such a box is left out of every count and *label_errors is incremented (a caller holding the labels
+ * on the host refuses them there, as veto_amd.DetectionEvaluator does).  n_det = 0 with n_gt > 0 is allowed (the GT boxes are
+ * counted, no record is written, the record pointers may be NULL).
+ * Time: one workgroup matches an image, a thread per (class, threshold, area), so the boxes of one class are walked serially:
+ * 0.2 ms per batch of 12 images x 80 detections; at the per-image limits with every box in ONE class (100 kept detections
+ * against 1024 GT boxes) about 34 ms per batch, whatever the number of images (MI355X, profiles/det_eval_bench.txt).
+ *
+ * Record r = row_offset + det_offset[image] + (position in the image's (class, score desc, index) order):
+ *   rec_key    class << 32 | ~order(score)   (order: larger score -> larger key, -0.0 and +0.0 share one);
+ *              class 0 = not counted (beyond the 100 per (image, class), or a label out of range)
+ *   rec_match  bit (threshold * 4 + area) = matched, bits 40..46 = rank within the (image, class) list
+ *   rec_ignore bit (threshold * 4 + area) = ignored */
+typedef struct veto_det_eval_match_args {
+  int32_t struct_size;
+  int32_t n_img;
+  int32_t n_cls;                   /* object classes with the background (151) */
+  int32_t n_gt;                    /* GT boxes of the batch */
+  int32_t n_det;                   /* detections of the batch */
+  int32_t reserved0;
+  int64_t first_gt_id;             /* see above */
+  int64_t row_offset;              /* records appended by the earlier batches of the split */
+  double iou_thrs[10];             /* np.linspace(.5, .95, 10) */
+  double area_rngs[8];             /* lo, hi of the four ranges */
+  const int32_t* gt_offset;        /* device [n_img + 1] */
+  const int32_t* det_offset;       /* device [n_img + 1] */
+  const int32_t* gt_offset_host;   /* host copies of the two: the per-image limits are checked on them */
+  const int32_t* det_offset_host;
+  const float* gt_boxes;           /* device [n_gt, 4] xyxy */
+  const int64_t* gt_labels;        /* device [n_gt] */
+  const float* det_boxes;          /* device [n_det, 4] xyxy */
+  const float* det_scores;         /* device [n_det], finite */
+  const int64_t* det_labels;       /* device [n_det] */
+  uint64_t* rec_key;               /* in/out device, at least row_offset + n_det rows each */
+  uint64_t* rec_match;
+  uint64_t* rec_ignore;
+  int64_t* gt_counts;              /* in/out device [n_cls - 1, 4]: non-ignored GT boxes per (class, area range), added to
+                                      (zeroed by the caller before the first batch) */
+  int32_t* label_errors;           /* in/out device [1], optional: added to */
+} veto_det_eval_match_args_t;
+
+size_t veto_det_eval_match_workspace_bytes(int32_t n_img, int32_t n_gt, int32_t n_det);
+int veto_det_eval_match(void* stream, const veto_det_eval_match_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* Once per split.  A device-wide stable LSD radix sort of the records by (class ascending, score descending) -- stability keeps
+ * the append order among ties, i.e. image order and then the in-image order, which is what COCOeval's mergesort over its
+ * concatenated per-image lists keeps -- then per (class k, area a, maxDets m) one pass over the class's records of rank < m with
+ * running counts TP (matched, not ignored) and FP (not matched, not ignored) for the ten thresholds:
+ *   rc = tp / npig,  pr = tp / (fp + tp + np.spacing(1)),
+ *   recall[t,k,a,m] = the last rc (0 without records),
+ *   precision[t,r,k,a,m] = max pr[i] over the i with rc[i] >= rec_thrs[r] (0 if none): COCOeval's backward envelope read at
+ *   np.searchsorted(rc, rec_thrs, side='left').
+ * Cells of a (class, area) without a non-ignored GT box stay -1.  stats[0..11] are summarize()'s: AP, AP50, AP75, APs, APm, APl,
+ * AR@1, AR@10, AR@100, ARs, ARm, ARl, each the mean over the entries > -1 or -1 without any, summed in double in a fixed order;
+ * recall50_100 is vg_eval.py:177's recall@100 at IoU 0.5.  n_rec = 0 is allowed.
+ * Time: measured up to 400 000 records.  Each of the six radix passes scans its 256 * ceil(n_rec / 2048) histogram entries with a
+ * single workgroup, so beyond a few million records the time of this call is unmeasured and dominated by that scan (about 2.7e8
+ * entries a pass at the limit of 2^31). */
+typedef struct veto_det_eval_accumulate_args {
+  int32_t struct_size;
+  int32_t n_cls;
+  int64_t n_rec;                   /* records appended over the split, below 2^31 */
+  double iou_thrs[10];
+  double rec_thrs[101];            /* np.linspace(0, 1, 101) */
+  const uint64_t* rec_key;         /* device [n_rec] each (not written) */
+  const uint64_t* rec_match;
+  const uint64_t* rec_ignore;
+  const int64_t* gt_counts;        /* device [n_cls - 1, 4] */
+  double* precision;               /* out device [10, 101, n_cls - 1, 4, 3] */
+  double* recall;                  /* out device [10, n_cls - 1, 4, 3] */
+  double* stats;                   /* out device [12] */
+  double* recall50_100;            /* out device [1] */
+} veto_det_eval_accumulate_args_t;
+
+size_t veto_det_eval_accumulate_workspace_bytes(int64_t n_rec, int32_t n_cls);
+int veto_det_eval_accumulate(void* stream, const veto_det_eval_accumulate_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* The sizes the evaluator is built with: GT boxes and detections per image, the records per step of the accumulate pass over a
+ * class segment, the records per workgroup of the radix sort (any of the pointers may be NULL). */
+int veto_det_eval_limits(int32_t* max_gt_per_image, int32_t* max_det_per_image, int32_t* scan_chunk, int32_t* sort_tile);
+
 /* ---- measurement hooks (bench.py): per-kernel device time from hipEvents on `stream` ---------- */
 int veto_profile_enable(veto_handle_t h, int32_t on);
 /* Synchronises the recorded events; returns the number of distinct kernels. */

@@ -1,6 +1,6 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
 // box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, the box head's loss, ROI pooling and
-// the evaluator.
+// the relation and detection evaluators.
 // Each checks its argument struct (the checks several of them make are in abi_internal.h), fills the launch struct and makes one
 // launch call (kernels.h).  An entry point with a workspace has ONE carve_*() that walks the layout and sets the launch struct's
 // workspace pointers: veto_X_workspace_bytes runs it on a null base, veto_X on the caller's buffer.
@@ -714,6 +714,97 @@ int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_to
   p.ng_rows = a->ng_rows; p.ng_cols = a->ng_cols; p.ng_count = a->ng_count; p.metrics = a->metrics;
   carve_sgg_eval(Carver{(char*)workspace}, a->n_img, n_pair_total, n_gt_total, a->n_rel_cls, &p);
   HIP_TRY(launch_sgg_eval(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_det_eval_limits(int32_t* max_gt_per_image, int32_t* max_det_per_image, int32_t* scan_chunk, int32_t* sort_tile) {
+  if (max_gt_per_image) *max_gt_per_image = det_eval_max_gt();
+  if (max_det_per_image) *max_det_per_image = det_eval_max_det();
+  if (scan_chunk) *scan_chunk = det_eval_scan_chunk();
+  if (sort_tile) *sort_tile = det_eval_sort_tile();
+  return VETO_OK;
+}
+
+// workspace: the "GT taken" flags
+static size_t carve_det_eval_match(Carver c, size_t n_gt, DetEvalMatchArgs* p) {
+  p->gtm = c.take<uint8_t>(n_gt * kDetEvalThrs * kDetEvalAreas + 1);
+  return c.off;
+}
+
+size_t veto_det_eval_match_workspace_bytes(int32_t n_img, int32_t n_gt, int32_t n_det) {
+  if (n_img <= 0 || n_gt < 0 || n_det < 0) return 0;
+  DetEvalMatchArgs p{};
+  return carve_det_eval_match(Carver{nullptr}, n_gt, &p);
+}
+
+int veto_det_eval_match(void* stream, const veto_det_eval_match_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT(veto_det_eval_match_args_t, a);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->n_img <= 0 || a->n_gt < 0 || a->n_det < 0)
+    return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_gt %d, n_det %d)", a->n_img, a->n_gt, a->n_det);
+  if (a->row_offset < 0 || a->row_offset + (int64_t)a->n_det >= ((int64_t)1 << 31))
+    return fail(VETO_ERR_INVALID, "row_offset %lld + n_det %d: the record total must stay below 2^31", (long long)a->row_offset, a->n_det);
+  if (!a->gt_offset_host || !a->det_offset_host) return fail(VETO_ERR_INVALID, "missing pointer: host offsets");
+  if (check_host_offsets(a->gt_offset_host, a->n_img, a->n_gt, det_eval_max_gt(), "gt_offset_host", "n_gt") < 0) return VETO_ERR_INVALID;
+  if (check_host_offsets(a->det_offset_host, a->n_img, a->n_det, det_eval_max_det(), "det_offset_host", "n_det") < 0) return VETO_ERR_INVALID;
+  for (int t = 0; t < kDetEvalThrs; ++t)
+    if (!(a->iou_thrs[t] > 0.0 && a->iou_thrs[t] <= 1.0)) return fail(VETO_ERR_INVALID, "iou_thrs[%d] = %g outside (0, 1]", t, a->iou_thrs[t]);
+  for (int r = 0; r < kDetEvalAreas; ++r)
+    if (!(a->area_rngs[2 * r] <= a->area_rngs[2 * r + 1])) return fail(VETO_ERR_INVALID, "area_rngs[%d]: lo above hi (or NaN)", r);
+  if ((a->n_gt > 0 && (!a->gt_boxes || !a->gt_labels)) || (a->n_det > 0 && (!a->det_boxes || !a->det_scores || !a->det_labels || !a->rec_key ||
+      !a->rec_match || !a->rec_ignore)) || !a->gt_offset || !a->det_offset || !a->gt_counts)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_det_eval_match_workspace_bytes(a->n_img, a->n_gt, a->n_det), true));
+  DetEvalMatchArgs p{};
+  p.n_img = a->n_img; p.n_cls = a->n_cls; p.first_gt_id = a->first_gt_id; p.row_offset = a->row_offset;
+  for (int t = 0; t < kDetEvalThrs; ++t) p.iou_thrs[t] = a->iou_thrs[t];
+  for (int r = 0; r < 2 * kDetEvalAreas; ++r) p.area_rngs[r] = a->area_rngs[r];
+  p.gt_off = a->gt_offset; p.det_off = a->det_offset;
+  p.gt_boxes = a->gt_boxes; p.gt_labels = a->gt_labels;
+  p.det_boxes = a->det_boxes; p.det_scores = a->det_scores; p.det_labels = a->det_labels;
+  p.rec_key = (unsigned long long*)a->rec_key; p.rec_match = (unsigned long long*)a->rec_match; p.rec_ignore = (unsigned long long*)a->rec_ignore;
+  p.npig = (unsigned long long*)a->gt_counts; p.label_errors = a->label_errors;
+  carve_det_eval_match(Carver{(char*)workspace}, a->n_gt, &p);
+  HIP_TRY(launch_det_eval_match(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// workspace: key_a | key_b | idx_a | idx_b | hist | seg_start
+static size_t carve_det_eval_accumulate(Carver c, size_t n_rec, int n_cls, DetEvalAccumArgs* p) {
+  p->key_a = c.take<unsigned long long>(n_rec * 8 + 8);
+  p->key_b = c.take<unsigned long long>(n_rec * 8 + 8);
+  p->idx_a = c.take<uint32_t>(n_rec * 4 + 4);
+  p->idx_b = c.take<uint32_t>(n_rec * 4 + 4);
+  p->hist = c.take<uint32_t>((size_t)det_eval_sort_tiles((long long)n_rec) * 256 * 4);
+  p->seg_start = c.take<int32_t>(((size_t)n_cls + 1) * 4);
+  return c.off;
+}
+
+size_t veto_det_eval_accumulate_workspace_bytes(int64_t n_rec, int32_t n_cls) {
+  if (n_rec < 0 || n_rec >= ((int64_t)1 << 31) || n_cls < 2 || n_cls > 1024) return 0;
+  DetEvalAccumArgs p{};
+  return carve_det_eval_accumulate(Carver{nullptr}, (size_t)n_rec, n_cls, &p);
+}
+
+int veto_det_eval_accumulate(void* stream, const veto_det_eval_accumulate_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT(veto_det_eval_accumulate_args_t, a);
+  if (a->n_cls < 2 || a->n_cls > 1024) return fail(VETO_ERR_INVALID, "n_cls %d outside 2..1024", a->n_cls);
+  if (a->n_rec < 0 || a->n_rec >= ((int64_t)1 << 31)) return fail(VETO_ERR_INVALID, "n_rec %lld outside 0..2^31-1", (long long)a->n_rec);
+  for (int r = 1; r < kDetEvalRecThrs; ++r)
+    if (!(a->rec_thrs[r - 1] <= a->rec_thrs[r])) return fail(VETO_ERR_INVALID, "rec_thrs must be non-decreasing (entry %d)", r);
+  if ((a->n_rec > 0 && (!a->rec_key || !a->rec_match || !a->rec_ignore)) || !a->gt_counts || !a->precision || !a->recall || !a->stats ||
+      !a->recall50_100)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_det_eval_accumulate_workspace_bytes(a->n_rec, a->n_cls), true));
+  DetEvalAccumArgs p{};
+  p.n_cls = a->n_cls; p.n_rec = a->n_rec;
+  for (int t = 0; t < kDetEvalThrs; ++t) p.iou_thrs[t] = a->iou_thrs[t];
+  for (int r = 0; r < kDetEvalRecThrs; ++r) p.rec_thrs[r] = a->rec_thrs[r];
+  p.rec_key = (const unsigned long long*)a->rec_key; p.rec_match = (const unsigned long long*)a->rec_match;
+  p.rec_ignore = (const unsigned long long*)a->rec_ignore; p.npig = (const unsigned long long*)a->gt_counts;
+  p.precision = a->precision; p.recall = a->recall; p.stats = a->stats; p.recall50_100 = a->recall50_100;
+  carve_det_eval_accumulate(Carver{(char*)workspace}, (size_t)a->n_rec, a->n_cls, &p);
+  HIP_TRY(launch_det_eval_accumulate(p, (hipStream_t)stream));
   return VETO_OK;
 }
 

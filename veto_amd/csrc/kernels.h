@@ -618,6 +618,55 @@ struct SggEvalArgs {
 };
 hipError_t launch_sgg_eval(const SggEvalArgs& a, hipStream_t s);
 
+// ---- detection (box mAP) evaluator (det_eval.hip) -------------------------------------------------------
+constexpr int kDetEvalThrs = 10;       // IoU thresholds
+constexpr int kDetEvalAreas = 4;       // area ranges
+constexpr int kDetEvalRecThrs = 101;   // recall thresholds
+struct DetEvalMatchArgs {
+  int n_img, n_cls;
+  long long first_gt_id;         // annotation id of this batch's first GT box
+  long long row_offset;          // record row of this batch's first detection
+  double iou_thrs[kDetEvalThrs];
+  double area_rngs[2 * kDetEvalAreas];   // lo, hi per range
+  const int32_t* gt_off;         // [n_img + 1] prefix sum of GT boxes
+  const int32_t* det_off;        // [n_img + 1] prefix sum of detections
+  const float* gt_boxes;         // [sum G, 4] xyxy
+  const int64_t* gt_labels;      // [sum G]
+  const float* det_boxes;        // [sum D, 4] xyxy
+  const float* det_scores;       // [sum D]
+  const int64_t* det_labels;     // [sum D]
+  unsigned long long* rec_key;   // out [row_offset + sum D ..): class << 32 | inverted score key (class 0: not counted)
+  unsigned long long* rec_match; // out: 40 matched bits (threshold * 4 + area) | rank << 40
+  unsigned long long* rec_ignore;// out: 40 ignored bits
+  unsigned long long* npig;      // in/out [n_cls - 1, 4]: non-ignored GT boxes, added to
+  int32_t* label_errors;         // in/out [1] or nullptr: labels outside 1..n_cls-1 met (they are not counted), added to
+  uint8_t* gtm;                  // workspace [sum G, 40]: "GT taken" per (threshold, area)
+};
+hipError_t launch_det_eval_match(const DetEvalMatchArgs& a, hipStream_t s);
+
+struct DetEvalAccumArgs {
+  int n_cls;
+  long long n_rec;
+  double iou_thrs[kDetEvalThrs];
+  double rec_thrs[kDetEvalRecThrs];
+  const unsigned long long *rec_key, *rec_match, *rec_ignore;   // [n_rec]
+  const unsigned long long* npig;                               // [n_cls - 1, 4]
+  double* precision;             // out [10, 101, n_cls - 1, 4, 3]
+  double* recall;                // out [10, n_cls - 1, 4, 3]
+  double* stats;                 // out [12]
+  double* recall50_100;          // out [1]
+  unsigned long long *key_a, *key_b;   // workspace [n_rec] each
+  uint32_t *idx_a, *idx_b;             // workspace [n_rec] each
+  uint32_t* hist;                      // workspace [256, tiles]
+  int32_t* seg_start;                  // workspace [n_cls + 1]: first sorted record of class c (entry n_cls: n_rec)
+};
+hipError_t launch_det_eval_accumulate(const DetEvalAccumArgs& a, hipStream_t s);
+int det_eval_max_gt();           // GT boxes per image
+int det_eval_max_det();          // detections per image
+int det_eval_scan_chunk();       // records per step of the accumulate pass over a class segment
+int det_eval_sort_tile();        // records per workgroup of the radix sort
+inline long long det_eval_sort_tiles(long long n_rec) { return n_rec > 0 ? (n_rec + det_eval_sort_tile() - 1) / det_eval_sort_tile() : 1; }
+
 // ---- training losses / MEET sampling (losses.hip) ----------------------------------------------------------
 struct CeLossArgs {
   const float* logits;           // row r at logits + r*ld

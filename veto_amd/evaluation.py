@@ -12,7 +12,10 @@ batch, and only the final numbers (and, for inspection, the per-relation match r
 `SGGEvaluator.evaluate(images)` takes per-image dicts with the reference's local_container names
 (gt_rels, gt_classes, gt_boxes, pred_rel_inds, rel_scores, pred_classes, pred_boxes, obj_scores);
 `evaluate_boxlists(groundtruths, predictions)` takes the BoxLists the reference's loop is fed with.
-The result dict follows the reference's result_dict ('<mode>_recall' -> {20, 50, 100}, ...)."""
+The result dict follows the reference's result_dict ('<mode>_recall' -> {20, 50, 100}, ...).
+
+`DetectionEvaluator` is the "bbox" branch of the same routine (vg_eval.py:67-182): box mAP by pycocotools' COCOeval rules, fed
+batch by batch like SGGEvaluator.update / finalize; `do_box_evaluation` is its drop-in form."""
 import ctypes
 
 import numpy as np
@@ -206,3 +209,155 @@ class SGGEvaluator:
                 "SGG eval: " + fmt(" mR", res["mean_recall"]) + " for mode=%s, type=Mean Recall.\n" % m +
                 "SGG eval: " + fmt("ng-mR", res["ng_mean_recall"]) + " for mode=%s, type=No Graph Constraint Mean Recall.\n" % m +
                 "SGG eval: " + fmt("  A", res["accuracy"]) + " for mode=%s, type=TopK Accuracy.\n" % m)
+
+
+# ---- detection (box mAP) evaluation: the "bbox" branch of do_vg_evaluation (vg_eval.py:67-182) ------------------------------------
+# COCOeval's Params for iouType 'bbox', formed as pycocotools forms them so that the device gets numpy's bits
+DET_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+DET_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+DET_MAX_DETS = (1, 10, 100)
+DET_AREA_RNGS = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))
+DET_STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl")      # COCOResults('bbox'): stats[0..5]
+
+
+class DetectionEvaluator:
+    """COCOeval.evaluate() / accumulate() / summarize() over a split, on the device (veto_det_eval_match per batch,
+    veto_det_eval_accumulate once).  update() appends one record per detection to device buffers that grow geometrically and reads
+    nothing back; finalize() returns precision [10, 101, C-1, 4, 3], recall [10, C-1, 4, 3], stats [12], 'mAp' (= stats[1], AP at
+    IoU 0.5: what the reference calls mAp), 'recall@100_iou0.5' and COCOResults('bbox')'s six names.
+
+    first_gt_id: the annotation id of the split's first GT box.  vg_eval.py:78 numbers from 0 and COCOeval tests the id for truth,
+    so with 0 (the default: the reference's numbers) a detection matched to the very first GT box of the split counts as unmatched;
+    1 is the COCO-correct count.
+
+    Limits (include/veto_amd.h): 2..1024 classes, 1024 GT boxes and 1024 detections per image, fewer than 2^31 detections per
+    split.  Labels must lie in 1..C-1: labels given on the host are checked in update(); labels that already live on the device
+    are checked there and reported by finalize().  Scores must be finite."""
+
+    def __init__(self, num_classes, device="cuda", first_gt_id=0):
+        self.num_classes, self.first_gt_id = int(num_classes), int(first_gt_id)
+        if not 2 <= self.num_classes <= 1024:
+            raise ValueError("veto_amd.DetectionEvaluator: num_classes %d outside 2..1024" % self.num_classes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("veto_amd.DetectionEvaluator runs only on a HIP device (got %s)" % self.device)
+        self.reset()
+
+    def reset(self):
+        """Forgets everything accumulated by update()."""
+        self._rows = self._gts = 0
+        self._rec = None                      # [3, capacity] int64: the key / match / ignore words of every record
+        self._gt_counts = torch.zeros((self.num_classes - 1, 4), dtype=torch.int64, device=self.device)
+        self._label_errors = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _reserve(self, rows):
+        cap = 0 if self._rec is None else self._rec.shape[1]
+        if rows <= cap:
+            return
+        grown = torch.empty((3, max(rows, 2 * cap, 4096)), dtype=torch.int64, device=self.device)
+        if self._rows:
+            grown[:, :self._rows] = self._rec[:, :self._rows]
+        self._rec = grown
+
+    def _labels(self, x, what):
+        if not (isinstance(x, torch.Tensor) and x.device.type == "cuda"):      # on the host: refuse here
+            lab = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x).reshape(-1)
+            if lab.size and (lab.min() < 1 or lab.max() >= self.num_classes):
+                raise ValueError("veto_amd.DetectionEvaluator: %s outside 1..%d" % (what, self.num_classes - 1))
+        return _t(x, torch.int64, self.device).reshape(-1)
+
+    def update(self, images):
+        """Matches one batch (dicts with gt_boxes, gt_classes, pred_boxes, pred_classes, obj_scores) and appends its records."""
+        if not len(images):
+            return
+        dev = self.device
+        call = native.Launch(dev, "veto_amd.DetectionEvaluator runs only on a HIP device")
+        f32 = torch.float32
+        gt_labels = [self._labels(im["gt_classes"], "gt_classes") for im in images]
+        det_labels = [self._labels(im["pred_classes"], "pred_classes") for im in images]
+        gt_boxes = [_t(im["gt_boxes"], f32, dev).reshape(-1, 4) for im in images]
+        det_boxes = [_t(im["pred_boxes"], f32, dev).reshape(-1, 4) for im in images]
+        det_scores = [_t(im["obj_scores"], f32, dev).reshape(-1) for im in images]
+        n_g, n_d = [int(x.shape[0]) for x in gt_labels], [int(x.shape[0]) for x in det_labels]
+        if [int(x.shape[0]) for x in gt_boxes] != n_g or [int(x.shape[0]) for x in det_boxes] != n_d or \
+                [int(x.shape[0]) for x in det_scores] != n_d:
+            raise ValueError("veto_amd.DetectionEvaluator: one box per label and one score per detection")
+        n_img, sum_g, sum_d = len(images), sum(n_g), sum(n_d)
+        self._reserve(max(self._rows + sum_d, 1))      # a batch without a detection still counts its GT boxes
+        off = native.device_offsets(n_g, n_d, device=dev)
+        host_g = (ctypes.c_int32 * (n_img + 1))(0, *np.cumsum(n_g).tolist())
+        host_d = (ctypes.c_int32 * (n_img + 1))(0, *np.cumsum(n_d).tolist())
+        a = call.args(native.VetoDetEvalMatchArgs, n_img=n_img, n_cls=self.num_classes, n_gt=sum_g, n_det=sum_d,
+                      first_gt_id=self.first_gt_id + self._gts, row_offset=self._rows,
+                      iou_thrs=(ctypes.c_double * 10)(*DET_IOU_THRS.tolist()),
+                      area_rngs=(ctypes.c_double * 8)(*[float(v) for r in DET_AREA_RNGS for v in r]),
+                      gt_offset=off[0], det_offset=off[1],
+                      gt_offset_host=ctypes.cast(host_g, ctypes.c_void_p), det_offset_host=ctypes.cast(host_d, ctypes.c_void_p),
+                      gt_boxes=torch.cat(gt_boxes).contiguous(), gt_labels=torch.cat(gt_labels).contiguous(),
+                      det_boxes=torch.cat(det_boxes).contiguous(), det_scores=torch.cat(det_scores).contiguous(),
+                      det_labels=torch.cat(det_labels).contiguous(),
+                      rec_key=self._rec[0], rec_match=self._rec[1], rec_ignore=self._rec[2],
+                      gt_counts=self._gt_counts, label_errors=self._label_errors)
+        ws = call.workspace(call.lib.veto_det_eval_match_workspace_bytes(n_img, sum_g, sum_d))
+        call.run("veto_det_eval_match", ctypes.byref(a), ws.data_ptr(), ws.numel())
+        self._rows += sum_d
+        self._gts += sum_g
+
+    def update_boxlists(self, groundtruths, predictions, mode="sgdet"):
+        """vg_eval.py:70-108: the fields of the GT / prediction BoxLists; predcls: the labels are the GT 'labels', the scores 1."""
+        images = []
+        for gt, pr in zip(groundtruths, predictions):
+            boxes = pr.convert("xyxy").bbox
+            if mode == "predcls":
+                labels = pr.get_field("labels")
+                scores = torch.ones(int(labels.shape[0]), dtype=torch.float32, device=labels.device)
+            else:
+                labels, scores = pr.get_field("pred_labels"), pr.get_field("pred_scores")
+            images.append({"gt_boxes": gt.convert("xyxy").bbox, "gt_classes": gt.get_field("labels"), "pred_boxes": boxes,
+                           "pred_classes": labels, "obj_scores": scores})
+        self.update(images)
+
+    def finalize(self):
+        """Sorts and folds every record appended since reset(); the one place that reads anything back.
+
+        Raises ValueError when a label outside 1..C-1 was met on the device.  The kernel has left those boxes out, so the tables
+        of this split are not returned and the error stays set: every later finalize() raises again until reset()."""
+        dev, K = self.device, self.num_classes - 1
+        call = native.Launch(dev, "veto_amd.DetectionEvaluator runs only on a HIP device")
+        self._reserve(1)
+        f64 = torch.float64
+        precision = torch.empty((10, 101, K, 4, 3), dtype=f64, device=dev)
+        recall = torch.empty((10, K, 4, 3), dtype=f64, device=dev)
+        tail = torch.empty(13, dtype=f64, device=dev)       # stats [12] | recall50_100
+        a = call.args(native.VetoDetEvalAccumulateArgs, n_cls=self.num_classes, n_rec=self._rows,
+                      iou_thrs=(ctypes.c_double * 10)(*DET_IOU_THRS.tolist()), rec_thrs=(ctypes.c_double * 101)(*DET_REC_THRS.tolist()),
+                      rec_key=self._rec[0], rec_match=self._rec[1], rec_ignore=self._rec[2], gt_counts=self._gt_counts,
+                      precision=precision, recall=recall, stats=tail, recall50_100=tail[12:])
+        ws = call.workspace(call.lib.veto_det_eval_accumulate_workspace_bytes(self._rows, self.num_classes))
+        call.run("veto_det_eval_accumulate", ctypes.byref(a), ws.data_ptr(), ws.numel())
+        bad = int(self._label_errors.item())
+        if bad:
+            raise ValueError("veto_amd.DetectionEvaluator: %d labels outside 1..%d were met on the device" % (bad, K))
+        t = tail.cpu().numpy()
+        res = {"precision": precision.cpu().numpy(), "recall": recall.cpu().numpy(), "stats": t[:12].copy(),
+               "mAp": float(t[1]), "recall@100_iou0.5": float(t[12])}
+        res.update({name: float(t[i]) for i, name in enumerate(DET_STAT_NAMES)})
+        return res
+
+    def evaluate(self, images):
+        self.reset()
+        self.update(images)
+        return self.finalize()
+
+    def evaluate_boxlists(self, groundtruths, predictions, mode="sgdet"):
+        self.reset()
+        self.update_boxlists(groundtruths, predictions, mode)
+        return self.finalize()
+
+
+def do_box_evaluation(groundtruths, predictions, mode, num_classes, device="cuda", first_gt_id=0):
+    """The "bbox" branch of do_vg_evaluation: (mAp, result_str, coco_res_to_save) with the two lines of vg_eval.py:176-178."""
+    res = DetectionEvaluator(num_classes, device=device, first_gt_id=first_gt_id).evaluate_boxlists(groundtruths, predictions, mode)
+    result_str = "Detection evaluation mAp=%.4f\n" % res["mAp"]
+    result_str += "recall@%d IOU:0.5 %.4f\n" % (DET_MAX_DETS[-1], res["recall@100_iou0.5"])
+    return res["mAp"], result_str, {"bbox/%s" % name: res[name] for name in DET_STAT_NAMES}

@@ -200,6 +200,21 @@ class VetoSggEvalArgs(Structure):
                                         "metrics", "pred_obj_offset")]
 
 
+class VetoDetEvalMatchArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_cls", "n_gt", "n_det", "reserved0")] + \
+               [("first_gt_id", c_int64), ("row_offset", c_int64), ("iou_thrs", c_double * 10), ("area_rngs", c_double * 8)] + \
+               [(n, c_void_p) for n in ("gt_offset", "det_offset", "gt_offset_host", "det_offset_host", "gt_boxes", "gt_labels",
+                                        "det_boxes", "det_scores", "det_labels", "rec_key", "rec_match", "rec_ignore",
+                                        "gt_counts", "label_errors")]
+
+
+class VetoDetEvalAccumulateArgs(Structure):
+    _fields_ = [("struct_size", c_int32), ("n_cls", c_int32), ("n_rec", c_int64), ("iou_thrs", c_double * 10),
+                ("rec_thrs", c_double * 101)] + \
+               [(n, c_void_p) for n in ("rec_key", "rec_match", "rec_ignore", "gt_counts", "precision", "recall", "stats",
+                                        "recall50_100")]
+
+
 class VetoTrainOpts(Structure):
     _fields_ = [("struct_size", c_int32), ("p_pos", ctypes.c_float), ("p_emb", ctypes.c_float), ("p_attn", ctypes.c_float),
                 ("seed", ctypes.c_uint64), ("d_roi_rgb", c_void_p), ("d_roi_depth", c_void_p)]
@@ -215,6 +230,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_rpn_loss_args_t": VetoRpnLossArgs, "veto_box_loss_args_t": VetoBoxLossArgs,
     "veto_optim_tensor_t": VetoOptimTensor, "veto_optim_args_t": VetoOptimArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
+    "veto_det_eval_match_args_t": VetoDetEvalMatchArgs, "veto_det_eval_accumulate_args_t": VetoDetEvalAccumulateArgs,
 }
 
 _P, _I, _Z = c_void_p, c_int32, c_size_t
@@ -297,6 +313,11 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_sgg_eval": _sig(_P, POINTER(VetoSggEvalArgs), _I, _I, _P, _Z),
     "veto_sgg_eval_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+    "veto_det_eval_match": _sig(_P, POINTER(VetoDetEvalMatchArgs), _P, _Z),
+    "veto_det_eval_match_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
+    "veto_det_eval_accumulate": _sig(_P, POINTER(VetoDetEvalAccumulateArgs), _P, _Z),
+    "veto_det_eval_accumulate_workspace_bytes": _sig(c_int64, _I, ret=_Z),
+    "veto_det_eval_limits": _sig(POINTER(_I), POINTER(_I), POINTER(_I), POINTER(_I)),
 }
 EXPORTS = list(SIGNATURES)   # what include/veto_amd.h declares
 
