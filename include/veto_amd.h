@@ -852,6 +852,55 @@ size_t veto_sgg_eval_workspace_bytes(int32_t n_img, int32_t n_pair_total, int32_
 int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* args, int32_t n_pair_total, int32_t n_gt_total,
                   void* workspace, size_t workspace_bytes);
 
+/* The same accumulation over a whole split, from per-relation records that stay on the device.  veto_sgg_eval, called batch by
+ * batch with gc_rank / ng_rank / acc_rank / zeroshot_flag pointing into caller-owned arrays at the batch's first row, leaves the
+ * records; the caller adds each GT relation's predicate (column 2 of gt_rels) and keeps, per image, its GT-relation and pair
+ * counts.  veto_sgg_eval_fold, once per split, restates sgg_eval.py:133-136, :209, :331-336, :420-466 over them; neither call
+ * copies anything to the host, and the fold makes two launches whatever the number of images.
+ *
+ * Image i owns rows img_gt_offset[i] .. img_gt_offset[i+1]-1 (G of them) and is evaluated iff G > 0 and img_pair_count[i] > 0
+ * (vg_eval.py:474, :548).  Ranks are compared as rank < K, K = 20 / 50 / 100; 0x3fffffff = no match.  Per evaluated image:
+ *   R@K = #(gc_rank < K) / G,  ngR@K = #(ng_rank < K) / G,  zR@K = #(gc_rank < K and zeroshot) / #zeroshot if that is > 0,
+ *   A@K hits = #(acc_rank < K), count = G,
+ *   per predicate c in 1..n_rel_cls-1 with count_c > 0 relations in the image: #(rank < K among them) / count_c.
+ * A GT predicate outside 1..n_rel_cls-1 counts for R, ngR, zR and A and for no class.  Over the split: R, ngR = the mean of the
+ * quotients over the evaluated images, zR over those with a zero-shot relation (NaN without any), A@K = mean(hits) /
+ * mean(counts) (NaN for mode 1), the per-class lists = the mean over the images that HAVE the class (0.0 for a class no image
+ * has), mR / ng-mR = their sum in class order / (n_rel_cls - 1).
+ *
+ * Summation order, in double: workgroup b adds the images [b * images_per_chunk, (b+1) * images_per_chunk) in image order from
+ * 0.0; the per-chunk sums are added in chunk order from 0.0.  No floating-point atomics: the same records give the same bits
+ * whatever batches, buffer capacities or ranks produced them.  The per-image predicate counts live in LDS.
+ *
+ * Limits, refused before any launch: n_rel_cls 2..max_rel_cls (1024); n_img >= 0 and n_gt_total >= 0, so fewer than 2^31 images
+ * and GT relations per split (n_img = 0 gives NaN recalls, mean recalls of 0.0 and counts of 0); the workspace, 256-byte aligned.
+ * An image whose offsets leave 0..n_gt_total is treated as not evaluated. */
+typedef struct veto_sgg_eval_fold_args {
+  int32_t struct_size;
+  int32_t n_img;
+  int32_t n_rel_cls;
+  int32_t mode;                    /* 0 = GT boxes (predcls / sgcls), 1 = sgdet: the A@K slots are NaN */
+  int32_t n_gt_total;              /* rows of the five record arrays = img_gt_offset[n_img] */
+  int32_t reserved0;
+  const int32_t* img_gt_offset;    /* device [n_img + 1] */
+  const int32_t* img_pair_count;   /* device [n_img] predicted pairs P of each image (NULL allowed when n_img = 0) */
+  const int32_t* gt_predicate;     /* device [n_gt_total] each (NULL allowed when n_gt_total = 0) */
+  const int32_t* gc_rank;
+  const int32_t* ng_rank;
+  const int32_t* acc_rank;
+  const int32_t* zeroshot_flag;
+  double* metrics;                 /* out device [18 + 6 * (n_rel_cls - 1) + 2], the layout of veto_sgg_eval_args_t.metrics */
+  double* per_image;               /* out device [n_img, 12], optional: R@20/50/100, ngR, zR (NaN without a zero-shot relation),
+                                      A hits / G (NaN for mode 1) of each image; all NaN for an image that is not evaluated */
+} veto_sgg_eval_fold_args_t;
+
+size_t veto_sgg_eval_fold_workspace_bytes(int32_t n_img, int32_t n_rel_cls);
+int veto_sgg_eval_fold(void* stream, const veto_sgg_eval_fold_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* The sizes the fold is built with: images per workgroup (the unit of the summation order) and the largest n_rel_cls (either
+ * pointer may be NULL). */
+int veto_sgg_eval_fold_limits(int32_t* images_per_chunk, int32_t* max_rel_cls);
+
 /* ---- detection (box mAP) evaluator ------------------------------------------------------------------
  * The "bbox" branch of do_vg_evaluation (pysgg/data/datasets/evaluation/vg/vg_eval.py:67-182): COCOeval.evaluate()
  * and accumulate() as that code drives them -- iouType 'bbox', no crowd boxes, the ten IoU thresholds

@@ -1,7 +1,10 @@
 """Device-resident test-time pipeline of the relation head on synthetic data, end to end:
 FPN / depth maps -> ROI pooling (veto_roi_pool) -> pair enumeration -> VETOPredictor (veto_forward) ->
 PostProcessor (veto_postprocess) -> relation evaluators (veto_sgg_eval).  Prints per-stage device time and the
-end-to-end images/s at the BASELINE cfg-2 batch shape (12 images x 36 objects).  usage: tools/eval_pipeline.py [steps]"""
+end-to-end images/s at the BASELINE cfg-2 batch shape (12 images x 36 objects).
+usage: tools/eval_pipeline.py [steps] [--accumulate]
+--accumulate: the eval loop keeps the per-relation records on the device (SGGEvaluator.accumulate_boxlists: no read-back per
+batch) and the split-level numbers come out of ONE finalize() at the end (veto_sgg_eval_fold, one device-to-host copy)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,7 +14,9 @@ from veto_amd.evaluation import SGGEvaluator
 from veto_amd.relation_head import VETORelationHead
 from veto_amd.structures import BoxList
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+accumulate = "--accumulate" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--accumulate"]
+steps = int(argv[0]) if argv else 10
 dev = torch.device("cuda:0")
 n_img, n_obj, W, H = 12, 36, 1024, 608
 cfg = testing.make_config(4, 8)
@@ -19,6 +24,7 @@ head = VETORelationHead(cfg)
 head.predictor = testing.make_predictor(cfg, synth.predictor_state_dict(0, layers=4), dev)
 head.eval()
 batch = synth.synthetic_batch(7, n_img, n_obj)
+torch.manual_seed(0)      # the same maps in every run: the metrics of an --accumulate run and of a plain one can be laid side by side
 feats = [torch.randn(n_img, 256, H >> (2 + l), W >> (2 + l), device=dev) for l in range(4)]
 depth = torch.randn(n_img, 256, H >> 4, W >> 4, device=dev)
 eval_imgs, zeroshot = synth.synthetic_eval_images(5, [n_obj] * n_img, "predcls")
@@ -77,12 +83,18 @@ for i in range(steps + 1):
     if pending is not None:
         with torch.cuda.stream(side):
             side.wait_event(pending[1])
-            evaluator.update_boxlists(gts, pending[0])      # per-relation match ranks accumulate over the split
+            if accumulate:
+                evaluator.accumulate_boxlists(gts, pending[0])      # the records stay on the device: nothing is read back here
+            else:
+                evaluator.update_boxlists(gts, pending[0])      # per-relation match ranks accumulate over the split
     pending = cur
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print("pipelined: %.2f ms per %d-image batch -> %.0f images/s, %.0f pairs/s end to end" %
-      (dt * 1e3, n_img, n_img / dt, n_img * n_obj * (n_obj - 1) / dt))
+print("pipelined (%s): %.2f ms per %d-image batch -> %.0f images/s, %.0f pairs/s end to end" %
+      ("accumulate: device-resident records" if accumulate else "update: read-back per batch", dt * 1e3, n_img, n_img / dt,
+       n_img * n_obj * (n_obj - 1) / dt))
+t0 = time.perf_counter()
 res = evaluator.finalize()                                   # ONE fold over every image seen, as the reference's evaluators do
-print("dataset-level metrics over %d images:" % res["images_evaluated"])
+print("dataset-level metrics over %d images (finalize: %.2f ms, %s):" %
+      (res["images_evaluated"], (time.perf_counter() - t0) * 1e3, "device fold, one copy" if accumulate else "host fold"))
 print(evaluator.generate_print_string(res), end="")

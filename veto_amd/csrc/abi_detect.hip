@@ -717,6 +717,44 @@ int veto_sgg_eval(void* stream, const veto_sgg_eval_args_t* a, int32_t n_pair_to
   return VETO_OK;
 }
 
+int veto_sgg_eval_fold_limits(int32_t* images_per_chunk, int32_t* max_rel_cls) {
+  if (images_per_chunk) *images_per_chunk = sgg_eval_fold_images_per_chunk();
+  if (max_rel_cls) *max_rel_cls = sgg_eval_fold_max_rel_cls();
+  return VETO_OK;
+}
+
+// workspace: one row of partial sums per image chunk
+static size_t carve_sgg_eval_fold(Carver c, size_t n_img, int n_rel_cls, SggEvalFoldArgs* p) {
+  p->partial = c.take<double>((sgg_eval_fold_chunks(n_img) * sgg_eval_fold_partial_doubles(n_rel_cls) + 1) * 8);
+  return c.off;
+}
+
+size_t veto_sgg_eval_fold_workspace_bytes(int32_t n_img, int32_t n_rel_cls) {
+  if (n_img < 0 || n_rel_cls < 2 || n_rel_cls > sgg_eval_fold_max_rel_cls()) return 0;
+  SggEvalFoldArgs p{};
+  return carve_sgg_eval_fold(Carver{nullptr}, (size_t)n_img, n_rel_cls, &p);
+}
+
+int veto_sgg_eval_fold(void* stream, const veto_sgg_eval_fold_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT(veto_sgg_eval_fold_args_t, a);
+  if (a->n_rel_cls < 2 || a->n_rel_cls > sgg_eval_fold_max_rel_cls())
+    return fail(VETO_ERR_INVALID, "n_rel_cls %d outside 2..%d", a->n_rel_cls, sgg_eval_fold_max_rel_cls());
+  if (a->mode != 0 && a->mode != 1) return fail(VETO_ERR_INVALID, "mode must be 0 (GT boxes) or 1 (sgdet)");
+  if (a->n_img < 0 || a->n_gt_total < 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_gt_total %d)", a->n_img, a->n_gt_total);
+  if (!a->img_gt_offset || (a->n_img > 0 && !a->img_pair_count) || !a->metrics ||
+      (a->n_gt_total > 0 && (!a->gt_predicate || !a->gc_rank || !a->ng_rank || !a->acc_rank || !a->zeroshot_flag)))
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_sgg_eval_fold_workspace_bytes(a->n_img, a->n_rel_cls), true));
+  SggEvalFoldArgs p{};
+  p.n_img = a->n_img; p.n_rel_cls = a->n_rel_cls; p.mode = a->mode; p.n_gt_total = a->n_gt_total;
+  p.img_gt_off = a->img_gt_offset; p.img_pair_cnt = a->img_pair_count;
+  p.gt_predicate = a->gt_predicate; p.gc_rank = a->gc_rank; p.ng_rank = a->ng_rank; p.acc_rank = a->acc_rank;
+  p.zeroshot_flag = a->zeroshot_flag; p.metrics = a->metrics; p.per_image = a->per_image;
+  carve_sgg_eval_fold(Carver{(char*)workspace}, (size_t)a->n_img, a->n_rel_cls, &p);
+  HIP_TRY(launch_sgg_eval_fold(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 int veto_det_eval_limits(int32_t* max_gt_per_image, int32_t* max_det_per_image, int32_t* scan_chunk, int32_t* sort_tile) {
   if (max_gt_per_image) *max_gt_per_image = det_eval_max_gt();
   if (max_det_per_image) *max_det_per_image = det_eval_max_det();

@@ -618,6 +618,23 @@ struct SggEvalArgs {
 };
 hipError_t launch_sgg_eval(const SggEvalArgs& a, hipStream_t s);
 
+// The split-level fold over the per-relation records that launch_sgg_eval leaves (ranks, zero-shot flags) and the GT predicates
+struct SggEvalFoldArgs {
+  int n_img, n_rel_cls, mode;    // mode 0 = GT boxes, 1 = sgdet (A@K = NaN)
+  int n_gt_total;                // rows of the record arrays
+  const int32_t* img_gt_off;     // [n_img + 1] prefix sum of GT relations
+  const int32_t* img_pair_cnt;   // [n_img] predicted pairs: an image with G == 0 or P == 0 contributes nothing
+  const int32_t *gt_predicate, *gc_rank, *ng_rank, *acc_rank, *zeroshot_flag;   // [n_gt_total]
+  double* metrics;               // out [18 + 6 * (n_rel_cls - 1) + 2], the layout of SggEvalArgs::metrics
+  double* per_image;             // out [n_img, 12] or nullptr
+  double* partial;               // workspace [chunks, sgg_eval_fold_partial_doubles(n_rel_cls)]
+};
+hipError_t launch_sgg_eval_fold(const SggEvalFoldArgs& a, hipStream_t s);
+int sgg_eval_fold_images_per_chunk();   // images one workgroup folds, in image order
+int sgg_eval_fold_max_rel_cls();        // predicate classes with the background: the per-image table lives in LDS
+inline size_t sgg_eval_fold_chunks(size_t n_img) { return (n_img + sgg_eval_fold_images_per_chunk() - 1) / sgg_eval_fold_images_per_chunk(); }
+__host__ __device__ inline size_t sgg_eval_fold_partial_doubles(int n_rel_cls) { return 16 + 7 * (size_t)n_rel_cls; }
+
 // ---- detection (box mAP) evaluator (det_eval.hip) -------------------------------------------------------
 constexpr int kDetEvalThrs = 10;       // IoU thresholds
 constexpr int kDetEvalAreas = 4;       // area ranges

@@ -12,7 +12,8 @@
 //   ng_rank   in the top-100 of obj_s * obj_o * rel_scores[:, 1:] over all (pair, predicate) cells (:221-229)
 // One workgroup per image computes the three ranks and the zero-shot flag of every GT relation plus the image's
 // per-predicate (count, hits@K) table; a second, single-workgroup kernel folds the images into the final
-// numbers in a fixed order (double precision, bit-reproducible).
+// numbers in a fixed order (double precision, bit-reproducible).  Over a whole split the same fold runs device-wide on the
+// records that the image kernel leaves batch after batch (sgg_eval_fold_*_kernel below, behind veto_sgg_eval_fold).
 //
 // The top-100 selection works on a unique 64-bit key (score bits, then inverted flat index), i.e. on the total
 // order (score descending, flat index ascending).  Fast path: the 100-th largest ROW maximum bounds the 100-th
@@ -400,7 +401,149 @@ __global__ __launch_bounds__(256) void sgg_eval_reduce_kernel(SggEvalArgs a) {
   }
 }
 
+// ---- the split-level fold --------------------------------------------------------------------------------------------------
+// The same accumulation over the records of a whole split (the ranks and zero-shot flags sgg_eval_image_kernel left, batch after
+// batch, plus the GT predicates), parallel over the device and in ONE summation order that only the image sequence decides:
+// workgroup b folds images [b * kFoldChunk, (b + 1) * kFoldChunk) in image order, each sum starting from 0.0, into a row of
+// partials; the combine kernel adds the rows in chunk order.  Every term is a quotient of two integers in double, so batch
+// boundaries, buffer capacities and the rank split that produced the records cannot reach the bits.
+// Partial row, sgg_eval_fold_partial_doubles(C) doubles:
+//   [0..2] sum of R@K quotients, [3..5] ngR@K, [6..8] zR@K (images with a zero-shot relation), [9..11] sum of A@K hits,
+//   [12] sum of G, [13] images evaluated, [14] images with a zero-shot relation, [15] unused,
+//   [16 + j * C + c] j = 0..5: sum over the images that have predicate c of hits / count (j = kind * 3 + K index),
+//   [16 + 6 * C + c] number of images that have predicate c.
+constexpr int kFoldThreads = 1024;
+constexpr int kFoldChunk = 32;
+constexpr int kFoldMaxCls = 1024;   // thread c of a workgroup owns predicate c: its LDS column and its six running sums
+
+__global__ __launch_bounds__(kFoldThreads) void sgg_eval_fold_chunk_kernel(SggEvalFoldArgs a) {
+  __shared__ int s_tab[7 * kFoldMaxCls];   // the image in hand: [count | hits gc@20,50,100 | hits ng@20,50,100][C]
+  __shared__ int s_cnt[2][16];             // [0..2] gc hits@K, [3..5] ng, [6..8] acc, [9] zero-shot relations, [10..12] their gc hits
+  const int tid = threadIdx.x, lane = tid & 63, C = a.n_rel_cls;
+  const int img0 = blockIdx.x * kFoldChunk;
+  const int img1 = img0 + kFoldChunk < a.n_img ? img0 + kFoldChunk : a.n_img;
+  for (int i = tid; i < 7 * C; i += kFoldThreads) s_tab[i] = 0;
+  if (tid < 32) (&s_cnt[0][0])[tid] = 0;
+  double cls_sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, cls_n = 0.0;   // predicate `tid`
+  double acc = 0.0;                                                    // partial-row entry `tid` (tid < 15)
+  int parity = 0;
+  __syncthreads();
+  for (int img = img0; img < img1; ++img) {
+    const int g0 = a.img_gt_off[img], g1 = a.img_gt_off[img + 1], G = g1 - g0;
+    // vg_eval.py:474 / :548; offsets that leave the record arrays are not followed
+    if (G <= 0 || a.img_pair_cnt[img] <= 0 || g0 < 0 || g1 > a.n_gt_total) {
+      if (a.per_image && tid < 12) a.per_image[(size_t)img * 12 + tid] = __builtin_nan("");
+      continue;
+    }
+    int* cnt = s_cnt[parity];
+    for (int base = 0; base < G; base += kFoldThreads) {   // uniform trip count: the ballots below see whole waves
+      const int g = base + tid;
+      const bool on = g < G;
+      const int r = on ? a.gt_predicate[g0 + g] : 0;
+      const int gc = on ? a.gc_rank[g0 + g] : kNoMatch, ng = on ? a.ng_rank[g0 + g] : kNoMatch;
+      const int ac = on ? a.acc_rank[g0 + g] : kNoMatch;
+      const bool z = on && a.zeroshot_flag[g0 + g] != 0;
+      const bool hit[13] = {gc < 20, gc < 50, gc < 100, ng < 20, ng < 50, ng < 100, ac < 20, ac < 50, ac < 100, z,
+                            z && gc < 20, z && gc < 50, z && gc < 100};
+#pragma unroll
+      for (int q = 0; q < 13; ++q) {
+        const unsigned long long m = __ballot(hit[q]);
+        if (lane == 0 && m) atomicAdd(&cnt[q], __popcll(m));
+      }
+      if (on && r > 0 && r < C) {   // a predicate outside 1..C-1 counts above and for no class
+        atomicAdd(&s_tab[r], 1);
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+          if (hit[j]) atomicAdd(&s_tab[(1 + j) * C + r], 1);
+      }
+    }
+    __syncthreads();
+    if (tid > 0 && tid < C) {
+      const int n = s_tab[tid];
+      if (n > 0) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          cls_sum[j] += (double)s_tab[(1 + j) * C + tid] / (double)n;
+          s_tab[(1 + j) * C + tid] = 0;
+        }
+        cls_n += 1.0;
+        s_tab[tid] = 0;
+      }
+    }
+    if (tid < 16) {
+      const int zs = cnt[9];
+      double term = 0.0, shown = __builtin_nan("");
+      if (tid < 6) term = shown = (double)cnt[tid] / (double)G;
+      else if (tid < 9) { if (zs > 0) term = shown = (double)cnt[tid + 4] / (double)zs; }
+      else if (tid < 12) { term = (double)cnt[tid - 3]; if (a.mode == 0) shown = term / (double)G; }
+      else if (tid == 12) term = (double)G;
+      else if (tid == 13) term = 1.0;
+      else if (tid == 14) term = zs > 0 ? 1.0 : 0.0;
+      acc += term;
+      if (a.per_image && tid < 12) a.per_image[(size_t)img * 12 + tid] = shown;
+      s_cnt[parity ^ 1][tid] = 0;   // the other set: last read one barrier ago, next written after the barrier below
+    }
+    parity ^= 1;
+    __syncthreads();
+  }
+  double* row = a.partial + (size_t)blockIdx.x * sgg_eval_fold_partial_doubles(C);
+  if (tid < 16) row[tid] = tid < 15 ? acc : 0.0;
+  if (tid < C) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) row[16 + j * C + tid] = cls_sum[j];
+    row[16 + 6 * C + tid] = cls_n;
+  }
+}
+
+// One workgroup, one thread per output quantity, the partial rows visited in chunk order; then the means over the classes.
+__global__ __launch_bounds__(kFoldThreads) void sgg_eval_fold_combine_kernel(SggEvalFoldArgs a, int n_chunks) {
+  __shared__ double s_sc[16];
+  const int tid = threadIdx.x, C = a.n_rel_cls, Cf = C - 1;
+  const size_t stride = sgg_eval_fold_partial_doubles(C);
+  double* out = a.metrics;
+  if (tid < 16) {
+    double s = 0.0;
+    for (int ch = 0; ch < n_chunks; ++ch) s += a.partial[ch * stride + tid];
+    s_sc[tid] = s;
+  }
+  for (int e = tid; e < 6 * Cf; e += kFoldThreads) {
+    const int j = e / Cf, c = e % Cf + 1;
+    double s = 0.0, n = 0.0;
+    for (int ch = 0; ch < n_chunks; ++ch) {
+      s += a.partial[ch * stride + 16 + j * C + c];
+      n += a.partial[ch * stride + 16 + 6 * C + c];
+    }
+    out[18 + e] = n > 0.0 ? s / n : 0.0;   // a predicate no image has: 0.0 (sgg_eval.py:452-456)
+  }
+  __syncthreads();
+  const double n_eval = s_sc[13], n_zs = s_sc[14], nan = __builtin_nan("");
+  if (tid < 6) out[tid] = n_eval > 0.0 ? s_sc[tid] / n_eval : nan;
+  else if (tid < 9) out[tid] = n_zs > 0.0 ? s_sc[tid] / n_zs : nan;
+  else if (tid < 12) out[tid] = a.mode == 0 && n_eval > 0.0 ? (s_sc[tid] / n_eval) / (s_sc[12] / n_eval) : nan;   // :331-336
+  else if (tid == 12) out[18 + 6 * Cf] = n_eval;
+  else if (tid == 13) out[18 + 6 * Cf + 1] = n_zs;
+  else if (tid >= 16 && tid < 22) {   // mean recall = sum of the per-class recalls / (C - 1), classes in index order (:452-466)
+    double s = 0.0;
+    for (int n = 0; n < Cf; ++n) s += out[18 + (tid - 16) * Cf + n];
+    out[12 + (tid - 16)] = s / (double)Cf;
+  }
+}
+
 }  // namespace
+
+int sgg_eval_fold_images_per_chunk() { return kFoldChunk; }
+int sgg_eval_fold_max_rel_cls() { return kFoldMaxCls; }
+
+hipError_t launch_sgg_eval_fold(const SggEvalFoldArgs& a, hipStream_t s) {
+  const size_t n_chunks = sgg_eval_fold_chunks((size_t)a.n_img);
+  if (n_chunks > 0) {
+    VETO_LAUNCH(sgg_eval_fold_chunk_kernel, dim3((unsigned)n_chunks), dim3(kFoldThreads), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  VETO_LAUNCH(sgg_eval_fold_combine_kernel, dim3(1), dim3(kFoldThreads), 0, s, a, (int)n_chunks);
+  return hipGetLastError();
+}
 
 hipError_t launch_sgg_eval(const SggEvalArgs& a, hipStream_t s) {
   VETO_LAUNCH(sgg_eval_image_kernel, dim3(a.n_img), dim3(kThreads), 0, s, a);

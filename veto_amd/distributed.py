@@ -117,3 +117,46 @@ def all_reduce_gradients(params, group=None, average=True, bucket_bytes=256 << 2
         calls += 1
         i = j
     return calls
+
+
+EVAL_STATE_ROW_FIELDS = ("gc_rank", "ng_rank", "acc_rank", "zeroshot_flag", "gt_predicate")   # one row per GT relation
+EVAL_STATE_IMAGE_FIELDS = ("gt_count", "pair_count")                                          # one row per image
+
+
+def all_gather_eval_state(state, group=None):
+    """state: SGGEvaluator.state() of this rank's shard -> the list of every rank's state, rank-major, on every rank: what
+    SGGEvaluator.load_state() takes.  Each rank scores its own images; what travels is about 20 bytes per GT relation and 16 per
+    image, and nothing is gathered before scoring.
+
+    The (relation, image) counts of every rank are gathered first and read back (one small copy); then each field goes out as
+    ONE all_gather_into_tensor, padded to the largest rank.  With the contiguous shards of shard_images, rank-major order is
+    dataset order, so the merged finalize() returns the bits of a single-rank run.
+
+    Runs on CPU tensors under gloo (tests/test_sgg_eval_split_gloo.py).  The RCCL path (device tensors, nccl backend) is the
+    same code and, like the rest of this module, has not been measured on hardware."""
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return [state]
+    world = dist.get_world_size(group)
+    dev = state["gt_count"].device
+    mine = [int(state["gc_rank"].numel()), int(state["gt_count"].numel())]
+    counts = torch.empty(2 * world, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(counts, torch.tensor(mine, dtype=torch.int64, device=dev), group=group)
+    counts = counts.view(world, 2).tolist()
+    out = [{} for _ in range(world)]
+    for fields, col in ((EVAL_STATE_ROW_FIELDS, 0), (EVAL_STATE_IMAGE_FIELDS, 1)):
+        width = max(c[col] for c in counts)
+        for name in fields:
+            t = state[name].reshape(-1).contiguous()
+            if t.numel() != mine[col]:
+                raise ValueError("all_gather_eval_state: field %r has %d rows, expected %d" % (name, t.numel(), mine[col]))
+            if width == 0:      # every rank knows it: no collective
+                for r in range(world):
+                    out[r][name] = t.new_empty(0)
+                continue
+            padded = t.new_zeros(width)
+            padded[:t.numel()] = t
+            got = t.new_empty(world * width)
+            dist.all_gather_into_tensor(got, padded, group=group)
+            for r in range(world):
+                out[r][name] = got[r * width: r * width + counts[r][col]].clone()
+    return out

@@ -14,6 +14,12 @@ batch, and only the final numbers (and, for inspection, the per-relation match r
 `evaluate_boxlists(groundtruths, predictions)` takes the BoxLists the reference's loop is fed with.
 The result dict follows the reference's result_dict ('<mode>_recall' -> {20, 50, 100}, ...).
 
+Over a split there are two ways to feed it.  update() / update_boxlists() read each batch's ranks back and finalize() folds them on
+the host.  accumulate() / accumulate_boxlists() leave the per-relation records (three ranks, the zero-shot flag, the GT predicate)
+in device buffers and read nothing back; finalize() then folds them in one veto_sgg_eval_fold call and makes one copy.  The fold's
+summation order depends on the image sequence alone, so state() / load_state() (and distributed.all_gather_eval_state between
+them) merge the records of several ranks into the bits of a single-rank run.
+
 `DetectionEvaluator` is the "bbox" branch of the same routine (vg_eval.py:67-182): box mAP by pycocotools' COCOeval rules, fed
 batch by batch like SGGEvaluator.update / finalize; `do_box_evaluation` is its drop-in form."""
 import ctypes
@@ -25,6 +31,7 @@ from . import native
 
 KS = (20, 50, 100)
 NO_MATCH = 0x3fffffff
+RECORD_FIELDS = ("gc_rank", "ng_rank", "acc_rank", "zeroshot_flag", "gt_predicate")      # rows of SGGEvaluator's device records
 
 
 def _t(x, dtype, device):
@@ -34,7 +41,7 @@ def _t(x, dtype, device):
 
 
 class SGGEvaluator:
-    def __init__(self, mode, num_rel_category, zeroshot_triplet, iou_thres=0.5, device="cuda"):
+    def __init__(self, mode, num_rel_category, zeroshot_triplet, iou_thres=0.5, device="cuda", reserve=4096):
         if mode not in ("predcls", "sgcls", "sgdet"):
             raise NotImplementedError("veto_amd.SGGEvaluator covers predcls / sgcls / sgdet, got %r" % (mode,))
         self.mode, self.num_rel, self.iou_thres = mode, int(num_rel_category), float(iou_thres)
@@ -42,17 +49,29 @@ class SGGEvaluator:
         if self.device.type != "cuda":
             raise RuntimeError("veto_amd.SGGEvaluator runs only on a HIP device (got %s)" % self.device)
         self.zeroshot = _t(zeroshot_triplet, torch.int64, self.device).reshape(-1, 3).contiguous()
+        self._reserve_rows = max(int(reserve), 1)      # first capacity of the device-resident records (accumulate())
         self.reset()
 
     # ---- dataset-level accumulation (the reference's evaluators keep per-image lists over the WHOLE split and fold them once,
     # sgg_eval.py:133-136,209,331-336,420-466; per-batch results cannot be averaged into mR@K / A@K afterwards) --------------
     def reset(self):
-        """Forgets everything accumulated by update()."""
+        """Forgets everything accumulated by update() or accumulate()."""
         self._acc = []        # per evaluated image: (gc_rank, ng_rank, acc_rank, zeroshot flags, GT predicate of every GT relation)
+        self._fed = None      # "update" (host lists in _acc) or "accumulate" (device records): one of the two between resets
+        self._rec = None      # [5, capacity] int32 on the device: the RECORD_FIELDS of every GT relation seen by accumulate()
+        self._rows = 0
+        self._img_g, self._img_p = [], []      # per image: GT relations, predicted pairs
+        self._scratch = {}    # images per batch -> the per-batch outputs nobody reads on this path
+
+    def _feed(self, how):
+        if self._fed not in (None, how):
+            raise ValueError("veto_amd.SGGEvaluator: %s*() after %s*(); reset() first" % (how, self._fed))
+        self._fed = how
 
     def update(self, images):
         """Scores one batch on the device (same launch as evaluate()) and keeps its per-relation match ranks for finalize().
         Returns the batch's own result dict."""
+        self._feed("update")
         res = self.evaluate(images)
         for im, r in zip(images, res["per_image"]):
             if r is None:
@@ -62,6 +81,7 @@ class SGGEvaluator:
         return res
 
     def update_boxlists(self, groundtruths, predictions):
+        self._feed("update")
         res = self.evaluate_boxlists(groundtruths, predictions)
         for gt, r in zip(groundtruths, res["per_image"]):
             if r is None:
@@ -72,7 +92,10 @@ class SGGEvaluator:
 
     def finalize(self):
         """Folds every image seen by update() the way the reference does at the end of the split: np.mean of the per-image
-        recalls, A@K = mean(hits) / mean(counts), mean recall from the per-image per-class hit ratios."""
+        recalls, A@K = mean(hits) / mean(counts), mean recall from the per-image per-class hit ratios.  After accumulate() the same
+        fold runs on the device over the resident records (_finalize_records)."""
+        if getattr(self, "_fed", None) == "accumulate":
+            return self._finalize_records()
         C = self.num_rel
         res = {"images_evaluated": len(self._acc)}
         lists = {n: {k: [] for k in KS} for n in ("recall", "recall_nogc", "zeroshot_recall", "acc_hit", "acc_cnt")}
@@ -107,8 +130,118 @@ class SGGEvaluator:
             res[name] = {k: sum(res[name + "_list"][k]) / float(C - 1) for k in KS}
         return res
 
+    # ---- the same over device-resident records: no read-back per batch, one fold and one copy at the end of the split ------------
+    def _reserve(self, rows):
+        cap = 0 if self._rec is None else self._rec.shape[1]
+        if rows <= cap:
+            return
+        # zeros: the flag rows of an image that is not evaluated are never written, and state() hands them out
+        grown = torch.zeros((len(RECORD_FIELDS), max(rows, 2 * cap, self._reserve_rows)), dtype=torch.int32, device=self.device)
+        if self._rows:
+            grown[:, :self._rows] = self._rec[:, :self._rows]
+        self._rec = grown
+
+    def accumulate(self, images):
+        """Scores one batch like update(), with the per-relation ranks and flags written straight into the evaluator's device
+        buffers, and the GT predicates copied beside them on the device.  No device-to-host copy, no stream synchronisation;
+        returns None.  finalize() folds the records of the whole split."""
+        self._feed("accumulate")
+        if not len(images):
+            return None
+        f, n_g, n_p = self._pack(images, record=True)
+        n_img, sum_g, sum_p, r0 = len(images), sum(n_g), sum(n_p), self._rows
+        if r0 + sum_g >= 1 << 31 or len(self._img_g) + n_img >= 1 << 31:
+            raise ValueError("veto_amd.SGGEvaluator: a split holds fewer than 2^31 GT relations and images")
+        self._reserve(r0 + sum_g + 1)      # + 1: a batch without a GT relation still hands the launch a valid pointer
+        sc = self._scratch.get(n_img)
+        if sc is None:
+            i32 = torch.int32
+            sc = self._scratch[n_img] = (torch.zeros((n_img, 100), dtype=i32, device=self.device),
+                                         torch.zeros((n_img, 100), dtype=i32, device=self.device),
+                                         torch.zeros(n_img, dtype=i32, device=self.device),
+                                         torch.empty(18 + 6 * (self.num_rel - 1) + 2, dtype=torch.float64, device=self.device))
+        rec = self._rec
+        self._launch(f, sum_g, sum_p, gc_rank=rec[0, r0:], ng_rank=rec[1, r0:], acc_rank=rec[2, r0:], zeroshot_flag=rec[3, r0:],
+                     ng_rows=sc[0], ng_cols=sc[1], ng_count=sc[2], metrics=sc[3])
+        if sum_g:
+            rec[4, r0:r0 + sum_g] = f["gt_rels"][:sum_g, 2]
+        self._img_g += n_g
+        self._img_p += n_p
+        self._rows = r0 + sum_g
+        return None
+
+    def accumulate_boxlists(self, groundtruths, predictions):
+        return self.accumulate(self._boxlist_images(groundtruths, predictions))
+
+    def _finalize_records(self):
+        """veto_sgg_eval_fold over the resident records, then ONE device-to-host copy: the metrics and the per-image quotients
+        share a buffer.  The records stay, so a second call returns the same bits."""
+        dev, C, n_img = self.device, self.num_rel, len(self._img_g)
+        Cf, n_m = C - 1, 18 + 6 * (C - 1) + 2
+        call = native.Launch(dev, "veto_amd.SGGEvaluator runs only on a HIP device")
+        self._reserve(1)
+        counts = np.zeros((2, n_img + 1), dtype=np.int64)
+        np.cumsum(np.asarray(self._img_g, dtype=np.int64), out=counts[0, 1:])
+        counts[1, :n_img] = self._img_p
+        counts = torch.from_numpy(counts.astype(np.int32)).to(dev)      # the one upload: offsets | pair counts
+        out = torch.empty(n_m + 12 * n_img, dtype=torch.float64, device=dev)
+        rec = self._rec
+        a = call.args(native.VetoSggEvalFoldArgs, n_img=n_img, n_rel_cls=C, mode=1 if self.mode == "sgdet" else 0,
+                      n_gt_total=self._rows, img_gt_offset=counts[0], img_pair_count=counts[1], gt_predicate=rec[4],
+                      gc_rank=rec[0], ng_rank=rec[1], acc_rank=rec[2], zeroshot_flag=rec[3], metrics=out,
+                      per_image=out[n_m:] if n_img else None)
+        ws = call.workspace(call.lib.veto_sgg_eval_fold_workspace_bytes(n_img, C))
+        call.run("veto_sgg_eval_fold", ctypes.byref(a), ws.data_ptr(), ws.numel())
+        h = out.cpu().numpy()
+        m, per = h[:n_m], h[n_m:].reshape(n_img, 12)
+        res = {"images_evaluated": int(m[18 + 6 * Cf]), "images_with_zeroshot": int(m[18 + 6 * Cf + 1])}
+        for j, name in enumerate(("recall", "recall_nogc", "zeroshot_recall", "accuracy", "mean_recall", "ng_mean_recall")):
+            res[name] = {k: float(m[3 * j + i]) for i, k in enumerate(KS)}
+        for kind, name in enumerate(("mean_recall_list", "ng_mean_recall_list")):
+            res[name] = {k: m[18 + (kind * 3 + i) * Cf: 18 + (kind * 3 + i + 1) * Cf].tolist() for i, k in enumerate(KS)}
+        for j, name in enumerate(("recall_list", "recall_nogc_list", "zeroshot_recall_list")):      # NaN: the image is not in the list
+            res[name] = {k: per[~np.isnan(per[:, 3 * j + i]), 3 * j + i].tolist() for i, k in enumerate(KS)}
+        return res
+
+    def state(self):
+        """The records as a dict of tensors trimmed to their rows (RECORD_FIELDS: [sum G] int32 each) plus the per-image counts
+        'gt_count' and 'pair_count' ([images] int64): what load_state() and distributed.all_gather_eval_state() take."""
+        self._feed("accumulate")
+        self._reserve(1)
+        st = {name: self._rec[i, :self._rows].clone() for i, name in enumerate(RECORD_FIELDS)}
+        st["gt_count"] = torch.tensor(self._img_g, dtype=torch.int64).to(self.device)
+        st["pair_count"] = torch.tensor(self._img_p, dtype=torch.int64).to(self.device)
+        return st
+
+    def load_state(self, states):
+        """Replaces the records by the concatenation of `states` (dicts as state() returns them, on any device) in list order:
+        with the contiguous shards of distributed.shard_images, rank-major order is dataset order and finalize() returns the
+        bits of a single-rank run."""
+        states = list(states)
+        for st in states:
+            rows = [int(st[name].numel()) for name in RECORD_FIELDS]
+            if len(set(rows)) != 1 or st["gt_count"].numel() != st["pair_count"].numel() or int(st["gt_count"].sum()) != rows[0]:
+                raise ValueError("veto_amd.SGGEvaluator.load_state: the fields of a state disagree about its rows")
+        self.reset()
+        self._fed = "accumulate"
+        for st in states:
+            self._img_g += [int(x) for x in st["gt_count"].tolist()]
+            self._img_p += [int(x) for x in st["pair_count"].tolist()]
+        rows = sum(self._img_g)
+        if rows >= 1 << 31 or len(self._img_g) >= 1 << 31:
+            raise ValueError("veto_amd.SGGEvaluator: a split holds fewer than 2^31 GT relations and images")
+        self._reserve(rows + 1)
+        for i, name in enumerate(RECORD_FIELDS):
+            if rows:
+                self._rec[i, :rows] = torch.cat([_t(st[name], torch.int32, self.device).reshape(-1) for st in states])
+        self._rows = rows
+
     def evaluate_boxlists(self, groundtruths, predictions):
         """vg_eval.py:470-498: unpack the fields of the GT / prediction BoxLists."""
+        return self.evaluate(self._boxlist_images(groundtruths, predictions))
+
+    @staticmethod
+    def _boxlist_images(groundtruths, predictions):
         images = []
         for gt, pr in zip(groundtruths, predictions):
             images.append({
@@ -116,14 +249,21 @@ class SGGEvaluator:
                 "pred_rel_inds": pr.get_field("rel_pair_idxs"), "rel_scores": pr.get_field("pred_rel_scores"),
                 "pred_classes": pr.get_field("pred_labels"), "pred_boxes": pr.convert("xyxy").bbox,
                 "obj_scores": pr.get_field("pred_scores")})
-        return self.evaluate(images)
+        return images
 
-    def evaluate(self, images):
+    def _pack(self, images, record=False):
+        """The batch as veto_sgg_eval takes it: concatenated device tensors, the offset arrays and the per-image counts.
+        record: keep the caller's device tensors alive on the current stream (a path that never synchronises may read them while
+        the stream that made them has moved on and released them)."""
         dev = self.device
-        call = native.Launch(dev, "veto_amd.SGGEvaluator runs only on a HIP device")
-        i64, f32, i32 = torch.int64, torch.float32, torch.int32
+        i64, f32 = torch.int64, torch.float32
+        stream = torch.cuda.current_stream(dev)
         def cat(key, dtype, shape):
-            t = torch.cat([_t(im[key], dtype, dev).reshape(shape) for im in images], 0).contiguous()
+            parts = [_t(im[key], dtype, dev).reshape(shape) for im in images]
+            if record:
+                for p in parts:
+                    p.record_stream(stream)
+            t = torch.cat(parts, 0).contiguous()
             # an all-empty field still needs a valid device pointer for the ABI's argument check
             return t if t.numel() else torch.zeros((1,) + tuple(abs(d) for d in shape[1:]), dtype=dtype, device=dev)
         gt_rels = cat("gt_rels", i64, (-1, 3))
@@ -148,20 +288,37 @@ class SGGEvaluator:
                 raise ValueError("sgdet: pred_classes, pred_boxes and obj_scores must have one row per predicted object")
             pred_off = native.device_offsets(n_q, device=dev)[0]
         off = native.device_offsets(n_g, n_o, n_p, device=dev)
+        fields = dict(n_img=len(images), n_rel_cls=self.num_rel, n_zeroshot=int(self.zeroshot.shape[0]), iou_thres=self.iou_thres,
+                      gt_offset=off[0], obj_offset=off[1], pair_offset=off[2], gt_rels=gt_rels, gt_classes=gt_classes,
+                      gt_boxes=gt_boxes, pred_pairs=pred_pairs, rel_scores=rel_scores, pred_classes=pred_classes,
+                      pred_boxes=pred_boxes, obj_scores=obj_scores, zeroshot=self.zeroshot,
+                      reserved0=1 if pred_off is not None else 0, pred_obj_offset=pred_off)
+        return fields, n_g, n_p
+
+    def _launch(self, f, sum_g, sum_p, gc_rank, ng_rank, acc_rank, zeroshot_flag, ng_rows, ng_cols, ng_count, metrics):
+        """veto_sgg_eval on a batch packed by _pack(), writing to the given output tensors."""
+        call = native.Launch(self.device, "veto_amd.SGGEvaluator runs only on a HIP device")
+        a = call.args(native.VetoSggEvalArgs, n_img=f["n_img"], n_rel_cls=f["n_rel_cls"], n_zeroshot=f["n_zeroshot"],
+                      iou_thres=f["iou_thres"], gt_offset=f["gt_offset"], obj_offset=f["obj_offset"], pair_offset=f["pair_offset"],
+                      gt_rels=f["gt_rels"], gt_classes=f["gt_classes"], gt_boxes=f["gt_boxes"], pred_pairs=f["pred_pairs"],
+                      rel_scores=f["rel_scores"], pred_classes=f["pred_classes"], pred_boxes=f["pred_boxes"],
+                      obj_scores=f["obj_scores"], zeroshot=f["zeroshot"], reserved0=f["reserved0"],
+                      pred_obj_offset=f["pred_obj_offset"], gc_rank=gc_rank, ng_rank=ng_rank, acc_rank=acc_rank,
+                      zeroshot_flag=zeroshot_flag, ng_rows=ng_rows, ng_cols=ng_cols, ng_count=ng_count, metrics=metrics)
+        ws = call.workspace(call.lib.veto_sgg_eval_workspace_bytes(f["n_img"], sum_p, sum_g, self.num_rel))
+        call.run("veto_sgg_eval", ctypes.byref(a), sum_p, sum_g, ws.data_ptr(), ws.numel())
+
+    def evaluate(self, images):
+        dev = self.device
+        i32 = torch.int32
+        fields, n_g, n_p = self._pack(images)
         n_img, sum_g, sum_p, C = len(images), sum(n_g), sum(n_p), self.num_rel
         out = {k: torch.empty(max(sum_g, 1), dtype=i32, device=dev) for k in ("gc_rank", "ng_rank", "acc_rank", "zeroshot_flag")}
         ng_rows = torch.zeros((n_img, 100), dtype=i32, device=dev)
         ng_cols = torch.zeros((n_img, 100), dtype=i32, device=dev)
         ng_count = torch.zeros(n_img, dtype=i32, device=dev)
         metrics = torch.empty(18 + 6 * (C - 1) + 2, dtype=torch.float64, device=dev)
-        a = call.args(native.VetoSggEvalArgs, n_img=n_img, n_rel_cls=C, n_zeroshot=int(self.zeroshot.shape[0]), iou_thres=self.iou_thres,
-                      gt_offset=off[0], obj_offset=off[1], pair_offset=off[2], gt_rels=gt_rels, gt_classes=gt_classes,
-                      gt_boxes=gt_boxes, pred_pairs=pred_pairs, rel_scores=rel_scores, pred_classes=pred_classes,
-                      pred_boxes=pred_boxes, obj_scores=obj_scores, zeroshot=self.zeroshot,
-                      reserved0=1 if pred_off is not None else 0, pred_obj_offset=pred_off, ng_rows=ng_rows, ng_cols=ng_cols,
-                      ng_count=ng_count, metrics=metrics, **out)
-        ws = call.workspace(call.lib.veto_sgg_eval_workspace_bytes(n_img, sum_p, sum_g, C))
-        call.run("veto_sgg_eval", ctypes.byref(a), sum_p, sum_g, ws.data_ptr(), ws.numel())
+        self._launch(fields, sum_g, sum_p, ng_rows=ng_rows, ng_cols=ng_cols, ng_count=ng_count, metrics=metrics, **out)
         m = metrics.cpu().numpy()
         Cf = C - 1
         res = {"images_evaluated": int(m[18 + 6 * Cf]), "images_with_zeroshot": int(m[18 + 6 * Cf + 1])}

@@ -200,6 +200,12 @@ class VetoSggEvalArgs(Structure):
                                         "metrics", "pred_obj_offset")]
 
 
+class VetoSggEvalFoldArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_rel_cls", "mode", "n_gt_total", "reserved0")] + \
+               [(n, c_void_p) for n in ("img_gt_offset", "img_pair_count", "gt_predicate", "gc_rank", "ng_rank", "acc_rank",
+                                        "zeroshot_flag", "metrics", "per_image")]
+
+
 class VetoDetEvalMatchArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_cls", "n_gt", "n_det", "reserved0")] + \
                [("first_gt_id", c_int64), ("row_offset", c_int64), ("iou_thrs", c_double * 10), ("area_rngs", c_double * 8)] + \
@@ -231,6 +237,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_optim_tensor_t": VetoOptimTensor, "veto_optim_args_t": VetoOptimArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
     "veto_det_eval_match_args_t": VetoDetEvalMatchArgs, "veto_det_eval_accumulate_args_t": VetoDetEvalAccumulateArgs,
+    "veto_sgg_eval_fold_args_t": VetoSggEvalFoldArgs,
 }
 
 _P, _I, _Z = c_void_p, c_int32, c_size_t
@@ -313,6 +320,9 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_sgg_eval": _sig(_P, POINTER(VetoSggEvalArgs), _I, _I, _P, _Z),
     "veto_sgg_eval_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+    "veto_sgg_eval_fold": _sig(_P, POINTER(VetoSggEvalFoldArgs), _P, _Z),
+    "veto_sgg_eval_fold_workspace_bytes": _sig(_I, _I, ret=_Z),
+    "veto_sgg_eval_fold_limits": _sig(POINTER(_I), POINTER(_I)),
     "veto_det_eval_match": _sig(_P, POINTER(VetoDetEvalMatchArgs), _P, _Z),
     "veto_det_eval_match_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
     "veto_det_eval_accumulate": _sig(_P, POINTER(VetoDetEvalAccumulateArgs), _P, _Z),
