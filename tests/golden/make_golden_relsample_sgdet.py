@@ -7,7 +7,11 @@ POSITIVE_FRACTION), the returned pairs, labels, rel_labels_all (when the target 
 locating_match, the IoUs boxlist_iou(target, proposal), and rel_possibility after the foreground removal -- the bound
 motif_rel_fg_bg_sampling is wrapped and its mutated argument cloned after the call (the reference stays untouched).
 The reference draws from numpy's and torch's generators, seeded per case here.
-Usage: python tests/golden/make_golden_relsample_sgdet.py"""
+
+With `large` it writes tests/golden/sgdet/relsample_large.npz instead: the same arrays for the cases of
+tests/relsample_cases.py (LARGE_CASES), one image each at the sizes sgdet training has and at the sampler's limits of 256
+proposals and 256 GT boxes.  relsample.npz is left alone then.
+Usage: python tests/golden/make_golden_relsample_sgdet.py [large]"""
 import os
 import sys
 
@@ -16,9 +20,11 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 from make_golden import import_reference  # noqa: E402
+import relsample_cases  # noqa: E402
 from veto_amd import synth  # noqa: E402
 
 OUT = os.path.join(HERE, "sgdet")
@@ -69,24 +75,34 @@ def run_case(BoxList, RelationSampling, seed, d, cfg, non_masked):
     return out
 
 
-def main():
+def store(arrays, name, d, out, cfg, non_masked):
+    for k in ("prp_boxes", "prp_labels", "pred_scores", "tgt_boxes", "tgt_labels", "relation"):
+        arrays[name + "__" + k] = d[k]
+    if non_masked:
+        arrays[name + "__relation_non_masked"] = d["relation_non_masked"]
+    arrays[name + "__config"] = np.array([cfg[0], float(cfg[1]), cfg[2], cfg[3], cfg[4]], np.float64)
+    for k, v in out.items():
+        arrays[name + "__" + k] = v
+    print(name, "rows", len(out["pairs"]), "fg", int((out["labels"] > 0).sum()))
+
+
+def main(large=False):
     _, _, BoxList = import_reference()
     from pysgg.modeling.roi_heads.relation_head.sampling import RelationSampling
     arrays = {}
-    for name, (seed, n_gt, n_det, n_rel, opts, cfg, non_masked) in CASES.items():
-        d = synth.synthetic_relsample_image(seed, n_gt, n_det, n_rel, **opts)
-        out = run_case(BoxList, RelationSampling, seed, d, cfg, non_masked)
-        for k in ("prp_boxes", "prp_labels", "pred_scores", "tgt_boxes", "tgt_labels", "relation"):
-            arrays[name + "__" + k] = d[k]
-        if non_masked:
-            arrays[name + "__relation_non_masked"] = d["relation_non_masked"]
-        arrays[name + "__config"] = np.array([cfg[0], float(cfg[1]), cfg[2], cfg[3], cfg[4]], np.float64)
-        for k, v in out.items():
-            arrays[name + "__" + k] = v
-        print(name, "rows", len(out["pairs"]), "fg", int((out["labels"] > 0).sum()))
+    if large:
+        for name, case in relsample_cases.LARGE_CASES.items():
+            d, cfg, non_masked = relsample_cases.large_case_inputs(name)
+            store(arrays, name, d, run_case(BoxList, RelationSampling, case[0], d, cfg, non_masked), cfg, non_masked)
+    else:
+        for name, (seed, n_gt, n_det, n_rel, opts, cfg, non_masked) in CASES.items():
+            d = synth.synthetic_relsample_image(seed, n_gt, n_det, n_rel, **opts)
+            store(arrays, name, d, run_case(BoxList, RelationSampling, seed, d, cfg, non_masked), cfg, non_masked)
     os.makedirs(OUT, exist_ok=True)
-    np.savez_compressed(os.path.join(OUT, "relsample.npz"), **arrays)
+    np.savez_compressed(os.path.join(OUT, "relsample_large.npz" if large else "relsample.npz"), **arrays)
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] not in ([], ["large"]):
+        sys.exit(__doc__)
+    main(large=sys.argv[1:] == ["large"])

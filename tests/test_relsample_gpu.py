@@ -1,6 +1,8 @@
 """sgdet training on the MI355X: veto_detect_relsample (DetectRelationSampler) against the reference's outputs
-(tests/golden/sgdet/relsample.npz) and the numpy restatement of tests/test_relsample_host.py, its distributions over one
-launch of many copies of an image, its limits, and VETORelationHead training on detected boxes (vanilla and MEET)."""
+(tests/golden/sgdet/relsample.npz, and relsample_large.npz at the sizes of sgdet training and at the limits of 256 proposals and
+256 GT boxes) and the numpy restatement of tests/test_relsample_host.py, an edge sweep over the mask-word and loop-step sizes,
+its distributions over one launch of many copies of an image (in the first and in the last mask word), its limits, and
+VETORelationHead training on detected boxes (vanilla and MEET)."""
 import itertools
 import os
 import random
@@ -11,8 +13,9 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import relsample_cases as rc  # noqa: E402
 from test_relsample_host import (case_config, case_image, case_names, deterministic, load_golden,  # noqa: E402
-                                 np_labels_all_fg, np_relsample_parts, rows_multiset)
+                                 load_golden_large, np_labels_all_fg, np_relsample_parts, rows_multiset)
 
 from veto_amd import native, synth, testing  # noqa: E402
 from veto_amd.structures import BoxList  # noqa: E402
@@ -64,6 +67,13 @@ def _check_image(d, cfg, s, pairs, labels, labels_all, binary, locating, g=None,
             for i in cand[row]:
                 per[i] = per.get(i, 0) + 1
         assert sum(min(len(r["cand"]), per_rel) for r in s["rels"]) == len(fg)
+        at = 0
+        for i, r in enumerate(s["rels"]):   # relation i owns the next min(candidates, per_rel) rows, all different
+            mine = fg[at:at + r["n"]]
+            at += r["n"]
+            assert len(set(mine)) == len(mine) and all(i in cand[row] for row in mine), (i, mine)
+            if len(r["cand"]) <= per_rel:
+                assert [(a, b) for a, b, _ in mine] == [tuple(map(int, c)) for c in r["cand"]]
     if s["num_neg"]:
         bg = [tuple(x) for x in pairs[n_fg:].tolist()]
         win = {tuple(x) for x in s["bg_sorted"][:s["window"]].tolist()}
@@ -87,7 +97,17 @@ def _run(d, cfg, seed, copies=1):
 
 @pytest.mark.parametrize("case", case_names(load_golden()))
 def test_kernel_matches_the_reference_fixtures(case):
-    g = load_golden()
+    _kernel_matches_the_reference_fixture(load_golden(), case)
+
+
+@pytest.mark.parametrize("case", sorted(rc.LARGE_CASES))
+def test_kernel_matches_the_reference_fixtures_at_real_and_limit_sizes(case):
+    g = load_golden_large()
+    d, cfg, s = _kernel_matches_the_reference_fixture(g, case)
+    print(rc.record_line(case, d, cfg, s, deterministic(s, cfg[2])))
+
+
+def _kernel_matches_the_reference_fixture(g, case):
     d, cfg = case_image(g, case), case_config(g, case)
     s = np_relsample_parts(d, *cfg)
     props, labels, labels_all, pairs, binary = _run(d, cfg, 1234)
@@ -102,6 +122,68 @@ def test_kernel_matches_the_reference_fixtures(case):
         assert len(la) == len(g[case + "__labels_all"])
     _check_image(d, cfg, s, pairs[0].cpu().numpy(), labels[0].cpu().numpy(), la, binary[0].cpu().numpy(),
                  props[0].get_field("locating_match").cpu().numpy(), g, case)
+    return d, cfg, s
+
+
+@pytest.mark.parametrize("sweep", sorted(rc.SWEEPS))
+def test_edge_sweep_matches_the_restatement(sweep):
+    """Every image of a sweep in one launch: proposals at the mask-word edges 31..33, 63..65 and 255/256, GT boxes at the
+    loop-step edges 15..17 (225, 256, 289 cells), 32/33 and 256."""
+    cfg, images = rc.sweep_images(sweep)
+    props, targets = [], []
+    for d in images:
+        p, t = _lists(d, with_nm=True)
+        props += p
+        targets += t
+    props, labels, labels_all, pairs, binary = _sampler(cfg).detect_relsample(props, targets, seed=4321)
+    for i, d in enumerate(images):
+        s = np_relsample_parts(d, *cfg)
+        pr, lb, la = pairs[i].cpu().numpy(), labels[i].cpu().numpy(), labels_all[i].cpu().numpy()
+        n_fg = int((lb > 0).sum())
+        rows = 2 if s["n_fg"] == 0 and s["num_neg"] == 0 else s["n_fg"] + s["num_neg"]
+        # counts = (rows, F, n_fg, status): the split of the outputs is made from them, and status 0 is the absence of the IndexError
+        assert (len(pr), len(la) - (len(pr) - n_fg), n_fg) == (rows, s["n_pre"], s["n_fg"]), (sweep, i)
+        corr = [k for k, r in enumerate(s["rels"]) for _ in range(r["n"])]
+        np.testing.assert_array_equal(la[:s["n_pre"]], np_labels_all_fg(d, corr))
+        _check_image(d, cfg, s, pr, lb, la, binary[i].cpu().numpy(), props[i].get_field("locating_match").cpu().numpy())
+        print(rc.record_line("sweep_%s_%d" % (sweep, i), d, cfg, s, False))
+
+
+def _outputs(out, i):
+    props, labels, labels_all, pairs, binary = out
+    return [x.cpu().numpy() for x in (pairs[i], labels[i], labels_all[i], binary[i], props[i].get_field("locating_match"))]
+
+
+def test_an_image_at_the_limits_does_not_depend_on_its_neighbours():
+    """Draws depend on the seed, the image index and the image's own inputs: each image of a ragged batch of limit-size,
+    real-size, one-proposal and zero-relation images is bit-equal to the same image at the same position among small ones."""
+    g, small = load_golden_large(), load_golden()
+    cfg = (0.5, False, 4, 1024, 0.25)
+    one = rc.seeded_image(61, 17, 1, 30)
+    assert len(one["prp_boxes"]) == 1
+    none = rc.seeded_image(62, 33, 65, 0, dict(n_extra_non_masked=0))
+    assert not none["relation"].any()
+    mixed = [case_image(g, "limit"), case_image(g, "real"), one, none, case_image(g, "padded_deterministic")]
+    filler = [case_image(small, c) for c in ("many", "twin", "cap", "small", "degenerate")]
+    assert all("relation_non_masked" in d for d in mixed + filler)
+
+    def run(images):
+        props, targets = [], []
+        for d in images:
+            p, t = _lists(d, with_nm=True)
+            props += p
+            targets += t
+        return _sampler(cfg).detect_relsample(props, targets, seed=99)
+
+    together = run(mixed)
+    for i, d in enumerate(mixed):
+        s = np_relsample_parts(d, *cfg)
+        got = _outputs(together, i)
+        _check_image(d, cfg, s, got[0], got[1], got[2], got[3], got[4])
+        alone = _outputs(run(filler[:i] + [d] + filler[i + 1:]), i)
+        for a, b in zip(got, alone):
+            assert a.dtype == b.dtype and np.array_equal(a, b), i
+    assert len(_outputs(together, 3)[0]) == cfg[3] and not _outputs(together, 3)[1].any()
 
 
 def test_a_batch_of_images_gives_each_image_its_own_result():
@@ -176,8 +258,35 @@ def _assert_freq(count, n, prob, what):
     assert (z < 5).all(), (what, count / n, prob, z)
 
 
-def test_foreground_draws_follow_the_weights():
+def _image_four_candidates():
+    """The first four detections of _image_six_candidates: 2 x 2 candidates, so no draws."""
     d = _image_six_candidates()
+    d["prp_boxes"] = d["prp_boxes"][[0, 1, 2, 3]]
+    d["prp_labels"], d["pred_scores"] = d["prp_labels"][[0, 1, 2, 3]], d["pred_scores"][[0, 1, 2, 3]]
+    return d
+
+
+def _run_copies(d, cfg, seed, copies):
+    """`copies` times the same image in one launch, the inputs uploaded once."""
+    (p,), (t,) = _lists(d)
+    out = _sampler(cfg).detect_relsample([p] * copies, [t] * copies, seed=seed)
+    torch.cuda.synchronize()
+    return out
+
+
+def test_foreground_draws_follow_the_weights():
+    _foreground_draws_follow_the_weights(_image_six_candidates(), (1, 2))
+
+
+def test_foreground_draws_follow_the_weights_in_the_last_mask_word():
+    """The same image at proposals 251..255 and GT boxes 254 and 255 of a 256 x 256 one (relation cell 65 279)."""
+    d = rc.pad_front(_image_six_candidates(), 256, 256)
+    s = np_relsample_parts(d, 0.5, False, 4, 1024, 0.25)
+    assert (s["rels"][0]["h"], s["rels"][0]["t"]) == (254, 255) and min(min(c) for c in s["rels"][0]["cand"]) == 251
+    _foreground_draws_follow_the_weights(d, (1, 2, 5, 6))
+
+
+def _foreground_draws_follow_the_weights(d, seeds):
     cfg = (0.5, False, 4, 1024, 0.25)
     s = np_relsample_parts(d, *cfg)
     r = s["rels"][0]
@@ -186,9 +295,9 @@ def test_foreground_draws_follow_the_weights():
     N = 2000
     first = np.zeros(6)
     count = np.zeros(6)
-    for seed in (1, 2):
-        _, labels, _, pairs, _ = _run(d, cfg, seed, copies=N // 2)
-        index = {c: j for j, c in enumerate(r["cand"])}
+    for seed in seeds:
+        _, labels, _, pairs, _ = _run_copies(d, cfg, seed, N // len(seeds))
+        index = {tuple(map(int, c)): j for j, c in enumerate(r["cand"])}
         for pr, lb in zip(pairs, labels):
             fg = [tuple(x) for x in pr[lb > 0].cpu().numpy().tolist()]
             assert len(fg) == 4 and len(set(fg)) == 4
@@ -201,20 +310,28 @@ def test_foreground_draws_follow_the_weights():
 
 
 def test_foreground_cap_and_background_subset_are_uniform():
-    d = _image_six_candidates()
-    d["relation"] = np.array([[0, 7], [0, 0]], np.int64)
-    d["prp_boxes"] = d["prp_boxes"][[0, 1, 2, 3]]
-    d["prp_labels"], d["pred_scores"] = d["prp_labels"][[0, 1, 2, 3]], d["pred_scores"][[0, 1, 2, 3]]
+    _foreground_cap_and_background_subset_are_uniform(_image_four_candidates(), (3, 4))
+
+
+def test_foreground_cap_and_background_subset_are_uniform_in_the_last_mask_word():
+    """The same image at proposals 252..255 and GT boxes 254 and 255 of a 256 x 256 one."""
+    d = rc.pad_front(_image_four_candidates(), 256, 256)
+    s = np_relsample_parts(d, 0.5, False, 4, 4, 0.25)
+    assert (s["rels"][0]["h"], s["rels"][0]["t"]) == (254, 255) and int(s["bg_sorted"].min()) == 252
+    _foreground_cap_and_background_subset_are_uniform(d, (3, 4, 7, 8))
+
+
+def _foreground_cap_and_background_subset_are_uniform(d, seeds):
     # 4 candidates (2 x 2), so no draws; B = 4 keeps 1 foreground row, then 3 of the 8 remaining pairs, window 6
     cfg = (0.5, False, 4, 4, 0.25)
     s = np_relsample_parts(d, *cfg)
     assert s["n_pre"] == 4 and s["num_pos"] == 1 and s["num_neg"] == 3 and s["window"] == 6 and len(s["bg_sorted"]) == 8
-    fg_index = {c: j for j, c in enumerate(s["rels"][0]["cand"])}
+    fg_index = {tuple(map(int, c)): j for j, c in enumerate(s["rels"][0]["cand"])}
     win = [tuple(x) for x in s["bg_sorted"][:6].tolist()]
     N = 2000
     fg_count, bg_count, bg_first = np.zeros(4), np.zeros(6), np.zeros(6)
-    for seed in (3, 4):
-        _, labels, _, pairs, _ = _run(d, cfg, seed, copies=N // 2)
+    for seed in seeds:
+        _, labels, _, pairs, _ = _run_copies(d, cfg, seed, N // len(seeds))
         for pr, lb in zip(pairs, labels):
             pr = pr.cpu().numpy()
             assert len(pr) == 4
@@ -249,15 +366,46 @@ def test_limits_are_errors_not_truncations():
         _run(short, (0.5, False, 4, 1024, 0.25), 1)
 
 
+def test_relation_non_masked_too_short_in_a_later_step_is_an_error():
+    """17 GT boxes: 289 cells, two steps.  relation_non_masked has a nonzero entry for every relation before the first relation
+    of the second step that produces triplets, and none from there on: the same IndexError as in the first step, nothing
+    clamped; with one more entry that relation is served and the next one fails; with all of them nothing does."""
+    cfg = (0.5, False, 4, 1024, 0.25)
+    d = rc.seeded_image(21, 17, 80, 30)
+    s = np_relsample_parts(d, *cfg)
+    cells = rc.relation_cells(s, 17)
+    live = [k for k, (c, r) in enumerate(zip(cells, s["rels"])) if r["n"] > 0]
+    assert any(cells[k] < rc.STEP for k in live)
+    later = [k for k in live if cells[k] >= rc.STEP]
+    assert len(later) >= 2 and later[0] >= sum(c < rc.STEP for c in cells)
+
+    def with_entries(count):
+        nm = np.zeros(17 * 17, np.int64)
+        nm[cells[:count]] = [r["label"] for r in s["rels"][:count]]
+        return dict(d, relation_non_masked=nm.reshape(17, 17))
+
+    for count in (later[0], later[-1]):
+        with pytest.raises(IndexError, match="relation_non_masked has fewer nonzero entries"):
+            _run(with_entries(count), cfg, 1)
+    full = with_entries(later[-1] + 1)
+    _, labels, labels_all, pairs, _ = _run(full, cfg, 1)
+    corr = [k for k, r in enumerate(s["rels"]) for _ in range(r["n"])]
+    np.testing.assert_array_equal(labels_all[0].cpu().numpy()[:s["n_pre"]], np_labels_all_fg(full, corr))
+
+
 # ---- the relation head training on detected boxes ----------------------------------------------------------------------
 
-def _head_inputs(dev, n_cls=151):
+SMALL_SIZES = ((6, 24, 6), (5, 18, 4))       # (GT boxes, detections, relations) per image
+REAL_SIZES = ((35, 80, 60), (50, 80, 90))    # 1225 and 2500 relation cells: 5 and 10 steps, mask words 0..2
+
+
+def _head_inputs(dev, n_cls=151, sizes=SMALL_SIZES):
     rng = np.random.RandomState(31)
     W, H = 800, 600
     feats = [torch.from_numpy((0.5 * rng.randn(2, 256, H >> (2 + l), W >> (2 + l))).astype(np.float32)).to(dev) for l in range(4)]
     depth = torch.from_numpy((0.5 * rng.randn(2, 256, H >> 4, W >> 4)).astype(np.float32)).to(dev)
     props, targets = [], []
-    for i, (n_gt, n_det, n_rel) in enumerate(((6, 24, 6), (5, 18, 4))):
+    for i, (n_gt, n_det, n_rel) in enumerate(sizes):
         d = synth.synthetic_relsample_image(40 + i, n_gt, n_det, n_rel, num_obj_cls=n_cls)
         (p,), (t,) = _lists(d, with_nm=False)
         logits = torch.from_numpy(synth.normal(50 + i, "head.logits", (n_det, n_cls), 0.0, 1.0)).to(dev)
@@ -293,9 +441,20 @@ def _sgdet_head(meet, dev):
 
 @pytest.mark.parametrize("meet", [False, True])
 def test_relation_head_trains_on_detected_boxes(meet):
+    _relation_head_trains_on_detected_boxes(meet, SMALL_SIZES)
+
+
+@pytest.mark.parametrize("meet", [False, True])
+def test_relation_head_trains_on_detected_boxes_at_real_size(meet):
+    """Two images of 80 detections against 35 and 50 GT boxes."""
+    _relation_head_trains_on_detected_boxes(meet, REAL_SIZES)
+
+
+def _relation_head_trains_on_detected_boxes(meet, sizes):
     dev = torch.device("cuda:0")
     cfg, head = _sgdet_head(meet, dev)
-    feats, depth, props, targets = _head_inputs(dev)
+    feats, depth, props, targets = _head_inputs(dev, sizes=sizes)
+    assert [(len(t), len(p)) for p, t in zip(props, targets)] == [s[:2] for s in sizes]
     depth.requires_grad_(True)
 
     def step(seed):

@@ -1,15 +1,19 @@
 """sgdet training, host side: a numpy restatement of RelationSampling.detect_relsample (sampling.py:109-176) and
 motif_rel_fg_bg_sampling (:179-309) with the randomness factored out, pinned to the reference's own outputs
-(tests/golden/sgdet/relsample.npz); the C ABI of veto_detect_relsample; the config key and the refusal without it."""
+(tests/golden/sgdet/relsample.npz, and relsample_large.npz at the sizes of sgdet training and at the sampler's limits of 256
+proposals and 256 GT boxes); the C ABI of veto_detect_relsample; the config key and the refusal without it."""
 import ctypes
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from veto_amd import native
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import relsample_cases as rc  # noqa: E402
+from veto_amd import native  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sgdet", "relsample.npz")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "veto_amd.h")
@@ -18,6 +22,10 @@ FIELDS = ("prp_boxes", "prp_labels", "pred_scores", "tgt_boxes", "tgt_labels", "
 
 def load_golden():
     return np.load(GOLDEN)
+
+
+def load_golden_large():
+    return np.load(rc.GOLDEN_LARGE)
 
 
 def case_names(g):
@@ -164,7 +172,10 @@ def test_fixture_covers_the_cases_the_sampler_must_handle():
 
 @pytest.mark.parametrize("case", case_names(load_golden()))
 def test_restatement_matches_the_reference_deterministic_quantities(case):
-    g = load_golden()
+    _restatement_matches_the_reference(load_golden(), case)
+
+
+def _restatement_matches_the_reference(g, case):
     d, cfg = case_image(g, case), case_config(g, case)
     s = np_relsample_parts(d, *cfg)
     np.testing.assert_array_equal(s["ious"], g[case + "__ious"])
@@ -183,11 +194,20 @@ def test_restatement_matches_the_reference_deterministic_quantities(case):
             cand[(c[0], c[1], r["label"])] += 1
     for row in rows_multiset(pairs[:n_fg], labels[:n_fg]):
         assert row in cand, row
-    # the background lies in the window, without duplicates; its quality multiset is the window's when it is all of it
-    win = {tuple(p) for p in s["bg_sorted"][:s["window"]].tolist()}
-    bg = [tuple(p) for p in pairs[n_fg:].tolist()] if s["num_neg"] else []
-    assert len(set(bg)) == len(bg) and set(bg) <= win
+    # the background lies in the window, without duplicates; its quality multiset is the window's when it is all of it.
+    # The reference's torch.sort (:290) is not stable, so where the window's edge falls inside a run of equal qualities its
+    # window holds everything above the run and any window - above members of the run (the restatement, like the kernel, takes
+    # the first of them in row-major order); without such a run this is the restatement's window exactly.
+    w, bq = s["window"], s["bg_quality"]
     q = d["pred_scores"].astype(np.float32)
+    bg = [tuple(p) for p in pairs[n_fg:].tolist()] if s["num_neg"] else []
+    if 0 < w < len(bq) and bq[w] == bq[w - 1]:
+        above = int((bq > bq[w - 1]).sum())
+        win = {tuple(p) for p in s["bg_sorted"][bq >= bq[w - 1]].tolist()}
+        assert sum(q[a] * q[b] == bq[w - 1] for a, b in bg) <= w - above
+    else:
+        win = {tuple(p) for p in s["bg_sorted"][:w].tolist()}
+    assert len(set(bg)) == len(bg) and set(bg) <= win
     if s["num_neg"] == s["window"]:
         got = sorted(q[[b[0] for b in bg]] * q[[b[1] for b in bg]])
         np.testing.assert_array_equal(got, sorted(s["bg_quality"][:s["window"]]))
@@ -203,7 +223,10 @@ def test_restatement_matches_the_reference_deterministic_quantities(case):
 
 
 def test_restatement_draws_respect_the_budgets():
-    g = load_golden()
+    _restatement_draws_respect_the_budgets(load_golden())
+
+
+def _restatement_draws_respect_the_budgets(g):
     rng = np.random.default_rng(5)
     for case in case_names(g):
         d, cfg = case_image(g, case), case_config(g, case)
@@ -213,6 +236,122 @@ def test_restatement_draws_respect_the_budgets():
         assert (labels > 0).sum() == s["n_fg"]
         if all_ is not None:
             assert len(all_) == len(g[case + "__labels_all"])
+
+
+# ---- the same at the sizes of sgdet training and at the limits: 256 proposals, 256 GT boxes, all eight mask words -----------------
+
+def test_large_fixture_holds_the_cases_of_the_case_table():
+    g = load_golden_large()
+    assert case_names(g) == sorted(rc.LARGE_CASES)
+    for case in case_names(g):
+        d, cfg, non_masked = rc.large_case_inputs(case)
+        assert case_config(g, case) == cfg
+        assert (case + "__relation_non_masked" in g.files) == non_masked
+        for k, v in case_image(g, case).items():
+            assert v.dtype == d[k].dtype and np.array_equal(v, d[k]), (case, k)
+    assert os.path.getsize(rc.GOLDEN_LARGE) <= 1 << 20
+    sizes = {c: (len(g[c + "__prp_boxes"]), len(g[c + "__tgt_boxes"])) for c in case_names(g)}
+    assert sizes == {"real": (80, 17), "word_edge": (65, 33), "limit": (256, 60), "limit_overlap": (256, 256),
+                     "over_sort_buffer": (256, 40), "padded_deterministic": (256, 256), "ties": (80, 17)}
+    assert case_config(g, "real") == (0.5, False, 4, 1024, 0.25)
+    assert case_config(g, "word_edge")[3] == 64 and case_config(g, "limit_overlap") == (0.5, True, 16, 2048, 0.25)
+    assert case_config(g, "over_sort_buffer")[2:4] == (16, 2048) and case_config(g, "padded_deterministic")[2:4] == (4, 2048)
+    assert int(np.count_nonzero(g["limit__relation"])) == 150
+    assert len(np.unique(g["ties__pred_scores"])) == 4
+
+
+def test_large_fixture_covers_what_the_small_sizes_cannot_reach():
+    g = load_golden_large()
+    parts = {}
+    for case in case_names(g):
+        cfg = case_config(g, case)
+        parts[case] = (case_image(g, case), cfg, np_relsample_parts(case_image(g, case), *cfg))
+    words, seen = set(), set()
+    for case, (d, cfg, s) in parts.items():
+        P, T, per_rel = len(d["prp_boxes"]), len(d["tgt_boxes"]), cfg[2]
+        words |= set(rc.match_words(s))
+        cells = rc.relation_cells(s, T)
+        live = [(c, r) for c, r in zip(cells, s["rels"]) if r["cand"]]     # relations that produce triplets
+        for lo in (256, 32768, 65280):
+            if any(c >= lo for c, _ in live):
+                seen.add("cell>=%d" % lo)
+        if len({c // rc.STEP for c, _ in live}) >= 3:
+            seen.add("three_steps")
+            if any(c >= rc.STEP and len(r["cand"]) > per_rel for c, r in live):
+                seen.add("draws_in_a_later_step")
+        if s["n_pre"] > rc.SORT_BUFFER and cfg[3] == 2048 and s["n_pre"] > s["num_pos"]:
+            seen.add("F>2048")
+        if s["n_pre"] > s["num_pos"] and s["window"] < len(s["bg_sorted"]) and P == 256:
+            seen.add("cap_and_window_at_256")
+        taken, left = rc.window_tie_run(s)
+        if len(taken) and len(left):
+            run = np.concatenate([taken, left])
+            # the run of equal qualities around the window's edge spans proposal rows and 32-column mask words, and so do the
+            # part inside the window and the part outside it
+            if min(len({int(x[0]) for x in part}) for part in (taken, left)) >= 3 and \
+                    min(len({int(x[1]) // 32 for x in part}) for part in (taken, left)) >= 2 and len(run) > 64:
+                seen.add("tie_run_across_words")
+        if P == 256 and T >= 17 and deterministic(s, per_rel) and s["num_neg"] > 0 and s["n_fg"] > 0:
+            seen.add("deterministic_at_256")
+    assert words == set(range(8)), words
+    assert seen == {"cell>=256", "cell>=32768", "cell>=65280", "three_steps", "draws_in_a_later_step", "F>2048",
+                    "cap_and_window_at_256", "tie_run_across_words", "deterministic_at_256"}, seen
+    # the cases the table names have the properties it names them for
+    d, cfg, s = parts["padded_deterministic"]
+    assert deterministic(s, cfg[2]) and s["num_neg"] == len(s["bg_sorted"]) > 0
+    assert rc.match_words(s) == [6, 7] and not s["is_match"][:, :216].any() and (d["prp_labels"][:216] == 0).all()
+    assert not d["relation"][:236].any() and not d["relation"][:, :236].any()
+    assert max(rc.relation_cells(s, 256)) >= 65280
+    d, cfg, s = parts["real"]
+    assert rc.steps_of(17) == 2 and {c // rc.STEP for c in rc.relation_cells(s, 17)} == {0, 1}
+    d, cfg, s = parts["word_edge"]
+    assert s["n_pre"] > s["num_pos"] and 2 in rc.match_words(s)
+    d, cfg, s = parts["limit"]
+    assert s["n_pre"] > s["num_pos"] and s["window"] < len(s["bg_sorted"])
+    d, cfg, s = parts["over_sort_buffer"]
+    assert s["n_pre"] > rc.SORT_BUFFER
+    d, cfg, s = parts["ties"]
+    assert len(d["prp_boxes"]) > 64 and len(rc.window_tie_run(s)[0]) > 0
+
+
+@pytest.mark.parametrize("case", sorted(rc.LARGE_CASES))
+def test_restatement_matches_the_reference_at_real_and_limit_sizes(case):
+    _restatement_matches_the_reference(load_golden_large(), case)
+
+
+def test_restatement_draws_respect_the_budgets_at_real_and_limit_sizes():
+    _restatement_draws_respect_the_budgets(load_golden_large())
+
+
+def test_front_padding_moves_an_image_without_changing_it():
+    d = rc.seeded_image(26, 20, 40, 30, dict(max_copies=2))
+    cfg = (0.5, False, 4, 2048, 0.25)
+    s, big = np_relsample_parts(d, *cfg), np_relsample_parts(rc.pad_front(d, 256, 256), *cfg)
+    assert [(r["h"] + 236, r["t"] + 236, r["label"], [(a + 216, b + 216) for a, b in r["cand"]]) for r in s["rels"]] == \
+        [(r["h"], r["t"], r["label"], [tuple(map(int, c)) for c in r["cand"]]) for r in big["rels"]]
+    np.testing.assert_array_equal(big["bg_sorted"], s["bg_sorted"] + 216)
+    np.testing.assert_array_equal(big["binary"][216:, 216:], s["binary"])
+    assert not big["binary"][:216].any() and not big["binary"][:, :216].any() and not big["poss0"][:216].any()
+    assert not big["locating"][:216].any()
+    assert (big["n_pre"], big["n_fg"], big["num_neg"], big["window"]) == (s["n_pre"], s["n_fg"], s["num_neg"], s["window"])
+
+
+def test_sweep_covers_every_edge_size_and_setting():
+    seen_p, seen_t, per_rel, batch, overlap, edge_t = set(), set(), set(), set(), set(), {}
+    for name in rc.SWEEPS:
+        cfg, images = rc.sweep_images(name)
+        per_rel.add(cfg[2])
+        batch.add(cfg[3])
+        overlap.add(cfg[1])
+        for d in images:
+            P, T = len(d["prp_boxes"]), len(d["tgt_boxes"])
+            assert "relation_non_masked" in d and np_relsample_parts(d, *cfg)["n_pre"] > 0
+            seen_p.add(P)
+            seen_t.add(T)
+            edge_t[P] = max(edge_t.get(P, 0), T)
+    assert seen_p == {31, 32, 33, 63, 64, 65, 255, 256} and seen_t == {15, 16, 17, 32, 33, 256}
+    assert per_rel == {1, 4, 16} and batch == {2, 64, 2048} and overlap == {False, True}
+    assert all(edge_t[P] > 16 for P in (64, 65, 255, 256))
 
 
 # ---- C ABI, config and the refusal without the key -----------------------------------------------------------------
