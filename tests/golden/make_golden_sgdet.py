@@ -14,7 +14,11 @@ A seed is rejected (the next one is tried) when the reference's labels change un
 consulted same-class IoU lies within 1e-6 of the threshold, or when a MEET-decoder tie between rows is decided by the
 last ulp of the reference's softmax (its row sums depend on where the one-hot's 1 sits) rather than by the row-major
 order that identical rows give; the hand-built image of synth.synthetic_detections_iou_tie
-is the one deliberate exact equality.  Usage: python tests/golden/make_golden_sgdet.py"""
+is the one deliberate exact equality.  Usage: python tests/golden/make_golden_sgdet.py
+
+`python tests/golden/make_golden_sgdet.py cases` writes only decode_cases.npz and pairs_cases.npz: the same three reference
+functions on the hand-built cases of tests/sgdet_cases.py (GOLDEN_DECODE, GOLDEN_PAIRS; prepare_test_pairs with its
+max_proposal_pairs argument set to the instance's cap), outputs only -- the inputs are rebuilt by the case builders."""
 import os
 import sys
 import types
@@ -181,8 +185,52 @@ def run_sgg_eval_sgdet(cfg, BoxList):
           "A lists", len(out["accuracy_hit_100"]))
 
 
+def run_cases(BoxList):
+    """decode_cases.npz: <case>__labels (the case's mode; launches and images concatenated) and, in "post", <case>__scores.
+    pairs_cases.npz: <case>__<instance>__pairs / __counts for the instances sgdet_cases.golden_pair_instances names."""
+    import sgdet_cases as sc
+    from pysgg.modeling.roi_heads.relation_head.sampling import RelationSampling
+    dec, pairs = {}, {}
+    for name in sc.GOLDEN_DECODE:
+        mode, = sc.decode_modes(name)
+        labels, scores = [], []
+        for imgs, thr in sc.decode_case(name):
+            for d in imgs:
+                post, meet, sco = ref_decode(d, thr, torch.float32)
+                p64, m64, _ = ref_decode(d, thr, torch.float64)
+                ref, ref64 = (post, p64) if mode == "post" else (meet, m64)
+                if mode == "post":     # (MEET: the fp64 softmax of a one-hot row has its own last-ulp pattern; the labels below decide)
+                    assert np.array_equal(ref, ref64), (name, "the reference's labels change in fp64")
+                labels.append(ref)
+                scores.append(sco)
+        dec[name + "__labels"] = np.concatenate(labels).astype(np.int64)
+        if mode == "post":
+            dec[name + "__scores"] = np.concatenate(scores).astype(np.float32)
+        print(name, dec[name + "__labels"][:24])
+    for name in sc.GOLDEN_PAIRS:
+        case = sc.pair_case(name)
+        for k in sc.golden_pair_instances(name):
+            imgs, cap, overlap = case[k]
+            samp = RelationSampling(0.5, False, 4, 1024, 0.25, cap, False, overlap)
+            props = []
+            for d in imgs:
+                b = BoxList(torch.from_numpy(d["boxes"]), d["image_size"], "xyxy")
+                b.add_field("pred_scores", torch.from_numpy(d["pred_scores"]))
+                props.append(b)
+            got = samp.prepare_test_pairs("cpu", props)
+            pairs["%s__%d__pairs" % (name, k)] = torch.cat(got).numpy().astype(np.int16)
+            pairs["%s__%d__counts" % (name, k)] = np.array([len(x) for x in got], np.int64)
+            print(name, k, "cap", cap, "overlap", overlap, "counts", [len(x) for x in got])
+    np.savez_compressed(os.path.join(OUT, "decode_cases.npz"), **dec)
+    np.savez_compressed(os.path.join(OUT, "pairs_cases.npz"), **pairs)
+    for f in ("decode_cases.npz", "pairs_cases.npz"):
+        print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
+
+
 def main():
     P, cfg, BoxList = import_reference()
+    if sys.argv[1:] == ["cases"]:
+        return run_cases(BoxList)
     os.makedirs(OUT, exist_ok=True)
     run_sgg_eval_sgdet(cfg, BoxList)
     for name in PRED_CASES:
