@@ -76,7 +76,12 @@ typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 
 // Saturating conversions (round 3, tools/micro/ovfl_probe.hip): with MODE.FP16_OVFL = 1 the f32 -> e4m3 conversions saturate at
 // +-448 (0x7e) instead of producing NaN, and f32 -> f16 saturates at +-65504 instead of Inf (measured on gfx950 for
-// v_cvt_scalef32_pk_fp8_f32, v_cvt_pk_fp8_f32 and v_cvt_f16_f32; a NaN stays a NaN).  Every kernel that writes mixed rows sets the
+// v_cvt_scalef32_pk_fp8_f32, v_cvt_pk_fp8_f32 and v_cvt_f16_f32; a NaN stays a NaN -- 0x7f | sign in e4m3 -- and a true +-Inf input stays
+// +-Inf in fp16 while its e4m3 planes become +-448 (Y) and NaN (X, the residual Inf - Inf)).  The bit reaches further than the
+// conversions: while it is set the matrix pipe (v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4 as the mixed GEMM issues
+// them) returns +0 for a dot product that holds a NaN: measured on gemm_split_ps_kernel, which therefore sets the bit only in the
+// instantiation that writes mixed rows (tests/test_operand_probes_gpu.py holds the others to NaN in, NaN out).  The fused launches set
+// it on entry and run their MFMAs under it; what they do with a non-finite row has not been measured.  Every kernel that writes mixed rows sets the
 // bit on entry (the mode is per wave), and the v_med3_f32 clamps in front of every conversion -- 8 of ~22 instructions per 4
 // values in the VALU-bound producers -- are gone.  -DVETO_FP16_OVFL=0 rebuilds the clamped form.
 #ifndef VETO_FP16_OVFL

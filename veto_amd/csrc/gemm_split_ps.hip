@@ -119,7 +119,11 @@ template <int NTERMS, int EPI_T, bool TN = false>
 __global__ __launch_bounds__(64 * (NCONS + NLOAD), 3) void gemm_split_ps_kernel(GemmArgs g) {
   constexpr bool kDrop = EPI_T == EPI_RESID_DROP;          // training-only instantiation: dropout before the residual add
   constexpr bool kMixed = NTERMS == 2;                     // fp16 + e4m3 operands (mixed rows)
-  if constexpr (kMixed) saturating_conversions_on();       // (only these instantiations can write mixed rows: the fc1 epilogue)
+  // Only the fc1 epilogue writes mixed rows.  The mode bit is not free for the others: with MODE.FP16_OVFL = 1 the matrix pipe returns
+  // +0 for a dot product that holds a NaN (an Inf activation included: its residual plane is Inf - Inf), so a launch that sets it
+  // turns a diverged row into zeros; without it the NaN reaches C (measured, profiles/operand_probes_parity.txt).  Finite results
+  // do not depend on the bit.
+  if constexpr (kMixed && EPI_T == EPI_GELU_SPLIT) saturating_conversions_on();
   static_assert(!(kMixed && TN), "the mixed-row format has no transposed (weight-gradient) form");
   constexpr bool kGeluBwd = EPI_T == EPI_GELU_BWD;         // training-only: the residual machinery reads the pre-activation, the result leaves as split rows
   constexpr int EPI = kDrop || kGeluBwd ? (int)EPI_RESID : EPI_T;
