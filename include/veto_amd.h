@@ -800,10 +800,26 @@ int veto_roi_pool(void* stream, const veto_roi_pool_args_t* args);
  * layers/roi_align.py:27-44): `args` describes the forward call (shapes, scales, rois; its feature / output
  * pointers are not read), grad_rgb / grad_depth are the gradients of the two pooled tensors, level_grad[l] /
  * depth_grad receive the map gradients (same shapes as the maps; ZERO-INITIALISED BY THE CALLER, accumulated
- * with atomic adds, so the summation order -- not the result up to rounding -- varies from run to run).
+ * with atomic adds, so the summation order -- not the result up to rounding -- varies from run to run;
+ * veto_roi_pool_backward_ordered below fixes the order).
  * grad_depth / depth_grad may be NULL. */
 int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
                            float* const* level_grad, float* depth_grad);
+
+/* The ordered sibling (the "ordered mode" of the training path, see veto_train_opts_t.deterministic): the same arguments and the
+ * same terms, gathered per map pixel instead of scattered, so the result is a pure function of the input bits, the library build
+ * and the device model.  EVERY element of every gradient map is written by the call (a pixel nothing touches gets +0): the
+ * caller zeroes nothing, and what the maps held before does not matter.
+ * For the pixel (image b, channel c, y, x) of a map the result is the float32 sequential sum, starting from +0, of
+ *     term = (g * w) / count       g = the pooled gradient of (ROI r, channel c, bin row ph, bin column pw),
+ *                                  w = the tap's bilinear weight (hy*hx, hy*lx, ly*hx, ly*lx for taps 0..3), count = sampling_ratio^2,
+ *                                  each operation rounded to float32 (no fused multiply-add), as in veto_roi_pool_backward,
+ * over (r, ph, pw, iy, ix, tap) in lexicographic order, restricted to the valid samples' taps that land on (y, x) and -- for a pyramid
+ * map -- to the ROIs of image b that the float32 LevelMapper of veto_roi_pool assigns to that level (the depth map takes every ROI of
+ * image b).  Taps that coincide at the far edge (low index == high index) both count, in tap order.
+ * Not promised: the bits of veto_roi_pool_backward (whose order varies), equality across library builds or device models. */
+int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
+                                   float* const* level_grad, float* depth_grad);
 
 /* ---- relation evaluators -----------------------------------------------
  * evaluate_relation_of_one_image (pysgg/data/datasets/evaluation/vg/vg_eval.py:459-566) over the evaluator
@@ -1121,9 +1137,37 @@ typedef struct veto_train_opts {
    * fp32 each.  The reference trains its depth backbone through roi_depth_features (tools/relation_train_net.py:166-170). */
   float* d_roi_rgb;
   float* d_roi_depth;
+  /* Ordered mode (0 = off: the default kernels, workspace and bits).  Read only when struct_size covers it: a caller built against
+   * the struct without this field passes the shorter struct_size and gets 0.  Both calls of a step must agree on it.
+   *
+   * With it on, every output of veto_forward_train and veto_backward (the logits, `grads`, d_roi_rgb / d_roi_depth) -- and of
+   * veto_roi_pool_backward_ordered for the map gradients -- is a pure function of
+   *     the input bits, the opts, the library build, and the device model:
+   * repeated calls give the same bits whatever the workspace held before and whatever runs on other streams.
+   * NOT promised: equality with the default path's bits, equality across library builds, equality across devices with another
+   * compute-unit count.
+   *
+   * Every float32 sum of the backward that the default path leaves to atomics has a stated order instead:
+   *   token assembly   dpatch[n, t, half] (and dlc, with the ReLU gate lc[subject] + lc[object] > 0 per term) = the float32 sequential
+   *                    sum, from +0, of the token-gradient rows dx[p * 19 + t] over the pairs p, in ascending row of the batch's pair
+   *                    list, whose subject (first half) / object (second half) is object n.  A pair listed twice counts twice; an object in
+   *                    no pair gets +0.
+   *   obj_embed        dE[label] = the float32 sequential sum, from +0, of the embedding-gradient rows over the object rows that carry the
+   *                    label, in ascending row.
+   *   LayerNorm        per block of 64 rows, the 8 row slots (slot s holds rows s, s + 8, ... of the block, added in that order) are added
+   *                    in slot order 0..7 from +0 -- dgamma / dbeta and, where the kernel emits them, the column sums of rows 0..31 and
+   *                    32..63 of the block; the per-block rows are folded in block order in double.
+   *   weight gradients split j of the reduction writes its float32 tile to partial plane j; the planes are added in split order in
+   *                    double and rounded once.  The split count is a function of the GEMM's shape (M, N, K) alone.
+   *   ROI pooling      see veto_roi_pool_backward_ordered.
+   * The workspace grows by the partial planes: size it with veto_train_workspace_bytes_opts. */
+  int32_t deterministic;
 } veto_train_opts_t;
 
+/* veto_train_workspace_bytes: the default path's need (unchanged by the ordered mode's existence); veto_train_workspace_bytes_opts: the
+ * need under `opts` (NULL = the default path) -- larger with opts->deterministic != 0. */
 size_t veto_train_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair);
+size_t veto_train_workspace_bytes_opts(veto_handle_t h, int32_t n_obj, int32_t n_pair, const veto_train_opts_t* opts);
 size_t veto_grad_floats(veto_handle_t h);
 int veto_weight_offset(veto_handle_t h, int index, size_t* offset_floats);
 int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
@@ -1136,6 +1180,11 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
 int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
                      int32_t k_splits, void* workspace, size_t workspace_bytes);
 size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits);
+/* The ordered form of the same GEMM: split j writes partial plane j (inside the workspace; every slot that is read is written by the
+ * call), the planes are folded in split order.  Same arguments; the workspace is larger by k_splits planes of [n, k] fp32. */
+int veto_debug_wgrad_ordered(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
+                             int32_t k_splits, void* workspace, size_t workspace_bytes);
+size_t veto_debug_wgrad_ordered_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits);
 
 /* ---- test hooks: backward building blocks of the transformer (chained by veto_backward) ----------------------
  * veto_debug_attention_backward: qkv, dqkv device [n_pair*19, 1728], dout device [n_pair*19, 576]   (model_veto.py:85-96)
@@ -1174,6 +1223,24 @@ int veto_debug_layernorm_backward_split(void* stream, const float* x, const floa
                                         float* dx, float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows,
                                         uint64_t drop_seed, uint32_t drop_thresh, float drop_scale, void* workspace,
                                         size_t workspace_bytes);
+
+
+/* ---- test hooks: the ordered forms (veto_train_opts_t.deterministic) of the backward's order-dependent sums, alone on caller-given buffers --
+ * veto_debug_assemble_backward_ordered: dx device [n_pair * 19, 576]; subj / obj device int32 [n_pair], batch-wide object rows; lc device
+ *   [n_obj, 2, 1152]; img_obj_offset / img_pair_offset device [n_img + 1] (the pairs of an image name objects of that image); out dpatch
+ *   [n_obj, 16, 1152] and dlc [n_obj, 2, 1152], every element written.
+ * veto_debug_scatter_rows_ordered: demb device [n, dim], labels device int64 [n]; out dtable [n_table_rows, dim], every element written.
+ * veto_debug_layernorm_backward_ordered: veto_debug_layernorm_backward_split in the ordered form; split_rows and col_partials may both be
+ *   NULL (the form without them). */
+int veto_debug_assemble_backward_ordered(void* stream, const float* dx, const int32_t* subj, const int32_t* obj, const float* lc,
+                                         const int32_t* img_obj_offset, const int32_t* img_pair_offset, int32_t n_img, int32_t n_obj,
+                                         float* dpatch, float* dlc);
+int veto_debug_scatter_rows_ordered(void* stream, const float* demb, const int64_t* labels, int32_t n, int32_t dim, int32_t n_table_rows,
+                                    float* dtable);
+int veto_debug_layernorm_backward_ordered(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
+                                          float* dx, float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows,
+                                          uint64_t drop_seed, uint32_t drop_thresh, float drop_scale, void* workspace,
+                                          size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

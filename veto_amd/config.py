@@ -96,4 +96,8 @@ def default_config():
     # has the distribution of the reference's gtbox_relsample but not its draws for a given seed, and needs no samp_processor;
     # False: the head uses the host code base's sampler (or an explicit one) as before
     c.VETO_AMD.DEVICE_GTBOX_RELSAMPLE = False
+    # True: the training step runs in the "ordered" mode (include/veto_amd.h, veto_train_opts_t.deterministic): every gradient sum
+    # has a fixed order, so two steps from one state and one seed give the same bits.  Also on under
+    # torch.use_deterministic_algorithms(True) and with VETO_DETERMINISTIC=1 in the environment.  Other bits than the default; more workspace.
+    c.VETO_AMD.DETERMINISTIC = False
     return c

@@ -648,8 +648,8 @@ int veto_roi_pool(void* stream, const veto_roi_pool_args_t* a) {
   return VETO_OK;
 }
 
-int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
-                           float* const* level_grad, float* depth_grad) {
+static int roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
+                             float* const* level_grad, float* depth_grad, bool ordered) {
   RoiPoolArgs p{};
   ABI_TRY(roi_pool_args(a, false, &p));
   if (!grad_rgb || !level_grad) return fail(VETO_ERR_INVALID, "missing gradient pointer");
@@ -662,8 +662,19 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const fl
   if (grad_depth) p.depth.feat = grad_depth;   // only its non-null-ness and the sizes are used
   else p.depth.feat = nullptr;
   p.gout_rgb = grad_rgb; p.gout_depth = grad_depth; p.depth_grad = depth_grad;
-  HIP_TRY(launch_roi_pool_backward(p, (hipStream_t)stream));
+  if (ordered) HIP_TRY(launch_roi_pool_backward_ordered(p, a->n_img, (hipStream_t)stream));
+  else HIP_TRY(launch_roi_pool_backward(p, (hipStream_t)stream));
   return VETO_OK;
+}
+
+int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
+                           float* const* level_grad, float* depth_grad) {
+  return roi_pool_backward(stream, a, grad_rgb, grad_depth, level_grad, depth_grad, false);
+}
+
+int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
+                                   float* const* level_grad, float* depth_grad) {
+  return roi_pool_backward(stream, a, grad_rgb, grad_depth, level_grad, depth_grad, true);
 }
 
 // workspace: label_tmp | flag_tmp | flag_before | pair_score | row_key | acc_first | cls_table

@@ -37,6 +37,9 @@ struct TrainWs {
   __bf16* wcat_t;   // Wcat^T [2112, 2*1152] split rows: weight operand of the patch projection's input gradient
   float* dpa;       // dPA [prow, 2112] fp32: gradient w.r.t. the patch rows
   size_t mp2;    // padded reduction length of the weight-gradient GEMMs
+  // ordered mode (veto_train_opts_t.deterministic) only, behind everything else so that the default layout and size stay what they were:
+  // the split-K partial planes of the weight-gradient GEMMs, [k_splits][N][K] fp32 of the largest call; nullptr = the default (atomic) path
+  float* planes;
   size_t total;
 };
 
@@ -72,7 +75,23 @@ bool train_ln_emits_split() {
   return on;
 }
 
-TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair) {
+int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps = 64);
+
+// the Linears of a layer and the patch projection, as (N, K) of their weight-gradient GEMMs: the ordered mode's planes hold the largest
+size_t wgrad_plane_floats(int m_tokens, int patch_rows) {
+  size_t most = 0;
+  auto take = [&](int n, int k, int m, int min_ksteps) {
+    int ks = wgrad_splits(n, k, m, 0, min_ksteps);
+    if (ks > 64) ks = 64;
+    const size_t need = (size_t)ks * n * k;
+    if (need > most) most = need;
+  };
+  for (const LayerLinear& q : kLayerLinears) take(q.N, q.K, m_tokens, 64);      // (the last layer's compact rows are fewer: no more splits)
+  take(2048, 2 * kDim, patch_rows, 8);
+  return most;
+}
+
+TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ordered = false) {
   TrainWs w;
   Carver c{base};
   const int L = h->cfg.layers, E = h->cfg.embed_dim;
@@ -138,13 +157,14 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair) {
   w.dwcat_t = c.take<float>((size_t)2048 * 2 * kDim * 4);
   w.wcat_t = c.take<__bf16>((size_t)kPatchTRows * 2 * 2 * kDim * 2);
   w.dpa = c.take<float>((size_t)gemm_rows_padded(n_obj * 16) * kPatchTRows * 4);
+  w.planes = ordered ? c.take<float>(wgrad_plane_floats((int)M, n_obj * 16) * 4) : nullptr;
   w.total = c.off;
   return w;
 }
 
 // dw[N,K] = dy[M,N]^T . x[M,K]: the weight-gradient shape (reduction over the M rows).  Both operands are
 // transposed into split rows ([N, 2*Mp] and [K, 2*Mp]) and the persistent GEMM runs split-K with atomic adds.
-int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps = 64) {
+int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps) {
   if (k_splits > 0) return k_splits;
   const int out_tiles = ((n + 255) / 256) * (k / 192);
   int ks = 2 * 256 / out_tiles;                         // just under 2 full rounds of the 256 persistent workgroups
@@ -176,14 +196,15 @@ int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const 
   if (mp > w.mp2) return fail(VETO_ERR_WORKSPACE, "weight-gradient partial buffer too small");
   if (dy) HIP_TRY(launch_prep_grad(dy, N, M, N, w.dsplit, (int)mp, db ? w.colp : nullptr, xf, s));
   if (db) HIP_TRY(launch_column_sums(w.colp, N, dy ? (int)(mp / 32) : presplit_partials, N, db, w.col_partial, column_sums_chunks(), s));
-  HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
+  if (!w.planes) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
   {
     GemmArgs g{};
-    g.a = gsplit; g.w = x_split; g.c = dw;
+    g.a = gsplit; g.w = x_split; g.c = w.planes ? w.planes : dw;
     g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
     g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = M; g.zero = w.zero;
     ProfScope ps(h, s, "bwd_wgrad", 2.0 * M * (double)N * K, 0);
-    HIP_TRY(launch_gemm_split(g, EPI_ATOMIC, 0, s));
+    HIP_TRY(launch_gemm_split(g, w.planes ? EPI_PLANES : EPI_ATOMIC, 0, s));
+    if (w.planes) HIP_TRY(launch_fold_rows(w.planes, (long)N * K, ks, (long)N * K, dw, s));      // the planes in split order
   }
   HIP_TRY(launch_transpose_split(weight, K, N, K, w.wdg, N, s));     // W [N, K] -> W^T split rows [K, 2N]
   {
@@ -218,15 +239,21 @@ DropSite drop_site(const veto_train_opts_t* o, int site, int row_step = 1) {
   return d;
 }
 
+// `deterministic` was appended to veto_train_opts_t: a caller built against the struct without it passes the shorter size and gets 0
+constexpr int32_t kTrainOptsSizeV1 = (int32_t)offsetof(veto_train_opts_t, deterministic);
+
+bool opts_ordered(const veto_train_opts_t* o) { return o && o->struct_size == (int32_t)sizeof(veto_train_opts_t) && o->deterministic != 0; }
+
 int check_train_opts(const veto_train_opts_t* o) {
   if (!o) return VETO_OK;
-  CHECK_STRUCT(veto_train_opts_t, o);
+  if (o->struct_size != (int32_t)sizeof(veto_train_opts_t) && o->struct_size != kTrainOptsSizeV1)
+    return fail(VETO_ERR_INVALID, "veto_train_opts_t size mismatch");
   for (float p : {o->p_pos, o->p_emb, o->p_attn})
     if (!(p >= 0.f && p < 1.f)) return fail(VETO_ERR_INVALID, "dropout probabilities must be in [0, 1)");
   return VETO_OK;
 }
 
-int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, void* workspace, size_t workspace_bytes) {
+int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace, size_t workspace_bytes) {
   CHECK_STRUCT_AND(veto_inputs_t, in, h && workspace);
   if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch");
   if (!in->roi_rgb || !in->roi_depth || !in->boxes || !in->rel_pairs || !in->img_obj_offset || !in->img_pair_offset)
@@ -234,7 +261,9 @@ int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, void* workspace
   if (!in->obj_labels && !in->obj_logits) return fail(VETO_ERR_INVALID, "neither obj_labels nor obj_logits given");
   if (!in->bn_batch_stats) return fail(VETO_ERR_INVALID, "the training path needs bn_batch_stats (training-mode BatchNorm)");
   if (h->cfg.precision == VETO_FAST) return fail(VETO_ERR_INVALID, "the training path runs on split-bf16 operands (precise / mixed handles) only");
-  if (workspace_bytes < veto_train_workspace_bytes(h, in->n_obj, in->n_pair)) return fail(VETO_ERR_WORKSPACE, "training workspace too small");
+  ABI_TRY(check_train_opts(opts));
+  if (workspace_bytes < carve_train(nullptr, h, in->n_obj, in->n_pair, opts_ordered(opts)).total)
+    return fail(VETO_ERR_WORKSPACE, opts_ordered(opts) ? "training workspace too small (ordered mode: veto_train_workspace_bytes_opts)" : "training workspace too small");
   return VETO_OK;
 }
 
@@ -247,10 +276,14 @@ size_t veto_train_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair
   return carve_train(nullptr, h, n_obj, n_pair).total;
 }
 
+size_t veto_train_workspace_bytes_opts(veto_handle_t h, int32_t n_obj, int32_t n_pair, const veto_train_opts_t* opts) {
+  if (!h || n_obj <= 0 || n_pair <= 0 || check_train_opts(opts) != VETO_OK) return 0;
+  return carve_train(nullptr, h, n_obj, n_pair, opts_ordered(opts)).total;
+}
+
 int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
                        size_t workspace_bytes, float* out_logits) {
-  ABI_TRY(check_train_inputs(h, in, workspace, workspace_bytes));
-  ABI_TRY(check_train_opts(opts));
+  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes));
   if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -258,7 +291,7 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
   h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
   const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out;
   const int M = n_pair * kTokens;
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair);
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, opts_ordered(opts));
   HIP_TRY(launch_pair_indices(in->rel_pairs, in->img_obj_offset, in->img_pair_offset, in->n_img, n_pair, ws.subj, ws.obj, nullptr,
                               nullptr, s));
   {
@@ -325,8 +358,7 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
 
 int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
                   size_t workspace_bytes, const float* dlogits, float* grads) {
-  ABI_TRY(check_train_inputs(h, in, workspace, workspace_bytes));
-  ABI_TRY(check_train_opts(opts));
+  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes));
   if (!dlogits || !grads) return fail(VETO_ERR_INVALID, "null gradient pointer");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
@@ -341,7 +373,8 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
   }
   const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out, E = h->cfg.embed_dim;
   const int M = n_pair * kTokens;
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair);
+  const bool ordered = opts_ordered(opts);
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, ordered);
   const std::string T = kT;
   auto G = [&](const std::string& name) { return grads + h->params[h->index.at(name)].offset; };
   struct LinGrad { const float* w; float *dw, *db; int N, K; };      // a layer's Linear (kLayerLinears): weight, its and the bias's gradient
@@ -390,9 +423,9 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     const bool ln_split = train_ln_emits_split();
     if (ln_split)
       HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, ws.dsplit, ws.colp,
-                                        dsite.seed, dsite.thresh, dsite.scale, dsite.row_step));
+                                        dsite.seed, dsite.thresh, dsite.scale, dsite.row_step, ordered));
     else
-      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s));
+      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, nullptr, nullptr, 0, 0, 1.f, 1, ordered));
     HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.bias")), ws.dgb + kDim, kDim * 4, hipMemcpyDeviceToDevice, s));
     GradXform drop;
@@ -418,10 +451,10 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     ABI_TRY(run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, ws.dtmp));
     // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
     if (ln_split && l > 0) {      // (its result is the gradient matrix of fc2 of the layer below)
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, ws.dsplit, ws.colp));
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, ws.dsplit, ws.colp, 0, 0, 1.f, 1, ordered));
       dx_presplit = layernorm_backward_col_partials(M);
     } else {
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s));
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, nullptr, nullptr, 0, 0, 1.f, 1, ordered));
       dx_presplit = 0;
     }
     HIP_TRY(hipMemcpyAsync(G(lname(l, "0.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
@@ -437,9 +470,14 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
   }
   HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, G(T + "pos_embedding"), ws.col_partial, column_sums_chunks(), s));
   HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, G(T + "cls_token"), ws.col_partial, column_sums_chunks(), s));
-  HIP_TRY(hipMemsetAsync(ws.dpatch, 0, (size_t)n_obj * 16 * 2 * kDim * 4, s));
-  HIP_TRY(hipMemsetAsync(ws.dlc, 0, (size_t)n_obj * 2 * 2 * kDim * 4, s));
-  HIP_TRY(launch_assemble_backward(ws.dx, ws.subj, ws.obj, ws.lc, ws.dpatch, ws.dlc, n_pair, s));
+  if (ordered) {
+    HIP_TRY(launch_assemble_backward_ordered(ws.dx, ws.subj, ws.obj, ws.lc, in->img_obj_offset, in->img_pair_offset, in->n_img, ws.dpatch,
+                                             ws.dlc, n_obj, s));
+  } else {
+    HIP_TRY(hipMemsetAsync(ws.dpatch, 0, (size_t)n_obj * 16 * 2 * kDim * 4, s));
+    HIP_TRY(hipMemsetAsync(ws.dlc, 0, (size_t)n_obj * 2 * 2 * kDim * 4, s));
+    HIP_TRY(launch_assemble_backward(ws.dx, ws.subj, ws.obj, ws.lc, ws.dpatch, ws.dlc, n_pair, s));
+  }
 
   // ---- patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half) ------------------------
   {
@@ -452,12 +490,13 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       const int ks = wgrad_splits(N, K, R, 0, 8);      // (few object rows: tiles of 8 k-steps already)
       const size_t mp = wgrad_mp(R, ks);
       HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, K, s));
-      HIP_TRY(hipMemsetAsync(ws.dwcat_t, 0, (size_t)N * K * 4, s));
+      if (!ordered) HIP_TRY(hipMemsetAsync(ws.dwcat_t, 0, (size_t)N * K * 4, s));
       GemmArgs g{};
-      g.a = ws.pa; g.w = ws.dsplit; g.c = ws.dwcat_t;
+      g.a = ws.pa; g.w = ws.dsplit; g.c = ordered ? ws.planes : ws.dwcat_t;
       g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
       g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = R; g.zero = ws.zero;
-      HIP_TRY(launch_gemm_split(g, EPI_ATOMIC, 0, s));
+      HIP_TRY(launch_gemm_split(g, ordered ? EPI_PLANES : EPI_ATOMIC, 0, s));
+      if (ordered) HIP_TRY(launch_fold_rows(ws.planes, (long)N * K, ks, (long)N * K, ws.dwcat_t, s));
     }
     HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
     // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
@@ -515,6 +554,7 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
     HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, ldlc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
     if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, G("obj_embed.weight"), E, n_obj, C_obj, E, s));
+    else if (ordered) HIP_TRY(launch_scatter_rows_ordered(ws.demb, in->obj_labels, E, G("obj_embed.weight"), n_obj, C_obj, s));
     else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, G("obj_embed.weight"), n_obj, s));
   }
   return VETO_OK;
@@ -568,33 +608,56 @@ int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint3
 // n % 32 == 0 (every Linear of the transformer): the row-major form, both operands as the split rows the backward holds
 // anyway, transposed on their way out of LDS (GemmArgs::tn), one row more than m each (partial tiles read, never use, the row behind
 // the last) and the zero row of GemmArgs::zero.  Otherwise: explicit transposed split copies, dy's padded to whole row tiles.
-struct WgradWs { __bf16 *a, *w, *zero; size_t total; };
-static WgradWs carve_wgrad(Carver c, int m, int n, int k, int k_splits) {      // (a braced list evaluates left to right)
-  if (n % 32 == 0) return WgradWs{c.take<__bf16>(((size_t)m + 1) * n * 4), c.take<__bf16>(((size_t)m + 1) * k * 4), c.take<__bf16>(1024), c.off};
-  const size_t mp = wgrad_mp(m, wgrad_splits(n, k, m, k_splits));
-  return WgradWs{c.take<__bf16>((size_t)gemm_rows_padded(n) * mp * 4), c.take<__bf16>((size_t)k * mp * 4), nullptr, c.off};
+// ordered: behind the operands, the k_splits partial planes [n, k] fp32 of the ordered form (operand bytes: the size of the default form)
+struct WgradWs { __bf16 *a, *w, *zero; size_t operand_bytes; float* planes; size_t total; };
+static WgradWs carve_wgrad(Carver c, int m, int n, int k, int k_splits, bool ordered = false) {      // (a braced list evaluates left to right)
+  const int ks = wgrad_splits(n, k, m, k_splits);
+  const size_t plane_bytes = ordered ? (size_t)ks * n * k * 4 : 0;
+  if (n % 32 == 0) return WgradWs{c.take<__bf16>(((size_t)m + 1) * n * 4), c.take<__bf16>(((size_t)m + 1) * k * 4), c.take<__bf16>(1024), c.off,
+                                  ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
+  const size_t mp = wgrad_mp(m, ks);
+  return WgradWs{c.take<__bf16>((size_t)gemm_rows_padded(n) * mp * 4), c.take<__bf16>((size_t)k * mp * 4), nullptr, c.off,
+                 ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
 }
+
+static int debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k, int32_t k_splits,
+                       void* workspace, size_t workspace_bytes, bool ordered);
 
 size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
   return carve_wgrad(Carver{nullptr}, m, n, k, k_splits).total;
 }
 
+size_t veto_debug_wgrad_ordered_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits, true).total;
+}
+
 int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
                      int32_t k_splits, void* workspace, size_t workspace_bytes) {
+  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, false);
+}
+
+int veto_debug_wgrad_ordered(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
+                             int32_t k_splits, void* workspace, size_t workspace_bytes) {
+  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, true);
+}
+
+static int debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k, int32_t k_splits,
+                       void* workspace, size_t workspace_bytes, bool ordered) {
   if (!dy || !x || !dw || !workspace) return fail(VETO_ERR_INVALID, "null argument");
   if (m <= 0 || n <= 0 || k <= 0 || k % 192 != 0) return fail(VETO_ERR_INVALID, "k must be a positive multiple of 192");
-  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_debug_wgrad_workspace_bytes(m, n, k, k_splits), false));
-  const WgradWs ws = carve_wgrad(Carver{(char*)workspace}, m, n, k, k_splits);
+  const WgradWs ws = carve_wgrad(Carver{(char*)workspace}, m, n, k, k_splits, ordered);
+  ABI_TRY(check_workspace(workspace, workspace_bytes, ws.total, false));
   hipStream_t s = (hipStream_t)stream;
   const int ks = wgrad_splits(n, k, m, k_splits);
   const size_t mp = wgrad_mp(m, ks);
-  HIP_TRY(hipMemsetAsync(dw, 0, (size_t)n * k * 4, s));
+  if (!ordered) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)n * k * 4, s));
   GemmArgs g{};
-  g.a = ws.a; g.w = ws.w; g.c = dw;
+  g.a = ws.a; g.w = ws.w; g.c = ordered ? ws.planes : dw;
   g.M = n; g.N = k; g.K = (int)mp; g.ldc = k; g.k_splits = ks;
   if (n % 32 == 0) {
-    HIP_TRY(hipMemsetAsync(ws.a, 0, ws.total, s));   // the row behind the last one is read (never used) by partial tiles
+    HIP_TRY(hipMemsetAsync(ws.a, 0, ws.operand_bytes, s));   // the row behind the last one is read (never used) by partial tiles
     HIP_TRY(launch_split_rows(dy, ws.a, (size_t)m, n, s));
     HIP_TRY(launch_split_rows(x, ws.w, (size_t)m, k, s));
     g.tn = 1; g.lda = 2 * (long)n; g.ldw = 2 * (long)k; g.k_valid = m;
@@ -604,8 +667,9 @@ int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, i
     HIP_TRY(launch_transpose_split(dy, n, m, n, ws.a, (int)mp, s));
     HIP_TRY(launch_transpose_split(x, k, m, k, ws.w, (int)mp, s));
   }
-  hipError_t e = launch_gemm_split(g, EPI_ATOMIC, 0, s);
+  hipError_t e = launch_gemm_split(g, ordered ? EPI_PLANES : EPI_ATOMIC, 0, s);
   if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "wgrad gemm launch failed: %s", hipGetErrorString(e));
+  if (ordered) HIP_TRY(launch_fold_rows(ws.planes, (long)n * k, ks, (long)n * k, dw, s));
   return VETO_OK;
 }
 
@@ -652,6 +716,34 @@ int veto_debug_layernorm_backward_split(void* stream, const float* x, const floa
   if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
   HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
                                     col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale));
+  return VETO_OK;
+}
+
+int veto_debug_layernorm_backward_ordered(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
+                                          float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
+                                          uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (!split_rows != !col_partials) return fail(VETO_ERR_INVALID, "split_rows and col_partials go together");
+  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
+                                    col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale, 1, true));
+  return VETO_OK;
+}
+
+int veto_debug_assemble_backward_ordered(void* stream, const float* dx, const int32_t* subj, const int32_t* obj, const float* lc,
+                                         const int32_t* img_obj_offset, const int32_t* img_pair_offset, int32_t n_img, int32_t n_obj,
+                                         float* dpatch, float* dlc) {
+  if (!dx || !subj || !obj || !lc || !img_obj_offset || !img_pair_offset || !dpatch || !dlc || n_img <= 0 || n_obj <= 0)
+    return fail(VETO_ERR_INVALID, "bad argument");
+  HIP_TRY(launch_assemble_backward_ordered(dx, subj, obj, lc, img_obj_offset, img_pair_offset, n_img, dpatch, dlc, n_obj, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_debug_scatter_rows_ordered(void* stream, const float* demb, const int64_t* labels, int32_t n, int32_t dim, int32_t n_table_rows,
+                                    float* dtable) {
+  if (!demb || !labels || !dtable || n <= 0 || dim <= 0 || n_table_rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  HIP_TRY(launch_scatter_rows_ordered(demb, labels, dim, dtable, n, n_table_rows, (hipStream_t)stream));
   return VETO_OK;
 }
 

@@ -464,7 +464,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // operand of that Linear's two gradient GEMMs) and the column sums of every 32 rows (its bias gradient's partials, [rows / 32, 576]) leave
 // from here, with the forward's dropout mask applied where the Linear's output was dropped (drop_thresh != 0: the attention out
 // projection) -- the preparation pass that read the matrix back (train.hip, prep_grad_kernel) is gone for these Linears.
-template <bool SPLIT>
+// ORDERED (veto_train_opts_t.deterministic): the 8 row slots do not meet through LDS float atomics, whose order the hardware picks, but through
+// a staged LDS array [slot][column] that one thread per column adds in slot order 0..7 from +0; the SPLIT column sums of the two 32-row
+// groups likewise.  dx and the split rows are the same bits in both forms.
+template <bool SPLIT, bool ORDERED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void layernorm_backward_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                  const float* __restrict__ gamma, const float* dres,
                                                                  float* dx, float* __restrict__ partial, int rows,      // dres may be dx
@@ -472,6 +475,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                                                                  unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step) {
   __shared__ float s_dg[kDim], s_db[kDim], s_w[kDim];
   __shared__ float s_cs[SPLIT ? 2 : 1][SPLIT ? kDim : 1];
+  __shared__ float s_stage[ORDERED ? kLnSlots : 1][ORDERED ? kDim : 1];
+  const int slot = threadIdx.x / kLnLanes;
+  // ORDERED: every thread of the block calls this at the same point (it holds barriers); dst[c] = sum over the slots, in slot order
+  auto meet_ordered = [&](const f32x2 (&acc)[9], float* dst) {
+    if constexpr (ORDERED) {
+#pragma unroll
+      for (int j = 0; j < 9; ++j) *(f32x2*)&s_stage[slot][2 * ((threadIdx.x & (kLnLanes - 1)) + kLnLanes * j)] = acc[j];
+      __syncthreads();
+      for (int c = threadIdx.x; c < kDim; c += 256) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < kLnSlots; ++k) t += s_stage[k][c];
+        dst[c] = t;
+      }
+      __syncthreads();
+    }
+  };
   for (int c = threadIdx.x; c < kDim; c += 256) {
     s_dg[c] = 0.f; s_db[c] = 0.f; s_w[c] = gamma[c];
     if (SPLIT) { s_cs[0][c] = 0.f; s_cs[SPLIT ? 1 : 0][c] = 0.f; }
@@ -496,7 +516,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   }
   // (SPLIT: the column sums of rows 0..31 and 32..63 of the block are flushed behind iterations 3 and 7)
   auto flush_cs = [&](int grp) {
-    if constexpr (SPLIT) {
+    if constexpr (SPLIT && ORDERED) {
+      meet_ordered(acc_c, s_cs[grp]);
+#pragma unroll
+      for (int j = 0; j < 9; ++j) acc_c[j] = f32x2{0.f, 0.f};
+    } else if constexpr (SPLIT) {
 #pragma unroll
       for (int j = 0; j < 9; ++j)
 #pragma unroll
@@ -508,10 +532,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   };
   for (int it = 0; it < kLnRowsPerBlock / kLnSlots; ++it) {
     const int row = blockIdx.x * kLnRowsPerBlock + it * kLnSlots + threadIdx.x / kLnLanes;
-    if (row >= rows) {      // uniform per half wave
+    if (!ORDERED && row >= rows) {      // uniform per half wave
       if (SPLIT && (it & 3) == 3) flush_cs(it >> 2);
       continue;
     }
+    if (row < rows) {      // (always true behind the `continue`; ORDERED: the flush below holds barriers, so every thread walks every iteration)
     const float* xr = x + (size_t)row * kDim;
     const float* gr = dy + (size_t)row * kDim;
     f32x2 xv[9], gv[9];
@@ -569,16 +594,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         *(bf16x2*)(d + 32) = bf16x2{l0, l1};
       }
     }
+    }
     if (SPLIT && (it & 3) == 3) flush_cs(it >> 2);
   }
+  if constexpr (ORDERED) {
+    meet_ordered(acc_g, s_dg);
+    meet_ordered(acc_b, s_db);
+  } else {
 #pragma unroll
-  for (int j = 0; j < 9; ++j)
+    for (int j = 0; j < 9; ++j)
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int c = 2 * (q + kLnLanes * j) + e;
-      atomicAdd(&s_dg[c], acc_g[j][e]);    // kLnSlots row slots per column, once per block
-      atomicAdd(&s_db[c], acc_b[j][e]);
-    }
+      for (int e = 0; e < 2; ++e) {
+        const int c = 2 * (q + kLnLanes * j) + e;
+        atomicAdd(&s_dg[c], acc_g[j][e]);    // kLnSlots row slots per column, once per block
+        atomicAdd(&s_db[c], acc_b[j][e]);
+      }
+  }
   __syncthreads();
   float* pr = partial + (size_t)blockIdx.x * 2 * kDim;
   for (int c = threadIdx.x; c < kDim; c += 256) { pr[c] = s_dg[c]; pr[kDim + c] = s_db[c]; }
@@ -691,10 +722,13 @@ int layernorm_backward_col_partials(int rows) { return (rows + kLnRowsPerBlock -
 
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
                                      float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out, float* colp,
-                                     unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step) {
+                                     unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step, bool ordered) {
   const int blocks = (rows + kLnRowsPerBlock - 1) / kLnRowsPerBlock;
   if (!split_out != !colp) return hipErrorInvalidValue;
-  if (split_out) VETO_LAUNCH(layernorm_backward_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
+  if (ordered && split_out) VETO_LAUNCH((layernorm_backward_kernel<true, true>), dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
+                                        drop_seed, drop_thresh, drop_scale, drop_row_step);
+  else if (ordered) VETO_LAUNCH((layernorm_backward_kernel<false, true>), dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
+  else if (split_out) VETO_LAUNCH(layernorm_backward_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
                              drop_seed, drop_thresh, drop_scale, drop_row_step);
   else VETO_LAUNCH(layernorm_backward_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
   hipError_t e = hipGetLastError();
@@ -710,6 +744,12 @@ hipError_t launch_column_sums(const float* dy, long ld, int rows, int n_cols, fl
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   VETO_LAUNCH(fold_rows_kernel, dim3((n_cols + 31) / 32), dim3(256), 0, s, partial, (long)n_cols, n_chunks, n_cols, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_fold_rows(const float* src, long ld, int n_rows, long n_cols, float* out, hipStream_t s) {
+  if (n_rows <= 0 || n_cols <= 0 || n_cols > 0x7fffffffL) return hipErrorInvalidValue;
+  VETO_LAUNCH(fold_rows_kernel, dim3((unsigned)((n_cols + 31) / 32)), dim3(256), 0, s, src, ld, n_rows, (int)n_cols, out);
   return hipGetLastError();
 }
 

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(64 * (NCONS + NLOAD), 3) void gemm_split_ps_kernel(
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.x;
-  const int ksp = EPI == EPI_ATOMIC && g.k_splits > 1 ? g.k_splits : 1;
+  const int ksp = (EPI == EPI_ATOMIC || EPI == EPI_PLANES) && g.k_splits > 1 ? g.k_splits : 1;
   const int out_tiles = g.tiles_m * g.tiles_n;
   const int ntiles = out_tiles * ksp;        // split-K: (k range, output tile), output tile fastest
   const int K = g.K;
@@ -515,6 +515,8 @@ __global__ __launch_bounds__(64 * (NCONS + NLOAD), 3) void gemm_split_ps_kernel(
             float* dstc = g.c + (size_t)row * g.ldc + col;
 #pragma unroll
             for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dstc + e, v[e]);
+          } else if (EPI == EPI_PLANES) {   // ordered weight gradient: k range j owns plane j; a fixed-order fold over the planes follows
+            *(f32x4*)(g.c + ((size_t)(tile_of(it) / out_tiles) * g.M + row) * g.ldc + col) = v;
           } else if (EPI == EPI_RESID) {
             acc[n][m] = v;    // (training, dropout form) stored below, after the last residual load
           } else if (EPI == EPI_F24) {
@@ -614,6 +616,12 @@ hipError_t launch_ps_terms(GemmArgs g, int epi, int nblocks, hipStream_t s) {
       if (g.tn) VETO_LAUNCH((gemm_split_ps_kernel<NTERMS, EPI_ATOMIC, true>), grid, block, 0, s, g);
       else VETO_LAUNCH((gemm_split_ps_kernel<NTERMS, EPI_ATOMIC>), grid, block, 0, s, g);
       break;
+    case EPI_PLANES:
+      if constexpr (NTERMS == 3) {
+        if (g.tn) VETO_LAUNCH((gemm_split_ps_kernel<NTERMS, EPI_PLANES, true>), grid, block, 0, s, g);
+        else VETO_LAUNCH((gemm_split_ps_kernel<NTERMS, EPI_PLANES>), grid, block, 0, s, g);
+        break;
+      } else return hipErrorInvalidValue;
     case EPI_RESID_DROP: VETO_LAUNCH((gemm_split_ps_kernel<NTERMS, EPI_RESID_DROP>), grid, block, 0, s, g); break;
     default: return hipErrorInvalidValue;
   }
@@ -639,12 +647,13 @@ hipError_t launch_gemm_split_ps(GemmArgs g, int epi, int precision, hipStream_t 
   if (num_cu < 1) return hipErrorInvalidDevice;
   num_cu = num_cu / 8 * 8;
   if (num_cu < 8) num_cu = 8;
-  const int ksp = epi == EPI_ATOMIC && g.k_splits > 1 ? g.k_splits : 1;
+  const bool split_k = epi == EPI_ATOMIC || epi == EPI_PLANES;
+  const int ksp = split_k && g.k_splits > 1 ? g.k_splits : 1;
   if ((g.K / BK) % ksp != 0) return hipErrorInvalidValue;
   if (g.kb_tiles > 0 && (ksp != 1 || g.tn || g.fmt == FMT_MIXED || g.kb_steps <= 0 || g.tiles_n % g.kb_tiles != 0 ||
                          (g.tiles_n / g.kb_tiles) * g.kb_steps != g.K / BK))
     return hipErrorInvalidValue;
-  if (g.tn && (epi != EPI_ATOMIC || !g.zero || g.lda <= 0 || g.ldw <= 0 || g.k_valid <= 0 || g.k_valid > g.K)) return hipErrorInvalidValue;
+  if (g.tn && (!split_k || !g.zero || g.lda <= 0 || g.ldw <= 0 || g.k_valid <= 0 || g.k_valid > g.K)) return hipErrorInvalidValue;
   const int ntiles = g.tiles_m * g.tiles_n * ksp;
   int nblocks = num_cu;  // one persistent workgroup per CU (LDS: 112 KiB each)
   if (ntiles < nblocks) nblocks = (ntiles + 7) / 8 * 8;

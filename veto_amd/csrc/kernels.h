@@ -4,7 +4,7 @@
 
 namespace veto {
 
-enum Epi { EPI_F32 = 0, EPI_RESID = 1, EPI_GELU_SPLIT = 2, EPI_ATOMIC = 3, EPI_RESID_DROP = 4, EPI_F24 = 5, EPI_SPLIT = 6, EPI_PRE_GELU = 7, EPI_GELU_BWD = 8 };   // EPI_F24: EPI_F32 written as 3-byte floats (common.h); EPI_SPLIT: split rows, no activation; EPI_PRE_GELU (training, split rows): the fp32 pre-activation to c (row stride ldc_f32) AND exact-erf gelu of it as split rows to c_split
+enum Epi { EPI_F32 = 0, EPI_RESID = 1, EPI_GELU_SPLIT = 2, EPI_ATOMIC = 3, EPI_RESID_DROP = 4, EPI_F24 = 5, EPI_SPLIT = 6, EPI_PRE_GELU = 7, EPI_GELU_BWD = 8, EPI_PLANES = 9 };   // EPI_F24: EPI_F32 written as 3-byte floats (common.h); EPI_SPLIT: split rows, no activation; EPI_PRE_GELU (training, split rows): the fp32 pre-activation to c (row stride ldc_f32) AND exact-erf gelu of it as split rows to c_split
 
 // C[M,N] = A[M,K] . W[N,K]^T with A and W in the split-row format (common.h): rows of 2K bf16.
 struct GemmArgs {
@@ -25,6 +25,8 @@ struct GemmArgs {
   float* col_partial;
   int k_splits;          // EPI_ATOMIC: the reduction K is cut into this many equal ranges (K/32 % k_splits == 0), each a
                          // tile of its own that ADDS into c with fp32 atomics (c zero-initialised); 0/1 = one range
+                         // EPI_PLANES (the ordered weight gradient): the same ranges, but range j WRITES its tile with plain stores to
+                         // plane j = c + j * M * ldc; every element of all k_splits planes is written; launch_fold_rows adds them in order
   // EPI_RESID_DROP (training only): EPI_RESID with dropout on (A.W^T + bias) before the residual is added; element (row, col) uses index
   // (row * drop_row_step) * N + col of site drop_seed.  drop_thresh = p * 2^24 (0 = off), drop_scale = 1 / (1 - p); drop_row_step: 1, or 19
   // where the rows are the compact CLS rows of the last layer (row p = token row 19 p: the numbering of include/veto_amd.h)
@@ -33,7 +35,7 @@ struct GemmArgs {
   float drop_scale;
   int drop_row_step;
   int tiles_m, tiles_n;  // filled by the launcher
-  // tn (EPI_ATOMIC only, weight gradients): C[M, N] += A^T B with BOTH operands row-major in the reduction index, i.e. the
+  // tn (EPI_ATOMIC / EPI_PLANES only, weight gradients): C[M, N] += A^T B with BOTH operands row-major in the reduction index, i.e. the
   // split rows the backward already holds: a = dY split rows [k_valid, lda] (M = its column count), w = X split rows
   // [k_valid, ldw] (N = its column count), K = the reduction length rounded up to 32 * k_splits.  Reduction rows >= k_valid
   // are read from `zero` (>= 1 KiB of zeros).  The operands are transposed on their way out of LDS (ds_read_b64_tr_b16).
@@ -587,6 +589,8 @@ struct RoiPoolArgs {
 };
 hipError_t launch_roi_pool(const RoiPoolArgs& a, hipStream_t s);
 hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s);
+// the ordered (gather) form: every element of every gradient map is written, in the summation order include/veto_amd.h states
+hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s);
 
 // ---- relation evaluators (sgg_eval.hip) ---------------------------------------------------------------
 struct SggEvalArgs {
@@ -731,7 +735,10 @@ int layernorm_backward_col_partials(int rows);
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
                                      float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out = nullptr,
                                      float* colp = nullptr, unsigned long long drop_seed = 0, unsigned drop_thresh = 0, float drop_scale = 1.f,
-                                     int drop_row_step = 1);
+                                     int drop_row_step = 1, bool ordered = false);
+// out[c] = (float) of the double sum over rows r = 0 .. n_rows - 1 of src[r * ld + c], rows in a fixed order (fold_rows_kernel): the fold of
+// the split-K partial planes of the ordered weight gradient
+hipError_t launch_fold_rows(const float* src, long ld, int n_rows, long n_cols, float* out, hipStream_t s);
 // out[c] = sum_r dy[r][c]; partial: workspace [n_chunks, n_cols]; column_sums_chunks() chunks keep every stage short
 int column_sums_chunks();
 hipError_t launch_column_sums(const float* dy, long ld, int rows, int n_cols, float* out, float* partial, int n_chunks, hipStream_t s);
@@ -760,6 +767,11 @@ hipError_t launch_head_backward(const float* dlogits, const float* w, const floa
                                 int n_pair, int n_out, long ld, hipStream_t s);
 hipError_t launch_assemble_backward(const float* dx, const int32_t* subj, const int32_t* obj, const float* lc, float* dpatch, float* dlc,
                                     int n_pair, hipStream_t s);
+// the ordered form (include/veto_amd.h, "ordered mode"): per object, token and half the float32 sum over the image's pair rows in
+// ascending order; writes every element of dpatch / dlc.  subj / obj: batch-wide object rows; img_*_off: device [n_img + 1]
+hipError_t launch_assemble_backward_ordered(const float* dx, const int32_t* subj, const int32_t* obj, const float* lc,
+                                            const int32_t* img_obj_off, const int32_t* img_pair_off, int n_img, float* dpatch, float* dlc,
+                                            int n_obj, hipStream_t s);
 hipError_t launch_sgemm_tn(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int n, int ka, int kb, hipStream_t s);
 hipError_t launch_sgemm_nt(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int n, int ki, int kj, hipStream_t s);
 hipError_t launch_obj_pos_backward(const float* boxes, int box_mode, const float* stats, const float* bn_w, const float* bn_b,
@@ -770,6 +782,9 @@ hipError_t launch_softmax_rows(const float* x, float* y, int n, int c, hipStream
 hipError_t launch_bias_relu(float* x, const float* b, int n, int k, hipStream_t s);
 hipError_t launch_gather_rows(const float* table, const int64_t* labels, int dim, float* out, int n, hipStream_t s);
 hipError_t launch_scatter_rows(const float* demb, const int64_t* labels, int dim, float* dtable, int n, hipStream_t s);
+// the ordered form: dtable [n_table_rows, dim] written whole, row r = the float32 sum over the object rows labelled r in ascending order
+hipError_t launch_scatter_rows_ordered(const float* demb, const int64_t* labels, int dim, float* dtable, int n, int n_table_rows,
+                                       hipStream_t s);
 hipError_t launch_untranspose_pair_proj(const float* dwt, float* dw, int kin, hipStream_t s);
 hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, hipStream_t s);
 // Input gradient of the patch projection (training): the TRANSPOSE of the combined patch weight as a GEMM weight operand,

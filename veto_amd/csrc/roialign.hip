@@ -215,6 +215,150 @@ __global__ __launch_bounds__(256) void roi_pool_backward_kernel(RoiPoolArgs a) {
   }
 }
 
+// Ordered backward (veto_roi_pool_backward_ordered): the gather that the scatter above inverts, so that every map pixel's sum has ONE
+// order -- (ROI, bin row, bin column, sample iy, sample ix, tap), ascending -- whatever the hardware does.  One launch per map.
+// Mapping: a workgroup owns a 32 x 8 pixel tile of one image's map and a 32-channel slab; a thread owns one pixel and keeps the slab's 32
+// sums in registers.  The workgroup walks the ROIs in index order, 256 at a time: thread i tests ROI i (image, level, footprint against the
+// tile), a ballot compacts the hits in order, and the hits' axis tables -- the forward's, built by the same axis_entry -- pass through LDS
+// 8 ROIs at a time.  A thread finds the few (ky, kx) entries whose low / high index is its pixel as four bit masks per ROI, then walks
+// its own bins in order and adds g * w / count per channel in tap order.  Tiles that no ROI reaches (most of a map) cost the index walk and a store of zeros: the call
+// writes every element, which replaces the caller's memset of the atomic form.
+constexpr int kTileW = 32, kTileH = 8;
+constexpr int kRoiPass = 256;    // ROIs tested per pass, one per thread
+constexpr int kRoiStage = 8;     // ROIs whose axis tables are in LDS at once
+
+template <int G>
+__global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolArgs a, int level, int tiles_x) {   // level < 0: the depth map
+  __shared__ AxisTable ty[kRoiStage], tx[kRoiStage];
+  __shared__ int s_list[kRoiPass];
+  __shared__ int s_cnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool depth = level < 0;
+  const RoiLevel L = depth ? a.depth : a.lv[level];
+  const int C = depth ? a.depth_channels : a.channels;
+  const int b = blockIdx.y, c0 = blockIdx.z * kSlab;
+  if (c0 >= C) return;      // (uniform)
+  const int tile_x0 = (blockIdx.x % tiles_x) * kTileW, tile_y0 = (blockIdx.x / tiles_x) * kTileH;
+  const int x = tile_x0 + (tid & (kTileW - 1)), y = tile_y0 + tid / kTileW;
+  const bool live = x < L.W && y < L.H;
+  const int P = a.pooled, n_axis = P * G;
+  const float count = (float)(G * G);
+  const float* gout = depth ? a.gout_depth : a.gout_rgb;
+  float acc[kSlab];
+#pragma unroll
+  for (int c = 0; c < kSlab; ++c) acc[c] = 0.f;
+
+  for (int r0 = 0; r0 < a.n_roi; r0 += kRoiPass) {
+    // ---- which ROIs of this pass can touch the tile: a superset (the masks below decide), kept in ROI order
+    bool hit = false;
+    const int r = r0 + tid;
+    if (r < a.n_roi) {
+      const float* roi = a.rois + (size_t)r * 5;
+      bool mine = (int)roi[0] == b;
+      if (mine && !depth && a.n_levels > 1) {      // LevelMapper, as roi_pool_kernel computes it
+        const float area = ((roi[3] - roi[1]) + 1.f) * ((roi[4] - roi[2]) + 1.f);
+        const float s = sqrtf(area);
+        float t = floorf(4.f + log2f(s / 224.f + 1e-6f));
+        t = fminf(fmaxf(t, (float)a.k_min), (float)a.k_max);
+        mine = (int)t - a.k_min == level;
+      }
+      if (mine) {
+        // a sample coordinate lies in [start, start + len]; its taps in [floor, floor + 1], clamped into the map: one pixel of margin each way
+        auto reach = [](float lo_c, float hi_c, int size, int t0, int t1) {
+          const float len = fmaxf(hi_c - lo_c, 1.0f);
+          const float f0 = fminf(fmaxf(lo_c, 0.f), (float)size), f1 = fminf(fmaxf(lo_c + len, 0.f), (float)size);
+          return (int)f0 - 1 <= t1 && (int)f1 + 2 >= t0;
+        };
+        hit = reach(roi[2] * L.scale, roi[4] * L.scale, L.H, tile_y0, tile_y0 + kTileH - 1) &&
+              reach(roi[1] * L.scale, roi[3] * L.scale, L.W, tile_x0, tile_x0 + kTileW - 1);
+      }
+    }
+    const unsigned long long votes = __ballot(hit);
+    if (lane == 0) s_cnt[wv] = __popcll(votes);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w < wv) before += s_cnt[w];
+      total += s_cnt[w];
+    }
+    if (hit) s_list[before + __popcll(votes & ((1ull << lane) - 1ull))] = r;
+    __syncthreads();
+
+    for (int i0 = 0; i0 < total; i0 += kRoiStage) {
+      const int ns = total - i0 < kRoiStage ? total - i0 : kRoiStage;
+      for (int e = tid; e < ns * 2 * n_axis; e += 256) {
+        const int j = e / (2 * n_axis), k2 = e % (2 * n_axis);
+        const bool is_y = k2 < n_axis;
+        const int k = is_y ? k2 : k2 - n_axis;
+        const float* roi = a.rois + (size_t)s_list[i0 + j] * 5;
+        const float lo_c = (is_y ? roi[2] : roi[1]) * L.scale;
+        const float hi_c = (is_y ? roi[4] : roi[3]) * L.scale;
+        const float len = fmaxf(hi_c - lo_c, 1.0f);
+        const float bin = len / (float)P;
+        axis_entry(is_y ? ty[j] : tx[j], k, lo_c, bin, k / G, k % G, G, is_y ? L.H : L.W);
+      }
+      __syncthreads();
+      if (live) {
+        for (int j = 0; j < ns; ++j) {
+          const AxisTable& Y = ty[j];
+          const AxisTable& X = tx[j];
+          unsigned ylo = 0, yhi = 0, xlo = 0, xhi = 0;      // bit k: entry k is valid and its low / high index is this pixel's
+          for (int k = 0; k < n_axis; ++k) {
+            if (Y.valid[k]) { ylo |= (unsigned)(Y.lo[k] == y) << k; yhi |= (unsigned)(Y.hi[k] == y) << k; }
+            if (X.valid[k]) { xlo |= (unsigned)(X.lo[k] == x) << k; xhi |= (unsigned)(X.hi[k] == x) << k; }
+          }
+          const unsigned ya = ylo | yhi, xa = xlo | xhi;
+          if (!ya || !xa) continue;
+          const float* gr = gout + ((size_t)s_list[i0 + j] * C + c0) * P * P;
+          // this lane's bins in (bin row, bin column) order, lowest set bit first: a lane walks only the few bins that touch its pixel (a
+          // loop over all P x P bins made every wave walk the union of its lanes' bins: 12.2 against 4.0 ms per call at 12 x 36 boxes)
+          constexpr unsigned gm = (1u << G) - 1u;
+          for (unsigned yrem = ya; yrem;) {
+            const int ph = (__ffs(yrem) - 1) / G;
+            yrem &= ~(gm << (ph * G));
+            for (unsigned xrem = xa; xrem;) {
+              const int pw = (__ffs(xrem) - 1) / G;
+              xrem &= ~(gm << (pw * G));
+              const float* gb = gr + ph * P + pw;
+              float g[kSlab];      // the bin's pooled gradient per channel: shared by its G x G samples
+#pragma unroll
+              for (int c = 0; c < kSlab; ++c) g[c] = c0 + c < C ? gb[(size_t)c * P * P] : 0.f;      // (uniform condition)
+              for (int iy = 0; iy < G; ++iy) {
+                const int ky = ph * G + iy;
+                if (!((ya >> ky) & 1u)) continue;
+                for (int ix = 0; ix < G; ++ix) {
+                  const int kx = pw * G + ix;
+                  if (!((xa >> kx) & 1u)) continue;
+                  const float hy = Y.h[ky], ly = Y.l[ky], hx = X.h[kx], lx = X.l[kx];
+                  const float w0 = hy * hx, w1 = hy * lx, w2 = ly * hx, w3 = ly * lx;      // :61, the taps of roi_pool_backward_kernel
+                  const bool t0 = ((ylo >> ky) & (xlo >> kx) & 1u) != 0, t1 = ((ylo >> ky) & (xhi >> kx) & 1u) != 0;
+                  const bool t2 = ((yhi >> ky) & (xlo >> kx) & 1u) != 0, t3 = ((yhi >> ky) & (xhi >> kx) & 1u) != 0;
+#pragma unroll
+                  for (int c = 0; c < kSlab; ++c) {      // (channels past C add into sums that are never stored)
+                    if (t0) acc[c] = acc[c] + g[c] * w0 / count;
+                    if (t1) acc[c] = acc[c] + g[c] * w1 / count;
+                    if (t2) acc[c] = acc[c] + g[c] * w2 / count;
+                    if (t3) acc[c] = acc[c] + g[c] * w3 / count;
+                  }
+                }
+              }
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (live) {
+    float* dst = (depth ? a.depth_grad : a.lv_grad[level]) + (((size_t)b * C + c0) * L.H + y) * L.W + x;
+    const size_t plane_sz = (size_t)L.H * L.W;
+#pragma unroll
+    for (int c = 0; c < kSlab; ++c)
+      if (c0 + c < C) dst[(size_t)c * plane_sz] = acc[c];
+  }
+}
+
 }  // namespace
 
 hipError_t launch_roi_pool(const RoiPoolArgs& a, hipStream_t s) {
@@ -244,6 +388,26 @@ hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s) {
+  if (a.pooled < 1 || a.pooled > 8 || a.sampling_ratio < 1 || a.sampling_ratio > 4 || n_img < 1 || n_img > 65535) return hipErrorInvalidValue;
+  const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
+  for (int level = with_depth ? -1 : 0; level < a.n_levels; ++level) {
+    const RoiLevel& L = level < 0 ? a.depth : a.lv[level];
+    const int C = level < 0 ? a.depth_channels : a.channels;
+    const int tiles_x = (L.W + kTileW - 1) / kTileW, tiles_y = (L.H + kTileH - 1) / kTileH;
+    dim3 grid((unsigned)tiles_x * tiles_y, n_img, (C + kSlab - 1) / kSlab);
+    switch (a.sampling_ratio) {
+      case 1: VETO_LAUNCH(roi_pool_backward_ordered_kernel<1>, grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 2: VETO_LAUNCH(roi_pool_backward_ordered_kernel<2>, grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 3: VETO_LAUNCH(roi_pool_backward_ordered_kernel<3>, grid, dim3(256), 0, s, a, level, tiles_x); break;
+      default: VETO_LAUNCH(roi_pool_backward_ordered_kernel<4>, grid, dim3(256), 0, s, a, level, tiles_x); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace veto

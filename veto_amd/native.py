@@ -223,7 +223,7 @@ class VetoDetEvalAccumulateArgs(Structure):
 
 class VetoTrainOpts(Structure):
     _fields_ = [("struct_size", c_int32), ("p_pos", ctypes.c_float), ("p_emb", ctypes.c_float), ("p_attn", ctypes.c_float),
-                ("seed", ctypes.c_uint64), ("d_roi_rgb", c_void_p), ("d_roi_depth", c_void_p)]
+                ("seed", ctypes.c_uint64), ("d_roi_rgb", c_void_p), ("d_roi_depth", c_void_p), ("deterministic", c_int32)]
 
 
 STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_abi_symbols.py compares every field's offset and size)
@@ -299,6 +299,7 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_optim_step": _sig(_P, POINTER(VetoOptimArgs), _P, _Z),
     "veto_optim_step_workspace_bytes": _sig(POINTER(VetoOptimArgs), ret=_Z),
     "veto_train_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
+    "veto_train_workspace_bytes_opts": _sig(_P, _I, _I, POINTER(VetoTrainOpts), ret=_Z),
     "veto_grad_floats": _sig(_P, ret=_Z),
     "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),
     "veto_forward_train": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), _P, _Z, _P),
@@ -313,11 +314,17 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_debug_layernorm_backward_col_partial_rows": _sig(_I, ret=_I),
     "veto_debug_wgrad": _sig(_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z),
     "veto_debug_wgrad_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+    "veto_debug_wgrad_ordered": _sig(_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z),
+    "veto_debug_wgrad_ordered_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
+    "veto_debug_assemble_backward_ordered": _sig(_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P),
+    "veto_debug_scatter_rows_ordered": _sig(_P, _P, _P, _I, _I, _I, _P),
+    "veto_debug_layernorm_backward_ordered": _sig(_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, c_uint64, c_uint32, c_float, _P, _Z),
     "veto_ce_loss": _sig(_P, _P, c_int64, _P, _P, _P, _I, _I, _P, _P, _P, _Z),
     "veto_ce_loss_workspace_bytes": _sig(_I, ret=_Z),
     "veto_meet_sample": _sig(_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P),
     "veto_roi_pool": _sig(_P, POINTER(VetoRoiPoolArgs)),
     "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
+    "veto_roi_pool_backward_ordered": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_sgg_eval": _sig(_P, POINTER(VetoSggEvalArgs), _I, _I, _P, _Z),
     "veto_sgg_eval_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
     "veto_sgg_eval_fold": _sig(_P, POINTER(VetoSggEvalFoldArgs), _P, _Z),
@@ -334,6 +341,19 @@ EXPORTS = list(SIGNATURES)   # what include/veto_amd.h declares
 
 class VetoError(RuntimeError):
     pass
+
+
+_ENV_DETERMINISTIC = None
+
+
+def ordered_mode(knob=False):
+    """Does the training path run in the ordered mode (include/veto_amd.h, veto_train_opts_t.deterministic)?  `knob` is the caller's
+    cfg.VETO_AMD.DETERMINISTIC; torch.use_deterministic_algorithms(True) and VETO_DETERMINISTIC=1 (read once per process, like the
+    library's VETO_TRAIN_* knobs) switch it on as well."""
+    global _ENV_DETERMINISTIC
+    if _ENV_DETERMINISTIC is None:
+        _ENV_DETERMINISTIC = os.environ.get("VETO_DETERMINISTIC") == "1"
+    return bool(knob) or _ENV_DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
 
 
 def library_path():

@@ -56,21 +56,23 @@ def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=No
     return out_rgb, out_depth, levels
 
 
-def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb, depth_shape, grad_depth):
-    """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None)."""
+def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb, depth_shape, grad_depth, ordered=False):
+    """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None).  ordered: through
+    veto_roi_pool_backward_ordered, which fixes the summation order and writes every element itself."""
     device = rois.device
     call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
     rois = rois.detach().to(**f32).contiguous()
     a = _pool_args(call, shapes, scales, rois, n_img, pooled, sampling_ratio, depth_shape if grad_depth is not None else None)
     grad_rgb = grad_rgb.detach().to(**f32).contiguous()
-    level_grads = [torch.zeros(shape, **f32) for shape in shapes]
+    make = torch.empty if ordered else torch.zeros
+    level_grads = [make(shape, **f32) for shape in shapes]
     ptrs = (ctypes.c_void_p * 4)(*[g.data_ptr() for g in level_grads])
     depth_grad = None
     if grad_depth is not None:
         grad_depth = grad_depth.detach().to(**f32).contiguous()
-        depth_grad = torch.zeros(depth_shape, **f32)
-    call.run("veto_roi_pool_backward", ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
+        depth_grad = make(depth_shape, **f32)
+    call.run("veto_roi_pool_backward_ordered" if ordered else "veto_roi_pool_backward", ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
     return level_grads, depth_grad
 
 
@@ -78,12 +80,13 @@ class _RoiPoolFn(torch.autograd.Function):
     """layers/roi_align.py:12-44 (_ROIAlign) for the fused multi-level + depth call: differentiable w.r.t. the maps."""
 
     @staticmethod
-    def forward(ctx, rois, scales, n_img, pooled, sampling_ratio, want_levels, n_levels, *maps):
+    def forward(ctx, rois, scales, n_img, pooled, sampling_ratio, want_levels, n_levels, ordered, *maps):
         feats, depth = list(maps[:n_levels]), (maps[n_levels] if len(maps) > n_levels else None)
         rgb, dep, levels = _roi_pool(feats, scales, rois, n_img, pooled, sampling_ratio, depth=depth, want_levels=want_levels)
         ctx.save_for_backward(rois)
         ctx.meta = ([tuple(f.shape) for f in feats], list(scales), n_img, pooled, sampling_ratio,
                     tuple(depth.shape) if depth is not None else None)
+        ctx.ordered = ordered
         ctx.mark_non_differentiable(*([levels] if levels is not None else []))
         outs = (rgb,) + ((dep,) if dep is not None else ()) + ((levels,) if levels is not None else ())
         return outs
@@ -97,16 +100,16 @@ class _RoiPoolFn(torch.autograd.Function):
         if grad_rgb is None:
             grad_rgb = torch.zeros((rois.shape[0], shapes[0][1], pooled, pooled), device=rois.device)
         level_grads, depth_grad = _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb,
-                                                     depth_shape, grad_dep)
-        return (None,) * 7 + tuple(level_grads) + ((depth_grad,) if depth_shape is not None else ())
+                                                     depth_shape, grad_dep, ordered=native.ordered_mode(ctx.ordered))
+        return (None,) * 8 + tuple(level_grads) + ((depth_grad,) if depth_shape is not None else ())
 
 
-def _roi_pool_autograd(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=None, want_levels=False):
+def _roi_pool_autograd(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=None, want_levels=False, ordered=False):
     """_roi_pool, recorded on the autograd tape when a map requires grad."""
     maps = list(level_feats) + ([depth] if depth is not None else [])
     if not (torch.is_grad_enabled() and any(m.requires_grad for m in maps)):
         return _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=depth, want_levels=want_levels)
-    outs = _RoiPoolFn.apply(rois, tuple(scales), n_img, pooled, sampling_ratio, want_levels, len(level_feats), *maps)
+    outs = _RoiPoolFn.apply(rois, tuple(scales), n_img, pooled, sampling_ratio, want_levels, len(level_feats), ordered, *maps)
     rgb = outs[0]
     dep = outs[1] if depth is not None else None
     levels = outs[-1] if want_levels else None
@@ -181,7 +184,8 @@ class Pooler(nn.Module):
             raise ValueError("%d feature levels for %d pooler scales" % (len(x), len(self.scales)))
         rgb, depth, levels = _roi_pool_autograd(list(x), self.scales, rois, x[0].shape[0], self.output_size[0],
                                                 self.sampling_ratio, depth=depth_features,
-                                                want_levels=getattr(self, "keep_levels", False))
+                                                want_levels=getattr(self, "keep_levels", False),
+                                                ordered=getattr(self, "deterministic", False))
         self.last_levels = levels
         if depth_features is not None:
             return rgb, depth
@@ -199,6 +203,8 @@ class VETOFeatureExtractor(nn.Module):
         sampling_ratio = cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO
         self.pooler = Pooler(output_size=(resolution, resolution), scales=scales, sampling_ratio=sampling_ratio,
                              in_channels=in_channels, cat_all_levels=cat_all_levels)
+        # VETO_AMD.DETERMINISTIC: the map gradients through veto_roi_pool_backward_ordered (fixed summation order)
+        self.pooler.deterministic = bool(getattr(getattr(cfg, "VETO_AMD", None), "DETERMINISTIC", False))
         self.out_channels = 256
 
     def forward(self, x, proposals, depth_features=None):

@@ -186,6 +186,7 @@ class _NativeForward:
         # VETO_AMD.COUNT_SATURATION: eval forwards go through veto_forward_saturation (slower: launch per stage, one stream
         # synchronisation) and leave the per-layer counts of clamped mixed-row elements in `self.last_saturation`
         self._count_saturation = bool(getattr(getattr(config, "VETO_AMD", None), "COUNT_SATURATION", False))
+        self._deterministic = bool(getattr(getattr(config, "VETO_AMD", None), "DETERMINISTIC", False))
         self.last_saturation = None
         object.__setattr__(self, "_trunk", trunk)  # not a sub-module registration
         self._engine = None
@@ -264,6 +265,7 @@ class _NativeForward:
             raise NotImplementedError("veto_amd: dropout is built for pos_embed, pos_drop and the attention output only; "
                                       "these modules also have p > 0: %s" % ", ".join(others[:6]))
         o.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        o.deterministic = int(native.ordered_mode(self._deterministic))
         return o
 
     def _run_native_train(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits):
@@ -380,7 +382,7 @@ class _TrainFn(torch.autograd.Function):
         launch, inp, n_objs, n_pairs, eng = owner._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
                                                                 labels, obj_logits, stats)
         opts = owner._train_opts()
-        need = launch.lib.veto_train_workspace_bytes(eng.handle, inp.n_obj, inp.n_pair)
+        need = launch.lib.veto_train_workspace_bytes_opts(eng.handle, inp.n_obj, inp.n_pair, ctypes.byref(opts))
         # tens of GB: keep one workspace on the module and hand it to the next step once its backward has run (an
         # allocation of this size goes to the driver every time, and releasing it synchronises the device)
         # The cached workspace belongs to at most one forward whose backward has not run yet.  Ownership is a token held by
