@@ -1175,6 +1175,45 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
 int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
                   size_t workspace_bytes, const float* dlogits, float* grads);
 
+/* ---- partial training: a step that computes only the gradients somebody reads, and honours eval-mode sub-modules -----------------
+ * A plan rides beside the opts.  plan == NULL in any of the three entry points below is the entry point above it: same launches,
+ * workspace and bits.  With a plan, veto_backward_plan launches nothing whose every output is unused:
+ *   the chain  head -> layers L-1 .. 0 (fc2, fc1, LayerNorm2, out, attention, qkv, LayerNorm1) -> pos_embedding / cls_token
+ *              -> patch projection and the map gradients -> location / class projections -> pos_embed.1, pos_embed.0, obj_embed
+ *   is walked down to the deepest stage with a consumer (a trainable tensor, or d_roi_rgb / d_roi_depth) and ends there; a frozen
+ *   Linear above that stage loses its weight-gradient GEMM, its zero-fill or fold and its bias sums, the deepest Linear with nothing
+ *   below it its input-gradient GEMM as well; a heads-only plan is the head's weight and bias gradient alone.
+ * Only the regions of `grads` that belong to trainable tensors are zeroed or written: a frozen tensor's region is left as the caller
+ * gave it.  A computed gradient has the bits the unplanned step gives it in the ordered mode (the stated orders are per sum).
+ * The forward keeps the activations of the layers the backward will read; the layers below the lowest consumer (the last layer
+ * excepted: its buffers are the compact ones) alternate between two sets of buffers, so veto_train_workspace_bytes_plan shrinks with
+ * the frozen prefix.  Both calls of a step must see the same plan: the forward stamps it with the workspace and the backward refuses
+ * another one, as it refuses a plan on the workspace of a veto_forward_train and the other way round. */
+typedef struct veto_train_plan {
+  int32_t struct_size;
+  /* pos_embed.0 (the BatchNorm) normalises with its running statistics: in->bn_batch_stats is neither needed nor written.  Refused
+   * while pos_embed.0.weight or pos_embed.0.bias is trainable. */
+  int32_t bn_eval;
+  /* host array of veto_num_weights(h) bytes, indexed like veto_weight_info: nonzero = the tensor's gradient is wanted.  The
+   * row-concatenated rel_out.weight / rel_out.bias take one flag each. */
+  const uint8_t* trainable;
+  /* host array [layers] of the dropout rates behind the attention out projections (site 3 + l), each in [0, 1); NULL: opts->p_attn
+   * for every layer. */
+  const float* p_attn_layer;
+  /* nonzero: veto_backward_plan will be given opts->d_roi_rgb and / or opts->d_roi_depth, so the chain runs down to the patch
+   * projection whatever is frozen (the pointers themselves are read by the backward only; asking for them there with 0 here is
+   * refused). */
+  int32_t d_roi;
+  int32_t reserved0;
+} veto_train_plan_t;
+
+size_t veto_train_workspace_bytes_plan(veto_handle_t h, int32_t n_obj, int32_t n_pair, const veto_train_opts_t* opts,
+                                       const veto_train_plan_t* plan);
+int veto_forward_train_plan(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts,
+                            const veto_train_plan_t* plan, void* workspace, size_t workspace_bytes, float* out_logits);
+int veto_backward_plan(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts,
+                       const veto_train_plan_t* plan, void* workspace, size_t workspace_bytes, const float* dlogits, float* grads);
+
 /* ---- test hook: dw[N,K] = dy[M,N]^T . x[M,K], the weight-gradient GEMM (reduction over the M rows) through the
  * production split-bf16 kernel in its split-K / atomic-add form.  k must be a multiple of 192; k_splits 0 = auto. */
 int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,

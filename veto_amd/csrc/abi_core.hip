@@ -286,6 +286,7 @@ int veto_load_weights(veto_handle_t h, const char* name, const float* src, size_
   HIP_TRY(hipMemcpyAsync(h->raw + q.offset, src, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
   q.loaded = true;
   h->dirty = true;
+  h->train_plan.clear();
   h->train_gen.clear();   // (no workspace's saved activations match the weights any more; also bounds the map)
   return VETO_OK;
 }

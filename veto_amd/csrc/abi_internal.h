@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <iterator>
 #include <map>
 #include <string>
 #include <vector>
@@ -211,7 +212,11 @@ struct veto_handle_s {
       train_gen.erase(old);
     }
     train_gen[ws] = weight_gen;
+    for (auto it = train_plan.begin(); it != train_plan.end();) it = train_gen.count(it->first) ? std::next(it) : train_plan.erase(it);
   }
+  // ... and the plan (veto_train_plan_t, flattened to bytes) its forward ran under; no entry: veto_forward_train, no plan.  Both calls of
+  // a step must agree on it: the plan decides the workspace layout and which activations the forward kept
+  std::map<const void*, std::string> train_plan;
   std::vector<LayerW> layers;
   SplitW patch_w = nullptr;
   // last layer, folded CLS attention (attention.hip): Mcat [heads*576, 2*576], Ncat [576, 2*heads*576], and their fp32 staging

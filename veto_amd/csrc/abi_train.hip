@@ -91,7 +91,25 @@ size_t wgrad_plane_floats(int m_tokens, int patch_rows) {
   return most;
 }
 
-TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ordered = false) {
+// What a step computes (include/veto_amd.h, veto_train_plan_t), derived once by make_sched from the plan.  The default-constructed
+// one is the step without a plan: everything wanted, batch statistics, one attention dropout rate.
+// The backward chain: head -> layers L-1 .. 0 (fc2, fc1, LayerNorm2, out, attention, qkv, LayerNorm1) -> pos_embedding / cls_token ->
+// patch projection (and the map gradients) -> location / class projections -> pos_embed.1, pos_embed.0, obj_embed.
+struct Sched {
+  bool full = true;
+  std::vector<uint8_t> on;        // per weight index (veto_weight_info): its gradient is wanted
+  std::vector<float> p_attn;      // per layer; empty: opts->p_attn everywhere
+  bool bn_eval = false;
+  bool maps = true;               // d_roi_rgb / d_roi_depth may be asked for
+  bool below = true;              // a stage under layer 0 has a consumer
+  std::vector<uint8_t> need_in;   // per layer: the gradient w.r.t. the layer's input has a consumer
+  int keep_from = 0;              // the lowest layer whose saved activations the backward reads (layers: none, the head reads xout only)
+  std::string key;                // the plan as bytes: what the forward stamps the workspace with
+  bool want(veto_handle_t h, const std::string& name) const { return full || on[h->index.at(name)] != 0; }
+  bool need(int l) const { return full || need_in[l] != 0; }
+};
+
+TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ordered = false, const Sched& sch = Sched()) {
   TrainWs w;
   Carver c{base};
   const int L = h->cfg.layers, E = h->cfg.embed_dim;
@@ -108,8 +126,15 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   const bool recompute = train_recompute();
   __bf16* a_scr = recompute ? c.take<__bf16>(mpad * 2 * kDim * 2) : nullptr;      // LayerNorm rows of whichever Linear is next (forward) / being differentiated (backward)
   __bf16* hid_scr = recompute ? c.take<__bf16>(mpad * 4 * kDim * 2) : nullptr;    // the same for the GELU rows
+  // (a plan: the layers under the lowest one the backward reads -- never the last, whose buffers are the compact ones -- alternate between
+  // the buffers of the first two of them: a layer reads its own set and writes the input rows of the next)
+  const int shared = sch.keep_from < L - 1 ? sch.keep_from : L - 1;
   for (int l = 0; l < L; ++l) {
     TrainLayer& t = w.layers[l];
+    if (l < shared && l >= 2) {
+      t = w.layers[l - 2];
+      continue;
+    }
     // (the last layer runs on the pairs' CLS rows behind its attention: those buffers are compact, one row per pair -- sized for every token
     // row until round 6, 4.4 GB too many at cfg-2)
     const size_t rows = l == L - 1 ? cpad : mpad;
@@ -185,6 +210,8 @@ size_t wgrad_mp(int m, int ks) { return ((size_t)m + 32 * (size_t)ks - 1) / (32 
 // gelu_pre (fc2 only): the input gradient is not written as fp32 rows: the GEMM's epilogue multiplies it by gelu'(gelu_pre) and writes the
 // split rows of fc1's backward to w.dsplit_b and their column-sum partials to w.colp (*next_partials rows): the pass that read dH and the
 // pre-activation back (0.9 ms per layer) is gone.
+// Partial training: dw == nullptr (a frozen weight) leaves out the weight-gradient GEMM with its zero-fill or fold, db == nullptr the bias
+// sums, dx == nullptr without gelu_pre (nothing below this Linear has a consumer) the weight transpose and the input-gradient GEMM.
 int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const float* dy, int M, int N, const __bf16* x_split, int K,
                         const float* weight, float* dw, float* db, float* dx, const GradXform& xf = GradXform(),
                         const __bf16* presplit = nullptr, int presplit_partials = 0, const float* gelu_pre = nullptr, int* next_partials = nullptr) {
@@ -196,8 +223,8 @@ int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const 
   if (mp > w.mp2) return fail(VETO_ERR_WORKSPACE, "weight-gradient partial buffer too small");
   if (dy) HIP_TRY(launch_prep_grad(dy, N, M, N, w.dsplit, (int)mp, db ? w.colp : nullptr, xf, s));
   if (db) HIP_TRY(launch_column_sums(w.colp, N, dy ? (int)(mp / 32) : presplit_partials, N, db, w.col_partial, column_sums_chunks(), s));
-  if (!w.planes) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
-  {
+  if (dw && !w.planes) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
+  if (dw) {
     GemmArgs g{};
     g.a = gsplit; g.w = x_split; g.c = w.planes ? w.planes : dw;
     g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
@@ -206,6 +233,7 @@ int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const 
     HIP_TRY(launch_gemm_split(g, w.planes ? EPI_PLANES : EPI_ATOMIC, 0, s));
     if (w.planes) HIP_TRY(launch_fold_rows(w.planes, (long)N * K, ks, (long)N * K, dw, s));      // the planes in split order
   }
+  if (!dx && !gelu_pre) return VETO_OK;
   HIP_TRY(launch_transpose_split(weight, K, N, K, w.wdg, N, s));     // W [N, K] -> W^T split rows [K, 2N]
   {
     GemmArgs g{};
@@ -227,11 +255,12 @@ int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const 
 // dropout sites of the training path: 1 = pos_embed Dropout(0.1), 2 = pos_drop on the tokens, 3 + l = to_out of layer l.  Elements are
 // numbered as include/veto_amd.h says, sites 2 and up by TOKEN row: where a site is applied to the last layer's compact CLS rows, row p is
 // token row 19 p (row_step), so that the masks do not depend on which rows the implementation chooses to compute.
-DropSite drop_site(const veto_train_opts_t* o, int site, int row_step = 1) {
+// sch: a plan's own rate for the attention site of layer site - 3 (veto_train_plan_t.p_attn_layer)
+DropSite drop_site(const veto_train_opts_t* o, int site, int row_step = 1, const Sched* sch = nullptr) {
   DropSite d;
   d.row_step = row_step;
   if (!o) return d;
-  const float p = site == 1 ? o->p_pos : site == 2 ? o->p_emb : o->p_attn;
+  const float p = site == 1 ? o->p_pos : site == 2 ? o->p_emb : sch && !sch->p_attn.empty() ? sch->p_attn[site - 3] : o->p_attn;
   if (!(p > 0.f)) return d;
   d.seed = o->seed + (unsigned long long)site * 0x632BE59BD9B4E019ull;
   d.thresh = (unsigned)(p * 16777216.0f);
@@ -253,17 +282,71 @@ int check_train_opts(const veto_train_opts_t* o) {
   return VETO_OK;
 }
 
-int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace, size_t workspace_bytes) {
+// The plan, checked and flattened; plan == nullptr: the step without one
+int make_sched(veto_handle_t h, const veto_train_opts_t* opts, const veto_train_plan_t* plan, Sched* out) {
+  Sched sch;
+  if (!plan) {
+    *out = sch;
+    return VETO_OK;
+  }
+  if (!h) return fail(VETO_ERR_INVALID, "null argument");
+  if (plan->struct_size != (int32_t)sizeof(veto_train_plan_t)) return fail(VETO_ERR_INVALID, "veto_train_plan_t size mismatch");
+  if (!plan->trainable) return fail(VETO_ERR_INVALID, "veto_train_plan_t.trainable is NULL");
+  const int L = h->cfg.layers;
+  sch.full = false;
+  sch.on.assign(plan->trainable, plan->trainable + h->params.size());
+  for (uint8_t& f : sch.on) f = f ? 1 : 0;
+  if (plan->p_attn_layer) {
+    sch.p_attn.assign(plan->p_attn_layer, plan->p_attn_layer + L);
+    for (float p : sch.p_attn) {
+      if (!(p >= 0.f && p < 1.f)) return fail(VETO_ERR_INVALID, "dropout probabilities must be in [0, 1)");
+      if (p > 0.f && !opts) return fail(VETO_ERR_INVALID, "veto_train_plan_t.p_attn_layer needs the opts (the seed of the masks)");
+    }
+  }
+  sch.bn_eval = plan->bn_eval != 0;
+  sch.maps = plan->d_roi != 0;
+  if (sch.bn_eval && (sch.want(h, "pos_embed.0.weight") || sch.want(h, "pos_embed.0.bias")))
+    return fail(VETO_ERR_INVALID, "bn_eval with a trainable pos_embed.0.weight / bias needs a BatchNorm backward on fixed statistics, which is not built");
+  const std::string T = kT;
+  sch.below = sch.maps;
+  for (const char* name : {"pos_embed.0.weight", "pos_embed.0.bias", "pos_embed.1.weight", "pos_embed.1.bias", "obj_embed.weight",
+                           "location_projection.0.weight", "location_projection.0.bias", "class_projection.0.weight", "class_projection.0.bias"})
+    sch.below = sch.below || sch.want(h, name);
+  for (const char* name : {"pos_embedding", "cls_token", "patch_embed.proj_d.weight", "patch_embed.proj_d.bias", "patch_embed.proj_v.weight",
+                           "patch_embed.proj_v.bias"})
+    sch.below = sch.below || sch.want(h, T + name);
+  sch.need_in.assign(L, 0);
+  sch.keep_from = L;
+  bool need = sch.below;
+  for (int l = 0; l < L; ++l) {
+    sch.need_in[l] = need;
+    bool any = false;
+    for (const LayerLinear& q : kLayerLinears) any = any || sch.want(h, lname(l, q.weight)) || (q.bias && sch.want(h, lname(l, q.bias)));
+    for (const char* name : {"0.norm.weight", "0.norm.bias", "1.norm.weight", "1.norm.bias"}) any = any || sch.want(h, lname(l, name));
+    if ((any || need) && sch.keep_from == L) sch.keep_from = l;
+    need = need || any;
+  }
+  sch.key.assign(1, 'P');      // (never empty: no entry in train_plan means no plan)
+  sch.key.append(sch.on.begin(), sch.on.end());
+  sch.key.append((const char*)sch.p_attn.data(), sch.p_attn.size() * sizeof(float));
+  sch.key.push_back(sch.bn_eval ? 'e' : 'b');
+  sch.key.push_back(sch.maps ? 'm' : '-');
+  *out = sch;
+  return VETO_OK;
+}
+
+int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace, size_t workspace_bytes,
+                       const Sched& sch = Sched()) {
   CHECK_STRUCT_AND(veto_inputs_t, in, h && workspace);
   if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch");
   if (!in->roi_rgb || !in->roi_depth || !in->boxes || !in->rel_pairs || !in->img_obj_offset || !in->img_pair_offset)
     return fail(VETO_ERR_INVALID, "missing input pointer");
   if (!in->obj_labels && !in->obj_logits) return fail(VETO_ERR_INVALID, "neither obj_labels nor obj_logits given");
-  if (!in->bn_batch_stats) return fail(VETO_ERR_INVALID, "the training path needs bn_batch_stats (training-mode BatchNorm)");
+  if (!in->bn_batch_stats && !sch.bn_eval) return fail(VETO_ERR_INVALID, "the training path needs bn_batch_stats (training-mode BatchNorm)");
   if (h->cfg.precision == VETO_FAST) return fail(VETO_ERR_INVALID, "the training path runs on split-bf16 operands (precise / mixed handles) only");
   ABI_TRY(check_train_opts(opts));
-  if (workspace_bytes < carve_train(nullptr, h, in->n_obj, in->n_pair, opts_ordered(opts)).total)
-    return fail(VETO_ERR_WORKSPACE, opts_ordered(opts) ? "training workspace too small (ordered mode: veto_train_workspace_bytes_opts)" : "training workspace too small");
+  if (workspace_bytes < carve_train(nullptr, h, in->n_obj, in->n_pair, opts_ordered(opts), sch).total)
+    return fail(VETO_ERR_WORKSPACE, !sch.full ? "training workspace too small (veto_train_workspace_bytes_plan)" : opts_ordered(opts) ? "training workspace too small (ordered mode: veto_train_workspace_bytes_opts)" : "training workspace too small");
   return VETO_OK;
 }
 
@@ -281,22 +364,33 @@ size_t veto_train_workspace_bytes_opts(veto_handle_t h, int32_t n_obj, int32_t n
   return carve_train(nullptr, h, n_obj, n_pair, opts_ordered(opts)).total;
 }
 
-int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
-                       size_t workspace_bytes, float* out_logits) {
-  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes));
+size_t veto_train_workspace_bytes_plan(veto_handle_t h, int32_t n_obj, int32_t n_pair, const veto_train_opts_t* opts,
+                                       const veto_train_plan_t* plan) {
+  if (!plan) return veto_train_workspace_bytes_opts(h, n_obj, n_pair, opts);
+  Sched sch;
+  if (!h || n_obj <= 0 || n_pair <= 0 || check_train_opts(opts) != VETO_OK || make_sched(h, opts, plan, &sch) != VETO_OK) return 0;
+  return carve_train(nullptr, h, n_obj, n_pair, opts_ordered(opts), sch).total;
+}
+
+static int forward_train_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, const Sched& sch,
+                              void* workspace, size_t workspace_bytes, float* out_logits) {
+  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes, sch));
   if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
   if (h->dirty) ABI_TRY(finalize_weights(h, s, true));
   h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
+  h->train_plan.erase(workspace);
   const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out;
   const int M = n_pair * kTokens;
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, opts_ordered(opts));
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, opts_ordered(opts), sch);
   HIP_TRY(launch_pair_indices(in->rel_pairs, in->img_obj_offset, in->img_pair_offset, in->n_img, n_pair, ws.subj, ws.obj, nullptr,
                               nullptr, s));
   {
-    HIP_TRY(launch_bn_batch_stats(in->boxes, in->box_mode, n_obj, in->bn_batch_stats, s));
-    ObjPrepArgs a = obj_prep_args(h, in, ws.lc);
+    veto_inputs_t in_bn = *in;      // (an eval-mode pos_embed.0: the running statistics, as the inference forward reads them)
+    if (sch.bn_eval) in_bn.bn_batch_stats = nullptr;
+    else HIP_TRY(launch_bn_batch_stats(in->boxes, in->box_mode, n_obj, in->bn_batch_stats, s));
+    ObjPrepArgs a = obj_prep_args(h, &in_bn, ws.lc);
     const DropSite d = drop_site(opts, 1);
     a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale;
     HIP_TRY(launch_obj_prep(a, s));
@@ -329,7 +423,7 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
         HIP_TRY(launch_attention(a, s));
       }
       ABI_TRY(run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
-                       EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens)));
+                       EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens, &sch)));
       HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
       ABI_TRY(run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU));
       ABI_TRY(run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID));
@@ -343,7 +437,7 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
       HIP_TRY(launch_attention(a, s));
     }
     ABI_TRY(run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0,
-                     drop_site(opts, 3 + l)));
+                     drop_site(opts, 3 + l, 1, &sch)));
     HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, M, s));
     // (the epilogue writes the fp32 pre-activation -- gelu' needs it -- AND its exact-erf GELU as fc2's split rows: round 6; before, a pass
     // of its own read the pre-activation back, 0.55 ms per layer)
@@ -353,13 +447,31 @@ int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, c
   }
   HIP_TRY(launch_head(ws.xout, h->head_wt, h->p("rel_out.bias"), out_logits, n_pair, n_out, s, (long)kDim));
   h->stamp_train_workspace(workspace);
+  if (!sch.full) h->train_plan[workspace] = sch.key;
   return VETO_OK;
 }
 
-int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
-                  size_t workspace_bytes, const float* dlogits, float* grads) {
-  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes));
+int veto_forward_train(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
+                       size_t workspace_bytes, float* out_logits) {
+  return forward_train_impl(h, stream, in, opts, Sched(), workspace, workspace_bytes, out_logits);
+}
+
+int veto_forward_train_plan(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts,
+                            const veto_train_plan_t* plan, void* workspace, size_t workspace_bytes, float* out_logits) {
+  if (!plan) return veto_forward_train(h, stream, in, opts, workspace, workspace_bytes, out_logits);
+  if (!h) return fail(VETO_ERR_INVALID, "null argument");
+  ABI_TRY(check_train_opts(opts));
+  Sched sch;
+  ABI_TRY(make_sched(h, opts, plan, &sch));
+  return forward_train_impl(h, stream, in, opts, sch, workspace, workspace_bytes, out_logits);
+}
+
+static int backward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, const Sched& sch,
+                         void* workspace, size_t workspace_bytes, const float* dlogits, float* grads) {
+  ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes, sch));
   if (!dlogits || !grads) return fail(VETO_ERR_INVALID, "null gradient pointer");
+  if (!sch.maps && opts && (opts->d_roi_rgb || opts->d_roi_depth))
+    return fail(VETO_ERR_INVALID, "veto_backward_plan: d_roi_rgb / d_roi_depth asked for under a plan with d_roi == 0");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
   // the backward reads the derived operands the matching forward used: a weight upload in between would pair this
@@ -370,28 +482,50 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     if (it == h->train_gen.end()) return fail(VETO_ERR_INVALID, "veto_backward: this workspace holds no veto_forward_train activations");
     if (it->second != h->weight_gen)
       return fail(VETO_ERR_WEIGHTS, "veto_backward: the weights were refreshed (by a later forward) since this workspace's veto_forward_train");
+    auto pl = h->train_plan.find(workspace);
+    if (sch.full ? pl != h->train_plan.end() : pl == h->train_plan.end() || pl->second != sch.key)
+      return fail(VETO_ERR_INVALID, "veto_backward: this workspace's forward ran under another plan (veto_train_plan_t) than this backward");
   }
   const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out, E = h->cfg.embed_dim;
   const int M = n_pair * kTokens;
   const bool ordered = opts_ordered(opts);
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, ordered);
+  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, ordered, sch);
   const std::string T = kT;
-  auto G = [&](const std::string& name) { return grads + h->params[h->index.at(name)].offset; };
+  // (a frozen tensor has no gradient pointer: every launch below that would only write it is left out)
+  auto W = [&](const std::string& name) { return sch.want(h, name); };
+  auto G = [&](const std::string& name) -> float* { return W(name) ? grads + h->params[h->index.at(name)].offset : nullptr; };
+  auto copy_grad = [&](const std::string& name, const float* src, size_t n) {
+    float* g = G(name);
+    return g ? hipMemcpyAsync(g, src, n * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  };
   struct LinGrad { const float* w; float *dw, *db; int N, K; };      // a layer's Linear (kLayerLinears): weight, its and the bias's gradient
   auto lin = [&](int l, int i) {
     const LayerLinear& q = kLayerLinears[i];
     return LinGrad{h->p(lname(l, q.weight)), G(lname(l, q.weight)), q.bias ? G(lname(l, q.bias)) : nullptr, q.N, q.K};
   };
-  HIP_TRY(hipMemsetAsync(grads, 0, veto_grad_floats(h) * 4, s));
+  if (sch.full) {
+    HIP_TRY(hipMemsetAsync(grads, 0, veto_grad_floats(h) * 4, s));
+  } else {      // the regions of the trainable tensors only, neighbours in one fill (tensors lie in index order, padded to 64 floats)
+    for (size_t i = 0; i < h->params.size();) {
+      if (!sch.on[i]) { ++i; continue; }
+      size_t j = i;
+      while (j + 1 < h->params.size() && sch.on[j + 1]) ++j;
+      HIP_TRY(hipMemsetAsync(grads + h->params[i].offset, 0, (h->params[j].offset + h->params[j].numel - h->params[i].offset) * 4, s));
+      i = j + 1;
+    }
+  }
   HIP_TRY(hipMemsetAsync(ws.zero, 0, 1024, s));
 
-  // ---- classifier head: gradient of the compact CLS rows ------------------------------------------------------------
-  HIP_TRY(launch_head_backward(dlogits, h->p("rel_out.weight"), ws.xout, ws.dx, G("rel_out.weight"), G("rel_out.bias"), ws.head_partial,
-                               n_pair, n_out, (long)kDim, s));
+  // ---- classifier head: gradient of the compact CLS rows (not written when nothing under the head has a consumer) --------
+  HIP_TRY(launch_head_backward(dlogits, h->p("rel_out.weight"), ws.xout, sch.keep_from < L ? ws.dx : nullptr, G("rel_out.weight"),
+                               G("rel_out.bias"), ws.head_partial, n_pair, n_out, (long)kDim, s));
 
   // ---- transformer layers, last to first -------------------------------------------------------------------------
+  // A layer's stages in chain order: fc2, fc1, LayerNorm2, out, attention, qkv, LayerNorm1.  own[i]: stage i has a trainable tensor;
+  // deeper[i]: something behind it (in this layer, a lower one or under layer 0) has a consumer, so its input gradient is computed.
+  // The walk ends behind the first stage with deeper[i] == false: every later stage of every lower layer is without a consumer too.
   int dx_presplit = 0;      // > 0: ws.dsplit / ws.colp already hold the split rows / that many rows of column partials of ws.dx
-  for (int l = L - 1; l >= 0; --l) {
+  for (int l = L - 1; l >= sch.keep_from; --l) {
     const LayerW& w = h->layers[l];
     TrainLayer& t = ws.layers[l];
     const bool last = l == L - 1;
@@ -404,30 +538,46 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     const float* dy2 = dx_presplit ? nullptr : ws.dx;
     const bool recompute = train_recompute();
     const LinGrad qkv = lin(l, LIN_QKV), out = lin(l, LIN_OUT), fc1 = lin(l, LIN_FC1), fc2 = lin(l, LIN_FC2);
-    if (recompute) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
+    const bool ln1 = W(lname(l, "0.norm.weight")) || W(lname(l, "0.norm.bias")), ln2 = W(lname(l, "1.norm.weight")) || W(lname(l, "1.norm.bias"));
+    enum { S_FC2, S_FC1, S_LN2, S_OUT, S_ATTN, S_QKV, S_LN1, S_COUNT };
+    const bool own[S_COUNT] = {fc2.dw || fc2.db, fc1.dw || fc1.db, ln2, out.dw || out.db, false, qkv.dw != nullptr, ln1};
+    bool deeper[S_COUNT];
+    for (int i = S_COUNT - 1, acc = sch.need(l); i >= 0; --i) {
+      deeper[i] = acc;
+      acc = acc || own[i];
+    }
+    if (recompute && fc2.dw) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
     if (train_gelu_epilogue()) {
       int partials = 0;
-      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit, t.pre, &partials));
-      if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));      // LayerNorm2 rows: fc1's operand
-      ABI_TRY(run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, GradXform(), ws.dsplit_b, partials));
+      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit,
+                                  deeper[S_FC2] ? t.pre : nullptr, &partials));
+      if (!deeper[S_FC2]) break;
+      if (recompute && fc1.dw) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));      // LayerNorm2 rows: fc1's operand
+      ABI_TRY(run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, deeper[S_FC1] ? ws.dtmp : nullptr, GradXform(),
+                                  ws.dsplit_b, partials));
     } else {
-      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, ws.dbig, GradXform(), nullptr, dx_presplit));
+      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, deeper[S_FC2] ? ws.dbig : nullptr, GradXform(), nullptr,
+                                  dx_presplit));
+      if (!deeper[S_FC2]) break;
       GradXform gelu;              // dpre = dh * gelu'(pre), folded into the operand preparation of the fc1 backward
       gelu.mode = XF_GELU;
       gelu.pre = t.pre;
-      if (recompute) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));
-      ABI_TRY(run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, ws.dtmp, gelu));
+      if (recompute && fc1.dw) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));
+      ABI_TRY(run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, deeper[S_FC1] ? ws.dtmp : nullptr, gelu));
     }
+    if (!deeper[S_FC1]) break;
     // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
-    const DropSite dsite = drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1);      // (last layer: compact CLS rows, as in the forward)
+    const DropSite dsite = drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1, &sch);      // (last layer: compact CLS rows, as in the forward)
     const bool ln_split = train_ln_emits_split();
     if (ln_split)
-      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, ws.dsplit, ws.colp,
+      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ln2 ? ws.dgb : nullptr, ws.ln_partial, R, s, ws.dsplit, ws.colp,
                                         dsite.seed, dsite.thresh, dsite.scale, dsite.row_step, ordered));
     else
-      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ws.dgb, ws.ln_partial, R, s, nullptr, nullptr, 0, 0, 1.f, 1, ordered));
-    HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(G(lname(l, "1.norm.bias")), ws.dgb + kDim, kDim * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ln2 ? ws.dgb : nullptr, ws.ln_partial, R, s, nullptr, nullptr, 0, 0, 1.f, 1,
+                                        ordered));
+    HIP_TRY(copy_grad(lname(l, "1.norm.weight"), ws.dgb, kDim));
+    HIP_TRY(copy_grad(lname(l, "1.norm.bias"), ws.dgb + kDim, kDim));
+    if (!deeper[S_LN2]) break;
     GradXform drop;
     if (dsite.thresh) {
       drop.mode = XF_DROP;
@@ -436,9 +586,13 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       drop.scale = dsite.scale;
       drop.row_step = dsite.row_step;
     }
-    ABI_TRY(run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, ws.dtmp, drop, nullptr,
-                                ln_split ? layernorm_backward_col_partials(R) : 0));
+    ABI_TRY(run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, deeper[S_OUT] ? ws.dtmp : nullptr,
+                                drop, nullptr, ln_split ? layernorm_backward_col_partials(R) : 0));
+    if (!deeper[S_OUT]) break;
     HIP_TRY(launch_attention_backward(t.qkv, ws.dtmp, nullptr, ws.dsplit, n_pair, H, last ? 1 : 0, s, train_qkv_f24(h)));
+    if (recompute && qkv.dw) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
+    ABI_TRY(run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, deeper[S_QKV] ? ws.dtmp : nullptr));
+    if (!deeper[S_QKV]) break;
     const float* dres = ws.dmid;
     if (last) {
       // the residual gradient d x_mid lives on the CLS rows only: spread the compact rows over a zeroed token matrix
@@ -447,19 +601,20 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
                                hipMemcpyDeviceToDevice, s));
       dres = ws.dx;
     }
-    if (recompute) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
-    ABI_TRY(run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, ws.dtmp));
     // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
     if (ln_split && l > 0) {      // (its result is the gradient matrix of fc2 of the layer below)
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, ws.dsplit, ws.colp, 0, 0, 1.f, 1, ordered));
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ln1 ? ws.dgb : nullptr, ws.ln_partial, M, s, ws.dsplit, ws.colp, 0, 0, 1.f, 1,
+                                        ordered));
       dx_presplit = layernorm_backward_col_partials(M);
     } else {
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ws.dgb, ws.ln_partial, M, s, nullptr, nullptr, 0, 0, 1.f, 1, ordered));
+      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ln1 ? ws.dgb : nullptr, ws.ln_partial, M, s, nullptr, nullptr, 0, 0, 1.f, 1,
+                                        ordered));
       dx_presplit = 0;
     }
-    HIP_TRY(hipMemcpyAsync(G(lname(l, "0.norm.weight")), ws.dgb, kDim * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(G(lname(l, "0.norm.bias")), ws.dgb + kDim, kDim * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(copy_grad(lname(l, "0.norm.weight"), ws.dgb, kDim));
+    HIP_TRY(copy_grad(lname(l, "0.norm.bias"), ws.dgb + kDim, kDim));
   }
+  if (!sch.below) return VETO_OK;      // (the walk above ended inside a layer, or behind layer keep_from)
 
   // ---- token assembly: cls_token, pos_embedding, per-object tables -----------------------------------------------
   // x0[p, t] = token + pos_embedding (ONE 576-vector broadcast over all tokens, model_veto.py:43,62): its gradient is
@@ -468,8 +623,15 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
     const DropSite d = drop_site(opts, 2);   // pos_drop sits between (token + pos_embedding) and the first layer
     if (d.thresh) HIP_TRY(launch_dropout_apply(ws.dx, ws.dx, (size_t)M, kDim, d.seed, d.thresh, d.scale, s));
   }
-  HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, G(T + "pos_embedding"), ws.col_partial, column_sums_chunks(), s));
-  HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, G(T + "cls_token"), ws.col_partial, column_sums_chunks(), s));
+  if (float* g = G(T + "pos_embedding")) HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, g, ws.col_partial, column_sums_chunks(), s));
+  if (float* g = G(T + "cls_token")) HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, g, ws.col_partial, column_sums_chunks(), s));
+  const std::string pe = T + "patch_embed.";
+  const bool want_maps = opts && (opts->d_roi_rgb || opts->d_roi_depth);
+  const bool patch_w = W(pe + "proj_d.weight") || W(pe + "proj_v.weight"), patch_b = W(pe + "proj_d.bias") || W(pe + "proj_v.bias");
+  const bool pos_side = W("pos_embed.0.weight") || W("pos_embed.0.bias") || W("pos_embed.1.weight") || W("pos_embed.1.bias");
+  const bool loc_w = W("location_projection.0.weight"), cls_w = W("class_projection.0.weight"), emb_w = W("obj_embed.weight");
+  const bool lc_side = pos_side || loc_w || cls_w || emb_w || W("location_projection.0.bias") || W("class_projection.0.bias");
+  if (!(patch_w || patch_b || want_maps || lc_side)) return VETO_OK;
   if (ordered) {
     HIP_TRY(launch_assemble_backward_ordered(ws.dx, ws.subj, ws.obj, ws.lc, in->img_obj_offset, in->img_pair_offset, in->n_img, ws.dpatch,
                                              ws.dlc, n_obj, s));
@@ -481,15 +643,14 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
 
   // ---- patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half) ------------------------
   {
-    const std::string pe = T + "patch_embed.";
     const int R = n_obj * 16;
+    if (patch_w || want_maps) HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, 2 * kDim, s));
     // dWcat^T [2048, 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch (fp32) in run_wgrad's roles swapped,
     // so that the output width (1152) is a multiple of 192
-    {
+    if (patch_w) {
       const int N = 2048, K = 2 * kDim;
       const int ks = wgrad_splits(N, K, R, 0, 8);      // (few object rows: tiles of 8 k-steps already)
       const size_t mp = wgrad_mp(R, ks);
-      HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, K, s));
       if (!ordered) HIP_TRY(hipMemsetAsync(ws.dwcat_t, 0, (size_t)N * K * 4, s));
       GemmArgs g{};
       g.a = ws.pa; g.w = ws.dsplit; g.c = ordered ? ws.planes : ws.dwcat_t;
@@ -497,16 +658,18 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
       g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = R; g.zero = ws.zero;
       HIP_TRY(launch_gemm_split(g, ordered ? EPI_PLANES : EPI_ATOMIC, 0, s));
       if (ordered) HIP_TRY(launch_fold_rows(ws.planes, (long)N * K, ks, (long)N * K, ws.dwcat_t, s));
+      HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
     }
-    HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
     // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
-    HIP_TRY(launch_column_sums(ws.dpatch, 2 * kDim, R, kDim, ws.dgb, ws.col_partial, column_sums_chunks(), s));
-    HIP_TRY(hipMemcpyAsync(G(pe + "proj_d.bias"), ws.dgb, 512 * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(G(pe + "proj_v.bias"), ws.dgb + 512, 64 * 4, hipMemcpyDeviceToDevice, s));
+    if (patch_b) {
+      HIP_TRY(launch_column_sums(ws.dpatch, 2 * kDim, R, kDim, ws.dgb, ws.col_partial, column_sums_chunks(), s));
+      HIP_TRY(copy_grad(pe + "proj_d.bias", ws.dgb, 512));
+      HIP_TRY(copy_grad(pe + "proj_v.bias", ws.dgb + 512, 64));
+    }
     // input gradient (optional): dPA = dpatch . Wcat, i.e. the forward GEMM kernel on split(dpatch) (still in ws.dsplit) and
     // Wcat^T as the weight operand; then the inverse of patchify onto the ROI maps.  The reference's depth backbone is
     // trained through roi_depth_features (tools/relation_train_net.py:166-170).
-    if (opts && (opts->d_roi_rgb || opts->d_roi_depth)) {
+    if (want_maps) {
       HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, s));
       GemmArgs g{};
       g.a = ws.dsplit; g.w = ws.wcat_t; g.c = ws.dpa;
@@ -517,47 +680,70 @@ int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const 
   }
 
   // ---- location / class projections and what feeds them -----------------------------------------------------------
-  {
+  if (lc_side) {
     const long ldlc = 2 * 2 * kDim;   // dlc row n = [location 1152 | class 1152]
     // biases sit on the subject half
-    HIP_TRY(launch_column_sums(ws.dlc, ldlc, n_obj, kDim, G("location_projection.0.bias"), ws.col_partial, column_sums_chunks(), s));
-    HIP_TRY(launch_column_sums(ws.dlc + 2 * kDim, ldlc, n_obj, kDim, G("class_projection.0.bias"), ws.col_partial, column_sums_chunks(), s));
-    // position branch: recompute pos (post-ReLU) through the masked gradient path
-    //   dpos = dlc_loc . loc_wt^T ; obj_pos_backward -> dpre (ReLU'), BatchNorm affine gradients
-    HIP_TRY(launch_sgemm_nt(ws.dlc, ldlc, h->loc_wt, 2 * kDim, ws.dpos, kPosDim, n_obj, kPosDim, 2 * kDim, s));
+    if (float* g = G("location_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc, ldlc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (float* g = G("class_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc + 2 * kDim, ldlc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
     const DropSite dpos_site = drop_site(opts, 1);   // Dropout(0.1) behind the ReLU of pos_embed
-    if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
-    HIP_TRY(launch_obj_pos_backward(in->boxes, in->box_mode, in->bn_batch_stats, h->p("pos_embed.0.weight"), h->p("pos_embed.0.bias"),
-                                    h->p("pos_embed.1.weight"), h->p("pos_embed.1.bias"), ws.dpos, ws.dpre, ws.xhat, ws.bn_out, ws.dbn_out,
-                                    G("pos_embed.0.weight"), G("pos_embed.0.bias"), n_obj, s));
+    if (pos_side || loc_w) {      // (the location projection's weight gradient reads bn_out, which obj_pos_backward recomputes)
+      // position branch: recompute pos (post-ReLU) through the masked gradient path
+      //   dpos = dlc_loc . loc_wt^T ; obj_pos_backward -> dpre (ReLU'), BatchNorm affine gradients
+      HIP_TRY(launch_sgemm_nt(ws.dlc, ldlc, h->loc_wt, 2 * kDim, ws.dpos, kPosDim, n_obj, kPosDim, 2 * kDim, s));
+      if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
+      // (what the forward normalised with: this batch's statistics, or the running ones of an eval-mode pos_embed.0)
+      const float* bn_mean = sch.bn_eval ? h->p("pos_embed.0.running_mean") : in->bn_batch_stats;
+      const float* bn_var = sch.bn_eval ? h->p("pos_embed.0.running_var") : in->bn_batch_stats + 4;
+      HIP_TRY(launch_obj_pos_backward(in->boxes, in->box_mode, bn_mean, bn_var, h->p("pos_embed.0.weight"), h->p("pos_embed.0.bias"),
+                                      h->p("pos_embed.1.weight"), h->p("pos_embed.1.bias"), ws.dpos, ws.dpre, ws.xhat, ws.bn_out, ws.dbn_out,
+                                      G("pos_embed.0.weight"), G("pos_embed.0.bias"), n_obj, s));
+    }
     // pos_embed.1: Linear(4, 128): dW[k, c] = sum_n dpre[n, k] bn_out[n, c]; db = column sums of dpre
-    HIP_TRY(launch_sgemm_tn(ws.dpre, kPosDim, ws.bn_out, 4, G("pos_embed.1.weight"), 4, n_obj, kPosDim, 4, s));
-    HIP_TRY(launch_column_sums(ws.dpre, kPosDim, n_obj, kPosDim, G("pos_embed.1.bias"), ws.col_partial, column_sums_chunks(), s));
-    // location_projection weight: d loc_wt[k, j] = sum_n pos[n, k] dlc_loc[n, j], pos = relu(pre): recompute pos = the
-    // forward's value; it equals (dpre != 0 ? ... ) no -- recompute it from bn_out
-    // pos[n, k] = relu(pos_b[k] + sum_c pos_w[k, c] bn_out[n, c]): one small product + ReLU, done by reusing dpos as storage
-    HIP_TRY(launch_sgemm_nt(ws.bn_out, 4, h->p("pos_embed.1.weight"), 4, ws.dpos, kPosDim, n_obj, kPosDim, 4, s));
-    HIP_TRY(launch_bias_relu(ws.dpos, h->p("pos_embed.1.bias"), n_obj, kPosDim, s));
-    if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
-    HIP_TRY(launch_sgemm_tn(ws.dpos, kPosDim, ws.dlc, ldlc, ws.dloc_wt, 2 * kDim, n_obj, kPosDim, 2 * kDim, s));
-    HIP_TRY(launch_untranspose_pair_proj(ws.dloc_wt, G("location_projection.0.weight"), kPosDim, s));
+    if (float* g = G("pos_embed.1.weight")) HIP_TRY(launch_sgemm_tn(ws.dpre, kPosDim, ws.bn_out, 4, g, 4, n_obj, kPosDim, 4, s));
+    if (float* g = G("pos_embed.1.bias")) HIP_TRY(launch_column_sums(ws.dpre, kPosDim, n_obj, kPosDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (loc_w) {
+      // location_projection weight: d loc_wt[k, j] = sum_n pos[n, k] dlc_loc[n, j], pos = relu(pre): recompute pos = the
+      // forward's value; it equals (dpre != 0 ? ... ) no -- recompute it from bn_out
+      // pos[n, k] = relu(pos_b[k] + sum_c pos_w[k, c] bn_out[n, c]): one small product + ReLU, done by reusing dpos as storage
+      HIP_TRY(launch_sgemm_nt(ws.bn_out, 4, h->p("pos_embed.1.weight"), 4, ws.dpos, kPosDim, n_obj, kPosDim, 4, s));
+      HIP_TRY(launch_bias_relu(ws.dpos, h->p("pos_embed.1.bias"), n_obj, kPosDim, s));
+      if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
+      HIP_TRY(launch_sgemm_tn(ws.dpos, kPosDim, ws.dlc, ldlc, ws.dloc_wt, 2 * kDim, n_obj, kPosDim, 2 * kDim, s));
+      HIP_TRY(launch_untranspose_pair_proj(ws.dloc_wt, G("location_projection.0.weight"), kPosDim, s));
+    }
     // class branch: emb = E[label] (hard labels) or softmax(logits) . E (sgcls, :4092-4095);
     // d cls_wt[k, j] = sum_n emb[n, k] dlc_cls[n, j]; demb = dlc_cls . cls_wt^T
     const int C_obj = h->cfg.num_obj_cls;
-    if (in->obj_logits) {
-      HIP_TRY(launch_softmax_rows(in->obj_logits, ws.prob, n_obj, C_obj, s));
-      HIP_TRY(launch_sgemm_nn(ws.prob, C_obj, h->p("obj_embed.weight"), E, ws.emb, E, n_obj, E, C_obj, s));
-    } else {
-      HIP_TRY(launch_gather_rows(h->p("obj_embed.weight"), in->obj_labels, E, ws.emb, n_obj, s));
+    if (in->obj_logits && (cls_w || emb_w)) HIP_TRY(launch_softmax_rows(in->obj_logits, ws.prob, n_obj, C_obj, s));
+    if (cls_w) {
+      if (in->obj_logits) HIP_TRY(launch_sgemm_nn(ws.prob, C_obj, h->p("obj_embed.weight"), E, ws.emb, E, n_obj, E, C_obj, s));
+      else HIP_TRY(launch_gather_rows(h->p("obj_embed.weight"), in->obj_labels, E, ws.emb, n_obj, s));
+      HIP_TRY(launch_sgemm_tn(ws.emb, E, ws.dlc + 2 * kDim, ldlc, ws.dcls_wt, 2 * kDim, n_obj, E, 2 * kDim, s));
+      HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
     }
-    HIP_TRY(launch_sgemm_tn(ws.emb, E, ws.dlc + 2 * kDim, ldlc, ws.dcls_wt, 2 * kDim, n_obj, E, 2 * kDim, s));
-    HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
-    HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, ldlc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
-    if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, G("obj_embed.weight"), E, n_obj, C_obj, E, s));
-    else if (ordered) HIP_TRY(launch_scatter_rows_ordered(ws.demb, in->obj_labels, E, G("obj_embed.weight"), n_obj, C_obj, s));
-    else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, G("obj_embed.weight"), n_obj, s));
+    if (float* g = G("obj_embed.weight")) {
+      HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, ldlc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
+      if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, g, E, n_obj, C_obj, E, s));
+      else if (ordered) HIP_TRY(launch_scatter_rows_ordered(ws.demb, in->obj_labels, E, g, n_obj, C_obj, s));
+      else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, g, n_obj, s));
+    }
   }
   return VETO_OK;
+}
+
+int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
+                  size_t workspace_bytes, const float* dlogits, float* grads) {
+  return backward_impl(h, stream, in, opts, Sched(), workspace, workspace_bytes, dlogits, grads);
+}
+
+int veto_backward_plan(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, const veto_train_plan_t* plan,
+                       void* workspace, size_t workspace_bytes, const float* dlogits, float* grads) {
+  if (!plan) return veto_backward(h, stream, in, opts, workspace, workspace_bytes, dlogits, grads);
+  if (!h) return fail(VETO_ERR_INVALID, "null argument");
+  ABI_TRY(check_train_opts(opts));
+  Sched sch;
+  ABI_TRY(make_sched(h, opts, plan, &sch));
+  return backward_impl(h, stream, in, opts, sch, workspace, workspace_bytes, dlogits, grads);
 }
 
 // workspace: lse | nll_w | w_row | inv_wsum

@@ -732,7 +732,7 @@ hipError_t launch_layernorm_backward(const float* x, const float* dy, const floa
                              drop_seed, drop_thresh, drop_scale, drop_row_step);
   else VETO_LAUNCH(layernorm_backward_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess || !dgamma_dbeta) return e;      // (nullptr: frozen gain and bias, the fold of their partial rows is left out)
   return launch_column_sums(partial, 2 * kDim, blocks, 2 * kDim, dgamma_dbeta, partial + (size_t)blocks * 2 * kDim, kColChunks, s);
 }
 

@@ -726,7 +726,7 @@ hipError_t launch_meet_sample(const MeetSampleArgs& a, hipStream_t s);
 hipError_t launch_attention_backward(const float* qkv, const float* dout, float* dqkv, __bf16* dqkv_split, int n_pair, int heads, int cls_only,
                                      hipStream_t s, bool qkv_f24 = false);
 // dx = LayerNorm backward of dy w.r.t. x (+ dres if given); dgamma_dbeta [2, 576]; partial: workspace of
-// layernorm_backward_partial_floats(rows) floats
+// layernorm_backward_partial_floats(rows) floats (dgamma_dbeta == nullptr: not wanted, the fold of the partial rows is left out)
 size_t layernorm_backward_partial_floats(int rows);
 // split_out / colp (both or neither): also write the result's split rows [rows, 2 * 576] (with the dropout mask of site drop_seed applied
 // when drop_thresh != 0: element (row, col) -> index (row * drop_row_step) * 576 + col) and layernorm_backward_col_partials(rows) rows of column sums [*, 576]
@@ -761,7 +761,7 @@ hipError_t launch_prep_grad(const float* src, long ld, int M, int N, __bf16* row
                             const GradXform& xf, hipStream_t s);
 hipError_t launch_gelu_split(const float* pre, __bf16* dst, size_t rows, int n_cols, hipStream_t s);
 // dx row p = dlogits[p] . W; dw [n_out, 576], db [n_out]; row p of x and of dx at + p * ld floats (the CLS rows)
-// partial: workspace of head_backward_partial_floats(n_out) floats
+// partial: workspace of head_backward_partial_floats(n_out) floats.  dx / dw / db == nullptr: that output and its launches are left out
 size_t head_backward_partial_floats(int n_out);
 hipError_t launch_head_backward(const float* dlogits, const float* w, const float* x, float* dx, float* dw, float* db, float* partial,
                                 int n_pair, int n_out, long ld, hipStream_t s);
@@ -774,7 +774,9 @@ hipError_t launch_assemble_backward_ordered(const float* dx, const int32_t* subj
                                             int n_obj, hipStream_t s);
 hipError_t launch_sgemm_tn(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int n, int ka, int kb, hipStream_t s);
 hipError_t launch_sgemm_nt(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int n, int ki, int kj, hipStream_t s);
-hipError_t launch_obj_pos_backward(const float* boxes, int box_mode, const float* stats, const float* bn_w, const float* bn_b,
+// mean / var [4]: what the forward's BatchNorm normalised with (the batch statistics, or the running ones of an eval-mode pos_embed.0);
+// dgamma / dbeta == nullptr: that affine gradient is not written (both: its kernel is not launched)
+hipError_t launch_obj_pos_backward(const float* boxes, int box_mode, const float* mean, const float* var, const float* bn_w, const float* bn_b,
                                    const float* pos_w, const float* pos_b, const float* dpos, float* dpre, float* xhat, float* bn_out,
                                    float* dbn_out, float* dgamma, float* dbeta, int n_obj, hipStream_t s);
 hipError_t launch_sgemm_nn(const float* a, long lda, const float* b, long ldb, float* c, long ldc, int n, int ki, int kj, hipStream_t s);
@@ -786,7 +788,7 @@ hipError_t launch_scatter_rows(const float* demb, const int64_t* labels, int dim
 hipError_t launch_scatter_rows_ordered(const float* demb, const int64_t* labels, int dim, float* dtable, int n, int n_table_rows,
                                        hipStream_t s);
 hipError_t launch_untranspose_pair_proj(const float* dwt, float* dw, int kin, hipStream_t s);
-hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, hipStream_t s);
+hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, hipStream_t s);      // (dwd / dwv == nullptr: not written)
 // Input gradient of the patch projection (training): the TRANSPOSE of the combined patch weight as a GEMM weight operand,
 // dst [kPatchTRows = 2112, 2*1152] split rows (rows 2048.. are zero: 2112 = 11 x 192 output columns), and the scatter of
 // dPA [n_obj*16, ld] fp32 (patch rows x patch features, depth features first) back onto the ROI maps [n_obj, 256, 8, 8]

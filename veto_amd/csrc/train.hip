@@ -254,7 +254,8 @@ __global__ __launch_bounds__(256) void bias_relu_kernel(float* __restrict__ x, c
 // ---- per-object stage backward: recompute the normalised box, the position pre-activation and apply ReLU' ------
 // in:  dpos [n, 128] (gradient of the ReLU'd position embedding);  out: dpre [n, 128] (masked), xhat [n, 4],
 //      bn_out [n, 4], dbn_out [n, 4] = dpre . pos_w
-__global__ __launch_bounds__(128) void obj_pos_backward_kernel(const float* __restrict__ boxes, int box_mode, const float* __restrict__ stats,
+__global__ __launch_bounds__(128) void obj_pos_backward_kernel(const float* __restrict__ boxes, int box_mode, const float* __restrict__ mean,
+                                                               const float* __restrict__ var,
                                                                const float* __restrict__ bn_w, const float* __restrict__ bn_b,
                                                                const float* __restrict__ pos_w, const float* __restrict__ pos_b,
                                                                const float* __restrict__ dpos, float* __restrict__ dpre,
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(128) void obj_pos_backward_kernel(const float* __re
     float w, h;
     if (box_mode == 0) { w = b[2] - b[0] + 1.f; h = b[3] - b[1] + 1.f; } else { w = b[2]; h = b[3]; }
     const float v = tid == 0 ? b[0] + 0.5f * w : tid == 1 ? b[1] + 0.5f * h : tid == 2 ? w : h;
-    s_x[tid] = (v - stats[tid]) / sqrtf(stats[4 + tid] + 1e-5f);
+    s_x[tid] = (v - mean[tid]) / sqrtf(var[tid] + 1e-5f);
     s_y[tid] = s_x[tid] * bn_w[tid] + bn_b[tid];
     xhat[(size_t)n * 4 + tid] = s_x[tid];
     bn_out[(size_t)n * 4 + tid] = s_y[tid];
@@ -294,8 +295,8 @@ __global__ void bn_affine_backward_kernel(const float* __restrict__ dy, const fl
   if (c >= 4) return;
   double g = 0.0, b = 0.0;
   for (int r = 0; r < n; ++r) { g += (double)dy[(size_t)r * 4 + c] * xhat[(size_t)r * 4 + c]; b += dy[(size_t)r * 4 + c]; }
-  dgamma[c] = (float)g;
-  dbeta[c] = (float)b;
+  if (dgamma) dgamma[c] = (float)g;
+  if (dbeta) dbeta[c] = (float)b;
 }
 
 // emb[n, :] = E[label[n], :]
@@ -341,8 +342,8 @@ __global__ __launch_bounds__(256) void patch_weight_grad_kernel(const float* __r
   const int half = j / kDim, jj = j % kDim;
   for (int f = threadIdx.x; f < 1024; f += 256) {
     const int pp = f >> 8, c = f & 255;
-    if (jj < 512) dwd[(size_t)jj * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)f * (2 * kDim) + j];
-    else dwv[(size_t)(jj - 512) * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)(1024 + f) * (2 * kDim) + j];
+    if (jj < 512) { if (dwd) dwd[(size_t)jj * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)f * (2 * kDim) + j]; }
+    else if (dwv) dwv[(size_t)(jj - 512) * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)(1024 + f) * (2 * kDim) + j];
   }
 }
 
@@ -379,15 +380,20 @@ size_t head_backward_partial_floats(int n_out) {
 
 hipError_t launch_head_backward(const float* dlogits, const float* w, const float* x, float* dx, float* dw, float* db, float* partial,
                                 int n_pair, int n_out, long ld, hipStream_t s) {
-  VETO_LAUNCH(head_dcls_kernel, dim3(n_pair), dim3(576), (size_t)n_out * 4, s, dlogits, w, dx, n_out, ld);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  // (partial training: dx / dw / db == nullptr leaves that output's launches out)
+  hipError_t e = hipSuccess;
+  if (dx) {
+    VETO_LAUNCH(head_dcls_kernel, dim3(n_pair), dim3(576), (size_t)n_out * 4, s, dlogits, w, dx, n_out, ld);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   const int n_chunks = 64, chunk = (n_pair + n_chunks - 1) / n_chunks;
-  VETO_LAUNCH(head_dw_kernel, dim3(n_out, n_chunks), dim3(576), 0, s, dlogits, x, partial, n_pair, n_out, chunk, ld);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   float* scratch = partial + (size_t)n_chunks * n_out * kDim;
-  if ((e = launch_column_sums(partial, (long)n_out * kDim, n_chunks, n_out * kDim, dw, scratch, 8, s)) != hipSuccess) return e;
-  return launch_column_sums(dlogits, n_out, n_pair, n_out, db, scratch, column_sums_chunks(), s);
+  if (dw) {
+    VETO_LAUNCH(head_dw_kernel, dim3(n_out, n_chunks), dim3(576), 0, s, dlogits, x, partial, n_pair, n_out, chunk, ld);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_column_sums(partial, (long)n_out * kDim, n_chunks, n_out * kDim, dw, scratch, 8, s)) != hipSuccess) return e;
+  }
+  return db ? launch_column_sums(dlogits, n_out, n_pair, n_out, db, scratch, column_sums_chunks(), s) : e;
 }
 
 hipError_t launch_assemble_backward(const float* dx, const int32_t* subj, const int32_t* obj, const float* lc, float* dpatch, float* dlc,
@@ -416,13 +422,13 @@ hipError_t launch_sgemm_nt(const float* a, long lda, const float* b, long ldb, f
   return hipGetLastError();
 }
 
-hipError_t launch_obj_pos_backward(const float* boxes, int box_mode, const float* stats, const float* bn_w, const float* bn_b,
+hipError_t launch_obj_pos_backward(const float* boxes, int box_mode, const float* mean, const float* var, const float* bn_w, const float* bn_b,
                                    const float* pos_w, const float* pos_b, const float* dpos, float* dpre, float* xhat, float* bn_out,
                                    float* dbn_out, float* dgamma, float* dbeta, int n_obj, hipStream_t s) {
-  VETO_LAUNCH(obj_pos_backward_kernel, dim3(n_obj), dim3(kPosDim), 0, s, boxes, box_mode, stats, bn_w, bn_b, pos_w, pos_b, dpos, dpre, xhat,
-              bn_out, dbn_out);
+  VETO_LAUNCH(obj_pos_backward_kernel, dim3(n_obj), dim3(kPosDim), 0, s, boxes, box_mode, mean, var, bn_w, bn_b, pos_w, pos_b, dpos, dpre,
+              xhat, bn_out, dbn_out);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess || (!dgamma && !dbeta)) return e;
   VETO_LAUNCH(bn_affine_backward_kernel, dim3(1), dim3(64), 0, s, dbn_out, xhat, n_obj, dgamma, dbeta);
   return hipGetLastError();
 }

@@ -226,6 +226,11 @@ class VetoTrainOpts(Structure):
                 ("seed", ctypes.c_uint64), ("d_roi_rgb", c_void_p), ("d_roi_depth", c_void_p), ("deterministic", c_int32)]
 
 
+class VetoTrainPlan(Structure):
+    _fields_ = [("struct_size", c_int32), ("bn_eval", c_int32), ("trainable", c_void_p), ("p_attn_layer", c_void_p),
+                ("d_roi", c_int32), ("reserved0", c_int32)]
+
+
 STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_abi_symbols.py compares every field's offset and size)
     "veto_config_t": VetoConfig, "veto_inputs_t": VetoInputs, "veto_debug_outputs_t": VetoDebugOutputs,
     "veto_saturation_t": VetoSaturation, "veto_post_args_t": VetoPostArgs, "veto_post_meet_args_t": VetoPostMeetArgs,
@@ -236,6 +241,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_rpn_loss_args_t": VetoRpnLossArgs, "veto_box_loss_args_t": VetoBoxLossArgs,
     "veto_optim_tensor_t": VetoOptimTensor, "veto_optim_args_t": VetoOptimArgs,
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
+    "veto_train_plan_t": VetoTrainPlan,
     "veto_det_eval_match_args_t": VetoDetEvalMatchArgs, "veto_det_eval_accumulate_args_t": VetoDetEvalAccumulateArgs,
     "veto_sgg_eval_fold_args_t": VetoSggEvalFoldArgs,
 }
@@ -304,6 +310,9 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_weight_offset": _sig(_P, _I, POINTER(_Z)),
     "veto_forward_train": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), _P, _Z, _P),
     "veto_backward": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), _P, _Z, _P, _P),
+    "veto_train_workspace_bytes_plan": _sig(_P, _I, _I, POINTER(VetoTrainOpts), POINTER(VetoTrainPlan), ret=_Z),
+    "veto_forward_train_plan": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), POINTER(VetoTrainPlan), _P, _Z, _P),
+    "veto_backward_plan": _sig(_P, _P, POINTER(VetoInputs), POINTER(VetoTrainOpts), POINTER(VetoTrainPlan), _P, _Z, _P, _P),
     "veto_debug_attention_backward": _sig(_P, _P, _P, _P, _I, _I),
     "veto_debug_layernorm_backward": _sig(_P, _P, _P, _P, _P, _P, _P, _I, _P, _Z),
     "veto_debug_layernorm_backward_workspace_bytes": _sig(_I, ret=_Z),

@@ -246,18 +246,25 @@ class _NativeForward:
             self._uploaded = ver
         return self._engine
 
+    @staticmethod
+    def _rate(drop):
+        """The rate a dropout site runs at: its module's p, or 0 while the module is in eval() (as nn.Dropout behaves)."""
+        return float(drop.p) if drop.training else 0.0
+
+    def _attn_rates(self):
+        return [self._rate(layer[0].fn.to_out[1]) for layer in self._trunk.fusion_transformer.transformer.layers]
+
     def _train_opts(self):
         """Dropout probabilities of the three sites the training path implements, read from the mirror modules (so that
-        `module.p = 0` behaves as in torch), plus a fresh seed drawn from torch's generator."""
+        `module.p = 0` and `module.eval()` behave as in torch), plus a fresh seed drawn from torch's generator.  Attention
+        rates that differ between the layers travel in the plan (_train_plan); p_attn is then not read."""
         t = self._trunk
         tr = t.fusion_transformer.transformer
         o = native.VetoTrainOpts(struct_size=ctypes.sizeof(native.VetoTrainOpts))
-        o.p_pos = float(t.pos_embed[3].p)
-        o.p_emb = float(tr.pos_drop.p)
-        ps = {float(layer[0].fn.to_out[1].p) for layer in tr.layers}
-        if len(ps) != 1:
-            raise NotImplementedError("veto_amd: per-layer attention dropout rates must be equal")
-        o.p_attn = ps.pop()
+        o.p_pos = self._rate(t.pos_embed[3])
+        o.p_emb = self._rate(tr.pos_drop)
+        ps = set(self._attn_rates())
+        o.p_attn = ps.pop() if len(ps) == 1 else 0.0
         others = [n for n, m in t.named_modules() if isinstance(m, nn.Dropout) and m.p > 0 and
                   not (n == "pos_embed.3" or n.endswith("pos_drop") or n.endswith("fn.to_out.1"))]
         others = [n for n in others if not n.startswith("bbox_embed")]        # bbox_embed is not on the VETO path
@@ -354,6 +361,25 @@ class _NativeForward:
             row += head.out_features
         return spec
 
+    def _train_plan(self, eng, spec, want_maps):
+        """The veto_train_plan_t of this step, or None when every parameter is trainable, pos_embed[0] is in training mode and
+        the layers share one attention dropout rate: the step then runs through the entry points without a plan, as it always
+        did.  Returns (plan, the ctypes arrays it points into)."""
+        flags = {}
+        for prm, name, _, _ in spec:      # (the heads of a MEET list share rel_out.*: one trainable head sets the flag)
+            flags[name] = flags.get(name, False) or bool(prm.requires_grad)
+        rates = self._attn_rates()
+        bn_eval = not self._trunk.pos_embed[0].training
+        if all(flags.values()) and not bn_eval and len(set(rates)) == 1:
+            return None, None
+        names = [n for n, _ in eng.weight_specs()]
+        trainable = (ctypes.c_uint8 * len(names))(*[1 if flags.get(n, False) else 0 for n in names])
+        p_layer = (ctypes.c_float * len(rates))(*rates)
+        plan = native.VetoTrainPlan(struct_size=ctypes.sizeof(native.VetoTrainPlan), bn_eval=int(bn_eval),
+                                    trainable=ctypes.cast(trainable, ctypes.c_void_p), p_attn_layer=ctypes.cast(p_layer, ctypes.c_void_p),
+                                    d_roi=int(bool(want_maps)))
+        return plan, (trainable, p_layer)
+
     def _run_native_train_grad(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits=None):
         """Training-mode forward whose result carries an autograd graph: logits [sum P, num_out]."""
         spec = self._train_param_spec()
@@ -371,18 +397,30 @@ class _WsToken:
 
 
 class _TrainFn(torch.autograd.Function):
-    """logits = VETO trunk + heads in training mode; backward fills the gradients of every parameter through
-    veto_backward.  The parameters are inputs only so that autograd routes their gradients."""
+    """logits = VETO trunk + heads in training mode; backward fills the gradients of every trainable parameter through
+    veto_backward (veto_backward_plan when a parameter is frozen or a sub-module is in eval mode: _NativeForward._train_plan)
+    and returns None for the frozen ones.  The parameters are inputs only so that autograd routes their gradients."""
 
     @staticmethod
     def forward(ctx, owner, call, roi_features, roi_depth_features, *params):
         proposals, rel_pair_idxs, labels, obj_logits = call
         device = roi_features.device
-        stats = torch.empty(12, dtype=torch.float32, device=device)
+        bn = owner._trunk.pos_embed[0]
+        # (an eval-mode BatchNorm normalises with its running statistics and leaves them alone: no batch statistics then)
+        stats = torch.empty(12, dtype=torch.float32, device=device) if bn.training else None
         launch, inp, n_objs, n_pairs, eng = owner._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
                                                                 labels, obj_logits, stats)
         opts = owner._train_opts()
-        need = launch.lib.veto_train_workspace_bytes_opts(eng.handle, inp.n_obj, inp.n_pair, ctypes.byref(opts))
+        ctx.spec = owner._train_param_spec()
+        plan, ctx.plan_arrays = owner._train_plan(eng, ctx.spec, ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        ctx.plan = plan
+        plan_ref = ctypes.byref(plan) if plan is not None else None
+        if plan is None:
+            need = launch.lib.veto_train_workspace_bytes_opts(eng.handle, inp.n_obj, inp.n_pair, ctypes.byref(opts))
+        else:
+            need = launch.lib.veto_train_workspace_bytes_plan(eng.handle, inp.n_obj, inp.n_pair, ctypes.byref(opts), plan_ref)
+            if need == 0:
+                raise native.VetoError("veto_amd: %s" % launch.lib.veto_last_error().decode())
         # tens of GB: keep one workspace on the module and hand it to the next step once its backward has run (an
         # allocation of this size goes to the driver every time, and releasing it synchronises the device)
         # The cached workspace belongs to at most one forward whose backward has not run yet.  Ownership is a token held by
@@ -401,16 +439,19 @@ class _TrainFn(torch.autograd.Function):
             ctx.ws_token = _WsToken()
             owner.__dict__["_train_ws_owner"] = weakref.ref(ctx.ws_token)
         out = torch.empty((inp.n_pair, owner._num_out), dtype=torch.float32, device=device)
-        launch.run("veto_forward_train", ctypes.byref(inp), ctypes.byref(opts), ws.data_ptr(), ws.numel(), out.data_ptr(), handle=eng.handle)
+        if plan is None:
+            launch.run("veto_forward_train", ctypes.byref(inp), ctypes.byref(opts), ws.data_ptr(), ws.numel(), out.data_ptr(), handle=eng.handle)
+        else:
+            launch.run("veto_forward_train_plan", ctypes.byref(inp), ctypes.byref(opts), plan_ref, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                       handle=eng.handle)
         ctx.opts = opts
-        bn = owner._trunk.pos_embed[0]
-        with torch.no_grad():    # nn.BatchNorm1d(momentum=0.001) running statistics
-            m = bn.momentum
-            bn.running_mean.mul_(1 - m).add_(stats[0:4].to(bn.running_mean.device), alpha=m)
-            bn.running_var.mul_(1 - m).add_(stats[8:12].to(bn.running_var.device), alpha=m)
-            bn.num_batches_tracked += 1
+        if stats is not None:
+            with torch.no_grad():    # nn.BatchNorm1d(momentum=0.001) running statistics
+                m = bn.momentum
+                bn.running_mean.mul_(1 - m).add_(stats[0:4].to(bn.running_mean.device), alpha=m)
+                bn.running_var.mul_(1 - m).add_(stats[8:12].to(bn.running_var.device), alpha=m)
+                bn.num_batches_tracked += 1
         ctx.owner, ctx.inp, ctx.launch, ctx.ws, ctx.eng = owner, inp, launch, ws, eng   # (launch: the tensors `inp` points into)
-        ctx.spec = owner._train_param_spec()
         return out
 
     @staticmethod
@@ -427,13 +468,20 @@ class _TrainFn(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             d_dep = torch.empty((n_obj, 256, 8, 8), dtype=torch.float32, device=device)
         ctx.opts.d_roi_rgb, ctx.opts.d_roi_depth = launch.ptr(d_rgb), launch.ptr(d_dep)
-        launch.run("veto_backward", ctypes.byref(ctx.inp), ctypes.byref(ctx.opts), ctx.ws.data_ptr(), ctx.ws.numel(),
-                 launch.ptr(dlogits), flat.data_ptr(), handle=eng.handle)
+        if ctx.plan is None:
+            launch.run("veto_backward", ctypes.byref(ctx.inp), ctypes.byref(ctx.opts), ctx.ws.data_ptr(), ctx.ws.numel(),
+                       launch.ptr(dlogits), flat.data_ptr(), handle=eng.handle)
+        else:      # (only the regions of `flat` that belong to trainable tensors are written, and only those are read below)
+            launch.run("veto_backward_plan", ctypes.byref(ctx.inp), ctypes.byref(ctx.opts), ctypes.byref(ctx.plan), ctx.ws.data_ptr(),
+                       ctx.ws.numel(), launch.ptr(dlogits), flat.data_ptr(), handle=eng.handle)
         if ctx.ws_token is not None:
             ctx.ws_token.done = True
         offsets = eng.weight_offsets()
         grads = []
         for prm, name, row0, rows in ctx.spec:
+            if not prm.requires_grad:      # frozen: autograd did not ask, and under a plan the region was never written
+                grads.append(None)
+                continue
             off, numel = offsets[name]
             if rows is None:
                 g = flat[off:off + numel]
