@@ -259,6 +259,46 @@ typedef struct veto_post_vote_args {
 /* workspace: veto_postprocess_workspace_bytes(n_groups * n_pair, n_rel_cls) */
 int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* args, void* workspace, size_t workspace_bytes);
 
+/* The MEET merge (experts_per_group 1) and the EXPERT_GROUP vote (experts_per_group 3) for a WHOLE ragged batch: image i gets exactly
+ * what veto_postprocess_meet / veto_postprocess_vote return for image i alone, bit for bit, in at most four launches per call
+ * (object scores, group scores, one sort workgroup per image, gather) whatever n_img and n_groups.
+ * Row layout of the four relation outputs (n_groups * n_pair rows, P_i = pairs of image i): image i owns the contiguous block of
+ * n_groups * P_i rows that starts at row n_groups * img_pair_offset[i].  Before the sort a block is ordered (group, pair) -- row
+ * k * P_i + p -- as the one-image merged list, and it is sorted by (score descending, that index ascending).  Vote: the first
+ * kept_count[i] rows of block i are the result; rows kept_count[i] .. of a block are padding with unspecified content.
+ * The group heads are batch-wide: row p of every head is pair p of the concatenated pair list.
+ * Refused before any launch: n_groups * P_i > 16384 (the message names the image), a group width outside 3..105 or not its class
+ * count + 2, n_rel_cls > 256, n_groups > 16, voting not 0 / 1, n_groups * n_pair beyond int32, pairs_per_image that do not add up to
+ * n_pair or whose maximum is not max_pairs_per_image, null pointers, a workspace below
+ * veto_postprocess_workspace_bytes(n_groups * n_pair, n_rel_cls). */
+typedef struct veto_post_groups_batch_args {
+  int32_t struct_size;
+  int32_t n_img, n_obj, n_pair;       /* images; objects and pairs over the batch */
+  int32_t n_groups, experts_per_group;/* experts_per_group: 1 = MEET merge, 3 = expert vote */
+  int32_t n_rel_cls, n_obj_cls;
+  int32_t voting;                     /* vote: 0 = 'C', 1 = 'U'; merge: 0 */
+  int32_t max_pairs_per_image;        /* host-side maximum of pairs_per_image; n_groups * max_pairs_per_image <= 16384 */
+  const float* const* head_logits;    /* HOST array of experts_per_group * n_groups device pointers, [experts_per_group * k + e],
+                                         each [n_pair, group_widths[k]] */
+  const int32_t* group_widths;        /* HOST array [n_groups]: g_k + 2 */
+  const int32_t* incre_idx_list;      /* HOST array [n_rel_cls]: 1-based group of each class, 0 = background */
+  const int32_t* pairs_per_image;     /* HOST array [n_img]: P_i >= 0, the differences of img_pair_offset */
+  const float* obj_logits;            /* device [n_obj, n_obj_cls]; NULL (sgdet): obj_scores / obj_pred are inputs */
+  const int64_t* rel_pairs;           /* device [n_pair, 2] image-local, images concatenated */
+  const int32_t* img_obj_offset;      /* device [n_img + 1] */
+  const int32_t* img_pair_offset;     /* device [n_img + 1] */
+  float* obj_scores;                  /* out device [n_obj] */
+  int64_t* obj_pred;                  /* out device [n_obj] */
+  float* rel_prob_sorted;             /* out device [n_groups*n_pair, n_rel_cls] */
+  int64_t* rel_pairs_sorted;          /* out device [n_groups*n_pair, 2] */
+  int64_t* rel_labels_sorted;         /* out device [n_groups*n_pair] (group-local labels) */
+  float* triple_sorted;               /* optional out device [n_groups*n_pair]; vote: -1 marks padding rows */
+  int32_t* kept_count;                /* vote: out device [n_img]; merge: NULL */
+} veto_post_groups_batch_args_t;
+
+/* workspace: veto_postprocess_workspace_bytes(n_groups * n_pair, n_rel_cls) */
+int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_args_t* args, void* workspace, size_t workspace_bytes);
+
 /* ---- sgdet: the relation head on the detector's own boxes (USE_GT_BOX False) ------------------------
  * veto_obj_decode: greedy class-aware NMS over softmax(logits), for a ragged batch (one workgroup per image).
  *   mode 0 = obj_prediction_nms (utils_relation.py:94-128) as the PostProcessor uses it (inference.py:410-429, the

@@ -1,0 +1,370 @@
+"""The MEET merge and the expert vote of a whole batch (veto_postprocess_groups_batch, PostProcessor with more than one image):
+image i of a batch call gets, bit for bit, what the one-image call on image i gives, and the oracle's rows; the ABI writes
+exactly the stated rows and refuses what it cannot hold before any launch.  The batches are those of tests/post_batch_cases.py,
+their premises are asserted on the CPU in tests/test_post_batch_host.py; the figures the tests print are kept in
+profiles/post_meet_batch.txt.  Every call is made twice and the two results must be equal."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import post_batch_cases as bc
+import post_eval_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+SENTINEL = 0x5A
+FIELDS = ("rel_pair_idxs", "pred_rel_scores", "pred_rel_labels", "pred_labels", "pred_scores")
+
+
+def _to(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+def _boxes(n):
+    from veto_amd.structures import BoxList
+    return BoxList(torch.zeros(n, 4), (800, 600)).to(DEV)
+
+
+def _post(voting=None, use_gt_box=True, thr=0.3):
+    from veto_amd import testing
+    from veto_amd.postprocess import PostProcessor
+    cfg = None
+    if voting:
+        cfg = testing.make_config(1, 8, meet=True, dataset="VG")
+        cfg.ENSEMBLE_LEARNING.EXPERT_GROUP = True
+        cfg.ENSEMBLE_LEARNING.VOTING = voting
+    return PostProcessor(False, use_gt_box=use_gt_box, later_nms_pred_thres=thr, cfg=cfg)
+
+
+def _snapshot(results, triples, bbox=False):
+    """Per image: the result's fields as tensors of their own (a GT-box call writes into the BoxLists it is given)."""
+    out = []
+    for r, t in zip(results, triples):
+        d = {k: r.get_field(k).clone() for k in FIELDS}
+        d["triple_scores"] = t.clone()
+        if bbox:
+            d["bbox"] = r.bbox.clone()
+        out.append(d)
+    torch.cuda.synchronize()
+    return out
+
+
+def _assert_same(a, b, where):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and torch.equal(a[k], b[k]), (where, k)
+
+
+def _twice(call):
+    first, second = call(), call()
+    for i, (a, b) in enumerate(zip(first, second)):
+        _assert_same(a, b, ("second call", i))
+    return first
+
+
+def _call(post, rel, objs, pairs, incre, boxes):
+    res = post(({k: _to(v) for k, v in rel.items()}, [_to(o) for o in objs]), [_to(p) for p in pairs], boxes, incre_idx_list=incre,
+               ensemble=True)
+    assert len(res) == len(boxes) == len(post.last_triple_scores)
+    assert all(r.get_field("rel_pair_idxs").dtype == torch.float32 for r in res)
+    return _snapshot(res, post.last_triple_scores, bbox=not post.use_gt_box)
+
+
+@functools.lru_cache(maxsize=None)
+def _run_batch(batch):
+    x = bc.inputs(batch)
+    post = _post(bc.voting(batch))
+    return _twice(lambda: _call(post, x["rel"], x["obj"], x["pairs"], x["incre"], [_boxes(n) for n in x["n_objs"]]))
+
+
+def _run_alone(batch, i):
+    x, s = bc.inputs(batch), bc.image_slices(batch, i)
+    post = _post(bc.voting(batch))
+    return _twice(lambda: _call(post, s["rel"], [s["obj"]], [s["pairs"]], x["incre"], [_boxes(x["n_objs"][i])]))[0]
+
+
+def _np(d):
+    return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+# ---- 1. batch = per image, bit for bit -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batch", bc.BATCH_NAMES)
+def test_batch_equals_the_one_image_calls_bit_for_bit(batch):
+    """Every image of every batch against PostProcessor called on that image alone with the slices of the same inputs: every
+    field, every row.  (Before the batch form existed this raised ValueError: 'one image per batch'.)"""
+    got = _run_batch(batch)
+    K = bc.n_groups(batch)
+    for i, g in enumerate(got):
+        _assert_same(g, _run_alone(batch, i), (batch, i))
+        if not bc.voting(batch):
+            assert g["triple_scores"].shape[0] == K * bc.inputs(batch)["n_pairs"][i]
+    print("post_batch: %-18s %d images, rows %s: equal to the one-image calls, bit for bit"
+          % (batch, len(got), [int(g["triple_scores"].shape[0]) for g in got]))
+
+
+@pytest.mark.parametrize("expert", [False, True])
+def test_sgdet_batch_equals_the_one_image_calls_bit_for_bit(expert):
+    """Detected boxes (use_gt_box False): three images of 1, 5 and 20 detections, merge and vote; the regressed boxes too."""
+    from veto_amd.structures import BoxList
+    s = bc.sgdet_batch(expert)
+    post = _post("C" if expert else None, use_gt_box=False, thr=bc.SGDET_THR)
+
+    def props(idx):
+        out = []
+        for i in idx:
+            d = s["dets"][i]
+            b = BoxList(_to(d["boxes"]), d["image_size"], "xyxy")
+            b.add_field("boxes_per_cls", _to(d["boxes_per_cls"]))
+            out.append(b)
+        return out
+
+    objs = [d["predict_logits"] for d in s["dets"]]
+    every = list(range(len(s["dets"])))
+    got = _twice(lambda: _call(post, s["rel"], objs, s["pairs"], s["incre"], props(every)))
+    p0 = np.concatenate([[0], np.cumsum(s["n_pairs"])])
+    for i in every:
+        rel = {k: v[p0[i]:p0[i + 1]] for k, v in s["rel"].items()}
+        alone = _twice(lambda: _call(post, rel, [objs[i]], [s["pairs"][i]], s["incre"], props([i])))[0]
+        _assert_same(got[i], alone, ("sgdet", expert, i))
+        lab = got[i]["pred_labels"].cpu().numpy()
+        assert np.array_equal(got[i]["bbox"].cpu().numpy(), s["dets"][i]["boxes_per_cls"][np.arange(len(lab)), lab])
+    assert not expert or sum(int(g["triple_scores"].shape[0]) for g in got) > 0
+    print("post_batch: sgdet %s rows %s: equal to the one-image calls, bit for bit"
+          % ("vote 'C'" if expert else "merge", [int(g["triple_scores"].shape[0]) for g in got]))
+
+
+# ---- 2. batch against the oracle -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("batch", bc.BATCH_NAMES)
+def test_batch_against_the_oracle_every_row(batch):
+    x, K = bc.inputs(batch), bc.n_groups(batch)
+    for i, (g, ref, exact) in enumerate(zip(_run_batch(batch), bc.expected(batch), bc.exact(batch))):
+        rows = None if bc.voting(batch) else K * x["n_pairs"][i]
+        fig = pc.compare_rows(_np(g), ref, x["pairs"][i], x["incre"], expect_all=rows, exact_order=exact)
+        print("post_batch: %-18s image %d rows %5d  max err: probabilities %.2e  triple %.2e  object score %.2e | bit-equal "
+              "neighbours %5d, rows not at the oracle's position %4d (their oracle scores within %.2e)"
+              % (batch, i, fig["rows"], fig["prob_err"], fig["triple_err"], fig["obj_err"], fig["bit_ties"], fig["moved"],
+                 fig["moved_gap"]))
+
+
+# ---- 3. reversed image order -----------------------------------------------------------------------------------------------------
+def test_reversed_image_order_gives_the_same_per_image_results():
+    for rev, fwd in bc.REVERSED.items():
+        a, b = _run_batch(rev), _run_batch(fwd)
+        for i, g in enumerate(a):
+            _assert_same(g, b[len(b) - 1 - i], (rev, i))
+
+
+# ---- 4. / 5. the ABI directly: sentinel-filled, oversized buffers ----------------------------------------------------------------
+def _filled(shape, dtype):
+    t = torch.empty(shape, dtype=dtype, device=DEV)
+    t.view(torch.uint8).fill_(SENTINEL)
+    return t
+
+
+def _untouched(tensors):
+    torch.cuda.synchronize()
+    return all(bool((t.reshape(-1).view(torch.uint8) == SENTINEL).all()) for t in tensors)
+
+
+EXTRA_ROWS = 7
+
+
+class _AbiCall:
+    """veto_postprocess_groups_batch on a batch of post_batch_cases, every output EXTRA_ROWS rows (kept_count: entries) longer
+    than stated and the workspace 4 096 bytes longer, all filled with 0x5A."""
+
+    def __init__(self, batch):
+        from veto_amd import native
+        self.native, self.lib = native, native.load_library()
+        x = bc.inputs(batch)
+        self.x, self.K, self.vote = x, bc.n_groups(batch), bc.voting(batch)
+        per = 3 if self.vote else 1
+        keys = ["group_%d%d" % (k, e + 1) for k in range(self.K) for e in range(3)] if self.vote else ["group_%d" % k for k in range(self.K)]
+        self.heads = [_to(x["rel"][k]) for k in keys]
+        self.obj, self.pairs = _to(np.concatenate(x["obj"])), _to(np.concatenate(x["pairs"]))
+        n_img, self.n_obj, self.n_pair, n_rel = len(x["n_pairs"]), sum(x["n_objs"]), sum(x["n_pairs"]), len(x["incre"])
+        self.total = total = self.K * self.n_pair
+        self.off = [_to(np.concatenate([[0], np.cumsum(c)]).astype(np.int32)) for c in (x["n_objs"], x["n_pairs"])]
+        self.ws_bytes = self.lib.veto_postprocess_workspace_bytes(total, n_rel)
+        R = total + EXTRA_ROWS
+        self.outs = {"obj_scores": _filled(self.n_obj + EXTRA_ROWS, torch.float32), "obj_pred": _filled(self.n_obj + EXTRA_ROWS, torch.int64),
+                     "prob": _filled((R, n_rel), torch.float32), "pairs": _filled((R, 2), torch.int64), "labels": _filled(R, torch.int64),
+                     "triple": _filled(R, torch.float32), "kept": _filled(n_img + EXTRA_ROWS, torch.int32),
+                     "workspace": _filled(self.ws_bytes + 4096, torch.uint8)}
+        o = self.outs
+        self._host = ((ctypes.c_void_p * len(self.heads))(*[h.data_ptr() for h in self.heads]),
+                      (ctypes.c_int32 * self.K)(*[self.heads[per * k].shape[1] for k in range(self.K)]),
+                      (ctypes.c_int32 * n_rel)(*x["incre"]), (ctypes.c_int32 * n_img)(*x["n_pairs"]))
+        a = self.a = native.VetoPostGroupsBatchArgs()
+        a.struct_size = ctypes.sizeof(native.VetoPostGroupsBatchArgs)
+        a.n_img, a.n_obj, a.n_pair, a.n_groups, a.experts_per_group = n_img, self.n_obj, self.n_pair, self.K, per
+        a.n_rel_cls, a.n_obj_cls, a.voting, a.max_pairs_per_image = n_rel, self.obj.shape[1], int(self.vote == "U"), max(x["n_pairs"])
+        a.head_logits, a.group_widths, a.incre_idx_list, a.pairs_per_image = [ctypes.cast(h, ctypes.c_void_p) for h in self._host]
+        a.obj_logits, a.rel_pairs = self.obj.data_ptr(), self.pairs.data_ptr()
+        a.img_obj_offset, a.img_pair_offset = self.off[0].data_ptr(), self.off[1].data_ptr()
+        a.obj_scores, a.obj_pred = o["obj_scores"].data_ptr(), o["obj_pred"].data_ptr()
+        a.rel_prob_sorted, a.rel_pairs_sorted = o["prob"].data_ptr(), o["pairs"].data_ptr()
+        a.rel_labels_sorted, a.triple_sorted = o["labels"].data_ptr(), o["triple"].data_ptr()
+        a.kept_count = o["kept"].data_ptr() if self.vote else None
+
+    def __call__(self, workspace_bytes=None):
+        stream = torch.cuda.current_stream(DEV)
+        rc = self.lib.veto_postprocess_groups_batch(ctypes.c_void_p(stream.cuda_stream), ctypes.byref(self.a),
+                                                    ctypes.c_void_p(self.outs["workspace"].data_ptr()),
+                                                    self.ws_bytes if workspace_bytes is None else workspace_bytes)
+        torch.cuda.synchronize()
+        return rc, self.lib.veto_last_error()
+
+
+@pytest.mark.parametrize("batch", ["meet_vg", "vote_U"])
+def test_abi_writes_exactly_the_stated_rows(batch):
+    """Behind the last block of every output, behind kept_count[n_img] and behind the stated workspace size every byte stays
+    0x5A; the blocks hold the PostProcessor's rows (merge: all K * P_i rows of each block; vote: the first kept_count[i])."""
+    call = _AbiCall(batch)
+    rc, msg = call()
+    assert rc == 0, msg
+    o, total, n_img = call.outs, call.total, len(call.x["n_pairs"])
+    assert _untouched([o["prob"][total:], o["pairs"][total:], o["labels"][total:], o["triple"][total:], o["obj_scores"][call.n_obj:],
+                       o["obj_pred"][call.n_obj:], o["workspace"][call.ws_bytes:]])
+    assert _untouched([o["kept"][n_img:] if call.vote else o["kept"]])
+    blocks = [call.K * p for p in call.x["n_pairs"]]
+    kept = o["kept"][:n_img].tolist() if call.vote else blocks
+    want = _run_batch(batch)
+    start = 0
+    for i, (rows, n) in enumerate(zip(blocks, kept)):
+        assert n == want[i]["triple_scores"].shape[0] and (call.vote or n == rows)
+        sl = slice(start, start + n)
+        assert torch.equal(o["triple"][sl], want[i]["triple_scores"]) and torch.equal(o["prob"][sl], want[i]["pred_rel_scores"])
+        assert torch.equal(o["pairs"][sl].to(torch.float32), want[i]["rel_pair_idxs"]) and torch.equal(o["labels"][sl], want[i]["pred_rel_labels"])
+        if not call.vote:   # every row of the block was written: none still holds the fill
+            assert not bool((o["triple"][sl].view(torch.int32) == 0x5A5A5A5A).any()) and not bool((o["labels"][sl] == 0x5A5A5A5A5A5A5A5A).any())
+        start += rows
+    assert start == total
+    print("post_batch: ABI %-8s %d rows in %d blocks%s; nothing written behind the stated sizes"
+          % (batch, total, n_img, ", kept %s" % kept if call.vote else ""))
+
+
+def test_abi_refuses_an_image_beyond_the_sort_limit_and_names_it():
+    """4 097 pairs x 4 GQA groups = 16 388 rows: refused with the image's index, nothing launched, the outputs untouched -- as
+    the only image (index 0) and behind a 3-object image (index 1), through the ABI and through the PostProcessor."""
+    from veto_amd import native
+    call = _AbiCall("meet_gqa_over")
+    rc, msg = call()
+    assert rc == -1 and b"image 0" in msg and b"exceeds 16384" in msg, msg
+    assert _untouched(call.outs.values())
+    small, over = bc.image("small_gqa:3"), bc.image("meet:gqa_over")
+    rel = {k: np.concatenate([small["rel"][k], over["rel"][k]]) for k in small["rel"]}
+    with pytest.raises(native.VetoError, match="image 1: .*exceeds 16384"):
+        _call(_post(), rel, [small["obj"], over["obj"]], [small["pairs"], over["pairs"]], over["incre"], [_boxes(3), _boxes(65)])
+
+
+def test_abi_refuses_bad_arguments_before_any_launch():
+    call = _AbiCall("vote_C")
+    a = call.a
+    for change, restore, needle in ((lambda: setattr(a, "voting", 2), lambda: setattr(a, "voting", 0), b"voting"),
+                                    (lambda: setattr(a, "struct_size", a.struct_size - 8),
+                                     lambda: setattr(a, "struct_size", ctypes.sizeof(call.native.VetoPostGroupsBatchArgs)), b"size mismatch"),
+                                    (lambda: setattr(a, "max_pairs_per_image", a.max_pairs_per_image - 1),
+                                     lambda: setattr(a, "max_pairs_per_image", max(call.x["n_pairs"])), b"max_pairs_per_image"),
+                                    (lambda: setattr(a, "kept_count", None), lambda: setattr(a, "kept_count", call.outs["kept"].data_ptr()),
+                                     b"missing pointer")):
+        change()
+        rc, msg = call()
+        assert rc == -1 and needle in msg, msg
+        restore()
+    rc, msg = call(workspace_bytes=call.ws_bytes - 1)
+    assert rc == -4 and b"workspace too small" in msg, msg
+    assert _untouched(call.outs.values())
+    rc, msg = call()                      # the same struct, restored: accepted
+    assert rc == 0, msg
+    assert not _untouched([call.outs["triple"][:call.total]])
+
+
+# ---- 6. end to end ---------------------------------------------------------------------------------------------------------------
+class _Recorder(torch.nn.Module):
+    """Stands in for the head's post-processor: keeps what the head hands it and calls it."""
+
+    def __init__(self, post):
+        super().__init__()
+        self.post = post
+
+    def forward(self, x, rel_pair_idxs, boxes, **kw):
+        self.seen = (x, rel_pair_idxs, boxes, kw)
+        return self.post(x, rel_pair_idxs, boxes, **kw)
+
+
+@pytest.mark.parametrize("mode", ["predcls", "sgdet"])
+def test_relation_head_end_to_end_on_three_images(mode):
+    """VETORelationHead.forward_pooled, one-layer MEET, images of 10, 1 and 6 objects: its results equal one-image
+    post-processor calls fed the SAME predictor logits, sliced, and the evaluator returns the same numbers for both."""
+    from veto_amd import predictor, synth, testing
+    from veto_amd.evaluation import SGGEvaluator
+    from veto_amd.relation_head import VETORelationHead
+    from veto_amd.structures import BoxList
+    n_objs = [10, 1, 6]
+    cfg = testing.make_config(1, 8, mode="predcls" if mode == "predcls" else "sgcls", meet=True)
+    cfg.MODEL.ROI_RELATION_HEAD.USE_GT_BOX = mode == "predcls"
+    cfg.TEST.RELATION.LATER_NMS_PREDICTION_THRES = 0.5
+    cfg.ENSEMBLE_LEARNING.EXPERT_GROUP = False
+    predictor.set_embedding_provider(lambda names, w, k: torch.zeros(len(names), k))
+    predictor.set_statistics_provider(lambda c: {"obj_classes": ["o%d" % i for i in range(151)], "rel_classes": ["r%d" % i for i in range(51)]})
+    head = VETORelationHead(cfg).to(DEV).eval()
+    sd = synth.meet_state_dict(0, head.predictor.max_group_element_number_list, layers=1)
+    head.predictor.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=False)
+    head.predictor.eval()
+    head.post_processor = rec = _Recorder(head.post_processor)
+    total = sum(n_objs)
+    if mode == "predcls":
+        props = testing.make_proposals(synth.synthetic_batch(41, len(n_objs), n_objs), "predcls", DEV)
+    else:
+        props = []
+        for i, n in enumerate(n_objs):
+            d = synth.synthetic_detections(400 + i, n, 151)
+            b = BoxList(_to(d["boxes"]), d["image_size"], "xyxy")
+            for k in ("pred_scores", "pred_labels", "boxes_per_cls", "predict_logits"):
+                b.add_field(k, _to(d[k]))
+            props.append(b)
+    feats = _to(synth.normal(3, "batch.roi", (total, 256, 8, 8), 0.0, 1.0))
+    depth = _to(synth.normal(4, "batch.depth", (total, 256, 8, 8), 0.0, 1.0))
+    with torch.no_grad():
+        _, result, _ = head.forward_pooled(props, feats, depth)
+    assert len(result) == 3
+    got = _snapshot(result, rec.post.last_triple_scores, bbox=True)
+    (rel, refine), pair_idxs, boxes, kw = rec.seen
+    n_pairs = [int(p.shape[0]) for p in pair_idxs]
+    assert isinstance(rel, dict) and all(v.shape[0] == sum(n_pairs) for v in rel.values())
+    p0 = np.concatenate([[0], np.cumsum(n_pairs)])
+    alone = []
+    for i in range(3):
+        one = rec.post(({k: v[p0[i]:p0[i + 1]] for k, v in rel.items()}, [refine[i]]), [pair_idxs[i]], [boxes[i]], **kw)
+        alone += _snapshot(one, rec.post.last_triple_scores, bbox=True)
+        _assert_same(got[i], alone[i], (mode, i))
+        assert got[i]["triple_scores"].shape[0] == len(rel) * n_pairs[i]
+    # the evaluator on both: GT = the first image-local pairs with a predicate each, on the results' own boxes and labels
+    ev = SGGEvaluator(mode, 51, np.zeros((0, 3), dtype=np.int64), iou_thres=0.5, device=DEV)
+
+    def boxlists(fields):
+        gts, preds = [], []
+        for f, size in zip(fields, [p.size for p in props]):
+            pr = BoxList(f["bbox"], size, "xyxy")
+            for k in FIELDS:
+                pr.add_field(k, f[k])
+            n = f["bbox"].shape[0]
+            gt = BoxList(f["bbox"], size, "xyxy")
+            gt.add_field("labels", f["pred_labels"])
+            tuples = [[a, b, 1 + (a + b) % 4] for a in range(n) for b in range(n) if a != b][:5]
+            gt.add_field("relation_tuple", torch.tensor(tuples, dtype=torch.int64, device=DEV).reshape(-1, 3))
+            gts.append(gt)
+            preds.append(pr)
+        return gts, preds
+
+    res_batch, res_alone = ev.evaluate_boxlists(*boxlists(got)), ev.evaluate_boxlists(*boxlists(alone))
+    for key in ("recall", "recall_nogc", "zeroshot_recall", "accuracy", "mean_recall", "ng_mean_recall", "images_evaluated"):
+        np.testing.assert_equal(res_batch[key], res_alone[key], err_msg=key)
+    assert res_batch["images_evaluated"] == 2           # the one-object image has no GT relation
+    print("post_batch: end to end %s, pairs %s: equal to the one-image calls on the same logits; R@100 %.4f on both"
+          % (mode, n_pairs, res_batch["recall"][100]))

@@ -106,6 +106,56 @@ int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* wo
   return VETO_OK;
 }
 
+int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT_AND(veto_post_groups_batch_args_t, a, workspace != nullptr);
+  if (a->n_img <= 0 || a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > kPostMaxGroups || a->n_rel_cls < 2 ||
+      a->n_rel_cls > kPostMaxRelCls || a->n_obj_cls < 2)
+    return fail(VETO_ERR_INVALID, "bad sizes (n_groups 1..%d, n_rel_cls 2..%d)", kPostMaxGroups, kPostMaxRelCls);
+  if (a->experts_per_group != 1 && a->experts_per_group != 3)
+    return fail(VETO_ERR_INVALID, "experts_per_group must be 1 (merge) or 3 (vote)");
+  const bool vote = a->experts_per_group == 3;
+  if (vote ? (a->voting != 0 && a->voting != 1) : a->voting != 0)
+    return fail(VETO_ERR_INVALID, "%s", vote ? "voting must be 0 ('C') or 1 ('U')" : "voting must be 0 for the merge");
+  if (!a->head_logits || !a->group_widths || !a->incre_idx_list || !a->pairs_per_image || !a->rel_pairs || !a->img_obj_offset ||
+      !a->img_pair_offset || !a->obj_scores || !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted ||
+      vote != (a->kept_count != nullptr))
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  const long total = (long)a->n_groups * a->n_pair;
+  if (total > INT32_MAX) return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds int32", total);
+  long sum = 0;
+  int largest = 0;
+  for (int i = 0; i < a->n_img; ++i) {
+    const long rows = (long)a->n_groups * a->pairs_per_image[i];
+    if (a->pairs_per_image[i] < 0) return fail(VETO_ERR_INVALID, "image %d: %d pairs", i, a->pairs_per_image[i]);
+    if (rows > postprocess_max_pairs_per_image())
+      return fail(VETO_ERR_INVALID, "image %d: n_groups * pairs = %ld exceeds %d", i, rows, postprocess_max_pairs_per_image());
+    sum += a->pairs_per_image[i];
+    if (a->pairs_per_image[i] > largest) largest = a->pairs_per_image[i];
+  }
+  if (sum != a->n_pair || largest != a->max_pairs_per_image)
+    return fail(VETO_ERR_INVALID, "pairs_per_image: sum %ld, maximum %d; n_pair %d, max_pairs_per_image %d", sum, largest, a->n_pair,
+                a->max_pairs_per_image);
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls), false));
+  PostGroupTables t{};
+  t.n_groups = a->n_groups; t.experts = a->experts_per_group; t.voting = a->voting;
+  for (int c = 0; c < a->n_rel_cls; ++c)
+    t.cls_group[c] = a->incre_idx_list[c] >= 0 && a->incre_idx_list[c] <= a->n_groups ? (uint8_t)a->incre_idx_list[c] : 255;
+  for (int k = 0; k < a->n_groups; ++k) {
+    int cols[104];   // the same check as the one-image entry points; the kernel derives the columns itself
+    ABI_TRY(fill_group_cols(cols, a->group_widths[k], k, a->incre_idx_list, a->n_rel_cls));
+    t.width[k] = a->group_widths[k];
+    for (int e = 0; e < a->experts_per_group; ++e) {
+      t.logits[a->experts_per_group * k + e] = a->head_logits[a->experts_per_group * k + e];
+      if (!t.logits[a->experts_per_group * k + e]) return fail(VETO_ERR_INVALID, "group %d head %d: null logits", k, e + 1);
+    }
+  }
+  PostArgs p = post_args(a);
+  p.n_img = a->n_img; p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset; p.kept_count = a->kept_count;
+  carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
+  HIP_TRY(launch_postprocess_groups_batch(p, t, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 static size_t carve_obj_decode(Carver c, int n_obj, int n_cls, ObjDecodeArgs* p) {
   p->prob_ws = c.take<float>((size_t)n_obj * n_cls * 4);
   return c.off;

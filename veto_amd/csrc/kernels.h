@@ -287,6 +287,20 @@ struct VoteGroup {               // one MEET group with its three expert heads, 
 };
 // voting: 0 = consensus ('C', two of three experts agree), 1 = unanimous ('U')
 hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_groups, int voting, hipStream_t s);
+// The MEET merge / expert vote of a whole batch in four launches (object scores, group scores, sort, gather), whatever n_img and
+// n_groups.  `a` as for launch_postprocess (img_obj_off / img_pair_off set, n_pair = the batch's pairs, workspace and outputs of
+// n_groups * n_pair rows; kept_count [n_img] for the vote).  Image i owns rows n_groups * img_pair_off[i] .. of n_groups * P_i rows,
+// ordered (group, pair) before the sort.
+constexpr int kPostMaxGroups = 16;
+constexpr int kPostMaxRelCls = 256;
+struct PostGroupTables {         // passed by value: the heads and the class -> group list; a wave derives its group's columns
+  const float* logits[3 * kPostMaxGroups];   // [experts * k + e]: [n_pair, width[k]]
+  int width[kPostMaxGroups];     // g_k + 2
+  uint8_t cls_group[kPostMaxRelCls];         // 1-based group of class c, 0 = background (255: no group)
+  int n_groups, experts;         // experts: 1 (merge) or 3 (vote)
+  int voting;                    // vote: 0 = consensus, 1 = unanimous
+};
+hipError_t launch_postprocess_groups_batch(const PostArgs& a, const PostGroupTables& t, hipStream_t s);
 int postprocess_max_pairs_per_image();
 hipError_t launch_postprocess(const PostArgs& a, hipStream_t s);   // obj_logits == nullptr: obj_scores / obj_pred are inputs
 

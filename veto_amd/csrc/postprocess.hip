@@ -255,6 +255,210 @@ __global__ __launch_bounds__(256) void vote_rel_score_kernel(PostArgs a, VoteGro
   }
 }
 
+// ---- the MEET merge and the expert vote of a whole batch -------------------------------------------------------------------------
+// Image i owns the rows K * img_pair_off[i] .. of K * P_i rows (K groups, P_i pairs); inside that block the order before the sort is
+// (group, pair), i.e. the one-image merged list, so image i's result is that of the one-image call on it, tie-break included.
+
+// largest i with off[i] <= x (off ascending, off[0] = 0; empty images share an offset and are skipped)
+__device__ __forceinline__ int image_of(const int32_t* __restrict__ off, int n_img, long x, int scale) {
+  int lo = 0, hi = n_img - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((long)scale * off[mid] <= x) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One wave per (pair, group) of the batch: grid (ceil(n_pair / 4), K).  The row arithmetic is that of meet_rel_score_kernel (kVote
+// false) / vote_rel_score_kernel (kVote true), statement for statement; new are the image look-up, the object offset, the output row
+// and the group's column table, which wave 0 derives from the class -> group list: column 1 + r is the r-th class of the group.
+template <bool kVote>
+__global__ __launch_bounds__(256) void group_batch_score_kernel(PostArgs a, PostGroupTables t) {
+  __shared__ int s_cols[104];
+  const int k = blockIdx.y, lane = threadIdx.x & 63;
+  if (threadIdx.x < 64) {
+    if (lane == 0) s_cols[0] = 0;
+    int base = 1;
+    for (int c0 = 0; c0 < a.n_rel_cls; c0 += 64) {
+      const int c = c0 + lane;
+      const bool mine = c < a.n_rel_cls && t.cls_group[c] == k + 1;
+      const unsigned long long m = __ballot(mine);
+      const int col = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (mine && col < 104) s_cols[col] = c;
+      base += __popcll(m);
+    }
+  }
+  __syncthreads();
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= a.n_pair) return;
+  const int img = image_of(a.img_pair_off, a.n_img, p, 1);
+  const int pair0 = a.img_pair_off[img], P = a.img_pair_off[img + 1] - pair0, obj0 = a.img_obj_off[img];
+  const size_t out_row = (size_t)t.n_groups * pair0 + (size_t)k * P + (p - pair0);
+  const int width = t.width[k];
+  float* prob = a.prob_tmp + out_row * a.n_rel_cls;
+  for (int c = lane; c < a.n_rel_cls; c += 64) prob[c] = 0.f;
+  const float s0 = a.obj_scores[obj0 + a.rel_pairs[2 * (size_t)p]];
+  const float s1 = a.obj_scores[obj0 + a.rel_pairs[2 * (size_t)p + 1]];
+  if constexpr (!kVote) {
+    const float* logit = t.logits[k] + (size_t)p * width;
+    float mx = -INFINITY;
+    for (int c = lane; c < width; c += 64) mx = fmaxf(mx, logit[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    float sum = 0.f;
+    for (int c = lane; c < width; c += 64) sum += expf(logit[c] - mx);
+    sum = wave_sum(sum);
+    const float inv = 1.f / sum;
+    float best = -1.f;
+    int best_cls = 0x7fffffff;
+    for (int c = lane; c < width - 1; c += 64) {  // the last column is dropped
+      const float pr = expf(logit[c] - mx) * inv;
+      prob[s_cols[c]] = pr;
+      if (c >= 1 && pr > best) { best = pr; best_cls = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o, 64);
+      const int oc = __shfl_xor(best_cls, o, 64);
+      if (ob > best || (ob == best && oc < best_cls)) { best = ob; best_cls = oc; }
+    }
+    if (lane == 0) {
+      a.triple[out_row] = best * s0 * s1;
+      a.label_tmp[out_row] = best_cls;
+    }
+  } else {
+    const int keepw = width - 1;  // the last column is dropped
+    float pr[3][2], tr[3];
+    int cls[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const float* logit = t.logits[3 * k + e] + (size_t)p * width;
+      float mx = -INFINITY;
+      for (int c = lane; c < width; c += 64) mx = fmaxf(mx, logit[c]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      float sum = 0.f;
+      for (int c = lane; c < width; c += 64) sum += expf(logit[c] - mx);
+      sum = wave_sum(sum);
+      const float inv = 1.f / sum;
+      float best = -1.f;
+      int best_cls = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        pr[e][j] = c < keepw ? expf(logit[c] - mx) * inv : 0.f;
+        if (c >= 1 && c < keepw && pr[e][j] > best) { best = pr[e][j]; best_cls = c; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oc = __shfl_xor(best_cls, o, 64);
+        if (ob > best || (ob == best && oc < best_cls)) { best = ob; best_cls = oc; }
+      }
+      tr[e] = best * s0 * s1;
+      cls[e] = best_cls;
+    }
+    const bool ag01 = cls[0] == cls[1], ag12 = cls[1] == cls[2], ag02 = cls[0] == cls[2];
+    float triple, out[2];
+    int label;
+    bool keep;
+    if (t.voting == 0) {
+      const int cnt = (int)ag01 + (int)ag12 + (int)ag02;
+      keep = cnt > 0;
+      const float fc = (float)cnt;
+      triple = (((ag01 ? (tr[0] + tr[1]) * 0.5f : 0.f) + (ag12 ? (tr[1] + tr[2]) * 0.5f : 0.f)) + (ag02 ? (tr[0] + tr[2]) * 0.5f : 0.f)) / fc;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        out[j] = (((ag01 ? (pr[0][j] + pr[1][j]) * 0.5f : 0.f) + (ag12 ? (pr[1][j] + pr[1][j]) * 0.5f : 0.f)) +
+                  (ag02 ? (pr[0][j] + pr[2][j]) * 0.5f : 0.f)) / fc;   // p_12 = p_1, as vote_rel_score_kernel
+      label = ag02 ? cls[2] : ag12 ? cls[1] : ag01 ? cls[0] : 0;
+    } else {
+      keep = ag01 && ag12 && ag02;
+      triple = ((tr[0] + tr[1]) + tr[2]) / 3.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) out[j] = ((pr[0][j] + pr[1][j]) + pr[2][j]) / 3.f;
+      label = cls[2];
+    }
+    if (keep) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        if (c < keepw) prob[s_cols[c]] = out[j];
+      }
+    }
+    if (lane == 0) {
+      a.triple[out_row] = keep ? triple : -1.f;
+      a.label_tmp[out_row] = keep ? label : 0;
+    }
+  }
+}
+
+// one workgroup per image: the bitonic sort of segment_sort_kernel over the image's block of K * P_i rows; perm holds batch rows
+__global__ __launch_bounds__(1024) void group_batch_sort_kernel(PostArgs a, int n_groups) {
+  __shared__ float s_key[kSortMax];
+  __shared__ int s_idx[kSortMax];
+  __shared__ int s_kept;
+  const int img = blockIdx.x;
+  const int pair0 = a.img_pair_off[img];
+  const size_t r0 = (size_t)n_groups * pair0;
+  const int cnt = n_groups * (a.img_pair_off[img + 1] - pair0);
+  if (cnt > kSortMax) return;  // refused on the host; never index LDS beyond its size
+  int n2 = 1;
+  while (n2 < cnt) n2 <<= 1;
+  for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+    s_key[i] = i < cnt ? a.triple[r0 + i] : -INFINITY;
+    s_idx[i] = i < cnt ? i : 0x7fffffff;  // padding sorts last
+  }
+  if (threadIdx.x == 0) s_kept = 0;
+  __syncthreads();
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+        const int l = i ^ j;
+        if (l > i) {
+          const float ki = s_key[i], kl = s_key[l];
+          const int ii = s_idx[i], il = s_idx[l];
+          const bool i_first = ki > kl || (ki == kl && ii < il);  // score descending, then the image-local merged index
+          const bool ascending_block = (i & k) == 0;
+          if (ascending_block ? !i_first : i_first) {
+            s_key[i] = kl; s_key[l] = ki;
+            s_idx[i] = il; s_idx[l] = ii;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < cnt; i += blockDim.x) a.perm[r0 + i] = s_idx[i];  // image-local: the gather adds the block's start
+  if (a.kept_count) {  // voted-out rows carry score -1 and sort last: the kept rows are a prefix of the block
+    int mine = 0;
+    for (int i = threadIdx.x; i < cnt; i += blockDim.x) mine += s_key[i] >= 0.f;
+    if (mine) atomicAdd(&s_kept, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) a.kept_count[img] = s_kept;
+  }
+}
+
+// one wave per output row: the image from the row (blocks start at K * img_pair_off), the source row from perm, its pair as
+// img_pair_off[img] + (local source row % P_img)
+__global__ __launch_bounds__(256) void group_batch_gather_kernel(PostArgs a, int n_groups) {
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= (long)n_groups * a.n_pair) return;
+  const int img = image_of(a.img_pair_off, a.n_img, r, n_groups);
+  const int pair0 = a.img_pair_off[img], P = a.img_pair_off[img + 1] - pair0;
+  const int local = a.perm[r];
+  const size_t src = (size_t)n_groups * pair0 + local;
+  for (int c = lane; c < a.n_rel_cls; c += 64) a.out_prob[(size_t)r * a.n_rel_cls + c] = a.prob_tmp[src * a.n_rel_cls + c];
+  if (lane == 0) {
+    const size_t psrc = (size_t)pair0 + local % P;
+    a.out_pairs[2 * (size_t)r] = a.rel_pairs[2 * psrc];
+    a.out_pairs[2 * (size_t)r + 1] = a.rel_pairs[2 * psrc + 1];
+    a.out_labels[r] = a.label_tmp[src];
+    if (a.out_triple) a.out_triple[r] = a.triple[src];
+  }
+}
+
 }  // namespace
 
 // obj_logits == nullptr (sgdet): obj_scores / obj_pred were filled by the object decoding (sgdet.hip) and are inputs here
@@ -295,6 +499,20 @@ hipError_t launch_postprocess_meet(PostArgs a, const MeetGroup* groups, int n_gr
   VETO_LAUNCH(segment_sort_kernel, dim3(1), dim3(1024), 0, s, m);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   VETO_LAUNCH(gather_sorted_kernel, dim3((m.n_pair + 3) / 4), dim3(256), 0, s, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_postprocess_groups_batch(const PostArgs& a, const PostGroupTables& t, hipStream_t s) {
+  hipError_t e = launch_obj_scores(a, s);
+  if (e != hipSuccess) return e;
+  const dim3 score_grid((a.n_pair + 3) / 4, t.n_groups);
+  if (t.experts == 3) VETO_LAUNCH(group_batch_score_kernel<true>, score_grid, dim3(256), 0, s, a, t);
+  else VETO_LAUNCH(group_batch_score_kernel<false>, score_grid, dim3(256), 0, s, a, t);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(group_batch_sort_kernel, dim3(a.n_img), dim3(1024), 0, s, a, t.n_groups);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const long rows = (long)t.n_groups * a.n_pair;
+  VETO_LAUNCH(group_batch_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a, t.n_groups);
   return hipGetLastError();
 }
 

@@ -182,6 +182,14 @@ class VetoPostVoteArgs(Structure):
                                         "rel_labels_sorted", "triple_sorted", "kept_count")]
 
 
+class VetoPostGroupsBatchArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_obj", "n_pair", "n_groups", "experts_per_group", "n_rel_cls",
+                                       "n_obj_cls", "voting", "max_pairs_per_image")] + \
+               [(n, c_void_p) for n in ("head_logits", "group_widths", "incre_idx_list", "pairs_per_image", "obj_logits",
+                                        "rel_pairs", "img_obj_offset", "img_pair_offset", "obj_scores", "obj_pred",
+                                        "rel_prob_sorted", "rel_pairs_sorted", "rel_labels_sorted", "triple_sorted", "kept_count")]
+
+
 class VetoRoiPoolArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_levels", "n_img", "n_roi", "channels", "depth_channels",
                                        "pooled", "sampling_ratio")] + \
@@ -234,7 +242,7 @@ class VetoTrainPlan(Structure):
 STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_abi_symbols.py compares every field's offset and size)
     "veto_config_t": VetoConfig, "veto_inputs_t": VetoInputs, "veto_debug_outputs_t": VetoDebugOutputs,
     "veto_saturation_t": VetoSaturation, "veto_post_args_t": VetoPostArgs, "veto_post_meet_args_t": VetoPostMeetArgs,
-    "veto_post_vote_args_t": VetoPostVoteArgs, "veto_obj_decode_args_t": VetoObjDecodeArgs, "veto_pair_args_t": VetoPairArgs,
+    "veto_post_vote_args_t": VetoPostVoteArgs, "veto_post_groups_batch_args_t": VetoPostGroupsBatchArgs, "veto_obj_decode_args_t": VetoObjDecodeArgs, "veto_pair_args_t": VetoPairArgs,
     "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
     "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
@@ -284,6 +292,7 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_postprocess_workspace_bytes": _sig(_I, _I, ret=_Z),
     "veto_postprocess_meet": _sig(_P, POINTER(VetoPostMeetArgs), _P, _Z),
     "veto_postprocess_vote": _sig(_P, POINTER(VetoPostVoteArgs), _P, _Z),
+    "veto_postprocess_groups_batch": _sig(_P, POINTER(VetoPostGroupsBatchArgs), _P, _Z),
     "veto_obj_decode": _sig(_P, POINTER(VetoObjDecodeArgs), _P, _Z),
     "veto_obj_decode_workspace_bytes": _sig(_I, _I, ret=_Z),
     "veto_prepare_test_pairs": _sig(_P, POINTER(VetoPairArgs)),
