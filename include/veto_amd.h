@@ -54,7 +54,8 @@ enum veto_status {
 enum veto_precision {
   VETO_PRECISE = 0,  /* 3-term split-bf16 MFMA on every Linear, meets the 1e-3 logit tolerance (2-3e-5 measured).  Range: the Linears'
                         operands keep the fp32 exponent range; the ATTENTION products (every mode, the training path included) split
-                        q / k / v and the probabilities into fp16 hi + fp16 lo planes (22 significant bits): |q|, |k|, |v| beyond 65504
+                        q / k / v and the probabilities into fp16 hi + fp16 lo planes (22 significant bits; on the training path q / k / v
+                        are stored as 3-byte floats by default and so carry 16, VETO_TRAIN_QKV_F24=0 restores 22): |q|, |k|, |v| beyond 65504
                         saturate there and components below ~2^-24 are dropped -- both far outside what LayerNorm'ed rows times
                         weights produce (O(10)); no audit counts them */
   VETO_FAST = 1,     /* single-pass form of VETO_MIXED (round 6; rounds 1-5: a single bf16 pass of every GEMM): the same launches

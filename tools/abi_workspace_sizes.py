@@ -70,6 +70,7 @@ def main():
         show("veto_debug_gemm_workspace_bytes", (m, n, k))
     for m, n, k, ks in itertools.product((0, 1, 63, 65, 4097), (0, 1, 31, 32, 33, 576), (0, 192, 384), (0, 3)):
         show("veto_debug_wgrad_workspace_bytes", (m, n, k, ks))       # n % 32 == 0 and not
+        show("veto_debug_wgrad_ordered_workspace_bytes", (m, n, k, ks))
     for rows, cls in itertools.product(SIZES, (0, 1, 2, 51, 151)):
         show("veto_postprocess_workspace_bytes", (rows, cls))
         show("veto_obj_decode_workspace_bytes", (rows, cls))

@@ -12,7 +12,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libveto_amd.so")
 OBJ = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "obj")
 SOURCES = ["gemm_split_ps.hip", "ffn_fused.hip", "qkv_attn_fused.hip", "rowops.hip", "attention.hip", "postprocess.hip", "sgdet.hip", "nms.hip", "rpn.hip", "relsample.hip", "gtbox_relsample.hip", "boxsample.hip", "rpnloss.hip", "boxloss.hip", "optim.hip", "roialign.hip",
-           "sgg_eval.hip", "det_eval.hip", "losses.hip", "backward.hip", "train.hip", "abi_core.hip", "abi_forward.hip", "abi_train.hip", "abi_detect.hip", "abi_debug.hip"]
+           "sgg_eval.hip", "det_eval.hip", "losses.hip", "backward.hip", "train.hip", "abi_core.hip", "abi_forward.hip", "abi_train.hip", "abi_optim.hip", "abi_detect.hip", "abi_debug.hip"]
 HEADERS = ["common.h", "kernels.h", "selection.h", "abi_internal.h", os.path.join("..", "..", "include", "veto_amd.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 

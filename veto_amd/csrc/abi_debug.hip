@@ -1,5 +1,6 @@
 // Test and measurement hooks of the inference path's GEMM and fused launches (include/veto_amd.h, veto_debug_*): each builds its
-// operands from fp32 inputs and makes the launch with the argument set the forward builds (abi_internal.h).
+// operands from fp32 inputs and makes the launch with the argument set the forward builds (abi_internal.h); and of the training
+// step's backward blocks, where veto_debug_wgrad makes its launch through the helper the step itself uses (launch_wgrad).
 #include "abi_internal.h"
 
 namespace {
@@ -63,6 +64,20 @@ QkvAttnWs carve_qkv_attn(Carver c, int n_pair) {
   const size_t tile_rows = qkv_attn_rows_padded(n_pair), m = (size_t)n_pair * kTokens, rows = tile_rows > m ? tile_rows : m;
   return QkvAttnWs{c.take<__bf16>(act_bytes(rows, kDim)), c.take(act_bytes(rows, kDim)), c.take((size_t)gemm_rows_padded((int)rows) * 3 * kDim * 3),
                    c.take<__bf16>(3 * kW), c.take<int>(256), c.off};
+}
+
+// veto_debug_wgrad.  n % 32 == 0 (every Linear of the transformer): the row-major form, both operands as the split rows the backward holds
+// anyway, transposed on their way out of LDS (GemmArgs::tn), one row more than m each (partial tiles read, never use, the row behind
+// the last) and the zero row of GemmArgs::zero.  Otherwise: explicit transposed split copies, dy's padded to whole row tiles.
+// ordered: behind the operands, the partial planes of the ordered form (operand bytes: the size of the default form)
+struct WgradWs { WgradSplit split; __bf16 *a, *w, *zero; size_t operand_bytes; float* planes; size_t total; };
+WgradWs carve_wgrad(Carver c, int m, int n, int k, int k_splits, bool ordered) {
+  const WgradSplit sp = wgrad_split(n, k, m, k_splits, kWgradLinearKsteps, 0);
+  const size_t plane_bytes = ordered ? sp.plane_floats * 4 : 0;
+  if (n % 32 == 0) return WgradWs{sp, c.take<__bf16>(((size_t)m + 1) * n * 4), c.take<__bf16>(((size_t)m + 1) * k * 4), c.take<__bf16>(1024), c.off,
+                                  ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
+  return WgradWs{sp, c.take<__bf16>((size_t)gemm_rows_padded(n) * sp.mp * 4), c.take<__bf16>((size_t)k * sp.mp * 4), nullptr, c.off,
+                 ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
 }
 
 }  // namespace
@@ -291,6 +306,136 @@ int veto_debug_qkv_attn(void* stream, const float* a, const float* wqkv, int32_t
   HIP_TRY(timer.stop());
   if (ms_per_rep) *ms_per_rep = timer.total_ms / reps;
   HIP_TRY(hipMemcpyAsync(out_rows, o_m, m * kDim * 4, hipMemcpyDeviceToDevice, s));
+  return VETO_OK;
+}
+
+// ---- the backward blocks of the training step (backward.hip, train.hip), one by one -------------------------------------------
+static int debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k, int32_t k_splits,
+                       void* workspace, size_t workspace_bytes, bool ordered) {
+  if (!dy || !x || !dw || !workspace) return fail(VETO_ERR_INVALID, "null argument");
+  if (m <= 0 || n <= 0 || k <= 0 || k % 192 != 0) return fail(VETO_ERR_INVALID, "k must be a positive multiple of 192");
+  const WgradWs ws = carve_wgrad(Carver{(char*)workspace}, m, n, k, k_splits, ordered);
+  ABI_TRY(check_workspace(workspace, workspace_bytes, ws.total, false));
+  hipStream_t s = (hipStream_t)stream;
+  if (n % 32 == 0) {
+    HIP_TRY(hipMemsetAsync(ws.a, 0, ws.operand_bytes, s));   // the row behind the last one is read (never used) by partial tiles
+    HIP_TRY(launch_split_rows(dy, ws.a, (size_t)m, n, s));
+    HIP_TRY(launch_split_rows(x, ws.w, (size_t)m, k, s));
+  } else {
+    HIP_TRY(hipMemsetAsync(ws.a, 0, (char*)ws.w - (char*)ws.a, s));   // rows n..padded stay zero
+    HIP_TRY(launch_transpose_split(dy, n, m, n, ws.a, (int)ws.split.mp, s));
+    HIP_TRY(launch_transpose_split(x, k, m, k, ws.w, (int)ws.split.mp, s));
+  }
+  const hipError_t e = launch_wgrad(nullptr, s, nullptr, ws.a, ws.w, ws.zero, m, n, k, ws.split, dw, ws.planes);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "wgrad gemm launch failed: %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits, false).total;
+}
+
+size_t veto_debug_wgrad_ordered_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits, true).total;
+}
+
+int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
+                     int32_t k_splits, void* workspace, size_t workspace_bytes) {
+  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, false);
+}
+
+int veto_debug_wgrad_ordered(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
+                             int32_t k_splits, void* workspace, size_t workspace_bytes) {
+  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, true);
+}
+
+int veto_debug_attention_backward(void* stream, const float* qkv, const float* dout, float* dqkv, int32_t n_pair, int32_t heads) {
+  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  hipError_t e = launch_attention_backward(qkv, dout, dqkv, nullptr, n_pair, heads, 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (heads must give a head width of 72, 96 or 144)", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+int veto_debug_attention_backward_forms(void* stream, const void* qkv, const float* dout, void* dqkv, float* qkv_unpacked, int32_t n_pair,
+                                        int32_t heads, uint32_t flags) {
+  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (flags & ~(uint32_t)(VETO_ATTN_BWD_CLS_ONLY | VETO_ATTN_BWD_QKV_F24 | VETO_ATTN_BWD_SPLIT_OUT)) return fail(VETO_ERR_INVALID, "unknown flag");
+  const bool f24 = (flags & VETO_ATTN_BWD_QKV_F24) != 0, split = (flags & VETO_ATTN_BWD_SPLIT_OUT) != 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (qkv_unpacked) {
+    if (!f24) return fail(VETO_ERR_INVALID, "qkv_unpacked goes with VETO_ATTN_BWD_QKV_F24");
+    HIP_TRY(launch_unpack_f24(qkv, qkv_unpacked, (size_t)n_pair * kTokens * 3 * kDim, s));
+  }
+  hipError_t e = launch_attention_backward((const float*)qkv, dout, split ? nullptr : (float*)dqkv, split ? (__bf16*)dqkv : nullptr, n_pair, heads,
+                                           (flags & VETO_ATTN_BWD_CLS_ONLY) ? 1 : 0, s, f24);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (head width 72, 96 or 144; 3-byte q / k / v with 72 or 96 only)", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+size_t veto_debug_layernorm_backward_workspace_bytes(int32_t rows) { return rows > 0 ? layernorm_backward_partial_floats(rows) * 4 : 0; }
+
+int veto_debug_layernorm_backward(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
+                                  float* dx, float* dgamma_dbeta, int32_t rows, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, nullptr, nullptr, DropSite(), false));
+  return VETO_OK;
+}
+
+int32_t veto_debug_layernorm_backward_col_partial_rows(int32_t rows) { return rows > 0 ? layernorm_backward_col_partials(rows) : 0; }
+
+int veto_debug_layernorm_backward_split(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
+                                        float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
+                                        uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !split_rows || !col_partials || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
+                                    col_partials, DropSite{drop_seed, drop_thresh, drop_scale, 1}, false));
+  return VETO_OK;
+}
+
+int veto_debug_layernorm_backward_ordered(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
+                                          float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
+                                          uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
+  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  if (!split_rows != !col_partials) return fail(VETO_ERR_INVALID, "split_rows and col_partials go together");
+  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
+  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
+  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
+                                    col_partials, DropSite{drop_seed, drop_thresh, drop_scale, 1}, true));
+  return VETO_OK;
+}
+
+int veto_debug_assemble_backward_ordered(void* stream, const float* dx, const int32_t* subj, const int32_t* obj, const float* lc,
+                                         const int32_t* img_obj_offset, const int32_t* img_pair_offset, int32_t n_img, int32_t n_obj,
+                                         float* dpatch, float* dlc) {
+  if (!dx || !subj || !obj || !lc || !img_obj_offset || !img_pair_offset || !dpatch || !dlc || n_img <= 0 || n_obj <= 0)
+    return fail(VETO_ERR_INVALID, "bad argument");
+  HIP_TRY(launch_assemble_backward_ordered(dx, subj, obj, lc, img_obj_offset, img_pair_offset, n_img, dpatch, dlc, n_obj, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_debug_scatter_rows_ordered(void* stream, const float* demb, const int64_t* labels, int32_t n, int32_t dim, int32_t n_table_rows,
+                                    float* dtable) {
+  if (!demb || !labels || !dtable || n <= 0 || dim <= 0 || n_table_rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
+  HIP_TRY(launch_scatter_rows_ordered(demb, labels, dim, dtable, n, n_table_rows, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_debug_gelu_backward(void* stream, const float* pre, const float* dh, float* dpre, size_t n) {
+  if (!pre || !dh || !dpre || n == 0 || n % 4 != 0) return fail(VETO_ERR_INVALID, "bad argument (n must be a positive multiple of 4)");
+  HIP_TRY(launch_gelu_backward(pre, dh, dpre, n, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_debug_column_sums(void* stream, const float* dy, int64_t ld, int32_t rows, int32_t n_cols, float* out, void* workspace,
+                           size_t workspace_bytes) {
+  if (!dy || !out || !workspace || rows <= 0 || n_cols <= 0 || ld < n_cols) return fail(VETO_ERR_INVALID, "bad argument");
+  if (workspace_bytes < (size_t)column_sums_chunks() * n_cols * 4) return fail(VETO_ERR_WORKSPACE, "workspace too small (256 * n_cols floats)");
+  HIP_TRY(launch_column_sums(dy, ld, rows, n_cols, out, (float*)workspace, column_sums_chunks(), (hipStream_t)stream));
   return VETO_OK;
 }
 

@@ -1,4 +1,4 @@
-// What the host-side translation units of the C ABI (abi_core / abi_forward / abi_train / abi_detect / abi_debug .hip) share: the
+// What the host-side translation units of the C ABI (abi_core / abi_forward / abi_train / abi_optim / abi_detect / abi_debug .hip) share: the
 // error string, the argument checks that several entry points make, the workspace carver, the handle with its weight store and
 // profiler, the GEMM launch helper and the argument builders of the launches that both a forward and a test hook of it make.
 // Host only; no kernel source includes it.
@@ -302,12 +302,30 @@ struct ProfScope {
 // (infer_dirty).
 int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only = false);
 
-struct DropSite {   // one dropout site of the training path: threshold p * 2^24 (0 = off), scale 1 / (1 - p)
-  unsigned long long seed = 0;
-  unsigned thresh = 0;
-  float scale = 1.f;
-  int row_step = 1;   // row r of the matrix the site is applied to is token row r * row_step (the last layer's compact CLS rows: 19)
-};
+// A dropout site (kernels.h, DropSite) into the argument structs that go into a kernel by value and so keep fields of their own:
+// ObjPrepArgs / AssembleArgs (their rows are token or object rows: no row_step), and the transform of launch_prep_grad
+template <class Args>
+inline void set_drop(Args& a, const DropSite& d) { a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale; }
+inline GradXform drop_xform(const DropSite& d) {
+  GradXform xf;
+  if (d.thresh) { xf.mode = XF_DROP; xf.seed = d.seed; xf.thresh = d.thresh; xf.scale = d.scale; xf.row_step = d.row_step; }
+  return xf;
+}
+
+// ---- the weight-gradient GEMM (abi_train.hip): dW[n, k] = A^T . B over m reduction rows, split-K ---------------------------------
+// The split of one call: ks ranges of the reduction, its length padded to mp (a multiple of 32 * ks), and the floats of the ordered
+// mode's ks partial planes.  k_splits > 0: the caller's count; else just under 2 full rounds of the 256 persistent workgroups with at
+// least min_ksteps k-steps per tile, at most `cap` (0 = none).  Launch, plane sizes and operand paddings all come from here.
+struct WgradSplit { int ks; size_t mp, plane_floats; };
+WgradSplit wgrad_split(int n, int k, int m, int k_splits, int min_ksteps, int cap);
+constexpr int kWgradLinearKsteps = 64, kWgradLinearCap = 64;      // a layer's Linears (TrainWs::mp2 has room for 64 splits)
+constexpr int kWgradPatchKsteps = 8;                              // the patch projection (few object rows: tiles of 8 k-steps already)
+// The launch.  zero != nullptr: a [m, 2n] and b [m, 2k] are split rows, transposed on their way out of LDS (GemmArgs::tn), `zero` what
+// is read for the reduction rows past m; nullptr: explicit transposed split copies [n, 2mp] / [k, 2mp].  planes == nullptr: dw is zeroed
+// and the ranges add into it with float atomics; else (ordered mode) range j writes plane j and launch_fold_rows adds them in order.
+// scope: the profile entry around GEMM and fold, or nullptr
+hipError_t launch_wgrad(veto_handle_t h, hipStream_t s, const char* scope, const __bf16* a, const __bf16* b, const __bf16* zero, int m, int n,
+                        int k, const WgradSplit& sp, float* dw, float* planes);
 
 // (abi_core.hip) lda / ldc of split operands are in bf16 elements (2K / 2N for contiguous rows).
 int run_gemm(veto_handle_t h, hipStream_t s, const char* name, const __bf16* a, SplitW w, const float* bias, const float* resid, long ldr,

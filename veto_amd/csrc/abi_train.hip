@@ -1,13 +1,15 @@
 // ================================================================================================================
-// Training path: forward that keeps every activation the backward needs, and the
-// backward itself.  One pass over all pairs (no chunking), precise mode, no dropout (the caller refuses p > 0).
-// Every layer runs on all 19 tokens (the CLS-only shortcut of the inference path would complicate the backward).
+// Training path: the forward that keeps every activation the backward needs, and the backward itself.
+// One pass over all pairs (no chunking) on split-bf16 operands.  Layers 0 .. L-2 run on all 19 tokens; the last layer's attention
+// reads the 19 keys / values but only the CLS query of each pair, and everything behind it (out projection, FeedForward, head) runs
+// on the compact CLS rows, as at inference.  Dropout runs on the device (drop_site: masks from a counter-based hash that forward and
+// backward both evaluate); veto_train_opts_t.deterministic selects the ordered mode (every gradient sum in a fixed order); a
+// veto_train_plan_t (Sched) leaves out what frozen tensors and an eval-mode pos_embed.0 do not need.
+// A step is a TrainStep: one method per stage, which forward_train_impl and backward_impl call in order.
 // ================================================================================================================
 #include "abi_internal.h"
 
-#include <cmath>
-#include <cstring>
-#include <mutex>
+#include <algorithm>
 
 namespace {
 
@@ -43,9 +45,10 @@ struct TrainWs {
   size_t total;
 };
 
-// q / k / v of the training path as 3-byte floats (common.h) between the QKV projection, the attention and the attention backward: all
-// three split them into 16-bit hi + lo parts anyway, so the 16-bit significand in memory is what they would have kept -- 1.7 KB per token
-// row and layer less to keep and to move (round 6).  MFMA head widths only; VETO_TRAIN_QKV_F24=0: fp32.
+// q / k / v of the training path as 3-byte floats (common.h) between the QKV projection, the attention and the attention backward: 1.7 KB
+// per token row and layer less to keep and to move (round 6).  They carry 16 significant bits by default: what the backward, which splits
+// them into bf16 hi + lo, would have kept anyway -- but 6 fewer than the forward's attention (fp16 hi + lo planes) keeps of fp32 rows;
+// VETO_TRAIN_QKV_F24=0 (fp32 rows) restores the forward's 22.  MFMA head widths only.
 bool train_qkv_f24(veto_handle_t h) {
   static const bool off = env_knob_is("VETO_TRAIN_QKV_F24", "0");
   return !off && (h->dh == 72 || h->dh == 96);
@@ -75,19 +78,15 @@ bool train_ln_emits_split() {
   return on;
 }
 
-int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps = 64);
+// The split of the weight-gradient GEMMs of the step (abi_internal.h, wgrad_split): a layer's Linear [n, k] over m rows, and the patch
+// projection's dWcat^T [2048, 1152] over the object rows
+WgradSplit linear_wgrad_split(int n, int k, int m) { return wgrad_split(n, k, m, 0, kWgradLinearKsteps, kWgradLinearCap); }
+WgradSplit patch_wgrad_split(int rows) { return wgrad_split(2048, 2 * kDim, rows, 0, kWgradPatchKsteps, 0); }
 
-// the Linears of a layer and the patch projection, as (N, K) of their weight-gradient GEMMs: the ordered mode's planes hold the largest
+// the ordered mode's planes hold the largest of them
 size_t wgrad_plane_floats(int m_tokens, int patch_rows) {
-  size_t most = 0;
-  auto take = [&](int n, int k, int m, int min_ksteps) {
-    int ks = wgrad_splits(n, k, m, 0, min_ksteps);
-    if (ks > 64) ks = 64;
-    const size_t need = (size_t)ks * n * k;
-    if (need > most) most = need;
-  };
-  for (const LayerLinear& q : kLayerLinears) take(q.N, q.K, m_tokens, 64);      // (the last layer's compact rows are fewer: no more splits)
-  take(2048, 2 * kDim, patch_rows, 8);
+  size_t most = patch_wgrad_split(patch_rows).plane_floats;
+  for (const LayerLinear& q : kLayerLinears) most = std::max(most, linear_wgrad_split(q.N, q.K, m_tokens).plane_floats);      // (the last layer's compact rows are fewer: no more splits)
   return most;
 }
 
@@ -185,71 +184,6 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   w.planes = ordered ? c.take<float>(wgrad_plane_floats((int)M, n_obj * 16) * 4) : nullptr;
   w.total = c.off;
   return w;
-}
-
-// dw[N,K] = dy[M,N]^T . x[M,K]: the weight-gradient shape (reduction over the M rows).  Both operands are
-// transposed into split rows ([N, 2*Mp] and [K, 2*Mp]) and the persistent GEMM runs split-K with atomic adds.
-int wgrad_splits(int n, int k, int m, int k_splits, int min_ksteps) {
-  if (k_splits > 0) return k_splits;
-  const int out_tiles = ((n + 255) / 256) * (k / 192);
-  int ks = 2 * 256 / out_tiles;                         // just under 2 full rounds of the 256 persistent workgroups
-  const int max_ks = (m + 32 * min_ksteps - 1) / (32 * min_ksteps);     // at least min_ksteps k-steps per tile
-  if (ks > max_ks) ks = max_ks;
-  return ks < 1 ? 1 : ks;
-}
-
-size_t wgrad_mp(int m, int ks) { return ((size_t)m + 32 * (size_t)ks - 1) / (32 * (size_t)ks) * 32 * (size_t)ks; }
-
-// Backward of y = x W^T (+ b) over the token rows: dW[N, K] = dY^T x, db[N] = column sums of dY (if db), dX[M, K] = dY W.
-// One pass over dY (prep_grad_kernel) produces its split rows -- the A operand of the input-gradient GEMM AND, read through
-// transposing LDS loads, of the weight-gradient GEMM (GemmArgs::tn; the saved activation x_split is its other operand as it
-// is) -- and the bias partials.  No transposed copies of dY or x exist.
-// dy == nullptr: the producer (attention backward) has already written the split rows into w.dsplit; no bias then.
-// presplit / presplit_partials: the producer wrote the split rows itself (to `presplit`; nullptr = w.dsplit) together with
-// `presplit_partials` rows of column sums in w.colp (0 = none: no bias gradient then).
-// gelu_pre (fc2 only): the input gradient is not written as fp32 rows: the GEMM's epilogue multiplies it by gelu'(gelu_pre) and writes the
-// split rows of fc1's backward to w.dsplit_b and their column-sum partials to w.colp (*next_partials rows): the pass that read dH and the
-// pre-activation back (0.9 ms per layer) is gone.
-// Partial training: dw == nullptr (a frozen weight) leaves out the weight-gradient GEMM with its zero-fill or fold, db == nullptr the bias
-// sums, dx == nullptr without gelu_pre (nothing below this Linear has a consumer) the weight transpose and the input-gradient GEMM.
-int run_linear_backward(veto_handle_t h, hipStream_t s, const TrainWs& w, const float* dy, int M, int N, const __bf16* x_split, int K,
-                        const float* weight, float* dw, float* db, float* dx, const GradXform& xf = GradXform(),
-                        const __bf16* presplit = nullptr, int presplit_partials = 0, const float* gelu_pre = nullptr, int* next_partials = nullptr) {
-  if (!dy && db && presplit_partials <= 0) return fail(VETO_ERR_INVALID, "a pre-split gradient without column partials cannot feed a bias gradient");
-  const __bf16* gsplit = !dy && presplit ? presplit : w.dsplit;
-  int ks = wgrad_splits(N, K, M, 0);
-  if (ks > 64) ks = 64;      // (w.mp2 has room for 64 splits)
-  const size_t mp = wgrad_mp(M, ks);
-  if (mp > w.mp2) return fail(VETO_ERR_WORKSPACE, "weight-gradient partial buffer too small");
-  if (dy) HIP_TRY(launch_prep_grad(dy, N, M, N, w.dsplit, (int)mp, db ? w.colp : nullptr, xf, s));
-  if (db) HIP_TRY(launch_column_sums(w.colp, N, dy ? (int)(mp / 32) : presplit_partials, N, db, w.col_partial, column_sums_chunks(), s));
-  if (dw && !w.planes) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)N * K * 4, s));
-  if (dw) {
-    GemmArgs g{};
-    g.a = gsplit; g.w = x_split; g.c = w.planes ? w.planes : dw;
-    g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
-    g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = M; g.zero = w.zero;
-    ProfScope ps(h, s, "bwd_wgrad", 2.0 * M * (double)N * K, 0);
-    HIP_TRY(launch_gemm_split(g, w.planes ? EPI_PLANES : EPI_ATOMIC, 0, s));
-    if (w.planes) HIP_TRY(launch_fold_rows(w.planes, (long)N * K, ks, (long)N * K, dw, s));      // the planes in split order
-  }
-  if (!dx && !gelu_pre) return VETO_OK;
-  HIP_TRY(launch_transpose_split(weight, K, N, K, w.wdg, N, s));     // W [N, K] -> W^T split rows [K, 2N]
-  {
-    GemmArgs g{};
-    g.a = gsplit; g.w = w.wdg; g.c = dx;
-    g.M = M; g.N = K; g.K = N; g.ldc = K;
-    ProfScope ps(h, s, "bwd_dgrad", 2.0 * M * (double)N * K, 0);
-    if (gelu_pre) {
-      if (gsplit == w.dsplit_b || !next_partials) return fail(VETO_ERR_INVALID, "internal: the fused gelu' epilogue writes w.dsplit_b");
-      g.c = nullptr; g.c_split = w.dsplit_b; g.ldc = 2L * K; g.resid = gelu_pre; g.ldr = K; g.col_partial = w.colp;
-      *next_partials = (M + 255) / 256 * 4;      // one partial row per 64-row slice of every 256-row tile
-      HIP_TRY(launch_gemm_split(g, EPI_GELU_BWD, 0, s));
-    } else {
-      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
-    }
-  }
-  return VETO_OK;
 }
 
 // dropout sites of the training path: 1 = pos_embed Dropout(0.1), 2 = pos_drop on the tokens, 3 + l = to_out of layer l.  Elements are
@@ -350,7 +284,434 @@ int check_train_inputs(veto_handle_t h, const veto_inputs_t* in, const veto_trai
   return VETO_OK;
 }
 
+// One training step on its way through the stages: what every stage needs, and one method per stage -- the forward's in the order
+// forward_train_impl calls them, then the backward's in the order of the chain (Sched)
+struct TrainStep {
+  veto_handle_t h;
+  hipStream_t s;
+  const veto_inputs_t* in;
+  const veto_train_opts_t* opts;
+  const Sched& sch;
+  float* grads;      // (backward only) laid out like the weight arena
+  const bool ordered;
+  const TrainWs ws;
+  const int n_obj, n_pair, M, L, H;
+  const bool q24, recompute;
+  const std::string T = kT, pe = T + "patch_embed.";
+  int dx_presplit = 0;      // > 0: ws.dsplit / ws.colp already hold the split rows / that many rows of column partials of ws.dx
+
+  TrainStep(veto_handle_t h_, void* stream, const veto_inputs_t* in_, const veto_train_opts_t* opts_, const Sched& sch_, void* workspace,
+            float* grads_ = nullptr)
+      : h(h_), s((hipStream_t)stream), in(in_), opts(opts_), sch(sch_), grads(grads_), ordered(opts_ordered(opts_)),
+        ws(carve_train((char*)workspace, h_, in_->n_obj, in_->n_pair, ordered, sch_)), n_obj(in_->n_obj), n_pair(in_->n_pair),
+        M(in_->n_pair * kTokens), L(h_->cfg.layers), H(h_->cfg.heads), q24(train_qkv_f24(h_)), recompute(train_recompute()) {}
+
+  // (a frozen tensor has no gradient pointer: every launch of the backward that would only write it is left out)
+  bool W(const std::string& name) const { return sch.want(h, name); }
+  float* G(const std::string& name) const { return W(name) ? grads + h->params[h->index.at(name)].offset : nullptr; }
+  hipError_t copy_grad(const std::string& name, const float* src, size_t n) const {
+    float* g = G(name);
+    return g ? hipMemcpyAsync(g, src, n * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  }
+  struct LinGrad { const float* w; float *dw, *db; int N, K; };      // a layer's Linear (kLayerLinears): weight, its and the bias's gradient
+  LinGrad lin(int l, int i) const {
+    const LayerLinear& q = kLayerLinears[i];
+    return LinGrad{h->p(lname(l, q.weight)), G(lname(l, q.weight)), q.bias ? G(lname(l, q.bias)) : nullptr, q.N, q.K};
+  }
+  // the dropout behind the out projection of layer l (the last layer: on its compact CLS rows)
+  DropSite attn_site(int l) const { return drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1, &sch); }
+
+  // ---- forward -----------------------------------------------------------------------------------------------------------
+  // pair indices, BatchNorm statistics and the per-object embeddings
+  int object_side() {
+    HIP_TRY(launch_pair_indices(in->rel_pairs, in->img_obj_offset, in->img_pair_offset, in->n_img, n_pair, ws.subj, ws.obj, nullptr, nullptr, s));
+    veto_inputs_t in_bn = *in;      // (an eval-mode pos_embed.0: the running statistics, as the inference forward reads them)
+    if (sch.bn_eval) in_bn.bn_batch_stats = nullptr;
+    else HIP_TRY(launch_bn_batch_stats(in->boxes, in->box_mode, n_obj, in->bn_batch_stats, s));
+    ObjPrepArgs a = obj_prep_args(h, &in_bn, ws.lc);
+    set_drop(a, drop_site(opts, 1));
+    HIP_TRY(launch_obj_prep(a, s));
+    return VETO_OK;
+  }
+
+  int patch_projection() {
+    HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
+    return run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16, 2 * kDim, 2048,
+                    EPI_F32);
+  }
+
+  // the token rows of layer 0 and their LayerNorm1 rows
+  int assemble_tokens() {
+    AssembleArgs a = assemble_args(h, ws.patch_tab, ws.lc, ws.subj, ws.obj, ws.layers[0].xin, ws.layers[0].a1, n_pair);
+    set_drop(a, drop_site(opts, 2));
+    HIP_TRY(launch_assemble(a, s));
+    return VETO_OK;
+  }
+
+  int attention(const TrainLayer& t, int cls_only) {
+    AttnArgs a{};
+    a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = cls_only; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
+    HIP_TRY(launch_attention(a, s));
+    return VETO_OK;
+  }
+
+  // a layer but the last, on all token rows; it leaves the LayerNorm1 rows of the next
+  int layer(int l) {
+    const LayerW& w = h->layers[l];
+    const TrainLayer &t = ws.layers[l], &next = ws.layers[l + 1];
+    ABI_TRY(run_gemm(h, s, "gemm_qkv", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, 3 * kDim, M, 3 * kDim, kDim, q24 ? EPI_F24 : EPI_F32));
+    ABI_TRY(attention(t, 0));
+    ABI_TRY(run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0, attn_site(l)));
+    HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, M, s));
+    // (the epilogue writes the fp32 pre-activation -- gelu' needs it -- AND its exact-erf GELU as fc2's split rows: round 6; before, a pass
+    // of its own read the pre-activation back, 0.55 ms per layer)
+    ABI_TRY(run_gemm(h, s, "gemm_fc1", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, M, 2 * kDim, kDim, EPI_PRE_GELU));
+    ABI_TRY(run_gemm(h, s, "gemm_fc2", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, next.xin, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID));
+    HIP_TRY(launch_layernorm(next.xin, kDim, h->layers[l + 1].ln1_w, h->layers[l + 1].ln1_b, next.a1, M, s));
+    return VETO_OK;
+  }
+
+  // Last layer: only x[:, 0] reaches the loss (model_veto.py:23), so -- as at inference -- keys / values cover the 19
+  // tokens, everything behind the attention runs on the CLS row of each pair.  The saved activations of this layer
+  // (ao, xmid, a2, pre, hid, ws.xout) are COMPACT: row p = pair p.  The backward mirrors this.
+  int last_layer() {
+    const int l = L - 1, qepi = q24 ? EPI_F24 : EPI_F32;
+    const LayerW& w = h->layers[l];
+    const TrainLayer& t = ws.layers[l];
+    ABI_TRY(run_gemm(h, s, "gemm_kv_last", t.a1, w.qkv, nullptr, nullptr, 0, q24 ? (float*)((char*)t.qkv + 3 * kDim) : t.qkv + kDim, nullptr,
+                     3 * kDim, M, 2 * kDim, kDim, qepi, 0, kDim));
+    ABI_TRY(run_gemm(h, s, "gemm_q_cls", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, (long)kTokens * 3 * kDim, n_pair, kDim, kDim, qepi,
+                     (long)kTokens * 2 * kDim, 0));
+    ABI_TRY(attention(t, 1));
+    ABI_TRY(run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim, EPI_RESID,
+                     0, 0, attn_site(l)));
+    HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
+    ABI_TRY(run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU));
+    return run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID);
+  }
+
+  int head(float* out_logits) {
+    HIP_TRY(launch_head(ws.xout, h->head_wt, h->p("rel_out.bias"), out_logits, n_pair, h->cfg.num_out, s, (long)kDim));
+    return VETO_OK;
+  }
+
+  // ---- backward ----------------------------------------------------------------------------------------------------------
+  // Backward of y = x W^T (+ b) over `rows` token rows: dW[N, K] = dY^T x, db[N] = column sums of dY (if q.db), dX[rows, K] = dY W.
+  // One pass over dY (prep_grad_kernel) produces its split rows -- the A operand of the input-gradient GEMM AND, read through
+  // transposing LDS loads, of the weight-gradient GEMM (launch_wgrad; the saved activation x_split is its other operand as it
+  // is) -- and the bias partials.  No transposed copies of dY or x exist.
+  // dy == nullptr: the producer (attention backward) has already written the split rows into ws.dsplit; no bias then.
+  // presplit / presplit_partials: the producer wrote the split rows itself (to `presplit`; nullptr = ws.dsplit) together with
+  // `presplit_partials` rows of column sums in ws.colp (0 = none: no bias gradient then).
+  // gelu_pre (fc2 only): the input gradient is not written as fp32 rows: the GEMM's epilogue multiplies it by gelu'(gelu_pre) and writes the
+  // split rows of fc1's backward to ws.dsplit_b and their column-sum partials to ws.colp (*next_partials rows): the pass that read dH and the
+  // pre-activation back (0.9 ms per layer) is gone.
+  // Partial training: q.dw == nullptr (a frozen weight) leaves out the weight-gradient GEMM with its zero-fill or fold, q.db == nullptr the
+  // bias sums, dx == nullptr without gelu_pre (nothing below this Linear has a consumer) the weight transpose and the input-gradient GEMM.
+  int linear_backward(const float* dy, int rows, const LinGrad& q, const __bf16* x_split, float* dx, const GradXform& xf = GradXform(),
+                      const __bf16* presplit = nullptr, int presplit_partials = 0, const float* gelu_pre = nullptr, int* next_partials = nullptr) {
+    const int N = q.N, K = q.K;
+    if (!dy && q.db && presplit_partials <= 0) return fail(VETO_ERR_INVALID, "a pre-split gradient without column partials cannot feed a bias gradient");
+    const __bf16* gsplit = !dy && presplit ? presplit : ws.dsplit;
+    const WgradSplit sp = linear_wgrad_split(N, K, rows);
+    if (sp.mp > ws.mp2) return fail(VETO_ERR_WORKSPACE, "weight-gradient partial buffer too small");
+    if (dy) HIP_TRY(launch_prep_grad(dy, N, rows, N, ws.dsplit, (int)sp.mp, q.db ? ws.colp : nullptr, xf, s));
+    if (q.db) HIP_TRY(launch_column_sums(ws.colp, N, dy ? (int)(sp.mp / 32) : presplit_partials, N, q.db, ws.col_partial, column_sums_chunks(), s));
+    if (q.dw) HIP_TRY(launch_wgrad(h, s, "bwd_wgrad", gsplit, x_split, ws.zero, rows, N, K, sp, q.dw, ws.planes));
+    if (!dx && !gelu_pre) return VETO_OK;
+    HIP_TRY(launch_transpose_split(q.w, K, N, K, ws.wdg, N, s));     // W [N, K] -> W^T split rows [K, 2N]
+    GemmArgs g{};
+    g.a = gsplit; g.w = ws.wdg; g.c = dx;
+    g.M = rows; g.N = K; g.K = N; g.ldc = K;
+    ProfScope ps(h, s, "bwd_dgrad", 2.0 * rows * (double)N * K, 0);
+    if (!gelu_pre) {
+      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
+      return VETO_OK;
+    }
+    if (gsplit == ws.dsplit_b || !next_partials) return fail(VETO_ERR_INVALID, "internal: the fused gelu' epilogue writes w.dsplit_b");
+    g.c = nullptr; g.c_split = ws.dsplit_b; g.ldc = 2L * K; g.resid = gelu_pre; g.ldr = K; g.col_partial = ws.colp;
+    *next_partials = (rows + 255) / 256 * 4;      // one partial row per 64-row slice of every 256-row tile
+    HIP_TRY(launch_gemm_split(g, EPI_GELU_BWD, 0, s));
+    return VETO_OK;
+  }
+
+  // the whole buffer, or under a plan the regions of the trainable tensors only, neighbours in one fill (tensors lie in index order,
+  // padded to 64 floats); and the zero row of the weight-gradient GEMMs
+  int zero_grads() {
+    if (sch.full) HIP_TRY(hipMemsetAsync(grads, 0, veto_grad_floats(h) * 4, s));
+    for (size_t i = 0; !sch.full && i < h->params.size();) {
+      if (!sch.on[i]) { ++i; continue; }
+      size_t j = i;
+      while (j + 1 < h->params.size() && sch.on[j + 1]) ++j;
+      HIP_TRY(hipMemsetAsync(grads + h->params[i].offset, 0, (h->params[j].offset + h->params[j].numel - h->params[i].offset) * 4, s));
+      i = j + 1;
+    }
+    HIP_TRY(hipMemsetAsync(ws.zero, 0, 1024, s));
+    return VETO_OK;
+  }
+
+  // classifier head: gradient of the compact CLS rows (not written when nothing under the head has a consumer)
+  int head_backward(const float* dlogits) {
+    HIP_TRY(launch_head_backward(dlogits, h->p("rel_out.weight"), ws.xout, sch.keep_from < L ? ws.dx : nullptr, G("rel_out.weight"),
+                                 G("rel_out.bias"), ws.head_partial, n_pair, h->cfg.num_out, (long)kDim, s));
+    return VETO_OK;
+  }
+
+  // A layer's stages in chain order: fc2, fc1, LayerNorm2, out, attention, qkv, LayerNorm1.  own[i]: stage i has a trainable tensor;
+  // deeper[i]: something behind it (in this layer, a lower one or under layer 0) has a consumer, so its input gradient is computed.
+  enum { S_FC2, S_FC1, S_LN2, S_OUT, S_ATTN, S_QKV, S_LN1, S_COUNT };
+  struct LayerPass {
+    int l;
+    bool last;
+    int R;      // rows behind the attention: the CLS rows only in the last layer (compact buffers)
+    LinGrad qkv, out, fc1, fc2;
+    bool ln1, ln2;
+    bool deeper[S_COUNT];
+    DropSite site;      // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
+  };
+
+  // The walk ends behind the first stage with deeper[i] == false: every later stage of this and of every lower layer is without a
+  // consumer too (so that layer is sch.keep_from, the last one backward_impl visits).
+  int layer_backward(int l) {
+    LayerPass p{l, l == L - 1, l == L - 1 ? n_pair : M, lin(l, LIN_QKV), lin(l, LIN_OUT), lin(l, LIN_FC1), lin(l, LIN_FC2)};
+    p.ln1 = W(lname(l, "0.norm.weight")) || W(lname(l, "0.norm.bias"));
+    p.ln2 = W(lname(l, "1.norm.weight")) || W(lname(l, "1.norm.bias"));
+    p.site = attn_site(l);
+    const bool own[S_COUNT] = {p.fc2.dw || p.fc2.db, p.fc1.dw || p.fc1.db, p.ln2, p.out.dw || p.out.db, false, p.qkv.dw != nullptr, p.ln1};
+    for (int i = S_COUNT - 1, acc = sch.need(l); i >= 0; --i) {
+      p.deeper[i] = acc;
+      acc = acc || own[i];
+    }
+    const struct { int (TrainStep::*run)(const LayerPass&); int stage; } chain[] = {
+        {&TrainStep::ffn_backward, S_FC1},        {&TrainStep::ln2_backward, S_LN2}, {&TrainStep::out_backward, S_OUT},
+        {&TrainStep::attention_backward, S_ATTN}, {&TrainStep::qkv_backward, S_QKV}, {&TrainStep::ln1_backward, S_LN1}};
+    for (const auto& c : chain) {
+      ABI_TRY((this->*c.run)(p));
+      if (!p.deeper[c.stage]) break;
+    }
+    return VETO_OK;
+  }
+
+  // x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2: fc2, then fc1 (not when fc2's input gradient has no consumer)
+  // dpre = dh * gelu'(pre): in the epilogue of fc2's input-gradient GEMM (round 6; VETO_TRAIN_GELU_EPI=0: a pass of its own inside the
+  // operand preparation of the fc1 backward, rounds 1-5)
+  // (the gradient of this layer's output: compact CLS rows from the head in the last layer, else the rows the LayerNorm1 backward of the
+  // layer above left -- with their split rows and bias partials when it emitted them)
+  int ffn_backward(const LayerPass& p) {
+    const LayerW& w = h->layers[p.l];
+    const TrainLayer& t = ws.layers[p.l];
+    const bool epi = train_gelu_epilogue(), d2 = p.deeper[S_FC2];
+    const float* dy2 = dx_presplit ? nullptr : ws.dx;
+    float* dx1 = p.deeper[S_FC1] ? ws.dtmp : nullptr;
+    int partials = 0;
+    if (recompute && p.fc2.dw) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)p.R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
+    if (epi) ABI_TRY(linear_backward(dy2, p.R, p.fc2, t.hid, nullptr, GradXform(), nullptr, dx_presplit, d2 ? t.pre : nullptr, &partials));
+    else ABI_TRY(linear_backward(dy2, p.R, p.fc2, t.hid, d2 ? ws.dbig : nullptr, GradXform(), nullptr, dx_presplit));
+    if (!d2) return VETO_OK;
+    if (recompute && p.fc1.dw) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, p.R, s));      // LayerNorm2 rows: fc1's operand
+    if (epi) return linear_backward(nullptr, p.R, p.fc1, t.a2, dx1, GradXform(), ws.dsplit_b, partials);
+    GradXform gelu;              // dpre = dh * gelu'(pre), folded into the operand preparation of the fc1 backward
+    gelu.mode = XF_GELU;
+    gelu.pre = t.pre;
+    return linear_backward(ws.dbig, p.R, p.fc1, t.a2, dx1, gelu);
+  }
+
+  // (VETO_TRAIN_LN_SPLIT=1: it also emits the masked split rows and bias partials of the out projection's backward)
+  int ln2_backward(const LayerPass& p) {
+    const bool emit = train_ln_emits_split();
+    HIP_TRY(launch_layernorm_backward(ws.layers[p.l].xmid, ws.dtmp, h->layers[p.l].ln2_w, ws.dx, ws.dmid, p.ln2 ? ws.dgb : nullptr, ws.ln_partial, p.R, s,
+                                      emit ? ws.dsplit : nullptr, emit ? ws.colp : nullptr, emit ? p.site : DropSite(), ordered));
+    HIP_TRY(copy_grad(lname(p.l, "1.norm.weight"), ws.dgb, kDim));
+    HIP_TRY(copy_grad(lname(p.l, "1.norm.bias"), ws.dgb + kDim, kDim));
+    return VETO_OK;
+  }
+
+  int out_backward(const LayerPass& p) {
+    const bool presplit = train_ln_emits_split();
+    return linear_backward(presplit ? nullptr : ws.dmid, p.R, p.out, ws.layers[p.l].ao, p.deeper[S_OUT] ? ws.dtmp : nullptr, drop_xform(p.site), nullptr,
+                           presplit ? layernorm_backward_col_partials(p.R) : 0);
+  }
+
+  int attention_backward(const LayerPass& p) {
+    HIP_TRY(launch_attention_backward(ws.layers[p.l].qkv, ws.dtmp, nullptr, ws.dsplit, n_pair, H, p.last ? 1 : 0, s, q24));
+    return VETO_OK;
+  }
+
+  int qkv_backward(const LayerPass& p) {
+    const LayerW& w = h->layers[p.l];
+    const TrainLayer& t = ws.layers[p.l];
+    if (recompute && p.qkv.dw) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
+    return linear_backward(nullptr, M, p.qkv, t.a1, p.deeper[S_QKV] ? ws.dtmp : nullptr);
+  }
+
+  // its result, ws.dx, is the gradient of the layer's input: of the output of the layer below
+  int ln1_backward(const LayerPass& p) {
+    const float* dres = ws.dmid;
+    if (p.last) {
+      // the residual gradient d x_mid lives on the CLS rows only: spread the compact rows over a zeroed token matrix
+      HIP_TRY(hipMemsetAsync(ws.dx, 0, (size_t)M * kDim * 4, s));
+      HIP_TRY(hipMemcpy2DAsync(ws.dx, (size_t)kTokens * kDim * 4, ws.dmid, (size_t)kDim * 4, (size_t)kDim * 4, (size_t)n_pair, hipMemcpyDeviceToDevice, s));
+      dres = ws.dx;
+    }
+    // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
+    const bool emit = train_ln_emits_split() && p.l > 0;      // (the split rows and bias partials of fc2 of the layer below)
+    HIP_TRY(launch_layernorm_backward(ws.layers[p.l].xin, ws.dtmp, h->layers[p.l].ln1_w, dres, ws.dx, p.ln1 ? ws.dgb : nullptr, ws.ln_partial, M, s,
+                                      emit ? ws.dsplit : nullptr, emit ? ws.colp : nullptr, DropSite(), ordered));
+    dx_presplit = emit ? layernorm_backward_col_partials(M) : 0;
+    HIP_TRY(copy_grad(lname(p.l, "0.norm.weight"), ws.dgb, kDim));
+    HIP_TRY(copy_grad(lname(p.l, "0.norm.bias"), ws.dgb + kDim, kDim));
+    return VETO_OK;
+  }
+
+  // What under layer 0 has a consumer
+  struct Below { bool maps, patch_w, patch_b, pos_side, loc_w, cls_w, emb_w, lc_side; };
+  Below below() const {
+    Below b;
+    b.maps = opts && (opts->d_roi_rgb || opts->d_roi_depth);
+    b.patch_w = W(pe + "proj_d.weight") || W(pe + "proj_v.weight");
+    b.patch_b = W(pe + "proj_d.bias") || W(pe + "proj_v.bias");
+    b.pos_side = W("pos_embed.0.weight") || W("pos_embed.0.bias") || W("pos_embed.1.weight") || W("pos_embed.1.bias");
+    b.loc_w = W("location_projection.0.weight"), b.cls_w = W("class_projection.0.weight"), b.emb_w = W("obj_embed.weight");
+    b.lc_side = b.pos_side || b.loc_w || b.cls_w || b.emb_w || W("location_projection.0.bias") || W("class_projection.0.bias");
+    return b;
+  }
+
+  // Token assembly: x0[p, t] = token + pos_embedding (ONE 576-vector broadcast over all tokens, model_veto.py:43,62): its gradient is
+  // the sum over every token row; the cls_token's is the sum over row 0 of every pair; then (objects: anything under the tokens has a
+  // consumer) the gradients of the per-object tables, dpatch and dlc
+  int assemble_backward(bool objects) {
+    const DropSite d = drop_site(opts, 2);   // pos_drop sits between (token + pos_embedding) and the first layer
+    if (d.thresh) HIP_TRY(launch_dropout_apply(ws.dx, ws.dx, (size_t)M, kDim, d, s));
+    if (float* g = G(T + "pos_embedding")) HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (float* g = G(T + "cls_token")) HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (!objects) return VETO_OK;
+    if (ordered) {
+      HIP_TRY(launch_assemble_backward_ordered(ws.dx, ws.subj, ws.obj, ws.lc, in->img_obj_offset, in->img_pair_offset, in->n_img, ws.dpatch, ws.dlc, n_obj, s));
+    } else {
+      HIP_TRY(hipMemsetAsync(ws.dpatch, 0, (size_t)n_obj * 16 * 2 * kDim * 4, s));
+      HIP_TRY(hipMemsetAsync(ws.dlc, 0, (size_t)n_obj * 2 * 2 * kDim * 4, s));
+      HIP_TRY(launch_assemble_backward(ws.dx, ws.subj, ws.obj, ws.lc, ws.dpatch, ws.dlc, n_pair, s));
+    }
+    return VETO_OK;
+  }
+
+  // Patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half)
+  int patch_backward(const Below& b) {
+    const int R = n_obj * 16;
+    if (b.patch_w || b.maps) HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, 2 * kDim, s));
+    // dWcat^T [2048, 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch in the roles of linear_backward swapped,
+    // so that the output width (1152) is a multiple of 192
+    if (b.patch_w) {
+      HIP_TRY(launch_wgrad(h, s, nullptr, ws.pa, ws.dsplit, ws.zero, R, 2048, 2 * kDim, patch_wgrad_split(R), ws.dwcat_t, ws.planes));
+      HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
+    }
+    // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
+    if (b.patch_b) {
+      HIP_TRY(launch_column_sums(ws.dpatch, 2 * kDim, R, kDim, ws.dgb, ws.col_partial, column_sums_chunks(), s));
+      HIP_TRY(copy_grad(pe + "proj_d.bias", ws.dgb, 512));
+      HIP_TRY(copy_grad(pe + "proj_v.bias", ws.dgb + 512, 64));
+    }
+    // input gradient (optional): dPA = dpatch . Wcat, i.e. the forward GEMM kernel on split(dpatch) (still in ws.dsplit) and
+    // Wcat^T as the weight operand; then the inverse of patchify onto the ROI maps.  The reference's depth backbone is
+    // trained through roi_depth_features (tools/relation_train_net.py:166-170).
+    if (b.maps) {
+      HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, s));
+      GemmArgs g{};
+      g.a = ws.dsplit; g.w = ws.wcat_t; g.c = ws.dpa;
+      g.M = R; g.N = kPatchTRows; g.K = 2 * kDim; g.ldc = kPatchTRows;
+      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
+      HIP_TRY(launch_unpatchify(ws.dpa, kPatchTRows, opts->d_roi_depth, opts->d_roi_rgb, n_obj, s));
+    }
+    return VETO_OK;
+  }
+
+  static constexpr long kLdLc = 2 * 2 * kDim;   // dlc row n = [location 1152 | class 1152]
+
+  // the biases of the location / class projections: they sit on the subject half
+  int lc_bias_backward() {
+    if (float* g = G("location_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc, kLdLc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (float* g = G("class_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc + 2 * kDim, kLdLc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
+    return VETO_OK;
+  }
+
+  // Position branch: pos_embed.0 (BatchNorm), pos_embed.1 and the location projection's weight
+  int position_backward(const Below& b) {
+    const DropSite site = drop_site(opts, 1);   // Dropout(0.1) behind the ReLU of pos_embed
+    if (b.pos_side || b.loc_w) {      // (the location projection's weight gradient reads bn_out, which obj_pos_backward recomputes)
+      // recompute pos (post-ReLU) through the masked gradient path
+      //   dpos = dlc_loc . loc_wt^T ; obj_pos_backward -> dpre (ReLU'), BatchNorm affine gradients
+      HIP_TRY(launch_sgemm_nt(ws.dlc, kLdLc, h->loc_wt, 2 * kDim, ws.dpos, kPosDim, n_obj, kPosDim, 2 * kDim, s));
+      if (site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, site, s));
+      // (what the forward normalised with: this batch's statistics, or the running ones of an eval-mode pos_embed.0)
+      const float* bn_mean = sch.bn_eval ? h->p("pos_embed.0.running_mean") : in->bn_batch_stats;
+      const float* bn_var = sch.bn_eval ? h->p("pos_embed.0.running_var") : in->bn_batch_stats + 4;
+      HIP_TRY(launch_obj_pos_backward(in->boxes, in->box_mode, bn_mean, bn_var, h->p("pos_embed.0.weight"), h->p("pos_embed.0.bias"),
+                                      h->p("pos_embed.1.weight"), h->p("pos_embed.1.bias"), ws.dpos, ws.dpre, ws.xhat, ws.bn_out, ws.dbn_out,
+                                      G("pos_embed.0.weight"), G("pos_embed.0.bias"), n_obj, s));
+    }
+    // pos_embed.1: Linear(4, 128): dW[k, c] = sum_n dpre[n, k] bn_out[n, c]; db = column sums of dpre
+    if (float* g = G("pos_embed.1.weight")) HIP_TRY(launch_sgemm_tn(ws.dpre, kPosDim, ws.bn_out, 4, g, 4, n_obj, kPosDim, 4, s));
+    if (float* g = G("pos_embed.1.bias")) HIP_TRY(launch_column_sums(ws.dpre, kPosDim, n_obj, kPosDim, g, ws.col_partial, column_sums_chunks(), s));
+    if (!b.loc_w) return VETO_OK;
+    // location_projection weight: d loc_wt[k, j] = sum_n pos[n, k] dlc_loc[n, j] with the forward's pos, recomputed from bn_out:
+    // pos[n, k] = dropout(relu(pos_b[k] + sum_c pos_w[k, c] bn_out[n, c])): one small product + ReLU, with dpos as its storage
+    HIP_TRY(launch_sgemm_nt(ws.bn_out, 4, h->p("pos_embed.1.weight"), 4, ws.dpos, kPosDim, n_obj, kPosDim, 4, s));
+    HIP_TRY(launch_bias_relu(ws.dpos, h->p("pos_embed.1.bias"), n_obj, kPosDim, s));
+    if (site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, site, s));
+    HIP_TRY(launch_sgemm_tn(ws.dpos, kPosDim, ws.dlc, kLdLc, ws.dloc_wt, 2 * kDim, n_obj, kPosDim, 2 * kDim, s));
+    HIP_TRY(launch_untranspose_pair_proj(ws.dloc_wt, G("location_projection.0.weight"), kPosDim, s));
+    return VETO_OK;
+  }
+
+  // Class branch: emb = E[label] (hard labels) or softmax(logits) . E (sgcls, :4092-4095);
+  // d cls_wt[k, j] = sum_n emb[n, k] dlc_cls[n, j]; demb = dlc_cls . cls_wt^T
+  int class_backward(const Below& b) {
+    const int C_obj = h->cfg.num_obj_cls, E = h->cfg.embed_dim;
+    if (in->obj_logits && (b.cls_w || b.emb_w)) HIP_TRY(launch_softmax_rows(in->obj_logits, ws.prob, n_obj, C_obj, s));
+    if (b.cls_w) {
+      if (in->obj_logits) HIP_TRY(launch_sgemm_nn(ws.prob, C_obj, h->p("obj_embed.weight"), E, ws.emb, E, n_obj, E, C_obj, s));
+      else HIP_TRY(launch_gather_rows(h->p("obj_embed.weight"), in->obj_labels, E, ws.emb, n_obj, s));
+      HIP_TRY(launch_sgemm_tn(ws.emb, E, ws.dlc + 2 * kDim, kLdLc, ws.dcls_wt, 2 * kDim, n_obj, E, 2 * kDim, s));
+      HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
+    }
+    if (float* g = G("obj_embed.weight")) {
+      HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, kLdLc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
+      if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, g, E, n_obj, C_obj, E, s));
+      else if (ordered) HIP_TRY(launch_scatter_rows_ordered(ws.demb, in->obj_labels, E, g, n_obj, C_obj, s));
+      else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, g, n_obj, s));
+    }
+    return VETO_OK;
+  }
+};
+
 }  // namespace
+
+// ---- the weight-gradient GEMM (abi_internal.h) -----------------------------------------------------------------------------
+WgradSplit wgrad_split(int n, int k, int m, int k_splits, int min_ksteps, int cap) {
+  int ks = k_splits;
+  if (ks <= 0) {
+    const int out_tiles = ((n + 255) / 256) * (k / 192);
+    const int max_ks = (m + 32 * min_ksteps - 1) / (32 * min_ksteps);     // at least min_ksteps k-steps per tile
+    ks = std::max(1, std::min(2 * 256 / out_tiles, max_ks));              // just under 2 full rounds of the 256 persistent workgroups
+  }
+  if (cap > 0 && ks > cap) ks = cap;
+  const size_t step = 32 * (size_t)ks;
+  return WgradSplit{ks, ((size_t)m + step - 1) / step * step, (size_t)ks * n * k};
+}
+
+hipError_t launch_wgrad(veto_handle_t h, hipStream_t s, const char* scope, const __bf16* a, const __bf16* b, const __bf16* zero, int m, int n,
+                        int k, const WgradSplit& sp, float* dw, float* planes) {
+  hipError_t e = planes ? hipSuccess : hipMemsetAsync(dw, 0, (size_t)n * k * 4, s);
+  if (e != hipSuccess) return e;
+  GemmArgs g{};
+  g.a = a; g.w = b; g.c = planes ? planes : dw;
+  g.M = n; g.N = k; g.K = (int)sp.mp; g.ldc = k; g.k_splits = sp.ks;
+  if (zero) { g.tn = 1; g.lda = 2 * (long)n; g.ldw = 2 * (long)k; g.k_valid = m; g.zero = zero; }
+  ProfScope ps(scope ? h : nullptr, s, scope, 2.0 * m * (double)n * k, 0);
+  e = launch_gemm_split(g, planes ? EPI_PLANES : EPI_ATOMIC, 0, s);
+  if (e == hipSuccess && planes) e = launch_fold_rows(planes, (long)n * k, sp.ks, (long)n * k, dw, s);      // the planes in split order
+  return e;
+}
 
 extern "C" {
 
@@ -376,76 +737,17 @@ static int forward_train_impl(veto_handle_t h, void* stream, const veto_inputs_t
                               void* workspace, size_t workspace_bytes, float* out_logits) {
   ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes, sch));
   if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
-  hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (h->dirty) ABI_TRY(finalize_weights(h, s, true));
+  if (h->dirty) ABI_TRY(finalize_weights(h, (hipStream_t)stream, true));
   h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
   h->train_plan.erase(workspace);
-  const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out;
-  const int M = n_pair * kTokens;
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, opts_ordered(opts), sch);
-  HIP_TRY(launch_pair_indices(in->rel_pairs, in->img_obj_offset, in->img_pair_offset, in->n_img, n_pair, ws.subj, ws.obj, nullptr,
-                              nullptr, s));
-  {
-    veto_inputs_t in_bn = *in;      // (an eval-mode pos_embed.0: the running statistics, as the inference forward reads them)
-    if (sch.bn_eval) in_bn.bn_batch_stats = nullptr;
-    else HIP_TRY(launch_bn_batch_stats(in->boxes, in->box_mode, n_obj, in->bn_batch_stats, s));
-    ObjPrepArgs a = obj_prep_args(h, &in_bn, ws.lc);
-    const DropSite d = drop_site(opts, 1);
-    a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale;
-    HIP_TRY(launch_obj_prep(a, s));
-  }
-  HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
-  ABI_TRY(run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16,
-                   2 * kDim, 2048, EPI_F32));
-  {
-    AssembleArgs a = assemble_args(h, ws.patch_tab, ws.lc, ws.subj, ws.obj, ws.layers[0].xin, ws.layers[0].a1, n_pair);
-    const DropSite d = drop_site(opts, 2);
-    a.drop_seed = d.seed; a.drop_thresh = d.thresh; a.drop_scale = d.scale;
-    HIP_TRY(launch_assemble(a, s));
-  }
-  const bool q24 = train_qkv_f24(h);
-  const int qepi = q24 ? EPI_F24 : EPI_F32;
-  for (int l = 0; l < L; ++l) {
-    const LayerW& w = h->layers[l];
-    TrainLayer& t = ws.layers[l];
-    if (l == L - 1) {
-      // Last layer: only x[:, 0] reaches the loss (model_veto.py:23), so -- as at inference -- keys / values cover the 19
-      // tokens, everything behind the attention runs on the CLS row of each pair.  The saved activations of this layer
-      // (ao, xmid, a2, pre, hid, ws.xout) are COMPACT: row p = pair p.  The backward mirrors this.
-      ABI_TRY(run_gemm(h, s, "gemm_kv_last", t.a1, w.qkv, nullptr, nullptr, 0, q24 ? (float*)((char*)t.qkv + 3 * kDim) : t.qkv + kDim, nullptr,
-                       3 * kDim, M, 2 * kDim, kDim, qepi, 0, kDim));
-      ABI_TRY(run_gemm(h, s, "gemm_q_cls", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, (long)kTokens * 3 * kDim, n_pair, kDim, kDim,
-                       qepi, (long)kTokens * 2 * kDim, 0));
-      {
-        AttnArgs a{};
-        a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 1; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
-        HIP_TRY(launch_attention(a, s));
-      }
-      ABI_TRY(run_gemm(h, s, "gemm_out_cls", t.ao, w.out, w.out_b, t.xin, (long)kTokens * kDim, t.xmid, nullptr, kDim, n_pair, kDim, kDim,
-                       EPI_RESID, 0, 0, drop_site(opts, 3 + l, kTokens, &sch)));
-      HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, n_pair, s));
-      ABI_TRY(run_gemm(h, s, "gemm_fc1_cls", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, n_pair, 2 * kDim, kDim, EPI_PRE_GELU));
-      ABI_TRY(run_gemm(h, s, "gemm_fc2_cls", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, ws.xout, nullptr, kDim, n_pair, kDim, 2 * kDim, EPI_RESID));
-      break;
-    }
-    float* xnext = ws.layers[l + 1].xin;
-    ABI_TRY(run_gemm(h, s, "gemm_qkv", t.a1, w.qkv, nullptr, nullptr, 0, t.qkv, nullptr, 3 * kDim, M, 3 * kDim, kDim, qepi));
-    {
-      AttnArgs a{};
-      a.qkv = t.qkv; a.n_pair = n_pair; a.heads = H; a.cls_only = 0; a.o = t.ao; a.qkv_f24 = q24 ? 1 : 0;
-      HIP_TRY(launch_attention(a, s));
-    }
-    ABI_TRY(run_gemm(h, s, "gemm_out", t.ao, w.out, w.out_b, t.xin, kDim, t.xmid, nullptr, kDim, M, kDim, kDim, EPI_RESID, 0, 0,
-                     drop_site(opts, 3 + l, 1, &sch)));
-    HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, M, s));
-    // (the epilogue writes the fp32 pre-activation -- gelu' needs it -- AND its exact-erf GELU as fc2's split rows: round 6; before, a pass
-    // of its own read the pre-activation back, 0.55 ms per layer)
-    ABI_TRY(run_gemm(h, s, "gemm_fc1", t.a2, w.fc1, w.fc1_b, nullptr, 0, t.pre, t.hid, 4 * kDim, M, 2 * kDim, kDim, EPI_PRE_GELU));
-    ABI_TRY(run_gemm(h, s, "gemm_fc2", t.hid, w.fc2, w.fc2_b, t.xmid, kDim, xnext, nullptr, kDim, M, kDim, 2 * kDim, EPI_RESID));
-    HIP_TRY(launch_layernorm(xnext, kDim, h->layers[l + 1].ln1_w, h->layers[l + 1].ln1_b, ws.layers[l + 1].a1, M, s));
-  }
-  HIP_TRY(launch_head(ws.xout, h->head_wt, h->p("rel_out.bias"), out_logits, n_pair, n_out, s, (long)kDim));
+  TrainStep st(h, stream, in, opts, sch, workspace);
+  ABI_TRY(st.object_side());
+  ABI_TRY(st.patch_projection());
+  ABI_TRY(st.assemble_tokens());
+  for (int l = 0; l < st.L - 1; ++l) ABI_TRY(st.layer(l));
+  ABI_TRY(st.last_layer());
+  ABI_TRY(st.head(out_logits));
   h->stamp_train_workspace(workspace);
   if (!sch.full) h->train_plan[workspace] = sch.key;
   return VETO_OK;
@@ -472,7 +774,6 @@ static int backward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in,
   if (!dlogits || !grads) return fail(VETO_ERR_INVALID, "null gradient pointer");
   if (!sch.maps && opts && (opts->d_roi_rgb || opts->d_roi_depth))
     return fail(VETO_ERR_INVALID, "veto_backward_plan: d_roi_rgb / d_roi_depth asked for under a plan with d_roi == 0");
-  hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
   // the backward reads the derived operands the matching forward used: a weight upload in between would pair this
   // workspace's activations with different weights
@@ -482,253 +783,24 @@ static int backward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in,
     if (it == h->train_gen.end()) return fail(VETO_ERR_INVALID, "veto_backward: this workspace holds no veto_forward_train activations");
     if (it->second != h->weight_gen)
       return fail(VETO_ERR_WEIGHTS, "veto_backward: the weights were refreshed (by a later forward) since this workspace's veto_forward_train");
-    auto pl = h->train_plan.find(workspace);
+    auto pl = h->train_plan.find(workspace);      // (before any launch)
     if (sch.full ? pl != h->train_plan.end() : pl == h->train_plan.end() || pl->second != sch.key)
       return fail(VETO_ERR_INVALID, "veto_backward: this workspace's forward ran under another plan (veto_train_plan_t) than this backward");
   }
-  const int n_obj = in->n_obj, n_pair = in->n_pair, L = h->cfg.layers, H = h->cfg.heads, n_out = h->cfg.num_out, E = h->cfg.embed_dim;
-  const int M = n_pair * kTokens;
-  const bool ordered = opts_ordered(opts);
-  TrainWs ws = carve_train((char*)workspace, h, n_obj, n_pair, ordered, sch);
-  const std::string T = kT;
-  // (a frozen tensor has no gradient pointer: every launch below that would only write it is left out)
-  auto W = [&](const std::string& name) { return sch.want(h, name); };
-  auto G = [&](const std::string& name) -> float* { return W(name) ? grads + h->params[h->index.at(name)].offset : nullptr; };
-  auto copy_grad = [&](const std::string& name, const float* src, size_t n) {
-    float* g = G(name);
-    return g ? hipMemcpyAsync(g, src, n * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
-  };
-  struct LinGrad { const float* w; float *dw, *db; int N, K; };      // a layer's Linear (kLayerLinears): weight, its and the bias's gradient
-  auto lin = [&](int l, int i) {
-    const LayerLinear& q = kLayerLinears[i];
-    return LinGrad{h->p(lname(l, q.weight)), G(lname(l, q.weight)), q.bias ? G(lname(l, q.bias)) : nullptr, q.N, q.K};
-  };
-  if (sch.full) {
-    HIP_TRY(hipMemsetAsync(grads, 0, veto_grad_floats(h) * 4, s));
-  } else {      // the regions of the trainable tensors only, neighbours in one fill (tensors lie in index order, padded to 64 floats)
-    for (size_t i = 0; i < h->params.size();) {
-      if (!sch.on[i]) { ++i; continue; }
-      size_t j = i;
-      while (j + 1 < h->params.size() && sch.on[j + 1]) ++j;
-      HIP_TRY(hipMemsetAsync(grads + h->params[i].offset, 0, (h->params[j].offset + h->params[j].numel - h->params[i].offset) * 4, s));
-      i = j + 1;
-    }
-  }
-  HIP_TRY(hipMemsetAsync(ws.zero, 0, 1024, s));
-
-  // ---- classifier head: gradient of the compact CLS rows (not written when nothing under the head has a consumer) --------
-  HIP_TRY(launch_head_backward(dlogits, h->p("rel_out.weight"), ws.xout, sch.keep_from < L ? ws.dx : nullptr, G("rel_out.weight"),
-                               G("rel_out.bias"), ws.head_partial, n_pair, n_out, (long)kDim, s));
-
-  // ---- transformer layers, last to first -------------------------------------------------------------------------
-  // A layer's stages in chain order: fc2, fc1, LayerNorm2, out, attention, qkv, LayerNorm1.  own[i]: stage i has a trainable tensor;
-  // deeper[i]: something behind it (in this layer, a lower one or under layer 0) has a consumer, so its input gradient is computed.
-  // The walk ends behind the first stage with deeper[i] == false: every later stage of every lower layer is without a consumer too.
-  int dx_presplit = 0;      // > 0: ws.dsplit / ws.colp already hold the split rows / that many rows of column partials of ws.dx
-  for (int l = L - 1; l >= sch.keep_from; --l) {
-    const LayerW& w = h->layers[l];
-    TrainLayer& t = ws.layers[l];
-    const bool last = l == L - 1;
-    const int R = last ? n_pair : M;     // rows behind the attention: the CLS rows only in the last layer (compact buffers)
-    // x_out = x_mid + gelu(LN2(x_mid) W1^T + b1) W2^T + b2
-    // dpre = dh * gelu'(pre): in the epilogue of fc2's input-gradient GEMM (round 6; VETO_TRAIN_GELU_EPI=0: a pass of its own inside the
-    // operand preparation of the fc1 backward, rounds 1-5)
-    // (the gradient of this layer's output: compact CLS rows from the head in the last layer, else the rows the LayerNorm1 backward of the
-    // layer above left -- with their split rows and bias partials when it emitted them)
-    const float* dy2 = dx_presplit ? nullptr : ws.dx;
-    const bool recompute = train_recompute();
-    const LinGrad qkv = lin(l, LIN_QKV), out = lin(l, LIN_OUT), fc1 = lin(l, LIN_FC1), fc2 = lin(l, LIN_FC2);
-    const bool ln1 = W(lname(l, "0.norm.weight")) || W(lname(l, "0.norm.bias")), ln2 = W(lname(l, "1.norm.weight")) || W(lname(l, "1.norm.bias"));
-    enum { S_FC2, S_FC1, S_LN2, S_OUT, S_ATTN, S_QKV, S_LN1, S_COUNT };
-    const bool own[S_COUNT] = {fc2.dw || fc2.db, fc1.dw || fc1.db, ln2, out.dw || out.db, false, qkv.dw != nullptr, ln1};
-    bool deeper[S_COUNT];
-    for (int i = S_COUNT - 1, acc = sch.need(l); i >= 0; --i) {
-      deeper[i] = acc;
-      acc = acc || own[i];
-    }
-    if (recompute && fc2.dw) HIP_TRY(launch_gelu_split(t.pre, t.hid, (size_t)R, 2 * kDim, s));      // gelu(pre): fc2's operand, as the forward's epilogue wrote it
-    if (train_gelu_epilogue()) {
-      int partials = 0;
-      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, nullptr, GradXform(), nullptr, dx_presplit,
-                                  deeper[S_FC2] ? t.pre : nullptr, &partials));
-      if (!deeper[S_FC2]) break;
-      if (recompute && fc1.dw) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));      // LayerNorm2 rows: fc1's operand
-      ABI_TRY(run_linear_backward(h, s, ws, nullptr, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, deeper[S_FC1] ? ws.dtmp : nullptr, GradXform(),
-                                  ws.dsplit_b, partials));
-    } else {
-      ABI_TRY(run_linear_backward(h, s, ws, dy2, R, fc2.N, t.hid, fc2.K, fc2.w, fc2.dw, fc2.db, deeper[S_FC2] ? ws.dbig : nullptr, GradXform(), nullptr,
-                                  dx_presplit));
-      if (!deeper[S_FC2]) break;
-      GradXform gelu;              // dpre = dh * gelu'(pre), folded into the operand preparation of the fc1 backward
-      gelu.mode = XF_GELU;
-      gelu.pre = t.pre;
-      if (recompute && fc1.dw) HIP_TRY(launch_layernorm(t.xmid, kDim, w.ln2_w, w.ln2_b, t.a2, R, s));
-      ABI_TRY(run_linear_backward(h, s, ws, ws.dbig, R, fc1.N, t.a2, fc1.K, fc1.w, fc1.dw, fc1.db, deeper[S_FC1] ? ws.dtmp : nullptr, gelu));
-    }
-    if (!deeper[S_FC1]) break;
-    // x_mid = x_in + dropout(attention(LN1(x_in) Wqkv^T) Wo^T + bo): the projection sees the masked gradient
-    const DropSite dsite = drop_site(opts, 3 + l, l == L - 1 ? kTokens : 1, &sch);      // (last layer: compact CLS rows, as in the forward)
-    const bool ln_split = train_ln_emits_split();
-    if (ln_split)
-      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ln2 ? ws.dgb : nullptr, ws.ln_partial, R, s, ws.dsplit, ws.colp,
-                                        dsite.seed, dsite.thresh, dsite.scale, dsite.row_step, ordered));
-    else
-      HIP_TRY(launch_layernorm_backward(t.xmid, ws.dtmp, w.ln2_w, ws.dx, ws.dmid, ln2 ? ws.dgb : nullptr, ws.ln_partial, R, s, nullptr, nullptr, 0, 0, 1.f, 1,
-                                        ordered));
-    HIP_TRY(copy_grad(lname(l, "1.norm.weight"), ws.dgb, kDim));
-    HIP_TRY(copy_grad(lname(l, "1.norm.bias"), ws.dgb + kDim, kDim));
-    if (!deeper[S_LN2]) break;
-    GradXform drop;
-    if (dsite.thresh) {
-      drop.mode = XF_DROP;
-      drop.seed = dsite.seed;
-      drop.thresh = dsite.thresh;
-      drop.scale = dsite.scale;
-      drop.row_step = dsite.row_step;
-    }
-    ABI_TRY(run_linear_backward(h, s, ws, ln_split ? nullptr : ws.dmid, R, out.N, t.ao, out.K, out.w, out.dw, out.db, deeper[S_OUT] ? ws.dtmp : nullptr,
-                                drop, nullptr, ln_split ? layernorm_backward_col_partials(R) : 0));
-    if (!deeper[S_OUT]) break;
-    HIP_TRY(launch_attention_backward(t.qkv, ws.dtmp, nullptr, ws.dsplit, n_pair, H, last ? 1 : 0, s, train_qkv_f24(h)));
-    if (recompute && qkv.dw) HIP_TRY(launch_layernorm(t.xin, kDim, w.ln1_w, w.ln1_b, t.a1, M, s));      // LayerNorm1 rows: the QKV projection's operand
-    ABI_TRY(run_linear_backward(h, s, ws, nullptr, M, qkv.N, t.a1, qkv.K, qkv.w, qkv.dw, qkv.db, deeper[S_QKV] ? ws.dtmp : nullptr));
-    if (!deeper[S_QKV]) break;
-    const float* dres = ws.dmid;
-    if (last) {
-      // the residual gradient d x_mid lives on the CLS rows only: spread the compact rows over a zeroed token matrix
-      HIP_TRY(hipMemsetAsync(ws.dx, 0, (size_t)M * kDim * 4, s));
-      HIP_TRY(hipMemcpy2DAsync(ws.dx, (size_t)kTokens * kDim * 4, ws.dmid, (size_t)kDim * 4, (size_t)kDim * 4, (size_t)n_pair,
-                               hipMemcpyDeviceToDevice, s));
-      dres = ws.dx;
-    }
-    // (in the last layer dres == ws.dx is also the output: every element is read and written by the same thread)
-    if (ln_split && l > 0) {      // (its result is the gradient matrix of fc2 of the layer below)
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ln1 ? ws.dgb : nullptr, ws.ln_partial, M, s, ws.dsplit, ws.colp, 0, 0, 1.f, 1,
-                                        ordered));
-      dx_presplit = layernorm_backward_col_partials(M);
-    } else {
-      HIP_TRY(launch_layernorm_backward(t.xin, ws.dtmp, w.ln1_w, dres, ws.dx, ln1 ? ws.dgb : nullptr, ws.ln_partial, M, s, nullptr, nullptr, 0, 0, 1.f, 1,
-                                        ordered));
-      dx_presplit = 0;
-    }
-    HIP_TRY(copy_grad(lname(l, "0.norm.weight"), ws.dgb, kDim));
-    HIP_TRY(copy_grad(lname(l, "0.norm.bias"), ws.dgb + kDim, kDim));
-  }
+  TrainStep st(h, stream, in, opts, sch, workspace, grads);
+  ABI_TRY(st.zero_grads());
+  ABI_TRY(st.head_backward(dlogits));
+  for (int l = st.L - 1; l >= sch.keep_from; --l) ABI_TRY(st.layer_backward(l));      // last to first
   if (!sch.below) return VETO_OK;      // (the walk above ended inside a layer, or behind layer keep_from)
-
-  // ---- token assembly: cls_token, pos_embedding, per-object tables -----------------------------------------------
-  // x0[p, t] = token + pos_embedding (ONE 576-vector broadcast over all tokens, model_veto.py:43,62): its gradient is
-  // the sum over every token row; the cls_token's is the sum over row 0 of every pair
-  {
-    const DropSite d = drop_site(opts, 2);   // pos_drop sits between (token + pos_embedding) and the first layer
-    if (d.thresh) HIP_TRY(launch_dropout_apply(ws.dx, ws.dx, (size_t)M, kDim, d.seed, d.thresh, d.scale, s));
-  }
-  if (float* g = G(T + "pos_embedding")) HIP_TRY(launch_column_sums(ws.dx, kDim, M, kDim, g, ws.col_partial, column_sums_chunks(), s));
-  if (float* g = G(T + "cls_token")) HIP_TRY(launch_column_sums(ws.dx, (long)kTokens * kDim, n_pair, kDim, g, ws.col_partial, column_sums_chunks(), s));
-  const std::string pe = T + "patch_embed.";
-  const bool want_maps = opts && (opts->d_roi_rgb || opts->d_roi_depth);
-  const bool patch_w = W(pe + "proj_d.weight") || W(pe + "proj_v.weight"), patch_b = W(pe + "proj_d.bias") || W(pe + "proj_v.bias");
-  const bool pos_side = W("pos_embed.0.weight") || W("pos_embed.0.bias") || W("pos_embed.1.weight") || W("pos_embed.1.bias");
-  const bool loc_w = W("location_projection.0.weight"), cls_w = W("class_projection.0.weight"), emb_w = W("obj_embed.weight");
-  const bool lc_side = pos_side || loc_w || cls_w || emb_w || W("location_projection.0.bias") || W("class_projection.0.bias");
-  if (!(patch_w || patch_b || want_maps || lc_side)) return VETO_OK;
-  if (ordered) {
-    HIP_TRY(launch_assemble_backward_ordered(ws.dx, ws.subj, ws.obj, ws.lc, in->img_obj_offset, in->img_pair_offset, in->n_img, ws.dpatch,
-                                             ws.dlc, n_obj, s));
-  } else {
-    HIP_TRY(hipMemsetAsync(ws.dpatch, 0, (size_t)n_obj * 16 * 2 * kDim * 4, s));
-    HIP_TRY(hipMemsetAsync(ws.dlc, 0, (size_t)n_obj * 2 * 2 * kDim * 4, s));
-    HIP_TRY(launch_assemble_backward(ws.dx, ws.subj, ws.obj, ws.lc, ws.dpatch, ws.dlc, n_pair, s));
-  }
-
-  // ---- patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half) ------------------------
-  {
-    const int R = n_obj * 16;
-    if (patch_w || want_maps) HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, 2 * kDim, s));
-    // dWcat^T [2048, 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch (fp32) in run_wgrad's roles swapped,
-    // so that the output width (1152) is a multiple of 192
-    if (patch_w) {
-      const int N = 2048, K = 2 * kDim;
-      const int ks = wgrad_splits(N, K, R, 0, 8);      // (few object rows: tiles of 8 k-steps already)
-      const size_t mp = wgrad_mp(R, ks);
-      if (!ordered) HIP_TRY(hipMemsetAsync(ws.dwcat_t, 0, (size_t)N * K * 4, s));
-      GemmArgs g{};
-      g.a = ws.pa; g.w = ws.dsplit; g.c = ordered ? ws.planes : ws.dwcat_t;
-      g.M = N; g.N = K; g.K = (int)mp; g.ldc = K; g.k_splits = ks;
-      g.tn = 1; g.lda = 2 * (long)N; g.ldw = 2 * (long)K; g.k_valid = R; g.zero = ws.zero;
-      HIP_TRY(launch_gemm_split(g, ordered ? EPI_PLANES : EPI_ATOMIC, 0, s));
-      if (ordered) HIP_TRY(launch_fold_rows(ws.planes, (long)N * K, ks, (long)N * K, ws.dwcat_t, s));
-      HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
-    }
-    // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
-    if (patch_b) {
-      HIP_TRY(launch_column_sums(ws.dpatch, 2 * kDim, R, kDim, ws.dgb, ws.col_partial, column_sums_chunks(), s));
-      HIP_TRY(copy_grad(pe + "proj_d.bias", ws.dgb, 512));
-      HIP_TRY(copy_grad(pe + "proj_v.bias", ws.dgb + 512, 64));
-    }
-    // input gradient (optional): dPA = dpatch . Wcat, i.e. the forward GEMM kernel on split(dpatch) (still in ws.dsplit) and
-    // Wcat^T as the weight operand; then the inverse of patchify onto the ROI maps.  The reference's depth backbone is
-    // trained through roi_depth_features (tools/relation_train_net.py:166-170).
-    if (want_maps) {
-      HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, s));
-      GemmArgs g{};
-      g.a = ws.dsplit; g.w = ws.wcat_t; g.c = ws.dpa;
-      g.M = R; g.N = kPatchTRows; g.K = 2 * kDim; g.ldc = kPatchTRows;
-      HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
-      HIP_TRY(launch_unpatchify(ws.dpa, kPatchTRows, opts->d_roi_depth, opts->d_roi_rgb, n_obj, s));
-    }
-  }
-
-  // ---- location / class projections and what feeds them -----------------------------------------------------------
-  if (lc_side) {
-    const long ldlc = 2 * 2 * kDim;   // dlc row n = [location 1152 | class 1152]
-    // biases sit on the subject half
-    if (float* g = G("location_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc, ldlc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
-    if (float* g = G("class_projection.0.bias")) HIP_TRY(launch_column_sums(ws.dlc + 2 * kDim, ldlc, n_obj, kDim, g, ws.col_partial, column_sums_chunks(), s));
-    const DropSite dpos_site = drop_site(opts, 1);   // Dropout(0.1) behind the ReLU of pos_embed
-    if (pos_side || loc_w) {      // (the location projection's weight gradient reads bn_out, which obj_pos_backward recomputes)
-      // position branch: recompute pos (post-ReLU) through the masked gradient path
-      //   dpos = dlc_loc . loc_wt^T ; obj_pos_backward -> dpre (ReLU'), BatchNorm affine gradients
-      HIP_TRY(launch_sgemm_nt(ws.dlc, ldlc, h->loc_wt, 2 * kDim, ws.dpos, kPosDim, n_obj, kPosDim, 2 * kDim, s));
-      if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
-      // (what the forward normalised with: this batch's statistics, or the running ones of an eval-mode pos_embed.0)
-      const float* bn_mean = sch.bn_eval ? h->p("pos_embed.0.running_mean") : in->bn_batch_stats;
-      const float* bn_var = sch.bn_eval ? h->p("pos_embed.0.running_var") : in->bn_batch_stats + 4;
-      HIP_TRY(launch_obj_pos_backward(in->boxes, in->box_mode, bn_mean, bn_var, h->p("pos_embed.0.weight"), h->p("pos_embed.0.bias"),
-                                      h->p("pos_embed.1.weight"), h->p("pos_embed.1.bias"), ws.dpos, ws.dpre, ws.xhat, ws.bn_out, ws.dbn_out,
-                                      G("pos_embed.0.weight"), G("pos_embed.0.bias"), n_obj, s));
-    }
-    // pos_embed.1: Linear(4, 128): dW[k, c] = sum_n dpre[n, k] bn_out[n, c]; db = column sums of dpre
-    if (float* g = G("pos_embed.1.weight")) HIP_TRY(launch_sgemm_tn(ws.dpre, kPosDim, ws.bn_out, 4, g, 4, n_obj, kPosDim, 4, s));
-    if (float* g = G("pos_embed.1.bias")) HIP_TRY(launch_column_sums(ws.dpre, kPosDim, n_obj, kPosDim, g, ws.col_partial, column_sums_chunks(), s));
-    if (loc_w) {
-      // location_projection weight: d loc_wt[k, j] = sum_n pos[n, k] dlc_loc[n, j], pos = relu(pre): recompute pos = the
-      // forward's value; it equals (dpre != 0 ? ... ) no -- recompute it from bn_out
-      // pos[n, k] = relu(pos_b[k] + sum_c pos_w[k, c] bn_out[n, c]): one small product + ReLU, done by reusing dpos as storage
-      HIP_TRY(launch_sgemm_nt(ws.bn_out, 4, h->p("pos_embed.1.weight"), 4, ws.dpos, kPosDim, n_obj, kPosDim, 4, s));
-      HIP_TRY(launch_bias_relu(ws.dpos, h->p("pos_embed.1.bias"), n_obj, kPosDim, s));
-      if (dpos_site.thresh) HIP_TRY(launch_dropout_apply(ws.dpos, ws.dpos, (size_t)n_obj, kPosDim, dpos_site.seed, dpos_site.thresh, dpos_site.scale, s));
-      HIP_TRY(launch_sgemm_tn(ws.dpos, kPosDim, ws.dlc, ldlc, ws.dloc_wt, 2 * kDim, n_obj, kPosDim, 2 * kDim, s));
-      HIP_TRY(launch_untranspose_pair_proj(ws.dloc_wt, G("location_projection.0.weight"), kPosDim, s));
-    }
-    // class branch: emb = E[label] (hard labels) or softmax(logits) . E (sgcls, :4092-4095);
-    // d cls_wt[k, j] = sum_n emb[n, k] dlc_cls[n, j]; demb = dlc_cls . cls_wt^T
-    const int C_obj = h->cfg.num_obj_cls;
-    if (in->obj_logits && (cls_w || emb_w)) HIP_TRY(launch_softmax_rows(in->obj_logits, ws.prob, n_obj, C_obj, s));
-    if (cls_w) {
-      if (in->obj_logits) HIP_TRY(launch_sgemm_nn(ws.prob, C_obj, h->p("obj_embed.weight"), E, ws.emb, E, n_obj, E, C_obj, s));
-      else HIP_TRY(launch_gather_rows(h->p("obj_embed.weight"), in->obj_labels, E, ws.emb, n_obj, s));
-      HIP_TRY(launch_sgemm_tn(ws.emb, E, ws.dlc + 2 * kDim, ldlc, ws.dcls_wt, 2 * kDim, n_obj, E, 2 * kDim, s));
-      HIP_TRY(launch_untranspose_pair_proj(ws.dcls_wt, G("class_projection.0.weight"), E, s));
-    }
-    if (float* g = G("obj_embed.weight")) {
-      HIP_TRY(launch_sgemm_nt(ws.dlc + 2 * kDim, ldlc, h->cls_wt, 2 * kDim, ws.demb, E, n_obj, E, 2 * kDim, s));
-      if (in->obj_logits) HIP_TRY(launch_sgemm_tn(ws.prob, C_obj, ws.demb, E, g, E, n_obj, C_obj, E, s));
-      else if (ordered) HIP_TRY(launch_scatter_rows_ordered(ws.demb, in->obj_labels, E, g, n_obj, C_obj, s));
-      else HIP_TRY(launch_scatter_rows(ws.demb, in->obj_labels, E, g, n_obj, s));
-    }
-  }
-  return VETO_OK;
+  const TrainStep::Below b = st.below();
+  const bool objects = b.patch_w || b.patch_b || b.maps || b.lc_side;
+  ABI_TRY(st.assemble_backward(objects));      // pos_embedding, cls_token; objects: the per-object tables' dpatch / dlc
+  if (!objects) return VETO_OK;
+  ABI_TRY(st.patch_backward(b));      // (the split rows of dpatch in ws.dsplit feed both its weight and its map gradients)
+  if (!b.lc_side) return VETO_OK;
+  ABI_TRY(st.lc_bias_backward());
+  ABI_TRY(st.position_backward(b));
+  return st.class_backward(b);
 }
 
 int veto_backward(veto_handle_t h, void* stream, const veto_inputs_t* in, const veto_train_opts_t* opts, void* workspace,
@@ -788,315 +860,6 @@ int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint3
   a.incre = incre_idx_list; a.pos_in_group = pos_in_group; a.group_size = group_size; a.rates = sample_rates;
   a.chosen = chosen; a.group_labels = group_labels; a.counts = counts; a.words_used = words_used;
   HIP_TRY(launch_meet_sample(a, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-// n % 32 == 0 (every Linear of the transformer): the row-major form, both operands as the split rows the backward holds
-// anyway, transposed on their way out of LDS (GemmArgs::tn), one row more than m each (partial tiles read, never use, the row behind
-// the last) and the zero row of GemmArgs::zero.  Otherwise: explicit transposed split copies, dy's padded to whole row tiles.
-// ordered: behind the operands, the k_splits partial planes [n, k] fp32 of the ordered form (operand bytes: the size of the default form)
-struct WgradWs { __bf16 *a, *w, *zero; size_t operand_bytes; float* planes; size_t total; };
-static WgradWs carve_wgrad(Carver c, int m, int n, int k, int k_splits, bool ordered = false) {      // (a braced list evaluates left to right)
-  const int ks = wgrad_splits(n, k, m, k_splits);
-  const size_t plane_bytes = ordered ? (size_t)ks * n * k * 4 : 0;
-  if (n % 32 == 0) return WgradWs{c.take<__bf16>(((size_t)m + 1) * n * 4), c.take<__bf16>(((size_t)m + 1) * k * 4), c.take<__bf16>(1024), c.off,
-                                  ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
-  const size_t mp = wgrad_mp(m, ks);
-  return WgradWs{c.take<__bf16>((size_t)gemm_rows_padded(n) * mp * 4), c.take<__bf16>((size_t)k * mp * 4), nullptr, c.off,
-                 ordered ? c.take<float>(plane_bytes) : nullptr, c.off};
-}
-
-static int debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k, int32_t k_splits,
-                       void* workspace, size_t workspace_bytes, bool ordered);
-
-size_t veto_debug_wgrad_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
-  if (m <= 0 || n <= 0 || k <= 0) return 0;
-  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits).total;
-}
-
-size_t veto_debug_wgrad_ordered_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t k_splits) {
-  if (m <= 0 || n <= 0 || k <= 0) return 0;
-  return carve_wgrad(Carver{nullptr}, m, n, k, k_splits, true).total;
-}
-
-int veto_debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
-                     int32_t k_splits, void* workspace, size_t workspace_bytes) {
-  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, false);
-}
-
-int veto_debug_wgrad_ordered(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k,
-                             int32_t k_splits, void* workspace, size_t workspace_bytes) {
-  return debug_wgrad(stream, dy, x, dw, m, n, k, k_splits, workspace, workspace_bytes, true);
-}
-
-static int debug_wgrad(void* stream, const float* dy, const float* x, float* dw, int32_t m, int32_t n, int32_t k, int32_t k_splits,
-                       void* workspace, size_t workspace_bytes, bool ordered) {
-  if (!dy || !x || !dw || !workspace) return fail(VETO_ERR_INVALID, "null argument");
-  if (m <= 0 || n <= 0 || k <= 0 || k % 192 != 0) return fail(VETO_ERR_INVALID, "k must be a positive multiple of 192");
-  const WgradWs ws = carve_wgrad(Carver{(char*)workspace}, m, n, k, k_splits, ordered);
-  ABI_TRY(check_workspace(workspace, workspace_bytes, ws.total, false));
-  hipStream_t s = (hipStream_t)stream;
-  const int ks = wgrad_splits(n, k, m, k_splits);
-  const size_t mp = wgrad_mp(m, ks);
-  if (!ordered) HIP_TRY(hipMemsetAsync(dw, 0, (size_t)n * k * 4, s));
-  GemmArgs g{};
-  g.a = ws.a; g.w = ws.w; g.c = ordered ? ws.planes : dw;
-  g.M = n; g.N = k; g.K = (int)mp; g.ldc = k; g.k_splits = ks;
-  if (n % 32 == 0) {
-    HIP_TRY(hipMemsetAsync(ws.a, 0, ws.operand_bytes, s));   // the row behind the last one is read (never used) by partial tiles
-    HIP_TRY(launch_split_rows(dy, ws.a, (size_t)m, n, s));
-    HIP_TRY(launch_split_rows(x, ws.w, (size_t)m, k, s));
-    g.tn = 1; g.lda = 2 * (long)n; g.ldw = 2 * (long)k; g.k_valid = m;
-    g.zero = ws.zero;
-  } else {
-    HIP_TRY(hipMemsetAsync(ws.a, 0, (char*)ws.w - (char*)ws.a, s));   // rows n..padded stay zero
-    HIP_TRY(launch_transpose_split(dy, n, m, n, ws.a, (int)mp, s));
-    HIP_TRY(launch_transpose_split(x, k, m, k, ws.w, (int)mp, s));
-  }
-  hipError_t e = launch_gemm_split(g, ordered ? EPI_PLANES : EPI_ATOMIC, 0, s);
-  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "wgrad gemm launch failed: %s", hipGetErrorString(e));
-  if (ordered) HIP_TRY(launch_fold_rows(ws.planes, (long)n * k, ks, (long)n * k, dw, s));
-  return VETO_OK;
-}
-
-int veto_debug_attention_backward(void* stream, const float* qkv, const float* dout, float* dqkv, int32_t n_pair, int32_t heads) {
-  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  hipError_t e = launch_attention_backward(qkv, dout, dqkv, nullptr, n_pair, heads, 0, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (heads must give a head width of 72, 96 or 144)", hipGetErrorString(e));
-  return VETO_OK;
-}
-
-int veto_debug_attention_backward_forms(void* stream, const void* qkv, const float* dout, void* dqkv, float* qkv_unpacked, int32_t n_pair,
-                                        int32_t heads, uint32_t flags) {
-  if (!qkv || !dout || !dqkv || n_pair <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  if (flags & ~(uint32_t)(VETO_ATTN_BWD_CLS_ONLY | VETO_ATTN_BWD_QKV_F24 | VETO_ATTN_BWD_SPLIT_OUT)) return fail(VETO_ERR_INVALID, "unknown flag");
-  const bool f24 = (flags & VETO_ATTN_BWD_QKV_F24) != 0, split = (flags & VETO_ATTN_BWD_SPLIT_OUT) != 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (qkv_unpacked) {
-    if (!f24) return fail(VETO_ERR_INVALID, "qkv_unpacked goes with VETO_ATTN_BWD_QKV_F24");
-    HIP_TRY(launch_unpack_f24(qkv, qkv_unpacked, (size_t)n_pair * kTokens * 3 * kDim, s));
-  }
-  hipError_t e = launch_attention_backward((const float*)qkv, dout, split ? nullptr : (float*)dqkv, split ? (__bf16*)dqkv : nullptr, n_pair, heads,
-                                           (flags & VETO_ATTN_BWD_CLS_ONLY) ? 1 : 0, s, f24);
-  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention backward: %s (head width 72, 96 or 144; 3-byte q / k / v with 72 or 96 only)", hipGetErrorString(e));
-  return VETO_OK;
-}
-
-size_t veto_debug_layernorm_backward_workspace_bytes(int32_t rows) { return rows > 0 ? layernorm_backward_partial_floats(rows) * 4 : 0; }
-
-int veto_debug_layernorm_backward(void* stream, const float* x, const float* dy, const float* gamma, const float* dres,
-                                  float* dx, float* dgamma_dbeta, int32_t rows, void* workspace, size_t workspace_bytes) {
-  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
-  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int32_t veto_debug_layernorm_backward_col_partial_rows(int32_t rows) { return rows > 0 ? layernorm_backward_col_partials(rows) : 0; }
-
-int veto_debug_layernorm_backward_split(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
-                                        float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
-                                        uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
-  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !split_rows || !col_partials || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
-  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
-  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
-                                    col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale));
-  return VETO_OK;
-}
-
-int veto_debug_layernorm_backward_ordered(void* stream, const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
-                                          float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows, uint64_t drop_seed,
-                                          uint32_t drop_thresh, float drop_scale, void* workspace, size_t workspace_bytes) {
-  if (!x || !dy || !gamma || !dx || !dgamma_dbeta || !workspace || rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  if (!split_rows != !col_partials) return fail(VETO_ERR_INVALID, "split_rows and col_partials go together");
-  if (drop_thresh >= (1u << 24)) return fail(VETO_ERR_INVALID, "drop_thresh is p * 2^24 with p < 1");
-  if (workspace_bytes < veto_debug_layernorm_backward_workspace_bytes(rows)) return fail(VETO_ERR_WORKSPACE, "workspace too small");
-  HIP_TRY(launch_layernorm_backward(x, dy, gamma, dres, dx, dgamma_dbeta, (float*)workspace, rows, (hipStream_t)stream, (__bf16*)split_rows,
-                                    col_partials, (unsigned long long)drop_seed, drop_thresh, drop_scale, 1, true));
-  return VETO_OK;
-}
-
-int veto_debug_assemble_backward_ordered(void* stream, const float* dx, const int32_t* subj, const int32_t* obj, const float* lc,
-                                         const int32_t* img_obj_offset, const int32_t* img_pair_offset, int32_t n_img, int32_t n_obj,
-                                         float* dpatch, float* dlc) {
-  if (!dx || !subj || !obj || !lc || !img_obj_offset || !img_pair_offset || !dpatch || !dlc || n_img <= 0 || n_obj <= 0)
-    return fail(VETO_ERR_INVALID, "bad argument");
-  HIP_TRY(launch_assemble_backward_ordered(dx, subj, obj, lc, img_obj_offset, img_pair_offset, n_img, dpatch, dlc, n_obj, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int veto_debug_scatter_rows_ordered(void* stream, const float* demb, const int64_t* labels, int32_t n, int32_t dim, int32_t n_table_rows,
-                                    float* dtable) {
-  if (!demb || !labels || !dtable || n <= 0 || dim <= 0 || n_table_rows <= 0) return fail(VETO_ERR_INVALID, "bad argument");
-  HIP_TRY(launch_scatter_rows_ordered(demb, labels, dim, dtable, n, n_table_rows, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int veto_debug_gelu_backward(void* stream, const float* pre, const float* dh, float* dpre, size_t n) {
-  if (!pre || !dh || !dpre || n == 0 || n % 4 != 0) return fail(VETO_ERR_INVALID, "bad argument (n must be a positive multiple of 4)");
-  HIP_TRY(launch_gelu_backward(pre, dh, dpre, n, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int veto_debug_column_sums(void* stream, const float* dy, int64_t ld, int32_t rows, int32_t n_cols, float* out, void* workspace,
-                           size_t workspace_bytes) {
-  if (!dy || !out || !workspace || rows <= 0 || n_cols <= 0 || ld < n_cols) return fail(VETO_ERR_INVALID, "bad argument");
-  if (workspace_bytes < (size_t)column_sums_chunks() * n_cols * 4) return fail(VETO_ERR_WORKSPACE, "workspace too small (256 * n_cols floats)");
-  HIP_TRY(launch_column_sums(dy, ld, rows, n_cols, out, (float*)workspace, column_sums_chunks(), (hipStream_t)stream));
-  return VETO_OK;
-}
-
-// ---- veto_optim_step ------------------------------------------------------------------------------------------------------
-static_assert(VETO_OPTIM_CHUNK == kOptimChunk, "the header's chunk size is the kernels'");
-
-// Does the tensor take part in this call?
-static bool optim_active(const veto_optim_tensor_t& t) { return t.grad != nullptr && t.numel > 0; }
-
-// the host fields every mode checks; *n_chunks: the rows of the chunk table
-static int optim_check_shapes(const veto_optim_args_t* a, long long* n_chunks) {
-  if (a->tensor_size != (int32_t)sizeof(veto_optim_tensor_t)) return fail(VETO_ERR_INVALID, "veto_optim_tensor_t size mismatch");
-  if (a->n_tensors < 1 || a->n_tensors > kOptimMaxTensors) return fail(VETO_ERR_INVALID, "n_tensors %d outside 1..%d", a->n_tensors, kOptimMaxTensors);
-  if (a->mode < VETO_OPTIM_NORMS || a->mode > VETO_OPTIM_CLIP_STEP) return fail(VETO_ERR_INVALID, "unknown mode %d", a->mode);
-  if (!a->tensors) return fail(VETO_ERR_INVALID, "missing pointer: tensors");
-  long long chunks = 0;
-  for (int i = 0; i < a->n_tensors; ++i) {
-    const veto_optim_tensor_t& t = a->tensors[i];
-    if (t.numel < 0 || t.numel >= (1ll << 31)) return fail(VETO_ERR_INVALID, "tensor %d: numel %lld outside 0..2^31 - 1", i, (long long)t.numel);
-    if (optim_active(t)) chunks += (t.numel + kOptimChunk - 1) / kOptimChunk;
-  }
-  if (chunks > kOptimMaxChunks) return fail(VETO_ERR_INVALID, "%lld chunks of %d elements, the limit is %d", chunks, kOptimChunk, kOptimMaxChunks);
-  *n_chunks = chunks;
-  return VETO_OK;
-}
-
-// The tables as the device reads them: [counter, 256 bytes][OptimTensor x n_tensors][OptimChunk x n_chunks], each part at a multiple
-// of 256 bytes; this prefix of the workspace is what the call uploads.  Behind it: partial [n_chunks] and tensor_sq [n_tensors] doubles.
-// (offsets, not pointers: the pinned staging copy of the prefix has the same layout)
-struct OptimLayout { size_t tensors, chunks, upload, partial, tensor_sq, total; };
-static OptimLayout optim_layout(int n_tensors, long long n_chunks) {
-  OptimLayout l;
-  Carver c{nullptr};
-  c.take_offset(256);      // the counter
-  l.tensors = c.take_offset((size_t)n_tensors * sizeof(OptimTensor));
-  l.chunks = c.take_offset((size_t)n_chunks * sizeof(OptimChunk));
-  l.upload = l.chunks + (size_t)n_chunks * sizeof(OptimChunk);      // (the upload ends with the table's last row, not with its region)
-  l.partial = c.take_offset((size_t)n_chunks * 8);
-  l.tensor_sq = c.take_offset((size_t)n_tensors * 8);
-  l.total = c.off;
-  return l;
-}
-
-size_t veto_optim_step_workspace_bytes(const veto_optim_args_t* a) {
-  if (!a || a->struct_size != (int32_t)sizeof(veto_optim_args_t)) return 0;
-  long long n_chunks = 0;
-  if (optim_check_shapes(a, &n_chunks) != VETO_OK) return 0;
-  return optim_layout(a->n_tensors, n_chunks).total;
-}
-
-// Pinned staging for the tables, one buffer per call in flight.  A buffer is taken again only when the event recorded behind the
-// call that used it has completed, so rewriting it cannot reach a copy that has not run yet.
-struct OptimStage { void* host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; int device = -1; };
-static std::mutex g_optim_mutex;
-static std::vector<OptimStage> g_optim_stages;
-constexpr size_t kOptimMaxStages = 256;
-
-static int optim_stage_acquire(size_t need, int device, OptimStage** out) {
-  OptimStage* idle_small = nullptr;
-  for (OptimStage& st : g_optim_stages) {
-    if (st.device != device || hipEventQuery(st.done) != hipSuccess) continue;
-    if (st.bytes >= need) { *out = &st; return VETO_OK; }
-    idle_small = &st;
-  }
-  (void)hipGetLastError();   // hipErrorNotReady of a busy buffer is no error
-  OptimStage* st = idle_small;
-  if (!st && g_optim_stages.size() >= kOptimMaxStages) {   // 256 calls in flight on this device: wait for the oldest buffer
-    for (OptimStage& o : g_optim_stages)
-      if (o.device == device) { st = &o; break; }
-    if (!st) return fail(VETO_ERR_HIP, "no staging buffer left for device %d", device);
-    HIP_TRY(hipEventSynchronize(st->done));
-    if (st->bytes >= need) { *out = st; return VETO_OK; }
-  }
-  if (st) {   // idle and too small: the parameter set grew
-    HIP_TRY(hipHostFree(st->host));
-    st->host = nullptr; st->bytes = 0;
-  } else {
-    g_optim_stages.emplace_back();
-    st = &g_optim_stages.back();
-    st->device = device;
-    HIP_TRY(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
-  }
-  size_t bytes = 64 << 10;
-  while (bytes < need) bytes *= 2;
-  HIP_TRY(hipHostMalloc(&st->host, bytes, hipHostMallocDefault));
-  st->bytes = bytes;
-  *out = st;
-  return VETO_OK;
-}
-
-int veto_optim_step(void* stream, const veto_optim_args_t* a, void* workspace, size_t workspace_bytes) {
-  CHECK_STRUCT(veto_optim_args_t, a);
-  long long n_chunks = 0;
-  ABI_TRY(optim_check_shapes(a, &n_chunks));
-  const bool norms = a->mode != VETO_OPTIM_STEP, steps = a->mode == VETO_OPTIM_STEP || a->mode == VETO_OPTIM_CLIP_STEP;
-  const bool clips = a->mode == VETO_OPTIM_CLIP || a->mode == VETO_OPTIM_CLIP_STEP;
-  if (clips && !(a->max_norm > 0.0)) return fail(VETO_ERR_INVALID, "max_norm %g must be > 0 in a mode that clips", a->max_norm);
-  if (norms && (!a->norms || !a->total_norm || !a->coef)) return fail(VETO_ERR_INVALID, "missing pointer: norms, total_norm and coef are required");
-  if (norms && (((uintptr_t)a->norms | (uintptr_t)a->total_norm | (uintptr_t)a->coef) & 3) != 0) return fail(VETO_ERR_INVALID, "misaligned norms, total_norm or coef");
-  for (int i = 0; i < a->n_tensors; ++i) {
-    const veto_optim_tensor_t& t = a->tensors[i];
-    if (!optim_active(t)) continue;
-    if (((uintptr_t)t.grad & 3) != 0) return fail(VETO_ERR_INVALID, "tensor %d: misaligned grad", i);
-    if (!steps) continue;
-    if (t.step < 1) return fail(VETO_ERR_INVALID, "tensor %d: step %lld must be >= 1 (the count including this update)", i, (long long)t.step);
-    if (!t.param || !t.exp_avg || !t.exp_avg_sq) return fail(VETO_ERR_INVALID, "tensor %d: missing pointer: param, exp_avg and exp_avg_sq are required", i);
-    if ((((uintptr_t)t.param | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq) & 3) != 0) return fail(VETO_ERR_INVALID, "tensor %d: misaligned param, exp_avg or exp_avg_sq", i);
-    if (!(t.lr >= 0.0)) return fail(VETO_ERR_INVALID, "tensor %d: lr %g must be >= 0", i, t.lr);
-    if (!(t.eps >= 0.0)) return fail(VETO_ERR_INVALID, "tensor %d: eps %g must be >= 0", i, t.eps);
-    if (!(t.weight_decay >= 0.0)) return fail(VETO_ERR_INVALID, "tensor %d: weight_decay %g must be >= 0", i, t.weight_decay);
-    if (!(t.beta1 >= 0.0 && t.beta1 < 1.0)) return fail(VETO_ERR_INVALID, "tensor %d: beta1 %g outside [0, 1)", i, t.beta1);
-    if (!(t.beta2 >= 0.0 && t.beta2 < 1.0)) return fail(VETO_ERR_INVALID, "tensor %d: beta2 %g outside [0, 1)", i, t.beta2);
-  }
-  const OptimLayout lay = optim_layout(a->n_tensors, n_chunks);
-  ABI_TRY(check_workspace(workspace, workspace_bytes, lay.total, true));
-
-  int device = 0;
-  HIP_TRY(hipGetDevice(&device));
-  std::lock_guard<std::mutex> lock(g_optim_mutex);
-  OptimStage* st = nullptr;
-  ABI_TRY(optim_stage_acquire(lay.upload, device, &st));
-  char* host = (char*)st->host;
-  memset(host, 0, 256);   // the counter
-  OptimTensor* rows = (OptimTensor*)(host + lay.tensors);
-  OptimChunk* chunk_rows = (OptimChunk*)(host + lay.chunks);
-  int next = 0;
-  for (int i = 0; i < a->n_tensors; ++i) {
-    const veto_optim_tensor_t& t = a->tensors[i];
-    OptimTensor r{};
-    r.numel = (int)t.numel; r.chunk0 = next;
-    if (optim_active(t)) {
-      r.p = t.param; r.g = t.grad; r.m = t.exp_avg; r.v = t.exp_avg_sq;
-      r.n_chunks = (int)((t.numel + kOptimChunk - 1) / kOptimChunk);
-      for (int k = 0; k < r.n_chunks; ++k) chunk_rows[next++] = OptimChunk{i, k};
-      if (steps) {
-        const double bc1 = 1.0 - pow(t.beta1, (double)t.step), bc2 = 1.0 - pow(t.beta2, (double)t.step);
-        r.wd = (float)t.weight_decay; r.beta1 = (float)t.beta1; r.omb1 = (float)(1.0 - t.beta1);
-        r.beta2 = (float)t.beta2; r.omb2 = (float)(1.0 - t.beta2); r.eps = (float)t.eps;
-        r.step_size = (float)(t.lr / bc1); r.bc2_sqrt = (float)sqrt(bc2);
-      }
-    }
-    rows[i] = r;
-  }
-  char* ws = (char*)workspace;
-  OptimArgs p{};
-  p.tensors = (const OptimTensor*)(ws + lay.tensors); p.chunks = (const OptimChunk*)(ws + lay.chunks); p.counter = (unsigned*)ws;
-  p.partial = (double*)(ws + lay.partial); p.tensor_sq = (double*)(ws + lay.tensor_sq);
-  p.n_tensors = a->n_tensors; p.n_chunks = (int)n_chunks; p.max_norm = a->max_norm;
-  p.norms = a->norms; p.total = a->total_norm; p.coef = a->coef;
-  HIP_TRY(hipMemcpyAsync(ws, host, lay.upload, hipMemcpyHostToDevice, (hipStream_t)stream));
-  const hipError_t e = launch_optim(p, norms, a->mode == VETO_OPTIM_CLIP ? 1 : steps ? 2 : 0, clips, (hipStream_t)stream);
-  HIP_TRY(hipEventRecord(st->done, (hipStream_t)stream));   // behind the copy, whatever became of the launches
-  if (e != hipSuccess) return fail(VETO_ERR_HIP, "launch_optim failed: %s", hipGetErrorString(e));
   return VETO_OK;
 }
 

@@ -223,7 +223,7 @@ __device__ __forceinline__ bf16x8 lds_tr_pair(const char* p0, const char* p1) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// QF24: qkv holds 3-byte floats (common.h: rows of 1728 x 3 bytes) -- lossless here: every operand is split into bf16 hi + lo anyway
+// QF24: qkv holds 3-byte floats (common.h: rows of 1728 x 3 bytes) -- lossless for THIS kernel, which splits every operand into bf16 hi + lo (16 bits) anyway; the training forward's attention would have kept 22
 template <int DH, bool QF24 = false>
 __global__ __launch_bounds__(128) void attention_backward_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                       float* __restrict__ dqkv, __bf16* __restrict__ dqkv_split,
@@ -722,14 +722,14 @@ int layernorm_backward_col_partials(int rows) { return (rows + kLnRowsPerBlock -
 
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
                                      float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out, float* colp,
-                                     unsigned long long drop_seed, unsigned drop_thresh, float drop_scale, int drop_row_step, bool ordered) {
+                                     const DropSite& site, bool ordered) {
   const int blocks = (rows + kLnRowsPerBlock - 1) / kLnRowsPerBlock;
   if (!split_out != !colp) return hipErrorInvalidValue;
   if (ordered && split_out) VETO_LAUNCH((layernorm_backward_kernel<true, true>), dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
-                                        drop_seed, drop_thresh, drop_scale, drop_row_step);
+                                        site.seed, site.thresh, site.scale, site.row_step);
   else if (ordered) VETO_LAUNCH((layernorm_backward_kernel<false, true>), dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
   else if (split_out) VETO_LAUNCH(layernorm_backward_kernel<true>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, split_out, colp,
-                             drop_seed, drop_thresh, drop_scale, drop_row_step);
+                             site.seed, site.thresh, site.scale, site.row_step);
   else VETO_LAUNCH(layernorm_backward_kernel<false>, dim3(blocks), dim3(256), 0, s, x, dy, gamma, dres, dx, partial, rows, nullptr, nullptr, 0ull, 0u, 1.f, 1);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !dgamma_dbeta) return e;      // (nullptr: frozen gain and bias, the fold of their partial rows is left out)

@@ -190,9 +190,6 @@ hipError_t launch_qkv0_combine(const float* sw, const float* ow, const float* st
                                const int32_t* obj, float* qkv, int n_pair, hipStream_t s);
 hipError_t launch_qkv0_consts(const float* wq, const float* gamma, const float* beta, const float* pos, const float* cls, float* wp,
                               float* vec, hipStream_t s);
-// y = dropout mask of site `seed` applied to x ([rows, n_cols], index row*n_cols + col), scaled by `scale`; in place allowed
-hipError_t launch_dropout_apply(const float* x, float* y, size_t rows, int n_cols, unsigned long long seed, unsigned thresh,
-                                float scale, hipStream_t s);
 
 // LayerNorm(eps 1e-5) of `rows` rows (row r at x + r*ldx) -> split rows [rows, 2*576]
 // dst row r at dst + r*ldd (bf16 elements; 0 = contiguous rows of 2*576)
@@ -732,6 +729,26 @@ struct MeetSampleArgs {
 };
 hipError_t launch_meet_sample(const MeetSampleArgs& a, hipStream_t s);
 
+// ---- dropout sites of the training path, and the elementwise backward in front of a Linear's gradient GEMMs ---------------------
+struct DropSite {   // one dropout site: threshold p * 2^24 (0 = off), scale 1 / (1 - p).  Host side only: what goes into a kernel by value
+                    // (GemmArgs, ObjPrepArgs, AssembleArgs, GradXform) keeps fields of its own, filled from the site
+  unsigned long long seed = 0;
+  unsigned thresh = 0;
+  float scale = 1.f;
+  int row_step = 1;   // row r of the matrix the site is applied to is token row r * row_step (the last layer's compact CLS rows: 19)
+};
+enum GradXformMode { XF_NONE = 0, XF_GELU = 1, XF_DROP = 2 };
+struct GradXform {
+  int mode = XF_NONE;
+  const float* pre = nullptr;           // XF_GELU: pre-activation [M, ld]
+  unsigned long long seed = 0;          // XF_DROP: element (m, n) -> index (m * row_step) * N + n
+  unsigned thresh = 0;
+  float scale = 1.f;
+  int row_step = 1;
+};
+// y = the mask of `site` applied to x ([rows, n_cols], index row*n_cols + col; row_step 1), scaled by site.scale; in place allowed
+hipError_t launch_dropout_apply(const float* x, float* y, size_t rows, int n_cols, const DropSite& site, hipStream_t s);
+
 // ---- backward building blocks (backward.hip) -----------------------------------------------------------------
 // qkv, dqkv: [n_pair*19, 1728]; dout: [n_pair*19, 576] (gradient of the attention output before the out projection)
 // exactly one of dqkv (fp32 [n_pair*19, 1728]) and dqkv_split (split rows [n_pair*19, 2*1728]) is written
@@ -742,14 +759,13 @@ hipError_t launch_attention_backward(const float* qkv, const float* dout, float*
 // dx = LayerNorm backward of dy w.r.t. x (+ dres if given); dgamma_dbeta [2, 576]; partial: workspace of
 // layernorm_backward_partial_floats(rows) floats (dgamma_dbeta == nullptr: not wanted, the fold of the partial rows is left out)
 size_t layernorm_backward_partial_floats(int rows);
-// split_out / colp (both or neither): also write the result's split rows [rows, 2 * 576] (with the dropout mask of site drop_seed applied
-// when drop_thresh != 0: element (row, col) -> index (row * drop_row_step) * 576 + col) and layernorm_backward_col_partials(rows) rows of column sums [*, 576]
+// split_out / colp (both or neither): also write the result's split rows [rows, 2 * 576] (with the dropout mask of `site` applied
+// when site.thresh != 0: element (row, col) -> index (row * site.row_step) * 576 + col) and layernorm_backward_col_partials(rows) rows of column sums [*, 576]
 // of those rows -- what launch_prep_grad would produce from dx, for the Linear behind this LayerNorm in the backward chain
 int layernorm_backward_col_partials(int rows);
 hipError_t launch_layernorm_backward(const float* x, const float* dy, const float* gamma, const float* dres, float* dx,
-                                     float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out = nullptr,
-                                     float* colp = nullptr, unsigned long long drop_seed = 0, unsigned drop_thresh = 0, float drop_scale = 1.f,
-                                     int drop_row_step = 1, bool ordered = false);
+                                     float* dgamma_dbeta, float* partial, int rows, hipStream_t s, __bf16* split_out, float* colp,
+                                     const DropSite& site, bool ordered);
 // out[c] = (float) of the double sum over rows r = 0 .. n_rows - 1 of src[r * ld + c], rows in a fixed order (fold_rows_kernel): the fold of
 // the split-K partial planes of the ordered weight gradient
 hipError_t launch_fold_rows(const float* src, long ld, int n_rows, long n_cols, float* out, hipStream_t s);
@@ -762,15 +778,6 @@ hipError_t launch_gelu_backward(const float* pre, const float* dh, float* dpre, 
 // dY fp32 [M, N] -> split rows [M, 2N] (the operand of BOTH gradient GEMMs) and (optional) per-32-row column sums
 // col_partial [Mp/32, N] (Mp = M rounded up to 32, >= M) in one pass.  GradXform: the elementwise backward that precedes this Linear, applied on load
 // (dY itself is not rewritten): gelu'(pre) or the forward's dropout mask.
-enum GradXformMode { XF_NONE = 0, XF_GELU = 1, XF_DROP = 2 };
-struct GradXform {
-  int mode = XF_NONE;
-  const float* pre = nullptr;           // XF_GELU: pre-activation [M, ld]
-  unsigned long long seed = 0;          // XF_DROP: element (m, n) -> index (m * row_step) * N + n
-  unsigned thresh = 0;
-  float scale = 1.f;
-  int row_step = 1;
-};
 hipError_t launch_prep_grad(const float* src, long ld, int M, int N, __bf16* rows_out, int Mp, float* col_partial,
                             const GradXform& xf, hipStream_t s);
 hipError_t launch_gelu_split(const float* pre, __bf16* dst, size_t rows, int n_cols, hipStream_t s);

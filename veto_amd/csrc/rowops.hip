@@ -760,11 +760,10 @@ hipError_t launch_transpose_head(const float* src, float* dst, int n_out, hipStr
   return hipGetLastError();
 }
 
-hipError_t launch_dropout_apply(const float* x, float* y, size_t rows, int n_cols, unsigned long long seed, unsigned thresh,
-                                float scale, hipStream_t s) {
+hipError_t launch_dropout_apply(const float* x, float* y, size_t rows, int n_cols, const DropSite& site, hipStream_t s) {
   const size_t n = rows * (size_t)n_cols;
   const int blocks = (int)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
-  VETO_LAUNCH(dropout_apply_kernel, dim3(blocks), dim3(256), 0, s, x, y, n, seed, thresh, scale);
+  VETO_LAUNCH(dropout_apply_kernel, dim3(blocks), dim3(256), 0, s, x, y, n, site.seed, site.thresh, site.scale);
   return hipGetLastError();
 }
 
