@@ -1135,15 +1135,60 @@ int veto_ce_loss(void* stream, const float* logits, int64_t ld, const int64_t* l
                  const int64_t* rows, int32_t n, int32_t n_cls, float* loss, float* grad, void* workspace,
                  size_t workspace_bytes);
 
-/* veto_meet_sample: the expert sampling loop of VETOPredictor_MEET.forward in training (:3940-3969,
- * ZERO_LABEL_PADDING_MODE 'rand_insert') followed by the per-group label remap of Ensemble.forward (:3812-3821).
- * `words` are the next raw 32-bit outputs of Python's `random` generator (MT19937), consumed exactly as
- * random.randint / random.random would; *words_used tells the host how far to advance its generator (-1: block too
- * short).  sample_rates is the [n_groups, n_cls] matrix of extra_function_utils.py:185-257 in double precision. */
+/* MEET expert sampling: the loop of VETOPredictor_MEET.forward in training (:3940-3969) followed by the per-group label
+ * remap of Ensemble.forward (:3812-3821).  `words` are the next raw 32-bit outputs of Python's `random` generator
+ * (MT19937), consumed exactly as random.randint / random.random would, relation by relation in index order;
+ * *words_used tells the host how far to advance its generator (-1: the block was too short; the other outputs of such a
+ * call are unspecified).  sample_rates is the [n_groups, n_cls] matrix of extra_function_utils.py:185-257 in double
+ * precision.  random() takes two words, u = ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53; randint(0, G-1) takes one word per
+ * attempt, r = w >> (32 - G.bit_length()), again while r >= G.
+ *
+ * A foreground relation (label != 0) draws u = random() in every mode and joins groups 0..act-1 for the first act = G..1
+ * with u <= sample_rates[act-1][label] or act < incre_idx_list[label] (no group if there is none).  A background relation
+ * follows GCL_SETTING.ZERO_LABEL_PADDING_MODE:
+ *   'rand_insert'   one word per attempt of randint(0, G-1); it joins the one drawn group
+ *   'rand_choose'   two words, u = random(); u >= 0.4 (the double 0.4, inclusive): every group, otherwise none
+ *   'all_include'   no word; every group
+ * In each group the rows stand in ascending relation index, each at most once.
+ *
+ * veto_meet_sample is 'rand_insert' on one device thread.  veto_meet_sample_parallel computes the same bits for all three
+ * modes: a relation's first word is a prefix sum of what the relations in front of it consume (fixed by the labels in
+ * 'rand_choose' and 'all_include'; in 'rand_insert' a chain over the words, walked by one wave on bit masks held in
+ * registers), every relation then decides by itself, and the lists are a stable compaction (no atomics: repeatable bit for
+ * bit).  Limits of both: n >= 1, 1 <= n_groups <= 64, n_cls >= 2; the parallel call also takes n_words = 0 (words may then be
+ * NULL) and needs a 256-byte aligned workspace. */
 int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint32_t* words, int32_t n_words,
                      const int32_t* incre_idx_list, const int32_t* pos_in_group, const int32_t* group_size,
                      const double* sample_rates, int32_t n_groups, int32_t n_cls, int64_t* chosen,
                      int64_t* group_labels, int32_t* counts, int32_t* words_used);
+
+enum veto_meet_pad_mode { VETO_MEET_RAND_INSERT = 0, VETO_MEET_RAND_CHOOSE = 1, VETO_MEET_ALL_INCLUDE = 2 };
+
+typedef struct veto_meet_sample_args {
+  int32_t struct_size;
+  int32_t mode;                    /* enum veto_meet_pad_mode */
+  int32_t n;                       /* relations */
+  int32_t n_words;
+  int32_t n_groups;
+  int32_t n_cls;
+  const int64_t* labels;           /* device [n] */
+  const uint32_t* words;           /* device [n_words] */
+  const int32_t* incre_idx_list;   /* device [n_cls]: 1-based group of each class */
+  const int32_t* pos_in_group;     /* device [n_cls]: 1-based position of the class inside its group */
+  const int32_t* group_size;       /* device [n_groups] */
+  const double* sample_rates;      /* device [n_groups, n_cls] */
+  int64_t* chosen;                 /* out device [n_groups, n]: row k holds counts[k] relation indices; the rest is not written */
+  int64_t* group_labels;           /* out device [n_groups, n]: the group-local labels of those rows */
+  int32_t* counts;                 /* out device [n_groups] */
+  int32_t* words_used;             /* out device [1] */
+} veto_meet_sample_args_t;
+
+size_t veto_meet_sample_parallel_workspace_bytes(int32_t n, int32_t n_words);
+int veto_meet_sample_parallel(void* stream, const veto_meet_sample_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* The sizes the parallel sampler is built with (any pointer may be NULL): relations per workgroup of the decision and the
+ * compaction (tile), words per register window of the 'rand_insert' walk (window), relations per mask word (chunk). */
+int veto_meet_sample_parallel_limits(int32_t* tile, int32_t* window, int32_t* chunk);
 
 /* ---- training path: forward that keeps the activations + backward --------------
  * The backward of VETOPredictor.forward's computation graph (roi_relation_predictors.py:4074-4133, model_veto.py)

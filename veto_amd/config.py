@@ -62,7 +62,7 @@ def default_config():
     c.GLOBAL_SETTING.BETA_LOSS = False
     c.GCL_SETTING = CfgNode()
     c.GCL_SETTING.GROUP_SPLIT_MODE = "divide4"
-    c.GCL_SETTING.ZERO_LABEL_PADDING_MODE = "rand_insert"
+    c.GCL_SETTING.ZERO_LABEL_PADDING_MODE = "rand_insert"      # or "rand_choose" / "all_include" (VETO_final.yaml): all three are built
     c.ENSEMBLE_LEARNING = CfgNode()
     c.ENSEMBLE_LEARNING.ENABLED = False
     c.ENSEMBLE_LEARNING.TYPE = ["group"]

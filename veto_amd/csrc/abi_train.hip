@@ -863,4 +863,50 @@ int veto_meet_sample(void* stream, const int64_t* labels, int32_t n, const uint3
   return VETO_OK;
 }
 
+int veto_meet_sample_parallel_limits(int32_t* tile, int32_t* window, int32_t* chunk) {
+  if (tile) *tile = meet_parallel_tile();
+  if (window) *window = meet_parallel_window();
+  if (chunk) *chunk = meet_parallel_chunk();
+  return VETO_OK;
+}
+
+static_assert((int)MEET_RAND_INSERT == VETO_MEET_RAND_INSERT && (int)MEET_RAND_CHOOSE == VETO_MEET_RAND_CHOOSE &&
+              (int)MEET_ALL_INCLUDE == VETO_MEET_ALL_INCLUDE, "veto_meet_pad_mode is passed to the kernels as it is");
+
+// workspace: fg_mask | acc_mask | pos | span | tile_count
+static size_t carve_meet_parallel(Carver c, size_t n, size_t n_words, MeetParallelArgs* p) {
+  p->fg_mask = c.take<unsigned long long>((n + 63) / 64 * 8);
+  p->acc_mask = c.take<unsigned long long>((n_words + 63) / 64 * 8);
+  p->pos = c.take<int32_t>(n * 4);
+  p->span = c.take<uint16_t>(n * 2);
+  p->tile_count = c.take<int32_t>((size_t)meet_parallel_tiles((long long)n) * 64 * 4);
+  return c.off;
+}
+
+size_t veto_meet_sample_parallel_workspace_bytes(int32_t n, int32_t n_words) {
+  if (n <= 0 || n_words < 0) return 0;
+  MeetParallelArgs p{};
+  return carve_meet_parallel(Carver{nullptr}, (size_t)n, (size_t)n_words, &p);
+}
+
+int veto_meet_sample_parallel(void* stream, const veto_meet_sample_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT(veto_meet_sample_args_t, a);
+  if (a->mode != VETO_MEET_RAND_INSERT && a->mode != VETO_MEET_RAND_CHOOSE && a->mode != VETO_MEET_ALL_INCLUDE)
+    return fail(VETO_ERR_INVALID, "mode %d is none of rand_insert (0), rand_choose (1), all_include (2)", a->mode);
+  if (a->n <= 0 || a->n_words < 0 || a->n_groups < 1 || a->n_groups > 64 || a->n_cls < 2)
+    return fail(VETO_ERR_INVALID, "bad sizes (n %d, n_words %d, n_groups %d, n_cls %d)", a->n, a->n_words, a->n_groups, a->n_cls);
+  if (!a->labels || (a->n_words > 0 && !a->words) || !a->incre_idx_list || !a->pos_in_group || !a->group_size || !a->sample_rates ||
+      !a->chosen || !a->group_labels || !a->counts || !a->words_used)
+    return fail(VETO_ERR_INVALID, "missing pointer");
+  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_meet_sample_parallel_workspace_bytes(a->n, a->n_words), true));
+  MeetParallelArgs p{};
+  p.s.labels = a->labels; p.s.n = a->n; p.s.n_groups = a->n_groups; p.s.n_cls = a->n_cls; p.s.n_words = a->n_words; p.s.words = a->words;
+  p.s.incre = a->incre_idx_list; p.s.pos_in_group = a->pos_in_group; p.s.group_size = a->group_size; p.s.rates = a->sample_rates;
+  p.s.chosen = a->chosen; p.s.group_labels = a->group_labels; p.s.counts = a->counts; p.s.words_used = a->words_used;
+  p.mode = a->mode;
+  carve_meet_parallel(Carver{(char*)workspace}, (size_t)a->n, (size_t)a->n_words, &p);
+  HIP_TRY(launch_meet_sample_parallel(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 }  // extern "C"

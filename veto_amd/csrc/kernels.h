@@ -729,6 +729,24 @@ struct MeetSampleArgs {
 };
 hipError_t launch_meet_sample(const MeetSampleArgs& a, hipStream_t s);
 
+// The same sampling for all three ZERO_LABEL_PADDING_MODEs, with only the rand_insert word chain left serial (losses.hip).
+enum MeetPadMode { MEET_RAND_INSERT = 0, MEET_RAND_CHOOSE = 1, MEET_ALL_INCLUDE = 2 };
+struct MeetParallelArgs {
+  MeetSampleArgs s;              // labels, words, tables and outputs: the serial sampler's
+  int mode;                      // MeetPadMode
+  unsigned long long* fg_mask;   // workspace [ceil(n / 64)]: bit i % 64 of word i / 64 = relation i is foreground
+  unsigned long long* acc_mask;  // workspace [ceil(n_words / 64)], rand_insert: the same for "randint accepts word j"
+  int32_t* pos;                  // workspace [n]: rand_insert: the word a relation decides on (foreground: its first; background: the
+                                 // accepted one); all_include: entry b = foreground relations in front of relation 64 b
+  uint16_t* span;                // workspace [n]: lo | hi << 8, the relation goes to groups lo .. hi-1
+  int32_t* tile_count;           // workspace [tiles, 64]: rows of a tile per group, then (in place) rows in front of the tile
+};
+hipError_t launch_meet_sample_parallel(const MeetParallelArgs& a, hipStream_t s);
+int meet_parallel_tile();        // relations per workgroup of the decision and of the compaction
+int meet_parallel_window();      // words per register window of the rand_insert walk (64 mask words)
+int meet_parallel_chunk();       // relations per mask word: the walk flushes its positions once per chunk
+inline long long meet_parallel_tiles(long long n) { return (n + meet_parallel_tile() - 1) / meet_parallel_tile(); }
+
 // ---- dropout sites of the training path, and the elementwise backward in front of a Linear's gradient GEMMs ---------------------
 struct DropSite {   // one dropout site: threshold p * 2^24 (0 = off), scale 1 / (1 - p).  Host side only: what goes into a kernel by value
                     // (GemmArgs, ObjPrepArgs, AssembleArgs, GradXform) keeps fields of its own, filled from the site

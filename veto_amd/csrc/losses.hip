@@ -129,7 +129,245 @@ __global__ __launch_bounds__(256) void meet_labels_kernel(MeetSampleArgs a) {
   a.group_labels[(size_t)k * a.n + i] = out;
 }
 
+// ---- the same sampling, parallel but for the rand_insert word chain ------------------------------------------------
+// What a relation does depends on the word it starts at, and that is a prefix sum of what the relations before it consumed:
+//   rand_choose   every relation consumes two words: relation i starts at 2 i;
+//   all_include   a foreground relation consumes two, a background none: 2 x (foreground relations in front of i);
+//   rand_insert   a background consumes words up to its first accepted one, so the start of relation i+1 depends on the WORDS:
+//                 pos' = fg ? pos + 2 : next_accepted(pos) + 1.  That chain stays serial, but it runs on two bit masks (one bit per
+//                 relation: foreground; one bit per word: randint accepts it) that a parallel pass makes first; one wave walks it
+//                 with every lane holding the same state, the masks in registers (lane l of a window register holds mask word
+//                 64 w + l, fetched with a lane read), so that no load sits on the dependent chain.
+// Then every relation decides in parallel from its own word(s) which groups lo..hi-1 it joins, and a stable compaction (ballot
+// ranks inside a wave, wave counts inside a tile, tile counts in front of a tile; no atomics) writes the per-group lists in
+// ascending relation order.  meet_labels_kernel, unchanged, comes last.
+constexpr int kMeetTile = 1024, kMeetChunk = 64, kMeetWindow = 64 * kMeetChunk;
+using u64 = unsigned long long;
+
+__device__ __forceinline__ int meet_kbits(int G) {
+  int kbits = 0;
+  while ((G >> kbits) != 0) ++kbits;
+  return kbits;
+}
+
+__device__ __forceinline__ double meet_uniform(unsigned a, unsigned b) {      // random.random() on the two raw words a, b
+  return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+__global__ __launch_bounds__(256) void meet_mask_kernel(MeetParallelArgs a) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;      // lane 0 of a wave: the first bit of one mask word
+  const int lane = threadIdx.x & 63;
+  const u64 fg = __ballot(idx < a.s.n && a.s.labels[idx] != 0);
+  if (lane == 0 && idx < a.s.n) a.fg_mask[idx >> 6] = fg;
+  if (a.mode != MEET_RAND_INSERT) return;
+  const int shift = 32 - meet_kbits(a.s.n_groups);
+  const u64 acc = __ballot(idx < a.s.n_words && (a.s.words[idx] >> shift) < (unsigned)a.s.n_groups);
+  if (lane == 0 && idx < a.s.n_words) a.acc_mask[idx >> 6] = acc;      // (the bits behind n_words are 0: never accepted)
+}
+
+__device__ __forceinline__ u64 meet_mask_word(const u64* m, long n_mask, long idx) { return idx < n_mask ? m[idx] : 0ull; }
+
+__device__ __forceinline__ u64 meet_lane_read(u64 v, int src) {      // v of lane src (the same src in every lane)
+  src = __builtin_amdgcn_readfirstlane(src);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+  return ((u64)hi << 32) | lo;
+}
+
+// one wave.  words_used, and what the decision needs to find each relation's words (MeetParallelArgs::pos)
+__global__ __launch_bounds__(64) void meet_position_kernel(MeetParallelArgs a) {
+  const int lane = threadIdx.x;
+  const int n = a.s.n;
+  const unsigned n_words = (unsigned)a.s.n_words;
+  const long nF = ((long)n + 63) >> 6;
+  if (a.mode == MEET_RAND_CHOOSE) {
+    if (lane == 0) a.s.words_used[0] = 2ll * n <= (long long)n_words ? 2 * n : -1;
+    return;
+  }
+  if (a.mode == MEET_ALL_INCLUDE) {      // exclusive prefix count of the foreground bits, 64 mask words per step
+    long long carry = 0;
+    for (long base = 0; base < nF; base += 64) {
+      const int c = __popcll(meet_mask_word(a.fg_mask, nF, base + lane));
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+      }
+      if (base + lane < nF) a.pos[base + lane] = (int)(carry + incl - c);      // (< n)
+      carry += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) a.s.words_used[0] = 2 * carry <= (long long)n_words ? (int)(2 * carry) : -1;
+    return;
+  }
+  // rand_insert: the chain.  Every lane holds the same pos / cur / nxt; r0, r1, r2 are the mask words of windows c, c+1, c+2 (the
+  // third was asked for a whole window ago: nobody waits for it)
+  const long nA = ((long)n_words + 63) >> 6;
+  int c = 0;
+  u64 r0 = meet_mask_word(a.acc_mask, nA, lane), r1 = meet_mask_word(a.acc_mask, nA, 64 + lane), r2 = meet_mask_word(a.acc_mask, nA, 128 + lane);
+  int curidx = 0;                                   // cur = mask word curidx, nxt = mask word curidx + 1
+  u64 cur = meet_lane_read(r0, 0), nxt = meet_lane_read(r0, 1);
+  unsigned pos = 0;
+  bool overflow = false;
+  u64 fg_next = meet_mask_word(a.fg_mask, nF, 0);
+  for (long fw = 0; fw < nF && !overflow; ++fw) {
+    const u64 fg = fg_next;
+    fg_next = meet_mask_word(a.fg_mask, nF, fw + 1);      // (asked for 64 relations before it is looked at)
+    const int cnt = (int)(n - fw * 64 < 64 ? n - fw * 64 : 64);
+    int mine = 0;
+    int b = 0;
+    while (b < cnt) {      // run by run: a lone wave pays per instruction, so a foreground run is one addition, a background one ctz
+      const u64 rest = fg >> b;
+      if (rest & 1ull) {
+        const u64 stop = ~rest;
+        int run = stop != 0 ? __builtin_ctzll(stop) : 64;
+        run = run < cnt - b ? run : cnt - b;
+        if ((u64)pos + 2ull * run > n_words) { overflow = true; break; }
+        if (lane >= b && lane < b + run) mine = (int)pos + 2 * (lane - b);
+        pos += 2u * run;
+        b += run;
+        continue;
+      }
+      const int run = rest != 0 ? __builtin_ctzll(rest) : 64;
+      const int end = b + run < cnt ? b + run : cnt;
+      while (b < end) {
+        if (pos >= n_words) { overflow = true; break; }
+        const int w = (int)(pos >> 6);
+        while (curidx < w) {
+          ++curidx;
+          cur = nxt;
+          const int want = curidx + 1;
+          if ((want >> 6) > c + 1) {      // (want grows by one per step: one shift is enough)
+            r0 = r1; r1 = r2; ++c;
+            r2 = meet_mask_word(a.acc_mask, nA, (long)(c + 2) * 64 + lane);
+          }
+          nxt = meet_lane_read((want >> 6) == c ? r0 : r1, want & 63);
+        }
+        u64 m = cur >> (pos & 63u);      // the accepted words from pos to the end of mask word w: one per background relation
+        while (m != 0 && b < end) {
+          const int t = __builtin_ctzll(m);
+          const unsigned rec = pos + (unsigned)t;      // (< n_words: the mask has no bit behind the block)
+          if (lane == b) mine = (int)rec;
+          ++b;
+          pos = rec + 1u;
+          m = (m >> t) >> 1;
+        }
+        if (b < end) pos = ((unsigned)w + 1u) << 6;      // nothing accepted in the rest of this mask word
+      }
+      if (overflow) break;
+    }
+    if (lane < cnt) a.pos[fw * 64 + lane] = mine;      // (after an overflow: unspecified, and the decision checks every position)
+  }
+  if (lane == 0) a.s.words_used[0] = overflow ? -1 : (int)pos;
+}
+
+__device__ __forceinline__ bool meet_member(int lo, int hi, int k) { return lo <= k && k < hi; }
+
+// per-wave rows of each group (lane k: group k) into s_cnt[wave][k]
+__device__ __forceinline__ void meet_wave_counts(int lo, int hi, int G, int (*s_cnt)[64]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int mine = 0;
+  for (int k = 0; k < G; ++k) {
+    const int c = __popcll(__ballot(meet_member(lo, hi, k)));
+    if (lane == k) mine = c;
+  }
+  s_cnt[wave][lane] = mine;
+}
+
+__global__ __launch_bounds__(kMeetTile) void meet_decide_kernel(MeetParallelArgs a) {
+  __shared__ int s_cnt[kMeetTile / 64][64];
+  const int G = a.s.n_groups, n = a.s.n;
+  const long long n_words = a.s.n_words;
+  const long i = (long)blockIdx.x * kMeetTile + threadIdx.x;
+  int lo = 0, hi = 0;
+  if (i < n) {
+    const long lab = a.s.labels[i];
+    long long p;      // the relation's first word (rand_insert background: its accepted word)
+    if (a.mode == MEET_RAND_INSERT) p = a.pos[i];
+    else if (a.mode == MEET_RAND_CHOOSE) p = 2ll * i;
+    else p = 2ll * (a.pos[i >> 6] + __popcll(a.fg_mask[i >> 6] & ((1ull << (i & 63)) - 1ull)));
+    if (lab != 0) {
+      if (lab > 0 && lab < a.s.n_cls && p >= 0 && p + 2 <= n_words) {      // (an overflowing call: no row, nothing read out of bounds)
+        const double u = meet_uniform(a.s.words[p], a.s.words[p + 1]);
+        const int g = a.s.incre[lab];
+        for (int act = G; act >= 1; --act)
+          if (u <= a.s.rates[(size_t)(act - 1) * a.s.n_cls + lab] || act < g) { hi = act; break; }
+      }
+    } else if (a.mode == MEET_RAND_INSERT) {
+      if (p >= 0 && p < n_words) {
+        const unsigned r = a.s.words[p] >> (32 - meet_kbits(G));
+        if (r < (unsigned)G) { lo = (int)r; hi = lo + 1; }
+      }
+    } else if (a.mode == MEET_RAND_CHOOSE) {
+      if (p + 2 <= n_words && meet_uniform(a.s.words[p], a.s.words[p + 1]) >= 0.4) hi = G;
+    } else {
+      hi = G;
+    }
+    a.span[i] = (uint16_t)(lo | (hi << 8));
+  }
+  meet_wave_counts(lo, hi, G, s_cnt);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    int sum = 0;
+    for (int w = 0; w < kMeetTile / 64; ++w) sum += s_cnt[w][threadIdx.x];
+    a.tile_count[(size_t)blockIdx.x * 64 + threadIdx.x] = sum;
+  }
+}
+
+// one wave, lane k = group k: tile counts -> rows in front of each tile, and the list lengths
+__global__ __launch_bounds__(64) void meet_offsets_kernel(MeetParallelArgs a, long tiles) {
+  const int k = threadIdx.x;
+  int run = 0;
+  for (long t = 0; t < tiles; ++t) {
+    const int c = a.tile_count[t * 64 + k];
+    a.tile_count[t * 64 + k] = run;
+    run += c;
+  }
+  if (k < a.s.n_groups) a.s.counts[k] = run;
+}
+
+__global__ __launch_bounds__(kMeetTile) void meet_scatter_kernel(MeetParallelArgs a) {
+  __shared__ int s_cnt[kMeetTile / 64][64];
+  const int G = a.s.n_groups, n = a.s.n;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long i = (long)blockIdx.x * kMeetTile + threadIdx.x;
+  const int sp = i < n ? a.span[i] : 0;
+  const int lo = sp & 255, hi = sp >> 8;
+  meet_wave_counts(lo, hi, G, s_cnt);
+  __syncthreads();
+  int base = a.tile_count[(size_t)blockIdx.x * 64 + lane];      // lane k: where this wave's rows of group k start
+  for (int w = 0; w < wave; ++w) base += s_cnt[w][lane];
+  for (int k = 0; k < G; ++k) {
+    const bool in = meet_member(lo, hi, k);
+    const u64 m = __ballot(in);
+    const int at = __shfl(base, k, 64);
+    if (in) a.s.chosen[(size_t)k * n + at + __popcll(m & ((1ull << lane) - 1ull))] = i;
+  }
+}
+
 }  // namespace
+
+int meet_parallel_tile() { return kMeetTile; }
+int meet_parallel_window() { return kMeetWindow; }
+int meet_parallel_chunk() { return kMeetChunk; }
+
+hipError_t launch_meet_sample_parallel(const MeetParallelArgs& a, hipStream_t s) {
+  const long span = a.mode == MEET_RAND_INSERT && a.s.n_words > a.s.n ? a.s.n_words : a.s.n;
+  const long tiles = meet_parallel_tiles(a.s.n);
+  hipError_t e;
+  VETO_LAUNCH(meet_mask_kernel, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(meet_position_kernel, dim3(1), dim3(64), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(meet_decide_kernel, dim3((unsigned)tiles), dim3(kMeetTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(meet_offsets_kernel, dim3(1), dim3(64), 0, s, a, tiles);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(meet_scatter_kernel, dim3((unsigned)tiles), dim3(kMeetTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  VETO_LAUNCH(meet_labels_kernel, dim3((a.s.n + 255) / 256, a.s.n_groups), dim3(256), 0, s, a.s);
+  return hipGetLastError();
+}
 
 hipError_t launch_ce_loss(const CeLossArgs& a, hipStream_t s) {
   VETO_LAUNCH(ce_rows_kernel, dim3((a.n + 3) / 4), dim3(256), 0, s, a);

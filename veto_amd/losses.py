@@ -8,7 +8,9 @@ and backward of the transformer itself are not built, so the predictors still re
                         with one .item() per relation; here the host hands the device the next raw words of the SAME
                         generator, the device consumes them exactly as randint / random would, and the host generator
                         is advanced by what was used, so a run stays in lock-step with the reference's stream.
+                        All three GCL_SETTING.ZERO_LABEL_PADDING_MODEs, through veto_meet_sample_parallel.
 """
+import ctypes
 import random
 
 import numpy as np
@@ -78,8 +80,10 @@ def _numpy_generator_from_python_random():
 
 class MeetTrainingSampler:
     def __init__(self, dataset, group_sizes, device="cuda", zero_label_padding_mode="rand_insert"):
-        if zero_label_padding_mode != "rand_insert":
-            raise NotImplementedError("only GCL_SETTING.ZERO_LABEL_PADDING_MODE = 'rand_insert' (VETO_final.yaml) is built")
+        if zero_label_padding_mode not in native.MEET_PAD_MODES:
+            raise NotImplementedError("GCL_SETTING.ZERO_LABEL_PADDING_MODE must be one of %s (got %r)"
+                                      % (", ".join(repr(m) for m in native.MEET_PAD_MODES), zero_label_padding_mode))
+        self.mode = zero_label_padding_mode
         self.device = torch.device(device)
         self.sizes = [int(x) for x in group_sizes]
         incre = meet_tables.incre_idx_list(self.sizes)
@@ -103,19 +107,27 @@ class MeetTrainingSampler:
         call = native.Launch(dev, "veto_amd losses run only on a HIP device")
         labels = rel_labels.to(device=dev, dtype=torch.int64).contiguous()
         n = int(labels.shape[0])
-        n_words = 4 * n + 64      # 2 words per foreground relation; background: 1 + rejections (p < 1/2 each)
+        # rand_insert: 2 words per foreground relation; background: 1 + rejections (p < 1/2 each).  The other two modes: at most 2 per
+        # relation, whatever the words are
+        retry = self.mode == "rand_insert"
+        n_words = 4 * n + 64 if retry else 2 * n
         while True:
             bg, st = _numpy_generator_from_python_random()
             words = torch.from_numpy(bg.random_raw(n_words).astype(np.uint32).view(np.int32)).to(dev)
             chosen = torch.empty((G, n), dtype=torch.int64, device=dev)
             glabels = torch.empty((G, n), dtype=torch.int64, device=dev)
             meta = torch.empty(G + 1, dtype=torch.int32, device=dev)
-            call.run("veto_meet_sample", call.ptr(labels), n, call.ptr(words), n_words, self.incre.data_ptr(),
-                     self.pos_in_group.data_ptr(), self.group_size.data_ptr(), self.rates.data_ptr(), G, self.n_cls,
-                     chosen.data_ptr(), glabels.data_ptr(), meta.data_ptr(), meta[G:].data_ptr())
+            ws = call.workspace(call.lib.veto_meet_sample_parallel_workspace_bytes(n, n_words))
+            a = call.args(native.VetoMeetSampleArgs, mode=native.MEET_PAD_MODES[self.mode], n=n, n_words=n_words, n_groups=G,
+                          n_cls=self.n_cls, labels=labels, words=words, incre_idx_list=self.incre, pos_in_group=self.pos_in_group,
+                          group_size=self.group_size, sample_rates=self.rates, chosen=chosen, group_labels=glabels, counts=meta,
+                          words_used=meta[G:])
+            call.run("veto_meet_sample_parallel", ctypes.byref(a), ws.data_ptr(), ws.numel())
             host = meta.cpu().tolist()       # the list lengths are data dependent: one small read-back
             if host[G] >= 0:
                 break
+            if not retry:
+                raise RuntimeError("veto_meet_sample_parallel: %d words did not cover %d relations in mode %s" % (n_words, n, self.mode))
             n_words *= 2                      # astronomically unlikely: the rejection loop outran the block
         used = host[G]
         bg2, st = _numpy_generator_from_python_random()

@@ -239,6 +239,16 @@ class VetoTrainPlan(Structure):
                 ("d_roi", c_int32), ("reserved0", c_int32)]
 
 
+class VetoMeetSampleArgs(Structure):
+    _fields_ = [(n, c_int32) for n in ("struct_size", "mode", "n", "n_words", "n_groups", "n_cls")] + \
+               [(n, c_void_p) for n in ("labels", "words", "incre_idx_list", "pos_in_group", "group_size", "sample_rates",
+                                        "chosen", "group_labels", "counts", "words_used")]
+
+
+VETO_MEET_RAND_INSERT, VETO_MEET_RAND_CHOOSE, VETO_MEET_ALL_INCLUDE = 0, 1, 2   # enum veto_meet_pad_mode
+MEET_PAD_MODES = {"rand_insert": VETO_MEET_RAND_INSERT, "rand_choose": VETO_MEET_RAND_CHOOSE, "all_include": VETO_MEET_ALL_INCLUDE}
+
+
 STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_abi_symbols.py compares every field's offset and size)
     "veto_config_t": VetoConfig, "veto_inputs_t": VetoInputs, "veto_debug_outputs_t": VetoDebugOutputs,
     "veto_saturation_t": VetoSaturation, "veto_post_args_t": VetoPostArgs, "veto_post_meet_args_t": VetoPostMeetArgs,
@@ -251,7 +261,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_roi_pool_args_t": VetoRoiPoolArgs, "veto_sgg_eval_args_t": VetoSggEvalArgs, "veto_train_opts_t": VetoTrainOpts,
     "veto_train_plan_t": VetoTrainPlan,
     "veto_det_eval_match_args_t": VetoDetEvalMatchArgs, "veto_det_eval_accumulate_args_t": VetoDetEvalAccumulateArgs,
-    "veto_sgg_eval_fold_args_t": VetoSggEvalFoldArgs,
+    "veto_sgg_eval_fold_args_t": VetoSggEvalFoldArgs, "veto_meet_sample_args_t": VetoMeetSampleArgs,
 }
 
 _P, _I, _Z = c_void_p, c_int32, c_size_t
@@ -340,6 +350,9 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_ce_loss": _sig(_P, _P, c_int64, _P, _P, _P, _I, _I, _P, _P, _P, _Z),
     "veto_ce_loss_workspace_bytes": _sig(_I, ret=_Z),
     "veto_meet_sample": _sig(_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P),
+    "veto_meet_sample_parallel": _sig(_P, POINTER(VetoMeetSampleArgs), _P, _Z),
+    "veto_meet_sample_parallel_workspace_bytes": _sig(_I, _I, ret=_Z),
+    "veto_meet_sample_parallel_limits": _sig(POINTER(_I), POINTER(_I), POINTER(_I)),
     "veto_roi_pool": _sig(_P, POINTER(VetoRoiPoolArgs)),
     "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_roi_pool_backward_ordered": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
