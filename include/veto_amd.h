@@ -188,7 +188,7 @@ typedef struct veto_post_args {
   int32_t struct_size;            /* sizeof(veto_post_args_t) */
   int32_t n_img, n_obj, n_pair;
   int32_t n_rel_cls, n_obj_cls;   /* 51 / 151 (VG) */
-  int32_t max_pairs_per_image;    /* host-side maximum of the per-image pair counts; must be <= 4096 */
+  int32_t max_pairs_per_image;    /* host-side maximum of the per-image pair counts; must be <= 16384 */
   int32_t reserved0;
   const float* rel_logits;        /* device [n_pair, n_rel_cls] */
   const float* obj_logits;        /* device [n_obj, n_obj_cls]  (refine logits / predict_logits); NULL (sgdet): obj_scores and
@@ -211,7 +211,9 @@ int veto_postprocess(void* stream, const veto_post_args_t* args, void* workspace
  * (the reference zips the group logits with the first image only).  Each of the n_groups heads is
  * soft-maxed over its g_k+2 logits, the last column dropped, the arg-max over columns 1..g_k taken as a
  * GROUP-LOCAL label; all n_groups*n_pair rows are merged and sorted by triple score; row probabilities are
- * scattered into n_rel_cls-wide rows at columns [0] + {c : incre_idx_list[c] == k+1}. */
+ * scattered into n_rel_cls-wide rows at columns [0] + {c : incre_idx_list[c] == k+1}.
+ * This is veto_postprocess_groups_batch (below) with n_img = 1 and experts_per_group = 1: the same kernels, limits (n_rel_cls <= 256
+ * and n_groups <= 16 among them) and refusals; the row limit's message reads "n_groups * n_pair = ... exceeds 16384". */
 typedef struct veto_post_meet_args {
   int32_t struct_size;
   int32_t n_obj, n_pair, n_groups;
@@ -236,7 +238,9 @@ int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* args, void*
  * inference.py:93-283, for ONE image: every group has three expert heads ('group_<k>1..3'); a pair's row
  * for group k is kept when two experts ('C', consensus) or all three ('U', unanimous) pick the same
  * class; kept rows carry the averaged score / probabilities of the agreeing experts.  Outputs are sized
- * for n_groups*n_pair rows; the first *kept_count rows (score order) are the result, the rest is padding. */
+ * for n_groups*n_pair rows; the first *kept_count rows (score order) are the result, the rest is padding.
+ * This is veto_postprocess_groups_batch (below) with n_img = 1 and experts_per_group = 3: the same kernels, limits (n_rel_cls <= 256
+ * and n_groups <= 16 among them) and refusals. */
 typedef struct veto_post_vote_args {
   int32_t struct_size;
   int32_t n_obj, n_pair, n_groups;
@@ -261,7 +265,7 @@ typedef struct veto_post_vote_args {
 int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* args, void* workspace, size_t workspace_bytes);
 
 /* The MEET merge (experts_per_group 1) and the EXPERT_GROUP vote (experts_per_group 3) for a WHOLE ragged batch: image i gets exactly
- * what veto_postprocess_meet / veto_postprocess_vote return for image i alone, bit for bit, in at most four launches per call
+ * what this call (or veto_postprocess_meet / veto_postprocess_vote) returns for image i alone, bit for bit, in at most four launches per call
  * (object scores, group scores, one sort workgroup per image, gather) whatever n_img and n_groups.
  * Row layout of the four relation outputs (n_groups * n_pair rows, P_i = pairs of image i): image i owns the contiguous block of
  * n_groups * P_i rows that starts at row n_groups * img_pair_offset[i].  Before the sort a block is ordered (group, pair) -- row

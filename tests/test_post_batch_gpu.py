@@ -284,6 +284,53 @@ def test_abi_refuses_bad_arguments_before_any_launch():
     assert not _untouched([call.outs["triple"][:call.total]])
 
 
+@pytest.mark.parametrize("batch,i", [("meet_vg", 2), ("meet_vg", 3), ("meet_vg", 4), ("vote_C", 2)])
+def test_one_image_entry_points_give_the_batch_calls_block(batch, i):
+    """veto_postprocess_meet / veto_postprocess_vote, which the PostProcessor no longer calls, directly on the slices of image i
+    (5, 10 and 450 merged rows; the 2-pair vote image), twice: every field bit-equal to image i's block of the batch call, and
+    nothing written behind the stated rows, kept_count[1] or the stated workspace size."""
+    from veto_amd import native
+    lib = native.load_library()
+    x, s, K, vote = bc.inputs(batch), bc.image_slices(batch, i), bc.n_groups(batch), bc.voting(batch)
+    keys = ["group_%d%d" % (k, e + 1) for k in range(K) for e in range(3)] if vote else ["group_%d" % k for k in range(K)]
+    heads, obj, pairs = [_to(s["rel"][k]) for k in keys], _to(s["obj"]), _to(s["pairs"])
+    n_obj, P, n_rel = x["n_objs"][i], x["n_pairs"][i], len(x["incre"])
+    total, ws_bytes = K * P, lib.veto_postprocess_workspace_bytes(K * P, n_rel)
+    host = ((ctypes.c_void_p * len(heads))(*[h.data_ptr() for h in heads]),
+            (ctypes.c_int32 * K)(*[heads[len(heads) // K * k].shape[1] for k in range(K)]), (ctypes.c_int32 * n_rel)(*x["incre"]))
+    want = _run_batch(batch)[i]
+    for _ in range(2):
+        R = total + EXTRA_ROWS
+        o = {"obj_scores": _filled(n_obj + EXTRA_ROWS, torch.float32), "obj_pred": _filled(n_obj + EXTRA_ROWS, torch.int64),
+             "prob": _filled((R, n_rel), torch.float32), "pairs": _filled((R, 2), torch.int64), "labels": _filled(R, torch.int64),
+             "triple": _filled(R, torch.float32), "kept": _filled(1 + EXTRA_ROWS, torch.int32),
+             "workspace": _filled(ws_bytes + 4096, torch.uint8)}
+        a = (native.VetoPostVoteArgs if vote else native.VetoPostMeetArgs)()
+        a.struct_size = ctypes.sizeof(a)
+        a.n_obj, a.n_pair, a.n_groups, a.n_rel_cls, a.n_obj_cls = n_obj, P, K, n_rel, obj.shape[1]
+        setattr(a, "expert_logits" if vote else "group_logits", ctypes.cast(host[0], ctypes.c_void_p))
+        a.group_widths, a.incre_idx_list = ctypes.cast(host[1], ctypes.c_void_p), ctypes.cast(host[2], ctypes.c_void_p)
+        a.obj_logits, a.rel_pairs = obj.data_ptr(), pairs.data_ptr()
+        a.obj_scores, a.obj_pred = o["obj_scores"].data_ptr(), o["obj_pred"].data_ptr()
+        a.rel_prob_sorted, a.rel_pairs_sorted = o["prob"].data_ptr(), o["pairs"].data_ptr()
+        a.rel_labels_sorted, a.triple_sorted = o["labels"].data_ptr(), o["triple"].data_ptr()
+        if vote:
+            a.voting, a.kept_count = int(vote == "U"), o["kept"].data_ptr()
+        entry = lib.veto_postprocess_vote if vote else lib.veto_postprocess_meet
+        rc = entry(ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream), ctypes.byref(a), ctypes.c_void_p(o["workspace"].data_ptr()),
+                   ws_bytes)
+        torch.cuda.synchronize()
+        assert rc == 0, lib.veto_last_error()
+        assert _untouched([o["prob"][total:], o["pairs"][total:], o["labels"][total:], o["triple"][total:], o["obj_scores"][n_obj:],
+                           o["obj_pred"][n_obj:], o["workspace"][ws_bytes:], o["kept"][1:] if vote else o["kept"]])
+        n = int(o["kept"][0]) if vote else total
+        assert n == want["triple_scores"].shape[0]
+        got = {"rel_pair_idxs": o["pairs"][:n].to(torch.float32), "pred_rel_scores": o["prob"][:n], "pred_rel_labels": o["labels"][:n],
+               "pred_labels": o["obj_pred"][:n_obj], "pred_scores": o["obj_scores"][:n_obj], "triple_scores": o["triple"][:n]}
+        _assert_same(got, want, (batch, i))
+    print("post_batch: one-image ABI %-8s image %d: %d of %d rows, equal to the batch call's block" % (batch, i, n, total))
+
+
 # ---- 6. end to end ---------------------------------------------------------------------------------------------------------------
 class _Recorder(torch.nn.Module):
     """Stands in for the head's post-processor: keeps what the head hands it and calls it."""

@@ -139,3 +139,45 @@ def test_the_abi_refuses_before_it_touches_a_device():
     counts[1] = 4096                        # at the limit the sizes pass, and the empty workspace is what is refused
     host[3][1], a.n_pair, a.max_pairs_per_image = 4096, sum(counts), 4096
     assert call() == -4 and b"workspace too small" in lib.veto_last_error()
+
+
+@pytest.mark.parametrize("vote", [False, True])
+def test_the_one_image_entry_points_refuse_before_they_touch_a_device(vote):
+    """veto_postprocess_meet / veto_postprocess_vote are the batch call with n_img = 1 and share its checks: a wrong struct size,
+    voting = 2, a null head, a group width that is not its class count + 2, n_groups * n_pair = 16 388 and n_rel_cls = 257 each
+    return -1 with their message, from host arrays alone (4 GQA groups, 101 classes; device pointers that are never read)."""
+    import ctypes
+    from veto_amd import native
+    lib = native.load_library()
+    incre, K, per = bc.inputs("meet_gqa_over")["incre"], len(bc.GQA_MEET_GROUPS), 3 if vote else 1
+    struct = native.VetoPostVoteArgs if vote else native.VetoPostMeetArgs
+    entry = lib.veto_postprocess_vote if vote else lib.veto_postprocess_meet
+
+    def call(heads=None, widths=None, workspace=True, **fields):
+        heads = [8] * (per * K) if heads is None else heads
+        host = ((ctypes.c_void_p * len(heads))(*heads), (ctypes.c_int32 * K)(*(widths or [g + 2 for g in bc.GQA_MEET_GROUPS])),
+                (ctypes.c_int32 * len(incre))(*incre))
+        a = struct()
+        a.struct_size = ctypes.sizeof(struct)
+        a.n_obj, a.n_pair, a.n_groups, a.n_rel_cls, a.n_obj_cls = 3, 6, K, len(incre), 201
+        setattr(a, "expert_logits" if vote else "group_logits", ctypes.cast(host[0], ctypes.c_void_p))
+        a.group_widths, a.incre_idx_list = ctypes.cast(host[1], ctypes.c_void_p), ctypes.cast(host[2], ctypes.c_void_p)
+        for f in ("rel_pairs", "obj_scores", "obj_pred", "rel_prob_sorted", "rel_pairs_sorted", "rel_labels_sorted") + ("kept_count",) * vote:
+            setattr(a, f, 8)                    # never dereferenced: the call is refused first
+        for f, v in fields.items():
+            setattr(a, f, v)
+        ws = lib.veto_postprocess_workspace_bytes(K * a.n_pair, min(a.n_rel_cls, 256))
+        return entry(None, ctypes.byref(a), ctypes.c_void_p(256), ws if workspace else 0), lib.veto_last_error()
+
+    cases = [(dict(struct_size=ctypes.sizeof(struct) - 8), b"size mismatch"),
+             (dict(heads=[8, None] + [8] * (per * K - 2)), b"group %d head %d: null logits" % ((0, 2) if vote else (1, 1))),
+             (dict(widths=[7, 12, 23, 67]), b"group 2: 20 classes but head width 23"),
+             (dict(n_pair=4097), b"n_groups * n_pair = 16388 exceeds 16384"),
+             (dict(n_rel_cls=257), b"n_rel_cls 2..256")]
+    if vote:
+        cases.append((dict(voting=2), b"voting must be 0 ('C') or 1 ('U')"))
+    for change, needle in cases:
+        rc, msg = call(**change)
+        assert rc == -1 and needle in msg, (change, rc, msg)
+    rc, msg = call(n_pair=4096, workspace=False)      # at the limit the sizes pass, and the empty workspace is what is refused
+    assert rc == -4 and b"workspace too small" in msg, msg

@@ -1,9 +1,10 @@
 """MEET post-processing of a whole batch in one call (veto_postprocess_groups_batch) against the loop of one-image calls
-(veto_postprocess_meet / veto_postprocess_vote) on the same inputs: 12 images x 36 objects (1 260 pairs each, 15 120 pairs), VG
+(the same entry point with n_img = 1) on the same inputs: 12 images x 36 objects (1 260 pairs each, 15 120 pairs), VG
 (5 groups, 51 classes) and GQA (4 groups, 101 classes), the merge and both votes, through veto_amd.postprocess.PostProcessor.
+One more setting, vg_vanilla, times the vanilla branch (one [15 120, 51] logit matrix) on the same 12 images, the batch call only.
 
   batch   one PostProcessor call on the 12 images: at most 4 launches, the vote reads kept_count[12] back once
-  loop    12 PostProcessor calls on one image each, on slices of the same tensors: 12 x (K + 3) launches, the vote reads back 12 x
+  loop    12 PostProcessor calls on one image each, on slices of the same tensors: 12 x 4 launches, the vote reads back 12 x
 
 Both forms are timed in the same process, alternating, after a warm-up; per repetition the device time is taken with device events
 around the call(s) and the host time with a host clock from the call to its return on an idle stream.  The report is the median
@@ -26,7 +27,7 @@ from veto_amd.structures import BoxList  # noqa: E402
 
 N_IMG, N_OBJ = 12, 36
 DATASETS = {"vg": ([4, 6, 9, 19, 12], 151), "gqa": ([5, 10, 20, 65], 201)}      # MEET group sizes (divide4 / divide4 of GQA), object classes
-SETTINGS = [d + "_" + m for d in DATASETS for m in ("merge", "vote_C", "vote_U")]
+SETTINGS = [d + "_" + m for d in DATASETS for m in ("merge", "vote_C", "vote_U")] + ["vg_vanilla"]
 
 
 def build(setting, dev):
@@ -39,7 +40,7 @@ def build(setting, dev):
     pairs = torch.stack(torch.meshgrid(idx, idx, indexing="ij"), -1).reshape(-1, 2)
     pairs = pairs[pairs[:, 0] != pairs[:, 1]].contiguous().to(dev)
     rel = {}
-    for k, g in enumerate(groups):
+    for k, g in enumerate(groups if mode != "vanilla" else []):
         if mode == "merge":
             rel["group_%d" % k] = (2.0 * torch.randn(N_IMG * P, g + 2, generator=gen)).to(dev)
         else:       # three experts that share a part, so that they often agree
@@ -48,13 +49,21 @@ def build(setting, dev):
                 rel["group_%d%d" % (k, e + 1)] = (base + torch.randn(N_IMG * P, g + 2, generator=gen)).to(dev)
     obj = (3.0 * torch.randn(N_IMG * N_OBJ, n_objc, generator=gen)).to(dev)
     cfg = None
-    if mode != "merge":
+    if mode.startswith("vote"):
         cfg = testing.make_config(1, 8, meet=True, dataset="VG")
         cfg.ENSEMBLE_LEARNING.EXPERT_GROUP = True
         cfg.ENSEMBLE_LEARNING.VOTING = mode[-1]
     post = PostProcessor(False, use_gt_box=True, cfg=cfg)
     boxes = [BoxList(torch.zeros(N_OBJ, 4), (800, 600)).to(dev) for _ in range(N_IMG)]
     objs, pair_lists = list(obj.split(N_OBJ)), [pairs] * N_IMG
+    if mode == "vanilla":
+        logits = list((2.0 * torch.randn(N_IMG * P, len(incre), generator=gen)).to(dev).split(P))
+
+        def vanilla():
+            res = post((logits, objs), pair_lists, boxes)
+            return res, post.last_triple_scores
+
+        return {"batch": vanilla}, 1
     slices = [{k: v[i * P:(i + 1) * P] for k, v in rel.items()} for i in range(N_IMG)]
 
     def batch():
@@ -101,7 +110,7 @@ def main():
         for _ in range(3):          # warm-up: code objects, allocator, workspace, the cached offsets
             got = {name: snapshot(call()) for name, call in calls.items()}
         torch.cuda.synchronize()
-        equal = all(torch.equal(x, y) for a, b in zip(got["batch"], got["loop"]) for x, y in zip(a, b))
+        equal = all(torch.equal(x, y) for a, b in zip(got["batch"], got.get("loop", got["batch"])) for x, y in zip(a, b))
         rows = [int(a[-1].shape[0]) for a in got["batch"]]
         dev_ms, host_ms = {n: [] for n in calls}, {n: [] for n in calls}
         for _ in range(args.reps):
@@ -121,8 +130,9 @@ def main():
         for name in calls:
             out.update({name + "_device_ms": med(dev_ms[name]), name + "_device_ms_min": round(min(dev_ms[name]), 4),
                         name + "_device_ms_max": round(max(dev_ms[name]), 4), name + "_host_ms": med(host_ms[name])})
-        out.update(loop_over_batch_device=round(out["loop_device_ms"] / out["batch_device_ms"], 2),
-                   loop_over_batch_host=round(out["loop_host_ms"] / out["batch_host_ms"], 2))
+        if "loop" in calls:
+            out.update(loop_over_batch_device=round(out["loop_device_ms"] / out["batch_device_ms"], 2),
+                       loop_over_batch_host=round(out["loop_host_ms"] / out["batch_host_ms"], 2))
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if args.out:

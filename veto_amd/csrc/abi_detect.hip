@@ -45,69 +45,14 @@ int veto_postprocess(void* stream, const veto_post_args_t* a, void* workspace, s
   PostArgs p = post_args(a);
   p.rel_logits = a->rel_logits; p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset; p.n_img = a->n_img;
   carve_post(Carver{(char*)workspace}, a->n_pair, a->n_rel_cls, &p);
-  HIP_TRY(launch_postprocess(p, (hipStream_t)stream));
+  HIP_TRY(launch_postprocess(p, nullptr, (hipStream_t)stream));
   return VETO_OK;
 }
 
-int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* workspace, size_t workspace_bytes) {
-  CHECK_STRUCT_AND(veto_post_meet_args_t, a, workspace != nullptr);
-  if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
-    return fail(VETO_ERR_INVALID, "bad sizes");
-  if (!a->group_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
-      !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted)
-    return fail(VETO_ERR_INVALID, "missing pointer");
-  const long total = (long)a->n_groups * a->n_pair;
-  if (total > postprocess_max_pairs_per_image())
-    return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
-  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls), false));
-  std::vector<MeetGroup> groups(a->n_groups);
-  for (int k = 0; k < a->n_groups; ++k) {
-    MeetGroup& g = groups[k];
-    g.logits = a->group_logits[k];
-    g.width = a->group_widths[k];
-    g.row0 = k * a->n_pair;
-    if (!g.logits) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, g.width);
-    ABI_TRY(fill_group_cols(g.cols, g.width, k, a->incre_idx_list, a->n_rel_cls));
-  }
-  PostArgs p = post_args(a);
-  p.n_img = 1;
-  carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
-  HIP_TRY(launch_postprocess_meet(p, groups.data(), a->n_groups, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* workspace, size_t workspace_bytes) {
-  CHECK_STRUCT_AND(veto_post_vote_args_t, a, workspace != nullptr);
-  if (a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > 16 || a->n_rel_cls < 2 || a->n_obj_cls < 2)
-    return fail(VETO_ERR_INVALID, "bad sizes");
-  if (a->voting != 0 && a->voting != 1) return fail(VETO_ERR_INVALID, "voting must be 0 ('C') or 1 ('U')");
-  if (!a->expert_logits || !a->group_widths || !a->incre_idx_list || !a->rel_pairs || !a->obj_scores ||
-      !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted || !a->kept_count)
-    return fail(VETO_ERR_INVALID, "missing pointer");
-  const long total = (long)a->n_groups * a->n_pair;
-  if (total > postprocess_max_pairs_per_image())
-    return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", total, postprocess_max_pairs_per_image());
-  ABI_TRY(check_workspace(workspace, workspace_bytes, veto_postprocess_workspace_bytes((int32_t)total, a->n_rel_cls), false));
-  std::vector<VoteGroup> groups(a->n_groups);
-  for (int k = 0; k < a->n_groups; ++k) {
-    VoteGroup& g = groups[k];
-    for (int e = 0; e < 3; ++e) {
-      g.logits[e] = a->expert_logits[3 * k + e];
-      if (!g.logits[e]) return fail(VETO_ERR_INVALID, "group %d expert %d: null logits", k, e + 1);
-    }
-    g.width = a->group_widths[k];
-    g.row0 = k * a->n_pair;
-    ABI_TRY(fill_group_cols(g.cols, g.width, k, a->incre_idx_list, a->n_rel_cls));
-  }
-  PostArgs p = post_args(a);
-  p.n_img = 1; p.kept_count = a->kept_count;
-  carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
-  HIP_TRY(launch_postprocess_vote(p, groups.data(), a->n_groups, a->voting, (hipStream_t)stream));
-  return VETO_OK;
-}
-
-int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_args_t* a, void* workspace, size_t workspace_bytes) {
-  CHECK_STRUCT_AND(veto_post_groups_batch_args_t, a, workspace != nullptr);
+// The MEET merge / expert vote of veto_postprocess_groups_batch and of the two one-image entry points, which are that call with
+// n_img = 1: every check, the group tables, the workspace and the launch.  one_image: `a` was filled by one_image_groups() -- null
+// offsets, pairs_per_image = {n_pair} -- and the row limit's message names no image.
+static int post_groups(void* stream, const veto_post_groups_batch_args_t* a, bool one_image, void* workspace, size_t workspace_bytes) {
   if (a->n_img <= 0 || a->n_obj <= 0 || a->n_pair <= 0 || a->n_groups <= 0 || a->n_groups > kPostMaxGroups || a->n_rel_cls < 2 ||
       a->n_rel_cls > kPostMaxRelCls || a->n_obj_cls < 2)
     return fail(VETO_ERR_INVALID, "bad sizes (n_groups 1..%d, n_rel_cls 2..%d)", kPostMaxGroups, kPostMaxRelCls);
@@ -116,9 +61,9 @@ int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_arg
   const bool vote = a->experts_per_group == 3;
   if (vote ? (a->voting != 0 && a->voting != 1) : a->voting != 0)
     return fail(VETO_ERR_INVALID, "%s", vote ? "voting must be 0 ('C') or 1 ('U')" : "voting must be 0 for the merge");
-  if (!a->head_logits || !a->group_widths || !a->incre_idx_list || !a->pairs_per_image || !a->rel_pairs || !a->img_obj_offset ||
-      !a->img_pair_offset || !a->obj_scores || !a->obj_pred || !a->rel_prob_sorted || !a->rel_pairs_sorted || !a->rel_labels_sorted ||
-      vote != (a->kept_count != nullptr))
+  if (!a->head_logits || !a->group_widths || !a->incre_idx_list || !a->pairs_per_image || !a->rel_pairs ||
+      (!one_image && (!a->img_obj_offset || !a->img_pair_offset)) || !a->obj_scores || !a->obj_pred || !a->rel_prob_sorted ||
+      !a->rel_pairs_sorted || !a->rel_labels_sorted || vote != (a->kept_count != nullptr))
     return fail(VETO_ERR_INVALID, "missing pointer");
   const long total = (long)a->n_groups * a->n_pair;
   if (total > INT32_MAX) return fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds int32", total);
@@ -128,7 +73,8 @@ int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_arg
     const long rows = (long)a->n_groups * a->pairs_per_image[i];
     if (a->pairs_per_image[i] < 0) return fail(VETO_ERR_INVALID, "image %d: %d pairs", i, a->pairs_per_image[i]);
     if (rows > postprocess_max_pairs_per_image())
-      return fail(VETO_ERR_INVALID, "image %d: n_groups * pairs = %ld exceeds %d", i, rows, postprocess_max_pairs_per_image());
+      return one_image ? fail(VETO_ERR_INVALID, "n_groups * n_pair = %ld exceeds %d", rows, postprocess_max_pairs_per_image())
+                       : fail(VETO_ERR_INVALID, "image %d: n_groups * pairs = %ld exceeds %d", i, rows, postprocess_max_pairs_per_image());
     sum += a->pairs_per_image[i];
     if (a->pairs_per_image[i] > largest) largest = a->pairs_per_image[i];
   }
@@ -141,8 +87,7 @@ int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_arg
   for (int c = 0; c < a->n_rel_cls; ++c)
     t.cls_group[c] = a->incre_idx_list[c] >= 0 && a->incre_idx_list[c] <= a->n_groups ? (uint8_t)a->incre_idx_list[c] : 255;
   for (int k = 0; k < a->n_groups; ++k) {
-    int cols[104];   // the same check as the one-image entry points; the kernel derives the columns itself
-    ABI_TRY(fill_group_cols(cols, a->group_widths[k], k, a->incre_idx_list, a->n_rel_cls));
+    ABI_TRY(check_group_width(a->group_widths[k], k, a->incre_idx_list, a->n_rel_cls));   // the kernel derives the columns itself
     t.width[k] = a->group_widths[k];
     for (int e = 0; e < a->experts_per_group; ++e) {
       t.logits[a->experts_per_group * k + e] = a->head_logits[a->experts_per_group * k + e];
@@ -152,8 +97,25 @@ int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_arg
   PostArgs p = post_args(a);
   p.n_img = a->n_img; p.img_obj_off = a->img_obj_offset; p.img_pair_off = a->img_pair_offset; p.kept_count = a->kept_count;
   carve_post(Carver{(char*)workspace}, total, a->n_rel_cls, &p);
-  HIP_TRY(launch_postprocess_groups_batch(p, t, (hipStream_t)stream));
+  HIP_TRY(launch_postprocess(p, &t, (hipStream_t)stream));
   return VETO_OK;
+}
+
+int veto_postprocess_meet(void* stream, const veto_post_meet_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT_AND(veto_post_meet_args_t, a, workspace != nullptr);
+  const veto_post_groups_batch_args_t b = one_image_groups(a, a->group_logits, 1, 0, nullptr);
+  return post_groups(stream, &b, true, workspace, workspace_bytes);
+}
+
+int veto_postprocess_vote(void* stream, const veto_post_vote_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT_AND(veto_post_vote_args_t, a, workspace != nullptr);
+  const veto_post_groups_batch_args_t b = one_image_groups(a, a->expert_logits, 3, a->voting, a->kept_count);
+  return post_groups(stream, &b, true, workspace, workspace_bytes);
+}
+
+int veto_postprocess_groups_batch(void* stream, const veto_post_groups_batch_args_t* a, void* workspace, size_t workspace_bytes) {
+  CHECK_STRUCT_AND(veto_post_groups_batch_args_t, a, workspace != nullptr);
+  return post_groups(stream, a, false, workspace, workspace_bytes);
 }
 
 static size_t carve_obj_decode(Carver c, int n_obj, int n_cls, ObjDecodeArgs* p) {

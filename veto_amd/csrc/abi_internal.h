@@ -118,22 +118,18 @@ inline int check_reg_weights(const float* w, bool positive, const char* suffix) 
   return VETO_OK;
 }
 
-// The columns of MEET / vote group k (MeetGroup::cols, VoteGroup::cols): the background, then every class c of the group
-// (incre_idx_list[c] == k + 1); the group's head must be exactly that wide
-inline int fill_group_cols(int* cols, int width, int k, const int32_t* incre_idx_list, int n_rel_cls) {
+// The head of MEET / vote group k holds the background, every class c of the group (incre_idx_list[c] == k + 1) and the "other
+// group" column: it must be exactly that wide, and the kernel's column table holds 104 columns
+inline int check_group_width(int width, int k, const int32_t* incre_idx_list, int n_rel_cls) {
   if (width < 3 || width - 1 > 104) return fail(VETO_ERR_INVALID, "bad group %d (width %d)", k, width);
   int n = 0;
-  cols[n++] = 0;
-  for (int c = 0; c < n_rel_cls; ++c)
-    if (incre_idx_list[c] == k + 1) {
-      if (n >= width - 1) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
-      cols[n++] = c;
-    }
-  if (n != width - 1) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n - 1, width);
+  for (int c = 0; c < n_rel_cls; ++c) n += incre_idx_list[c] == k + 1;
+  if (n > width - 2) return fail(VETO_ERR_INVALID, "group %d has more classes than its head is wide", k);
+  if (n != width - 2) return fail(VETO_ERR_INVALID, "group %d: %d classes but head width %d", k, n, width);
   return VETO_OK;
 }
 
-// What the argument structs of the three relation post-processors have in common (the caller adds n_img and its own inputs)
+// What the argument structs of the relation post-processors have in common (the caller adds n_img and its own inputs)
 template <class T>
 inline PostArgs post_args(const T* a) {
   PostArgs p{};
@@ -142,6 +138,19 @@ inline PostArgs post_args(const T* a) {
   p.obj_scores = a->obj_scores; p.obj_pred = a->obj_pred; p.out_prob = a->rel_prob_sorted;
   p.out_pairs = a->rel_pairs_sorted; p.out_labels = a->rel_labels_sorted; p.out_triple = a->triple_sorted;
   return p;
+}
+
+// veto_post_meet_args_t / veto_post_vote_args_t as the batch call's struct: one image of n_pair pairs, no offsets
+template <class T>
+inline veto_post_groups_batch_args_t one_image_groups(const T* a, const float* const* heads, int experts, int voting, int32_t* kept_count) {
+  veto_post_groups_batch_args_t b{};
+  b.n_img = 1; b.n_obj = a->n_obj; b.n_pair = a->n_pair; b.n_groups = a->n_groups; b.experts_per_group = experts;
+  b.n_rel_cls = a->n_rel_cls; b.n_obj_cls = a->n_obj_cls; b.voting = voting; b.max_pairs_per_image = a->n_pair;
+  b.head_logits = heads; b.group_widths = a->group_widths; b.incre_idx_list = a->incre_idx_list; b.pairs_per_image = &a->n_pair;
+  b.obj_logits = a->obj_logits; b.rel_pairs = a->rel_pairs; b.obj_scores = a->obj_scores; b.obj_pred = a->obj_pred;
+  b.rel_prob_sorted = a->rel_prob_sorted; b.rel_pairs_sorted = a->rel_pairs_sorted; b.rel_labels_sorted = a->rel_labels_sorted;
+  b.triple_sorted = a->triple_sorted; b.kept_count = kept_count;
+  return b;
 }
 
 struct Param {

@@ -247,47 +247,27 @@ bool cls_fold_reads_f24();   // whether the kernel takes u as 3-byte floats (the
 hipError_t launch_head(const float* cls, const float* wt, const float* bias, float* out, int n_pair,
                        int n_out, hipStream_t s, long ld = kDim);
 
-// ---- post-processing (inference.py:398-453, GT-box branch) -------------------------------------
+// ---- post-processing (inference.py:398-453, GT-box branch; the MEET merge :284-397 and the expert vote :93-283) ----------------
+// `rows` below: n_pair for the vanilla branch, n_groups * n_pair for the merge and the vote
 struct PostArgs {
-  const float* rel_logits;       // [n_pair, n_rel_cls]
-  const float* obj_logits;       // [n_obj, n_obj_cls]
+  const float* rel_logits;       // vanilla: [n_pair, n_rel_cls]
+  const float* obj_logits;       // [n_obj, n_obj_cls]; nullptr (sgdet): obj_scores / obj_pred are inputs
   const int64_t* rel_pairs;      // [n_pair, 2] image-local
-  const int32_t* img_obj_off;    // [n_img + 1]
+  const int32_t* img_obj_off;    // [n_img + 1]; both offset arrays nullptr: ONE image that owns every pair and object
   const int32_t* img_pair_off;   // [n_img + 1]
   int n_img, n_obj, n_pair, n_rel_cls, n_obj_cls;
   float* obj_scores;             // out [n_obj]
   int64_t* obj_pred;             // out [n_obj]
-  float* out_prob;               // out [n_pair, n_rel_cls], sorted
-  int64_t* out_pairs;            // out [n_pair, 2], sorted
-  int64_t* out_labels;           // out [n_pair], sorted
-  float* out_triple;             // optional out [n_pair], sorted
-  float* prob_tmp;               // workspace [n_pair, n_rel_cls]
-  float* triple;                 // workspace [n_pair]
-  int32_t* label_tmp;            // workspace [n_pair]
-  int32_t* perm;                 // workspace [n_pair]
-  int single_cnt;                // > 0: one segment of this many rows (MEET merge) instead of img_pair_off
-  int pair_mod;                  // > 0: row r refers to pair r % pair_mod (MEET: K copies of the pair list)
-  int32_t* kept_count;           // optional out [1]: rows of the sorted segment with score >= 0 (expert voting)
+  float* out_prob;               // out [rows, n_rel_cls], sorted
+  int64_t* out_pairs;            // out [rows, 2], sorted
+  int64_t* out_labels;           // out [rows], sorted
+  float* out_triple;             // optional out [rows], sorted
+  float* prob_tmp;               // workspace [rows, n_rel_cls]
+  float* triple;                 // workspace [rows]
+  int32_t* label_tmp;            // workspace [rows]
+  int32_t* perm;                 // workspace [rows]
+  int32_t* kept_count;           // optional out [n_img]: rows of each image's sorted block with score >= 0 (expert voting)
 };
-struct MeetGroup {               // one MEET head, passed by value
-  const float* logits;           // [n_pair, width], width = g + 2
-  int width;
-  int row0;                      // first row of this group in the merged list
-  int cols[104];                 // cols[c] = global class of the group's column c (cols[0] = 0), c < width - 1
-};
-hipError_t launch_postprocess_meet(PostArgs a, const MeetGroup* groups, int n_groups, hipStream_t s);
-struct VoteGroup {               // one MEET group with its three expert heads, passed by value
-  const float* logits[3];        // each [n_pair, width]
-  int width;
-  int row0;
-  int cols[104];
-};
-// voting: 0 = consensus ('C', two of three experts agree), 1 = unanimous ('U')
-hipError_t launch_postprocess_vote(PostArgs a, const VoteGroup* groups, int n_groups, int voting, hipStream_t s);
-// The MEET merge / expert vote of a whole batch in four launches (object scores, group scores, sort, gather), whatever n_img and
-// n_groups.  `a` as for launch_postprocess (img_obj_off / img_pair_off set, n_pair = the batch's pairs, workspace and outputs of
-// n_groups * n_pair rows; kept_count [n_img] for the vote).  Image i owns rows n_groups * img_pair_off[i] .. of n_groups * P_i rows,
-// ordered (group, pair) before the sort.
 constexpr int kPostMaxGroups = 16;
 constexpr int kPostMaxRelCls = 256;
 struct PostGroupTables {         // passed by value: the heads and the class -> group list; a wave derives its group's columns
@@ -295,11 +275,13 @@ struct PostGroupTables {         // passed by value: the heads and the class -> 
   int width[kPostMaxGroups];     // g_k + 2
   uint8_t cls_group[kPostMaxRelCls];         // 1-based group of class c, 0 = background (255: no group)
   int n_groups, experts;         // experts: 1 (merge) or 3 (vote)
-  int voting;                    // vote: 0 = consensus, 1 = unanimous
+  int voting;                    // vote: 0 = consensus ('C', two of three experts agree), 1 = unanimous ('U')
 };
-hipError_t launch_postprocess_groups_batch(const PostArgs& a, const PostGroupTables& t, hipStream_t s);
 int postprocess_max_pairs_per_image();
-hipError_t launch_postprocess(const PostArgs& a, hipStream_t s);   // obj_logits == nullptr: obj_scores / obj_pred are inputs
+// Four launches (object scores, row scores, one sort workgroup per image, gather) whatever n_img and n_groups.  t == nullptr: the
+// vanilla branch on a.rel_logits.  Else the MEET merge / expert vote of t's heads: image i owns rows n_groups * img_pair_off[i] .. of
+// n_groups * P_i rows, ordered (group, pair) before the sort.
+hipError_t launch_postprocess(const PostArgs& a, const PostGroupTables* t, hipStream_t s);
 
 // ---- sgdet: object decoding and test pairs on detected boxes (sgdet.hip) ----------------------------
 struct ObjDecodeArgs {

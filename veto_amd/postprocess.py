@@ -7,14 +7,14 @@ Mirrors the vanilla, GT-box branch of the reference's PostProcessor
 arithmetic (softmax, foreground max, triple score, per-image descending sort, gather) runs in
 libveto_amd.so (veto_postprocess).  When the relation logits are the MEET dict of group heads
 (ENSEMBLE_LEARNING.ENABLED with EXPERT_GROUP False), the MEET merge branch (inference.py:284-397) runs
-through veto_postprocess_meet with the reference's quirks kept: group-local labels, float pair indices.  With
+with the reference's quirks kept: group-local labels, float pair indices.  With
 EXPERT_GROUP True (three expert heads per group, keys 'group_<k><e>') the voting branch (inference.py:93-283,
-ENSEMBLE_LEARNING.VOTING 'C' or 'U') runs through veto_postprocess_vote; its row count is data dependent, so that
-branch reads one int32 back from the device.  The reference zips the batch-wide group logits with the first image only
-(inference.py:114-116, :302-306); here both MEET branches take any number of images: one image goes through the
-one-image entry points above, more go through veto_postprocess_groups_batch in at most four launches (plus the object
-decoding in sgdet), every image getting exactly the one-image call's result, the vote reading kept_count[n_img] back
-once per batch.  With detected boxes
+ENSEMBLE_LEARNING.VOTING 'C' or 'U') runs; its row counts are data dependent, so that
+branch reads one int32 per image back from the device.  The reference zips the batch-wide group logits with the first image only
+(inference.py:114-116, :302-306); here both MEET branches take any number of images, one included, through
+veto_postprocess_groups_batch in at most four launches (plus the object
+decoding in sgdet), every image getting exactly the result of a call on it alone, the vote reading kept_count[n_img] back
+once per call.  With detected boxes
 (sgdet, use_gt_box False) every branch first decodes the objects with the class-aware NMS of inference.py:413-429
 (veto_obj_decode, LATER_NMS_PREDICTION_THRES) and returns NEW BoxLists holding the regressed boxes
 boxes_per_cls[i, label_i]; the relation kernels then read those labels / scores (obj_logits = NULL).  Attributes
@@ -74,8 +74,7 @@ class PostProcessor(nn.Module):
         if incre_idx_list is None:
             raise ValueError("the MEET merge needs incre_idx_list (4th element of the predictor's return tuple)")
         keys = ["group_%d" % k for k in range(len(relation_logits))]
-        return self._forward_groups(relation_logits, keys, 1, refine_logits, rel_pair_idxs, boxes, incre_idx_list,
-                                    native.VetoPostMeetArgs, "veto_postprocess_meet", "group_logits")
+        return self._forward_groups(relation_logits, keys, 1, refine_logits, rel_pair_idxs, boxes, incre_idx_list)
 
     def _forward_vote(self, relation_logits, refine_logits, rel_pair_idxs, boxes, incre_idx_list):
         if incre_idx_list is None:
@@ -87,67 +86,29 @@ class PostProcessor(nn.Module):
             raise ValueError("expected three expert heads per group, got %d heads" % len(relation_logits))
         keys = ["group_%d%d" % (k, e + 1) for k in range(len(relation_logits) // 3) for e in range(3)]
         return self._forward_groups(relation_logits, keys, 3, refine_logits, rel_pair_idxs, boxes, incre_idx_list,
-                                    native.VetoPostVoteArgs, "veto_postprocess_vote", "expert_logits",
                                     voting=0 if voting == "C" else 1)
 
-    def _forward_groups(self, relation_logits, keys, per_group, refine_logits, rel_pair_idxs, boxes, incre_idx_list, struct_cls,
-                        entry, heads_field, voting=None):
-        """The MEET merge (per_group 1) and the expert vote (per_group 3, `voting` set): K groups of per_group heads each.  One
-        image goes through the one-image entry point `entry`, more through veto_postprocess_groups_batch, which gives every image
-        the one-image call's result.  The vote's row count is data dependent and is read back; the merge keeps all K * n_pair rows."""
+    def _forward_groups(self, relation_logits, keys, per_group, refine_logits, rel_pair_idxs, boxes, incre_idx_list, voting=None):
+        """The MEET merge (per_group 1) and the expert vote (per_group 3, `voting` set): K groups of per_group heads each, one
+        image or a batch in ONE call: the batch-wide head logits as they are, the concatenated image-local pair lists and
+        refine logits (one image: its own tensors, no copy).  Image i owns the K * P_i rows from K * (pairs before it) on
+        (include/veto_amd.h).  The merge reads nothing back; the vote's row counts are data dependent: kept_count[n_img] is
+        read back once, to cut the blocks."""
         if len(boxes) == 0:
             raise ValueError("the MEET post-processor needs at least one image")
-        if len(boxes) > 1:
-            return self._forward_groups_batch(relation_logits, keys, per_group, refine_logits, rel_pair_idxs, boxes, incre_idx_list,
-                                              voting)
         device = relation_logits[keys[0]].device
         call = native.Launch(device, "veto_amd.PostProcessor runs only on a HIP device")
         heads = [relation_logits[k].detach().to(device=device, dtype=torch.float32).contiguous() for k in keys]
-        obj = (refine_logits[0] if isinstance(refine_logits, (list, tuple)) else refine_logits)
-        obj = obj.detach().to(device=device, dtype=torch.float32).contiguous()
-        pairs = rel_pair_idxs[0].reshape(-1, 2).to(device=device, dtype=torch.int64).contiguous()
-        K, n_rel = len(heads) // per_group, len(incre_idx_list)
-        total = K * pairs.shape[0]
-        out, reg_boxes = self._outputs(obj, boxes[:1], total, n_rel)
-        fields = self._shared_fields(obj, out, reg_boxes)
-        kept = None
-        if voting is not None:
-            kept = torch.zeros(1, dtype=torch.int32, device=device)
-            fields.update(voting=voting, kept_count=kept)
-        # host arrays: the ABI reads them before it returns
-        ptrs = (ctypes.c_void_p * len(heads))(*[call.ptr(h) for h in heads])
-        widths = (ctypes.c_int32 * K)(*[heads[per_group * k].shape[1] for k in range(K)])
-        incre = (ctypes.c_int32 * n_rel)(*[int(x) for x in incre_idx_list])
-        fields[heads_field] = ctypes.cast(ptrs, ctypes.c_void_p)
-        a = call.args(struct_cls, n_obj=obj.shape[0], n_pair=pairs.shape[0], n_groups=K, n_rel_cls=n_rel, n_obj_cls=obj.shape[1],
-                      group_widths=ctypes.cast(widths, ctypes.c_void_p), incre_idx_list=ctypes.cast(incre, ctypes.c_void_p),
-                      rel_pairs=pairs, **fields)
-        ws = call.workspace(call.lib.veto_postprocess_workspace_bytes(total, n_rel))
-        call.run(entry, ctypes.byref(a), ws.data_ptr(), ws.numel())
-        rows = slice(None)
-        if kept is not None:
-            rows = slice(int(kept.item()))   # the one device read-back: the result's row count is data dependent
-        self.last_triple_scores = [out["triple"][rows]]
-        # float pair indices (torch.zeros(total, 2) in the reference, inference.py:381 / :267) and group-local labels (:388)
-        return [self._fill(boxes[0], reg_boxes, out["obj_scores"], out["obj_pred"], out["pairs"][rows].to(torch.float32),
-                           out["prob"][rows], out["labels"][rows])]
-
-    def _forward_groups_batch(self, relation_logits, keys, per_group, refine_logits, rel_pair_idxs, boxes, incre_idx_list, voting):
-        """A batch of images in ONE call: the batch-wide head logits as they are, the concatenated image-local pair lists and
-        refine logits.  Image i owns the K * P_i rows from K * (pairs before it) on (include/veto_amd.h).  The merge reads
-        nothing back; the vote reads kept_count[n_img] back once, to cut the blocks."""
-        device = relation_logits[keys[0]].device
-        call = native.Launch(device, "veto_amd.PostProcessor runs only on a HIP device")
-        heads = [relation_logits[k].detach().to(device=device, dtype=torch.float32).contiguous() for k in keys]
-        obj = torch.cat(list(refine_logits), 0) if isinstance(refine_logits, (list, tuple)) else refine_logits
+        obj = _cat(list(refine_logits)) if isinstance(refine_logits, (list, tuple)) else refine_logits
         obj = obj.detach().to(device=device, dtype=torch.float32).contiguous()
         n_objs = [len(b) for b in boxes]
-        n_pairs = [int(p.reshape(-1, 2).shape[0]) for p in rel_pair_idxs]
+        pair_lists = [p.reshape(-1, 2) for p in rel_pair_idxs]
+        n_pairs = [int(p.shape[0]) for p in pair_lists]
         n_obj, n_pair = sum(n_objs), sum(n_pairs)
         if len(n_pairs) != len(boxes) or obj.shape[0] != n_obj or any(h.shape[0] != n_pair for h in heads):
             raise ValueError("head rows %s / object rows %d do not match the batch's pairs %s / objects %s"
                              % (sorted({int(h.shape[0]) for h in heads}), obj.shape[0], n_pairs, n_objs))
-        pairs = torch.cat([p.reshape(-1, 2) for p in rel_pair_idxs], 0).to(device=device, dtype=torch.int64).contiguous()
+        pairs = _cat(pair_lists).to(device=device, dtype=torch.int64).contiguous()
         off = native.device_offsets(n_objs, n_pairs, device=device)   # no host-blocking H2D copy in the steady state
         K, n_rel = len(heads) // per_group, len(incre_idx_list)
         total = K * n_pair
@@ -170,14 +131,17 @@ class PostProcessor(nn.Module):
         ws = call.workspace(call.lib.veto_postprocess_workspace_bytes(total, n_rel))
         call.run("veto_postprocess_groups_batch", ctypes.byref(a), ws.data_ptr(), ws.numel())
         blocks = [K * p for p in n_pairs]
-        keep = blocks if kept is None else kept.tolist()   # the vote's one device read-back: the row counts are data dependent
-        cut = lambda t: [b[:n] for b, n in zip(t.split(blocks), keep)]
+        if kept is None:
+            cut = lambda t: _split(t, blocks)
+        else:
+            keep = kept.tolist()   # the vote's one device read-back: the row counts are data dependent
+            cut = lambda t: [b[:n] for b, n in zip(_split(t, blocks), keep)]
         self.last_triple_scores = cut(out["triple"])
-        regs = reg_boxes.split(n_objs) if reg_boxes is not None else [None] * len(boxes)
+        regs = _split(reg_boxes, n_objs) if reg_boxes is not None else [None] * len(boxes)
         # float pair indices (torch.zeros(total, 2) in the reference, inference.py:381 / :267) and group-local labels (:388)
         # (one conversion for the batch, not one per image)
         return [self._fill(box, reg, sc, pr, pidx, prob, lab)
-                for box, reg, sc, pr, pidx, prob, lab in zip(boxes, regs, out["obj_scores"].split(n_objs), out["obj_pred"].split(n_objs),
+                for box, reg, sc, pr, pidx, prob, lab in zip(boxes, regs, _split(out["obj_scores"], n_objs), _split(out["obj_pred"], n_objs),
                                                              cut(out["pairs"].to(torch.float32)), cut(out["prob"]), cut(out["labels"]))]
 
     def _outputs(self, obj, boxes, rows, n_rel):
@@ -228,6 +192,16 @@ class PostProcessor(nn.Module):
         if reg is None:
             return box
         return type(box)(reg, box.size, "xyxy")
+
+
+def _cat(tensors):
+    """torch.cat along rows; a single tensor as it is, without the copy."""
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, 0)
+
+
+def _split(t, sizes):
+    """t.split(sizes); one size: the tensor as it is (a call on one image pays for no views)."""
+    return [t] if len(sizes) == 1 else t.split(sizes)
 
 
 def make_roi_relation_post_processor(cfg):
