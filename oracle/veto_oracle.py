@@ -70,6 +70,13 @@ def center_xywh_from_xyxy(boxes):
     return torch.stack([x1 + 0.5 * w, y1 + 0.5 * h, w, h], dim=-1)
 
 
+def center_xywh_from_xywh(boxes):
+    """roi_relation_predictors.py:4097-4100: a BoxList that is not in xyxy mode is taken as it is (no conversion, so no +1),
+    then model_mpv2.py:341-345 (centre = corner + 0.5 * size)."""
+    x1, y1, w, h = boxes.unbind(-1)
+    return torch.stack([x1 + 0.5 * w, y1 + 0.5 * h, w, h], dim=-1)
+
+
 def object_embeddings(sd, cfg, labels, predict_logits, pred_labels, dtype):
     """roi_relation_predictors.py:4086-4095 (vanilla) / :3769-3784 (MEET Ensemble)."""
     E = _t(sd[cfg.prefix + "obj_embed.weight"], dtype)
@@ -87,13 +94,14 @@ def object_embeddings(sd, cfg, labels, predict_logits, pred_labels, dtype):
     return emb, obj_dists
 
 
-def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False, drop=None):
+def position_embedding(sd, cfg, boxes_xyxy, dtype, batch_stats=False, drop=None, xywh=False):
     """pos_embed = BatchNorm1d(4) (eval: running stats, eps 1e-5) -> Linear(4,128) -> ReLU;
     roi_relation_predictors.py:4042-4047,4097-4102.  `batch_stats`: the training-mode BatchNorm, normalising with the
     batch mean and the BIASED batch variance (the running update, which takes the unbiased one, is not part of the forward).
-    `drop` (training, optional): the [n_obj, 128] factor keep / (1 - p) of the Dropout behind the ReLU (oracle/dropout.py, site 1)."""
+    `drop` (training, optional): the [n_obj, 128] factor keep / (1 - p) of the Dropout behind the ReLU (oracle/dropout.py, site 1).
+    `xywh`: the boxes are in xywh mode already (the else branch of :4097-4100)."""
     p = cfg.prefix + "pos_embed."
-    x = center_xywh_from_xyxy(_t(boxes_xyxy, dtype))
+    x = (center_xywh_from_xywh if xywh else center_xywh_from_xyxy)(_t(boxes_xyxy, dtype))
     if batch_stats:
         mean, var = x.mean(0), x.var(0, unbiased=False)
     else:
@@ -176,16 +184,21 @@ def head_weights(sd, cfg, dtype):
     return torch.cat([_t(sd[n + ".weight"], dtype) for n in names]), torch.cat([_t(sd[n + ".bias"], dtype) for n in names])
 
 
+def pair_location_class(sd, cfg, emb, pos, s, o, dtype):
+    """rel_location / rel_class of the pairs (s, o), roi_relation_predictors.py:4118-4121, as (the sums in front of the two ReLUs,
+    the ReLU'd rows): two pairs of [len(s), 576] tensors."""
+    pre = cfg.prefix
+    loc = (torch.cat([pos[s], pos[o]], dim=1) @ _t(sd[pre + "location_projection.0.weight"], dtype).t()
+           + _t(sd[pre + "location_projection.0.bias"], dtype))
+    cls = (torch.cat([emb[s], emb[o]], dim=1) @ _t(sd[pre + "class_projection.0.weight"], dtype).t()
+           + _t(sd[pre + "class_projection.0.bias"], dtype))
+    return (loc, cls), (torch.relu(loc), torch.relu(cls))
+
+
 def pair_tokens(sd, cfg, emb, pos, rgb, dep, s, o, dtype, drop=None):
     """The [len(s), 19, 576] token rows of the pairs (s, o): the materialised pair gathers of :4118-4123 and
     build_tokens (`drop`: its pos_drop factor)."""
-    pre = cfg.prefix
-    rel_location = torch.cat([pos[s], pos[o]], dim=1)
-    rel_location = torch.relu(rel_location @ _t(sd[pre + "location_projection.0.weight"], dtype).t()
-                              + _t(sd[pre + "location_projection.0.bias"], dtype))
-    rel_class = torch.cat([emb[s], emb[o]], dim=1)
-    rel_class = torch.relu(rel_class @ _t(sd[pre + "class_projection.0.weight"], dtype).t()
-                           + _t(sd[pre + "class_projection.0.bias"], dtype))
+    _, (rel_location, rel_class) = pair_location_class(sd, cfg, emb, pos, s, o, dtype)
     rel_visual = torch.cat([rgb[s], rgb[o]], dim=1)
     rel_depth = torch.cat([dep[s], dep[o]], dim=1)
     return build_tokens(sd, cfg, rel_depth, rel_visual, rel_location, rel_class, dtype, drop)
