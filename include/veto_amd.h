@@ -76,15 +76,29 @@ enum veto_precision {
                         one-exponential GELU (|error| <= 1e-6) in every mode; the training path keeps the erf form */
 };
 
-/* MODEL.ROI_RELATION_HEAD.VETOTRANSFORMER.* (config/defaults.py:331-338) + class counts. */
+/* MODEL.ROI_RELATION_HEAD.VETOTRANSFORMER.* (config/defaults.py:331-338) + class counts.
+ *
+ * Patch grids.  (resolution, patch) = (POOLER_RESOLUTION, PATCH_SIZE) is one of (4, 1), (8, 2), (12, 3), (16, 4): resolution == 4 * patch, so
+ * that an object's map always cuts into a 4 x 4 grid of patches and a pair into 19 tokens (CLS, location, class, 16 patches), which is
+ * what the fused launches hold; veto_create refuses every other pair with a message that names these four, before it allocates
+ * anything.  With p = patch, R = 4 p, K = 512 p^2 (512 / 2048 / 4608 / 8192):
+ *   ROI maps (inputs and their gradients)       [n_obj, 256, R, R]
+ *   patch_embed.proj_d.weight / .proj_v.weight  [512, K] / [64, K]; input feature (p1 p2 c) of cat(subject, object) = (p1 p + p2) 512 +
+ *                                               half 256 + c, as einops 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' leaves them
+ *   patch rows (workspaces)                     [n_obj * 16 padded to 256, 2 K] bf16 split rows: depth features 0 .. K/2 - 1, then
+ *                                               rgb, feature (p1 p + p2) 256 + c
+ *   staged patch weight                         [1152, 2 K] split rows;  its transpose for the map gradients [K padded to a multiple
+ *                                               of 192 (576 / 2112 / 4608 / 8256), 2 * 1152], the padding rows zero
+ * veto_workspace_bytes and veto_train_workspace_bytes* size these from the handle's patch.  Everything behind the patch
+ * projection (token assembly, layers, head) is the same for the four. */
 typedef struct veto_config {
   int32_t struct_size;     /* sizeof(veto_config_t), for ABI evolution */
   int32_t dim;             /* T_INPUT_DIM; must be 576 (model_veto.py:105-113 force it) */
   int32_t layers;          /* ENC_LAYERS */
   int32_t heads;           /* NHEADS; must divide 576 with 576/heads % 4 == 0 */
-  int32_t patch;           /* PATCH_SIZE; must be 2 */
+  int32_t patch;           /* PATCH_SIZE p: 1, 2, 3 or 4 */
   int32_t channels;        /* ROI channels per modality; must be 256 */
-  int32_t resolution;      /* POOLER_RESOLUTION; must be 8 */
+  int32_t resolution;      /* POOLER_RESOLUTION; must be 4 * patch (4, 8, 12 or 16) */
   int32_t num_obj_cls;     /* 151 (VG) / 201 (GQA); <= 256 */
   int32_t embed_dim;       /* 200 */
   int32_t num_out;         /* head width: num_rel_cls (51/101) or sum_k (g_k + 2) for MEET */
@@ -98,8 +112,8 @@ typedef struct veto_inputs {
   int32_t n_obj;              /* total objects over the batch */
   int32_t n_pair;             /* total pairs over the batch */
   int32_t n_img;              /* images in the batch */
-  const float* roi_rgb;       /* device [n_obj, 256, 8, 8]  roi_features        (relation_head.py:140-141) */
-  const float* roi_depth;     /* device [n_obj, 256, 8, 8]  roi_depth_features                              */
+  const float* roi_rgb;       /* device [n_obj, 256, R, R]  roi_features        (relation_head.py:140-141); R = the handle's resolution */
+  const float* roi_depth;     /* device [n_obj, 256, R, R]  roi_depth_features                              */
   const float* boxes;         /* device [n_obj, 4]  BoxList.bbox */
   int32_t box_mode;           /* 0 = xyxy, 1 = xywh (BoxList.mode) */
   int32_t reserved0;
@@ -825,7 +839,7 @@ typedef struct veto_roi_pool_args {
   int32_t n_img, n_roi;
   int32_t channels;               /* of the pyramid maps (256) */
   int32_t depth_channels;         /* of the depth map (256); ignored when depth_feat is NULL */
-  int32_t pooled;                 /* POOLER_RESOLUTION (8); 1..8 */
+  int32_t pooled;                 /* POOLER_RESOLUTION (8); 1..16, with pooled * sampling_ratio <= 32 */
   int32_t sampling_ratio;         /* POOLER_SAMPLING_RATIO (2); 1..4 (0 = adaptive is not built) */
   const float* level_feat[4];     /* device [n_img, channels, level_h[l], level_w[l]], finest level first */
   int32_t level_h[4];
@@ -861,7 +875,8 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const
  *                                  each operation rounded to float32 (no fused multiply-add), as in veto_roi_pool_backward,
  * over (r, ph, pw, iy, ix, tap) in lexicographic order, restricted to the valid samples' taps that land on (y, x) and -- for a pyramid
  * map -- to the ROIs of image b that the float32 LevelMapper of veto_roi_pool assigns to that level (the depth map takes every ROI of
- * image b).  Taps that coincide at the far edge (low index == high index) both count, in tap order.
+ * image b).  Taps that coincide at the far edge (low index == high index) both count, in tap order.  pooled 9..16 changes nothing in
+ * this: ph and pw run over 0 .. pooled - 1 in the same lexicographic order, whichever lane of veto_roi_pool computed the bin.
  * Not promised: the bits of veto_roi_pool_backward (whose order varies), equality across library builds or device models. */
 int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
                                    float* const* level_grad, float* depth_grad);
@@ -1223,8 +1238,8 @@ typedef struct veto_train_opts {
   int32_t struct_size;
   float p_pos, p_emb, p_attn;
   uint64_t seed;
-  /* veto_backward only, optional (NULL = not wanted): gradients of the loss w.r.t. the ROI maps, device [n_obj, 256, 8, 8]
-   * fp32 each.  The reference trains its depth backbone through roi_depth_features (tools/relation_train_net.py:166-170). */
+  /* veto_backward only, optional (NULL = not wanted): gradients of the loss w.r.t. the ROI maps, device [n_obj, 256, R, R]
+   * (R = the handle's resolution) fp32 each.  The reference trains its depth backbone through roi_depth_features (tools/relation_train_net.py:166-170). */
   float* d_roi_rgb;
   float* d_roi_depth;
   /* Ordered mode (0 = off: the default kernels, workspace and bits).  Read only when struct_size covers it: a caller built against

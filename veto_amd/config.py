@@ -28,7 +28,7 @@ def default_config():
     rh.PREDICTOR = "VETOPredictor"
     rh.USE_GT_BOX = True
     rh.USE_GT_OBJECT_LABEL = True
-    rh.POOLER_RESOLUTION = 8                      # VETO_final.yaml:57
+    rh.POOLER_RESOLUTION = 8                      # VETO_final.yaml:57; 4 * PATCH_SIZE (predictor.SUPPORTED_PATCH_GRIDS)
     rh.MAX_PROPOSAL_PAIR = 2048
     rh.BATCH_SIZE_PER_IMAGE = 1024                # VETO_final.yaml:64
     rh.POSITIVE_FRACTION = 0.25                   # VETO_final.yaml:65

@@ -59,7 +59,7 @@ int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only) {
   if (base) {
   const std::string pe = std::string(kT) + "patch_embed.";
   HIP_TRY(launch_build_patch_weight(h->p(pe + "proj_d.weight"), h->p(pe + "proj_d.bias"), h->p(pe + "proj_v.weight"),
-                                    h->p(pe + "proj_v.bias"), h->patch_w, h->patch_bias, s));
+                                    h->p(pe + "proj_v.bias"), h->patch_w, h->patch_bias, h->cfg.patch, s));
   HIP_TRY(launch_transpose_pair_proj(h->p("location_projection.0.weight"), h->loc_wt, kPosDim, s));
   HIP_TRY(launch_transpose_pair_proj(h->p("class_projection.0.weight"), h->cls_wt, h->cfg.embed_dim, s));
   HIP_TRY(launch_transpose_head(h->p("rel_out.weight"), h->head_wt, h->cfg.num_out, s));
@@ -152,7 +152,7 @@ static size_t carve_derived(veto_handle_t h, char* base) {
   }
   int* exps = c.take<int>((size_t)L * 4 * sizeof(int));
   for (int l = 0; l < L && mixed && exps; ++l) h->layers[l].exp_m = exps + 4 * l;
-  h->patch_w = c.take<__bf16>((size_t)2 * kDim * 2048 * 4);
+  h->patch_w = c.take<__bf16>((size_t)2 * kDim * patch_feats(cfg.patch) * 4);
   h->patch_bias = c.take<float>((size_t)2 * kDim * 4);
   h->loc_wt = c.take<float>((size_t)kPosDim * 2 * kDim * 4);
   h->cls_wt = c.take<float>((size_t)E * 2 * kDim * 4);
@@ -180,8 +180,11 @@ const char* veto_version(void) { return "veto_amd 0.1 (gfx950)"; }
 int veto_create(const veto_config_t* cfg, veto_handle_t* out) {
   CHECK_STRUCT_AND(veto_config_t, cfg, out != nullptr);
   if (cfg->dim != kDim) return fail(VETO_ERR_INVALID, "T_INPUT_DIM must be 576 (proj_d 512 + proj_v 64), got %d", cfg->dim);
-  if (cfg->patch != 2 || cfg->channels != 256 || cfg->resolution != 8)
-    return fail(VETO_ERR_INVALID, "only PATCH_SIZE 2, 256 channels, POOLER_RESOLUTION 8 are supported");
+  // (the fused launches hold 19 tokens per pair: CLS, location, class and a 4 x 4 grid of patches)
+  if (cfg->patch < 1 || cfg->patch > 4 || cfg->resolution != 4 * cfg->patch || cfg->channels != 256)
+    return fail(VETO_ERR_INVALID, "POOLER_RESOLUTION %d / PATCH_SIZE %d / %d channels: supported are (4, 1), (8, 2), (12, 3), (16, 4) with 256 "
+                "channels -- the fused launches hold 19 tokens per pair, i.e. a 4 x 4 patch grid (resolution == 4 * patch)",
+                cfg->resolution, cfg->patch, cfg->channels);
   if (cfg->layers < 1 || cfg->layers > 64) return fail(VETO_ERR_INVALID, "bad ENC_LAYERS %d", cfg->layers);
   if (cfg->heads < 1 || kDim % cfg->heads != 0 || (kDim / cfg->heads) % 4 != 0)
     return fail(VETO_ERR_INVALID, "NHEADS %d must divide 576 with head dim %% 4 == 0", cfg->heads);
@@ -209,9 +212,10 @@ int veto_create(const veto_config_t* cfg, veto_handle_t* out) {
   h->add("location_projection.0.bias", kDim);
   h->add(std::string(kT) + "cls_token", kDim);
   h->add(std::string(kT) + "pos_embedding", kDim);
-  h->add(std::string(kT) + "patch_embed.proj_d.weight", (size_t)512 * 2048);
+  const size_t KP = patch_feats(cfg->patch);      // 512 p^2: cat(subject, object) x p^2 x 256 channels
+  h->add(std::string(kT) + "patch_embed.proj_d.weight", (size_t)512 * KP);
   h->add(std::string(kT) + "patch_embed.proj_d.bias", 512);
-  h->add(std::string(kT) + "patch_embed.proj_v.weight", (size_t)64 * 2048);
+  h->add(std::string(kT) + "patch_embed.proj_v.weight", (size_t)64 * KP);
   h->add(std::string(kT) + "patch_embed.proj_v.bias", 64);
   for (int l = 0; l < L; ++l) {
     h->add(lname(l, "0.norm.weight"), kDim);

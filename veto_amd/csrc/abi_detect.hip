@@ -624,10 +624,14 @@ static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArg
   CHECK_STRUCT(veto_roi_pool_args_t, a);
   if (a->n_levels < 1 || a->n_levels > 4) return fail(VETO_ERR_INVALID, "n_levels must be 1..4, got %d", a->n_levels);
   if (a->n_img <= 0 || a->n_roi <= 0 || a->channels <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_roi %d, channels %d)", a->n_img, a->n_roi, a->channels);
-  if (a->pooled < 1 || a->pooled > 8) return fail(VETO_ERR_INVALID, "pooled must be 1..8, got %d", a->pooled);
+  if (a->pooled < 1 || a->pooled > 16) return fail(VETO_ERR_INVALID, "pooled must be 1..16, got %d", a->pooled);
   if (a->sampling_ratio < 1 || a->sampling_ratio > 4)
     return fail(VETO_ERR_INVALID, "sampling_ratio must be 1..4 (adaptive sampling is not built), got %d", a->sampling_ratio);
-  if (!a->rois || (forward && !a->out_rgb)) return fail(VETO_ERR_INVALID, "missing pointer");
+  if (a->pooled * a->sampling_ratio > 32)
+    return fail(VETO_ERR_INVALID, "pooled * sampling_ratio must be at most 32 (the per-ROI axis tables), got %d x %d", a->pooled, a->sampling_ratio);
+  if (!a->rois || (forward && !a->out_rgb))
+    return fail(VETO_ERR_INVALID, "missing pointer:%s%s", !a->rois ? " rois [n_roi, 5]" : "",
+                forward && !a->out_rgb ? " out_rgb [n_roi, channels, pooled, pooled]" : "");
   const bool has_depth = forward ? a->depth_feat != nullptr : a->depth_h > 0;
   if (has_depth && ((forward && !a->out_depth) || a->depth_channels <= 0 || a->depth_h <= 0 || a->depth_w <= 0))
     return fail(VETO_ERR_INVALID, "depth map given without out_depth / sizes");

@@ -8,7 +8,7 @@ namespace {
 struct Workspace {
   int32_t *subj, *obj;
   float* lc;
-  __bf16* pa;       // patch rows, split [prow, 2*2048]
+  __bf16* pa;       // patch rows, split [prow, 2*patch_feats(p)]
   float* patch_tab;
   float* x;
   __bf16* a;        // LN(x) / attention output, split [mpad, 2*576]
@@ -22,7 +22,7 @@ struct Workspace {
 };
 
 // Carves (or, with base == nullptr, just sizes) the workspace.
-Workspace carve(char* base, int n_obj, int n_pair, int chunk) {
+Workspace carve(char* base, int n_obj, int n_pair, int chunk, int patch) {
   Workspace w;
   Carver c{base};
   const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
@@ -33,7 +33,7 @@ Workspace carve(char* base, int n_obj, int n_pair, int chunk) {
   w.subj = c.take<int32_t>((size_t)n_pair * 4);
   w.obj = c.take<int32_t>((size_t)n_pair * 4);
   w.lc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
-  w.pa = c.take<__bf16>(prow * 2 * 2048 * 2);
+  w.pa = c.take<__bf16>(prow * 2 * patch_feats(patch) * 2);
   w.patch_tab = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
   w.x = c.take<float>(mpad * kDim * 4);
   w.a = c.take<__bf16>(mpad * 2 * kDim * 2);
@@ -127,11 +127,11 @@ int object_side(veto_handle_t h, hipStream_t s, const Workspace& ws, const Forwa
     HIP_TRY(launch_obj_prep(a, s));
   }
   {
-    ProfScope ps(h, s, "patchify", 0, (double)n_obj * 2 * 256 * 64 * (4 + 4));
-    HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
+    ProfScope ps(h, s, "patchify", 0, (double)n_obj * patch_feats(h->cfg.patch) * 16 * (4 + 4));
+    HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, h->cfg.patch, s));
   }
   int rc = run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim,
-                    n_obj * 16, 2 * kDim, 2048, EPI_F32);
+                    n_obj * 16, 2 * kDim, patch_feats(h->cfg.patch), EPI_F32);
   if (rc || !p.qkv0_tables) return rc;
   const int R = n_obj * 16;
   HIP_TRY(launch_centre_split(ws.patch_tab, ws.ptab_split, R, s));
@@ -426,8 +426,8 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
   if (h->dirty || h->infer_dirty) ABI_TRY(finalize_weights(h, s));
   const int n_obj = in->n_obj, n_pair = in->n_pair;
   const int chunk = n_pair < h->chunk ? n_pair : h->chunk;
-  ABI_TRY(check_workspace(workspace, workspace_bytes, carve(nullptr, n_obj, n_pair, chunk).total, true));
-  const Workspace ws = carve((char*)workspace, n_obj, n_pair, chunk);
+  ABI_TRY(check_workspace(workspace, workspace_bytes, carve(nullptr, n_obj, n_pair, chunk, h->cfg.patch).total, true));
+  const Workspace ws = carve((char*)workspace, n_obj, n_pair, chunk, h->cfg.patch);
   const ForwardPlan p = make_plan(h, sat != nullptr);
 
   ABI_TRY(object_side(h, s, ws, p, in, dbg));
@@ -461,7 +461,7 @@ extern "C" {
 size_t veto_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair) {
   if (!h || n_obj <= 0 || n_pair <= 0) return 0;
   const int chunk = n_pair < h->chunk ? n_pair : h->chunk;
-  return carve(nullptr, n_obj, n_pair, chunk).total;
+  return carve(nullptr, n_obj, n_pair, chunk, h->cfg.patch).total;
 }
 
 int veto_forward(veto_handle_t h, void* stream, const veto_inputs_t* in, void* workspace,

@@ -36,8 +36,8 @@ struct TrainWs {
                       // while its own operand, rows of 2 * 576 bf16, occupies the first third)
   float *ln_partial, *col_partial, *colp, *dgb, *head_partial;
   float *dpatch, *dlc, *dpos, *dpre, *xhat, *bn_out, *dbn_out, *emb, *demb, *prob, *dloc_wt, *dcls_wt, *dwcat_t;
-  __bf16* wcat_t;   // Wcat^T [2112, 2*1152] split rows: weight operand of the patch projection's input gradient
-  float* dpa;       // dPA [prow, 2112] fp32: gradient w.r.t. the patch rows
+  __bf16* wcat_t;   // Wcat^T [patch_t_rows(p), 2*1152] split rows: weight operand of the patch projection's input gradient
+  float* dpa;       // dPA [prow, patch_t_rows(p)] fp32: gradient w.r.t. the patch rows
   size_t mp2;    // padded reduction length of the weight-gradient GEMMs
   // ordered mode (veto_train_opts_t.deterministic) only, behind everything else so that the default layout and size stay what they were:
   // the split-K partial planes of the weight-gradient GEMMs, [k_splits][N][K] fp32 of the largest call; nullptr = the default (atomic) path
@@ -79,13 +79,13 @@ bool train_ln_emits_split() {
 }
 
 // The split of the weight-gradient GEMMs of the step (abi_internal.h, wgrad_split): a layer's Linear [n, k] over m rows, and the patch
-// projection's dWcat^T [2048, 1152] over the object rows
+// projection's dWcat^T [patch_feats(p), 1152] over the object rows
 WgradSplit linear_wgrad_split(int n, int k, int m) { return wgrad_split(n, k, m, 0, kWgradLinearKsteps, kWgradLinearCap); }
-WgradSplit patch_wgrad_split(int rows) { return wgrad_split(2048, 2 * kDim, rows, 0, kWgradPatchKsteps, 0); }
+WgradSplit patch_wgrad_split(int patch, int rows) { return wgrad_split(patch_feats(patch), 2 * kDim, rows, 0, kWgradPatchKsteps, 0); }
 
 // the ordered mode's planes hold the largest of them
-size_t wgrad_plane_floats(int m_tokens, int patch_rows) {
-  size_t most = patch_wgrad_split(patch_rows).plane_floats;
+size_t wgrad_plane_floats(int patch, int m_tokens, int patch_rows) {
+  size_t most = patch_wgrad_split(patch, patch_rows).plane_floats;
   for (const LayerLinear& q : kLayerLinears) most = std::max(most, linear_wgrad_split(q.N, q.K, m_tokens).plane_floats);      // (the last layer's compact rows are fewer: no more splits)
   return most;
 }
@@ -118,7 +118,8 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   w.subj = c.take<int32_t>((size_t)n_pair * 4);
   w.obj = c.take<int32_t>((size_t)n_pair * 4);
   w.lc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
-  w.pa = c.take<__bf16>(prow * 2 * 2048 * 2);
+  const int patch = h->cfg.patch;
+  w.pa = c.take<__bf16>(prow * 2 * patch_feats(patch) * 2);
   w.patch_tab = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
   w.layers.resize(L);
   const size_t cpad = (size_t)gemm_rows_padded(n_pair);
@@ -178,10 +179,10 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   w.prob = c.take<float>((size_t)n_obj * 256 * 4);
   w.dloc_wt = c.take<float>((size_t)kPosDim * 2 * kDim * 4);
   w.dcls_wt = c.take<float>((size_t)E * 2 * kDim * 4);
-  w.dwcat_t = c.take<float>((size_t)2048 * 2 * kDim * 4);
-  w.wcat_t = c.take<__bf16>((size_t)kPatchTRows * 2 * 2 * kDim * 2);
-  w.dpa = c.take<float>((size_t)gemm_rows_padded(n_obj * 16) * kPatchTRows * 4);
-  w.planes = ordered ? c.take<float>(wgrad_plane_floats((int)M, n_obj * 16) * 4) : nullptr;
+  w.dwcat_t = c.take<float>((size_t)patch_feats(patch) * 2 * kDim * 4);
+  w.wcat_t = c.take<__bf16>((size_t)patch_t_rows(patch) * 2 * 2 * kDim * 2);
+  w.dpa = c.take<float>((size_t)gemm_rows_padded(n_obj * 16) * patch_t_rows(patch) * 4);
+  w.planes = ordered ? c.take<float>(wgrad_plane_floats(patch, (int)M, n_obj * 16) * 4) : nullptr;
   w.total = c.off;
   return w;
 }
@@ -335,8 +336,8 @@ struct TrainStep {
   }
 
   int patch_projection() {
-    HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, s));
-    return run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16, 2 * kDim, 2048,
+    HIP_TRY(launch_patchify(in->roi_depth, in->roi_rgb, ws.pa, n_obj, h->cfg.patch, s));
+    return run_gemm(h, s, "gemm_patch", ws.pa, h->patch_w, h->patch_bias, nullptr, 0, ws.patch_tab, nullptr, 2 * kDim, n_obj * 16, 2 * kDim, patch_feats(h->cfg.patch),
                     EPI_F32);
   }
 
@@ -597,13 +598,13 @@ struct TrainStep {
 
   // Patch projection: patch_tab = PA . Wcat^T + bias_cat (bias only on the subject half)
   int patch_backward(const Below& b) {
-    const int R = n_obj * 16;
+    const int R = n_obj * 16, patch = h->cfg.patch, TR = patch_t_rows(patch);
     if (b.patch_w || b.maps) HIP_TRY(launch_split_rows(ws.dpatch, ws.dsplit, (size_t)R, 2 * kDim, s));
-    // dWcat^T [2048, 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch in the roles of linear_backward swapped,
+    // dWcat^T [patch_feats(p), 1152] = PA^T . dpatch: "dy" = PA (split rows), "x" = dpatch in the roles of linear_backward swapped,
     // so that the output width (1152) is a multiple of 192
     if (b.patch_w) {
-      HIP_TRY(launch_wgrad(h, s, nullptr, ws.pa, ws.dsplit, ws.zero, R, 2048, 2 * kDim, patch_wgrad_split(R), ws.dwcat_t, ws.planes));
-      HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), s));
+      HIP_TRY(launch_wgrad(h, s, nullptr, ws.pa, ws.dsplit, ws.zero, R, patch_feats(patch), 2 * kDim, patch_wgrad_split(patch, R), ws.dwcat_t, ws.planes));
+      HIP_TRY(launch_patch_weight_grad(ws.dwcat_t, G(pe + "proj_d.weight"), G(pe + "proj_v.weight"), patch, s));
     }
     // biases: column sums of the subject half of dpatch: columns 0..511 -> proj_d.bias, 512..575 -> proj_v.bias
     if (b.patch_b) {
@@ -615,12 +616,12 @@ struct TrainStep {
     // Wcat^T as the weight operand; then the inverse of patchify onto the ROI maps.  The reference's depth backbone is
     // trained through roi_depth_features (tools/relation_train_net.py:166-170).
     if (b.maps) {
-      HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, s));
+      HIP_TRY(launch_build_patch_weight_t(h->p(pe + "proj_d.weight"), h->p(pe + "proj_v.weight"), ws.wcat_t, patch, s));
       GemmArgs g{};
       g.a = ws.dsplit; g.w = ws.wcat_t; g.c = ws.dpa;
-      g.M = R; g.N = kPatchTRows; g.K = 2 * kDim; g.ldc = kPatchTRows;
+      g.M = R; g.N = TR; g.K = 2 * kDim; g.ldc = TR;
       HIP_TRY(launch_gemm_split(g, EPI_F32, 0, s));
-      HIP_TRY(launch_unpatchify(ws.dpa, kPatchTRows, opts->d_roi_depth, opts->d_roi_rgb, n_obj, s));
+      HIP_TRY(launch_unpatchify(ws.dpa, TR, opts->d_roi_depth, opts->d_roi_rgb, n_obj, patch, s));
     }
     return VETO_OK;
   }

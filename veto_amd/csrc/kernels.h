@@ -122,9 +122,14 @@ hipError_t launch_mixed_weight_rows(const float* src, __bf16* dst, size_t rows, 
 // src [M, ld] fp32 (N columns used) -> dst [N, 2*Mp] split rows of the TRANSPOSE, Mp = M rounded up to 32*mult
 // (zero padded): the operand layout of a GEMM that reduces over M (weight gradients)
 hipError_t launch_transpose_split(const float* src, long ld, int M, int N, __bf16* dst, int Mp, hipStream_t s);
-// W_cat [1152, 2*2048] split rows + bias_cat [1152] from proj_d [512,2048], proj_v [64,2048]
+// PATCH_SIZE p in 1..4 on maps of 4p x 4p (always a 4 x 4 patch grid: 16 patch tokens).  The patch features of one object row,
+// K of the patch projection: [depth 256 p^2 | rgb 256 p^2], 512 / 2048 / 4608 / 8192; and that count as GEMM output columns
+// (a multiple of the 192-column tile): 576 / 2112 / 4608 / 8256
+constexpr int patch_feats(int p) { return 512 * p * p; }
+constexpr int patch_t_rows(int p) { return (patch_feats(p) + 191) / 192 * 192; }
+// W_cat [1152, 2*K] split rows + bias_cat [1152] from proj_d [512, K], proj_v [64, K], K = patch_feats(p)
 hipError_t launch_build_patch_weight(const float* wd, const float* bd, const float* wv, const float* bv,
-                                     __bf16* dst, float* bias_cat, hipStream_t s);
+                                     __bf16* dst, float* bias_cat, int p, hipStream_t s);
 // dst[k][half*576 + j] = src[j][half*kin + k]   (src is [576, 2*kin])
 hipError_t launch_transpose_pair_proj(const float* src, float* dst, int kin, hipStream_t s);
 // dst[k][c] = src[c][k]  (src [n_out, 576])
@@ -154,8 +159,8 @@ hipError_t launch_obj_prep(const ObjPrepArgs& a, hipStream_t s);
 // training-mode BatchNorm1d(4) statistics of the box features center_xywh(boxes): out[0..3] mean, [4..7] biased
 // variance (what the batch is normalised with), [8..11] unbiased variance (what running_var is updated with)
 hipError_t launch_bn_batch_stats(const float* boxes, int box_mode, int n_obj, float* out, hipStream_t s);
-// rgb/depth [n_obj, 256, 8, 8] -> patch rows [n_obj*16, 2*2048] split rows (depth features first)
-hipError_t launch_patchify(const float* depth, const float* rgb, __bf16* dst, int n_obj, hipStream_t s);
+// rgb/depth [n_obj, 256, 4p, 4p] -> patch rows [n_obj*16, 2*patch_feats(p)] split rows (depth features first)
+hipError_t launch_patchify(const float* depth, const float* rgb, __bf16* dst, int n_obj, int p, hipStream_t s);
 
 // ---- pair stage --------------------------------------------------------------------------------
 hipError_t launch_pair_indices(const int64_t* rel_pairs, const int32_t* img_obj_off,
@@ -809,12 +814,11 @@ hipError_t launch_scatter_rows(const float* demb, const int64_t* labels, int dim
 hipError_t launch_scatter_rows_ordered(const float* demb, const int64_t* labels, int dim, float* dtable, int n, int n_table_rows,
                                        hipStream_t s);
 hipError_t launch_untranspose_pair_proj(const float* dwt, float* dw, int kin, hipStream_t s);
-hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, hipStream_t s);      // (dwd / dwv == nullptr: not written)
+hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, int p, hipStream_t s);      // (dwd / dwv == nullptr: not written)
 // Input gradient of the patch projection (training): the TRANSPOSE of the combined patch weight as a GEMM weight operand,
-// dst [kPatchTRows = 2112, 2*1152] split rows (rows 2048.. are zero: 2112 = 11 x 192 output columns), and the scatter of
-// dPA [n_obj*16, ld] fp32 (patch rows x patch features, depth features first) back onto the ROI maps [n_obj, 256, 8, 8]
-constexpr int kPatchTRows = 2112;
-hipError_t launch_build_patch_weight_t(const float* wd, const float* wv, __bf16* dst, hipStream_t s);
-hipError_t launch_unpatchify(const float* dpa, long ld, float* d_depth, float* d_rgb, int n_obj, hipStream_t s);
+// dst [patch_t_rows(p), 2*1152] split rows (rows patch_feats(p).. are zero; p = 2: 2112 = 2048 padded to 11 x 192 output columns), and
+// the scatter of dPA [n_obj*16, ld] fp32 (patch rows x patch features, depth features first) back onto the ROI maps [n_obj, 256, 4p, 4p]
+hipError_t launch_build_patch_weight_t(const float* wd, const float* wv, __bf16* dst, int p, hipStream_t s);
+hipError_t launch_unpatchify(const float* dpa, long ld, float* d_depth, float* d_rgb, int n_obj, int p, hipStream_t s);
 
 }  // namespace veto

@@ -9,7 +9,9 @@
 // in LDS and shared by every channel -- the reference recomputes it per output element.  A wave then
 // owns one channel plane at a time: its 64 lanes are the 64 output bins, so the 16 taps of a lane fall
 // in the ROI's footprint of ONE plane (L1/L2 resident after the first touch) and the store is one
-// contiguous 256-byte row of the [R, C, 8, 8] output.
+// contiguous 256-byte row of the [R, C, 8, 8] output.  pooled 9..16 (WALK): a lane walks the bins lane, lane + 64, ...
+// (ceil(P*P / 64) <= 4 of them), every pass of a wave stores the next contiguous 256 bytes of the [R, C, P, P] output; the
+// instantiation for pooled <= 8 is the one-bin-per-lane code.
 //
 // Arithmetic: float32 in the reference's operation order with FMA contraction switched off, so the result
 // is bit-identical to the CPU restatement in oracle/roi_align_oracle.py.
@@ -54,7 +56,7 @@ __device__ __forceinline__ void axis_entry(AxisTable& t, int k, float start, flo
   t.valid[k] = valid;
 }
 
-template <int G>  // G = sampling ratio (samples per bin and axis)
+template <int G, bool WALK>  // G = sampling ratio (samples per bin and axis); WALK: pooled > 8, a lane owns several bins
 __global__ __launch_bounds__(256) void roi_pool_kernel(RoiPoolArgs a) {
   __shared__ AxisTable ty, tx;
   __shared__ int s_level;
@@ -95,54 +97,58 @@ __global__ __launch_bounds__(256) void roi_pool_kernel(RoiPoolArgs a) {
   __syncthreads();
 
   const int b = (int)roi[0];
-  const int bin_id = tid & 63, wv = tid >> 6;
-  const int ph = bin_id / P, pw = bin_id % P;
-  if (bin_id >= P * P) return;
-  // this lane's G x G samples: 4 tap offsets and 4 weights each, fixed for every channel
-  int off[G * G][4];
-  float wgt[G * G][4];
-  bool ok[G * G];
+  const int wv = tid >> 6;
+  const int n_pass = WALK ? (P * P + 63) / 64 : 1;
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const int bin_id = pass * 64 + (tid & 63);
+    const int ph = bin_id / P, pw = bin_id % P;
+    if (bin_id >= P * P) return;
+    // this lane's G x G samples: 4 tap offsets and 4 weights each, fixed for every channel
+    int off[G * G][4];
+    float wgt[G * G][4];
+    bool ok[G * G];
 #pragma unroll
-  for (int iy = 0; iy < G; ++iy)
+    for (int iy = 0; iy < G; ++iy)
 #pragma unroll
-    for (int ix = 0; ix < G; ++ix) {
-      const int ky = ph * G + iy, kx = pw * G + ix, q = iy * G + ix;
-      ok[q] = ty.valid[ky] && tx.valid[kx];  // otherwise bilinear_interpolate returns 0 (:26-29)
-      const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
-      off[q][0] = ty.lo[ky] * L.W + tx.lo[kx];
-      off[q][1] = ty.lo[ky] * L.W + tx.hi[kx];
-      off[q][2] = ty.hi[ky] * L.W + tx.lo[kx];
-      off[q][3] = ty.hi[ky] * L.W + tx.hi[kx];
-      wgt[q][0] = hy * hx;  // :61
-      wgt[q][1] = hy * lx;
-      wgt[q][2] = ly * hx;
-      wgt[q][3] = ly * lx;
-    }
-  const float count = (float)(G * G);
-  const size_t plane_sz = (size_t)L.H * L.W;
-  float* out = (depth ? a.out_depth : a.out_rgb) + (size_t)r * C * P * P;
+      for (int ix = 0; ix < G; ++ix) {
+        const int ky = ph * G + iy, kx = pw * G + ix, q = iy * G + ix;
+        ok[q] = ty.valid[ky] && tx.valid[kx];  // otherwise bilinear_interpolate returns 0 (:26-29)
+        const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
+        off[q][0] = ty.lo[ky] * L.W + tx.lo[kx];
+        off[q][1] = ty.lo[ky] * L.W + tx.hi[kx];
+        off[q][2] = ty.hi[ky] * L.W + tx.lo[kx];
+        off[q][3] = ty.hi[ky] * L.W + tx.hi[kx];
+        wgt[q][0] = hy * hx;  // :61
+        wgt[q][1] = hy * lx;
+        wgt[q][2] = ly * hx;
+        wgt[q][3] = ly * lx;
+      }
+    const float count = (float)(G * G);
+    const size_t plane_sz = (size_t)L.H * L.W;
+    float* out = (depth ? a.out_depth : a.out_rgb) + (size_t)r * C * P * P;
 #pragma unroll 4
-  for (int c = c0 + wv; c < c0 + kSlab && c < C; c += 4) {
-    const float* plane = L.feat + ((size_t)b * C + c) * plane_sz;
-    float v[G * G][4];
+    for (int c = c0 + wv; c < c0 + kSlab && c < C; c += 4) {
+      const float* plane = L.feat + ((size_t)b * C + c) * plane_sz;
+      float v[G * G][4];
 #pragma unroll
-    for (int q = 0; q < G * G; ++q)
+      for (int q = 0; q < G * G; ++q)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) v[q][t] = plane[off[q][t]];
-    float acc = 0.f;
+        for (int t = 0; t < 4; ++t) v[q][t] = plane[off[q][t]];
+      float acc = 0.f;
 #pragma unroll
-    for (int q = 0; q < G * G; ++q) {
-      const float val = ((wgt[q][0] * v[q][0] + wgt[q][1] * v[q][1]) + wgt[q][2] * v[q][2]) + wgt[q][3] * v[q][3];  // :63
-      acc = acc + (ok[q] ? val : 0.f);
+      for (int q = 0; q < G * G; ++q) {
+        const float val = ((wgt[q][0] * v[q][0] + wgt[q][1] * v[q][1]) + wgt[q][2] * v[q][2]) + wgt[q][3] * v[q][3];  // :63
+        acc = acc + (ok[q] ? val : 0.f);
+      }
+      out[(size_t)c * P * P + bin_id] = acc / count;
     }
-    out[(size_t)c * P * P + bin_id] = acc / count;
   }
 }
 
 // Backward (ROIAlign_cuda.cu:178-262): every output gradient is spread over the 4 taps of each of its G x G
 // samples as top_diff * w / count, accumulated into the map gradient with atomic adds (several ROIs and bins
 // touch the same pixel).  Same mapping and the same LDS sample table as the forward kernel.
-template <int G>
+template <int G, bool WALK>
 __global__ __launch_bounds__(256) void roi_pool_backward_kernel(RoiPoolArgs a) {
   __shared__ AxisTable ty, tx;
   __shared__ int s_level;
@@ -178,40 +184,44 @@ __global__ __launch_bounds__(256) void roi_pool_backward_kernel(RoiPoolArgs a) {
   }
   __syncthreads();
   const int b = (int)roi[0];
-  const int bin_id = tid & 63, wv = tid >> 6;
-  const int ph = bin_id / P, pw = bin_id % P;
-  if (bin_id >= P * P) return;
-  int off[G * G][4];
-  float wgt[G * G][4];
-  bool ok[G * G];
+  const int wv = tid >> 6;
+  const int n_pass = WALK ? (P * P + 63) / 64 : 1;
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const int bin_id = pass * 64 + (tid & 63);
+    const int ph = bin_id / P, pw = bin_id % P;
+    if (bin_id >= P * P) return;
+    int off[G * G][4];
+    float wgt[G * G][4];
+    bool ok[G * G];
 #pragma unroll
-  for (int iy = 0; iy < G; ++iy)
+    for (int iy = 0; iy < G; ++iy)
 #pragma unroll
-    for (int ix = 0; ix < G; ++ix) {
-      const int ky = ph * G + iy, kx = pw * G + ix, q = iy * G + ix;
-      ok[q] = ty.valid[ky] && tx.valid[kx];
-      const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
-      off[q][0] = ty.lo[ky] * L.W + tx.lo[kx];
-      off[q][1] = ty.lo[ky] * L.W + tx.hi[kx];
-      off[q][2] = ty.hi[ky] * L.W + tx.lo[kx];
-      off[q][3] = ty.hi[ky] * L.W + tx.hi[kx];
-      wgt[q][0] = hy * hx;
-      wgt[q][1] = hy * lx;
-      wgt[q][2] = ly * hx;
-      wgt[q][3] = ly * lx;
-    }
-  const float count = (float)(G * G);
-  const size_t plane_sz = (size_t)L.H * L.W;
-  const float* gout = (depth ? a.gout_depth : a.gout_rgb) + (size_t)r * C * P * P;
-  for (int c = c0 + wv; c < c0 + kSlab && c < C; c += 4) {
-    float* plane = grad_map + ((size_t)b * C + c) * plane_sz;
-    const float g = gout[(size_t)c * P * P + bin_id];
-#pragma unroll
-    for (int q = 0; q < G * G; ++q)
-      if (ok[q]) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) atomicAdd(plane + off[q][t], g * wgt[q][t] / count);   // :240-243
+      for (int ix = 0; ix < G; ++ix) {
+        const int ky = ph * G + iy, kx = pw * G + ix, q = iy * G + ix;
+        ok[q] = ty.valid[ky] && tx.valid[kx];
+        const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
+        off[q][0] = ty.lo[ky] * L.W + tx.lo[kx];
+        off[q][1] = ty.lo[ky] * L.W + tx.hi[kx];
+        off[q][2] = ty.hi[ky] * L.W + tx.lo[kx];
+        off[q][3] = ty.hi[ky] * L.W + tx.hi[kx];
+        wgt[q][0] = hy * hx;
+        wgt[q][1] = hy * lx;
+        wgt[q][2] = ly * hx;
+        wgt[q][3] = ly * lx;
       }
+    const float count = (float)(G * G);
+    const size_t plane_sz = (size_t)L.H * L.W;
+    const float* gout = (depth ? a.gout_depth : a.gout_rgb) + (size_t)r * C * P * P;
+    for (int c = c0 + wv; c < c0 + kSlab && c < C; c += 4) {
+      float* plane = grad_map + ((size_t)b * C + c) * plane_sz;
+      const float g = gout[(size_t)c * P * P + bin_id];
+#pragma unroll
+      for (int q = 0; q < G * G; ++q)
+        if (ok[q]) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) atomicAdd(plane + off[q][t], g * wgt[q][t] / count);   // :240-243
+        }
+    }
   }
 }
 
@@ -359,39 +369,64 @@ __global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolA
   }
 }
 
+// pooled 1..16, sampling ratio 1..4, and an axis table of pooled * sampling_ratio <= kMaxAxis entries (the ordered kernel's bit masks too)
+bool roi_pool_sizes_ok(const RoiPoolArgs& a) {
+  return a.pooled >= 1 && a.pooled <= 16 && a.sampling_ratio >= 1 && a.sampling_ratio <= 4 && a.pooled * a.sampling_ratio <= kMaxAxis;
+}
+
 }  // namespace
 
 hipError_t launch_roi_pool(const RoiPoolArgs& a, hipStream_t s) {
-  if (a.pooled < 1 || a.pooled > 8 || a.sampling_ratio < 1 || a.sampling_ratio > 4) return hipErrorInvalidValue;
+  if (!roi_pool_sizes_ok(a)) return hipErrorInvalidValue;
   const int cmax = a.depth.feat && a.depth_channels > a.channels ? a.depth_channels : a.channels;
   dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, a.depth.feat ? 2 : 1);
+  const bool walk = a.pooled > 8;
   switch (a.sampling_ratio) {
-    case 1: VETO_LAUNCH(roi_pool_kernel<1>, grid, dim3(256), 0, s, a); break;
-    case 2: VETO_LAUNCH(roi_pool_kernel<2>, grid, dim3(256), 0, s, a); break;
-    case 3: VETO_LAUNCH(roi_pool_kernel<3>, grid, dim3(256), 0, s, a); break;
-    case 4: VETO_LAUNCH(roi_pool_kernel<4>, grid, dim3(256), 0, s, a); break;
+    case 1:
+      if (walk) VETO_LAUNCH((roi_pool_kernel<1, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<1, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 2:
+      if (walk) VETO_LAUNCH((roi_pool_kernel<2, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<2, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 3:
+      if (walk) VETO_LAUNCH((roi_pool_kernel<3, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<3, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 4: VETO_LAUNCH((roi_pool_kernel<4, false>), grid, dim3(256), 0, s, a); break;      // (pooled <= 8: 4 x 9 samples would not fit the axis table)
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
 hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s) {
-  if (a.pooled < 1 || a.pooled > 8 || a.sampling_ratio < 1 || a.sampling_ratio > 4) return hipErrorInvalidValue;
+  if (!roi_pool_sizes_ok(a)) return hipErrorInvalidValue;
   const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
   const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
   dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, with_depth ? 2 : 1);
+  const bool walk = a.pooled > 8;
   switch (a.sampling_ratio) {
-    case 1: VETO_LAUNCH(roi_pool_backward_kernel<1>, grid, dim3(256), 0, s, a); break;
-    case 2: VETO_LAUNCH(roi_pool_backward_kernel<2>, grid, dim3(256), 0, s, a); break;
-    case 3: VETO_LAUNCH(roi_pool_backward_kernel<3>, grid, dim3(256), 0, s, a); break;
-    case 4: VETO_LAUNCH(roi_pool_backward_kernel<4>, grid, dim3(256), 0, s, a); break;
+    case 1:
+      if (walk) VETO_LAUNCH((roi_pool_backward_kernel<1, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_backward_kernel<1, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 2:
+      if (walk) VETO_LAUNCH((roi_pool_backward_kernel<2, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_backward_kernel<2, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 3:
+      if (walk) VETO_LAUNCH((roi_pool_backward_kernel<3, true>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_backward_kernel<3, false>), grid, dim3(256), 0, s, a);
+      break;
+    case 4: VETO_LAUNCH((roi_pool_backward_kernel<4, false>), grid, dim3(256), 0, s, a); break;      // (pooled <= 8: 4 x 9 samples would not fit the axis table)
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
 hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s) {
-  if (a.pooled < 1 || a.pooled > 8 || a.sampling_ratio < 1 || a.sampling_ratio > 4 || n_img < 1 || n_img > 65535) return hipErrorInvalidValue;
+  if (!roi_pool_sizes_ok(a) || n_img < 1 || n_img > 65535) return hipErrorInvalidValue;
   const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
   for (int level = with_depth ? -1 : 0; level < a.n_levels; ++level) {
     const RoiLevel& L = level < 0 ? a.depth : a.lv[level];

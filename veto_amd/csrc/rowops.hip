@@ -122,37 +122,41 @@ __global__ __launch_bounds__(256) void transpose_split_kernel(const float* __res
 // proj(cat(subj, obj)) is linear, so it splits into a subject and an object partial product per
 // OBJECT (restructuring (a)).  Row j of the combined weight is one column of
 // the per-object table: [subj: depth 0..511 | rgb 512..575 | obj: depth 576..1087 | rgb 1088..1151];
-// K = [depth patch features 0..1023 | rgb patch features 1024..2047], feature = (p1*2+p2)*256 + c.
+// K = 512 p^2 patch features (kernels.h, patch_feats) = [depth 0..F-1 | rgb F..2F-1], F = 256 p^2, feature = (p1*p+p2)*256 + c
+// (p = 2: [depth 0..1023 | rgb 1024..2047]).
 // NB the crossed naming of the reference: proj_d (512 wide) acts on DEPTH, proj_v (64 wide) on RGB.
 __global__ void build_patch_weight_kernel(const float* __restrict__ wd, const float* __restrict__ bd,
                                           const float* __restrict__ wv, const float* __restrict__ bv,
-                                          __bf16* __restrict__ dst, float* __restrict__ bias_cat) {
+                                          __bf16* __restrict__ dst, float* __restrict__ bias_cat, int p) {
   const int j = blockIdx.x;  // 0..1151
   const int half = j / kDim, jj = j % kDim;
-  for (int kk = threadIdx.x; kk < 2048; kk += blockDim.x) {
-    const int mod = kk >> 10, f = kk & 1023, pp = f >> 8, c = f & 255;
+  const int F = 256 * p * p, K = 2 * F;
+  for (int kk = threadIdx.x; kk < K; kk += blockDim.x) {
+    const int mod = kk / F, f = kk - mod * F, pp = f >> 8, c = f & 255;
     float v = 0.f;
-    if (jj < 512 && mod == 0) v = wd[(size_t)jj * 2048 + pp * 512 + half * 256 + c];
-    if (jj >= 512 && mod == 1) v = wv[(size_t)(jj - 512) * 2048 + pp * 512 + half * 256 + c];
+    if (jj < 512 && mod == 0) v = wd[(size_t)jj * K + pp * 512 + half * 256 + c];
+    if (jj >= 512 && mod == 1) v = wv[(size_t)(jj - 512) * K + pp * 512 + half * 256 + c];
     __bf16 h, l;
     split_bf16(v, h, l);
-    __bf16* d = dst + (size_t)j * 4096 + split_index(kk);
+    __bf16* d = dst + (size_t)j * (2 * K) + split_index(kk);
     d[0] = h;
     d[32] = l;
   }
   if (threadIdx.x == 0) bias_cat[j] = half == 0 ? (jj < 512 ? bd[jj] : bv[jj - 512]) : 0.f;
 }
 
-// Wcat^T as a GEMM weight operand: row kk (patch feature), column j (table column) = Wcat[j][kk] of the kernel above
-__global__ void build_patch_weight_t_kernel(const float* __restrict__ wd, const float* __restrict__ wv, __bf16* __restrict__ dst) {
-  const int kk = blockIdx.x;  // 0..2111
-  const int mod = kk >> 10, f = kk & 1023, pp = f >> 8, c = f & 255;
+// Wcat^T as a GEMM weight operand: row kk (patch feature), column j (table column) = Wcat[j][kk] of the kernel above;
+// rows K .. patch_t_rows(p) - 1 (one block each, like the others) are zero
+__global__ void build_patch_weight_t_kernel(const float* __restrict__ wd, const float* __restrict__ wv, __bf16* __restrict__ dst, int p) {
+  const int kk = blockIdx.x;  // 0..patch_t_rows(p)-1
+  const int F = 256 * p * p, K = 2 * F;
+  const int mod = kk / F, f = kk - mod * F, pp = f >> 8, c = f & 255;
   for (int j = threadIdx.x; j < 2 * kDim; j += blockDim.x) {
     const int half = j / kDim, jj = j % kDim;
     float v = 0.f;
-    if (kk < 2048) {
-      if (jj < 512 && mod == 0) v = wd[(size_t)jj * 2048 + pp * 512 + half * 256 + c];
-      if (jj >= 512 && mod == 1) v = wv[(size_t)(jj - 512) * 2048 + pp * 512 + half * 256 + c];
+    if (kk < K) {
+      if (jj < 512 && mod == 0) v = wd[(size_t)jj * K + pp * 512 + half * 256 + c];
+      if (jj >= 512 && mod == 1) v = wv[(size_t)(jj - 512) * K + pp * 512 + half * 256 + c];
     }
     __bf16 h, l;
     split_bf16(v, h, l);
@@ -288,52 +292,60 @@ __global__ __launch_bounds__(256) void obj_prep_kernel(ObjPrepArgs a) {
   }
 }
 
-// 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)', p = 2, 8x8 maps, one thread per channel.
+// 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' of P x P patches on 4P x 4P maps (a 4 x 4 patch grid), one thread per channel.
+// A thread holds the whole map while it has at most 64 pixels (P <= 2), else one band of P map rows (one row of patches).
+template <int P>
 __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ depth,
                                                        const float* __restrict__ rgb,
                                                        __bf16* __restrict__ dst) {
+  constexpr int R = 4 * P, F = 256 * P * P, BAND = R * R <= 64 ? R : P;
   const int n = blockIdx.x, mod = blockIdx.y, c = threadIdx.x;
-  const float* in = (mod == 0 ? depth : rgb) + ((size_t)n * 256 + c) * 64;
-  float v[64];
+  const float* in = (mod == 0 ? depth : rgb) + ((size_t)n * 256 + c) * (R * R);
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const f32x4 t = *(const f32x4*)(in + 4 * i);
-    v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
-  }
+  for (int y0 = 0; y0 < R; y0 += BAND) {
+    float v[BAND * R];
 #pragma unroll
-  for (int y = 0; y < 8; ++y)
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const int row = n * 16 + (y >> 1) * 4 + (x >> 1);
-      const int col = mod * 1024 + ((y & 1) * 2 + (x & 1)) * 256 + c;
-      __bf16 h, l;
-      split_bf16(v[y * 8 + x], h, l);
-      __bf16* d = dst + (size_t)row * 4096 + split_index(col);
-      d[0] = h;
-      d[32] = l;
+    for (int i = 0; i < BAND * R / 4; ++i) {
+      const f32x4 t = *(const f32x4*)(in + y0 * R + 4 * i);
+      v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
     }
+#pragma unroll
+    for (int yy = 0; yy < BAND; ++yy)
+#pragma unroll
+      for (int x = 0; x < R; ++x) {
+        const int y = y0 + yy;
+        const int row = n * 16 + (y / P) * 4 + (x / P);
+        const int col = mod * F + ((y % P) * P + (x % P)) * 256 + c;
+        __bf16 h, l;
+        split_bf16(v[yy * R + x], h, l);
+        __bf16* d = dst + (size_t)row * (4 * F) + split_index(col);
+        d[0] = h;
+        d[32] = l;
+      }
+  }
 }
 
-// the inverse index map of patchify_kernel, on fp32 gradients: thread c of block (n, modality) gathers the 64 pixels of
+// the inverse index map of patchify_kernel, on fp32 gradients: thread c of block (n, modality) gathers the (4P)^2 pixels of
 // channel c from the 16 patch rows of object n (every pixel receives exactly one contribution: patches do not overlap)
+template <int P>
 __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict__ dpa, long ld, float* __restrict__ d_depth,
                                                          float* __restrict__ d_rgb) {
+  constexpr int R = 4 * P, F = 256 * P * P;
   const int n = blockIdx.x, mod = blockIdx.y, c = threadIdx.x;
   float* out = (mod == 0 ? d_depth : d_rgb);
   if (!out) return;
-  out += ((size_t)n * 256 + c) * 64;
+  out += ((size_t)n * 256 + c) * (R * R);
 #pragma unroll
-  for (int y = 0; y < 8; ++y) {
-    f32x4 lo, hi;
+  for (int y = 0; y < R; ++y) {
+    f32x4 q[P];
 #pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const int row = n * 16 + (y >> 1) * 4 + (x >> 1);
-      const int col = mod * 1024 + ((y & 1) * 2 + (x & 1)) * 256 + c;
-      const float v = dpa[(size_t)row * ld + col];
-      if (x < 4) lo[x] = v; else hi[x - 4] = v;
+    for (int x = 0; x < R; ++x) {
+      const int row = n * 16 + (y / P) * 4 + (x / P);
+      const int col = mod * F + ((y % P) * P + (x % P)) * 256 + c;
+      q[x >> 2][x & 3] = dpa[(size_t)row * ld + col];
     }
-    *(f32x4*)(out + y * 8) = lo;
-    *(f32x4*)(out + y * 8 + 4) = hi;
+#pragma unroll
+    for (int i = 0; i < P; ++i) *(f32x4*)(out + y * R + 4 * i) = q[i];
   }
 }
 
@@ -728,13 +740,21 @@ hipError_t launch_fold_blocks(const float* qkv, const float* wo, float* out, int
   return hipGetLastError();
 }
 
-hipError_t launch_build_patch_weight_t(const float* wd, const float* wv, __bf16* dst, hipStream_t s) {
-  VETO_LAUNCH(build_patch_weight_t_kernel, dim3(kPatchTRows), dim3(256), 0, s, wd, wv, dst);
+hipError_t launch_build_patch_weight_t(const float* wd, const float* wv, __bf16* dst, int p, hipStream_t s) {
+  if (p < 1 || p > 4) return hipErrorInvalidValue;
+  VETO_LAUNCH(build_patch_weight_t_kernel, dim3(patch_t_rows(p)), dim3(256), 0, s, wd, wv, dst, p);
   return hipGetLastError();
 }
 
-hipError_t launch_unpatchify(const float* dpa, long ld, float* d_depth, float* d_rgb, int n_obj, hipStream_t s) {
-  VETO_LAUNCH(unpatchify_kernel, dim3(n_obj, 2), dim3(256), 0, s, dpa, ld, d_depth, d_rgb);
+hipError_t launch_unpatchify(const float* dpa, long ld, float* d_depth, float* d_rgb, int n_obj, int p, hipStream_t s) {
+  const dim3 grid(n_obj, 2), block(256);
+  switch (p) {
+    case 1: VETO_LAUNCH(unpatchify_kernel<1>, grid, block, 0, s, dpa, ld, d_depth, d_rgb); break;
+    case 2: VETO_LAUNCH(unpatchify_kernel<2>, grid, block, 0, s, dpa, ld, d_depth, d_rgb); break;
+    case 3: VETO_LAUNCH(unpatchify_kernel<3>, grid, block, 0, s, dpa, ld, d_depth, d_rgb); break;
+    case 4: VETO_LAUNCH(unpatchify_kernel<4>, grid, block, 0, s, dpa, ld, d_depth, d_rgb); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
@@ -745,8 +765,9 @@ hipError_t launch_transpose_split(const float* src, long ld, int M, int N, __bf1
 }
 
 hipError_t launch_build_patch_weight(const float* wd, const float* bd, const float* wv, const float* bv,
-                                     __bf16* dst, float* bias_cat, hipStream_t s) {
-  VETO_LAUNCH(build_patch_weight_kernel, dim3(2 * kDim), dim3(256), 0, s, wd, bd, wv, bv, dst, bias_cat);
+                                     __bf16* dst, float* bias_cat, int p, hipStream_t s) {
+  if (p < 1 || p > 4) return hipErrorInvalidValue;
+  VETO_LAUNCH(build_patch_weight_kernel, dim3(2 * kDim), dim3(256), 0, s, wd, bd, wv, bv, dst, bias_cat, p);
   return hipGetLastError();
 }
 
@@ -778,8 +799,15 @@ hipError_t launch_obj_prep(const ObjPrepArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_patchify(const float* depth, const float* rgb, __bf16* dst, int n_obj, hipStream_t s) {
-  VETO_LAUNCH(patchify_kernel, dim3(n_obj, 2), dim3(256), 0, s, depth, rgb, dst);
+hipError_t launch_patchify(const float* depth, const float* rgb, __bf16* dst, int n_obj, int p, hipStream_t s) {
+  const dim3 grid(n_obj, 2), block(256);
+  switch (p) {
+    case 1: VETO_LAUNCH(patchify_kernel<1>, grid, block, 0, s, depth, rgb, dst); break;
+    case 2: VETO_LAUNCH(patchify_kernel<2>, grid, block, 0, s, depth, rgb, dst); break;
+    case 3: VETO_LAUNCH(patchify_kernel<3>, grid, block, 0, s, depth, rgb, dst); break;
+    case 4: VETO_LAUNCH(patchify_kernel<4>, grid, block, 0, s, depth, rgb, dst); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

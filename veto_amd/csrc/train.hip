@@ -335,15 +335,16 @@ __global__ __launch_bounds__(256) void untranspose_pair_proj_kernel(const float*
   }
 }
 
-// inverse of build_patch_weight_kernel: dWcatT [2048, 1152] (row = patch feature kk, column = table column j) ->
-// proj_d.weight.grad [512, 2048], proj_v.weight.grad [64, 2048]
-__global__ __launch_bounds__(256) void patch_weight_grad_kernel(const float* __restrict__ dwcat_t, float* __restrict__ dwd, float* __restrict__ dwv) {
+// inverse of build_patch_weight_kernel: dWcatT [K, 1152], K = 512 p^2 (row = patch feature kk, column = table column j) ->
+// proj_d.weight.grad [512, K], proj_v.weight.grad [64, K]
+__global__ __launch_bounds__(256) void patch_weight_grad_kernel(const float* __restrict__ dwcat_t, float* __restrict__ dwd, float* __restrict__ dwv, int p) {
   const int j = blockIdx.x;  // 0..1151
   const int half = j / kDim, jj = j % kDim;
-  for (int f = threadIdx.x; f < 1024; f += 256) {
+  const int F = 256 * p * p, K = 2 * F;
+  for (int f = threadIdx.x; f < F; f += 256) {
     const int pp = f >> 8, c = f & 255;
-    if (jj < 512) { if (dwd) dwd[(size_t)jj * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)f * (2 * kDim) + j]; }
-    else if (dwv) dwv[(size_t)(jj - 512) * 2048 + pp * 512 + half * 256 + c] = dwcat_t[(size_t)(1024 + f) * (2 * kDim) + j];
+    if (jj < 512) { if (dwd) dwd[(size_t)jj * K + pp * 512 + half * 256 + c] = dwcat_t[(size_t)f * (2 * kDim) + j]; }
+    else if (dwv) dwv[(size_t)(jj - 512) * K + pp * 512 + half * 256 + c] = dwcat_t[(size_t)(F + f) * (2 * kDim) + j];
   }
 }
 
@@ -471,8 +472,9 @@ hipError_t launch_untranspose_pair_proj(const float* dwt, float* dw, int kin, hi
   return hipGetLastError();
 }
 
-hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, hipStream_t s) {
-  VETO_LAUNCH(patch_weight_grad_kernel, dim3(2 * kDim), dim3(256), 0, s, dwcat_t, dwd, dwv);
+hipError_t launch_patch_weight_grad(const float* dwcat_t, float* dwd, float* dwv, int p, hipStream_t s) {
+  if (p < 1 || p > 4) return hipErrorInvalidValue;
+  VETO_LAUNCH(patch_weight_grad_kernel, dim3(2 * kDim), dim3(256), 0, s, dwcat_t, dwd, dwv, p);
   return hipGetLastError();
 }
 

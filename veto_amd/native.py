@@ -496,9 +496,9 @@ class Engine:
     """Owns one veto_handle_t. Thin: every method maps 1:1 onto a C-ABI call."""
 
     def __init__(self, layers, heads, num_obj_cls, num_out, precision=VETO_PRECISE, device=0, dim=576,
-                 embed_dim=200, max_chunk_pairs=0):
+                 embed_dim=200, max_chunk_pairs=0, patch=2, resolution=8):
         self.lib = load_library()
-        cfg = VetoConfig(ctypes.sizeof(VetoConfig), dim, layers, heads, 2, 256, 8, num_obj_cls, embed_dim,
+        cfg = VetoConfig(ctypes.sizeof(VetoConfig), dim, layers, heads, patch, 256, resolution, num_obj_cls, embed_dim,
                          num_out, precision, device, max_chunk_pairs)
         self.cfg = cfg
         h = c_void_p()

@@ -194,7 +194,7 @@ class Pooler(nn.Module):
 
 class VETOFeatureExtractor(nn.Module):
     """roi_box_feature_extractors.py:75-121: forward(x, proposals, depth_features) ->
-    (x_2d, d_2d, None, None), the pooled [sum N, 256, 8, 8] RGB / depth ROI maps."""
+    (x_2d, d_2d, None, None), the pooled [sum N, 256, R, R] RGB / depth ROI maps (R = POOLER_RESOLUTION, 1..16)."""
 
     def __init__(self, cfg, in_channels, half_out=False, cat_all_levels=False, for_relation=False):
         super().__init__()

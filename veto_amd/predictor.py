@@ -116,6 +116,21 @@ def _prenorm(dim, fn):
     return m
 
 
+# (POOLER_RESOLUTION, PATCH_SIZE) the library runs: a 4 x 4 grid of patches, so that a pair is 19 tokens (include/veto_amd.h)
+SUPPORTED_PATCH_GRIDS = ((4, 1), (8, 2), (12, 3), (16, 4))
+
+
+def patch_grid(config):
+    """(POOLER_RESOLUTION, PATCH_SIZE) of the config; ValueError naming the supported pairs for any other."""
+    rh = config.MODEL.ROI_RELATION_HEAD
+    pair = (rh.POOLER_RESOLUTION, rh.VETOTRANSFORMER.PATCH_SIZE)
+    if pair not in SUPPORTED_PATCH_GRIDS:
+        raise ValueError("veto_amd: ROI_RELATION_HEAD.POOLER_RESOLUTION %r with VETOTRANSFORMER.PATCH_SIZE %r is not supported: the fused "
+                         "launches hold 19 tokens per pair (a 4 x 4 patch grid), so (POOLER_RESOLUTION, PATCH_SIZE) must be one of %s"
+                         % (pair[0], pair[1], ", ".join("(%d, %d)" % q for q in SUPPORTED_PATCH_GRIDS)))
+    return int(pair[0]), int(pair[1])
+
+
 def _transformer_params(config, in_channels):
     vt = config.MODEL.ROI_RELATION_HEAD.VETOTRANSFORMER
     dim, patch = vt.T_INPUT_DIM, vt.PATCH_SIZE
@@ -178,6 +193,7 @@ class _NativeForward:
     def _native_init(self, config, trunk, num_obj_cls, head_modules):
         vt = config.MODEL.ROI_RELATION_HEAD.VETOTRANSFORMER
         self._layers, self._heads = int(vt.ENC_LAYERS), int(vt.NHEADS)
+        self._resolution, self._patch = patch_grid(config)
         self._num_obj_cls = num_obj_cls
         self._head_modules = head_modules
         self._num_out = sum(h.out_features for h in head_modules)
@@ -226,7 +242,8 @@ class _NativeForward:
             if self._engine is not None:
                 self._engine.close()
             self._engine = native.Engine(self._layers, self._heads, self._num_obj_cls, self._num_out,
-                                         precision=self._precision, device=idx, max_chunk_pairs=self._max_chunk)
+                                         precision=self._precision, device=idx, max_chunk_pairs=self._max_chunk,
+                                         patch=self._patch, resolution=self._resolution)
             self._engine_device = idx
             self._uploaded = None
         ver = self._weights_version()
@@ -295,13 +312,14 @@ class _NativeForward:
         """Validates the call and flattens it into a veto_inputs_t.  Returns (call, inp, n_objs, n_pairs, eng); `call` keeps the
         tensors the struct points into."""
         device = roi_features.device
+        want = (256, self._resolution, self._resolution)
+        if tuple(roi_features.shape[1:]) != want or tuple(roi_depth_features.shape[1:]) != want:
+            raise ValueError("roi features must be [N, %d, %d, %d] (POOLER_RESOLUTION %d), got %s / %s"
+                             % (want + (self._resolution, tuple(roi_features.shape), tuple(roi_depth_features.shape))))
         eng = self._ensure_engine(device)
         call = native.Launch(device, "veto_amd: the predictor runs only on a HIP device")
         n_objs = [len(p) for p in proposals]
         n_pairs = [int(p.shape[0]) for p in rel_pair_idxs]
-        if tuple(roi_features.shape[1:]) != (256, 8, 8) or tuple(roi_depth_features.shape[1:]) != (256, 8, 8):
-            raise ValueError("roi features must be [N, 256, 8, 8], got %s / %s"
-                             % (tuple(roi_features.shape), tuple(roi_depth_features.shape)))
         if roi_features.shape[0] != sum(n_objs) or roi_depth_features.shape[0] != sum(n_objs):
             raise ValueError("roi feature rows (%d) != total proposals (%d)" % (roi_features.shape[0], sum(n_objs)))
         f32 = dict(device=device, dtype=torch.float32)
@@ -464,9 +482,9 @@ class _TrainFn(torch.autograd.Function):
         d_rgb = d_dep = None
         n_obj = ctx.inp.n_obj
         if ctx.needs_input_grad[2]:
-            d_rgb = torch.empty((n_obj, 256, 8, 8), dtype=torch.float32, device=device)
+            d_rgb = torch.empty((n_obj, 256, owner._resolution, owner._resolution), dtype=torch.float32, device=device)
         if ctx.needs_input_grad[3]:
-            d_dep = torch.empty((n_obj, 256, 8, 8), dtype=torch.float32, device=device)
+            d_dep = torch.empty((n_obj, 256, owner._resolution, owner._resolution), dtype=torch.float32, device=device)
         ctx.opts.d_roi_rgb, ctx.opts.d_roi_depth = launch.ptr(d_rgb), launch.ptr(d_dep)
         if ctx.plan is None:
             launch.run("veto_backward", ctypes.byref(ctx.inp), ctypes.byref(ctx.opts), ctx.ws.data_ptr(), ctx.ws.numel(),

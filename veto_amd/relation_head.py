@@ -136,7 +136,7 @@ class VETORelationHead(nn.Module):
             p.add_field("pred_labels", lab)
 
     def forward_pooled(self, proposals, roi_features, roi_depth_features, logger=None):
-        """Same, from already pooled ROI maps [sum N, 256, 8, 8] (the rest of :104-243)."""
+        """Same, from already pooled ROI maps [sum N, 256, R, R], R = POOLER_RESOLUTION (the rest of :104-243)."""
         if self.training:
             raise NotImplementedError("forward_pooled is the test-time tail; call forward(features, proposals, targets, ...) to train")
         device = roi_features.device

@@ -100,7 +100,7 @@ def transformer_state_dict(seed, prefix, dim=576, layers=6, in_channels=256, pat
     return sd
 
 
-def trunk_state_dict(seed, prefix="", dim=576, layers=6, num_obj_cls=151, embed_dim=200):
+def trunk_state_dict(seed, prefix="", dim=576, layers=6, num_obj_cls=151, embed_dim=200, patch=2):
     """Everything VETOPredictor and the MEET Ensemble share (all keys but rel_out)."""
     sd = {}
     sd[prefix + "obj_embed2.weight"] = normal(seed, prefix + "obj_embed2.weight", (num_obj_cls, embed_dim))
@@ -119,13 +119,13 @@ def trunk_state_dict(seed, prefix="", dim=576, layers=6, num_obj_cls=151, embed_
     sd[p + "num_batches_tracked"] = np.array(1000, dtype=np.int64)
     _linear(sd, seed, prefix + "pos_embed.1", 128, 4)
     _linear(sd, seed, prefix + "location_projection.0", dim, 256)
-    sd.update(transformer_state_dict(seed, prefix + "fusion_transformer.", dim=dim, layers=layers))
+    sd.update(transformer_state_dict(seed, prefix + "fusion_transformer.", dim=dim, layers=layers, patch=patch))
     return sd
 
 
-def predictor_state_dict(seed, dim=576, layers=6, num_obj_cls=151, num_rel_cls=51):
+def predictor_state_dict(seed, dim=576, layers=6, num_obj_cls=151, num_rel_cls=51, patch=2):
     """Full state dict of the vanilla VETOPredictor."""
-    sd = trunk_state_dict(seed, "", dim, layers, num_obj_cls)
+    sd = trunk_state_dict(seed, "", dim, layers, num_obj_cls, patch=patch)
     std = math.sqrt(2.0 / (dim + num_rel_cls))  # xavier_normal_, utils/miscellaneous.py
     sd["rel_out.weight"] = normal(seed, "rel_out.weight", (num_rel_cls, dim), 0.0, std)
     sd["rel_out.bias"] = uniform(seed, "rel_out.bias", (num_rel_cls,), -0.04, 0.04)
@@ -133,12 +133,12 @@ def predictor_state_dict(seed, dim=576, layers=6, num_obj_cls=151, num_rel_cls=5
     return sd
 
 
-def meet_state_dict(seed, group_sizes, dim=576, layers=6, num_obj_cls=151, experts=0):
+def meet_state_dict(seed, group_sizes, dim=576, layers=6, num_obj_cls=151, experts=0, patch=2):
     """State dict of VETOPredictor_MEET (everything lives under `model.`).  experts=3 gives the
     ENSEMBLE_LEARNING.EXPERT_GROUP layout: `model.rel_out_group.{e}.{k}` for 3 experts x K groups, with
     `model.rel_out.{k}` the same tensors as the LAST expert's (roi_relation_predictors.py:3717-3723
     leaves `self.rel_out` bound to the last list it appended)."""
-    sd = trunk_state_dict(seed, "model.", dim, layers, num_obj_cls)
+    sd = trunk_state_dict(seed, "model.", dim, layers, num_obj_cls, patch=patch)
     del sd["model.obj_embed2.weight"]  # Ensemble has no obj_embed2 (roi_relation_predictors.py:3676)
 
     def head(name, g):
@@ -164,8 +164,13 @@ def meet_state_dict(seed, group_sizes, dim=576, layers=6, num_obj_cls=151, exper
 # ---------------------------------------------------------------------------
 
 def synthetic_batch(seed, num_images, num_objs, num_obj_cls=151, channels=256, res=8,
-                    relu_like=False):
-    """Returns a dict of numpy arrays; `num_objs` may be an int or a per-image list."""
+                    relu_like=False, patch=None, resolution=None):
+    """Returns a dict of numpy arrays; `num_objs` may be an int or a per-image list.  The ROI maps are res x res; `resolution=`
+    (POOLER_RESOLUTION) overrides `res`, and `patch=` (PATCH_SIZE) alone asks for the 4 x 4 patch grid's 4 * patch."""
+    if resolution is None and patch is not None:
+        resolution = 4 * patch
+    if resolution is not None:
+        res = int(resolution)
     if isinstance(num_objs, int):
         num_objs = [num_objs] * num_images
     total = int(sum(num_objs))

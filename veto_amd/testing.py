@@ -8,9 +8,11 @@ from .config import default_config
 from .structures import BoxList
 
 
-def make_config(layers, heads, mode="predcls", meet=False, dataset="VG", precision="mixed", max_chunk_pairs=0):
+def make_config(layers, heads, mode="predcls", meet=False, dataset="VG", precision="mixed", max_chunk_pairs=0, patch=2, resolution=8):
     cfg = default_config()
     rh = cfg.MODEL.ROI_RELATION_HEAD
+    rh.POOLER_RESOLUTION = resolution
+    rh.VETOTRANSFORMER.PATCH_SIZE = patch
     rh.PREDICTOR = "VETOPredictor_MEET" if meet else "VETOPredictor"
     rh.USE_GT_BOX = True
     rh.USE_GT_OBJECT_LABEL = (mode == "predcls")
