@@ -832,7 +832,26 @@ int veto_optim_step(void* stream, const veto_optim_args_t* args, void* workspace
  * (pysgg/modeling/roi_heads/box_head/roi_box_feature_extractors.py:75-121, pysgg/modeling/poolers.py:109-171)
  * over the legacy ROIAlign of pysgg/csrc/cuda/ROIAlign_cuda.cu:65-125 (layers/roi_align.py:12-61):
  * every ROI is pooled from ITS FPN level (LevelMapper, poolers.py:17-43) at that level's scale, the depth
- * map with the fixed pooler of level 2 (poolers.py:144-153; level 0 when there is one level).  One launch. */
+ * map with the fixed pooler of level 2 (poolers.py:144-153; level 0 when there is one level).  One launch when every map is
+ * float32 NCHW; otherwise one launch for the pyramid and one for the depth map.
+ *
+ * Map forms.  The maps are read in place in the form the four trailing fields name: an element type (level_dtype / depth_dtype:
+ * VETO_ROI_F32, VETO_ROI_F16 (IEEE binary16), VETO_ROI_BF16) and a layout (level_layout / depth_layout: VETO_ROI_NCHW, dense
+ * [n_img, C, H, W], or VETO_ROI_NHWC, dense [n_img, H, W, C] -- torch.channels_last).  All pyramid levels of one call share a type
+ * and a layout; the depth map has its own pair.  Codes outside these ranges are refused with VETO_ERR_INVALID before any launch.
+ * A call whose struct_size is offsetof(veto_roi_pool_args_t, level_dtype) -- the struct before these fields existed -- is
+ * accepted and means float32 NCHW for every map.  Maps need only the alignment of their element type: the kernels use wider
+ * accesses only where the row length in bytes and the base address allow them.
+ * Promised: an element is widened to float32 (exact for both 16-bit types) and from there the arithmetic is that of the float32
+ * NCHW form, in the same operation order without fused multiply-add.  So the pooled outputs of every form are bit-identical to
+ * the call on the float32 NCHW copy of the same values (NaN and Inf travel the same way), and the float32 NCHW form is the code
+ * it was before the fields existed.  The pooled outputs are float32, [n_roi, C, pooled, pooled], dense, whatever the map form. */
+#define VETO_ROI_F32 0
+#define VETO_ROI_F16 1
+#define VETO_ROI_BF16 2
+#define VETO_ROI_NCHW 0
+#define VETO_ROI_NHWC 1
+
 typedef struct veto_roi_pool_args {
   int32_t struct_size;
   int32_t n_levels;               /* 1..4 */
@@ -841,16 +860,21 @@ typedef struct veto_roi_pool_args {
   int32_t depth_channels;         /* of the depth map (256); ignored when depth_feat is NULL */
   int32_t pooled;                 /* POOLER_RESOLUTION (8); 1..16, with pooled * sampling_ratio <= 32 */
   int32_t sampling_ratio;         /* POOLER_SAMPLING_RATIO (2); 1..4 (0 = adaptive is not built) */
-  const float* level_feat[4];     /* device [n_img, channels, level_h[l], level_w[l]], finest level first */
+  const void* level_feat[4];      /* device [n_img, channels, level_h[l], level_w[l]] (or NHWC), finest level first */
   int32_t level_h[4];
   int32_t level_w[4];
   float level_scale[4];           /* POOLER_SCALES, e.g. 1/4, 1/8, 1/16, 1/32 */
-  const float* depth_feat;        /* device [n_img, depth_channels, depth_h, depth_w] or NULL */
+  const void* depth_feat;         /* device [n_img, depth_channels, depth_h, depth_w] (or NHWC) or NULL */
   int32_t depth_h, depth_w;
   const float* rois;              /* device [n_roi, 5]: image index, x1, y1, x2, y2 (Pooler.convert_to_roi_format) */
   float* out_rgb;                 /* out device [n_roi, channels, pooled, pooled]        -> roi_features */
   float* out_depth;               /* out device [n_roi, depth_channels, pooled, pooled]  -> roi_depth_features */
   int32_t* out_levels;            /* optional out device [n_roi]: the level each ROI was pooled from */
+  /* ---- the map forms (see above); absent from a struct of the earlier size, which means float32 NCHW ---- */
+  int32_t level_dtype;            /* VETO_ROI_F32 / F16 / BF16: element type of every level_feat[l] */
+  int32_t depth_dtype;            /* the same for depth_feat */
+  int32_t level_layout;           /* VETO_ROI_NCHW / NHWC: layout of every level_feat[l] and of every level_grad[l] */
+  int32_t depth_layout;           /* the same for depth_feat and depth_grad */
 } veto_roi_pool_args_t;
 
 int veto_roi_pool(void* stream, const veto_roi_pool_args_t* args);
@@ -861,7 +885,10 @@ int veto_roi_pool(void* stream, const veto_roi_pool_args_t* args);
  * depth_grad receive the map gradients (same shapes as the maps; ZERO-INITIALISED BY THE CALLER, accumulated
  * with atomic adds, so the summation order -- not the result up to rounding -- varies from run to run;
  * veto_roi_pool_backward_ordered below fixes the order).
- * grad_depth / depth_grad may be NULL. */
+ * grad_depth / depth_grad may be NULL.
+ * Both backward entry points read only the LAYOUT fields of `args`: the gradient maps are always float32, level_grad[l] in
+ * level_layout and depth_grad in depth_layout (for a 16-bit map the caller casts afterwards); grad_rgb / grad_depth are float32
+ * [n_roi, C, pooled, pooled] whatever the layout.  The terms are the same (g * w) / count per tap in both layouts. */
 int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
                            float* const* level_grad, float* depth_grad);
 
@@ -877,6 +904,8 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const
  * map -- to the ROIs of image b that the float32 LevelMapper of veto_roi_pool assigns to that level (the depth map takes every ROI of
  * image b).  Taps that coincide at the far edge (low index == high index) both count, in tap order.  pooled 9..16 changes nothing in
  * this: ph and pw run over 0 .. pooled - 1 in the same lexicographic order, whichever lane of veto_roi_pool computed the bin.
+ * The order is stated per pixel and does not depend on the layout: the VETO_ROI_NHWC result is the VETO_ROI_NCHW result bit for bit,
+ * permuted to [n_img, H, W, C], and every element is written in that layout too.
  * Not promised: the bits of veto_roi_pool_backward (whose order varies), equality across library builds or device models. */
 int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
                                    float* const* level_grad, float* depth_grad);

@@ -621,7 +621,17 @@ int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, 
 
 // shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
 static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
-  CHECK_STRUCT(veto_roi_pool_args_t, a);
+  // two sizes: the struct before the map-form fields (float32 NCHW) and the current one, as veto_sgg_eval does for pred_obj_offset
+  if (!a) return fail(VETO_ERR_INVALID, "veto_roi_pool_args_t is null");
+  const bool has_forms = a->struct_size == (int32_t)sizeof(veto_roi_pool_args_t);
+  if (!has_forms && a->struct_size != (int32_t)offsetof(veto_roi_pool_args_t, level_dtype))
+    return fail(VETO_ERR_INVALID, "veto_roi_pool_args_t size mismatch");
+  const int lv_dtype = has_forms ? a->level_dtype : VETO_ROI_F32, dp_dtype = has_forms ? a->depth_dtype : VETO_ROI_F32;
+  const int lv_layout = has_forms ? a->level_layout : VETO_ROI_NCHW, dp_layout = has_forms ? a->depth_layout : VETO_ROI_NCHW;
+  if (lv_dtype < VETO_ROI_F32 || lv_dtype > VETO_ROI_BF16 || dp_dtype < VETO_ROI_F32 || dp_dtype > VETO_ROI_BF16)
+    return fail(VETO_ERR_INVALID, "level_dtype / depth_dtype must be 0 (float32), 1 (float16) or 2 (bfloat16), got %d / %d", lv_dtype, dp_dtype);
+  if (lv_layout < VETO_ROI_NCHW || lv_layout > VETO_ROI_NHWC || dp_layout < VETO_ROI_NCHW || dp_layout > VETO_ROI_NHWC)
+    return fail(VETO_ERR_INVALID, "level_layout / depth_layout must be 0 (NCHW) or 1 (NHWC), got %d / %d", lv_layout, dp_layout);
   if (a->n_levels < 1 || a->n_levels > 4) return fail(VETO_ERR_INVALID, "n_levels must be 1..4, got %d", a->n_levels);
   if (a->n_img <= 0 || a->n_roi <= 0 || a->channels <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_roi %d, channels %d)", a->n_img, a->n_roi, a->channels);
   if (a->pooled < 1 || a->pooled > 16) return fail(VETO_ERR_INVALID, "pooled must be 1..16, got %d", a->pooled);
@@ -636,7 +646,13 @@ static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArg
   if (has_depth && ((forward && !a->out_depth) || a->depth_channels <= 0 || a->depth_h <= 0 || a->depth_w <= 0))
     return fail(VETO_ERR_INVALID, "depth map given without out_depth / sizes");
   RoiPoolArgs p{};
+  // the backward reads the layouts only: its gradient maps are float32
+  p.lv_dtype = forward ? lv_dtype : kRoiF32; p.depth_dtype = forward ? dp_dtype : kRoiF32;
+  p.lv_layout = lv_layout; p.depth_layout = dp_layout;
+  const uintptr_t lv_mask = p.lv_dtype == kRoiF32 ? 3 : 1, dp_mask = p.depth_dtype == kRoiF32 ? 3 : 1;
+  if (forward && has_depth && ((uintptr_t)a->depth_feat & dp_mask) != 0) return fail(VETO_ERR_INVALID, "depth_feat is not aligned to its element type");
   for (int l = 0; l < a->n_levels; ++l) {
+    if (forward && ((uintptr_t)a->level_feat[l] & lv_mask) != 0) return fail(VETO_ERR_INVALID, "level_feat[%d] is not aligned to its element type", l);
     if ((forward && !a->level_feat[l]) || a->level_h[l] <= 0 || a->level_w[l] <= 0 || !(a->level_scale[l] > 0.f))
       return fail(VETO_ERR_INVALID, "bad pyramid level %d", l);
     p.lv[l] = RoiLevel{a->level_feat[l], a->level_h[l], a->level_w[l], a->level_scale[l]};

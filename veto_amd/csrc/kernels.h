@@ -565,13 +565,18 @@ hipError_t launch_optim(const OptimArgs& a, bool norms, int apply, bool use_coef
 
 // ---- ROI feature extraction (roialign.hip) ----------------------------------------------------------
 struct RoiLevel {
-  const float* feat;             // [n_img, C, H, W]
+  const void* feat;              // [n_img, C, H, W] (NCHW) or [n_img, H, W, C] (NHWC) of the map group's element type
   int H, W;
   float scale;
 };
+enum RoiDtype { kRoiF32 = 0, kRoiF16 = 1, kRoiBF16 = 2 };      // veto_roi_pool_args_t.level_dtype / depth_dtype
+enum RoiLayout { kRoiNCHW = 0, kRoiNHWC = 1 };                 // veto_roi_pool_args_t.level_layout / depth_layout
 struct RoiPoolArgs {
   RoiLevel lv[4];                // FPN levels of the RGB pyramid, finest first
   RoiLevel depth;                // depth map (feat == nullptr: none)
+  int lv_dtype, lv_layout;       // of all pyramid levels (the gradient maps are float32 in lv_layout)
+  int depth_dtype, depth_layout; // of the depth map
+  int z0;                        // set by the launchers: blockIdx.z + z0 == 1 is the depth map (a launch of one map group)
   int n_levels, k_min, k_max;    // LevelMapper range: -log2(first scale) .. -log2(last scale)
   int n_roi, channels, depth_channels;
   int pooled, sampling_ratio;

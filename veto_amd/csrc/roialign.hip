@@ -13,6 +13,9 @@
 // (ceil(P*P / 64) <= 4 of them), every pass of a wave stores the next contiguous 256 bytes of the [R, C, P, P] output; the
 // instantiation for pooled <= 8 is the one-bin-per-lane code.
 //
+// Map forms: the above is the NCHW mapping, instantiated on the maps' element type (float32, float16, bfloat16; a load widens to
+// float32).  NHWC maps (torch.channels_last) have kernels of their own further down, with the lanes over channels.
+//
 // Arithmetic: float32 in the reference's operation order with FMA contraction switched off, so the result
 // is bit-identical to the CPU restatement in oracle/roi_align_oracle.py.
 #include "common.h"
@@ -56,44 +59,57 @@ __device__ __forceinline__ void axis_entry(AxisTable& t, int k, float start, flo
   t.valid[k] = valid;
 }
 
-template <int G, bool WALK>  // G = sampling ratio (samples per bin and axis); WALK: pooled > 8, a lane owns several bins
+// LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min; the
+// area uses the +1 pixel convention of BoxList.area() (bounding_box.py:249-259).  One level: 0.
+__device__ __forceinline__ int roi_level(const RoiPoolArgs& a, const float* roi) {
+  if (a.n_levels <= 1) return 0;
+  const float area = ((roi[3] - roi[1]) + 1.f) * ((roi[4] - roi[2]) + 1.f);
+  const float s = sqrtf(area);
+  float t = floorf(4.f + log2f(s / 224.f + 1e-6f));
+  t = fminf(fmaxf(t, (float)a.k_min), (float)a.k_max);
+  return (int)t - a.k_min;
+}
+
+// entry k2 of an ROI's two axis tables (0 .. P * G - 1: the y axis, then the x axis) on the map L
+__device__ __forceinline__ void roi_axis_pair_entry(AxisTable& ty, AxisTable& tx, const float* roi, const RoiLevel& L, int P, int G, int k2) {
+  const int n_axis = P * G;
+  const bool is_y = k2 < n_axis;
+  const int k = is_y ? k2 : k2 - n_axis;
+  // :84-98 no rounding of the scaled box; malformed ROIs become 1x1
+  const float lo_c = (is_y ? roi[2] : roi[1]) * L.scale;
+  const float hi_c = (is_y ? roi[4] : roi[3]) * L.scale;
+  const float len = fmaxf(hi_c - lo_c, 1.0f);
+  const float bin = len / (float)P;
+  axis_entry(is_y ? ty : tx, k, lo_c, bin, k / G, k % G, G, is_y ? L.H : L.W);
+}
+
+// The element types a map may have (RoiDtype).  A load widens to float32, which is exact for both 16-bit types: everything
+// after the load is the float32 arithmetic.
+struct bf16_t { unsigned short bits; };
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float widen(bf16_t v) { return __uint_as_float((unsigned)v.bits << 16); }
+
+template <int G, bool WALK, typename T>  // G = sampling ratio (samples per bin and axis); WALK: pooled > 8, a lane owns several bins; T: the maps' element type
 __global__ __launch_bounds__(256) void roi_pool_kernel(RoiPoolArgs a) {
   __shared__ AxisTable ty, tx;
   __shared__ int s_level;
   const int r = blockIdx.x, tid = threadIdx.x;
-  const bool depth = blockIdx.z == 1;
+  const bool depth = blockIdx.z + a.z0 == 1;
   const float* roi = a.rois + (size_t)r * 5;
   const int C = depth ? a.depth_channels : a.channels;
   const int c0 = blockIdx.y * kSlab;
   if (c0 >= C) return;
 
   if (tid == 0) {
-    int lvl = 0;
-    if (a.n_levels > 1) {
-      // LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min; the
-      // area uses the +1 pixel convention of BoxList.area() (bounding_box.py:249-259)
-      const float area = ((roi[3] - roi[1]) + 1.f) * ((roi[4] - roi[2]) + 1.f);
-      const float s = sqrtf(area);
-      float t = floorf(4.f + log2f(s / 224.f + 1e-6f));
-      t = fminf(fmaxf(t, (float)a.k_min), (float)a.k_max);
-      lvl = (int)t - a.k_min;
-    }
+    const int lvl = roi_level(a, roi);
     s_level = lvl;
     if (a.out_levels && !depth && blockIdx.y == 0) a.out_levels[r] = lvl;
   }
   __syncthreads();
   const RoiLevel L = depth ? a.depth : a.lv[s_level];
   const int P = a.pooled, n_axis = P * G;
-  if (tid < 2 * n_axis) {
-    const bool is_y = tid < n_axis;
-    const int k = is_y ? tid : tid - n_axis;
-    // :84-98 no rounding of the scaled box; malformed ROIs become 1x1
-    const float lo_c = (is_y ? roi[2] : roi[1]) * L.scale;
-    const float hi_c = (is_y ? roi[4] : roi[3]) * L.scale;
-    const float len = fmaxf(hi_c - lo_c, 1.0f);
-    const float bin = len / (float)P;
-    axis_entry(is_y ? ty : tx, k, lo_c, bin, k / G, k % G, G, is_y ? L.H : L.W);
-  }
+  if (tid < 2 * n_axis) roi_axis_pair_entry(ty, tx, roi, L, P, G, tid);
   __syncthreads();
 
   const int b = (int)roi[0];
@@ -126,14 +142,17 @@ __global__ __launch_bounds__(256) void roi_pool_kernel(RoiPoolArgs a) {
     const float count = (float)(G * G);
     const size_t plane_sz = (size_t)L.H * L.W;
     float* out = (depth ? a.out_depth : a.out_rgb) + (size_t)r * C * P * P;
-#pragma unroll 4
+    // four channel planes in flight; a 16-bit map at 4 x 4 samples one: its 64 taps take an address pair each (the compiler forms no
+    // base + 32-bit offset load for them), and four planes of those spilled 668 bytes per lane
+    constexpr int kPlanes = sizeof(T) == 4 || G < 4 ? 4 : 1;
+#pragma unroll kPlanes
     for (int c = c0 + wv; c < c0 + kSlab && c < C; c += 4) {
-      const float* plane = L.feat + ((size_t)b * C + c) * plane_sz;
+      const T* plane = (const T*)L.feat + ((size_t)b * C + c) * plane_sz;
       float v[G * G][4];
 #pragma unroll
       for (int q = 0; q < G * G; ++q)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) v[q][t] = plane[off[q][t]];
+        for (int t = 0; t < 4; ++t) v[q][t] = widen(plane[off[q][t]]);
       float acc = 0.f;
 #pragma unroll
       for (int q = 0; q < G * G; ++q) {
@@ -153,35 +172,17 @@ __global__ __launch_bounds__(256) void roi_pool_backward_kernel(RoiPoolArgs a) {
   __shared__ AxisTable ty, tx;
   __shared__ int s_level;
   const int r = blockIdx.x, tid = threadIdx.x;
-  const bool depth = blockIdx.z == 1;
+  const bool depth = blockIdx.z + a.z0 == 1;
   const float* roi = a.rois + (size_t)r * 5;
   const int C = depth ? a.depth_channels : a.channels;
   const int c0 = blockIdx.y * kSlab;
   if (c0 >= C) return;
-  if (tid == 0) {
-    int lvl = 0;
-    if (a.n_levels > 1) {
-      const float area = ((roi[3] - roi[1]) + 1.f) * ((roi[4] - roi[2]) + 1.f);
-      const float s = sqrtf(area);
-      float t = floorf(4.f + log2f(s / 224.f + 1e-6f));
-      t = fminf(fmaxf(t, (float)a.k_min), (float)a.k_max);
-      lvl = (int)t - a.k_min;
-    }
-    s_level = lvl;
-  }
+  if (tid == 0) s_level = roi_level(a, roi);
   __syncthreads();
   const RoiLevel L = depth ? a.depth : a.lv[s_level];
   float* grad_map = depth ? a.depth_grad : a.lv_grad[s_level];
   const int P = a.pooled, n_axis = P * G;
-  if (tid < 2 * n_axis) {
-    const bool is_y = tid < n_axis;
-    const int k = is_y ? tid : tid - n_axis;
-    const float lo_c = (is_y ? roi[2] : roi[1]) * L.scale;
-    const float hi_c = (is_y ? roi[4] : roi[3]) * L.scale;
-    const float len = fmaxf(hi_c - lo_c, 1.0f);
-    const float bin = len / (float)P;
-    axis_entry(is_y ? ty : tx, k, lo_c, bin, k / G, k % G, G, is_y ? L.H : L.W);
-  }
+  if (tid < 2 * n_axis) roi_axis_pair_entry(ty, tx, roi, L, P, G, tid);
   __syncthreads();
   const int b = (int)roi[0];
   const int wv = tid >> 6;
@@ -237,7 +238,7 @@ constexpr int kTileW = 32, kTileH = 8;
 constexpr int kRoiPass = 256;    // ROIs tested per pass, one per thread
 constexpr int kRoiStage = 8;     // ROIs whose axis tables are in LDS at once
 
-template <int G>
+template <int G, bool NHWC>      // NHWC: the gradient map is [n_img, H, W, C]; the sums and their order are the same
 __global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolArgs a, int level, int tiles_x) {   // level < 0: the depth map
   __shared__ AxisTable ty[kRoiStage], tx[kRoiStage];
   __shared__ int s_list[kRoiPass];
@@ -265,13 +266,7 @@ __global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolA
     if (r < a.n_roi) {
       const float* roi = a.rois + (size_t)r * 5;
       bool mine = (int)roi[0] == b;
-      if (mine && !depth && a.n_levels > 1) {      // LevelMapper, as roi_pool_kernel computes it
-        const float area = ((roi[3] - roi[1]) + 1.f) * ((roi[4] - roi[2]) + 1.f);
-        const float s = sqrtf(area);
-        float t = floorf(4.f + log2f(s / 224.f + 1e-6f));
-        t = fminf(fmaxf(t, (float)a.k_min), (float)a.k_max);
-        mine = (int)t - a.k_min == level;
-      }
+      if (mine && !depth && a.n_levels > 1) mine = roi_level(a, roi) == level;      // LevelMapper, as roi_pool_kernel computes it
       if (mine) {
         // a sample coordinate lies in [start, start + len]; its taps in [floor, floor + 1], clamped into the map: one pixel of margin each way
         auto reach = [](float lo_c, float hi_c, int size, int t0, int t1) {
@@ -299,14 +294,7 @@ __global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolA
       const int ns = total - i0 < kRoiStage ? total - i0 : kRoiStage;
       for (int e = tid; e < ns * 2 * n_axis; e += 256) {
         const int j = e / (2 * n_axis), k2 = e % (2 * n_axis);
-        const bool is_y = k2 < n_axis;
-        const int k = is_y ? k2 : k2 - n_axis;
-        const float* roi = a.rois + (size_t)s_list[i0 + j] * 5;
-        const float lo_c = (is_y ? roi[2] : roi[1]) * L.scale;
-        const float hi_c = (is_y ? roi[4] : roi[3]) * L.scale;
-        const float len = fmaxf(hi_c - lo_c, 1.0f);
-        const float bin = len / (float)P;
-        axis_entry(is_y ? ty[j] : tx[j], k, lo_c, bin, k / G, k % G, G, is_y ? L.H : L.W);
+        roi_axis_pair_entry(ty[j], tx[j], a.rois + (size_t)s_list[i0 + j] * 5, L, P, G, k2);
       }
       __syncthreads();
       if (live) {
@@ -361,11 +349,174 @@ __global__ __launch_bounds__(256) void roi_pool_backward_ordered_kernel(RoiPoolA
     }
   }
   if (live) {
-    float* dst = (depth ? a.depth_grad : a.lv_grad[level]) + (((size_t)b * C + c0) * L.H + y) * L.W + x;
-    const size_t plane_sz = (size_t)L.H * L.W;
+    float* base = depth ? a.depth_grad : a.lv_grad[level];
+    if constexpr (NHWC) {
+      // the pixel's slab is 32 contiguous floats.  c0 is a multiple of 32, so with C a multiple of 4 and a 16-byte aligned map every
+      // group of four is aligned and lies wholly inside or wholly outside the C channels; otherwise element by element
+      float* dst = base + (((size_t)b * L.H + y) * L.W + x) * C + c0;
+      if ((C & 3) == 0 && ((uintptr_t)base & 15) == 0) {
 #pragma unroll
-    for (int c = 0; c < kSlab; ++c)
-      if (c0 + c < C) dst[(size_t)c * plane_sz] = acc[c];
+        for (int c = 0; c < kSlab; c += 4)
+          if (c0 + c < C) *reinterpret_cast<float4*>(dst + c) = make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < kSlab; ++c)
+          if (c0 + c < C) dst[c] = acc[c];
+      }
+    } else {
+      float* dst = base + (((size_t)b * C + c0) * L.H + y) * L.W + x;
+      const size_t plane_sz = (size_t)L.H * L.W;
+#pragma unroll
+      for (int c = 0; c < kSlab; ++c)
+        if (c0 + c < C) dst[(size_t)c * plane_sz] = acc[c];
+    }
+  }
+}
+
+// ---- NHWC maps ([n_img, H, W, C], torch.channels_last) ----------------------------------------------------------------------------------
+// One tap of one bin is a contiguous channel vector, so the lanes of a wave are 64 consecutive channels: a tap is one full-line
+// load (forward; four channels per lane where alignment allows, see load_channels) or one run of 256 contiguous bytes of float
+// atomics (backward), and its offsets and weights are wave-uniform reads of the LDS axis tables.  One workgroup per (ROI, 64-channel slab); wave w takes the bins w, w + 4, ... of a pass of 64 bins.
+// The pooled tensors stay [n_roi, C, P, P]: a 64-channel x 64-bin float32 tile (padded rows, 16.25 KiB) is transposed through LDS so
+// that the global side is contiguous 256-byte rows there too.  The sampling ratio is a run-time loop here: nothing per lane depends
+// on it.  Same axis tables, level choice and operation order as the NCHW kernels above.
+constexpr int kSlabN = 64;
+
+// V consecutive channels of one pixel, widened.  V = 4 is one 16-byte (float32) or 8-byte (16-bit) load and needs that alignment:
+// the launcher takes it only where the channel count is a multiple of 4 and every map of the launch starts on such a boundary.
+template <int V, typename T>
+__device__ __forceinline__ void load_channels(const T* p, float (&v)[V]) {
+  if constexpr (V == 1) {
+    v[0] = widen(p[0]);
+  } else if constexpr (sizeof(T) == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    const uint2 q = *reinterpret_cast<const uint2*>(p);
+    T e[4];
+    __builtin_memcpy(e, &q, 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = widen(e[i]);
+  }
+}
+
+template <typename T, int V>      // V channels per lane: 1 (any map) or 4 (vector loads)
+__global__ __launch_bounds__(256) void roi_pool_nhwc_kernel(RoiPoolArgs a) {
+  __shared__ AxisTable ty, tx;
+  __shared__ int s_level;
+  __shared__ float tile[kSlabN][65];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const bool depth = blockIdx.z + a.z0 == 1;
+  const float* roi = a.rois + (size_t)r * 5;
+  const int C = depth ? a.depth_channels : a.channels;
+  const int c0 = blockIdx.y * kSlabN;
+  if (c0 >= C) return;
+  if (tid == 0) {
+    const int lvl = roi_level(a, roi);
+    s_level = lvl;
+    if (a.out_levels && !depth && blockIdx.y == 0) a.out_levels[r] = lvl;
+  }
+  __syncthreads();
+  const RoiLevel L = depth ? a.depth : a.lv[s_level];
+  const int P = a.pooled, G = a.sampling_ratio;
+  if (tid < 2 * P * G) roi_axis_pair_entry(ty, tx, roi, L, P, G, tid);
+  __syncthreads();
+
+  // kLanes lanes cover the slab's channels, V each; the workgroup works on kSlots bins at a time (V = 1: a wave per bin, the tap
+  // offsets wave-uniform; V = 4: sixteen lanes per bin, four bins per wave)
+  constexpr int kLanes = kSlabN / V, kSlots = 256 / kLanes;
+  const int b = (int)roi[0];
+  const int lane = tid & 63, wv = tid >> 6;
+  const int cl = tid % kLanes, slot = tid / kLanes;
+  const int c = c0 + cl * V;      // (V = 4: C is a multiple of 4, so c < C covers c .. c + 3)
+  const float count = (float)(G * G);
+  const T* img = (const T*)L.feat + (size_t)b * L.H * L.W * C;
+  float* out = (depth ? a.out_depth : a.out_rgb) + (size_t)r * C * P * P;
+  for (int bin0 = 0; bin0 < P * P; bin0 += 64) {
+    for (int j = slot; j < 64; j += kSlots) {
+      const int bin_id = bin0 + j;
+      if (bin_id >= P * P) break;
+      const int ph = bin_id / P, pw = bin_id % P;
+      float acc[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) acc[i] = 0.f;
+      if (c < C) {
+        for (int iy = 0; iy < G; ++iy)
+          for (int ix = 0; ix < G; ++ix) {
+            const int ky = ph * G + iy, kx = pw * G + ix;
+            if (!(ty.valid[ky] && tx.valid[kx])) continue;      // bilinear_interpolate returns 0 (:26-29); acc + 0 is acc (a sum from +0 never holds -0)
+            const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
+            const float w0 = hy * hx, w1 = hy * lx, w2 = ly * hx, w3 = ly * lx;      // :61
+            const size_t row_lo = (size_t)ty.lo[ky] * L.W, row_hi = (size_t)ty.hi[ky] * L.W;
+            float v0[V], v1[V], v2[V], v3[V];
+            load_channels<V>(img + (row_lo + tx.lo[kx]) * C + c, v0);
+            load_channels<V>(img + (row_lo + tx.hi[kx]) * C + c, v1);
+            load_channels<V>(img + (row_hi + tx.lo[kx]) * C + c, v2);
+            load_channels<V>(img + (row_hi + tx.hi[kx]) * C + c, v3);
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+              const float val = ((w0 * v0[i] + w1 * v1[i]) + w2 * v2[i]) + w3 * v3[i];      // :63
+              acc[i] = acc[i] + val;
+            }
+          }
+      }
+#pragma unroll
+      for (int i = 0; i < V; ++i) tile[cl * V + i][j] = acc[i] / count;
+    }
+    __syncthreads();
+    for (int cc = wv; cc < kSlabN; cc += 4)
+      if (c0 + cc < C && bin0 + lane < P * P) out[(size_t)(c0 + cc) * P * P + bin0 + lane] = tile[cc][lane];
+    __syncthreads();
+  }
+}
+
+// the atomic backward into NHWC gradient maps: the pooled gradients pass through the same LDS tile the other way
+__global__ __launch_bounds__(256) void roi_pool_backward_nhwc_kernel(RoiPoolArgs a) {
+  __shared__ AxisTable ty, tx;
+  __shared__ int s_level;
+  __shared__ float tile[kSlabN][65];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const bool depth = blockIdx.z + a.z0 == 1;
+  const float* roi = a.rois + (size_t)r * 5;
+  const int C = depth ? a.depth_channels : a.channels;
+  const int c0 = blockIdx.y * kSlabN;
+  if (c0 >= C) return;
+  if (tid == 0) s_level = roi_level(a, roi);
+  __syncthreads();
+  const RoiLevel L = depth ? a.depth : a.lv[s_level];
+  const int P = a.pooled, G = a.sampling_ratio;
+  if (tid < 2 * P * G) roi_axis_pair_entry(ty, tx, roi, L, P, G, tid);
+  __syncthreads();
+
+  const int b = (int)roi[0];
+  const int lane = tid & 63, wv = tid >> 6;
+  const int c = c0 + lane;
+  const float count = (float)(G * G);
+  float* img = (depth ? a.depth_grad : a.lv_grad[s_level]) + (size_t)b * L.H * L.W * C;
+  const float* gout = (depth ? a.gout_depth : a.gout_rgb) + (size_t)r * C * P * P;
+  for (int bin0 = 0; bin0 < P * P; bin0 += 64) {
+    for (int cc = wv; cc < kSlabN; cc += 4)
+      tile[cc][lane] = c0 + cc < C && bin0 + lane < P * P ? gout[(size_t)(c0 + cc) * P * P + bin0 + lane] : 0.f;
+    __syncthreads();
+    for (int j = wv; j < 64; j += 4) {
+      const int bin_id = bin0 + j;
+      if (bin_id >= P * P) break;      // (wave-uniform)
+      if (c >= C) continue;
+      const int ph = bin_id / P, pw = bin_id % P;
+      const float g = tile[lane][j];
+      for (int iy = 0; iy < G; ++iy)
+        for (int ix = 0; ix < G; ++ix) {
+          const int ky = ph * G + iy, kx = pw * G + ix;
+          if (!(ty.valid[ky] && tx.valid[kx])) continue;
+          const float hy = ty.h[ky], ly = ty.l[ky], hx = tx.h[kx], lx = tx.l[kx];
+          const size_t row_lo = (size_t)ty.lo[ky] * L.W, row_hi = (size_t)ty.hi[ky] * L.W;
+          atomicAdd(img + (row_lo + tx.lo[kx]) * C + c, g * (hy * hx) / count);      // :240-243, the taps in the NCHW kernel's order
+          atomicAdd(img + (row_lo + tx.hi[kx]) * C + c, g * (hy * lx) / count);
+          atomicAdd(img + (row_hi + tx.lo[kx]) * C + c, g * (ly * hx) / count);
+          atomicAdd(img + (row_hi + tx.hi[kx]) * C + c, g * (ly * lx) / count);
+        }
+    }
+    __syncthreads();
   }
 }
 
@@ -374,37 +525,59 @@ bool roi_pool_sizes_ok(const RoiPoolArgs& a) {
   return a.pooled >= 1 && a.pooled <= 16 && a.sampling_ratio >= 1 && a.sampling_ratio <= 4 && a.pooled * a.sampling_ratio <= kMaxAxis;
 }
 
-}  // namespace
-
-hipError_t launch_roi_pool(const RoiPoolArgs& a, hipStream_t s) {
-  if (!roi_pool_sizes_ok(a)) return hipErrorInvalidValue;
-  const int cmax = a.depth.feat && a.depth_channels > a.channels ? a.depth_channels : a.channels;
-  dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, a.depth.feat ? 2 : 1);
+// one forward launch over nz map groups (z0 = 0: the pyramid first; z0 = 1: the depth map alone) that share an element type and a layout
+template <typename T>
+hipError_t launch_roi_pool_group(const RoiPoolArgs& a, int layout, int cmax, int nz, hipStream_t s) {
+  if (layout == kRoiNHWC) {
+    // four channels per load where every pixel's channel vector of every map of this launch starts on a 4-element boundary
+    const bool levels = a.z0 == 0, with_depth = a.z0 == 1 || nz == 2;
+    uintptr_t bits = 0;
+    if (levels) {
+      bits |= (uintptr_t)a.channels * sizeof(T);
+      for (int l = 0; l < a.n_levels; ++l) bits |= (uintptr_t)a.lv[l].feat;
+    }
+    if (with_depth) bits |= (uintptr_t)a.depth_channels * sizeof(T) | (uintptr_t)a.depth.feat;
+    dim3 grid(a.n_roi, (cmax + kSlabN - 1) / kSlabN, nz);
+    if ((bits & (4 * sizeof(T) - 1)) == 0) VETO_LAUNCH((roi_pool_nhwc_kernel<T, 4>), grid, dim3(256), 0, s, a);
+    else VETO_LAUNCH((roi_pool_nhwc_kernel<T, 1>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  }
+  dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, nz);
   const bool walk = a.pooled > 8;
   switch (a.sampling_ratio) {
     case 1:
-      if (walk) VETO_LAUNCH((roi_pool_kernel<1, true>), grid, dim3(256), 0, s, a);
-      else VETO_LAUNCH((roi_pool_kernel<1, false>), grid, dim3(256), 0, s, a);
+      if (walk) VETO_LAUNCH((roi_pool_kernel<1, true, T>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<1, false, T>), grid, dim3(256), 0, s, a);
       break;
     case 2:
-      if (walk) VETO_LAUNCH((roi_pool_kernel<2, true>), grid, dim3(256), 0, s, a);
-      else VETO_LAUNCH((roi_pool_kernel<2, false>), grid, dim3(256), 0, s, a);
+      if (walk) VETO_LAUNCH((roi_pool_kernel<2, true, T>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<2, false, T>), grid, dim3(256), 0, s, a);
       break;
     case 3:
-      if (walk) VETO_LAUNCH((roi_pool_kernel<3, true>), grid, dim3(256), 0, s, a);
-      else VETO_LAUNCH((roi_pool_kernel<3, false>), grid, dim3(256), 0, s, a);
+      if (walk) VETO_LAUNCH((roi_pool_kernel<3, true, T>), grid, dim3(256), 0, s, a);
+      else VETO_LAUNCH((roi_pool_kernel<3, false, T>), grid, dim3(256), 0, s, a);
       break;
-    case 4: VETO_LAUNCH((roi_pool_kernel<4, false>), grid, dim3(256), 0, s, a); break;      // (pooled <= 8: 4 x 9 samples would not fit the axis table)
+    case 4: VETO_LAUNCH((roi_pool_kernel<4, false, T>), grid, dim3(256), 0, s, a); break;      // (pooled <= 8: 4 x 9 samples would not fit the axis table)
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s) {
-  if (!roi_pool_sizes_ok(a)) return hipErrorInvalidValue;
-  const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
-  const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
-  dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, with_depth ? 2 : 1);
+hipError_t launch_roi_pool_typed(const RoiPoolArgs& a, int dtype, int layout, int cmax, int nz, hipStream_t s) {
+  switch (dtype) {
+    case kRoiF32: return launch_roi_pool_group<float>(a, layout, cmax, nz, s);
+    case kRoiF16: return launch_roi_pool_group<_Float16>(a, layout, cmax, nz, s);
+    case kRoiBF16: return launch_roi_pool_group<bf16_t>(a, layout, cmax, nz, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_roi_pool_backward_group(const RoiPoolArgs& a, int layout, int cmax, int nz, hipStream_t s) {
+  if (layout == kRoiNHWC) {
+    VETO_LAUNCH(roi_pool_backward_nhwc_kernel, dim3(a.n_roi, (cmax + kSlabN - 1) / kSlabN, nz), dim3(256), 0, s, a);
+    return hipGetLastError();
+  }
+  dim3 grid(a.n_roi, (cmax + kSlab - 1) / kSlab, nz);
   const bool walk = a.pooled > 8;
   switch (a.sampling_ratio) {
     case 1:
@@ -425,19 +598,60 @@ hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+}  // namespace
+
+// The pyramid and the depth map share one launch (blockIdx.z) when they have one element type and one layout -- always so for
+// float32 NCHW maps; otherwise each map group gets the launch of its own form.
+hipError_t launch_roi_pool(const RoiPoolArgs& a0, hipStream_t s) {
+  if (!roi_pool_sizes_ok(a0)) return hipErrorInvalidValue;
+  RoiPoolArgs a = a0;
+  const bool with_depth = a.depth.feat != nullptr;
+  if (!with_depth || (a.lv_dtype == a.depth_dtype && a.lv_layout == a.depth_layout)) {
+    const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
+    a.z0 = 0;
+    return launch_roi_pool_typed(a, a.lv_dtype, a.lv_layout, cmax, with_depth ? 2 : 1, s);
+  }
+  a.z0 = 0;
+  hipError_t e = launch_roi_pool_typed(a, a.lv_dtype, a.lv_layout, a.channels, 1, s);
+  if (e != hipSuccess) return e;
+  a.z0 = 1;
+  return launch_roi_pool_typed(a, a.depth_dtype, a.depth_layout, a.depth_channels, 1, s);
+}
+
+hipError_t launch_roi_pool_backward(const RoiPoolArgs& a0, hipStream_t s) {
+  if (!roi_pool_sizes_ok(a0)) return hipErrorInvalidValue;
+  RoiPoolArgs a = a0;
+  const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
+  if (!with_depth || a.lv_layout == a.depth_layout) {
+    const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
+    a.z0 = 0;
+    return launch_roi_pool_backward_group(a, a.lv_layout, cmax, with_depth ? 2 : 1, s);
+  }
+  a.z0 = 0;
+  hipError_t e = launch_roi_pool_backward_group(a, a.lv_layout, a.channels, 1, s);
+  if (e != hipSuccess) return e;
+  a.z0 = 1;
+  return launch_roi_pool_backward_group(a, a.depth_layout, a.depth_channels, 1, s);
+}
+
 hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s) {
   if (!roi_pool_sizes_ok(a) || n_img < 1 || n_img > 65535) return hipErrorInvalidValue;
   const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
   for (int level = with_depth ? -1 : 0; level < a.n_levels; ++level) {
     const RoiLevel& L = level < 0 ? a.depth : a.lv[level];
     const int C = level < 0 ? a.depth_channels : a.channels;
+    const bool nhwc = (level < 0 ? a.depth_layout : a.lv_layout) == kRoiNHWC;
     const int tiles_x = (L.W + kTileW - 1) / kTileW, tiles_y = (L.H + kTileH - 1) / kTileH;
     dim3 grid((unsigned)tiles_x * tiles_y, n_img, (C + kSlab - 1) / kSlab);
-    switch (a.sampling_ratio) {
-      case 1: VETO_LAUNCH(roi_pool_backward_ordered_kernel<1>, grid, dim3(256), 0, s, a, level, tiles_x); break;
-      case 2: VETO_LAUNCH(roi_pool_backward_ordered_kernel<2>, grid, dim3(256), 0, s, a, level, tiles_x); break;
-      case 3: VETO_LAUNCH(roi_pool_backward_ordered_kernel<3>, grid, dim3(256), 0, s, a, level, tiles_x); break;
-      default: VETO_LAUNCH(roi_pool_backward_ordered_kernel<4>, grid, dim3(256), 0, s, a, level, tiles_x); break;
+    switch (a.sampling_ratio * 2 + (nhwc ? 1 : 0)) {
+      case 2: VETO_LAUNCH((roi_pool_backward_ordered_kernel<1, false>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 3: VETO_LAUNCH((roi_pool_backward_ordered_kernel<1, true>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 4: VETO_LAUNCH((roi_pool_backward_ordered_kernel<2, false>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 5: VETO_LAUNCH((roi_pool_backward_ordered_kernel<2, true>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 6: VETO_LAUNCH((roi_pool_backward_ordered_kernel<3, false>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 7: VETO_LAUNCH((roi_pool_backward_ordered_kernel<3, true>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      case 8: VETO_LAUNCH((roi_pool_backward_ordered_kernel<4, false>), grid, dim3(256), 0, s, a, level, tiles_x); break;
+      default: VETO_LAUNCH((roi_pool_backward_ordered_kernel<4, true>), grid, dim3(256), 0, s, a, level, tiles_x); break;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

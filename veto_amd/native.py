@@ -196,7 +196,13 @@ class VetoRoiPoolArgs(Structure):
                [("level_feat", c_void_p * 4), ("level_h", c_int32 * 4), ("level_w", c_int32 * 4),
                 ("level_scale", ctypes.c_float * 4), ("depth_feat", c_void_p), ("depth_h", c_int32),
                 ("depth_w", c_int32), ("rois", c_void_p), ("out_rgb", c_void_p), ("out_depth", c_void_p),
-                ("out_levels", c_void_p)]
+                ("out_levels", c_void_p)] + \
+               [(n, c_int32) for n in ("level_dtype", "depth_dtype", "level_layout", "depth_layout")]
+
+
+VETO_ROI_F32, VETO_ROI_F16, VETO_ROI_BF16 = 0, 1, 2   # veto_roi_pool_args_t.level_dtype / depth_dtype
+VETO_ROI_NCHW, VETO_ROI_NHWC = 0, 1                    # veto_roi_pool_args_t.level_layout / depth_layout
+ROI_POOL_ARGS_SIZE_V1 = VetoRoiPoolArgs.level_dtype.offset   # the struct before the map-form fields: means float32 NCHW
 
 
 class VetoSggEvalArgs(Structure):

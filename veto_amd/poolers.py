@@ -7,7 +7,8 @@ Host-side mirror of the reference's
   * `VETOFeatureExtractor`     pysgg/modeling/roi_heads/box_head/roi_box_feature_extractors.py:75-121
 with the same constructor arguments, call signatures and return values.  All arithmetic runs in
 libveto_amd.so (veto_roi_pool): one launch pools every ROI from its own FPN level and the depth map with
-the fixed 1/16 pooler; differentiable w.r.t. the maps (veto_roi_pool_backward, the atomic-add scatter of
+the fixed 1/16 pooler; dense NCHW or channels_last maps of float32, float16 or bfloat16 are read in place (anything else is
+first copied to float32 NCHW), and their gradients come back in the leaf's dtype and memory format; differentiable w.r.t. the maps (veto_roi_pool_backward, the atomic-add scatter of
 ROIAlign_cuda.cu:178-262).  Union pooling
 (7x7, Pooler.forward(union=True)) and cat_all_levels=True are not used by VETO and raise."""
 import ctypes
@@ -33,47 +34,102 @@ def _pool_args(call, feats, scales, rois, n_img, pooled, sampling_ratio, depth_s
     return a
 
 
+_DTYPE_CODES = {torch.float32: native.VETO_ROI_F32, torch.float16: native.VETO_ROI_F16, torch.bfloat16: native.VETO_ROI_BF16}
+_NCHW, _NHWC = native.VETO_ROI_NCHW, native.VETO_ROI_NHWC
+# Which map forms (dtype code, layout code) each entry point takes in place; every other form goes through the float32 NCHW copy.
+# Decided per form by measurement against copy-then-pool (profiles/roi_layouts.txt states the times and what follows from them).
+IN_PLACE = {
+    "forward": {(d, l) for d in _DTYPE_CODES.values() for l in (_NCHW, _NHWC)},
+    "backward": {_NCHW, _NHWC},            # the gradient maps' layout (they are float32 whatever the maps were)
+    "backward_ordered": {_NCHW, _NHWC},
+}
+
+
+def _map_form(maps):
+    """(dtype code, layout code) when every map of the group is dense in one and the same memory format and of one dtype the
+    kernels read; None otherwise (strided views, mixed formats, float64, ...).  Where both formats hold (C == 1 or
+    H == W == 1) this is NCHW."""
+    code = _DTYPE_CODES.get(maps[0].dtype)
+    if code is None or any(m.dtype != maps[0].dtype or m.dim() != 4 for m in maps):
+        return None
+    if all(m.is_contiguous() for m in maps):
+        return code, _NCHW
+    if all(m.is_contiguous(memory_format=torch.channels_last) for m in maps):
+        return code, _NHWC
+    return None
+
+
+def _in_place(maps, device):
+    """(the maps as the call reads them, (dtype code, layout code)): in place when their form is dispatched that way, else the
+    dense float32 NCHW copies."""
+    form = _map_form(maps)
+    if form is not None and form in IN_PLACE["forward"] and all(m.device == device for m in maps):
+        return [m.detach() for m in maps], form
+    return [m.detach().to(device=device, dtype=torch.float32).contiguous() for m in maps], (native.VETO_ROI_F32, _NCHW)
+
+
 def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=None, want_levels=False):
     device = rois.device
     call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
-    feats = [f.detach().to(**f32).contiguous() for f in level_feats]
+    feats, (level_dtype, level_layout) = _in_place(list(level_feats), device)
     rois = rois.detach().to(**f32).contiguous()
     n_roi, C = rois.shape[0], feats[0].shape[1]
     for l, f in enumerate(feats):
         if f.shape[0] != n_img or f.shape[1] != C:
             raise ValueError("pyramid level %d has shape %s, expected [%d, %d, H, W]" % (l, tuple(f.shape), n_img, C))
+    depth_dtype, depth_layout = native.VETO_ROI_F32, _NCHW
     if depth is not None:
-        depth = depth.detach().to(**f32).contiguous()
+        (depth,), (depth_dtype, depth_layout) = _in_place([depth], device)
     out_rgb = torch.empty((n_roi, C, pooled, pooled), **f32)
     out_depth = None
     if depth is not None:
         out_depth = torch.empty((n_roi, depth.shape[1], pooled, pooled), **f32)
     levels = torch.empty(n_roi, dtype=torch.int32, device=device) if want_levels else None
     a = _pool_args(call, feats, scales, rois, n_img, pooled, sampling_ratio, tuple(depth.shape) if depth is not None else None,
-                   depth_feat=depth, out_rgb=out_rgb, out_depth=out_depth, out_levels=levels)
+                   depth_feat=depth, out_rgb=out_rgb, out_depth=out_depth, out_levels=levels, level_dtype=level_dtype,
+                   level_layout=level_layout, depth_dtype=depth_dtype, depth_layout=depth_layout)
     call.run("veto_roi_pool", ctypes.byref(a))
     return out_rgb, out_depth, levels
 
 
-def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb, depth_shape, grad_depth, ordered=False):
-    """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None).  ordered: through
-    veto_roi_pool_backward_ordered, which fixes the summation order and writes every element itself."""
+def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb, depth_shape, grad_depth, ordered=False,
+                       level_layout=_NCHW, depth_layout=_NCHW):
+    """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None), float32 and dense in
+    level_layout / depth_layout (NHWC: torch.channels_last).  ordered: through veto_roi_pool_backward_ordered, which fixes the
+    summation order and writes every element itself."""
     device = rois.device
     call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
     rois = rois.detach().to(**f32).contiguous()
-    a = _pool_args(call, shapes, scales, rois, n_img, pooled, sampling_ratio, depth_shape if grad_depth is not None else None)
+    a = _pool_args(call, shapes, scales, rois, n_img, pooled, sampling_ratio, depth_shape if grad_depth is not None else None,
+                   level_layout=level_layout, depth_layout=depth_layout)
     grad_rgb = grad_rgb.detach().to(**f32).contiguous()
-    make = torch.empty if ordered else torch.zeros
-    level_grads = [make(shape, **f32) for shape in shapes]
+    formats = {_NCHW: torch.contiguous_format, _NHWC: torch.channels_last}
+
+    def make(shape, memory_format):      # (torch.zeros takes no memory_format)
+        g = torch.empty(shape, memory_format=memory_format, **f32)
+        return g if ordered else g.zero_()
+
+    level_grads = [make(shape, memory_format=formats[level_layout]) for shape in shapes]
     ptrs = (ctypes.c_void_p * 4)(*[g.data_ptr() for g in level_grads])
     depth_grad = None
     if grad_depth is not None:
         grad_depth = grad_depth.detach().to(**f32).contiguous()
-        depth_grad = make(depth_shape, **f32)
+        depth_grad = make(depth_shape, memory_format=formats[depth_layout])
     call.run("veto_roi_pool_backward_ordered" if ordered else "veto_roi_pool_backward", ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
     return level_grads, depth_grad
+
+
+_TORCH_DTYPES = {code: dtype for dtype, code in _DTYPE_CODES.items()}
+
+
+def _as_leaf(grad, form):
+    """The float32 gradient in its leaf's dtype and memory format: one cast in torch (a no-op for a float32 gradient that is
+    already in the leaf's layout).  form None: the leaf went through the conversion path and autograd does the rest, as before."""
+    if grad is None or form is None:
+        return grad
+    return grad.to(dtype=_TORCH_DTYPES[form[0]], memory_format=torch.channels_last if form[1] == _NHWC else torch.contiguous_format)
 
 
 class _RoiPoolFn(torch.autograd.Function):
@@ -87,6 +143,8 @@ class _RoiPoolFn(torch.autograd.Function):
         ctx.meta = ([tuple(f.shape) for f in feats], list(scales), n_img, pooled, sampling_ratio,
                     tuple(depth.shape) if depth is not None else None)
         ctx.ordered = ordered
+        # the leaves' forms: a group of one readable form gets its gradient back in that dtype and memory format
+        ctx.forms = (_map_form(feats), _map_form([depth]) if depth is not None else None)
         ctx.mark_non_differentiable(*([levels] if levels is not None else []))
         outs = (rgb,) + ((dep,) if dep is not None else ()) + ((levels,) if levels is not None else ())
         return outs
@@ -99,8 +157,13 @@ class _RoiPoolFn(torch.autograd.Function):
         grad_dep = grads[1] if depth_shape is not None else None
         if grad_rgb is None:
             grad_rgb = torch.zeros((rois.shape[0], shapes[0][1], pooled, pooled), device=rois.device)
+        ordered = native.ordered_mode(ctx.ordered)
+        in_place = IN_PLACE["backward_ordered" if ordered else "backward"]
+        layouts = [form[1] if form is not None and form[1] in in_place else _NCHW for form in ctx.forms]
         level_grads, depth_grad = _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb,
-                                                     depth_shape, grad_dep, ordered=native.ordered_mode(ctx.ordered))
+                                                     depth_shape, grad_dep, ordered=ordered, level_layout=layouts[0], depth_layout=layouts[1])
+        level_grads = [_as_leaf(g, ctx.forms[0]) for g in level_grads]
+        depth_grad = _as_leaf(depth_grad, ctx.forms[1])
         return (None,) * 8 + tuple(level_grads) + ((depth_grad,) if depth_shape is not None else ())
 
 

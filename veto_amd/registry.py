@@ -144,6 +144,33 @@ def install_box_loss_ops():
     return patched
 
 
+def install_pooler_ops():
+    """Point the reference's ROI pooling at the device kernels: `pysgg.layers.ROIAlign` (and `pysgg.layers.roi_align.ROIAlign`,
+    which it was imported from) become veto_amd.poolers.ROIAlign and `pysgg.modeling.poolers.Pooler` becomes veto_amd.poolers.Pooler -- the box head's 7 x 7
+    pooler included, whose `pysgg._C.roi_align_forward` has no HIP build.  Modules that bound one of the originals by name when
+    they were imported (`from pysgg.modeling.poolers import Pooler`, roi_box_feature_extractors.py:8; `from pysgg.layers import
+    ROIAlign`, poolers.py:6) are re-pointed too.  Pooler(cat_all_levels=True) and Pooler.forward(union=True) keep raising.
+    `pysgg` must be importable.  Independent of the other installers.  Returns the patched (module, name) pairs."""
+    import importlib
+    import sys
+    import types
+    from . import poolers
+    patched = []
+    for mod, name, value in (("pysgg.layers", "ROIAlign", poolers.ROIAlign),
+                             ("pysgg.modeling.poolers", "Pooler", poolers.Pooler)):
+        module = importlib.import_module(mod)
+        original = getattr(module, name)
+        if original is value:
+            continue
+        targets = [(mod, module)] + sorted((n, m) for n, m in list(sys.modules.items())
+                                           if isinstance(m, types.ModuleType) and m is not module and vars(m).get(name) is original)
+        for n, m in targets:
+            if vars(m).get(name) is original:
+                setattr(m, name, value)
+                patched.append((n, name))
+    return patched
+
+
 _SOLVER_ORIGINALS = []   # (module, name, what install_solver_ops replaced), for uninstall_solver_ops
 
 
