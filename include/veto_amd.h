@@ -1177,7 +1177,13 @@ size_t veto_debug_qkv_attn_workspace_bytes(int32_t n_pair);
  * veto_ce_loss: nn.CrossEntropyLoss(weight)(logits[rows], labels), mean reduction -- the relation loss of
  * VETOPredictor.forward (roi_relation_predictors.py:4133, BETA_LOSS weights :4057-4068) and, on a row subset with
  * group-local labels, the per-group losses of Ensemble.forward (:3842-3846).  Writes the loss (device float) and,
- * if grad is non-NULL, d loss / d logits for the selected rows [n, n_cls]. */
+ * if grad is non-NULL, d loss / d logits for the selected rows [n, n_cls].
+ * Shift invariance: the loss term and the gradient's exponent are both formed as (z - max z) - logf(sum exp(z - max z)), the row
+ * maximum and the log of the shifted sum kept apart, so the result does not depend on the offset of a row's logits (rows whose
+ * logits differ by an exactly representable shift give the same gradient bits).  Labels: a negative label is an ignored row --
+ * weight 0 in the loss, a gradient of exactly 0 whatever the weight sum (with every row ignored the loss is NaN, as torch's, and
+ * the gradient all 0); a label >= n_cls makes the loss and its gradient row NaN; valid rows under a weight sum of 0 are NaN, as in
+ * torch.  The workspace holds floats only and need not be 256-byte aligned. */
 size_t veto_ce_loss_workspace_bytes(int32_t n);
 int veto_ce_loss(void* stream, const float* logits, int64_t ld, const int64_t* labels, const float* weight,
                  const int64_t* rows, int32_t n, int32_t n_cls, float* loss, float* grad, void* workspace,

@@ -305,7 +305,8 @@ def default_hashes():
 def test_default_grid_keeps_the_parent_commits_bits():
     """(8, 2): the p = 2 instantiations do the parent's arithmetic in the parent's order.  The hashes in
     tests/golden/patchgrid_parent_hashes.txt were taken with this function from a library built from the parent commit, on an MI355X
-    (profiles/patchgrid_parity.txt says how)."""
+    (profiles/patchgrid_parity.txt says how); its two training hashes were taken again when the relation loss's gradient changed in its
+    last bits (the file and profiles/ce_loss_parity.txt say why)."""
     want = dict(line.split() for line in open(HASH_FILE) if line.strip() and not line.startswith("#"))
     got = default_hashes()
     assert set(got) == set(want)

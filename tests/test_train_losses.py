@@ -415,6 +415,14 @@ def test_ce_loss_edge_cases_follow_torch():
     # ... and its gradient row too (and, through the NaN weight sum, nothing else can be trusted either): no optimizer step on it
     loss, grad = relation_ce_loss(logits.to(dev), bad.to(dev), weight=w.to(dev), want_grad=True)
     assert torch.isnan(loss).all() and torch.isnan(grad[5]).all()
+    # every row ignored: torch's loss is NaN (0 / 0) and its gradient exactly 0; the same here, not 0 * inf
+    none = torch.full((40,), -100, dtype=torch.int64)
+    ref_in = logits.clone().requires_grad_(True)
+    ref = torch.nn.CrossEntropyLoss(weight=w)(ref_in, none)
+    ref.backward()
+    assert torch.isnan(ref) and float(ref_in.grad.abs().max()) == 0.0
+    loss, grad = relation_ce_loss(logits.to(dev), none.to(dev), weight=w.to(dev), want_grad=True)
+    assert torch.isnan(loss).all() and float(grad.abs().max()) == 0.0
 
 
 @pytest.mark.gpu

@@ -819,9 +819,9 @@ int veto_backward_plan(veto_handle_t h, void* stream, const veto_inputs_t* in, c
   return backward_impl(h, stream, in, opts, sch, workspace, workspace_bytes, dlogits, grads);
 }
 
-// workspace: lse | nll_w | w_row | inv_wsum
+// workspace: log_sum | nll_w | w_row | inv_wsum
 static size_t carve_ce_loss(Carver c, size_t n, CeLossArgs* a) {
-  a->lse = c.take<float>(n * 4);
+  a->log_sum = c.take<float>(n * 4);
   a->nll_w = c.take<float>(n * 4);
   a->w_row = c.take<float>(n * 4);
   a->inv_wsum = c.take<float>(256);

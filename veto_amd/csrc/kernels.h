@@ -699,7 +699,7 @@ struct CeLossArgs {
   const float* weight;           // [C] or nullptr
   const int64_t* rows;           // [n] row indices into logits, or nullptr = rows 0..n-1
   int n, C;
-  float *lse, *nll_w, *w_row;    // workspace [n] each
+  float *log_sum, *nll_w, *w_row;   // workspace [n] each; log_sum = logf(sum exp(z - max z)), the row maximum is NOT folded in
   float* inv_wsum;               // workspace [1]
   float* loss;                   // out [1]
   float* grad;                   // optional out [n, C]

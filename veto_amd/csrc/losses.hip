@@ -3,8 +3,8 @@
 //     VETOPredictor (roi_relation_predictors.py:4067-4068,4133; BETA_LOSS class-balanced weights :4057-4066) and,
 //     unweighted on a row subset with remapped labels, the per-group losses of Ensemble.forward (:3842-3846).
 //     loss = sum_i w[y_i] (logsumexp(z_i) - z_i[y_i]) / sum_i w[y_i]; d loss / d z_i = w[y_i] (softmax(z_i) - e_{y_i}) / sum w.
-//     One wave per row for the log-sum-exp, a fixed-order double-precision fold (deterministic), one wave per row
-//     for the gradient.
+//     One wave per row for the row maximum and the log of the shifted sum (kept apart: the result does not depend on the
+//     logits' offset), a fixed-order double-precision fold (deterministic), one wave per row for the gradient.
 //   * the expert sampling loop of VETOPredictor_MEET.forward (:3940-3969), which the reference runs in Python with one
 //     .item() per relation: here one wave walks the relations in order, consuming the SAME random stream (raw MT19937
 //     words of Python's `random`, prepared by the host: random() = two words, randint = rejection on the top bits),
@@ -16,6 +16,10 @@ namespace veto {
 
 namespace {
 
+// Cross entropy is invariant under a shift of a row's logits, and so is this kernel: the row maximum mx and log_sum = logf(sum exp(z - mx))
+// are kept apart, and both the loss term and the gradient's exponent are formed as (z - mx) - log_sum.  (One float holding
+// mx + log_sum is rounded at the size of mx: ulp(mx) / 2 of absolute error in every exponent, 3.5e-4 of the gradient at logits
+// near 1e4.)  Every rounding after z - mx happens at the size of the row's spread, whatever its offset.
 __global__ __launch_bounds__(256) void ce_rows_kernel(CeLossArgs a) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= a.n) return;
@@ -34,10 +38,10 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(CeLossArgs a) {
     const long yl = a.labels[i];
     const bool valid = yl >= 0 && yl < a.C, bad = yl >= a.C;
     const int y = valid ? (int)yl : 0;
-    const float lse = mx + logf(sum);
+    const float log_sum = logf(sum);
     const float w = valid ? (a.weight ? a.weight[y] : 1.f) : 0.f;
-    a.lse[i] = lse;
-    a.nll_w[i] = bad ? __builtin_nanf("") : valid ? w * (lse - z[y]) : 0.f;
+    a.log_sum[i] = log_sum;
+    a.nll_w[i] = bad ? __builtin_nanf("") : valid ? w * (log_sum - (z[y] - mx)) : 0.f;
     a.w_row[i] = w;
   }
 }
@@ -60,18 +64,30 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(CeLossArgs a) {
   }
 }
 
+// d loss / d z = w_row / sum w (softmax(z) - e_y), the softmax as expf((z - mx) - log_sum) with mx found again (one more pass over a
+// row of at most a few hundred values, which keeps the workspace layout).  An ignored row's gradient is exactly 0 whatever the weight
+// sum -- with every label negative 1 / sum w is inf, and 0 * inf would be NaN; torch gives 0 there.  A valid row of weight 0 under a
+// weight sum of 0 is NaN, as in torch.
 __global__ __launch_bounds__(256) void ce_grad_kernel(CeLossArgs a) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= a.n) return;
   const long r = a.rows ? a.rows[i] : i;
   const float* z = a.logits + r * a.ld;
   const long yl = a.labels[i];
-  const int y = (yl >= 0 && yl < a.C) ? (int)yl : -1;      // ignored rows have w_row = 0: zero gradient
+  const int y = (yl >= 0 && yl < a.C) ? (int)yl : -1;
+  float* g = a.grad + (size_t)i * a.C;
+  if (yl < 0) {
+    for (int c = lane; c < a.C; c += 64) g[c] = 0.f;
+    return;
+  }
+  float mx = -INFINITY;
+  for (int c = lane; c < a.C; c += 64) mx = fmaxf(mx, z[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   // a label >= C made the loss NaN (above); its gradient row is NaN too, so that an optimizer step cannot proceed on a loss that
   // never was one (torch raises in this case)
-  const float scale = yl >= a.C ? __builtin_nanf("") : a.w_row[i] * a.inv_wsum[0], lse = a.lse[i];
-  float* g = a.grad + (size_t)i * a.C;
-  for (int c = lane; c < a.C; c += 64) g[c] = (expf(z[c] - lse) - (c == y ? 1.f : 0.f)) * scale;
+  const float scale = yl >= a.C ? __builtin_nanf("") : a.w_row[i] * a.inv_wsum[0], log_sum = a.log_sum[i];
+  for (int c = lane; c < a.C; c += 64) g[c] = (expf((z[c] - mx) - log_sum) - (c == y ? 1.f : 0.f)) * scale;
 }
 
 // ---- MEET expert sampling --------------------------------------------------------------------------------
