@@ -859,7 +859,7 @@ typedef struct veto_roi_pool_args {
   int32_t channels;               /* of the pyramid maps (256) */
   int32_t depth_channels;         /* of the depth map (256); ignored when depth_feat is NULL */
   int32_t pooled;                 /* POOLER_RESOLUTION (8); 1..16, with pooled * sampling_ratio <= 32 */
-  int32_t sampling_ratio;         /* POOLER_SAMPLING_RATIO (2); 1..4 (0 = adaptive is not built) */
+  int32_t sampling_ratio;         /* POOLER_SAMPLING_RATIO (2); 1..4 (0 = the adaptive grid: veto_roi_pool_adaptive below, only there) */
   const void* level_feat[4];      /* device [n_img, channels, level_h[l], level_w[l]] (or NHWC), finest level first */
   int32_t level_h[4];
   int32_t level_w[4];
@@ -909,6 +909,35 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* args, const
  * Not promised: the bits of veto_roi_pool_backward (whose order varies), equality across library builds or device models. */
 int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
                                    float* const* level_grad, float* depth_grad);
+
+/* The adaptive sampling grid, POOLER_SAMPLING_RATIO = 0 (the default of pysgg/config/defaults.py; ROIAlign_cuda.cu:103-104): the
+ * same pooling with a grid chosen per ROI.  Entry points of their own: the three above keep every check, message and bit.
+ * `args` is the veto_roi_pool_args_t of veto_roi_pool at either accepted struct_size, with sampling_ratio == 0 REQUIRED.
+ * Accepted: pooled 1..16 (there is no axis table, so no pooled * ratio condition), 1..4 levels with the float32 LevelMapper, the
+ * depth map on its fixed level, out_levels, maps of VETO_ROI_F32 / F16 / BF16 in VETO_ROI_NCHW.
+ * Refused with VETO_ERR_INVALID before any launch: VETO_ROI_NHWC in either layout field, sampling_ratio != 0, and everything
+ * veto_roi_pool refuses (one shared argument check).
+ * Per ROI and map, in float32 with every operation rounded (no fused multiply-add), for the y axis and the x axis separately:
+ *     len = max(hi * scale - lo * scale, 1)      bin = len / pooled      g = (int)ceil(len / pooled)       (gh for y, gw for x)
+ *     sample i of bin p lies at  v = (lo * scale + p * bin) + ((i + 0.5) * bin) / g,   i = 0 .. g - 1,
+ * valid when !(v < -1 || v > size), with the clamping, tap indices and weights of veto_roi_pool.  Per bin and channel the sum starts
+ * at +0 and adds  ((w0*v0 + w1*v1) + w2*v2) + w3*v3  of every valid sample, iy outer and ix inner, sequentially; an invalid sample
+ * adds +0; the output is sum / (float)(gh * gw).  One bin's sum is never split, so the result is bit-identical to the reference's
+ * kernel and, on ROIs whose grid is (g, g), g = 1..4, to veto_roi_pool at sampling_ratio = g.
+ * Work bound: v is non-decreasing in i, so an axis of a bin has ONE contiguous range of valid samples; it is found by bisection on
+ * the same float32 expression and only the product of the two ranges is visited.  The sample spacing bin / g lies in (0.5, 1] once
+ * len >= pooled (g = 1 below that), so an axis holds at most 2 * size + 3 valid samples whatever the box: the work per ROI is bounded
+ * by the map, not by the ROI's coordinates.  Outside the contract (the call still ends within that bound): ROIs with gh * gw >= 2^31,
+ * whose count overflows in the reference too, non-finite coordinates, and coordinates so large (beyond 2^22 map pixels) that
+ * float32 cannot tell neighbouring samples apart -- an axis range longer than 2 * size + 3 samples is treated as empty.
+ * veto_roi_pool_adaptive_backward: the arguments and conventions of veto_roi_pool_backward (float32 NCHW gradient maps,
+ * ZERO-INITIALISED BY THE CALLER, atomic adds, order not fixed); per valid sample and tap it adds (g * w) / count with
+ * count = (float)(gh * gw), the terms of veto_roi_pool_backward.
+ * Not built: an ordered (bit-repeatable) backward for the adaptive grid -- veto_roi_pool_backward_ordered refuses sampling_ratio 0
+ * and the ordered mode must not fall back to this one --, VETO_ROI_NHWC maps in place, and rectangular outputs. */
+int veto_roi_pool_adaptive(void* stream, const veto_roi_pool_args_t* args);
+int veto_roi_pool_adaptive_backward(void* stream, const veto_roi_pool_args_t* args, const float* grad_rgb, const float* grad_depth,
+                                    float* const* level_grad, float* depth_grad);
 
 /* ---- relation evaluators -----------------------------------------------
  * evaluate_relation_of_one_image (pysgg/data/datasets/evaluation/vg/vg_eval.py:459-566) over the evaluator

@@ -619,8 +619,9 @@ int veto_box_loss(void* stream, const veto_box_loss_args_t* a, void* workspace, 
   return VETO_OK;
 }
 
-// shared argument check / conversion of veto_roi_pool and veto_roi_pool_backward
-static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out) {
+// shared argument check / conversion of veto_roi_pool, veto_roi_pool_backward and their adaptive-grid siblings (adaptive: the
+// sampling ratio must be 0 and the maps NCHW; everything else is checked the same way, with the same messages)
+static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArgs* out, bool adaptive = false) {
   // two sizes: the struct before the map-form fields (float32 NCHW) and the current one, as veto_sgg_eval does for pred_obj_offset
   if (!a) return fail(VETO_ERR_INVALID, "veto_roi_pool_args_t is null");
   const bool has_forms = a->struct_size == (int32_t)sizeof(veto_roi_pool_args_t);
@@ -635,10 +636,18 @@ static int roi_pool_args(const veto_roi_pool_args_t* a, bool forward, RoiPoolArg
   if (a->n_levels < 1 || a->n_levels > 4) return fail(VETO_ERR_INVALID, "n_levels must be 1..4, got %d", a->n_levels);
   if (a->n_img <= 0 || a->n_roi <= 0 || a->channels <= 0) return fail(VETO_ERR_INVALID, "bad sizes (n_img %d, n_roi %d, channels %d)", a->n_img, a->n_roi, a->channels);
   if (a->pooled < 1 || a->pooled > 16) return fail(VETO_ERR_INVALID, "pooled must be 1..16, got %d", a->pooled);
-  if (a->sampling_ratio < 1 || a->sampling_ratio > 4)
-    return fail(VETO_ERR_INVALID, "sampling_ratio must be 1..4 (adaptive sampling is not built), got %d", a->sampling_ratio);
-  if (a->pooled * a->sampling_ratio > 32)
-    return fail(VETO_ERR_INVALID, "pooled * sampling_ratio must be at most 32 (the per-ROI axis tables), got %d x %d", a->pooled, a->sampling_ratio);
+  if (adaptive) {
+    if (a->sampling_ratio != 0)
+      return fail(VETO_ERR_INVALID, "sampling_ratio must be 0 for the adaptive entry points (veto_roi_pool takes 1..4), got %d", a->sampling_ratio);
+    if (lv_layout == VETO_ROI_NHWC || dp_layout == VETO_ROI_NHWC)
+      return fail(VETO_ERR_INVALID, "VETO_ROI_NHWC is not built for the adaptive grid: level_layout / depth_layout must be VETO_ROI_NCHW, got %d / %d",
+                  lv_layout, dp_layout);
+  } else {
+    if (a->sampling_ratio < 1 || a->sampling_ratio > 4)
+      return fail(VETO_ERR_INVALID, "sampling_ratio must be 1..4 (adaptive sampling is not built), got %d", a->sampling_ratio);
+    if (a->pooled * a->sampling_ratio > 32)
+      return fail(VETO_ERR_INVALID, "pooled * sampling_ratio must be at most 32 (the per-ROI axis tables), got %d x %d", a->pooled, a->sampling_ratio);
+  }
   if (!a->rois || (forward && !a->out_rgb))
     return fail(VETO_ERR_INVALID, "missing pointer:%s%s", !a->rois ? " rois [n_roi, 5]" : "",
                 forward && !a->out_rgb ? " out_rgb [n_roi, channels, pooled, pooled]" : "");
@@ -681,9 +690,9 @@ int veto_roi_pool(void* stream, const veto_roi_pool_args_t* a) {
 }
 
 static int roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
-                             float* const* level_grad, float* depth_grad, bool ordered) {
+                             float* const* level_grad, float* depth_grad, bool ordered, bool adaptive = false) {
   RoiPoolArgs p{};
-  ABI_TRY(roi_pool_args(a, false, &p));
+  ABI_TRY(roi_pool_args(a, false, &p, adaptive));
   if (!grad_rgb || !level_grad) return fail(VETO_ERR_INVALID, "missing gradient pointer");
   for (int l = 0; l < p.n_levels; ++l) {
     if (!level_grad[l]) return fail(VETO_ERR_INVALID, "level_grad[%d] is null", l);
@@ -694,7 +703,8 @@ static int roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const 
   if (grad_depth) p.depth.feat = grad_depth;   // only its non-null-ness and the sizes are used
   else p.depth.feat = nullptr;
   p.gout_rgb = grad_rgb; p.gout_depth = grad_depth; p.depth_grad = depth_grad;
-  if (ordered) HIP_TRY(launch_roi_pool_backward_ordered(p, a->n_img, (hipStream_t)stream));
+  if (adaptive) HIP_TRY(launch_roi_pool_adaptive_backward(p, (hipStream_t)stream));
+  else if (ordered) HIP_TRY(launch_roi_pool_backward_ordered(p, a->n_img, (hipStream_t)stream));
   else HIP_TRY(launch_roi_pool_backward(p, (hipStream_t)stream));
   return VETO_OK;
 }
@@ -707,6 +717,18 @@ int veto_roi_pool_backward(void* stream, const veto_roi_pool_args_t* a, const fl
 int veto_roi_pool_backward_ordered(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
                                    float* const* level_grad, float* depth_grad) {
   return roi_pool_backward(stream, a, grad_rgb, grad_depth, level_grad, depth_grad, true);
+}
+
+int veto_roi_pool_adaptive(void* stream, const veto_roi_pool_args_t* a) {
+  RoiPoolArgs p{};
+  ABI_TRY(roi_pool_args(a, true, &p, true));
+  HIP_TRY(launch_roi_pool_adaptive(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+int veto_roi_pool_adaptive_backward(void* stream, const veto_roi_pool_args_t* a, const float* grad_rgb, const float* grad_depth,
+                                    float* const* level_grad, float* depth_grad) {
+  return roi_pool_backward(stream, a, grad_rgb, grad_depth, level_grad, depth_grad, false, true);
 }
 
 // workspace: label_tmp | flag_tmp | flag_before | pair_score | row_key | acc_first | cls_table

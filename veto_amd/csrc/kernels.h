@@ -594,6 +594,9 @@ hipError_t launch_roi_pool(const RoiPoolArgs& a, hipStream_t s);
 hipError_t launch_roi_pool_backward(const RoiPoolArgs& a, hipStream_t s);
 // the ordered (gather) form: every element of every gradient map is written, in the summation order include/veto_amd.h states
 hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s);
+// the adaptive sampling grid (sampling_ratio == 0: ceil(roi_size / pooled) samples per bin and axis, per ROI); NCHW maps only
+hipError_t launch_roi_pool_adaptive(const RoiPoolArgs& a, hipStream_t s);
+hipError_t launch_roi_pool_adaptive_backward(const RoiPoolArgs& a, hipStream_t s);
 
 // ---- relation evaluators (sgg_eval.hip) ---------------------------------------------------------------
 struct SggEvalArgs {

@@ -15,6 +15,7 @@
 //
 // Map forms: the above is the NCHW mapping, instantiated on the maps' element type (float32, float16, bfloat16; a load widens to
 // float32).  NHWC maps (torch.channels_last) have kernels of their own further down, with the lanes over channels.
+// The adaptive grid (sampling ratio 0: the grid chosen per ROI) has NCHW kernels of its own at the end, without axis tables.
 //
 // Arithmetic: float32 in the reference's operation order with FMA contraction switched off, so the result
 // is bit-identical to the CPU restatement in oracle/roi_align_oracle.py.
@@ -39,10 +40,21 @@ struct AxisTable {
   int valid[kMaxAxis];
 };
 
-// one axis entry, ROIAlign_cuda.cu:21-57 restricted to one coordinate
-__device__ __forceinline__ void axis_entry(AxisTable& t, int k, float start, float bin, int p, int i, int grid, int size) {
-  float v = (start + (float)p * bin) + (((float)i + 0.5f) * bin) / (float)grid;
-  const bool valid = !(v < -1.0f || v > (float)size);
+// one axis entry, ROIAlign_cuda.cu:21-57 restricted to one coordinate: the coordinate of sample i of bin p on a grid of `grid`
+// samples per bin (non-decreasing in i: every operation is a monotone rounding of a monotone function), ...
+__device__ __forceinline__ float axis_coord(float start, float bin, int p, int i, int grid) {
+  return (start + (float)p * bin) + (((float)i + 0.5f) * bin) / (float)grid;
+}
+
+// ... and its validity, tap indices and low weight
+struct AxisTap {
+  int lo, hi;
+  float l;
+  bool valid;
+};
+__device__ __forceinline__ AxisTap axis_tap(float v, int size) {
+  AxisTap e;
+  e.valid = !(v < -1.0f || v > (float)size);
   if (v <= 0.f) v = 0.f;
   int lo = (int)v, hi;
   if (lo >= size - 1) {
@@ -51,12 +63,19 @@ __device__ __forceinline__ void axis_entry(AxisTable& t, int k, float start, flo
   } else {
     hi = lo + 1;
   }
-  const float l = v - (float)lo;
-  t.lo[k] = valid ? lo : 0;
-  t.hi[k] = valid ? hi : 0;
-  t.l[k] = l;
-  t.h[k] = 1.0f - l;
-  t.valid[k] = valid;
+  e.lo = lo;
+  e.hi = hi;
+  e.l = v - (float)lo;
+  return e;
+}
+
+__device__ __forceinline__ void axis_entry(AxisTable& t, int k, float start, float bin, int p, int i, int grid, int size) {
+  const AxisTap e = axis_tap(axis_coord(start, bin, p, i, grid), size);
+  t.lo[k] = e.valid ? e.lo : 0;
+  t.hi[k] = e.valid ? e.hi : 0;
+  t.l[k] = e.l;
+  t.h[k] = 1.0f - e.l;
+  t.valid[k] = e.valid;
 }
 
 // LevelMapper: floor(4 + log2(sqrt(area) / 224 + 1e-6)) clamped to [k_min, k_max], minus k_min; the
@@ -520,6 +539,194 @@ __global__ __launch_bounds__(256) void roi_pool_backward_nhwc_kernel(RoiPoolArgs
   }
 }
 
+// ---- the adaptive sampling grid (sampling_ratio == 0, ROIAlign_cuda.cu:103-104) -----------------------------------------------------------
+// The grid is chosen per ROI and axis: g = ceil(len / P) samples per bin, from the float32 quotient.  Same mapping as roi_pool_kernel
+// (a workgroup per (ROI, 32-channel slab), the lanes are bins, a lane walks bins lane, lane + 64, ... for P > 8, the four waves
+// take channel planes), but there is no axis table: g has no bound a table could be sized for, so every entry is computed where it
+// is used, by the axis_coord / axis_tap that axis_entry is made of -- once per sample, then used for the wave's kSlab / 4 channels,
+// which have an accumulator each in registers.  One bin's sum is never split: iy outer, ix inner, sequential, as in the reference.
+//
+// Work bound.  axis_coord is non-decreasing in i, so the valid samples of an axis of a bin are ONE index range; axis_first finds its
+// two ends by bisection on the same float32 expression (at most 31 steps each) and the loops run over the product of the two ranges.
+// The spacing bin / g is in (0.5, 1] once len >= P (below that g = 1), so an axis has at most 2 * size + 3 valid samples whatever
+// the box: a ROI of +-4000 px costs what its part inside the map costs.  A range longer than that can only come from coordinates
+// that float32 no longer separates (or from NaN, which every comparison lets through); it is outside the contract and taken as empty.
+struct AdaptiveAxis {
+  float start, bin;
+  int g;
+};
+
+__device__ __forceinline__ AdaptiveAxis adaptive_axis(float lo, float hi, float scale, int P) {
+  const float lo_c = lo * scale, hi_c = hi * scale;
+  const float len = fmaxf(hi_c - lo_c, 1.0f);      // :95-96
+  AdaptiveAxis A;
+  A.start = lo_c;
+  A.bin = len / (float)P;
+  A.g = (int)fminf(ceilf(len / (float)P), 2147483520.f);      // :103-104; the clamp keeps the conversion defined for an infinite box
+  return A;
+}
+
+// the first i in [0, g] whose coordinate is > size (UPPER) or no longer < -1 (!UPPER); g when there is none
+template <bool UPPER>
+__device__ __forceinline__ int axis_first(const AdaptiveAxis& A, int p, int size) {
+  int lo = 0, hi = A.g;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    const float v = axis_coord(A.start, A.bin, p, mid, A.g);
+    if (UPPER ? v > (float)size : !(v < -1.0f)) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+// [i0, i0 + n): the valid samples of bin p on this axis
+__device__ __forceinline__ void axis_valid_range(const AdaptiveAxis& A, int p, int size, int& i0, int& n) {
+  i0 = n = 0;
+  if (!(fabsf(A.start) <= 3.0e38f && A.bin <= 3.0e38f)) return;      // NaN or infinite box: no comparison would hold a NaN sample back
+  i0 = axis_first<false>(A, p, size);
+  n = axis_first<true>(A, p, size) - i0;
+  if (n < 0 || n > 2 * size + 3) n = 0;
+}
+
+constexpr int kPerWave = kSlab / 4;      // channels of a slab that one wave takes: c0 + wave, + 4, ...
+
+template <typename T>
+__global__ __launch_bounds__(256) void roi_pool_adaptive_kernel(RoiPoolArgs a) {
+  __shared__ int s_level;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const bool depth = blockIdx.z + a.z0 == 1;
+  const float* roi = a.rois + (size_t)r * 5;
+  const int C = depth ? a.depth_channels : a.channels;
+  const int c0 = blockIdx.y * kSlab;
+  if (c0 >= C) return;
+  if (tid == 0) {
+    const int lvl = roi_level(a, roi);
+    s_level = lvl;
+    if (a.out_levels && !depth && blockIdx.y == 0) a.out_levels[r] = lvl;
+  }
+  __syncthreads();
+  const RoiLevel L = depth ? a.depth : a.lv[s_level];
+  const int P = a.pooled;
+  const AdaptiveAxis ay = adaptive_axis(roi[2], roi[4], L.scale, P), ax = adaptive_axis(roi[1], roi[3], L.scale, P);
+  const float count = (float)(int)((unsigned)ay.g * (unsigned)ax.g);      // :112 (an int product in the reference)
+  const int b = (int)roi[0];
+  const int wv = tid >> 6;
+  const size_t plane_sz = (size_t)L.H * L.W;
+  const T* base = (const T*)L.feat + ((size_t)b * C + c0 + wv) * plane_sz;
+  float* out = (depth ? a.out_depth : a.out_rgb) + ((size_t)r * C + c0 + wv) * P * P;
+  const int n_pass = (P * P + 63) / 64;
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const int bin_id = pass * 64 + (tid & 63);
+    if (bin_id >= P * P) return;
+    const int ph = bin_id / P, pw = bin_id % P;
+    int y0, ny, x0, nx;
+    axis_valid_range(ay, ph, L.H, y0, ny);
+    axis_valid_range(ax, pw, L.W, x0, nx);
+    float acc[kPerWave];
+#pragma unroll
+    for (int j = 0; j < kPerWave; ++j) acc[j] = 0.f;
+    for (int iy = y0; iy < y0 + ny; ++iy) {
+      const AxisTap ey = axis_tap(axis_coord(ay.start, ay.bin, ph, iy, ay.g), L.H);
+      const float ly = ey.l, hy = 1.0f - ey.l;
+      for (int ix = x0; ix < x0 + nx; ++ix) {
+        const AxisTap ex = axis_tap(axis_coord(ax.start, ax.bin, pw, ix, ax.g), L.W);
+        const float lx = ex.l, hx = 1.0f - ex.l;
+        const float w0 = hy * hx, w1 = hy * lx, w2 = ly * hx, w3 = ly * lx;      // :61
+        const int o0 = ey.lo * L.W + ex.lo, o1 = ey.lo * L.W + ex.hi, o2 = ey.hi * L.W + ex.lo, o3 = ey.hi * L.W + ex.hi;
+#pragma unroll
+        for (int j = 0; j < kPerWave; ++j)
+          if (c0 + wv + 4 * j < C) {      // (wave-uniform)
+            const T* plane = base + (size_t)(4 * j) * plane_sz;
+            const float v0 = widen(plane[o0]), v1 = widen(plane[o1]), v2 = widen(plane[o2]), v3 = widen(plane[o3]);
+            acc[j] = acc[j] + (((w0 * v0 + w1 * v1) + w2 * v2) + w3 * v3);      // :63, :115
+          }
+      }
+    }
+    const bool skipped = ny != ay.g || nx != ax.g;      // a sample outside the map adds +0 (:26-29): once is as good as every time
+#pragma unroll
+    for (int j = 0; j < kPerWave; ++j)
+      if (c0 + wv + 4 * j < C) {
+        if (skipped) acc[j] = acc[j] + 0.f;
+        out[(size_t)(4 * j) * P * P + bin_id] = acc[j] / count;      // :118
+      }
+  }
+}
+
+// Backward on the adaptive grid: the same ranges and the same mapping; per valid sample and tap one atomic add of (g * w) / count,
+// the terms of roi_pool_backward_kernel.
+__global__ __launch_bounds__(256) void roi_pool_adaptive_backward_kernel(RoiPoolArgs a) {
+  __shared__ int s_level;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const bool depth = blockIdx.z + a.z0 == 1;
+  const float* roi = a.rois + (size_t)r * 5;
+  const int C = depth ? a.depth_channels : a.channels;
+  const int c0 = blockIdx.y * kSlab;
+  if (c0 >= C) return;
+  if (tid == 0) s_level = roi_level(a, roi);
+  __syncthreads();
+  const RoiLevel L = depth ? a.depth : a.lv[s_level];
+  float* grad_map = depth ? a.depth_grad : a.lv_grad[s_level];
+  const int P = a.pooled;
+  const AdaptiveAxis ay = adaptive_axis(roi[2], roi[4], L.scale, P), ax = adaptive_axis(roi[1], roi[3], L.scale, P);
+  const float count = (float)(int)((unsigned)ay.g * (unsigned)ax.g);
+  const int b = (int)roi[0];
+  const int wv = tid >> 6;
+  const size_t plane_sz = (size_t)L.H * L.W;
+  float* base = grad_map + ((size_t)b * C + c0 + wv) * plane_sz;
+  const float* gout = (depth ? a.gout_depth : a.gout_rgb) + ((size_t)r * C + c0 + wv) * P * P;
+  const int n_pass = (P * P + 63) / 64;
+  for (int pass = 0; pass < n_pass; ++pass) {
+    const int bin_id = pass * 64 + (tid & 63);
+    if (bin_id >= P * P) return;
+    const int ph = bin_id / P, pw = bin_id % P;
+    int y0, ny, x0, nx;
+    axis_valid_range(ay, ph, L.H, y0, ny);
+    axis_valid_range(ax, pw, L.W, x0, nx);
+    if (ny == 0 || nx == 0) continue;
+    float g[kPerWave];
+#pragma unroll
+    for (int j = 0; j < kPerWave; ++j) g[j] = c0 + wv + 4 * j < C ? gout[(size_t)(4 * j) * P * P + bin_id] : 0.f;
+    for (int iy = y0; iy < y0 + ny; ++iy) {
+      const AxisTap ey = axis_tap(axis_coord(ay.start, ay.bin, ph, iy, ay.g), L.H);
+      const float ly = ey.l, hy = 1.0f - ey.l;
+      for (int ix = x0; ix < x0 + nx; ++ix) {
+        const AxisTap ex = axis_tap(axis_coord(ax.start, ax.bin, pw, ix, ax.g), L.W);
+        const float lx = ex.l, hx = 1.0f - ex.l;
+        const float w0 = hy * hx, w1 = hy * lx, w2 = ly * hx, w3 = ly * lx;
+        const int o0 = ey.lo * L.W + ex.lo, o1 = ey.lo * L.W + ex.hi, o2 = ey.hi * L.W + ex.lo, o3 = ey.hi * L.W + ex.hi;
+#pragma unroll
+        for (int j = 0; j < kPerWave; ++j)
+          if (c0 + wv + 4 * j < C) {      // (wave-uniform)
+            float* plane = base + (size_t)(4 * j) * plane_sz;
+            atomicAdd(plane + o0, g[j] * w0 / count);      // :240-243
+            atomicAdd(plane + o1, g[j] * w1 / count);
+            atomicAdd(plane + o2, g[j] * w2 / count);
+            atomicAdd(plane + o3, g[j] * w3 / count);
+          }
+      }
+    }
+  }
+}
+
+template <typename T>
+hipError_t launch_roi_pool_adaptive_group(const RoiPoolArgs& a, int cmax, int nz, hipStream_t s) {
+  VETO_LAUNCH((roi_pool_adaptive_kernel<T>), dim3(a.n_roi, (cmax + kSlab - 1) / kSlab, nz), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_roi_pool_adaptive_typed(const RoiPoolArgs& a, int dtype, int cmax, int nz, hipStream_t s) {
+  switch (dtype) {
+    case kRoiF32: return launch_roi_pool_adaptive_group<float>(a, cmax, nz, s);
+    case kRoiF16: return launch_roi_pool_adaptive_group<_Float16>(a, cmax, nz, s);
+    case kRoiBF16: return launch_roi_pool_adaptive_group<bf16_t>(a, cmax, nz, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+bool roi_pool_adaptive_ok(const RoiPoolArgs& a) {
+  return a.pooled >= 1 && a.pooled <= 16 && a.sampling_ratio == 0 && a.lv_layout == kRoiNCHW && a.depth_layout == kRoiNCHW;
+}
+
 // pooled 1..16, sampling ratio 1..4, and an axis table of pooled * sampling_ratio <= kMaxAxis entries (the ordered kernel's bit masks too)
 bool roi_pool_sizes_ok(const RoiPoolArgs& a) {
   return a.pooled >= 1 && a.pooled <= 16 && a.sampling_ratio >= 1 && a.sampling_ratio <= 4 && a.pooled * a.sampling_ratio <= kMaxAxis;
@@ -632,6 +839,32 @@ hipError_t launch_roi_pool_backward(const RoiPoolArgs& a0, hipStream_t s) {
   if (e != hipSuccess) return e;
   a.z0 = 1;
   return launch_roi_pool_backward_group(a, a.depth_layout, a.depth_channels, 1, s);
+}
+
+// The adaptive grid: NCHW maps; one launch when the pyramid and the depth map share an element type, else one each.
+hipError_t launch_roi_pool_adaptive(const RoiPoolArgs& a0, hipStream_t s) {
+  if (!roi_pool_adaptive_ok(a0)) return hipErrorInvalidValue;
+  RoiPoolArgs a = a0;
+  const bool with_depth = a.depth.feat != nullptr;
+  a.z0 = 0;
+  if (!with_depth || a.lv_dtype == a.depth_dtype) {
+    const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
+    return launch_roi_pool_adaptive_typed(a, a.lv_dtype, cmax, with_depth ? 2 : 1, s);
+  }
+  hipError_t e = launch_roi_pool_adaptive_typed(a, a.lv_dtype, a.channels, 1, s);
+  if (e != hipSuccess) return e;
+  a.z0 = 1;
+  return launch_roi_pool_adaptive_typed(a, a.depth_dtype, a.depth_channels, 1, s);
+}
+
+hipError_t launch_roi_pool_adaptive_backward(const RoiPoolArgs& a0, hipStream_t s) {
+  if (!roi_pool_adaptive_ok(a0)) return hipErrorInvalidValue;
+  RoiPoolArgs a = a0;
+  const bool with_depth = a.depth.feat && a.gout_depth && a.depth_grad;
+  const int cmax = with_depth && a.depth_channels > a.channels ? a.depth_channels : a.channels;
+  a.z0 = 0;
+  VETO_LAUNCH(roi_pool_adaptive_backward_kernel, dim3(a.n_roi, (cmax + kSlab - 1) / kSlab, with_depth ? 2 : 1), dim3(256), 0, s, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_roi_pool_backward_ordered(const RoiPoolArgs& a, int n_img, hipStream_t s) {

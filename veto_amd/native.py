@@ -362,6 +362,8 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_roi_pool": _sig(_P, POINTER(VetoRoiPoolArgs)),
     "veto_roi_pool_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_roi_pool_backward_ordered": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
+    "veto_roi_pool_adaptive": _sig(_P, POINTER(VetoRoiPoolArgs)),
+    "veto_roi_pool_adaptive_backward": _sig(_P, POINTER(VetoRoiPoolArgs), _P, _P, POINTER(_P), _P),
     "veto_sgg_eval": _sig(_P, POINTER(VetoSggEvalArgs), _I, _I, _P, _Z),
     "veto_sgg_eval_workspace_bytes": _sig(_I, _I, _I, _I, ret=_Z),
     "veto_sgg_eval_fold": _sig(_P, POINTER(VetoSggEvalFoldArgs), _P, _Z),

@@ -6,8 +6,8 @@ Host-side mirror of the reference's
                                relation_head.py:53)
   * `VETOFeatureExtractor`     pysgg/modeling/roi_heads/box_head/roi_box_feature_extractors.py:75-121
 with the same constructor arguments, call signatures and return values.  All arithmetic runs in
-libveto_amd.so (veto_roi_pool): one launch pools every ROI from its own FPN level and the depth map with
-the fixed 1/16 pooler; dense NCHW or channels_last maps of float32, float16 or bfloat16 are read in place (anything else is
+libveto_amd.so (veto_roi_pool; veto_roi_pool_adaptive for sampling_ratio 0, the reference's default, whose grid is
+chosen per ROI): one launch pools every ROI from its own FPN level and the depth map with the fixed 1/16 pooler; dense NCHW or channels_last maps of float32, float16 or bfloat16 are read in place (anything else is
 first copied to float32 NCHW), and their gradients come back in the leaf's dtype and memory format; differentiable w.r.t. the maps (veto_roi_pool_backward, the atomic-add scatter of
 ROIAlign_cuda.cu:178-262).  Union pooling
 (7x7, Pooler.forward(union=True)) and cat_all_levels=True are not used by VETO and raise."""
@@ -42,7 +42,15 @@ IN_PLACE = {
     "forward": {(d, l) for d in _DTYPE_CODES.values() for l in (_NCHW, _NHWC)},
     "backward": {_NCHW, _NHWC},            # the gradient maps' layout (they are float32 whatever the maps were)
     "backward_ordered": {_NCHW, _NHWC},
+    # the adaptive grid (sampling_ratio 0, veto_roi_pool_adaptive): NCHW maps of the three dtypes in place; channels_last maps take the
+    # float32 NCHW copy (the same bits), and their gradients go back through autograd's own conversion.  No ordered backward.
+    "adaptive_forward": {(d, _NCHW) for d in _DTYPE_CODES.values()},
+    "adaptive_backward": {_NCHW},
 }
+_ADAPTIVE_ORDERED = ("veto_amd ROI pooling: sampling_ratio = 0 (the adaptive grid) has no ordered backward, and the ordered mode "
+                     "(VETO_AMD.DETERMINISTIC, torch.use_deterministic_algorithms(True) or VETO_DETERMINISTIC=1) is on; it does not "
+                     "fall back to atomic adds.  Use POOLER_SAMPLING_RATIO 1-4, which veto_roi_pool_backward_ordered supports, or "
+                     "switch the ordered mode off")
 
 
 def _map_form(maps):
@@ -59,11 +67,11 @@ def _map_form(maps):
     return None
 
 
-def _in_place(maps, device):
-    """(the maps as the call reads them, (dtype code, layout code)): in place when their form is dispatched that way, else the
-    dense float32 NCHW copies."""
+def _in_place(maps, device, key="forward"):
+    """(the maps as the call reads them, (dtype code, layout code)): in place when their form is dispatched that way (IN_PLACE[key]),
+    else the dense float32 NCHW copies."""
     form = _map_form(maps)
-    if form is not None and form in IN_PLACE["forward"] and all(m.device == device for m in maps):
+    if form is not None and form in IN_PLACE[key] and all(m.device == device for m in maps):
         return [m.detach() for m in maps], form
     return [m.detach().to(device=device, dtype=torch.float32).contiguous() for m in maps], (native.VETO_ROI_F32, _NCHW)
 
@@ -72,7 +80,9 @@ def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=No
     device = rois.device
     call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
-    feats, (level_dtype, level_layout) = _in_place(list(level_feats), device)
+    adaptive = sampling_ratio == 0      # the grid chosen per ROI: entry points of its own
+    key = "adaptive_forward" if adaptive else "forward"
+    feats, (level_dtype, level_layout) = _in_place(list(level_feats), device, key)
     rois = rois.detach().to(**f32).contiguous()
     n_roi, C = rois.shape[0], feats[0].shape[1]
     for l, f in enumerate(feats):
@@ -80,7 +90,7 @@ def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=No
             raise ValueError("pyramid level %d has shape %s, expected [%d, %d, H, W]" % (l, tuple(f.shape), n_img, C))
     depth_dtype, depth_layout = native.VETO_ROI_F32, _NCHW
     if depth is not None:
-        (depth,), (depth_dtype, depth_layout) = _in_place([depth], device)
+        (depth,), (depth_dtype, depth_layout) = _in_place([depth], device, key)
     out_rgb = torch.empty((n_roi, C, pooled, pooled), **f32)
     out_depth = None
     if depth is not None:
@@ -89,7 +99,7 @@ def _roi_pool(level_feats, scales, rois, n_img, pooled, sampling_ratio, depth=No
     a = _pool_args(call, feats, scales, rois, n_img, pooled, sampling_ratio, tuple(depth.shape) if depth is not None else None,
                    depth_feat=depth, out_rgb=out_rgb, out_depth=out_depth, out_levels=levels, level_dtype=level_dtype,
                    level_layout=level_layout, depth_dtype=depth_dtype, depth_layout=depth_layout)
-    call.run("veto_roi_pool", ctypes.byref(a))
+    call.run("veto_roi_pool_adaptive" if adaptive else "veto_roi_pool", ctypes.byref(a))
     return out_rgb, out_depth, levels
 
 
@@ -97,7 +107,9 @@ def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad
                        level_layout=_NCHW, depth_layout=_NCHW):
     """Map gradients of one veto_roi_pool call: (list of per-level gradients, depth gradient or None), float32 and dense in
     level_layout / depth_layout (NHWC: torch.channels_last).  ordered: through veto_roi_pool_backward_ordered, which fixes the
-    summation order and writes every element itself."""
+    summation order and writes every element itself.  sampling_ratio 0: veto_roi_pool_adaptive_backward (atomic, NCHW only)."""
+    if sampling_ratio == 0 and ordered:
+        raise NotImplementedError(_ADAPTIVE_ORDERED)
     device = rois.device
     call = native.Launch(device, "veto_amd ROI pooling runs only on a HIP device")
     f32 = dict(device=device, dtype=torch.float32)
@@ -117,7 +129,8 @@ def _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad
     if grad_depth is not None:
         grad_depth = grad_depth.detach().to(**f32).contiguous()
         depth_grad = make(depth_shape, memory_format=formats[depth_layout])
-    call.run("veto_roi_pool_backward_ordered" if ordered else "veto_roi_pool_backward", ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
+    entry = "veto_roi_pool_adaptive_backward" if sampling_ratio == 0 else "veto_roi_pool_backward_ordered" if ordered else "veto_roi_pool_backward"
+    call.run(entry, ctypes.byref(a), call.ptr(grad_rgb), call.ptr(grad_depth), ptrs, call.ptr(depth_grad))
     return level_grads, depth_grad
 
 
@@ -158,7 +171,9 @@ class _RoiPoolFn(torch.autograd.Function):
         if grad_rgb is None:
             grad_rgb = torch.zeros((rois.shape[0], shapes[0][1], pooled, pooled), device=rois.device)
         ordered = native.ordered_mode(ctx.ordered)
-        in_place = IN_PLACE["backward_ordered" if ordered else "backward"]
+        if ordered and sampling_ratio == 0:
+            raise NotImplementedError(_ADAPTIVE_ORDERED)
+        in_place = IN_PLACE["adaptive_backward" if sampling_ratio == 0 else "backward_ordered" if ordered else "backward"]
         layouts = [form[1] if form is not None and form[1] in in_place else _NCHW for form in ctx.forms]
         level_grads, depth_grad = _roi_pool_backward(shapes, scales, rois, n_img, pooled, sampling_ratio, grad_rgb,
                                                      depth_shape, grad_dep, ordered=ordered, level_layout=layouts[0], depth_layout=layouts[1])

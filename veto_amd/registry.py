@@ -149,7 +149,8 @@ def install_pooler_ops():
     which it was imported from) become veto_amd.poolers.ROIAlign and `pysgg.modeling.poolers.Pooler` becomes veto_amd.poolers.Pooler -- the box head's 7 x 7
     pooler included, whose `pysgg._C.roi_align_forward` has no HIP build.  Modules that bound one of the originals by name when
     they were imported (`from pysgg.modeling.poolers import Pooler`, roi_box_feature_extractors.py:8; `from pysgg.layers import
-    ROIAlign`, poolers.py:6) are re-pointed too.  Pooler(cat_all_levels=True) and Pooler.forward(union=True) keep raising.
+    ROIAlign`, poolers.py:6) are re-pointed too.  sampling_ratio 0, the default of pysgg/config/defaults.py, is served (the adaptive
+    grid, veto_roi_pool_adaptive); its backward raises in the ordered mode.  Pooler(cat_all_levels=True) and Pooler.forward(union=True) keep raising.
     `pysgg` must be importable.  Independent of the other installers.  Returns the patched (module, name) pairs."""
     import importlib
     import sys

@@ -289,7 +289,7 @@ def roi_test_boxes(rng, n, W, H):
     return b
 
 
-ROI_SINGLE_CASES = [(8, 2), (7, 2), (8, 1), (4, 4), (6, 0)]   # (pooled, sampling_ratio); 0 = adaptive grid (oracle only)
+ROI_SINGLE_CASES = [(8, 2), (7, 2), (8, 1), (4, 4), (6, 0)]   # (pooled, sampling_ratio); 0 = adaptive grid (veto_roi_pool_adaptive)
 # the pairs the ROI pooling suite added to the same fixture file (every kernel instance, full axis tables, mostly idle waves); a list of
 # its own, so that a test written against ROI_SINGLE_CASES keeps reading the keys it was written for
 ROI_SINGLE_CASES_MORE = [(8, 3), (8, 4), (5, 3), (3, 4), (2, 1), (1, 1), (1, 4)]
