@@ -55,8 +55,9 @@ enum veto_precision {
   VETO_PRECISE = 0,  /* 3-term split-bf16 MFMA on every Linear, meets the 1e-3 logit tolerance (2-3e-5 measured).  Range: the Linears'
                         operands keep the fp32 exponent range; the ATTENTION products (every mode, the training path included) split
                         q / k / v and the probabilities into fp16 hi + fp16 lo planes (22 significant bits; on the training path q / k / v
-                        are stored as 3-byte floats by default and so carry 16, VETO_TRAIN_QKV_F24=0 restores 22): |q|, |k|, |v| beyond 65504
-                        saturate there and components below ~2^-24 are dropped -- both far outside what LayerNorm'ed rows times
+                        are stored as 3-byte floats by default and so carry 16, VETO_TRAIN_QKV_F24=0 restores 22): each plane saturates at
+                        +-65504, so of |q|, |k|, |v| beyond 65504 the lo plane keeps the excess with its own 11 bits and the operand clamps
+                        only beyond +-131008; components below ~2^-24 are dropped -- both far outside what LayerNorm'ed rows times
                         weights produce (O(10)); no audit counts them */
   VETO_FAST = 1,     /* single-pass form of VETO_MIXED (round 6; rounds 1-5: a single bf16 pass of every GEMM): the same launches
                         on the same operand rows, but the two fused token-row launches of a layer (QKV + attention, layer tail) skip the
@@ -1449,6 +1450,32 @@ int veto_debug_layernorm_backward_ordered(void* stream, const float* x, const fl
                                           float* dx, float* dgamma_dbeta, void* split_rows, float* col_partials, int32_t rows,
                                           uint64_t drop_seed, uint32_t drop_thresh, float drop_scale, void* workspace,
                                           size_t workspace_bytes);
+
+/* ---- test hooks: the forward attention kernels and the layer-0 row combiner, each alone on caller-given device buffers ----------
+ * (model_veto.py:85-96 per pair and head over the 19 tokens; tests/attention_cases.py states the contracts in float64.)
+ * veto_debug_attention: qkv [19 n_pair, 1728] fp32 (q | k | v, heads side by side), or with qkv_f24 = 1 the same matrix as 3-byte
+ *   floats (rows of 5184 bytes).  o receives the merged-heads output rows: split rows (o_fmt 0: 2 x 576 bf16 per row) or mixed
+ *   activation rows (o_fmt 1: 2304 bytes per row), 19 n_pair of them, or n_pair (the CLS query's row of every pair) with cls_only = 1.
+ *   Per-object form of layer 0 (all six of sw .. obj non-NULL, else all NULL): sw / ow fp32 [n_obj * 16, 1728], stats fp32
+ *   [19 n_pair, 2] = (mean, rstd) per token row, vec fp32 [3, 1728] = c2 | b0 | the CLS row, subj / obj int32 [n_pair]: the row of
+ *   token t = 1..16 of pair p is rstd[p, t] (sw[subj[p] * 16 + t - 1] + ow[obj[p] * 16 + t - 1]) + c2, token 0 is vec's third row,
+ *   and only the rows of tokens 17 / 18 are read from qkv.
+ *   Refused with VETO_ERR_INVALID before any launch: a NULL qkv or o, n_pair <= 0, heads that do not divide 576, table operands
+ *   given in part, tables with cls_only or qkv_f24, tables / qkv_f24 / o_fmt 1 at a head width other than 72 or 96, a generic head
+ *   width that is no multiple of 4 or needs more than 160 KB of LDS (heads 1, 2, 3).
+ * veto_debug_cls_fold_attention: the folded CLS-query attention of the last layer.  x fp32 [19 n_pair, 576] (the residual stream;
+ *   a_j = LayerNorm(x_j; ln_w, ln_b, eps 1e-5) is formed inside), u [n_pair, heads * 576] fp32 or (u_f24 = 1) 3-byte floats;
+ *   score[h][j] = dh^-0.5 u_h . a_j, p = softmax over j, abar_h = sum_j p[h][j] a_j; abar = split rows [n_pair, 2 x heads x 576].
+ *   Refused: NULL pointers, n_pair <= 0, heads that do not divide 576 or exceed 12, u_f24 with the vector-ALU form (VETO_CLS_MFMA=0).
+ * veto_debug_qkv0_combine: writes the rows of tokens 0..16 of qkv fp32 [19 n_pair, 1728] from the per-object operands above (the
+ *   rows of tokens 17 / 18 are left alone). */
+int veto_debug_attention(void* stream, const void* qkv, void* o, int32_t n_pair, int32_t heads, int32_t cls_only, int32_t o_fmt,
+                         int32_t qkv_f24, const float* sw, const float* ow, const float* stats, const float* vec, const int32_t* subj,
+                         const int32_t* obj);
+int veto_debug_cls_fold_attention(void* stream, const float* x, const float* ln_w, const float* ln_b, const void* u, void* abar,
+                                  int32_t n_pair, int32_t heads, int32_t u_f24);
+int veto_debug_qkv0_combine(void* stream, const float* sw, const float* ow, const float* stats, const float* vec, const int32_t* subj,
+                            const int32_t* obj, float* qkv, int32_t n_pair);
 
 #ifdef __cplusplus
 }

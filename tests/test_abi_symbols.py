@@ -14,7 +14,7 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 def _declared():
     text = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(veto_[a-z_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(veto_[a-z0-9_]+)\s*\(", text)))      # (digits: veto_debug_qkv0_combine)
 
 
 def test_header_and_binding_list_the_same_entry_points():

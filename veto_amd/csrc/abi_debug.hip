@@ -439,4 +439,56 @@ int veto_debug_column_sums(void* stream, const float* dy, int64_t ld, int32_t ro
   return VETO_OK;
 }
 
+// ---- the forward attention kernels (attention.hip) and qkv0_combine_kernel (rowops.hip), each alone on caller-given buffers --------
+// Everything launch_attention / launch_cls_fold_attention answer with hipErrorInvalidValue is refused here first, with its reason.
+int veto_debug_attention(void* stream, const void* qkv, void* o, int32_t n_pair, int32_t heads, int32_t cls_only, int32_t o_fmt,
+                         int32_t qkv_f24, const float* sw, const float* ow, const float* stats, const float* vec, const int32_t* subj,
+                         const int32_t* obj) {
+  if (!qkv || !o) return fail(VETO_ERR_INVALID, "null argument");
+  if (n_pair <= 0) return fail(VETO_ERR_INVALID, "n_pair must be positive");
+  if ((cls_only != 0 && cls_only != 1) || (qkv_f24 != 0 && qkv_f24 != 1) || (o_fmt != FMT_SPLIT && o_fmt != FMT_MIXED))
+    return fail(VETO_ERR_INVALID, "cls_only and qkv_f24 are 0 or 1, o_fmt is 0 (split rows) or 1 (mixed rows)");
+  if (heads <= 0 || kDim % heads != 0) return fail(VETO_ERR_INVALID, "heads %d does not divide 576", heads);
+  const int dh = kDim / heads;
+  const bool mfma = dh == 72 || dh == 96;
+  const bool any_tab = sw || ow || stats || vec || subj || obj, all_tab = sw && ow && stats && vec && subj && obj;
+  if (any_tab && !all_tab) return fail(VETO_ERR_INVALID, "the table operands sw, ow, stats, vec, subj, obj go together");
+  if (any_tab && cls_only) return fail(VETO_ERR_INVALID, "the per-object form has no cls_only instance");
+  if (any_tab && qkv_f24) return fail(VETO_ERR_INVALID, "the per-object form reads fp32 rows for tokens 17 / 18");
+  if (!mfma) {
+    if (any_tab || qkv_f24) return fail(VETO_ERR_INVALID, "tables and 3-byte q / k / v need a head width of 72 or 96 (heads %d: %d)", heads, dh);
+    if (o_fmt != FMT_SPLIT) return fail(VETO_ERR_INVALID, "the generic kernel (head width %d) writes split rows only", dh);
+    if (dh % 4 != 0) return fail(VETO_ERR_INVALID, "head width %d is no multiple of 4", dh);
+    if (attention_generic_lds_bytes(dh) > kAttentionGenericLdsMax)
+      return fail(VETO_ERR_INVALID, "head width %d needs %zu bytes of LDS (limit %zu)", dh, attention_generic_lds_bytes(dh), kAttentionGenericLdsMax);
+  }
+  AttnArgs a{};
+  a.qkv = (const float*)qkv; a.o = (__bf16*)o; a.n_pair = n_pair; a.heads = heads; a.cls_only = cls_only; a.qkv_f24 = qkv_f24; a.o_fmt = o_fmt;
+  a.sw = sw; a.ow = ow; a.stats = stats; a.vec = vec; a.subj = subj; a.obj = obj;
+  const hipError_t e = launch_attention(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "attention launch: %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+int veto_debug_cls_fold_attention(void* stream, const float* x, const float* ln_w, const float* ln_b, const void* u, void* abar,
+                                  int32_t n_pair, int32_t heads, int32_t u_f24) {
+  if (!x || !ln_w || !ln_b || !u || !abar) return fail(VETO_ERR_INVALID, "null argument");
+  if (n_pair <= 0) return fail(VETO_ERR_INVALID, "n_pair must be positive");
+  if (u_f24 != 0 && u_f24 != 1) return fail(VETO_ERR_INVALID, "u_f24 is 0 or 1");
+  if (heads <= 0 || kDim % heads != 0) return fail(VETO_ERR_INVALID, "heads %d does not divide 576", heads);
+  if (heads > cls_fold_max_heads()) return fail(VETO_ERR_INVALID, "the folded kernels take at most %d heads", cls_fold_max_heads());
+  if (u_f24 && cls_fold_on_vector_alu()) return fail(VETO_ERR_INVALID, "the vector-ALU folded kernel (VETO_CLS_MFMA=0) reads u as fp32 only");
+  const hipError_t e = launch_cls_fold_attention(x, ln_w, ln_b, (const float*)u, (__bf16*)abar, n_pair, heads, (hipStream_t)stream, u_f24 != 0);
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? VETO_ERR_INVALID : VETO_ERR_HIP, "folded attention launch: %s", hipGetErrorString(e));
+  return VETO_OK;
+}
+
+int veto_debug_qkv0_combine(void* stream, const float* sw, const float* ow, const float* stats, const float* vec, const int32_t* subj,
+                            const int32_t* obj, float* qkv, int32_t n_pair) {
+  if (!sw || !ow || !stats || !vec || !subj || !obj || !qkv) return fail(VETO_ERR_INVALID, "null argument");
+  if (n_pair <= 0) return fail(VETO_ERR_INVALID, "n_pair must be positive");
+  HIP_TRY(launch_qkv0_combine(sw, ow, stats, vec, subj, obj, qkv, n_pair, (hipStream_t)stream));
+  return VETO_OK;
+}
+
 }  // extern "C"

@@ -102,7 +102,9 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 // Two fp32 values -> packed 16-bit hi and lo parts, x ~= hi + lo: the operand planes of the attention products (three MFMA terms hi hi + hi lo + lo hi).
 // As in qkv_attn_fused.hip: fp16 hi (11 significant bits) + fp16 lo, 22 bits in all, FOUR vector instructions per value pair
 // (v_cvt_pk_f16_f32, two v_fma_mix_f32 that read the packed halves in place, v_cvt_pk_f16_f32); q / k / v are O(10) (LayerNorm'ed rows times weights), far
-// inside the fp16 range (the conversions saturate: MODE.FP16_OVFL is set), a lo part below 2^-24 is lost -- less than a bf16 lo keeps of such a value.
+// inside the fp16 range, a lo part below 2^-24 is lost -- less than a bf16 lo keeps of such a value.  Both conversions saturate (MODE.FP16_OVFL is set),
+// which does NOT clamp the operand at 65504: there hi stays at +-65504 and lo = fp16(x - hi) carries the excess with lo's own 11 bits, so the operand follows x
+// up to +-131008 (2 x 65504) and clamps only beyond (measured: tests/test_attention_forward_gpu.py, the "overflow" family; profiles/attention_forward_parity.txt).
 // (bf16 hi + bf16 lo, 16 bits and six instructions, measured the same 0.532-0.537 ms at 1300 instead of 1226 vector instructions per item.)
 __device__ __forceinline__ void att_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
   uint32_t h, l;
@@ -892,17 +894,21 @@ __global__ __launch_bounds__(256, 3) void cls_fold_attention_mfma_kernel(const f
 
 int cls_fold_max_heads() { return kFoldMaxHeads; }
 
+bool cls_fold_on_vector_alu() {
+  static const bool valu = env_knob_is("VETO_CLS_MFMA", "0");     // A/B knob of the parity tests: the fp32 VALU form
+  return valu;
+}
+
 bool cls_fold_reads_f24() {
-  static const bool valu = env_knob_is("VETO_CLS_MFMA", "0");
   static const bool f32 = env_knob_is("VETO_QKV_F24", "0");
-  return !valu && !f32;
+  return !cls_fold_on_vector_alu() && !f32;
 }
 
 hipError_t launch_cls_fold_attention(const float* x, const float* ln_w, const float* ln_b, const float* u, __bf16* abar, int n_pair, int heads,
                                      hipStream_t s, bool u_f24) {
   if (heads <= 0 || heads > kFoldMaxHeads || kDim % heads != 0 || n_pair <= 0) return hipErrorInvalidValue;
   const float scale = 1.0f / sqrtf((float)(kDim / heads));
-  static const bool valu = env_knob_is("VETO_CLS_MFMA", "0");     // A/B knob of the parity tests: the fp32 VALU form
+  const bool valu = cls_fold_on_vector_alu();
   if (u_f24 && valu) return hipErrorInvalidValue;
   if (valu) VETO_LAUNCH(cls_fold_attention_kernel, dim3(n_pair), dim3(256), 0, s, x, ln_w, ln_b, u, abar, n_pair, heads, scale);
   else if (u_f24) VETO_LAUNCH(cls_fold_attention_mfma_kernel<true>, dim3(n_pair), dim3(256), 0, s, x, ln_w, ln_b, u, abar, n_pair, heads, scale);
@@ -921,6 +927,10 @@ hipError_t launch_cls_fold_attention(const float* x, const float* ln_w, const fl
   }
 #endif
   return hipGetLastError();
+}
+
+size_t attention_generic_lds_bytes(int dh) {
+  return (size_t)kWavesPerBlock * (3 * kTokens * (dh + 4) + kTokens * 20) * sizeof(float);
 }
 
 bool attention_reads_tables(int heads) {
@@ -968,12 +978,12 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   if (a.sw || a.qkv_f24) return hipErrorInvalidValue;
   if (dh % 4 != 0) return hipErrorInvalidValue;
   const int ldh = dh + 4;
-  const size_t lds = (size_t)kWavesPerBlock * (3 * kTokens * ldh + kTokens * 20) * sizeof(float);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const size_t lds = attention_generic_lds_bytes(dh);
+  if (lds > kAttentionGenericLdsMax) return hipErrorInvalidValue;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)attention_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAttentionGenericLdsMax);
     if (e != hipSuccess) return e;
     attr_set = true;
   }

@@ -224,6 +224,9 @@ struct AttnArgs {
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 bool attention_reads_tables(int heads);   // whether launch_attention takes the per-object form for this head count
+// the generic (vector-ALU) kernel's dynamic LDS at head width dh, and the most launch_attention accepts
+constexpr size_t kAttentionGenericLdsMax = 160 * 1024;
+size_t attention_generic_lds_bytes(int dh);
 
 // QKV projection + attention of a middle layer in one launch (qkv_attn_fused.hip; VETO_MIXED, head widths 72 / 96): a = LayerNorm1 rows
 // (mixed, [rows padded to qkv_attn_rows_padded(n_pair), 4*576 B]), w = Wqkv as mixed weight rows [1728, 4*576 B] with its e4m3 exponent
@@ -246,6 +249,7 @@ hipError_t launch_qkv_attn_fused(const QkvAttnArgs& g, hipStream_t s);
 int cls_fold_max_heads();
 hipError_t launch_cls_fold_attention(const float* x, const float* ln_w, const float* ln_b, const float* u, __bf16* abar, int n_pair, int heads,
                                      hipStream_t s, bool u_f24 = false);
+bool cls_fold_on_vector_alu();   // VETO_CLS_MFMA=0 (read once per process): the fp32 vector-ALU kernel, which takes u as fp32 only
 bool cls_fold_reads_f24();   // whether the kernel takes u as 3-byte floats (the MFMA form; VETO_QKV_F24=0 / VETO_CLS_MFMA=0: fp32)
 
 // cls row p at cls + p*ld (ld = 576 for compact CLS rows, 19*576 to read row 0 of every pair of a token matrix)

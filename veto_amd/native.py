@@ -353,6 +353,9 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_debug_assemble_backward_ordered": _sig(_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P),
     "veto_debug_scatter_rows_ordered": _sig(_P, _P, _P, _I, _I, _I, _P),
     "veto_debug_layernorm_backward_ordered": _sig(_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, c_uint64, c_uint32, c_float, _P, _Z),
+    "veto_debug_attention": _sig(_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P),
+    "veto_debug_cls_fold_attention": _sig(_P, _P, _P, _P, _P, _P, _I, _I, _I),
+    "veto_debug_qkv0_combine": _sig(_P, _P, _P, _P, _P, _P, _P, _P, _I),
     "veto_ce_loss": _sig(_P, _P, c_int64, _P, _P, _P, _I, _I, _P, _P, _P, _Z),
     "veto_ce_loss_workspace_bytes": _sig(_I, ret=_Z),
     "veto_meet_sample": _sig(_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P),
