@@ -151,8 +151,31 @@ int veto_destroy(veto_handle_t h);
  * row-concatenated as "rel_out.weight"/"rel_out.bias". */
 int veto_num_weights(veto_handle_t h);
 int veto_weight_info(veto_handle_t h, int index, const char** name, size_t* numel);
-/* Copies `numel` fp32 values from `src` (device or host pointer) on `stream`. */
+/* Copies `numel` fp32 values from `src` (device or host pointer) on `stream`.
+ * The next forward rebuilds the derived operands that read this tensor, and only those:
+ *   a layer Linear (to_qkv / to_out.0 / net.0 / net.3 .weight)                     its own split rows and mixed rows
+ *   layer 0's 0.norm.weight / .bias, to_qkv.weight, pos_embedding, cls_token       the layer-0 constants (Wqkv diag(gamma), vectors)
+ *   the last layer's to_qkv.weight / to_out.0.weight                               the folded last layer's factors
+ *   patch_embed.*                                                                  the staged patch weight and bias
+ *   location_projection.0.weight, class_projection.0.weight, rel_out.weight       their transposes
+ *   every other tensor (biases, obj_embed, pos_embed.*, LayerNorm2 gains, ...)     nothing: it is read in place
+ * A rebuilt operand has the bytes a rebuild of everything gives it. */
 int veto_load_weights(veto_handle_t h, const char* name, const float* src, size_t numel, void* stream);
+
+/* Test hook: what the last rebuild of derived operands (at the head of a forward that found uploaded weights) launched, as a count
+ * of rebuilt operands per kind.  counts: host array of `capacity` >= VETO_BUILD_KINDS entries.  Returns VETO_BUILD_KINDS. */
+enum veto_build_kind {
+  VETO_BUILD_SPLIT_ROWS = 0,   /* split rows of a layer Linear */
+  VETO_BUILD_MIXED_ROWS = 1,   /* mixed rows of a layer Linear (VETO_MIXED / VETO_FAST handles) */
+  VETO_BUILD_PATCH = 2,        /* the staged patch weight and bias */
+  VETO_BUILD_LOC_T = 3,        /* location_projection.0.weight transposed */
+  VETO_BUILD_CLS_T = 4,        /* class_projection.0.weight transposed */
+  VETO_BUILD_HEAD_T = 5,       /* rel_out.weight transposed */
+  VETO_BUILD_QKV0 = 6,         /* the layer-0 constants */
+  VETO_BUILD_FOLD = 7,         /* the folded last layer's factors */
+  VETO_BUILD_KINDS = 8
+};
+int veto_debug_last_finalize(veto_handle_t h, int32_t* counts, int32_t capacity);
 
 size_t veto_workspace_bytes(veto_handle_t h, int32_t n_obj, int32_t n_pair);
 
@@ -1374,7 +1397,22 @@ typedef struct veto_train_plan {
    * projection whatever is frozen (the pointers themselves are read by the backward only; asking for them there with 0 here is
    * refused). */
   int32_t d_roi;
-  int32_t reserved0;
+  /* nonzero: the frozen-fused step (opt-in; 0 leaves every launch, workspace size and bit as it was).  The frozen region -- the
+   * prelude (pair indices, object side, patch GEMM, token assembly) and layers 0 .. k-1, k the lowest layer with a trainable tensor
+   * (k = layers when only rel_out.* is trainable) -- is the inference forward: veto_forward's stages in the handle's own precision,
+   * chunk by chunk, on operands that are rebuilt per changed tensor (veto_load_weights).
+   *   k == layers: the whole forward is veto_forward's (logits bit-equal to it); the CLS rows [n_pair, 576] stay in the workspace
+   *                and the backward is the head's weight and bias gradient.
+   *   k <  layers: behind layer k-1's tail the chunk's fp32 residual rows are copied to the buffer the training forward of layer k
+   *                reads; layers k .. L-1 and the head run on the training path as under the same plan without this flag (saved
+   *                activations, the step seed's dropout masks in those layers, the plain last layer).
+   * The backward is the planned step's: it ends at layer k.  The workspace holds the inference forward's regions, the hand-off or CLS
+   * rows and the saved activations of layers >= k.
+   * Refused (VETO_ERR_INVALID by the forward and the backward, 0 by the size query, before any launch): a trainable tensor inside
+   * the prelude; k == 0; bn_eval == 0; d_roi != 0; a non-zero opts->p_pos or opts->p_emb, or a non-zero attention dropout rate
+   * in a layer < k; a VETO_FAST handle (its logit error is above the 1e-3 bar); VETO_X_F24=1.  Both calls of a step must agree on the
+   * flag as on the rest of the plan. */
+  int32_t frozen_fused;
 } veto_train_plan_t;
 
 size_t veto_train_workspace_bytes_plan(veto_handle_t h, int32_t n_obj, int32_t n_pair, const veto_train_opts_t* opts,

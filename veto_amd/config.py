@@ -100,4 +100,8 @@ def default_config():
     # has a fixed order, so two steps from one state and one seed give the same bits.  Also on under
     # torch.use_deterministic_algorithms(True) and with VETO_DETERMINISTIC=1 in the environment.  Other bits than the default; more workspace.
     c.VETO_AMD.DETERMINISTIC = False
+    # True: a training step whose frozen region (everything under the lowest layer with a trainable parameter) is in eval mode runs
+    # that region through the fused inference launches (include/veto_amd.h, veto_train_plan_t.frozen_fused) and uploads only the
+    # tensors that changed.  Eligibility is decided per step (predictor.last_frozen_fused); an ineligible step runs as with False.
+    c.VETO_AMD.FROZEN_FUSED = False
     return c

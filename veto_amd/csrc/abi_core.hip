@@ -38,45 +38,88 @@ static int fold_block_width(int heads) {
   return 192 % dhp == 0 && (heads * dhp) % 192 == 0 ? dhp : 0;
 }
 
-int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only) {
+// THE dependency table of the per-tensor refresh (include/veto_amd.h, veto_load_weights): the derived operands that read the
+// state-dict tensor `name`.  A tensor that is read in place (biases, obj_embed, pos_embed.*, LayerNorm2 gains, ...) has none.
+static std::vector<int> operands_of(veto_handle_t h, const std::string& name) {
+  const int L = h->cfg.layers;
+  const std::string T = kT;
+  std::vector<int> ops;
+  for (int l = 0; l < L; ++l)
+    for (int i = 0; i < 4; ++i)
+      if (name == lname(l, kLayerLinears[i].weight)) ops.push_back(OP_LINEAR0 + 4 * l + i);
+  for (const std::string& q : {lname(0, "0.norm.weight"), lname(0, "0.norm.bias"), lname(0, "0.fn.to_qkv.weight"), T + "pos_embedding", T + "cls_token"})
+    if (name == q) ops.push_back(OP_QKV0);
+  for (const std::string& q : {lname(L - 1, "0.fn.to_qkv.weight"), lname(L - 1, "0.fn.to_out.0.weight")})
+    if (name == q) ops.push_back(OP_FOLD);
+  if (name.compare(0, T.size() + 12, T + "patch_embed.") == 0) ops.push_back(OP_PATCH);
+  if (name == "location_projection.0.weight") ops.push_back(OP_LOC_T);
+  if (name == "class_projection.0.weight") ops.push_back(OP_CLS_T);
+  if (name == "rel_out.weight") ops.push_back(OP_HEAD_T);
+  return ops;
+}
+
+// the builds operand `op` has: the four re-layouts are the training path's too, the layer-0 constants and the fold the inference forward's alone
+static uint8_t builds_of(int op) {
+  return op >= OP_LINEAR0 ? STALE_TRAIN | STALE_INFER : op == OP_QKV0 || op == OP_FOLD ? STALE_INFER : STALE_TRAIN;
+}
+
+int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only, int infer_layers) {
   for (const Param& q : h->params)
     if (!q.loaded) return fail(VETO_ERR_WEIGHTS, "weight '%s' was never loaded", q.name.c_str());
   const int L = h->cfg.layers;
-  const bool base = h->dirty;      // (false: only the inference-side operands are missing)
+  const bool uploaded = h->dirty;      // (false: only inference-side operands are missing)
+  const bool mixed = h->cfg.precision != VETO_PRECISE;      // (VETO_FAST runs VETO_MIXED's launches, with the correction stages of the fused ones skipped)
+  const int infer_upto = infer_layers < 0 ? L : infer_layers;
+  for (int32_t& n : h->built) n = 0;
+  // does build `bit` of operand `op` run now?  It is then current.
+  auto take = [&](int op, int bit) {
+    if (!(h->stale[op] & bit)) return false;
+    h->stale[op] &= ~bit;
+    return true;
+  };
   for (int l = 0; l < L; ++l) {
     LayerW& w = h->layers[l];
-    if (base)
-      for (int i = 0; i < 4; ++i) {
-        const LayerLinear& q = kLayerLinears[i];
+    for (int i = 0; i < 4; ++i) {
+      const LayerLinear& q = kLayerLinears[i];
+      if (take(OP_LINEAR0 + 4 * l + i, STALE_TRAIN)) {
         HIP_TRY(launch_split_rows(h->p(lname(l, q.weight)), w.split(i), q.N, q.K, s));
+        ++h->built[VETO_BUILD_SPLIT_ROWS];
       }
-    if (h->cfg.precision != VETO_PRECISE && !train_only)      // (VETO_FAST runs VETO_MIXED's launches, with the correction stages of the fused ones skipped)
-      for (int i = 0; i < 4; ++i) {
-        const LayerLinear& q = kLayerLinears[i];
+      if (!mixed) h->stale[OP_LINEAR0 + 4 * l + i] &= ~STALE_INFER;      // (a VETO_PRECISE handle has no mixed rows)
+      else if (!train_only && l < infer_upto && take(OP_LINEAR0 + 4 * l + i, STALE_INFER)) {
         HIP_TRY(launch_mixed_weight_rows(h->p(lname(l, q.weight)), w.mixed_rows(i), q.N, q.K, w.exp_m + i, s));
+        ++h->built[VETO_BUILD_MIXED_ROWS];
       }
+    }
   }
-  if (base) {
   const std::string pe = std::string(kT) + "patch_embed.";
-  HIP_TRY(launch_build_patch_weight(h->p(pe + "proj_d.weight"), h->p(pe + "proj_d.bias"), h->p(pe + "proj_v.weight"),
-                                    h->p(pe + "proj_v.bias"), h->patch_w, h->patch_bias, h->cfg.patch, s));
-  HIP_TRY(launch_transpose_pair_proj(h->p("location_projection.0.weight"), h->loc_wt, kPosDim, s));
-  HIP_TRY(launch_transpose_pair_proj(h->p("class_projection.0.weight"), h->cls_wt, h->cfg.embed_dim, s));
-  HIP_TRY(launch_transpose_head(h->p("rel_out.weight"), h->head_wt, h->cfg.num_out, s));
+  if (take(OP_PATCH, STALE_TRAIN)) {
+    HIP_TRY(launch_build_patch_weight(h->p(pe + "proj_d.weight"), h->p(pe + "proj_d.bias"), h->p(pe + "proj_v.weight"),
+                                      h->p(pe + "proj_v.bias"), h->patch_w, h->patch_bias, h->cfg.patch, s));
+    ++h->built[VETO_BUILD_PATCH];
   }
-  if (train_only) {
-    h->dirty = false;
-    h->infer_dirty = true;
-    ++h->weight_gen;
-    return VETO_OK;
+  if (take(OP_LOC_T, STALE_TRAIN)) {
+    HIP_TRY(launch_transpose_pair_proj(h->p("location_projection.0.weight"), h->loc_wt, kPosDim, s));
+    ++h->built[VETO_BUILD_LOC_T];
   }
-  {   // layer 0: Wqkv diag(gamma) and the weight-only vectors of the per-object form (fold_tmp holds >= 1728 x 576 floats)
+  if (take(OP_CLS_T, STALE_TRAIN)) {
+    HIP_TRY(launch_transpose_pair_proj(h->p("class_projection.0.weight"), h->cls_wt, h->cfg.embed_dim, s));
+    ++h->built[VETO_BUILD_CLS_T];
+  }
+  if (take(OP_HEAD_T, STALE_TRAIN)) {
+    HIP_TRY(launch_transpose_head(h->p("rel_out.weight"), h->head_wt, h->cfg.num_out, s));
+    ++h->built[VETO_BUILD_HEAD_T];
+  }
+  if (!train_only && infer_upto >= 1 && take(OP_QKV0, STALE_INFER)) {
+    // layer 0: Wqkv diag(gamma) and the weight-only vectors of the per-object form (fold_tmp holds >= 1728 x 576 floats)
     const std::string T0 = kT;
     HIP_TRY(launch_qkv0_consts(h->p(lname(0, "0.fn.to_qkv.weight")), h->layers[0].ln1_w, h->layers[0].ln1_b, h->p(T0 + "pos_embedding"),
                                h->p(T0 + "cls_token"), h->fold_tmp, h->q0_vec, s));
     HIP_TRY(launch_split_rows(h->fold_tmp, h->q0_w, 3 * kDim, kDim, s));
+    ++h->built[VETO_BUILD_QKV0];
   }
-  if (h->cfg.heads <= cls_fold_max_heads()) {
+  if (h->cfg.heads > cls_fold_max_heads()) h->stale[OP_FOLD] = 0;      // (no folded last layer at this head count)
+  else if (!train_only && infer_upto >= L && take(OP_FOLD, STALE_INFER)) {
     // last layer: M_h = W_q,h^T W_k,h and N_h = W_o,h W_v,h (products over the head width, fp32), as GEMM weight operands
     const int H = h->cfg.heads, dh = kDim / H;
     const float* qkv = h->p(lname(L - 1, "0.fn.to_qkv.weight"));      // [1728, 576]: q rows, k rows, v rows
@@ -101,10 +144,14 @@ int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only) {
                               (long)H * kDim, kDim, kDim, dh, s));
     HIP_TRY(launch_split_rows(h->fold_tmp, h->fold_n, (size_t)kDim, H * kDim, s));
     }
+    ++h->built[VETO_BUILD_FOLD];
   }
-  if (base) ++h->weight_gen;      // (completing a training-side upload changes no operand a training workspace was computed with)
+  // an upload changes what a training workspace was computed with (a tensor read in place included); completing the inference side of
+  // an earlier upload does not
+  if (uploaded) ++h->weight_gen;
   h->dirty = false;
   h->infer_dirty = false;
+  for (uint8_t f : h->stale) h->infer_dirty = h->infer_dirty || (f & STALE_INFER);
   return VETO_OK;
 }
 
@@ -236,6 +283,8 @@ int veto_create(const veto_config_t* cfg, veto_handle_t* out) {
     q.offset = h->raw_floats;
     h->raw_floats += align_up(q.numel, 64);
   }
+  for (const Param& q : h->params) h->deps.push_back(operands_of(h, q.name));
+  for (int op = 0; op < OP_LINEAR0 + 4 * L; ++op) h->stale.push_back(builds_of(op));      // (nothing is built yet)
   hipError_t e = hipMalloc((void**)&h->raw, h->raw_floats * sizeof(float));
   if (e != hipSuccess) { delete h; return fail(VETO_ERR_HIP, "hipMalloc(raw weights): %s", hipGetErrorString(e)); }
 
@@ -290,9 +339,17 @@ int veto_load_weights(veto_handle_t h, const char* name, const float* src, size_
   HIP_TRY(hipMemcpyAsync(h->raw + q.offset, src, numel * sizeof(float), hipMemcpyDefault, (hipStream_t)stream));
   q.loaded = true;
   h->dirty = true;
+  for (int op : h->deps[it->second]) h->stale[op] = builds_of(op);
   h->train_plan.clear();
   h->train_gen.clear();   // (no workspace's saved activations match the weights any more; also bounds the map)
   return VETO_OK;
+}
+
+int veto_debug_last_finalize(veto_handle_t h, int32_t* counts, int32_t capacity) {
+  if (!h || !counts) return fail(VETO_ERR_INVALID, "null argument");
+  if (capacity < VETO_BUILD_KINDS) return fail(VETO_ERR_INVALID, "counts holds %d entries, need VETO_BUILD_KINDS = %d", capacity, (int)VETO_BUILD_KINDS);
+  for (int i = 0; i < VETO_BUILD_KINDS; ++i) counts[i] = h->built[i];
+  return VETO_BUILD_KINDS;
 }
 
 size_t veto_grad_floats(veto_handle_t h) { return h ? h->raw_floats : 0; }

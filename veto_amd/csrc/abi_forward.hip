@@ -21,8 +21,10 @@ struct Workspace {
   size_t total;
 };
 
-// Carves (or, with base == nullptr, just sizes) the workspace.
-Workspace carve(char* base, int n_obj, int n_pair, int chunk, int patch) {
+// Carves (or, with base == nullptr, just sizes) the workspace.  fold_heads: the head count the folded last layer's region is sized
+// for (veto_forward: the most the fold supports, whatever the handle's); cls_rows false: a forward that stops below the last layer
+// (frozen_forward) has neither that region nor the compact CLS-row buffers.
+Workspace carve(char* base, int n_obj, int n_pair, int chunk, int patch, int fold_heads = cls_fold_max_heads(), bool cls_rows = true) {
   Workspace w;
   Carver c{base};
   const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
@@ -38,19 +40,22 @@ Workspace carve(char* base, int n_obj, int n_pair, int chunk, int patch) {
   w.x = c.take<float>(mpad * kDim * 4);
   w.a = c.take<__bf16>(mpad * 2 * kDim * 2);
   {   // qkv of a chunk; in the last layer instead u [cpad, H*576] fp32 + abar [cpad, 2*H*576] split (folded CLS attention)
-    const size_t qkv_bytes = mpad * 3 * kDim * 4, fold_bytes = 2 * (align_up(cpad * (size_t)cls_fold_max_heads() * kDim * 4, 256));
+    const size_t qkv_bytes = mpad * 3 * kDim * 4, fold_bytes = cls_rows ? 2 * (align_up(cpad * (size_t)fold_heads * kDim * 4, 256)) : 0;
     w.big = c.take(qkv_bytes > fold_bytes ? qkv_bytes : fold_bytes);
   }
-  w.xc = c.take<float>(cpad * kDim * 4);
+  w.xc = c.take<float>(cls_rows ? cpad * kDim * 4 : 0);
   w.ptab_split = c.take<__bf16>(prow * 2 * 2 * kDim * 2);
   w.sw = c.take<float>(prow * 3 * kDim * 4);
   w.ow = c.take<float>(prow * 3 * kDim * 4);
   w.stats = c.take<float>(mpad * 2 * 4);
-  w.ac = c.take<__bf16>(cpad * 2 * kDim * 2);
-  w.hc = c.take<__bf16>(cpad * 4 * kDim * 2);
+  w.ac = c.take<__bf16>(cls_rows ? cpad * 2 * kDim * 2 : 0);
+  w.hc = c.take<__bf16>(cls_rows ? cpad * 4 * kDim * 2 : 0);
   w.total = c.off;
   return w;
 }
+
+// the head count a frozen region's workspace holds the folded last layer for: the handle's own (0: it has no folded form)
+int frozen_fold_heads(veto_handle_t h) { return h->cfg.heads <= cls_fold_max_heads() ? h->cfg.heads : 0; }
 
 // Which form every stage of the forward takes: resolved once per call from the handle and from whether the saturation audit runs.
 struct ForwardPlan {
@@ -410,9 +415,16 @@ struct Chunk {
   }
 };
 
+// The frozen region of a training step (frozen_forward): the forward covers layers < k; k < layers: it ends behind layer k - 1's tail
+// with the residual rows copied to handoff
+struct FrozenRegion {
+  int k;
+  float* handoff;
+};
+
 // sat != nullptr (veto_forward_saturation): device counters [layers][VETO_SAT_SITES][4]
 int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* workspace, size_t workspace_bytes, float* out_logits,
-                 const veto_debug_outputs_t* dbg, unsigned long long* sat) {
+                 const veto_debug_outputs_t* dbg, unsigned long long* sat, const FrozenRegion* fz = nullptr) {
   CHECK_STRUCT_AND(veto_inputs_t, in, h && out_logits);
   if (dbg) CHECK_STRUCT(veto_debug_outputs_t, dbg);
   if (in->n_obj <= 0 || in->n_pair <= 0 || in->n_img <= 0) return fail(VETO_ERR_INVALID, "empty batch (n_obj=%d n_pair=%d n_img=%d)", in->n_obj, in->n_pair, in->n_img);
@@ -423,12 +435,17 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
     return fail(VETO_ERR_INVALID, "batch too large");
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (h->dirty || h->infer_dirty) ABI_TRY(finalize_weights(h, s));
   const int n_obj = in->n_obj, n_pair = in->n_pair;
   const int chunk = n_pair < h->chunk ? n_pair : h->chunk;
-  ABI_TRY(check_workspace(workspace, workspace_bytes, carve(nullptr, n_obj, n_pair, chunk, h->cfg.patch).total, true));
-  const Workspace ws = carve((char*)workspace, n_obj, n_pair, chunk, h->cfg.patch);
+  const int stop = fz && fz->k < h->cfg.layers ? fz->k : 0;      // > 0: the forward ends behind the tail of layer stop - 1
+  if (fz && (fz->k < 1 || fz->k > h->cfg.layers || (stop && !fz->handoff))) return fail(VETO_ERR_INVALID, "internal: bad frozen region");
+  // (a frozen region: the step's own trainable layers have no use for their inference operands)
+  if (h->dirty || h->infer_dirty) ABI_TRY(finalize_weights(h, s, false, fz ? fz->k : -1));
+  const Workspace ws = fz ? carve((char*)workspace, n_obj, n_pair, chunk, h->cfg.patch, frozen_fold_heads(h), stop == 0)
+                          : carve((char*)workspace, n_obj, n_pair, chunk, h->cfg.patch);
+  ABI_TRY(check_workspace(workspace, workspace_bytes, ws.total, true));
   const ForwardPlan p = make_plan(h, sat != nullptr);
+  if (fz && p.x_f24) return fail(VETO_ERR_INVALID, "internal: the frozen region hands over fp32 residual rows (VETO_X_F24=1)");
 
   ABI_TRY(object_side(h, s, ws, p, in, dbg));
   // ---- pairs, in chunks that bound the workspace ----------------------------------------------
@@ -436,7 +453,7 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
     const int np = (n_pair - c0 < chunk) ? n_pair - c0 : chunk;
     Chunk c{h, s, ws, p, c0, np, np * kTokens, sat, ws.x};
     int rc = c.assemble_tokens(dbg ? dbg->tokens : nullptr);
-    for (int l = 0; l < p.L - 1 && !rc; ++l) {
+    for (int l = 0; l < (stop ? stop : p.L - 1) && !rc; ++l) {
       bool attn_in_big = false;      // this layer's attention output is in ws.big (fused QKV + attention launch)
       if (l == 0 && p.qkv0_tables) {
         if (!(rc = c.qkv0_from_tables())) rc = c.attention(0, false);
@@ -444,7 +461,12 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
         rc = c.qkv_attention(l, &attn_in_big);
       }
       if (!rc) rc = c.layer_tail(l, attn_in_big);
-      if (!rc) rc = c.layernorm_next(l);
+      if (!rc && l + 1 != stop) rc = c.layernorm_next(l);      // (the training forward of layer `stop` LayerNorms its input rows itself)
+    }
+    if (stop) {      // hand the chunk's residual rows to the training forward
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(fz->handoff + (size_t)c0 * kTokens * kDim, ws.x, (size_t)c.M * kDim * 4, hipMemcpyDeviceToDevice, s));
+      continue;
     }
     if (!rc) rc = p.fold_last ? c.last_layer_folded() : c.last_layer_plain();
     if (!rc) rc = c.cls_feed_forward();
@@ -455,6 +477,23 @@ int forward_impl(veto_handle_t h, void* stream, const veto_inputs_t* in, void* w
 }
 
 }  // namespace
+
+// ---- the frozen region of a training step (abi_internal.h) -----------------------------------------------------------------
+size_t frozen_forward_workspace_bytes(veto_handle_t h, int n_obj, int n_pair, int k) {
+  const int chunk = n_pair < h->chunk ? n_pair : h->chunk;
+  return carve(nullptr, n_obj, n_pair, chunk, h->cfg.patch, frozen_fold_heads(h), k >= h->cfg.layers).total;
+}
+
+int frozen_forward(veto_handle_t h, void* stream, const veto_inputs_t* in, void* workspace, size_t workspace_bytes, int k, float* handoff,
+                   float* out_logits, float* cls_rows) {
+  veto_inputs_t eval_in = *in;      // (an eval-mode pos_embed.0: the running statistics)
+  eval_in.bn_batch_stats = nullptr;
+  veto_debug_outputs_t dbg{};
+  dbg.struct_size = (int32_t)sizeof(dbg);
+  dbg.cls = cls_rows;
+  const FrozenRegion fz{k, handoff};
+  return forward_impl(h, stream, &eval_in, workspace, workspace_bytes, out_logits, &dbg, nullptr, &fz);
+}
 
 extern "C" {
 

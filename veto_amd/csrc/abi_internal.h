@@ -196,6 +196,12 @@ struct ProfRec {
   double flops, bytes;
 };
 
+// The derived operands finalize_weights builds, and the two builds an operand can have: the one the training path reads (a Linear's
+// split rows, the patch weight, the projection and head transposes) and the one only the inference forward reads (a Linear's mixed
+// rows, the layer-0 constants, the folded last layer's factors)
+enum operand_id { OP_PATCH, OP_LOC_T, OP_CLS_T, OP_HEAD_T, OP_QKV0, OP_FOLD, OP_LINEAR0 };      // OP_LINEAR0 + 4 l + i: Linear i of layer l
+enum { STALE_TRAIN = 1, STALE_INFER = 2 };
+
 struct veto_handle_s {
   veto_config_t cfg;
   int dh = 0;
@@ -206,7 +212,14 @@ struct veto_handle_s {
   size_t raw_floats = 0;     // ... and their end: the floats of the arena, and of a gradient buffer laid out like it
   char* derived = nullptr;   // split planes, transposes, folded tables
   bool dirty = true;         // a weight was uploaded since the derived operands were built
-  bool infer_dirty = false;  // ... the training-side operands are current, the inference-only ones (mixed rows, layer-0 tables, folded last layer) are not
+  bool infer_dirty = false;  // ... the training-side operands are current, an inference-only one (mixed rows, layer-0 tables, folded last layer) is not
+  // Per-tensor refresh.  deps[i]: the derived operands (operand_id) that read weight i -- THE dependency table, filled once by
+  // veto_create (abi_core.hip, operands_of); a tensor read in place has none.  stale[op]: which builds of the operand have not seen
+  // its tensors' last upload (STALE_TRAIN | STALE_INFER); everything is stale until the first finalize_weights.
+  // built[]: what the last finalize_weights launched, per veto_build_kind (veto_debug_last_finalize)
+  std::vector<std::vector<int>> deps;
+  std::vector<uint8_t> stale;
+  int32_t built[VETO_BUILD_KINDS] = {};
   // generation of the derived weight operands (bumped by every finalize_weights) and, per training workspace, the generation its
   // saved activations were computed with: veto_backward refuses a workspace whose forward saw other weights
   uint64_t weight_gen = 0;
@@ -308,8 +321,18 @@ struct ProfScope {
 // abi_core.hip.  train_only: just the operands the training path reads (split rows of the Linears, the patch / pair-projection / head
 // re-layouts).  A training loop uploads every weight after every optimizer step; the mixed rows (a max-|w| reduction per tensor), the
 // table form of layer 0 and the folded last layer are the inference path's, and are built when an inference forward next needs them
-// (infer_dirty).
-int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only = false);
+// (infer_dirty).  Only the operands that read a tensor uploaded since their last build are rebuilt (veto_handle_s::deps / stale).
+// infer_layers >= 0 (the frozen-fused training step): of the inference-only operands just those of layers < infer_layers, the layer-0
+// constants, and the folded last layer when infer_layers covers it -- the rest stays stale for an inference forward to build.
+int finalize_weights(veto_handle_t h, hipStream_t s, bool train_only = false, int infer_layers = -1);
+
+// abi_forward.hip: the inference forward as the frozen region of a training step (veto_train_plan_t.frozen_fused).  The prelude and
+// layers < k run through forward_impl's stages, chunk by chunk, in `workspace` (frozen_forward_workspace_bytes).  k < layers: the fp32
+// residual rows behind layer k - 1 go to handoff [n_pair * 19, 576] and nothing else is computed; k == layers: the whole forward, the
+// logits to out_logits and the CLS rows to cls_rows [n_pair, 576]
+size_t frozen_forward_workspace_bytes(veto_handle_t h, int n_obj, int n_pair, int k);
+int frozen_forward(veto_handle_t h, void* stream, const veto_inputs_t* in, void* workspace, size_t workspace_bytes, int k, float* handoff,
+                   float* out_logits, float* cls_rows);
 
 // A dropout site (kernels.h, DropSite) into the argument structs that go into a kernel by value and so keep fields of their own:
 // ObjPrepArgs / AssembleArgs (their rows are token or object rows: no row_step), and the transform of launch_prep_grad

@@ -39,6 +39,9 @@ struct TrainWs {
   __bf16* wcat_t;   // Wcat^T [patch_t_rows(p), 2*1152] split rows: weight operand of the patch projection's input gradient
   float* dpa;       // dPA [prow, patch_t_rows(p)] fp32: gradient w.r.t. the patch rows
   size_t mp2;    // padded reduction length of the weight-gradient GEMMs
+  // the frozen-fused step (Sched::fused) only: the workspace of the frozen region's inference forward (abi_forward.hip, frozen_forward)
+  char* infer;
+  size_t infer_bytes;
   // ordered mode (veto_train_opts_t.deterministic) only, behind everything else so that the default layout and size stay what they were:
   // the split-K partial planes of the weight-gradient GEMMs, [k_splits][N][K] fp32 of the largest call; nullptr = the default (atomic) path
   float* planes;
@@ -103,6 +106,9 @@ struct Sched {
   bool below = true;              // a stage under layer 0 has a consumer
   std::vector<uint8_t> need_in;   // per layer: the gradient w.r.t. the layer's input has a consumer
   int keep_from = 0;              // the lowest layer whose saved activations the backward reads (layers: none, the head reads xout only)
+  // veto_train_plan_t.frozen_fused: the prelude and layers < keep_from run as the inference forward in a workspace region of its own
+  // and keep nothing; layer keep_from's input rows are its hand-off (keep_from == layers: the CLS rows in xout)
+  bool fused = false;
   std::string key;                // the plan as bytes: what the forward stamps the workspace with
   bool want(veto_handle_t h, const std::string& name) const { return full || on[h->index.at(name)] != 0; }
   bool need(int l) const { return full || need_in[l] != 0; }
@@ -115,12 +121,14 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   const size_t M = (size_t)n_pair * kTokens;
   const size_t mpad = (size_t)gemm_rows_padded((int)M);
   const size_t prow = (size_t)gemm_rows_padded(n_obj * 16);
-  w.subj = c.take<int32_t>((size_t)n_pair * 4);
-  w.obj = c.take<int32_t>((size_t)n_pair * 4);
-  w.lc = c.take<float>((size_t)n_obj * 2 * 2 * kDim * 4);
+  // (the frozen-fused step: the prelude runs in the frozen region's own workspace, and nothing under layer keep_from is differentiated)
+  const auto prelude = [&](size_t bytes) { return sch.fused ? (size_t)0 : bytes; };
+  w.subj = c.take<int32_t>(prelude((size_t)n_pair * 4));
+  w.obj = c.take<int32_t>(prelude((size_t)n_pair * 4));
+  w.lc = c.take<float>(prelude((size_t)n_obj * 2 * 2 * kDim * 4));
   const int patch = h->cfg.patch;
-  w.pa = c.take<__bf16>(prow * 2 * patch_feats(patch) * 2);
-  w.patch_tab = c.take<float>((size_t)n_obj * 16 * 2 * kDim * 4);
+  w.pa = c.take<__bf16>(prelude(prow * 2 * patch_feats(patch) * 2));
+  w.patch_tab = c.take<float>(prelude((size_t)n_obj * 16 * 2 * kDim * 4));
   w.layers.resize(L);
   const size_t cpad = (size_t)gemm_rows_padded(n_pair);
   const bool recompute = train_recompute();
@@ -131,6 +139,10 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   const int shared = sch.keep_from < L - 1 ? sch.keep_from : L - 1;
   for (int l = 0; l < L; ++l) {
     TrainLayer& t = w.layers[l];
+    if (sch.fused && l < sch.keep_from) {      // a layer of the frozen region: no buffers here
+      t = TrainLayer{};
+      continue;
+    }
     if (l < shared && l >= 2) {
       t = w.layers[l - 2];
       continue;
@@ -183,6 +195,8 @@ TrainWs carve_train(char* base, veto_handle_t h, int n_obj, int n_pair, bool ord
   w.wcat_t = c.take<__bf16>((size_t)patch_t_rows(patch) * 2 * 2 * kDim * 2);
   w.dpa = c.take<float>((size_t)gemm_rows_padded(n_obj * 16) * patch_t_rows(patch) * 4);
   w.planes = ordered ? c.take<float>(wgrad_plane_floats(patch, (int)M, n_obj * 16) * 4) : nullptr;
+  w.infer_bytes = sch.fused ? frozen_forward_workspace_bytes(h, n_obj, n_pair, sch.keep_from) : 0;
+  w.infer = sch.fused ? c.take(w.infer_bytes) : nullptr;
   w.total = c.off;
   return w;
 }
@@ -244,12 +258,21 @@ int make_sched(veto_handle_t h, const veto_train_opts_t* opts, const veto_train_
     return fail(VETO_ERR_INVALID, "bn_eval with a trainable pos_embed.0.weight / bias needs a BatchNorm backward on fixed statistics, which is not built");
   const std::string T = kT;
   sch.below = sch.maps;
+  std::vector<std::string> prelude;      // the tensors under layer 0
   for (const char* name : {"pos_embed.0.weight", "pos_embed.0.bias", "pos_embed.1.weight", "pos_embed.1.bias", "obj_embed.weight",
                            "location_projection.0.weight", "location_projection.0.bias", "class_projection.0.weight", "class_projection.0.bias"})
-    sch.below = sch.below || sch.want(h, name);
+    prelude.push_back(name);
   for (const char* name : {"pos_embedding", "cls_token", "patch_embed.proj_d.weight", "patch_embed.proj_d.bias", "patch_embed.proj_v.weight",
                            "patch_embed.proj_v.bias"})
-    sch.below = sch.below || sch.want(h, T + name);
+    prelude.push_back(T + name);
+  for (const std::string& name : prelude) sch.below = sch.below || sch.want(h, name);
+  sch.fused = plan->frozen_fused != 0;
+  if (sch.fused) {      // what the frozen-fused step refuses, part 1 (include/veto_amd.h): what would make the chain reach under layer 0
+    for (const std::string& name : prelude)
+      if (sch.want(h, name)) return fail(VETO_ERR_INVALID, "frozen_fused: '%s' is trainable inside the frozen prelude", name.c_str());
+    if (sch.maps) return fail(VETO_ERR_INVALID, "frozen_fused: d_roi != 0 (the map gradients run through the frozen prelude)");
+    if (!sch.bn_eval) return fail(VETO_ERR_INVALID, "frozen_fused: bn_eval == 0 (the frozen prelude normalises with the running statistics of pos_embed.0)");
+  }
   sch.need_in.assign(L, 0);
   sch.keep_from = L;
   bool need = sch.below;
@@ -266,6 +289,20 @@ int make_sched(veto_handle_t h, const veto_train_opts_t* opts, const veto_train_
   sch.key.append((const char*)sch.p_attn.data(), sch.p_attn.size() * sizeof(float));
   sch.key.push_back(sch.bn_eval ? 'e' : 'b');
   sch.key.push_back(sch.maps ? 'm' : '-');
+  sch.key.push_back(sch.fused ? 'F' : '-');
+  if (sch.fused) {      // part 2: the frozen region is layers < k = keep_from (nothing under layer 0 has a consumer), the inference forward
+    const int k = sch.keep_from;
+    if (k == 0) return fail(VETO_ERR_INVALID, "frozen_fused: layer 0 has a trainable tensor (k = 0: there is no frozen layer to run fused)");
+    if (opts && opts->p_pos > 0.f) return fail(VETO_ERR_INVALID, "frozen_fused: p_pos = %g, the frozen prelude runs without dropout", opts->p_pos);
+    if (opts && opts->p_emb > 0.f) return fail(VETO_ERR_INVALID, "frozen_fused: p_emb = %g, the frozen prelude runs without dropout", opts->p_emb);
+    for (int l = 0; l < k; ++l) {
+      const float p = !sch.p_attn.empty() ? sch.p_attn[l] : opts ? opts->p_attn : 0.f;
+      if (p > 0.f) return fail(VETO_ERR_INVALID, "frozen_fused: attention dropout rate %g in frozen layer %d (p_attn_layer), the frozen layers run without dropout", p, l);
+    }
+    if (h->cfg.precision == VETO_FAST)
+      return fail(VETO_ERR_INVALID, "frozen_fused: a VETO_FAST handle (its logit error is above the 1e-3 bar of a training step's forward)");
+    if (env_knob_is("VETO_X_F24", "1")) return fail(VETO_ERR_INVALID, "frozen_fused: VETO_X_F24=1 (the hand-off takes fp32 residual rows)");
+  }
   *out = sch;
   return VETO_OK;
 }
@@ -332,6 +369,16 @@ struct TrainStep {
     ObjPrepArgs a = obj_prep_args(h, &in_bn, ws.lc);
     set_drop(a, drop_site(opts, 1));
     HIP_TRY(launch_obj_prep(a, s));
+    return VETO_OK;
+  }
+
+  // The frozen-fused step: the prelude and layers < k = sch.keep_from as the inference forward.  k == L: that is the whole forward, and
+  // it leaves the logits and the CLS rows (ws.xout); else layer k's input rows, and here their LayerNorm1 rows as the layer below
+  // would have left them
+  int frozen_region(float* out_logits) {
+    const int k = sch.keep_from;
+    ABI_TRY(frozen_forward(h, s, in, ws.infer, ws.infer_bytes, k, k < L ? ws.layers[k].xin : nullptr, out_logits, k < L ? nullptr : ws.xout));
+    if (k < L) HIP_TRY(launch_layernorm(ws.layers[k].xin, kDim, h->layers[k].ln1_w, h->layers[k].ln1_b, ws.layers[k].a1, M, s));
     return VETO_OK;
   }
 
@@ -739,16 +786,23 @@ static int forward_train_impl(veto_handle_t h, void* stream, const veto_inputs_t
   ABI_TRY(check_train_inputs(h, in, opts, workspace, workspace_bytes, sch));
   if (!out_logits) return fail(VETO_ERR_INVALID, "null out_logits");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  if (h->dirty) ABI_TRY(finalize_weights(h, (hipStream_t)stream, true));
+  // (the frozen region's forward refreshes the operands itself: the training side's and the inference side's of its own layers)
+  if (h->dirty && !sch.fused) ABI_TRY(finalize_weights(h, (hipStream_t)stream, true));
   h->train_gen.erase(workspace);     // (stamped at the end: a failed forward leaves no workspace that veto_backward would accept)
   h->train_plan.erase(workspace);
   TrainStep st(h, stream, in, opts, sch, workspace);
-  ABI_TRY(st.object_side());
-  ABI_TRY(st.patch_projection());
-  ABI_TRY(st.assemble_tokens());
-  for (int l = 0; l < st.L - 1; ++l) ABI_TRY(st.layer(l));
-  ABI_TRY(st.last_layer());
-  ABI_TRY(st.head(out_logits));
+  if (sch.fused) {
+    ABI_TRY(st.frozen_region(out_logits));
+  } else {
+    ABI_TRY(st.object_side());
+    ABI_TRY(st.patch_projection());
+    ABI_TRY(st.assemble_tokens());
+  }
+  if (!sch.fused || sch.keep_from < st.L) {
+    for (int l = sch.fused ? sch.keep_from : 0; l < st.L - 1; ++l) ABI_TRY(st.layer(l));
+    ABI_TRY(st.last_layer());
+    ABI_TRY(st.head(out_logits));
+  }
   h->stamp_train_workspace(workspace);
   if (!sch.full) h->train_plan[workspace] = sch.key;
   return VETO_OK;

@@ -242,7 +242,10 @@ class VetoTrainOpts(Structure):
 
 class VetoTrainPlan(Structure):
     _fields_ = [("struct_size", c_int32), ("bn_eval", c_int32), ("trainable", c_void_p), ("p_attn_layer", c_void_p),
-                ("d_roi", c_int32), ("reserved0", c_int32)]
+                ("d_roi", c_int32), ("frozen_fused", c_int32)]
+
+
+BUILD_KINDS = ("split_rows", "mixed_rows", "patch", "loc_t", "cls_t", "head_t", "qkv0", "fold")   # enum veto_build_kind
 
 
 class VetoMeetSampleArgs(Structure):
@@ -285,6 +288,7 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_num_weights": _sig(_P),
     "veto_weight_info": _sig(_P, _I, POINTER(c_char_p), POINTER(_Z)),
     "veto_load_weights": _sig(_P, c_char_p, _P, _Z, _P),
+    "veto_debug_last_finalize": _sig(_P, POINTER(_I), _I),
     "veto_workspace_bytes": _sig(_P, _I, _I, ret=_Z),
     "veto_forward": _sig(_P, _P, POINTER(VetoInputs), _P, _Z, _P, POINTER(VetoDebugOutputs)),
     "veto_forward_saturation": _sig(_P, _P, POINTER(VetoInputs), _P, _Z, _P, POINTER(VetoSaturation), _I),
@@ -537,6 +541,12 @@ class Engine:
 
     def load_weight(self, name, ptr, numel, stream=0):
         check(self.lib.veto_load_weights(self.handle, name.encode(), c_void_p(ptr), numel, c_void_p(stream)))
+
+    def last_finalize(self):
+        """veto_debug_last_finalize: {build kind: operands rebuilt} of the last rebuild of derived operands (BUILD_KINDS)."""
+        counts = (c_int32 * len(BUILD_KINDS))()
+        check(self.lib.veto_debug_last_finalize(self.handle, counts, len(BUILD_KINDS)))
+        return dict(zip(BUILD_KINDS, (int(c) for c in counts)))
 
     def workspace_bytes(self, n_obj, n_pair):
         return self.lib.veto_workspace_bytes(self.handle, n_obj, n_pair)

@@ -12,6 +12,7 @@ There is no PyTorch or CPU fallback; if the library is missing, or the inputs ar
 device, forward raises.
 """
 import ctypes
+import os
 import weakref
 import warnings
 
@@ -204,10 +205,16 @@ class _NativeForward:
         self._count_saturation = bool(getattr(getattr(config, "VETO_AMD", None), "COUNT_SATURATION", False))
         self._deterministic = bool(getattr(getattr(config, "VETO_AMD", None), "DETERMINISTIC", False))
         self.last_saturation = None
+        # VETO_AMD.FROZEN_FUSED: eligible training steps run their frozen region through the fused inference launches
+        # (frozen_fused_eligibility); what the last training step decided, and why: (bool, reason)
+        self._frozen_fused = bool(getattr(getattr(config, "VETO_AMD", None), "FROZEN_FUSED", False))
+        self.last_frozen_fused = (False, "no training step has run")
         object.__setattr__(self, "_trunk", trunk)  # not a sub-module registration
         self._engine = None
         self._engine_device = None
         self._uploaded = None
+        self._tensor_versions = {}      # per engine weight: the (data_ptr, _version) of its module tensors at their last upload
+        self._forced = set()            # refresh_weights(names): uploaded next time whatever their version
         self._workspace = None
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
@@ -225,16 +232,60 @@ class _NativeForward:
     def _weights_version(self):
         return tuple((p.data_ptr(), p._version) for p in list(self._trunk.parameters()) + list(self._trunk.buffers()))
 
-    def refresh_weights(self):
+    def refresh_weights(self, names=None):
         """Forces the next call to re-upload every weight (and rebuild the engine's derived operands: split / mixed rows,
         Wqkv diag(gamma), Mcat, Ncat).  Weight changes are detected through (data_ptr, Tensor._version), which writes
         through `.data` (`p.data.copy_()`, EMA updates, hand-written optimisers, some checkpoint loaders) do NOT bump:
-        call this after such a write in eval mode.  In training mode and after load_state_dict it happens by itself."""
+        call this after such a write in eval mode.  In training mode and after load_state_dict it happens by itself.
+
+        names: an optional list of state-dict names (the engine's: veto_weight_info; the heads are "rel_out.weight" /
+        "rel_out.bias") -- only these are known to have changed.  A frozen-fused training step (VETO_AMD.FROZEN_FUSED), which
+        uploads a tensor only when its (data_ptr, _version) changed since its last upload, then uploads just these besides,
+        and the engine rebuilds just the operands that read them; every other path re-uploads everything, as without names.
+        The caveat above holds there too: a frozen tensor written through `.data` between two frozen-fused steps is NOT seen;
+        name it here."""
         self._uploaded = None
+        if names is None:
+            self._tensor_versions = {}
+        else:
+            self._forced.update(names)
 
     invalidate = refresh_weights
 
-    def _ensure_engine(self, device):
+    def _module_tensors(self):
+        """{engine weight name: the module tensors it is made of, in row order} (rel_out.*: one per head)."""
+        keep = ("obj_embed.", "class_projection.0.", "pos_embed.", "location_projection.0.", "fusion_transformer.")
+        t = self._trunk
+        out = {k: (v,) for k, v in list(t.named_parameters()) + list(t.named_buffers())
+               if k.startswith(keep) and k != "pos_embed.0.num_batches_tracked"}
+        out["rel_out.weight"] = tuple(h.weight for h in self._head_modules)
+        out["rel_out.bias"] = tuple(h.bias for h in self._head_modules)
+        return out
+
+    def _upload_changed(self, device):
+        """The frozen-fused step's upload: the tensors whose (data_ptr, _version) changed since their last upload (the trainable
+        ones after an optimizer step; frozen ones normally never) and the ones refresh_weights(names) named."""
+        eng = self._engine
+        src = self._module_tensors()
+        stamp = {n: tuple((t.data_ptr(), t._version) for t in ts) for n, ts in src.items()}
+        stream = torch.cuda.current_stream(device)
+        keep = []
+        for name, numel in eng.weight_specs():
+            if self._tensor_versions.get(name) == stamp[name] and name not in self._forced:
+                continue
+            ts = src[name]
+            t = (ts[0] if len(ts) == 1 else torch.cat(ts, 0)).detach().to(device=device, dtype=torch.float32).contiguous()
+            if t.numel() != numel:
+                raise RuntimeError("veto_amd: weight %s has %d elements, expected %d" % (name, t.numel(), numel))
+            keep.append(t)
+            eng.load_weight(name, t.data_ptr(), numel, stream.cuda_stream)
+        if keep:
+            stream.synchronize()  # `keep` may be freed after this
+        self._tensor_versions = stamp
+        self._forced = set()
+        self._uploaded = self._weights_version()      # (everything the engine holds is current: an eval forward may trust it)
+
+    def _ensure_engine(self, device, per_tensor=False):
         if device.type != "cuda":
             raise RuntimeError("veto_amd: the predictor runs only on a HIP device (got %s); there is no CPU path" % device)
         idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -246,6 +297,10 @@ class _NativeForward:
                                          patch=self._patch, resolution=self._resolution)
             self._engine_device = idx
             self._uploaded = None
+            self._tensor_versions = {}
+        if per_tensor:
+            self._upload_changed(device)
+            return self._engine
         ver = self._weights_version()
         if self._trunk.training:
             self._uploaded = None      # a training step changes the weights: never trust the version stamp there
@@ -261,6 +316,7 @@ class _NativeForward:
                 self._engine.load_weight(name, t.data_ptr(), numel, stream)
             torch.cuda.current_stream(device).synchronize()  # `keep` may be freed after this
             self._uploaded = ver
+            self._tensor_versions, self._forced = {}, set()      # (no per-tensor stamps were taken: a frozen-fused step uploads all once)
         return self._engine
 
     @staticmethod
@@ -308,15 +364,16 @@ class _NativeForward:
             bn.num_batches_tracked += 1
         return out
 
-    def _prepare_inputs(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits, bn_batch_stats=None):
+    def _prepare_inputs(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits, bn_batch_stats=None,
+                        per_tensor=False):
         """Validates the call and flattens it into a veto_inputs_t.  Returns (call, inp, n_objs, n_pairs, eng); `call` keeps the
-        tensors the struct points into."""
+        tensors the struct points into.  per_tensor: a frozen-fused step's upload (_upload_changed)."""
         device = roi_features.device
         want = (256, self._resolution, self._resolution)
         if tuple(roi_features.shape[1:]) != want or tuple(roi_depth_features.shape[1:]) != want:
             raise ValueError("roi features must be [N, %d, %d, %d] (POOLER_RESOLUTION %d), got %s / %s"
                              % (want + (self._resolution, tuple(roi_features.shape), tuple(roi_depth_features.shape))))
-        eng = self._ensure_engine(device)
+        eng = self._ensure_engine(device, per_tensor)
         call = native.Launch(device, "veto_amd: the predictor runs only on a HIP device")
         n_objs = [len(p) for p in proposals]
         n_pairs = [int(p.shape[0]) for p in rel_pair_idxs]
@@ -379,10 +436,50 @@ class _NativeForward:
             row += head.out_features
         return spec
 
+    def frozen_fused_eligibility(self, want_maps=False):
+        """Does a training step of the module as it stands run its frozen region through the fused inference launches
+        (veto_train_plan_t.frozen_fused)?  A pure function of the module's state (no device, no engine; besides it only the
+        VETO_X_F24 knob of the environment is read): (eligible, reason, k),
+        k the lowest transformer layer with a trainable parameter (the layer count when only the heads are trainable).  The
+        frozen region is everything under layer k; it must compute what the inference forward computes: pos_embed[0] on its
+        running statistics, its dropout sites at rate 0, no gradient asked of anything inside it.  want_maps: a ROI map
+        requires grad."""
+        layers = self._layers
+        if not self._frozen_fused:
+            return False, "VETO_AMD.FROZEN_FUSED is off", layers
+        if self._precision == native.VETO_FAST:
+            return False, "VETO_AMD.PRECISION is fast (logit error above the 1e-3 bar)", layers
+        if os.environ.get("VETO_X_F24") == "1":      # (the library refuses the flag under this A/B knob: the hand-off takes fp32 rows)
+            return False, "VETO_X_F24=1 is set", layers
+        if want_maps:
+            return False, "a ROI map requires grad", layers
+        k, prefix = layers, "fusion_transformer.transformer.layers."
+        for prm, name, _, _ in self._train_param_spec():
+            if not prm.requires_grad or name.startswith("rel_out."):
+                continue
+            if not name.startswith(prefix):
+                return False, "the prelude parameter %s requires grad" % name, layers
+            k = min(k, int(name[len(prefix):].split(".", 1)[0]))
+        if k == 0:
+            return False, "layer 0 has a trainable parameter (k = 0)", 0
+        t = self._trunk
+        if t.pos_embed[0].training:
+            return False, "pos_embed[0] is in training mode (batch statistics)", k
+        for what, drop in (("pos_embed[3]", t.pos_embed[3]), ("pos_drop", t.fusion_transformer.transformer.pos_drop)):
+            if self._rate(drop) > 0:
+                return False, "the Dropout %s of the frozen region runs at p = %g" % (what, self._rate(drop)), k
+        for l, p in enumerate(self._attn_rates()[:k]):
+            if p > 0:
+                return False, "the attention Dropout of frozen layer %d runs at p = %g" % (l, p), k
+        return True, "frozen region: the prelude and layers 0..%d" % (k - 1), k
+
     def _train_plan(self, eng, spec, want_maps):
         """The veto_train_plan_t of this step, or None when every parameter is trainable, pos_embed[0] is in training mode and
         the layers share one attention dropout rate: the step then runs through the entry points without a plan, as it always
-        did.  Returns (plan, the ctypes arrays it points into)."""
+        did.  An eligible step (frozen_fused_eligibility) sets the plan's frozen_fused; the decision and its reason stay in
+        self.last_frozen_fused.  Returns (plan, the ctypes arrays it points into)."""
+        fused, reason, _ = self.frozen_fused_eligibility(want_maps)
+        self.last_frozen_fused = (fused, reason)
         flags = {}
         for prm, name, _, _ in spec:      # (the heads of a MEET list share rel_out.*: one trainable head sets the flag)
             flags[name] = flags.get(name, False) or bool(prm.requires_grad)
@@ -395,7 +492,7 @@ class _NativeForward:
         p_layer = (ctypes.c_float * len(rates))(*rates)
         plan = native.VetoTrainPlan(struct_size=ctypes.sizeof(native.VetoTrainPlan), bn_eval=int(bn_eval),
                                     trainable=ctypes.cast(trainable, ctypes.c_void_p), p_attn_layer=ctypes.cast(p_layer, ctypes.c_void_p),
-                                    d_roi=int(bool(want_maps)))
+                                    d_roi=int(bool(want_maps)), frozen_fused=int(fused))
         return plan, (trainable, p_layer)
 
     def _run_native_train_grad(self, proposals, rel_pair_idxs, roi_features, roi_depth_features, labels, logits=None):
@@ -426,11 +523,14 @@ class _TrainFn(torch.autograd.Function):
         bn = owner._trunk.pos_embed[0]
         # (an eval-mode BatchNorm normalises with its running statistics and leaves them alone: no batch statistics then)
         stats = torch.empty(12, dtype=torch.float32, device=device) if bn.training else None
+        want_maps = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        # (a frozen-fused step uploads only the tensors that changed: decided from the module's state, before the engine is touched)
         launch, inp, n_objs, n_pairs, eng = owner._prepare_inputs(proposals, rel_pair_idxs, roi_features, roi_depth_features,
-                                                                labels, obj_logits, stats)
+                                                                labels, obj_logits, stats,
+                                                                per_tensor=owner.frozen_fused_eligibility(want_maps)[0])
         opts = owner._train_opts()
         ctx.spec = owner._train_param_spec()
-        plan, ctx.plan_arrays = owner._train_plan(eng, ctx.spec, ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        plan, ctx.plan_arrays = owner._train_plan(eng, ctx.spec, want_maps)
         ctx.plan = plan
         plan_ref = ctypes.byref(plan) if plan is not None else None
         if plan is None:
