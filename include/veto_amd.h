@@ -19,6 +19,7 @@
  *   veto_nms               <- pysgg._C.nms / boxlist_nms            csrc/cuda/nms.cu, structures/boxlist_ops.py:10-32
  *   veto_box_postprocess   <- PostProcessor (box head)              roi_heads/box_head/inference.py:51-238
  *   veto_rpn_proposals     <- RPNPostProcessor                      rpn/inference.py:13-183
+ *   veto_anchor_grid       <- AnchorGenerator.forward (grid_anchors, add_visibility_to)   rpn/anchor_generator.py:73-125
  *   veto_box_match         <- FastRCNNSampling.assign_label_to_proposals / prepare_targets   roi_heads/box_head/sampling.py:34-82, 118-133
  *   veto_box_subsample     <- BalancedPositiveNegativeSampler + FastRCNNSampling.subsample    balanced_positive_negative_sampler.py:37-66
  *   veto_rpn_loss          <- RPNLossComputation (prepare_targets, __call__) and its backward   rpn/loss.py:21-157
@@ -510,6 +511,42 @@ typedef struct veto_rpn_args {
 /* reads the host fields of `args` only (n_img, n_lvl, pre_nms_top_n, level_a / level_h / level_w); 0 when they are out of range */
 size_t veto_rpn_proposals_workspace_bytes(const veto_rpn_args_t* args);
 int veto_rpn_proposals(void* stream, const veto_rpn_args_t* args, void* workspace, size_t workspace_bytes);
+
+/* veto_anchor_grid: AnchorGenerator.forward (rpn/anchor_generator.py:73-125) for n_lvl pyramid levels and n_img images, ONE launch
+ * whatever n_img and n_lvl are (the contract allows two), no workspace, nothing copied to the host and nothing synchronised.
+ *   anchors (grid_anchors, :73-95): every level in one buffer [sum_l A_l H_l W_l, 4] float32 xyxy, level l starting at row
+ *   sum_{j<l} A_j H_j W_j.  Row (h W + w) A + a of a level is cell_anchors[l][a] + (w stride, h stride, w stride, h stride): the
+ *   order of veto_rpn_proposals and veto_rpn_loss.  Bit-equal to the reference: its shifts are arange(0, W stride, stride) in
+ *   float32, integers below 2^24 and so exact, and each coordinate is one float32 addition of a cell anchor and a shift, which is
+ *   what the kernel computes (the product w stride is formed in int32 and converted, the sum is never contracted).  The cell
+ *   anchors (generate_anchors, :220-289, float64 numpy rounded to float32) are the caller's, computed on the host.
+ *   visibility (add_visibility_to, :97-110; optional): a byte plane [n_img, total]; byte (i, r) is
+ *   x1 >= -t && y1 >= -t && x2 < width_i + t && y2 < height_i + t of row r, evaluated in float32 on the float32 anchors as the
+ *   reference's tensor-scalar comparisons are (the sums width + t, height + t are formed in float32: exact for the integers a
+ *   configuration holds); t = straddle_thresh < 0: every byte is 1 (:107-109) and image_sizes is not read.
+ *   anchors == NULL with visibility given: the rows are read from anchors_in (a buffer an earlier call wrote) and only the
+ *   plane is written -- the call of a caller that caches the anchors per grid shape.
+ * Limits, checked on the host fields before anything is launched: n_lvl 1..VETO_RPN_MAX_LEVELS; A, H, W, stride >= 1;
+ * (W - 1) stride and (H - 1) stride below 2^24; at most 1 048 576 rows in all (what veto_rpn_loss accepts per image); anchors or
+ * visibility given; with visibility n_img 1..65535 and, for t >= 0, image_sizes; cell_anchors, anchors and anchors_in 16-byte
+ * aligned.  Left out: the cell anchors themselves (host), and BoxLists (veto_amd.rpn.AnchorGenerator wraps the buffers). */
+typedef struct veto_anchor_args {
+  int32_t struct_size;
+  int32_t n_img;                      /* rows of the visibility plane; not read when visibility is NULL */
+  int32_t n_lvl;
+  float straddle_thresh;              /* MODEL.RPN.STRADDLE_THRESH; < 0: every anchor is visible */
+  int32_t level_a[VETO_RPN_MAX_LEVELS];   /* HOST: anchors per location, height, width and stride of every level */
+  int32_t level_h[VETO_RPN_MAX_LEVELS];
+  int32_t level_w[VETO_RPN_MAX_LEVELS];
+  int32_t level_stride[VETO_RPN_MAX_LEVELS];
+  const float* cell_anchors[VETO_RPN_MAX_LEVELS];   /* device [A, 4] xyxy, 16-byte aligned; not read when anchors is NULL */
+  const float* image_sizes;           /* device [n_img, 2]: (width, height) */
+  float* anchors;                     /* out device [total, 4], 16-byte aligned; NULL: read anchors_in instead */
+  const float* anchors_in;            /* device [total, 4], 16-byte aligned; read only when anchors is NULL */
+  uint8_t* visibility;                /* optional out device [n_img, total] */
+} veto_anchor_args_t;
+
+int veto_anchor_grid(void* stream, const veto_anchor_args_t* args);
 
 /* veto_detect_relsample: RelationSampling.detect_relsample (sampling.py:109-176) with motif_rel_fg_bg_sampling (:179-309),
  * the training-time relation sampler on detected boxes, for a ragged batch (one workgroup per image).  Per image:

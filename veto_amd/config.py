@@ -44,6 +44,12 @@ def default_config():
     vt.NHEADS = 6
     vt.EMB_DROPOUT = 0.35
     vt.T_DROPOUT = 0.35
+    rpn = c.MODEL.RPN = CfgNode()                 # what veto_amd.rpn.make_anchor_generator reads, as VETO_final.yaml:17-21 sets it
+    rpn.USE_FPN = True
+    rpn.ANCHOR_SIZES = (32, 64, 128, 256, 512)
+    rpn.ANCHOR_STRIDE = (4, 8, 16, 32, 64)
+    rpn.ASPECT_RATIOS = (0.23232838, 0.63365731, 1.28478321, 3.15089189)
+    rpn.STRADDLE_THRESH = 0                       # defaults.py:161 (the yaml leaves it)
     c.MODEL.ROI_HEADS = CfgNode()
     c.MODEL.ROI_HEADS.FG_IOU_THRESHOLD = 0.5      # defaults.py:202
     c.MODEL.ROI_HEADS.BG_IOU_THRESHOLD = 0.3      # defaults.py:205

@@ -1,5 +1,5 @@
 // Detection-side entry points of the C ABI: pair enumeration / preparation, the relation post-processors, object decoding, NMS,
-// box-head and RPN post-processing, the relation samplers, the box head's proposal sampler, the RPN loss, the box head's loss, ROI pooling and
+// box-head and RPN post-processing, the RPN's anchor generator, the relation samplers, the box head's proposal sampler, the RPN loss, the box head's loss, ROI pooling and
 // the relation and detection evaluators.
 // Each checks its argument struct (the checks several of them make are in abi_internal.h), fills the launch struct and makes one
 // launch call (kernels.h).  An entry point with a workspace has ONE carve_*() that walks the layout and sets the launch struct's
@@ -336,6 +336,55 @@ int veto_rpn_proposals(void* stream, const veto_rpn_args_t* a, void* workspace, 
   carve_rpn(Carver{(char*)workspace}, a->n_img, a->n_lvl, capacity, &p);
   p.boxes = a->boxes; p.objectness = a->objectness_out; p.level = a->level; p.anchor_index = a->anchor_index; p.counts = a->counts;
   HIP_TRY(launch_rpn_proposals(p, (hipStream_t)stream));
+  return VETO_OK;
+}
+
+// the host fields of the anchor generator's arguments: rows of the concatenated levels, or a negative status (error set)
+static int anchor_check_shapes(const veto_anchor_args_t* a) {
+  if (a->n_lvl <= 0 || a->n_lvl > VETO_RPN_MAX_LEVELS) return fail(VETO_ERR_INVALID, "n_lvl %d outside 1..%d", a->n_lvl, VETO_RPN_MAX_LEVELS);
+  int64_t total = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    ABI_TRY(check_rpn_level(a, l));
+    if (a->level_stride[l] < 1) return fail(VETO_ERR_INVALID, "level %d: stride %d must be >= 1 (ANCHOR_STRIDE)", l, a->level_stride[l]);
+    const int64_t sx = (int64_t)(a->level_w[l] - 1) * a->level_stride[l], sy = (int64_t)(a->level_h[l] - 1) * a->level_stride[l];
+    if (sx >= (1 << 24) || sy >= (1 << 24))
+      return fail(VETO_ERR_INVALID, "level %d: the largest shift (%lld, %lld) must stay below 2^24 to be exact in float32", l, (long long)sx,
+                  (long long)sy);
+    total += (int64_t)a->level_a[l] * a->level_h[l] * a->level_w[l];
+    if (total > rpn_loss_max_anchors())
+      return fail(VETO_ERR_INVALID, "levels 0..%d: an image holds %lld anchors, the limit is %d", l, (long long)total, rpn_loss_max_anchors());
+  }
+  return (int)total;
+}
+
+int veto_anchor_grid(void* stream, const veto_anchor_args_t* a) {
+  CHECK_STRUCT(veto_anchor_args_t, a);
+  const int total = anchor_check_shapes(a);
+  if (total < 0) return total;
+  if (!a->anchors && !a->visibility) return fail(VETO_ERR_INVALID, "missing pointer: anchors and visibility are both NULL, nothing to write");
+  if (!a->anchors && !a->anchors_in) return fail(VETO_ERR_INVALID, "missing pointer: anchors_in (anchors is NULL, so the plane is computed from it)");
+  if ((((uintptr_t)a->anchors | (uintptr_t)a->anchors_in) & 15) != 0) return fail(VETO_ERR_INVALID, "anchors and anchors_in must be 16-byte aligned");
+  if (a->anchors)
+    for (int l = 0; l < a->n_lvl; ++l) {
+      if (!a->cell_anchors[l]) return fail(VETO_ERR_INVALID, "missing pointer: cell_anchors[%d]", l);
+      if (((uintptr_t)a->cell_anchors[l] & 15) != 0) return fail(VETO_ERR_INVALID, "cell_anchors[%d] must be 16-byte aligned", l);
+    }
+  if (a->visibility) {
+    if (a->n_img < 1 || a->n_img > 65535) return fail(VETO_ERR_INVALID, "n_img %d outside 1..65535 (visibility is asked for)", a->n_img);
+    if (a->straddle_thresh >= 0.f && !a->image_sizes) return fail(VETO_ERR_INVALID, "missing pointer: image_sizes (straddle_thresh >= 0)");
+    if (!(a->straddle_thresh == a->straddle_thresh)) return fail(VETO_ERR_INVALID, "straddle_thresh is NaN");
+  }
+  AnchorArgs p{};
+  int row0 = 0;
+  for (int l = 0; l < a->n_lvl; ++l) {
+    AnchorLevel& v = p.lvl[l];
+    v.cell = a->cell_anchors[l]; v.A = a->level_a[l]; v.W = a->level_w[l]; v.stride = a->level_stride[l]; v.row0 = row0;
+    row0 += a->level_a[l] * a->level_h[l] * a->level_w[l];
+  }
+  p.n_lvl = a->n_lvl; p.total = total;
+  p.anchors = a->anchors; p.anchors_in = a->anchors_in; p.image_sizes = a->image_sizes;
+  p.n_img = a->n_img; p.straddle = a->straddle_thresh; p.visibility = a->visibility;
+  HIP_TRY(launch_anchor_grid(p, (hipStream_t)stream));
   return VETO_OK;
 }
 

@@ -401,6 +401,24 @@ struct RpnArgs {
 int rpn_batch_cut_max_images();
 hipError_t launch_rpn_proposals(const RpnArgs& a, hipStream_t s);
 
+// ---- the RPN's anchor generator: the grid of every level and the per-image visibility plane (rpn.hip) ----------------
+struct AnchorLevel {
+  const float* cell;             // [A, 4] xyxy, 16-byte aligned
+  int A, W, stride;
+  int row0;                      // first row of the level in the concatenated buffer
+};
+struct AnchorArgs {
+  AnchorLevel lvl[kRpnMaxLevels];
+  int n_lvl, total;              // total = sum of A H W
+  float* anchors;                // out [total, 4], or null: the rows are read from anchors_in
+  const float* anchors_in;       // [total, 4]
+  const float* image_sizes;      // [n_img, 2] (width, height); not read when straddle < 0
+  int n_img;
+  float straddle;
+  uint8_t* visibility;           // out [n_img, total], or null
+};
+hipError_t launch_anchor_grid(const AnchorArgs& a, hipStream_t s);
+
 // ---- sgdet training: detected-box relation sampling (relsample.hip) ---------------------------------
 struct RelSampleArgs {
   const float* prp_boxes;        // [n_prp, 4] xyxy

@@ -18,6 +18,9 @@
 // One workgroup per segment for the select, not a split over workgroups: a batch already has n_img x n_lvl segments in flight
 // (60 for the VETO batch), the largest plane (91 200 logits, 356 KiB) stays in L2 across the five passes, and a split would need
 // a hand-off between workgroups (an agent-scope release / acquire per pass, or a launch per pass) that costs more than the pass.
+//
+// The anchors it reads come from anchor_grid_kernel (below; AnchorGenerator.forward, rpn/anchor_generator.py:73-125): the grid of
+// every level and the visibility plane of every image in one launch, one thread per anchor row.
 #include "common.h"
 #include "kernels.h"
 #include "selection.h"
@@ -281,9 +284,59 @@ __global__ __launch_bounds__(256) void rpn_emit_kernel(RpnArgs a) {
   if (tid == 0) a.counts[img] = fc;
 }
 
+// AnchorGenerator.forward (anchor_generator.py:73-125): one thread per anchor row of the concatenated levels.  kGenerate: row
+// (h W + w) A + a of a level is cell[a] + (w, h, w, h) * stride -- the shifts are integers below 2^24, exact in float32, so each
+// coordinate is the one float32 addition the reference makes -- stored with one 16-byte store; otherwise the row is read from
+// anchors_in.  Then, if asked for, the row's byte of every image's visibility plane (:100-106, in float32 like the reference's
+// comparisons; straddle < 0: 1).  blockIdx.y owns kAnchorImages images; every y derives the row itself, y = 0 stores it.
+// Store-bound: no LDS, nothing shared between threads.  With more than kAnchorImages images the generating instance derives a row
+// once per y slice (a few integer operations, one 16-byte load from a table of A rows and four additions) to keep the slices
+// independent; only the bytes of the plane are written more than once per row.
+constexpr int kAnchorImages = 16;
+
+template <bool kGenerate>
+__global__ __launch_bounds__(256) void anchor_grid_kernel(AnchorArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.total) return;
+  float4 p;
+  if (kGenerate) {
+    int l = 0;
+    while (l + 1 < a.n_lvl && i >= a.lvl[l + 1].row0) ++l;
+    const AnchorLevel& lv = a.lvl[l];
+    const int r = i - lv.row0, cellpos = r / lv.A, c = r - cellpos * lv.A;
+    const int h = cellpos / lv.W, w = cellpos - h * lv.W;
+    const float sx = (float)(w * lv.stride), sy = (float)(h * lv.stride);
+    const float4 q = ((const float4*)lv.cell)[c];
+    p = make_float4(q.x + sx, q.y + sy, q.z + sx, q.w + sy);
+    if (blockIdx.y == 0) ((float4*)a.anchors)[i] = p;
+  } else {
+    p = ((const float4*)a.anchors_in)[i];
+  }
+  if (!a.visibility) return;
+  const int img0 = blockIdx.y * kAnchorImages, img1 = min(a.n_img, img0 + kAnchorImages);
+  const float t = a.straddle;
+  for (int img = img0; img < img1; ++img) {
+    bool visible = true;
+    if (t >= 0.f) {
+      const float iw = a.image_sizes[2 * img], ih = a.image_sizes[2 * img + 1];
+      visible = p.x >= -t && p.y >= -t && p.z < iw + t && p.w < ih + t;
+    }
+    a.visibility[(size_t)img * a.total + i] = visible ? 1 : 0;
+  }
+}
+
 }  // namespace
 
 int rpn_batch_cut_max_images() { return kCutImages; }
+
+hipError_t launch_anchor_grid(const AnchorArgs& a, hipStream_t s) {
+  const dim3 grid((a.total + 255) / 256, a.visibility ? (a.n_img + kAnchorImages - 1) / kAnchorImages : 1);
+  if (a.anchors)
+    VETO_LAUNCH(anchor_grid_kernel<true>, grid, dim3(256), 0, s, a);
+  else
+    VETO_LAUNCH(anchor_grid_kernel<false>, grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_rpn_proposals(const RpnArgs& a, hipStream_t s) {
   const int n_seg = a.n_img * a.n_lvl;

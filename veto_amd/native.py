@@ -100,6 +100,13 @@ class VetoRpnArgs(Structure):
                                         "counts")]
 
 
+class VetoAnchorArgs(Structure):
+    _fields_ = [("struct_size", c_int32), ("n_img", c_int32), ("n_lvl", c_int32), ("straddle_thresh", ctypes.c_float)] + \
+               [(n, c_int32 * RPN_MAX_LEVELS) for n in ("level_a", "level_h", "level_w", "level_stride")] + \
+               [("cell_anchors", c_void_p * RPN_MAX_LEVELS)] + \
+               [(n, c_void_p) for n in ("image_sizes", "anchors", "anchors_in", "visibility")]
+
+
 class VetoDetectRelsampleArgs(Structure):
     _fields_ = [(n, c_int32) for n in ("struct_size", "n_img", "n_prp", "n_tgt", "n_rel_cells", "max_prp_per_image",
                                        "max_tgt_per_image", "require_overlap", "num_sample_per_gt_rel",
@@ -263,6 +270,7 @@ STRUCTS = {   # C typedef name in include/veto_amd.h -> its mirror (tests/test_a
     "veto_saturation_t": VetoSaturation, "veto_post_args_t": VetoPostArgs, "veto_post_meet_args_t": VetoPostMeetArgs,
     "veto_post_vote_args_t": VetoPostVoteArgs, "veto_post_groups_batch_args_t": VetoPostGroupsBatchArgs, "veto_obj_decode_args_t": VetoObjDecodeArgs, "veto_pair_args_t": VetoPairArgs,
     "veto_nms_args_t": VetoNmsArgs, "veto_box_post_args_t": VetoBoxPostArgs, "veto_rpn_args_t": VetoRpnArgs,
+    "veto_anchor_args_t": VetoAnchorArgs,
     "veto_detect_relsample_args_t": VetoDetectRelsampleArgs, "veto_gtbox_relsample_args_t": VetoGtboxRelsampleArgs,
     "veto_box_match_args_t": VetoBoxMatchArgs, "veto_box_subsample_args_t": VetoBoxSubsampleArgs,
     "veto_rpn_loss_args_t": VetoRpnLossArgs, "veto_box_loss_args_t": VetoBoxLossArgs,
@@ -327,6 +335,7 @@ SIGNATURES = {   # entry point -> (restype, argtypes): load_library() applies al
     "veto_box_postprocess_workspace_bytes": _sig(_I, _I, _I, ret=_Z),
     "veto_rpn_proposals": _sig(_P, POINTER(VetoRpnArgs), _P, _Z),
     "veto_rpn_proposals_workspace_bytes": _sig(POINTER(VetoRpnArgs), ret=_Z),
+    "veto_anchor_grid": _sig(_P, POINTER(VetoAnchorArgs)),
     "veto_rpn_loss": _sig(_P, POINTER(VetoRpnLossArgs), _P, _Z),
     "veto_rpn_loss_workspace_bytes": _sig(POINTER(VetoRpnLossArgs), ret=_Z),
     "veto_box_loss": _sig(_P, POINTER(VetoBoxLossArgs), _P, _Z),

@@ -125,6 +125,46 @@ def install_rpn_loss_ops():
     return patched
 
 
+_ANCHOR_ORIGINALS = []   # (module, name, what install_anchor_ops replaced), for uninstall_anchor_ops
+
+
+def install_anchor_ops():
+    """Point the reference's RPN at the device anchor generator: `pysgg.modeling.rpn.anchor_generator.make_anchor_generator`,
+    `make_anchor_generator_retinanet` and the class `AnchorGenerator` become veto_amd.rpn's (one launch per forward for the anchors
+    of every level and the visibility of every image, the anchors cached per grid shape).  Modules that bound one of them by name
+    when they were imported (`from .anchor_generator import make_anchor_generator`, rpn/rpn.py:9;
+    `make_anchor_generator_retinanet`, rpn/retinanet/retinanet.py:8) are re-pointed too.  `pysgg` must be importable.
+    Independent of the other installers.  Returns the patched (module, name) pairs; uninstall_anchor_ops() puts the originals
+    back."""
+    import importlib
+    import sys
+    import types
+    from . import rpn
+    patched = []
+    module = importlib.import_module("pysgg.modeling.rpn.anchor_generator")
+    for name in ("make_anchor_generator", "make_anchor_generator_retinanet", "AnchorGenerator"):
+        value, original = getattr(rpn, name), getattr(module, name)
+        if original is value:
+            continue
+        targets = [(module.__name__, module)] + sorted((n, m) for n, m in list(sys.modules.items())
+                                                       if isinstance(m, types.ModuleType) and m is not module and vars(m).get(name) is original)
+        for n, m in targets:
+            if vars(m).get(name) is original:
+                setattr(m, name, value)
+                _ANCHOR_ORIGINALS.append((m, name, original))
+                patched.append((n, name))
+    return patched
+
+
+def uninstall_anchor_ops():
+    """Undo install_anchor_ops: every name it replaced gets its original back.  Returns how many."""
+    n = len(_ANCHOR_ORIGINALS)
+    while _ANCHOR_ORIGINALS:
+        module, name, original = _ANCHOR_ORIGINALS.pop()
+        setattr(module, name, original)
+    return n
+
+
 def install_box_loss_ops():
     """Point the reference's box head at the device loss: `pysgg.modeling.roi_heads.box_head.loss.make_roi_box_loss_evaluator`
     returns veto_amd.boxloss.FastRCNNLossComputation (both losses and their gradients in one call).  `pysgg` must be importable.
